@@ -59,6 +59,47 @@ def make_batch(base, batch: int, phase: int = 0):
     return gray, depth, Tcw.astype(np.float32), Twc.astype(np.float32)
 
 
+DUMP_FRAMES = 256            # --dump-outputs: frames of the last timed batch written (a fixed seeded sample of larger batches)
+DUMP_BYTES = 64 * 10 ** 6    # --dump-outputs: ceiling of the files written, in all
+
+
+def dump_outputs(out_dir: str, fe, B: int, seed: int = 0):
+    """--dump-outputs: what the timed path handed back in its last step, read the way a caller of drfe_pipeline_submit reads it
+    from the context that ran the step (drfe_orb_download / drfe_match_download per frame): the keypoints, descriptors and
+    SearchByProjection(frame k, frame k-1) match array of every frame of the batch, or of a fixed seeded sample of DUMP_FRAMES
+    of them.  Valid rows only (rows past a frame's count are unspecified), concatenated in slot order; every value is exact:
+      slots.npy         float64 [F]       the batch slots written
+      kp_counts.npy     float64 [F]       keypoints of each of those frames
+      keypoints.npy     float32 [N, 7]    x, y, size, angle, response, octave, class_id
+      descriptors.npy   float32 [N, 32]   the rBRIEF descriptor's bytes
+      matches.npy       float32 [N]       index of the matched keypoint of slot - 1, -1 = none
+      match_counts.npy  float64 [F]       matches of each frame
+    -> {"frames", "keypoints", "bytes"}"""
+    if B > DUMP_FRAMES:
+        slots = np.sort(np.random.default_rng(seed).choice(B, DUMP_FRAMES, replace=False))
+    else:
+        slots = np.arange(B)
+    kps, descs, matches, n_kp, n_m = [], [], [], [], []
+    for s in slots:
+        k, d = fe.keypoints(int(s))
+        m, nm = fe.matches(int(s))
+        kps.append(np.stack([k[f].astype(np.float32) for f in k.dtype.names], axis=1).reshape(-1, 7))
+        descs.append(d.astype(np.float32))
+        matches.append(m[:len(k)].astype(np.float32))
+        n_kp.append(len(k))
+        n_m.append(nm)
+    arrays = {"slots": slots.astype(np.float64), "kp_counts": np.array(n_kp, np.float64),
+              "keypoints": np.concatenate(kps), "descriptors": np.concatenate(descs).reshape(-1, 32),
+              "matches": np.concatenate(matches), "match_counts": np.array(n_m, np.float64)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte ceiling" % (total, DUMP_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"frames": int(len(slots)), "keypoints": int(sum(n_kp)), "bytes": int(total)}
+
+
 def _native_oracle():
     """BASELINE.md section 2 asks for -O3 -march=native -ffp-contract=off: the checked-in oracle build is x86-64-v3 (it has to
     run in the build container too), so the timing leg compiles its own copy for THIS host into a scratch directory and
@@ -794,7 +835,13 @@ def main():
     ap.add_argument("--full-frontend", action="store_true",
                     help="at --gpus N > 1: after the headline, every rank also runs BASELINE config 3's whole front-end (ORB + LSD + AHC + CAPE + match) on "
                          "its own device and sequence; rank 0 reports total frames over the slowest rank's time.  Needs 3 host CPUs per rank")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0: keypoints, descriptors and matches of its "
+                         "batch, or of a fixed seeded sample of %d frames of it) as DIR/<name>.npy, float32 / float64, at most %d bytes "
+                         "in all; the same arguments give the same inputs, so two builds compare output for output" % (DUMP_FRAMES, DUMP_BYTES))
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch(args))
@@ -944,6 +991,10 @@ def main():
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
     el, total_frames = sharding.reduce_elapsed_and_frames(el, B * args.steps, dev, dist if world > 1 else None)
+    dumped = None
+    if args.dump_outputs and rank == 0:               # before anything else runs on the contexts: the last timed step's results
+        last = (next_ctx[0] - 1) % nfl
+        dumped = dict(dump_outputs(args.dump_outputs, fes[last], B), dir=args.dump_outputs, context=last)
 
     # sanity: the batch really produced keypoints and matches
     for f in fes:
@@ -1037,6 +1088,8 @@ def main():
         }
         if one_at_a_time:
             out["one_batch_at_a_time"] = one_at_a_time
+        if dumped:
+            out["dump_outputs"] = dumped
         if exchange:
             out["initial_exchange"] = exchange
         out["render"] = {"frames": len(base), "workers": workers, "seconds": round(t_render, 2)}
