@@ -642,6 +642,7 @@ int drfe_surface_normals(drfe_ctx* c, const float* depth_m, int w, int h, size_t
     HIPCHK(c, hipMemcpy2DAsync(b->d_depth, (size_t)w * 4, depth_m, stride * 4, (size_t)w * 4, h, hipMemcpyHostToDevice, c->stream));
     hipError_t e = drfe_launch_surface_normals(b->d_depth, 0, 1.0f, (size_t)w * h, w, w, h, K4, max_point_dist, 1, *b, c->stream);
     if (e != hipSuccess) { c->err = std::string("surface_normals: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
+    b->lastFrames = 1;
     if (out) HIPCHK(c, hipMemcpyAsync(out, b->d_recs, nrec * sizeof(drfe_surface_normal), hipMemcpyDeviceToHost, c->stream));
     if (cloud_tap) HIPCHK(c, hipMemcpyAsync(cloud_tap, b->d_cloud, W * H * 12, hipMemcpyDeviceToHost, c->stream));
     if (normals_tap) HIPCHK(c, hipMemcpyAsync(normals_tap, b->d_normals, W * H * 12, hipMemcpyDeviceToHost, c->stream));
@@ -662,6 +663,7 @@ int drfe_surface_normals_batch(drfe_ctx* c, const uint16_t* d_depth, size_t fram
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     hipError_t e = drfe_launch_surface_normals(d_depth, 1, depth_factor, frame_stride, row_stride, w, h, K4, max_point_dist, nframes, *b, s);
     if (e != hipSuccess) { c->err = std::string("surface_normals_batch: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
+    b->lastFrames = nframes;
     return DRFE_OK;
 }
 

@@ -16,11 +16,20 @@ struct SnBuffers {            /* device scratch of the surface-normal pass, [fra
     drfe_surface_normal* d_recs;   /* (W/2)*(H/2) */
     void* d_depth;            /* staging of the host-buffer entry point */
     size_t frames, w, h;      /* capacity */
+    int lastFrames;           /* frames of the most recent drfe_surface_normals_batch (drfe_manhattan_track_batch reads them) */
 };
 
 hipError_t drfe_launch_surface_normals(const void* d_depth, int isU16, float factor, size_t frameStride, size_t rowStride, int w,
                                        int h, const float K4[4], float maxDist, int nframes, const SnBuffers& b, hipStream_t s);
 void drfe_post_free(drfe_ctx* c);
+/* Manhattan-frame tracking of nseq sequences of seq_len frames (manhattan_kernels.hip; one workgroup per sequence): records
+ * of frame f at d_recs + f * nrec, lines of frame f at d_dirs[d_loff[f] .. d_loff[f + 1]).  d_cone / d_sums: per sequence
+ * `scratch` bytes / 3 x `scratch` doubles, scratch >= nrec + the largest line count of a frame. */
+hipError_t drfe_launch_manhattan(const drfe_surface_normal* d_recs, int nrec, const float* d_R0, int nseq, int seq_len,
+                                 const double* d_dirs, const int32_t* d_loff, int n_calls, uint8_t* d_cone, double* d_sums,
+                                 size_t scratch, float* d_R, drfe_manhattan_info* d_info, uint16_t* d_rbits, uint16_t* d_lbits,
+                                 hipStream_t s);
+void drfe_manhattan_free(drfe_ctx* c);
 #include <string>
 /* pcl::VoxelGrid for njobs point clouds at once (voxel_kernels.hip): job j = points [jobs[j].x, jobs[j].x + jobs[j].y) of d_pts
  * (xyz packed); d_list: njobs + 2 ints of scratch (the job order); scratch arrays span all points; centroids of job j to d_out at the job's offset, their number to d_counts[j]

@@ -41,6 +41,7 @@ SYMBOLS = (
     "drfe_lsd_search_by_sim3", "drfe_frame_submit", "drfe_frame_collect", "drfe_pipeline_create", "drfe_pipeline_destroy",
     "drfe_pipeline_depth", "drfe_pipeline_context", "drfe_pipeline_last_error", "drfe_pipeline_submit", "drfe_pipeline_sync",
     "drfe_lsd_configure", "drfe_lsd_configure_rect", "drfe_shard_unique_id", "drfe_shard_create", "drfe_shard_destroy", "drfe_shard_broadcast", "drfe_shard_reduce_report", "drfe_shard_sequences_of_rank", "drfe_shard_last_error", "drfe_planes_configure_cape", "drfe_planes_cape_stats", "drfe_lsd_configure_nfa", "drfe_lsd_stats", "drfe_lsd_segments_host_mode", "drfe_debug_cr_sincos", "drfe_debug_device_order_sort", "drfe_debug_device_order_sort_depth", "drfe_batch_status_async", "drfe_batch_check", "drfe_frame_submit_tracked", "drfe_frame_collect_tracked", "drfe_planes_cape_batch", "drfe_planes_configure", "drfe_planes_configure_extractor", "drfe_planes_ahc_stats", "drfe_planes_configure_refit", "drfe_planes_refit_stats", "drfe_frame_load", "drfe_bow_transform_slot", "drfe_long_kernel_clock", "drfe_long_kernel_ms",
+    "drfe_manhattan_track_host", "drfe_manhattan_track_batch", "drfe_manhattan_download", "drfe_debug_manhattan_math",
 )
 
 FRUSTUM_POINT_DTYPE = np.dtype([("world", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"),
@@ -64,6 +65,14 @@ CAPE_PLANE_DTYPE = np.dtype([("normal", "<f8", (3,)), ("mean", "<f8", (3,)), ("d
 PLANE_POST_DTYPE = np.dtype([("coef", "<f4", (4,)), ("accepted", "<i4"), ("n_voxels", "<i4")])      # drfe_plane_post, 24 B
 SURFACE_NORMAL_DTYPE = np.dtype([("normal", "<f4", (3,)), ("camera_position", "<f4", (3,)), ("frame_x", "<i4"),
                                  ("frame_y", "<i4")])                                               # drfe_surface_normal, 32 B
+
+MANHATTAN_CALL_DTYPE = np.dtype([("in_cone", "<i4", (3,)), ("n_selected", "<i4", (3,)), ("threshold", "<i4"),
+                                 ("deficient", "<i4"), ("found", "<i4"), ("svd", "<i4"), ("density", "<f4", (3,)),
+                                 ("pad", "<i4")])                                           # drfe_manhattan_call, 56 B
+MANHATTAN_MAX_CALLS = 5
+MANHATTAN_INLINE_BIT = 0x8000
+MANHATTAN_INFO_DTYPE = np.dtype([("n_calls", "<i4"), ("pad", "<i4"),
+                                 ("call", MANHATTAN_CALL_DTYPE, (MANHATTAN_MAX_CALLS,))])   # drfe_manhattan_info, 288 B
 
 PLANE_DTYPE = np.dtype([("normal", "<f8", (3,)), ("center", "<f8", (3,)), ("mse", "<f8"), ("curvature", "<f8"),
                         ("n_points", "<i4"), ("rid", "<i4")])
@@ -199,6 +208,10 @@ def load() -> C.CDLL:
     L.drfe_surface_normals.argtypes = [vp, vp, i32, i32, sz, vp, f32, vp, i32, C.POINTER(i32), vp, vp, vp]
     L.drfe_surface_normals_batch.argtypes = [vp, vp, sz, sz, i32, i32, vp, f32, f32, i32, vp]
     L.drfe_surface_normals_download.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
+    L.drfe_manhattan_track_host.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp, vp]
+    L.drfe_manhattan_track_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp]
+    L.drfe_manhattan_download.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.drfe_debug_manhattan_math.argtypes = [i32, vp, i32, vp]
     L.drfe_lsd_segments_host.argtypes = [vp, vp, vp, i32, i32, f64, vp, i32, C.POINTER(i32)]
     L.drfe_lsd_configure.argtypes = [vp, i32]
     L.drfe_lsd_configure_rect.argtypes = [vp, i32]
@@ -299,6 +312,34 @@ def plane_refit(coef4, xyz, dist_threshold):
     if rc != 0:
         raise DrfeError(f"drfe_plane_refit failed ({rc})")
     return bool(v.value), c
+
+
+def manhattan_track_host(R, recs, line_dirs=None, n_calls=3):
+    """Tracking::TrackManhattanFrame chained n_calls times on one frame's SurfaceNormal records (SURFACE_NORMAL_DTYPE) and
+    optional line directions (n x 3 float64).  Returns (R_out 3x3 float32, info (MANHATTAN_INFO_DTYPE), rec_bits uint16,
+    line_bits uint16)."""
+    L = load()
+    R = np.ascontiguousarray(R, np.float32).reshape(3, 3)
+    recs = np.ascontiguousarray(recs, SURFACE_NORMAL_DTYPE)
+    dirs = np.ascontiguousarray(np.zeros((0, 3)) if line_dirs is None else line_dirs, np.float64).reshape(-1, 3)
+    out = np.zeros((3, 3), np.float32)
+    info = np.zeros((), MANHATTAN_INFO_DTYPE)
+    rb = np.zeros(len(recs), np.uint16)
+    lb = np.zeros(len(dirs), np.uint16)
+    rc = L.drfe_manhattan_track_host(_p(R), _p(recs), len(recs), _p(dirs), len(dirs), n_calls, _p(out), _p(info), _p(rb), _p(lb))
+    if rc != 0:
+        raise DrfeError(f"drfe_manhattan_track_host failed ({rc})")
+    return out, info, rb, lb
+
+
+def manhattan_math(which, x):
+    """drfe_asin (0), drfe_exp (1), drfe_tanf (2) of include/drfe_math.h over float64 inputs (drfe_tanf: rounded to float32)"""
+    L = load()
+    x = np.ascontiguousarray(x, np.float64)
+    out = np.zeros_like(x)
+    if L.drfe_debug_manhattan_math(which, _p(x), len(x), _p(out)) != 0:
+        raise DrfeError("drfe_debug_manhattan_math failed")
+    return out
 
 
 def make_camera(fx, fy, cx, cy, bf, depth_map_factor, width, height) -> Camera:
@@ -1240,6 +1281,32 @@ class Context:
         self._chk(self.L.drfe_surface_normals_download(self.h, slot, _p(out), len(out), C.byref(n)),
                   "drfe_surface_normals_download")
         return out
+
+    def manhattan_track_batch(self, R0, nseq: int, seq_len: int, line_dirs=None, line_offsets=None, n_calls=3, stream: int = 0):
+        """Manhattan-frame tracking of nseq sequences of seq_len frames of the most recent surface_normals_batch_ptr (frame
+        s * seq_len + t = frame t of sequence s); R0: nseq x 3 x 3 starting rotations; line_dirs (n x 3 float64) with
+        line_offsets (nseq * seq_len + 1) or None."""
+        R0 = np.ascontiguousarray(R0, np.float32).reshape(nseq, 9)
+        if line_dirs is not None:
+            line_dirs = np.ascontiguousarray(line_dirs, np.float64).reshape(-1, 3)
+            line_offsets = np.ascontiguousarray(line_offsets, np.int32)
+            if len(line_offsets) != nseq * seq_len + 1 or line_offsets[-1] != len(line_dirs):
+                raise ValueError("line_offsets must have nseq * seq_len + 1 entries ending at len(line_dirs)")
+        self._frame_lines = None if line_offsets is None else line_offsets.copy()
+        self._chk(self.L.drfe_manhattan_track_batch(self.h, _p(R0), nseq, seq_len, _p(line_dirs), _p(line_offsets), n_calls,
+                                                    C.c_void_p(stream)), "drfe_manhattan_track_batch")
+
+    def manhattan_download(self, frame: int, n_records: int):
+        """(R 3x3 float32, info, rec_bits uint16[n_records], line_bits uint16) of one frame of the most recent batch"""
+        lo = getattr(self, "_frame_lines", None)
+        nl = 0 if lo is None else int(lo[frame + 1] - lo[frame])
+        R = np.zeros((3, 3), np.float32)
+        info = np.zeros((), MANHATTAN_INFO_DTYPE)
+        rb = np.zeros(n_records, np.uint16)
+        lb = np.zeros(nl, np.uint16)
+        self._chk(self.L.drfe_manhattan_download(self.h, frame, _p(R), _p(info), _p(rb), _p(lb) if nl else None),
+                  "drfe_manhattan_download")
+        return R, info, rb, lb
 
     # --- measurement -------------------------------------------------------------------------------
     def profile_enable(self, on=True):

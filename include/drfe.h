@@ -785,6 +785,49 @@ int drfe_surface_normals_batch(drfe_ctx* ctx, const uint16_t* d_depth, size_t fr
 /* Records of frame `slot` of the most recent drfe_surface_normals_batch (synchronises). */
 int drfe_surface_normals_download(drfe_ctx* ctx, int slot, drfe_surface_normal* out, int cap, int* n_out);
 
+/* Manhattan-frame tracking (Tracking::TrackManhattanFrame, src/Tracking.cc:1336-1527, with ProjectSN2Conic :1198-1266,
+ * ProjectSN2MF :1055-1196 and MeanShift :1529-1546).  One call refines R_cm (Manhattan frame -> camera, row-major 3x3 float)
+ * from a frame's SurfaceNormal records and optional line directions (FrameLine::direction, 3 doubles each); Tracking::Track
+ * chains three calls per frame (:328-332), each starting from the previous call's output.  Bit-exact with the reference's
+ * arithmetic (asin / exp / tanf canonicalised in drfe_math.h; the OpenCV pieces unpinned: DESIGN.md section 11).
+ *
+ * Side outputs rebuild what the reference leaves on the frame: rec_bits[i] (one per record) and line_bits[l] (one per line)
+ * have bit 3 * call + axis (axis 0..2 = x, y, z) set when ProjectSN2MF pushed the record / line to that axis's list
+ * (Frame::vSurfaceNormalx/y/z and vSurfacePointx/y/z; vVanishingLinex/y/z) in that call, NaN m_j included, and bit 15
+ * when it was inside a cone of the conic pass in any call (bsurfacenormal_inline).  The lists are call-major, then record
+ * order. */
+#define DRFE_MANHATTAN_MAX_CALLS 5
+#define DRFE_MANHATTAN_INLINE_BIT 0x8000
+typedef struct drfe_manhattan_call {
+    int32_t in_cone[3];     /* normals inside each axis's cone (conic pass, numInCone) */
+    int32_t n_selected[3];  /* m_j_selected.size() per axis (non-NaN m_j of normals and lines in the mean-shift cone) */
+    int32_t threshold;      /* minNumOfSN used: records / 20 (NaN records counted), or (smallest + middle) / 2 */
+    int32_t deficient;      /* 1 when the "normal vector deficiency" rule replaced the threshold */
+    int32_t found;          /* bit a: axis a's column was replaced (sum of the new column != 0) */
+    int32_t svd;            /* 1 when 2 or 3 axes were found and R = U * VT ran */
+    float density[3];       /* MeanShift density of each axis taken (n_selected > threshold), else 0 */
+    int32_t pad;
+} drfe_manhattan_call;      /* 56 B */
+typedef struct drfe_manhattan_info {
+    int32_t n_calls, pad;
+    drfe_manhattan_call call[DRFE_MANHATTAN_MAX_CALLS];
+} drfe_manhattan_info;      /* 288 B */
+
+/* Single frame on the host, no context: n_calls (1..DRFE_MANHATTAN_MAX_CALLS, the reference uses 3) chained calls from
+ * R_in to R_out.  line_dirs may be NULL when n_lines == 0; info, rec_bits (n) and line_bits (n_lines) may be NULL. */
+int drfe_manhattan_track_host(const float* R_in, const drfe_surface_normal* recs, int n, const double* line_dirs, int n_lines,
+                              int n_calls, float* R_out, drfe_manhattan_info* info, uint16_t* rec_bits, uint16_t* line_bits);
+/* The same for nseq * seq_len frames of the context's most recent drfe_surface_normals_batch, read in place on the device:
+ * frame s * seq_len + t is frame t of sequence s; frame 0 of sequence s starts from R0 + 9 * s (host), frame t > 0 from
+ * frame t - 1's result (mLastRcm).  line_dirs (host, 3 doubles per line) / line_offsets (host, nseq * seq_len + 1 entries)
+ * give each frame's lines, both NULL for none.  Asynchronous on `stream` (hipStream_t; NULL = the context stream). */
+int drfe_manhattan_track_batch(drfe_ctx* ctx, const float* R0, int nseq, int seq_len, const double* line_dirs,
+                               const int32_t* line_offsets, int n_calls, void* stream);
+/* Results of frame `frame` of the most recent drfe_manhattan_track_batch (synchronises): R (9 floats), info, rec_bits (the
+ * frame's record count) and line_bits (the frame's line count); any may be NULL. */
+int drfe_manhattan_download(drfe_ctx* ctx, int frame, float* R, drfe_manhattan_info* info, uint16_t* rec_bits,
+                            uint16_t* line_bits);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

@@ -8,6 +8,7 @@
  *   Planar_SLAM::PlaneDetection_CAPE   include/PlaneExtractor.h:84-115
  *   Planar_SLAM::ORBmatcher            include/ORBmatcher.h:41-84  - the reference's thirteen signatures (templates over Frame / KeyFrame / MapPoint)
  *   Planar_SLAM::LSDmatcher            include/LSDmatcher.h:21-36  - the reference's ten signatures (templates over Frame / KeyFrame / MapLine)
+ *   drfe::TrackManhattanFrame          src/Tracking.cc:1336          - Tracking's Manhattan-frame tracker (host entry)
  * With -DDRFE_WITH_OPENCV the container types are OpenCV's (cv::Mat, cv::KeyPoint, cv::line_descriptor::KeyLine);
  * without it (this image has no OpenCV) minimal stand-ins with the same member names and memory layout are used, so the
  * header is compiled and exercised here (tests/native/adaptor_caller.cpp, run by tests/test_gpu_native.py).
@@ -1438,5 +1439,104 @@ private:
     static drfe_ctx*& process_ctx() { static drfe_ctx* c = nullptr; return c; }
     static std::mutex& process_mutex() { static std::mutex m; return m; }
 };
+
+
+/* Tracking::TrackManhattanFrame (src/Tracking.cc:1336-1527) over drfe_manhattan_track_host: one call, as the reference makes it
+ * (Tracking::Track chains three, :328-332).  With -DDRFE_WITH_OPENCV, R is the reference's 3x3 CV_32F cv::Mat and SN / FL are the
+ * reference's SurfaceNormal / FrameLine (include/LSDextractor.h:34-41, 141-189); without it, the stand-ins below.  The overload
+ * with `frame` appends what ProjectSN2MF pushes onto the frame - vSurfaceNormalx/y/z (FramePosition), vSurfacePointx/y/z
+ * (cameraPosition), vVanishingLinex/y/z (the reference's four-point pair: two default points, then p, q) and
+ * vVaishingLinePCx/y/z (rndpts3d) - in its order, and sets inline[i] for the normals inside a cone (bsurfacenormal_inline). */
+namespace drfe {
+#ifdef DRFE_WITH_OPENCV
+using RotationMat = cv::Mat;
+inline void rotation_get(const cv::Mat& m, float R[9]) { for (int i = 0; i < 9; i++) R[i] = m.at<float>(i / 3, i % 3); }
+inline cv::Mat rotation_make(const float R[9]) { cv::Mat m(3, 3, CV_32F); for (int i = 0; i < 9; i++) m.at<float>(i / 3, i % 3) = R[i]; return m; }
+#else
+struct Point2i { int x, y; };
+struct Point2d { double x, y; };
+struct Point3f { float x, y, z; };
+struct Point3d { double x, y, z; };
+struct Mat33f { float v[9]; };             /* row-major 3x3 CV_32F */
+using RotationMat = Mat33f;
+inline void rotation_get(const Mat33f& m, float R[9]) { std::memcpy(R, m.v, sizeof(m.v)); }
+inline Mat33f rotation_make(const float R[9]) { Mat33f m; std::memcpy(m.v, R, sizeof(m.v)); return m; }
+struct SurfaceNormal { Point3f normal, cameraPosition; Point2i FramePosition; };
+struct RandomPoint3d { Point3d pos; };
+struct FrameLine { Point2d p, q; Point3d direction; std::vector<RandomPoint3d> rndpts3d; };
+/* the members of Frame that ProjectSN2MF fills (include/Frame.h) */
+struct ManhattanFrameOut {
+    std::vector<Point2i> vSurfaceNormalx, vSurfaceNormaly, vSurfaceNormalz;
+    std::vector<Point3f> vSurfacePointx, vSurfacePointy, vSurfacePointz;
+    std::vector<std::vector<Point2d>> vVanishingLinex, vVanishingLiney, vVanishingLinez;
+    std::vector<RandomPoint3d> vVaishingLinePCx, vVaishingLinePCy, vVaishingLinePCz;
+};
+#endif
+
+namespace detail {
+template <class SN, class FL>
+inline RotationMat track_manhattan(const RotationMat& Rin, const std::vector<SN>& sn, const std::vector<FL>& lines,
+                                   std::vector<uint16_t>* rb, std::vector<uint16_t>* lb)
+{
+    float R[9], Rout[9];
+    rotation_get(Rin, R);
+    std::vector<drfe_surface_normal> recs(sn.size());
+    for (size_t i = 0; i < sn.size(); i++) {
+        drfe_surface_normal& r = recs[i];
+        r.normal[0] = sn[i].normal.x; r.normal[1] = sn[i].normal.y; r.normal[2] = sn[i].normal.z;
+        r.camera_position[0] = sn[i].cameraPosition.x; r.camera_position[1] = sn[i].cameraPosition.y;
+        r.camera_position[2] = sn[i].cameraPosition.z;
+        r.frame_x = sn[i].FramePosition.x; r.frame_y = sn[i].FramePosition.y;
+    }
+    std::vector<double> dirs(3 * lines.size());
+    for (size_t l = 0; l < lines.size(); l++) {
+        dirs[3 * l] = lines[l].direction.x; dirs[3 * l + 1] = lines[l].direction.y; dirs[3 * l + 2] = lines[l].direction.z;
+    }
+    if (rb) rb->assign(sn.size(), 0);
+    if (lb) lb->assign(lines.size(), 0);
+    const int rc = drfe_manhattan_track_host(R, recs.data(), (int)recs.size(), dirs.data(), (int)lines.size(), 1, Rout, nullptr,
+                                             rb ? rb->data() : nullptr, lb ? lb->data() : nullptr);
+    if (rc != DRFE_OK) throw std::runtime_error("drfe_manhattan_track_host failed");
+    return rotation_make(Rout);
+}
+}  // namespace detail
+
+template <class SN, class FL>
+inline RotationMat TrackManhattanFrame(RotationMat& mLastRcm, std::vector<SN>& vSurfaceNormal, std::vector<FL>& vVanishingDirection)
+{
+    return detail::track_manhattan(mLastRcm, vSurfaceNormal, vVanishingDirection, nullptr, nullptr);
+}
+
+template <class SN, class FL, class Frame>
+inline RotationMat TrackManhattanFrame(RotationMat& mLastRcm, std::vector<SN>& vSurfaceNormal, std::vector<FL>& vVanishingDirection,
+                                       Frame& frame, std::vector<bool>& bsurfacenormal_inline)
+{
+    std::vector<uint16_t> rb, lb;
+    RotationMat R = detail::track_manhattan(mLastRcm, vSurfaceNormal, vVanishingDirection, &rb, &lb);
+    if (bsurfacenormal_inline.size() < vSurfaceNormal.size()) bsurfacenormal_inline.resize(vSurfaceNormal.size(), false);
+    for (size_t i = 0; i < rb.size(); i++)
+        if (rb[i] & DRFE_MANHATTAN_INLINE_BIT) bsurfacenormal_inline[i] = true;
+    for (int a = 0; a < 3; a++) {                     /* ProjectSN2MF runs axis by axis: x, then y, then z */
+        auto& pos = a == 0 ? frame.vSurfaceNormalx : a == 1 ? frame.vSurfaceNormaly : frame.vSurfaceNormalz;
+        auto& pts = a == 0 ? frame.vSurfacePointx : a == 1 ? frame.vSurfacePointy : frame.vSurfacePointz;
+        auto& vl = a == 0 ? frame.vVanishingLinex : a == 1 ? frame.vVanishingLiney : frame.vVanishingLinez;
+        auto& pc = a == 0 ? frame.vVaishingLinePCx : a == 1 ? frame.vVaishingLinePCy : frame.vVaishingLinePCz;
+        for (size_t i = 0; i < rb.size(); i++)
+            if (rb[i] & (1u << a)) {
+                pos.push_back(vSurfaceNormal[i].FramePosition);
+                pts.push_back(vSurfaceNormal[i].cameraPosition);
+            }
+        for (size_t l = 0; l < lb.size(); l++)
+            if (lb[l] & (1u << a)) {
+                typename std::decay<decltype(vl)>::type::value_type pair(2);   /* vector<Point2d> pointPair(2), then p, q pushed */
+                pair.push_back(vVanishingDirection[l].p);
+                pair.push_back(vVanishingDirection[l].q);
+                vl.push_back(pair);
+                for (const auto& p : vVanishingDirection[l].rndpts3d) pc.push_back(p);
+            }
+    }
+    return R;
+}
+}  // namespace drfe
 
 #endif /* DRFE_ADAPTOR_HPP */

@@ -36,6 +36,10 @@ int drfe_debug_ahc_trials(const double* sums9, const int32_t* N, int n, int mode
  * without a level-line angle never seed a region).  DRFE_ERR_STATE if this CPU lacks AVX2 (mode 2).  Host code. */
 int drfe_debug_order_sort(void* recs, size_t n, int kind, int mode, int depth_limit, uint32_t skip_below);
 
+/* Test hook of include/drfe_math.h's canonical libm of the Manhattan-frame tracker: out[i] = drfe_asin(x[i]) (which 0),
+ * drfe_exp(x[i]) (which 1) or drfe_tanf((float)x[i]) widened to double (which 2).  Host code. */
+int drfe_debug_manhattan_math(int which, const double* x, int n, double* out);
+
 #ifdef __cplusplus
 }
 #endif

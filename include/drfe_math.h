@@ -12,6 +12,9 @@
  *                            build canonicalises on this routine.
  *   drfe_logf             <- log(float) of MapPoint::PredictScale / MapLine::PredictScale (reference
  *                            src/MapPoint.cc:456, src/MapLine.cpp:389) — same libm caveat, same remedy.
+ *   drfe_asin, drfe_exp,  <- asin(double), exp(double) and tan(float) of the Manhattan-frame tracker
+ *   drfe_tanf                (reference src/Tracking.cc:1103, :1539, :1156) — same libm caveat, same remedy;
+ *                            within 1 ulp of glibc over the domains the tracker uses (tests/test_manhattan_cpu.py).
  */
 #ifndef DRFE_MATH_H
 #define DRFE_MATH_H
@@ -136,6 +139,73 @@ DRFE_HD int drfe_hamming256(const uint64_t* a, const uint64_t* b)
     return __builtin_popcountll(a[0] ^ b[0]) + __builtin_popcountll(a[1] ^ b[1]) +
            __builtin_popcountll(a[2] ^ b[2]) + __builtin_popcountll(a[3] ^ b[3]);
 #endif
+}
+
+/* The cone radii of Tracking::ProjectSN2Conic / ProjectSN2MF (src/Tracking.cc:1229, :1251, :1099): sin() of the
+ * doubles nearest 0.2018, 0.1018 and 0.2518, correctly rounded. */
+#define DRFE_MF_SIN_NORMAL_CONE 0x1.9a7caf08cdfccp-3   /* sin(0.2018): normals, conic pass */
+#define DRFE_MF_SIN_LINE_CONE 0x1.a040c2f653a3cp-4     /* sin(0.1018): line directions, conic pass */
+#define DRFE_MF_SIN_MS_CONE 0x1.fe4118cace77ep-3       /* sin(0.2518): mean-shift pass */
+
+/* asin of a double in [0, 0.25] (the tracker's lambda < sin 0.2518): the Maclaurin series x + x * (z * P(z)),
+ * z = x^2 <= 1/16, to the x^31 term (truncation < 1e-19 relative).  The correction term is below 1.1% of x, so the
+ * result is within ~0.51 ulp.  Outside that domain the result is not asin. */
+DRFE_HD double drfe_asin(double x)
+{
+    const double z = x * x;
+    double p = 0.004660143486915096;                  /* (2n)! / (4^n (n!)^2 (2n+1)), n = 15 .. 1 */
+    p = p * z + 0.005153309682319905; p = p * z + 0.005740037670841924; p = p * z + 0.006447210311889649;
+    p = p * z + 0.0073125258735988454; p = p * z + 0.008390335809616815; p = p * z + 0.009761609529194078;
+    p = p * z + 0.011551800896139705; p = p * z + 0.01396484375; p = p * z + 0.017352764423076924;
+    p = p * z + 0.022372159090909092; p = p * z + 0.030381944444444444; p = p * z + 0.044642857142857144;
+    p = p * z + 0.075; p = p * z + 0.16666666666666666;
+    return x + x * (z * p);
+}
+
+/* exp of a double in [-2, 0] (the mean-shift weight exp(-20 |m|^2)): x = k ln2 + r with a Cody-Waite split of ln2
+ * (k in [-3, 0], k * ln2_hi exact), |r| <= ln2 / 2, exp(r) = 1 + (r + r^2 * (1/2! + r * (1/3! + ...))) to r^18
+ * (truncation < 1e-21), times 2^k (exact).  NaN in, NaN out; outside [-2, 0] the result is not exp. */
+DRFE_HD double drfe_exp(double x)
+{
+    if (x != x) return x;
+    const double ln2_hi = 6.93147180369123816490e-01;    /* 32 significant bits */
+    const double ln2_lo = 1.90821492927058770002e-10;
+    const double kd = rint(x * 1.44269504088896338700);
+    double r = x - kd * ln2_hi;
+    r = r - kd * ln2_lo;
+    double p = 1.5619206968586225e-16;                  /* 1/18! .. 1/2! */
+    p = p * r + 2.8114572543455206e-15; p = p * r + 4.779477332387385e-14; p = p * r + 7.647163731819816e-13;
+    p = p * r + 1.1470745597729725e-11; p = p * r + 1.6059043836821613e-10; p = p * r + 2.08767569878681e-09;
+    p = p * r + 2.505210838544172e-08; p = p * r + 2.755731922398589e-07; p = p * r + 2.7557319223985893e-06;
+    p = p * r + 2.48015873015873e-05; p = p * r + 0.0001984126984126984; p = p * r + 0.001388888888888889;
+    p = p * r + 0.008333333333333333; p = p * r + 0.041666666666666664; p = p * r + 0.16666666666666666;
+    p = p * r + 0.5;
+    const double e = 1.0 + (r + (r * r) * p);
+    const int k = (int)kd;
+    uint64_t bits = (uint64_t)(1023 + k) << 52;          /* 2^k, k >= -1022 on this domain */
+    double scale;
+    memcpy(&scale, &bits, 8);
+    return e * scale;
+}
+
+/* tan of a float32 angle in [0, 0.27] (the tracker's alfa = |s_j| < 0.26), evaluated in float64 as sin / cos
+ * (Maclaurin series to x^17 / x^18, truncation < 1e-22) and rounded once to float32. */
+DRFE_HD float drfe_tanf(float xf)
+{
+    const double x = (double)xf, z = x * x;
+    double ps = 2.81145725434552076320e-15;               /*  1/17! .. -1/3! */
+    ps = ps * z + -7.64716373181981647590e-13; ps = ps * z + 1.60590438368216145994e-10;
+    ps = ps * z + -2.50521083854417187751e-08; ps = ps * z + 2.75573192239858906526e-06;
+    ps = ps * z + -1.98412698412698412698e-04; ps = ps * z + 8.33333333333333333333e-03;
+    ps = ps * z + -1.66666666666666666667e-01;
+    const double sn = x + x * (z * ps);
+    double pc = -1.56192069685862264622e-16;              /* -1/18! .. -1/2! */
+    pc = pc * z + 4.77947733238738529744e-14; pc = pc * z + -1.14707455977297247139e-11;
+    pc = pc * z + 2.08767569878680989792e-09; pc = pc * z + -2.75573192239858906526e-07;
+    pc = pc * z + 2.48015873015873015873e-05; pc = pc * z + -1.38888888888888888889e-03;
+    pc = pc * z + 4.16666666666666666667e-02; pc = pc * z + -5.00000000000000000000e-01;
+    const double cs = 1.0 + z * pc;
+    return (float)(sn / cs);
 }
 
 #endif /* DRFE_MATH_H */
