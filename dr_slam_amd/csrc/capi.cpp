@@ -153,6 +153,7 @@ void drfe_destroy(drfe_ctx* c)
     drfe_lines_free(c);
     drfe_cape_lanes_free(c);
     drfe_manhattan_free(c);
+    drfe_plane_match_free(c);
     drfe_post_free(c);
     drfe_one_shot_free(c);
     drfe_frame_lanes_free(c);

@@ -177,6 +177,7 @@ struct drfe_ctx {
     void* capeLanes;          /* std::vector<CapeLane>*: lanes of drfe_planes_cape_batch (planes_cape.cpp) */
     void* sn;                 /* SnBuffers*: surface-normal scratch (post_internal.h) */
     void* mf;                 /* MfBuffers*: drfe_manhattan_track_batch's buffers (manhattan.cpp) */
+    void* pm;                 /* PmBuffers*: drfe_plane_map_upload's maps and drfe_plane_match_batch's buffers (plane_match.cpp) */
     void* lineWorkers;        /* std::vector<LineWorker>*: lanes of drfe_lsd_extract_batch (lines_lsd.cpp) */
     struct LinesScratch* lsBatch; /* frame slots of drfe_lsd_extract_batch's device region growing (lines_lsd.cpp) */
     int lsdDeviceGrow;        /* drfe_lsd_configure: 1 = the batch entry grows regions on the device (default) */

@@ -30,6 +30,33 @@ hipError_t drfe_launch_manhattan(const drfe_surface_normal* d_recs, int nrec, co
                                  size_t scratch, float* d_R, drfe_manhattan_info* d_info, uint16_t* d_rbits, uint16_t* d_lbits,
                                  hipStream_t s);
 void drfe_manhattan_free(drfe_ctx* c);
+/* Plane association of a batch of frames against device-resident maps (plane_match_kernels.hip, driven by plane_match.cpp).
+ * Frame plane q (of Q) belongs to frame qFrame[q] and map qMap[q]; its pairs with the map's planes are angle / key
+ * [qPair[q], qPair[q] + planes of the map).  Map s owns planes [planeOff[s], planeOff[s + 1]) and points
+ * [pointOff[s], pointOff[s + 1]).  Expects key memset to 0xFF, counter / nmatches / npairs to 0 and (flagPoints) flags to 0. */
+#define PM_CHUNK 2048             /* cloud points per work item of the distance pass (256 lanes x 8) */
+#define PM_FLAG_POINTS 2048       /* map points per workgroup of the flag sweep */
+struct PmLaunch {
+    const float *Tcw, *coefs;
+    const int32_t *qFrame, *qMap, *qPair, *planeOff, *pointOff;
+    int32_t *mapOut, *parOut, *verOut;
+    const float* mapCoefs;
+    const uint8_t* mapBad;
+    const int32_t* cloudOff;
+    const float *cloud, *points;
+    float* angle;
+    uint32_t* key;
+    int4* work;
+    int workCap;
+    uint32_t* counter;
+    int32_t *nmatches, *npairs;
+    uint8_t* flags;
+    int Q, maxPts;
+    drfe_plane_match_params params;
+    bool flagPoints;
+};
+hipError_t drfe_launch_plane_match(const PmLaunch& L, hipStream_t s);
+void drfe_plane_match_free(drfe_ctx* c);
 #include <string>
 /* pcl::VoxelGrid for njobs point clouds at once (voxel_kernels.hip): job j = points [jobs[j].x, jobs[j].x + jobs[j].y) of d_pts
  * (xyz packed); d_list: njobs + 2 ints of scratch (the job order); scratch arrays span all points; centroids of job j to d_out at the job's offset, their number to d_counts[j]

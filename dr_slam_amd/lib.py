@@ -42,6 +42,8 @@ SYMBOLS = (
     "drfe_pipeline_depth", "drfe_pipeline_context", "drfe_pipeline_last_error", "drfe_pipeline_submit", "drfe_pipeline_sync",
     "drfe_lsd_configure", "drfe_lsd_configure_rect", "drfe_shard_unique_id", "drfe_shard_create", "drfe_shard_destroy", "drfe_shard_broadcast", "drfe_shard_reduce_report", "drfe_shard_sequences_of_rank", "drfe_shard_last_error", "drfe_planes_configure_cape", "drfe_planes_cape_stats", "drfe_lsd_configure_nfa", "drfe_lsd_stats", "drfe_lsd_segments_host_mode", "drfe_debug_cr_sincos", "drfe_debug_device_order_sort", "drfe_debug_device_order_sort_depth", "drfe_batch_status_async", "drfe_batch_check", "drfe_frame_submit_tracked", "drfe_frame_collect_tracked", "drfe_planes_cape_batch", "drfe_planes_configure", "drfe_planes_configure_extractor", "drfe_planes_ahc_stats", "drfe_planes_configure_refit", "drfe_planes_refit_stats", "drfe_frame_load", "drfe_bow_transform_slot", "drfe_long_kernel_clock", "drfe_long_kernel_ms",
     "drfe_manhattan_track_host", "drfe_manhattan_track_batch", "drfe_manhattan_download", "drfe_debug_manhattan_math",
+    "drfe_plane_match_host", "drfe_plane_flag_points_host", "drfe_plane_match_status_host", "drfe_plane_map_upload",
+    "drfe_plane_match_batch", "drfe_plane_match_download", "drfe_plane_flags_download",
 )
 
 FRUSTUM_POINT_DTYPE = np.dtype([("world", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"),
@@ -73,6 +75,9 @@ MANHATTAN_MAX_CALLS = 5
 MANHATTAN_INLINE_BIT = 0x8000
 MANHATTAN_INFO_DTYPE = np.dtype([("n_calls", "<i4"), ("pad", "<i4"),
                                  ("call", MANHATTAN_CALL_DTYPE, (MANHATTAN_MAX_CALLS,))])   # drfe_manhattan_info, 288 B
+
+# drfe_plane_match_params (dTh, aTh, verTh, parTh): PlaneMatcher's constructor defaults, as the float arguments receive them
+PLANE_MATCH_DEFAULTS = np.array([0.1, 0.86, 0.08716, 0.9962], np.float32)
 
 PLANE_DTYPE = np.dtype([("normal", "<f8", (3,)), ("center", "<f8", (3,)), ("mse", "<f8"), ("curvature", "<f8"),
                         ("n_points", "<i4"), ("rid", "<i4")])
@@ -212,6 +217,13 @@ def load() -> C.CDLL:
     L.drfe_manhattan_track_batch.argtypes = [vp, vp, i32, i32, vp, vp, i32, vp]
     L.drfe_manhattan_download.argtypes = [vp, i32, vp, vp, vp, vp]
     L.drfe_debug_manhattan_math.argtypes = [i32, vp, i32, vp]
+    L.drfe_plane_match_host.argtypes = [vp, vp, vp, i32, vp, vp, vp, vp, i32, vp, vp, vp, C.POINTER(i32)]
+    L.drfe_plane_flag_points_host.argtypes = [vp, vp, i32, vp, vp, i32, vp, C.POINTER(i32)]
+    L.drfe_plane_match_status_host.argtypes = [vp, vp, vp, i32, vp, vp, i32, vp, C.POINTER(i32)]
+    L.drfe_plane_map_upload.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.drfe_plane_match_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
+    L.drfe_plane_match_download.argtypes = [vp, i32, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.drfe_plane_flags_download.argtypes = [vp, i32, vp]
     L.drfe_lsd_segments_host.argtypes = [vp, vp, vp, i32, i32, f64, vp, i32, C.POINTER(i32)]
     L.drfe_lsd_configure.argtypes = [vp, i32]
     L.drfe_lsd_configure_rect.argtypes = [vp, i32]
@@ -330,6 +342,77 @@ def manhattan_track_host(R, recs, line_dirs=None, n_calls=3):
     if rc != 0:
         raise DrfeError(f"drfe_manhattan_track_host failed ({rc})")
     return out, info, rb, lb
+
+
+def _plane_params(params):
+    return np.ascontiguousarray(PLANE_MATCH_DEFAULTS if params is None else params, np.float32).reshape(4)
+
+
+def _clouds_csr(clouds):
+    """list of [n, 3] clouds -> (offsets int32[len + 1], xyz float32[total, 3])"""
+    off = np.zeros(len(clouds) + 1, np.int32)
+    off[1:] = np.cumsum([len(c) for c in clouds]) if len(clouds) else []
+    xyz = np.concatenate([np.asarray(c, np.float32).reshape(-1, 3) for c in clouds]) if len(clouds) else np.zeros((0, 3), np.float32)
+    return off, np.ascontiguousarray(xyz, np.float32)
+
+
+def _priors(p, n):
+    return np.full(n, -1, np.int32) if p is None else np.array(p, np.int32).reshape(n)
+
+
+def plane_match_host(Tcw, coefs, map_coefs, map_bad, clouds, map_idx=None, par_idx=None, ver_idx=None, params=None):
+    """PlaneMatcher::SearchMapByCoefficients on one frame (host entry): Tcw 4x4, coefs [P, 4] camera-frame planes, map planes
+    map_coefs [M, 4] (world), map_bad [M], clouds (list of M [n, 3] arrays); the three prior index arrays (None = all -1).
+    Returns (map_idx, par_idx, ver_idx, nmatches)."""
+    L = load()
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+    cf = np.ascontiguousarray(coefs, np.float32).reshape(-1, 4)
+    mc = np.ascontiguousarray(map_coefs, np.float32).reshape(-1, 4)
+    bad = np.ascontiguousarray(map_bad, np.uint8).reshape(len(mc))
+    off, xyz = _clouds_csr(clouds)
+    assert len(off) == len(mc) + 1
+    P = len(cf)
+    mi, pi, vi = _priors(map_idx, P), _priors(par_idx, P), _priors(ver_idx, P)
+    n = C.c_int()
+    prm = _plane_params(params)
+    rc = L.drfe_plane_match_host(_p(prm), _p(T), _p(cf), P, _p(mc), _p(bad), _p(off), _p(xyz), len(mc), _p(mi), _p(pi), _p(vi),
+                                 C.byref(n))
+    if rc != 0:
+        raise DrfeError(f"drfe_plane_match_host failed ({rc})")
+    return mi, pi, vi, n.value
+
+
+def plane_flag_points_host(Tcw, coefs, map_idx, points, flags=None):
+    """Map::FlagMatchedPlanePoints on one frame (host entry): flags (uint8 per map point, OR-ed into `flags` when given) and
+    the (plane, point) pair count."""
+    L = load()
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+    cf = np.ascontiguousarray(coefs, np.float32).reshape(-1, 4)
+    mi = np.ascontiguousarray(map_idx, np.int32).reshape(len(cf))
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+    fl = np.zeros(len(pts), np.uint8) if flags is None else np.array(flags, np.uint8).reshape(len(pts))
+    n = C.c_int()
+    rc = L.drfe_plane_flag_points_host(_p(T), _p(cf), len(cf), _p(mi), _p(pts), len(pts), _p(fl), C.byref(n))
+    if rc != 0:
+        raise DrfeError(f"drfe_plane_flag_points_host failed ({rc})")
+    return fl, n.value
+
+
+def plane_match_status_host(Tcw, coefs, matched_coefs, matched, mf_contrast, Rwc_MF=None, params=None):
+    """PlaneMatcher::bMatchStatus on one frame (host entry): matched_coefs [P, 4] world coefficients of mvpMapPlanes[i],
+    matched [P] (0 = null or bad).  Returns the bool result."""
+    L = load()
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+    cf = np.ascontiguousarray(coefs, np.float32).reshape(-1, 4)
+    mc = np.ascontiguousarray(matched_coefs, np.float32).reshape(len(cf), 4)
+    m = np.ascontiguousarray(matched, np.uint8).reshape(len(cf))
+    R = None if Rwc_MF is None else np.ascontiguousarray(Rwc_MF, np.float32).reshape(9)
+    st = C.c_int()
+    prm = _plane_params(params)
+    rc = L.drfe_plane_match_status_host(_p(prm), _p(T), _p(cf), len(cf), _p(mc), _p(m), int(bool(mf_contrast)), _p(R), C.byref(st))
+    if rc != 0:
+        raise DrfeError(f"drfe_plane_match_status_host failed ({rc})")
+    return bool(st.value)
 
 
 def manhattan_math(which, x):
@@ -1307,6 +1390,53 @@ class Context:
         self._chk(self.L.drfe_manhattan_download(self.h, frame, _p(R), _p(info), _p(rb), _p(lb) if nl else None),
                   "drfe_manhattan_download")
         return R, info, rb, lb
+
+    # --- plane association (PlaneMatcher / Map::FlagMatchedPlanePoints) over device-resident maps --------
+    def plane_map_upload(self, maps):
+        """maps: list of dict(coefs [M, 4] world, bad [M], clouds (list of M [n, 3]), points [N, 3]) -> drfe_plane_map_upload"""
+        poff = np.zeros(len(maps) + 1, np.int32)
+        poff[1:] = np.cumsum([len(m["coefs"]) for m in maps])
+        qoff = np.zeros(len(maps) + 1, np.int32)
+        qoff[1:] = np.cumsum([len(m["points"]) for m in maps])
+        coefs = np.ascontiguousarray(np.concatenate([np.asarray(m["coefs"], np.float32).reshape(-1, 4) for m in maps]), np.float32)
+        bad = np.ascontiguousarray(np.concatenate([np.asarray(m["bad"], np.uint8).reshape(-1) for m in maps]), np.uint8)
+        coff, cloud = _clouds_csr([c for m in maps for c in m["clouds"]])
+        pts = np.ascontiguousarray(np.concatenate([np.asarray(m["points"], np.float32).reshape(-1, 3) for m in maps]), np.float32)
+        self._plane_points = [len(m["points"]) for m in maps]
+        self._chk(self.L.drfe_plane_map_upload(self.h, len(maps), _p(poff), _p(coefs), _p(bad), _p(coff), _p(cloud), _p(qoff),
+                                               _p(pts)), "drfe_plane_map_upload")
+
+    def plane_match_batch(self, frame_map, Tcw, coefs, map_idx=None, par_idx=None, ver_idx=None, flag_points=True, params=None,
+                          stream: int = 0):
+        """frame f (Tcw [F, 4, 4], coefs[f] [P_f, 4]) against uploaded map frame_map[f]; priors: per-frame lists of index
+        arrays or None"""
+        F = len(frame_map)
+        fm = np.ascontiguousarray(frame_map, np.int32)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(F, 16)
+        off = np.zeros(F + 1, np.int32)
+        off[1:] = np.cumsum([len(np.asarray(c).reshape(-1, 4)) for c in coefs])
+        cf = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).reshape(-1, 4) for c in coefs]), np.float32)
+        pri = [None if p is None else np.ascontiguousarray(np.concatenate([_priors(p[f], off[f + 1] - off[f]) for f in range(F)]),
+                                                            np.int32) for p in (map_idx, par_idx, ver_idx)]
+        prm = _plane_params(params)
+        self._plane_frames = off.copy()
+        self._chk(self.L.drfe_plane_match_batch(self.h, _p(prm), F, _p(fm), _p(T), _p(off), _p(cf), _p(pri[0]), _p(pri[1]),
+                                                _p(pri[2]), int(bool(flag_points)), C.c_void_p(stream)), "drfe_plane_match_batch")
+
+    def plane_match_download(self, frame: int):
+        """(map_idx, par_idx, ver_idx, nmatches, n_pairs) of one frame of the most recent plane_match_batch"""
+        P = int(self._plane_frames[frame + 1] - self._plane_frames[frame])
+        mi, pi, vi = (np.zeros(P, np.int32) for _ in range(3))
+        nm, npair = C.c_int(), C.c_int()
+        self._chk(self.L.drfe_plane_match_download(self.h, frame, _p(mi), _p(pi), _p(vi), C.byref(nm), C.byref(npair)),
+                  "drfe_plane_match_download")
+        return mi, pi, vi, nm.value, npair.value
+
+    def plane_flags_download(self, map_id: int):
+        """uint8 flags of the map's points: the OR over the frames of that map in the most recent batch"""
+        out = np.zeros(max(self._plane_points[map_id], 1), np.uint8)
+        self._chk(self.L.drfe_plane_flags_download(self.h, map_id, _p(out)), "drfe_plane_flags_download")
+        return out[:self._plane_points[map_id]]
 
     # --- measurement -------------------------------------------------------------------------------
     def profile_enable(self, on=True):

@@ -828,6 +828,59 @@ int drfe_manhattan_track_batch(drfe_ctx* ctx, const float* R0, int nseq, int seq
 int drfe_manhattan_download(drfe_ctx* ctx, int frame, float* R, drfe_manhattan_info* info, uint16_t* rec_bits,
                             uint16_t* line_bits);
 
+/* Plane association (PlaneMatcher::SearchMapByCoefficients, src/PlaneMatcher.cpp:11-91 with PointDistanceFromPlane :206-226;
+ * Map::FlagMatchedPlanePoints, src/Map.cc:406-431; PlaneMatcher::bMatchStatus, src/PlaneMatcher.cpp:94-201).  Tracking calls
+ * SearchMapByCoefficients up to twice per frame (src/Tracking.cc:2202, 2332, 2451, 2584, 2807) and FlagMatchedPlanePoints once
+ * (:532).  Frame planes are camera-frame coefficients (Frame::mvPlaneCoefficients, 4 floats); world coefficients are
+ * transpose(Tcw) * coef (Frame::ComputePlaneWorldCoeff, src/Frame.cc:1311-1317).  A map plane is its world coefficients
+ * (MapPlane::GetWorldPos), its isBad() and its merged cloud (mvPlanePoints, xyz floats) in CSR form: plane j owns points
+ * [cloud_offsets[j], cloud_offsets[j + 1]) of cloud_xyz.  Map planes are indexed in vpMapPlanes order; -1 is a null pointer.
+ * Bit-exact with the reference's float arithmetic; DESIGN.md section 12. */
+typedef struct drfe_plane_match_params {
+    float dTh, aTh, verTh, parTh;   /* PlaneMatcher's constructor arguments; the reference's defaults 0.1, 0.86, 0.08716, 0.9962 */
+} drfe_plane_match_params;
+
+/* SearchMapByCoefficients on one frame, on the host, no context.  map_idx / par_idx / ver_idx (n_planes each:
+ * mvpMapPlanes / mvpParallelPlanes / mvpVerticalPlanes) are in / out: the reference does not reset them, so an entry the
+ * call does not assign keeps what it held.  *nmatches = the return value (frame planes that found a map plane). */
+int drfe_plane_match_host(const drfe_plane_match_params* params, const float* Tcw, const float* coefs, int n_planes,
+                          const float* map_coefs, const uint8_t* map_bad, const int32_t* cloud_offsets, const float* cloud_xyz,
+                          int n_map, int32_t* map_idx, int32_t* par_idx, int32_t* ver_idx, int* nmatches);
+/* FlagMatchedPlanePoints on one frame, on the host: every frame plane with map_idx[i] >= 0 (its map plane's isBad() is not
+ * read) sets flags[p] = 1 for the map points p (xyz floats, MapPoint::GetWorldPos) with |world coef . (x, y, z, 1)| < 0.5;
+ * flags are only ever set (SetAssociatedWithPlaneFlag(true)), never cleared.  The reference's dTh argument is unused there and
+ * has no counterpart.  *n_pairs (may be NULL) = the reference's nMatches, the number of (plane, point) pairs that passed. */
+int drfe_plane_flag_points_host(const float* Tcw, const float* coefs, int n_planes, const int32_t* map_idx, const float* points_xyz,
+                                int n_points, uint8_t* flags, int* n_pairs);
+/* bMatchStatus on one frame, on the host: matched_coefs[i] (4 floats) and matched[i] describe mvpMapPlanes[i] (matched 0: null
+ * or isBad(), skipped).  Rwc_MF (row-major 3x3) is read only when MF_contrast != 0; with MF_contrast == 0 the reference reads an
+ * uninitialised angle_MF, canonicalised to 0 here (the test then never fails).  *status = the return value (1 = true). */
+int drfe_plane_match_status_host(const drfe_plane_match_params* params, const float* Tcw, const float* coefs, int n_planes,
+                                 const float* matched_coefs, const uint8_t* matched, int MF_contrast, const float* Rwc_MF,
+                                 int* status);
+
+/* Device-resident maps of drfe_plane_match_batch: n_maps maps, map s owning map planes [plane_offsets[s], plane_offsets[s + 1])
+ * of map_coefs / map_bad / cloud_offsets (plane-local order = vpMapPlanes order; cloud_offsets has one entry per plane plus
+ * one, global into cloud_xyz) and map points [point_offsets[s], point_offsets[s + 1]) of points_xyz (mspMapPoints, any order).
+ * Replaces the previous upload (synchronises). */
+int drfe_plane_map_upload(drfe_ctx* ctx, int n_maps, const int32_t* plane_offsets, const float* map_coefs, const uint8_t* map_bad,
+                          const int32_t* cloud_offsets, const float* cloud_xyz, const int32_t* point_offsets,
+                          const float* points_xyz);
+/* SearchMapByCoefficients (then, with flag_points, FlagMatchedPlanePoints) of nframes frames on the device, each against map
+ * frame_map[f] as uploaded: frame f has planes [plane_offsets[f], plane_offsets[f + 1]) of coefs (4 floats each) and pose
+ * Tcw + 16 f.  map_idx / par_idx / ver_idx: the prior contents of the three pointer vectors, plane-local map indices, one per
+ * frame plane (NULL = all null).  Host inputs; asynchronous on `stream` (hipStream_t; NULL = the context stream). */
+int drfe_plane_match_batch(drfe_ctx* ctx, const drfe_plane_match_params* params, int nframes, const int32_t* frame_map,
+                           const float* Tcw, const int32_t* plane_offsets, const float* coefs, const int32_t* map_idx,
+                           const int32_t* par_idx, const int32_t* ver_idx, int flag_points, void* stream);
+/* Results of frame `frame` of the most recent drfe_plane_match_batch (synchronises): the three index arrays (the frame's plane
+ * count each), *nmatches and *n_pairs (0 without flag_points); any may be NULL. */
+int drfe_plane_match_download(drfe_ctx* ctx, int frame, int32_t* map_idx, int32_t* par_idx, int32_t* ver_idx, int* nmatches,
+                              int* n_pairs);
+/* The map-point flags of map `map` after the most recent drfe_plane_match_batch with flag_points: the OR over every frame of
+ * that map in the call (0 everywhere for a map no frame used); one byte per map point (synchronises). */
+int drfe_plane_flags_download(drfe_ctx* ctx, int map, uint8_t* flags);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

@@ -9,6 +9,8 @@
  *   Planar_SLAM::ORBmatcher            include/ORBmatcher.h:41-84  - the reference's thirteen signatures (templates over Frame / KeyFrame / MapPoint)
  *   Planar_SLAM::LSDmatcher            include/LSDmatcher.h:21-36  - the reference's ten signatures (templates over Frame / KeyFrame / MapLine)
  *   drfe::TrackManhattanFrame          src/Tracking.cc:1336          - Tracking's Manhattan-frame tracker (host entry)
+ *   Planar_SLAM::PlaneMatcher          include/PlaneMatcher.h:10-31  - SearchMapByCoefficients and bMatchStatus (host entries)
+ *   drfe::FlagMatchedPlanePoints       src/Map.cc:406-431            - Map::FlagMatchedPlanePoints (host entry)
  * With -DDRFE_WITH_OPENCV the container types are OpenCV's (cv::Mat, cv::KeyPoint, cv::line_descriptor::KeyLine);
  * without it (this image has no OpenCV) minimal stand-ins with the same member names and memory layout are used, so the
  * header is compiled and exercised here (tests/native/adaptor_caller.cpp, run by tests/test_gpu_native.py).
@@ -1536,6 +1538,136 @@ inline RotationMat TrackManhattanFrame(RotationMat& mLastRcm, std::vector<SN>& v
             }
     }
     return R;
+}
+}  // namespace drfe
+
+/* PlaneMatcher (include/PlaneMatcher.h:10-31, src/PlaneMatcher.cpp) over drfe_plane_match_host / drfe_plane_match_status_host,
+ * and Map::FlagMatchedPlanePoints (src/Map.cc:406-431) over drfe_plane_flag_points_host: no context, no device.  Templates over
+ * the frame / map-plane / map-point types that read only the members the reference reads
+ *   Frame:    mnPlaneNum, mTcw (4x4 float), mvPlaneCoefficients (4x1 float each), mvpMapPlanes, mvpParallelPlanes,
+ *             mvpVerticalPlanes, mbNewPlane
+ *   MapPlane: isBad(), GetWorldPos() (4x1 float), mvPlanePoints->points[k].x / y / z
+ *   MapPoint: GetWorldPos() (3x1 float), SetAssociatedWithPlaneFlag(bool)
+ * through Mat::ptr<float>(row), which cv::Mat and the stand-in share.  The three pointer vectors are written where the reference
+ * writes them and left alone elsewhere (the reference does not reset them).  PlaneMatcher::Fuse is declared in the reference
+ * but never defined, so it has no counterpart.  DESIGN.md section 12. */
+namespace Planar_SLAM {
+namespace drfe_detail {
+template <class M> inline float mat_f(const M& m, int r, int c = 0) { return m.template ptr<float>(r)[c]; }
+template <class FrameT> inline void frame_planes_of(FrameT& pF, float Tcw[16], std::vector<float>& coefs)
+{
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) Tcw[r * 4 + c] = mat_f(pF.mTcw, r, c);
+    coefs.resize(4 * (size_t)pF.mnPlaneNum);
+    for (int i = 0; i < pF.mnPlaneNum; i++)
+        for (int k = 0; k < 4; k++) coefs[4 * (size_t)i + k] = mat_f(pF.mvPlaneCoefficients[i], k);
+}
+}  // namespace drfe_detail
+
+class PlaneMatcher {
+public:
+    PlaneMatcher(float dTh = 0.1, float aTh = 0.86, float verTh = 0.08716, float parTh = 0.9962) : dTh(dTh), aTh(aTh), verTh(verTh), parTh(parTh) {}
+
+    /* src/PlaneMatcher.cpp:11-91; Rwc_MF is unused, as in the reference */
+    template <class FrameT, class MapPlaneT, class MatT>
+    int SearchMapByCoefficients(FrameT& pF, const std::vector<MapPlaneT*>& vpMapPlanes, MatT /*Rwc_MF*/)
+    {
+        pF.mbNewPlane = false;
+        float Tcw[16];
+        std::vector<float> coefs;
+        drfe_detail::frame_planes_of(pF, Tcw, coefs);
+        const int M = (int)vpMapPlanes.size(), P = pF.mnPlaneNum;
+        std::vector<float> mc(4 * (size_t)M, 0.f), xyz;
+        std::vector<uint8_t> bad(M);
+        std::vector<int32_t> off(M + 1, 0);
+        for (int j = 0; j < M; j++) {
+            MapPlaneT* pl = vpMapPlanes[j];
+            bad[j] = pl->isBad() ? 1 : 0;
+            if (!bad[j]) {                    /* a bad plane's position and cloud are never read */
+                const auto pW = pl->GetWorldPos();
+                for (int k = 0; k < 4; k++) mc[4 * (size_t)j + k] = drfe_detail::mat_f(pW, k);
+                for (const auto& p : pl->mvPlanePoints->points) {
+                    xyz.push_back(p.x); xyz.push_back(p.y); xyz.push_back(p.z);
+                }
+            }
+            off[j + 1] = (int32_t)(xyz.size() / 3);
+        }
+        std::vector<int32_t> mi(P, -1), pi(P, -1), vi(P, -1);
+        const drfe_plane_match_params prm = {dTh, aTh, verTh, parTh};
+        int n = 0;
+        if (drfe_plane_match_host(&prm, Tcw, coefs.data(), P, mc.data(), bad.data(), off.data(), xyz.data(), M, mi.data(), pi.data(),
+                                  vi.data(), &n) != DRFE_OK)
+            throw std::runtime_error("drfe_plane_match_host failed");
+        for (int i = 0; i < P; i++) {
+            if (mi[i] >= 0) pF.mvpMapPlanes[i] = vpMapPlanes[mi[i]];
+            if (pi[i] >= 0) pF.mvpParallelPlanes[i] = vpMapPlanes[pi[i]];
+            if (vi[i] >= 0) pF.mvpVerticalPlanes[i] = vpMapPlanes[vi[i]];
+        }
+        return n;
+    }
+
+    /* src/PlaneMatcher.cpp:94-201 over the planes already in mvpMapPlanes (vpMapPlanes is not read); without MF_contrast the
+     * reference compares with an uninitialised angle_MF, taken as 0 here (the call then returns true) */
+    template <class FrameT, class MapPlaneT, class MatT>
+    bool bMatchStatus(FrameT& pF, const std::vector<MapPlaneT*>& /*vpMapPlanes*/, const bool MF_contrast, MatT Rwc_MF)
+    {
+        pF.mbNewPlane = false;
+        float Tcw[16], R[9];
+        std::vector<float> coefs;
+        drfe_detail::frame_planes_of(pF, Tcw, coefs);
+        const int P = pF.mnPlaneNum;
+        if (P < 2) return true;
+        std::vector<float> mc(4 * (size_t)P, 0.f);
+        std::vector<uint8_t> matched(P, 0);
+        for (int i = 0; i < P; i++) {
+            auto* pl = pF.mvpMapPlanes[i];
+            if (!pl || pl->isBad()) continue;
+            matched[i] = 1;
+            const auto pW = pl->GetWorldPos();
+            for (int k = 0; k < 4; k++) mc[4 * (size_t)i + k] = drfe_detail::mat_f(pW, k);
+        }
+        if (MF_contrast)
+            for (int r = 0; r < 3; r++)
+                for (int c = 0; c < 3; c++) R[r * 3 + c] = drfe_detail::mat_f(Rwc_MF, r, c);
+        const drfe_plane_match_params prm = {dTh, aTh, verTh, parTh};
+        int st = 1;
+        if (drfe_plane_match_status_host(&prm, Tcw, coefs.data(), P, mc.data(), matched.data(), MF_contrast ? 1 : 0,
+                                         MF_contrast ? R : nullptr, &st) != DRFE_OK)
+            throw std::runtime_error("drfe_plane_match_status_host failed");
+        return st != 0;
+    }
+
+protected:
+    float dTh, aTh, verTh, parTh;
+};
+}  // namespace Planar_SLAM
+
+namespace drfe {
+/* Map::FlagMatchedPlanePoints(pF, dTh) (src/Map.cc:406-431) with the map's point set passed in (mspMapPoints; the caller holds
+ * the map mutex): SetAssociatedWithPlaneFlag(true) on every map point within 0.5 of a matched frame plane.  dTh is unused, as
+ * in the reference.  Returns the reference's (discarded) nMatches. */
+template <class FrameT, class MapPointSet>
+inline int FlagMatchedPlanePoints(FrameT& pF, const MapPointSet& mspMapPoints, const float& /*dTh*/)
+{
+    float Tcw[16];
+    std::vector<float> coefs;
+    Planar_SLAM::drfe_detail::frame_planes_of(pF, Tcw, coefs);
+    const int P = pF.mnPlaneNum;
+    std::vector<int32_t> mi(P);
+    for (int i = 0; i < P; i++) mi[i] = pF.mvpMapPlanes[i] ? 0 : -1;
+    std::vector<typename MapPointSet::value_type> pts(mspMapPoints.begin(), mspMapPoints.end());
+    std::vector<float> xyz(3 * pts.size());
+    for (size_t p = 0; p < pts.size(); p++) {
+        const auto pW = pts[p]->GetWorldPos();
+        for (int k = 0; k < 3; k++) xyz[3 * p + k] = Planar_SLAM::drfe_detail::mat_f(pW, k);
+    }
+    std::vector<uint8_t> flags(pts.size(), 0);
+    int n = 0;
+    if (drfe_plane_flag_points_host(Tcw, coefs.data(), P, mi.data(), xyz.data(), (int)pts.size(), flags.data(), &n) != DRFE_OK)
+        throw std::runtime_error("drfe_plane_flag_points_host failed");
+    for (size_t p = 0; p < pts.size(); p++)
+        if (flags[p]) pts[p]->SetAssociatedWithPlaneFlag(true);
+    return n;
 }
 }  // namespace drfe
 
