@@ -55,10 +55,16 @@ struct DevLevel {
     float scale;              /* mvScaleFactor[l] */
     float kpSize;             /* (float)(int)(31*scale) */
     int xtabOff, ytabOff;     /* resize coefficient tables (level >= 1), element offsets */
-    int xwinOff, ywinOff;     /* per 256-column / 16-row block of the bordered level: (lowest, highest) source index its
-                                 taps touch, stored as ResizeTap{s0 = lo, s1 = hi}; resizeLds = 0 if a window exceeds the
-                                 LDS tile of k_pyr_resize_lds */
+    /* k_pyr_resize_tile: items (row group of 4 rows, column group of 4 columns) numbered densely, rzCols column groups per
+     * row group covering the bordered columns, rzGroups row groups covering bordered rows [rzRow0, rzRow0 + 4 rzGroups):
+     * every interior row and as many border rows as make the frame's items fill its rzBlocks blocks of 256; the other
+     * border rows are stored as mirror images.  A block stages the source window of its items in LDS: rzRows rows of
+     * rzWq 16-byte quads, rzFill loads per thread, origin per block at rzWinOff as ResizeTap{s0 = bordered source row,
+     * s1 = bordered source column}.  resizeLds = 0: the level runs k_pyr_resize. */
     int resizeLds;
+    int rzRow0, rzGroups, rzCols, rzBlocks;
+    int rzRows, rzWq, rzFill, rzWinOff;
+    uint32_t rzColsMagic, rzWqMagic;   /* drfe_div_magic of rzCols, rzWq */
     int cellBegin, cellEnd;   /* range in the FAST cell table */
     int tileBegin, tileEnd;   /* range in the blur tile table */
 };
@@ -329,8 +335,9 @@ hipError_t drfe_launch_kp_pixels(drfe_ctx* c, int nframes, uint32_t* d_uv, hipSt
 hipError_t drfe_launch_match_consecutive(drfe_ctx* c, const drfe_camera& cam, float th, int mono, int checkOri,
                                          int nframes, hipStream_t s);
 
-#define DRFE_RESIZE_LDS_WD 88     /* dwords per source row of the k_pyr_resize_lds tile (256 output columns * 1.25 + slack) */
-#define DRFE_RESIZE_LDS_ROWS 24   /* source rows of the tile (16 output rows * 1.25 + slack) */
+#define DRFE_RESIZE_BLOCK 256          /* items (4 x 4 output pixels) per k_pyr_resize_tile block */
+#define DRFE_RESIZE_MAX_FILL 8         /* most 16-byte tile loads per thread (template instances) */
+#define DRFE_RESIZE_TILE_BYTES 32768   /* largest source tile; a level whose blocks need more runs k_pyr_resize */
 /* XCD-aware block numbering for the batch-wide 2-D grids (x = item inside a frame, y = frame slot).  Workgroups are dealt
  * round-robin over the 8 XCDs in dispatch order (x fastest), so consecutive cells / tiles / keypoint groups of one frame -
  * which share pyramid lines - would land on eight different private L2s and every line would cross the fabric several

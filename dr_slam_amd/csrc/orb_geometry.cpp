@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 
 static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
@@ -90,6 +91,67 @@ static void build_taps(int src, int dst, int padded, std::vector<ResizeTap>* out
         if (p < 0) p = -p;
         if (p >= dst) p = 2 * (dst - 1) - p;
         out->push_back(axis[p]);
+    }
+}
+
+/* Item layout and source tiles of k_pyr_resize_tile for level L resized from P (see DevLevel).  Lanes go to bordered columns
+ * only (rzCols = ceil((w + 38) / 4) per row group), and the rows computed directly are chosen among [h, h + 38] so that the
+ * frame's last block is as full as possible.  Each block's tile is the union of the source windows of its items; all blocks
+ * of a level load the same rzRows x rzWq quads (origins pulled back inside the source level where needed), so the fill is a
+ * fixed count per thread. */
+static void plan_resize_tile(DevLevel& L, const DevLevel& P, std::vector<ResizeTap>* taps)
+{
+    const int bw = L.w + 2 * DRFE_EDGE, bh = L.h + 2 * DRFE_EDGE, B = DRFE_RESIZE_BLOCK;
+    const int cols = (bw + 3) / 4;
+    int groups = 0, blocks = 0;
+    for (int ng = (L.h + 3) / 4; 4 * ng <= bh; ng++) {
+        const int nb = (ng * cols + B - 1) / B;
+        /* fill = ng * cols / (nb * B); ties keep the fewer rows */
+        if (!groups || (long long)ng * cols * blocks > (long long)groups * cols * nb) { groups = ng; blocks = nb; }
+    }
+    const int extra = 4 * groups - L.h;
+    L.rzCols = cols; L.rzGroups = groups; L.rzBlocks = blocks;
+    L.rzRow0 = DRFE_EDGE - std::max(0, extra - DRFE_EDGE);
+    L.rzColsMagic = drfe_div_magic((uint32_t)cols);
+    /* the kernel serves both taps of a column with one 8-byte window per column pair: the pair's first taps must lie within
+     * 3 pixels of each other; scale factors up to 2 give at most 2, and that is what is checked */
+    bool ok = true;
+    const ResizeTap* xt = taps->data() + L.xtabOff;
+    const ResizeTap* yt = taps->data() + L.ytabOff;
+    for (int x = 0; x < 4 * cols; x += 2)
+        if (std::abs((int)xt[x].s0 - (int)xt[x + 1].s0) > 2) ok = false;
+    /* per block: bordered source rows [r0, r1] and columns [c0, c1] its taps read (the kernel reads s0 + 1 for the second tap) */
+    std::vector<int> r0v(blocks), c0v(blocks);
+    int rows = 0, quads = 0;
+    for (int b = 0; b < blocks; b++) {
+        const int i0 = b * B, i1 = std::min(groups * cols, i0 + B);
+        int r0 = 1 << 30, r1 = -1, c0 = 1 << 30, c1 = -1;
+        for (int g = i0 / cols; g <= (i1 - 1) / cols; g++) {
+            for (int y = L.rzRow0 + 4 * g; y < L.rzRow0 + 4 * g + 4; y++) {
+                r0 = std::min(r0, (int)yt[y].s0 + DRFE_EDGE); r1 = std::max(r1, (int)yt[y].s1 + DRFE_EDGE);
+            }
+            const int ca = std::max(i0 - g * cols, 0), cb = std::min(i1 - g * cols, cols);
+            for (int x = 4 * ca; x < 4 * cb; x++) {
+                c0 = std::min(c0, (int)xt[x].s0 + DRFE_EDGE); c1 = std::max(c1, (int)xt[x].s0 + 1 + DRFE_EDGE);
+            }
+        }
+        r0v[b] = r0; c0v[b] = c0 & ~15;
+        rows = std::max(rows, r1 - r0 + 1);
+        quads = std::max(quads, (c1 - c0v[b]) / 16 + 1);
+    }
+    const int pbh = P.h + 2 * DRFE_EDGE;
+    if (rows > pbh || 16 * quads > P.pyrPitch) ok = false;
+    quads = std::max(quads, 2);                 /* divisors of the kernel's multiply-high quotients must be >= 2 */
+    L.rzRows = rows; L.rzWq = quads;
+    L.rzWqMagic = drfe_div_magic((uint32_t)quads);
+    L.rzFill = (rows * quads + B - 1) / B;
+    if (L.rzFill > DRFE_RESIZE_MAX_FILL || rows * quads * 16 + 16 > DRFE_RESIZE_TILE_BYTES) ok = false;
+    L.resizeLds = ok ? 1 : 0;
+    L.rzWinOff = (int)taps->size();
+    for (int b = 0; b < blocks; b++) {
+        /* pulled back so that every block's rows x quads stay inside the source level (P.pyrPitch is a multiple of 64) */
+        const int r0 = std::max(0, std::min(r0v[b], pbh - rows)), c0 = std::max(0, std::min(c0v[b], P.pyrPitch - 16 * quads));
+        taps->push_back(ResizeTap{(uint16_t)r0, (uint16_t)c0, 0, 0});
     }
 }
 
@@ -209,8 +271,9 @@ int drfe_build_geometry(drfe_ctx* c, int w, int h, DevGeom* g, std::vector<FastC
         L.tileEnd = tiles ? (int)tiles->size() : 0;
         /* resize taps from level l-1 (cascade, :1120) */
         L.xtabOff = L.ytabOff = 0;
-        L.xwinOff = L.ywinOff = 0;
         L.resizeLds = 0;
+        L.rzRow0 = L.rzGroups = L.rzCols = L.rzBlocks = L.rzRows = L.rzWq = L.rzFill = L.rzWinOff = 0;
+        L.rzColsMagic = L.rzWqMagic = 0;
         if (l > 0 && taps) {
             if (taps->size() & 1) taps->push_back(ResizeTap{0, 0, 0, 0});
             L.xtabOff = (int)taps->size();
@@ -218,33 +281,10 @@ int drfe_build_geometry(drfe_ctx* c, int w, int h, DevGeom* g, std::vector<FastC
             if (taps->size() & 1) taps->push_back(ResizeTap{0, 0, 0, 0});
             L.ytabOff = (int)taps->size();
             build_taps(g->lv[l - 1].h, L.h, align_up(L.h + 2 * DRFE_EDGE, 4), taps);   /* 4 rows per thread */
-            /* source windows of the 256 x 16 output blocks of k_pyr_resize_lds */
-            const int bh = L.h + 2 * DRFE_EDGE;
-            const int nbx = (L.pyrPitch + 255) / 256, nby = (bh + 15) / 16;
-            L.resizeLds = 1;
-            L.xwinOff = (int)taps->size();
-            for (int b = 0; b < nbx; b++) {
-                int lo = 1 << 30, hi = -1;
-                for (int x = b * 256; x < std::min(b * 256 + 256, L.pyrPitch); x++) {
-                    const ResizeTap& t = (*taps)[L.xtabOff + x];
-                    lo = std::min(lo, (int)t.s0); hi = std::max(hi, (int)t.s1);
-                }
-                const int ws = (lo + DRFE_EDGE) & ~3;
-                if ((hi + DRFE_EDGE - ws) / 4 + 1 > DRFE_RESIZE_LDS_WD) L.resizeLds = 0;
-                taps->push_back(ResizeTap{(uint16_t)lo, (uint16_t)hi, 0, 0});
-            }
-            L.ywinOff = (int)taps->size();
-            for (int b = 0; b < nby; b++) {
-                int lo = 1 << 30, hi = -1;
-                for (int y = b * 16; y < std::min(b * 16 + 16, bh); y++) {
-                    const ResizeTap& t = (*taps)[L.ytabOff + y];
-                    lo = std::min(lo, (int)t.s0); hi = std::max(hi, (int)t.s1);
-                }
-                if (hi - lo + 1 > DRFE_RESIZE_LDS_ROWS) L.resizeLds = 0;
-                taps->push_back(ResizeTap{(uint16_t)lo, (uint16_t)hi, 0, 0});
-            }
-            if (!L.resizeLds) {
-                /* the register-only kernel reads a 12-byte window per four output columns: make sure it is enough */
+            plan_resize_tile(L, g->lv[l - 1], taps);
+            {
+                /* the register-only kernel reads a 12-byte window per four output columns: the supported scale factors are
+                 * those it can run, whichever kernel a level takes */
                 for (int x = 0; x + 3 < L.pyrPitch; x += 4) {
                     int lo = 1 << 30, hi = -1;
                     for (int k = 0; k < 4; k++) {

@@ -153,101 +153,100 @@ __global__ __launch_bounds__(256) void k_pyr_resize(const DevLevel L, const DevL
     }
 }
 
-/* The same resize with the source staged in LDS: a 64 x 4 block (256 output columns x 16 rows) first copies the
- * source window its taps touch — host-computed per block, <= 24 rows x 88 dwords — into LDS with coalesced dword loads
- * (6-7 per thread instead of 24), and every tap becomes one ds_read_u8 instead of a byte picked out of registers.
- * Arithmetic and results are identical to k_pyr_resize; measured speed is the same (~2.3 TB/s: neither version is
- * VALU- or issue-bound), so this is the default only because it is the simpler inner loop.  (Tried: 16 pixels per
- * thread with 16-byte loads and stores — slower, the strided LDS byte reads conflict.) */
-#define RES_PITCH (DRFE_RESIZE_LDS_WD * 4 + 4)      /* bytes per LDS row: odd dword count, no bank aliasing between rows */
-__global__ __launch_bounds__(256) void k_pyr_resize_lds(const DevLevel L, const DevLevel P, int pyrSlotBytes,
-                                                        const ResizeTap* __restrict__ taps, uint8_t* __restrict__ pyr,
-                                                        uint32_t magicXY, uint32_t magicX)
+/* The resize with the source staged in LDS.  A thread computes one item, 4 x 4 pixels of the bordered level; items are
+ * numbered densely over the bordered columns and the rows the host chose (DevLevel rz*), 256 per block, so no lane works on
+ * pitch padding and a frame's last block is nearly full.  Arithmetic and results are identical to k_pyr_resize.
+ *   fill        the block's source window, rzRows x rzWq 16-byte quads from a host-computed origin, FILL loads per thread
+ *               on the block's scalar base with 32-bit offsets, all issued before the first LDS write
+ *   horizontal  per source row two dword pairs (ds_read2_b32), one per column pair; v_perm_b32 picks a column's two taps
+ *               as a u16x2 (selector fixed per thread) and v_dot2_u32_u16 applies both weights: exact, 255 * 2049 < 2^32
+ *   vertical    (b * h) >> 16 as one v_mul_hi_u32 of h by b << 16 (weights and sums are non-negative)
+ * The source row shared by consecutive output rows is reused, and interior rows whose mirror image in the border is not
+ * computed directly are stored there as well (copyMakeBorder REFLECT_101 of the resized interior, :1122-1123). */
+template <int FILL>
+__global__ __launch_bounds__(256) void k_pyr_resize_tile(const DevLevel L, const DevLevel P, int pyrSlotBytes,
+                                                         const ResizeTap* __restrict__ taps, uint8_t* __restrict__ pyr,
+                                                         uint32_t magicBlocks)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t tile[DRFE_RESIZE_LDS_ROWS * RES_PITCH];
-    int bx, by, bz;
-    drfe_xcd_swizzle_3d(magicXY, magicX, bx, by, bz);   /* a frame's tiles on one XCD: neighbouring source windows overlap */
-    bx = __builtin_amdgcn_readfirstlane(bx); by = __builtin_amdgcn_readfirstlane(by);    /* block-uniform: scalar bases */
-    const int slot = __builtin_amdgcn_readfirstlane(bz);
-    const int tid = threadIdx.y * 64 + threadIdx.x;
-    uint8_t* base = pyr + (size_t)slot * pyrSlotBytes;
-    const ResizeTap wx = taps[L.xwinOff + bx], wy = taps[L.ywinOff + by];
-    /* this thread's taps first: their latency overlaps the tile fill instead of following the barrier */
-    /* a wavefront is one row of the 64 x 4 block: its four output rows, their source rows and vertical weights are
-     * wave-uniform, and readfirstlane tells the compiler so (scalar row bases, scalar branches below) */
-    const int y0 = (by * 4 + __builtin_amdgcn_readfirstlane((int)threadIdx.y)) * PYR_ROWS;
-    const int x4 = (bx * 64 + threadIdx.x) * 4;
-    const int bh = L.h + 2 * DRFE_EDGE;
-    const bool active = y0 < bh && x4 < L.pyrPitch;
-    const int yT = y0 < bh ? y0 : 0, xT = active ? x4 : 0;
-    const uint4 tya = *reinterpret_cast<const uint4*>(taps + L.ytabOff + yT);
-    const uint4 tyb = *reinterpret_cast<const uint4*>(taps + L.ytabOff + yT + 2);
-    const uint4 ta = *reinterpret_cast<const uint4*>(taps + L.xtabOff + xT);
-    const uint4 tb = *reinterpret_cast<const uint4*>(taps + L.xtabOff + xT + 2);
-    /* The 19 border rows above and below the level are mirror images of interior rows (copyMakeBorder REFLECT_101 of the resized
-     * interior, :1122-1123): the thread that computes interior row p in [1, 19] or [h - 20, h - 2] stores it a second time at
-     * its mirror row, and nobody computes a border row - 38 of a level's h + 38 rows, a fifth of the small levels.  A block
-     * whose sixteen rows are all border rows has nothing to do (block-uniform: before the tile fill and the barrier). */
+    extern __shared__ __attribute__((aligned(16))) uint8_t tile[];
+    int bx, slot;
+    drfe_xcd_swizzle_2d(magicBlocks, bx, slot);          /* a frame's blocks on one XCD: neighbouring windows overlap */
+    bx = __builtin_amdgcn_readfirstlane(bx); slot = __builtin_amdgcn_readfirstlane(slot);
+    const int tid = threadIdx.x;
+    uint8_t* const base = pyr + (size_t)slot * pyrSlotBytes;
+    /* the block's window origin through the constant address space: a scalar load */
+    const uint32_t winp = ((const __attribute__((address_space(4))) uint32_t*)taps)[2 * (L.rzWinOff + bx)];
+    const struct { uint32_t s0, s1; } win = {winp & 0xFFFFu, winp >> 16};   /* bordered source row, column of tile byte 0 */
+    const uint32_t nItems = (uint32_t)(L.rzGroups * L.rzCols);
+    uint32_t item = (uint32_t)(bx * DRFE_RESIZE_BLOCK + tid);
+    const bool active = item < nItems;
+    if (!active) item = nItems - 1;
+    /* quotients as one multiply-high and a correction (the host keeps both divisors >= 2, so the magics are not 0) */
+    auto divm = [](uint32_t n, uint32_t d, uint32_t magic) { const uint32_t q = __umulhi(n, magic); return q * d > n ? q - 1 : q; };
+    const uint32_t g = divm(item, (uint32_t)L.rzCols, L.rzColsMagic);
+    const int y0 = L.rzRow0 + 4 * (int)g, x4 = 4 * (int)(item - g * (uint32_t)L.rzCols);
+    /* this thread's taps first: their latency overlaps the tile fill.  Row taps as four 8-byte loads (rzRow0 may be odd);
+     * 32-bit byte offsets from the table's scalar base */
+    const uint8_t* const tb8 = reinterpret_cast<const uint8_t*>(taps);
+    const uint32_t tyo = (uint32_t)(L.ytabOff + y0) * 8u, txo = (uint32_t)(L.xtabOff + x4) * 8u;
+    const uint2 t0 = *reinterpret_cast<const uint2*>(tb8 + tyo), t1 = *reinterpret_cast<const uint2*>(tb8 + (tyo + 8u));
+    const uint2 t2 = *reinterpret_cast<const uint2*>(tb8 + (tyo + 16u)), t3 = *reinterpret_cast<const uint2*>(tb8 + (tyo + 24u));
+    const uint4 ta = *reinterpret_cast<const uint4*>(tb8 + txo);            /* taps of x4, x4+1 */
+    const uint4 tb = *reinterpret_cast<const uint4*>(tb8 + (txo + 16u));    /* x4+2, x4+3 */
     {
-        const int r0 = by * (4 * PYR_ROWS);
-        if (r0 + 4 * PYR_ROWS <= DRFE_EDGE || r0 >= DRFE_EDGE + L.h) return;
-    }
-    const int ws = ((int)wx.s0 + DRFE_EDGE) & ~3;                       /* bordered source column of tile byte 0 */
-    const int wd = (((int)wx.s1 + DRFE_EDGE - ws) >> 2) + 1;           /* dwords per tile row */
-    const int nr = (int)wy.s1 - (int)wy.s0 + 1;
-    const uint8_t* srcw = base + P.pyrOff + (size_t)((int)wy.s0 + DRFE_EDGE) * P.pyrPitch + ws;
-    {   /* (row, dword) of element tid + 256 k, carried incrementally: one division per thread, none in the loop */
-        const int q256 = 256 / wd, r256 = 256 - q256 * wd;
-        int r = tid / wd, cdw = tid - r * wd;
-        while (r < nr) {
-            *reinterpret_cast<uint32_t*>(&tile[r * RES_PITCH + cdw * 4]) =
-                *reinterpret_cast<const uint32_t*>(srcw + (size_t)r * P.pyrPitch + cdw * 4);
-            r += q256; cdw += r256;
-            if (cdw >= wd) { cdw -= wd; r++; }
+        const uint8_t* const srcw = base + P.pyrOff + (uint32_t)((int)win.s0 * P.pyrPitch + (int)win.s1);
+        const uint32_t nq = (uint32_t)(L.rzRows * L.rzWq), tpitch = (uint32_t)L.rzWq * 16u;
+        uint4 v[FILL];
+        uint32_t dst[FILL];
+        /* every load is issued before the first LDS write: a thread past the window reloads quad 0 and writes it into the
+         * 16 spare bytes behind the tile, so neither the loads nor the writes are predicated */
+#pragma unroll
+        for (int k = 0; k < FILL; k++) {
+            const uint32_t j = (uint32_t)tid + (uint32_t)(k * DRFE_RESIZE_BLOCK), jc = j < nq ? j : 0u;
+            const uint32_t r = divm(jc, (uint32_t)L.rzWq, L.rzWqMagic), q = jc - r * (uint32_t)L.rzWq;
+            v[k] = *reinterpret_cast<const uint4*>(srcw + (__umul24(r, (uint32_t)P.pyrPitch) + q * 16u));
+            dst[k] = j < nq ? __umul24(r, tpitch) + q * 16u : nq * 16u;
         }
+#pragma unroll
+        for (int k = 0; k < FILL; k++) *reinterpret_cast<uint4*>(&tile[dst[k]]) = v[k];
     }
     __syncthreads();
-    if (y0 >= bh) return;                        /* wave-uniform; columns past the pitch compute on column 0 and store nothing */
-    if (y0 + PYR_ROWS <= DRFE_EDGE || y0 >= DRFE_EDGE + L.h) return;    /* four border rows: nothing to compute */
-    uint8_t* const dstLevel = base + L.pyrOff;   /* block-uniform: the stores address with one 32-bit offset (a level is < 2^24 bytes) */
-    const uint32_t syp[PYR_ROWS] = {tya.x, tya.z, tyb.x, tyb.z}, wyp[PYR_ROWS] = {tya.y, tya.w, tyb.y, tyb.w};
-    const uint32_t sp[4] = {ta.x, ta.z, tb.x, tb.z}, wp[4] = {ta.y, ta.w, tb.y, tb.w};
-    /* The second tap of a column is the pixel right of the first (s1 == s0 + 1), except at the level's last column where the
-     * table repeats s0 with weight 0: reading s0 + 1 there multiplies whatever the tile holds by zero, so ONE address per
-     * column serves both taps (the second is the +1 immediate of the LDS load; a tile row has a spare dword behind it):
-     * four address adds per source row instead of eight, 22 VGPRs instead of 30 */
-    int o0[4], w0[4], w1[4];
+    if (!active) return;
+    const uint32_t tpitch = (uint32_t)L.rzWq * 16u;
+    const uint32_t sp[4] = {ta.x, ta.z, tb.x, tb.z}, wp[4] = {ta.y, ta.w, tb.y, tb.w};   /* s0 | s1 << 16, w0 | w1 << 16 */
+    /* tile byte of each column's first tap; a column pair reads the two dwords from the lower one's aligned dword, and its
+     * second tap is the next byte (s1 == s0 + 1, or s1 == s0 with w1 == 0 at the level's last column: the byte is multiplied
+     * by zero) */
+    int o[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) o[k] = (int)(sp[k] & 0xFFFFu) + DRFE_EDGE - (int)win.s1;
+    const uint32_t p01 = (uint32_t)min(o[0], o[1]) & ~3u, p23 = (uint32_t)min(o[2], o[3]) & ~3u;
+    uint32_t sel[4];
 #pragma unroll
     for (int k = 0; k < 4; k++) {
-        o0[k] = (int)(sp[k] & 0xFFFF) + DRFE_EDGE - ws;
-        w0[k] = (int)(short)(wp[k] & 0xFFFF); w1[k] = (int)(short)(wp[k] >> 16);
+        const uint32_t rel = (uint32_t)o[k] - (k < 2 ? p01 : p23);
+        sel[k] = rel | ((rel + 1u) << 16) | 0x0C000C00u;     /* bytes rel, rel + 1 into the low bytes of two u16 halves */
     }
-    /* horizontal pass of one source row for this thread's four columns, already shifted (the vertical pass only ever
-     * uses h >> 4) */
+    typedef unsigned short u16x2v __attribute__((ext_vector_type(2)));
     auto hrow = [&](int srow, uint32_t (&H)[4]) {
-        const uint8_t* R = &tile[srow * RES_PITCH];
+        const uint32_t* A = reinterpret_cast<const uint32_t*>(&tile[(uint32_t)srow * tpitch + p01]);
+        const uint32_t* C = reinterpret_cast<const uint32_t*>(&tile[(uint32_t)srow * tpitch + p23]);
+        const uint32_t a0 = A[0], a1 = A[1], c0 = C[0], c1 = C[1];
+        const uint32_t pr[4] = {__builtin_amdgcn_perm(a1, a0, sel[0]), __builtin_amdgcn_perm(a1, a0, sel[1]),
+                                __builtin_amdgcn_perm(c1, c0, sel[2]), __builtin_amdgcn_perm(c1, c0, sel[3])};
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            /* two byte loads on purpose: merged into one 16-bit load (what the compiler does with plain accesses) they are
-             * misaligned for half of the columns, and the LDS serves those at a third of the speed (measured: pyramid stage
-             * 0.50 -> 1.43 ms).  The volatile LDS-address-space pointer keeps them apart. */
-            typedef const volatile __attribute__((address_space(3))) uint8_t* lds_u8p;
-            lds_u8p q = (lds_u8p)(R + o0[k]);
-            H[k] = (uint32_t)(((int)q[0] * w0[k] + (int)q[1] * w1[k]) >> 4);
-        }
+        for (int k = 0; k < 4; k++)
+            H[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2v, pr[k]), __builtin_bit_cast(u16x2v, wp[k]), 0u, false) >> 4;
     };
-    /* Consecutive output rows mostly share a source row (scale 1.2: rows (s, s+1), (s+1, s+2), ...): the lower row's
-     * horizontal pass is kept for the next output row, 5 instead of 8 row passes per thread.  (b * h) >> 16 is the high
-     * half of h * (b << 16): one v_mul_hi_u32 instead of a multiply and a shift (weights and sums are non-negative). */
+    uint8_t* const dstLevel = base + L.pyrOff;           /* the stores address with one 32-bit offset (a level is < 2^24 bytes) */
+    const uint2 typ[4] = {t0, t1, t2, t3};
+    const int rowEnd = L.rzRow0 + 4 * L.rzGroups;
     int prevB = -1;
     uint32_t Hp[4] = {0, 0, 0, 0};
 #pragma unroll
-    for (int r = 0; r < PYR_ROWS; r++) {
-        if (y0 + r >= bh) break;
-        const int pr = y0 + r - DRFE_EDGE;                               /* interior row; wave-uniform */
-        if (pr < 0 || pr >= L.h) continue;                               /* border row: written with its mirror image below */
-        const uint32_t sy = (uint32_t)__builtin_amdgcn_readfirstlane((int)syp[r]), wy2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)wyp[r]);
-        const int a = (int)(sy & 0xFFFF) - (int)wy.s0, b = (int)(sy >> 16) - (int)wy.s0;
+    for (int r = 0; r < 4; r++) {
+        const uint32_t sy = typ[r].x, wy2 = typ[r].y;
+        const int a = (int)(sy & 0xFFFFu) + DRFE_EDGE - (int)win.s0, b = (int)(sy >> 16) + DRFE_EDGE - (int)win.s0;
         uint32_t Ha[4], Hb[4];
         if (a == prevB) {
 #pragma unroll
@@ -258,24 +257,21 @@ __global__ __launch_bounds__(256) void k_pyr_resize_lds(const DevLevel L, const 
             for (int k = 0; k < 4; k++) Hb[k] = Ha[k];
         } else hrow(b, Hb);
         const uint32_t b0s = wy2 << 16, b1s = wy2 & 0xFFFF0000u;
-        /* no saturation needed: H <= (255 * 2049) >> 4 = 32655 and b0 + b1 <= 2049 (two independently rounded 11-bit
-         * weights), so the two floored products sum to at most 1020 and (1020 + 2) >> 2 = 255.  The four 10-bit sums are
-         * shifted two at a time (v_pk_lshrrev_b16 on 16-bit halves) and their low bytes gathered by one v_perm_b32 */
+        /* no saturation needed: H <= (255 * 2049) >> 4 = 32655 and b0 + b1 <= 2049, so the sum is at most 1022 */
         uint32_t sm[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) sm[k] = __umulhi(Ha[k], b0s) + __umulhi(Hb[k], b1s) + 2u;
-        typedef unsigned short u16x2r __attribute__((ext_vector_type(2)));
-        const u16x2r two = {2, 2};
-        const uint32_t q01 = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2r, sm[0] | (sm[1] << 16)) >> two);
-        const uint32_t q23 = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2r, sm[2] | (sm[3] << 16)) >> two);
+        const u16x2v two = {2, 2};
+        const uint32_t q01 = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2v, sm[0] | (sm[1] << 16)) >> two);
+        const uint32_t q23 = __builtin_bit_cast(uint32_t, __builtin_bit_cast(u16x2v, sm[2] | (sm[3] << 16)) >> two);
         const uint32_t out = __builtin_amdgcn_perm(q23, q01, 0x06040200u);
-        if (active) {
-            *reinterpret_cast<uint32_t*>(dstLevel + (uint32_t)(__umul24((uint32_t)(y0 + r), (uint32_t)L.pyrPitch) + (uint32_t)x4)) = out;
-            if (pr >= 1 && pr <= DRFE_EDGE)                              /* mirrors into the top border: bordered row 19 - p */
-                *reinterpret_cast<uint32_t*>(dstLevel + (uint32_t)(__umul24((uint32_t)(DRFE_EDGE - pr), (uint32_t)L.pyrPitch) + (uint32_t)x4)) = out;
-            if (pr >= L.h - 1 - DRFE_EDGE && pr <= L.h - 2)              /* ... into the bottom border: 19 + 2 (h - 1) - p */
-                *reinterpret_cast<uint32_t*>(dstLevel + (uint32_t)(__umul24((uint32_t)(DRFE_EDGE + 2 * (L.h - 1) - pr), (uint32_t)L.pyrPitch) + (uint32_t)x4)) = out;
-        }
+        const int y = y0 + r, p = y - DRFE_EDGE;
+        *reinterpret_cast<uint32_t*>(dstLevel + (uint32_t)(__umul24((uint32_t)y, (uint32_t)L.pyrPitch) + (uint32_t)x4)) = out;
+        if (p >= 1 && p <= DRFE_EDGE && DRFE_EDGE - p < L.rzRow0)                 /* top border row 19 - p, not computed */
+            *reinterpret_cast<uint32_t*>(dstLevel + (uint32_t)(__umul24((uint32_t)(DRFE_EDGE - p), (uint32_t)L.pyrPitch) + (uint32_t)x4)) = out;
+        const int yb = DRFE_EDGE + 2 * (L.h - 1) - p;                          /* bottom border row of interior rows h-20..h-2 */
+        if (p >= L.h - 1 - DRFE_EDGE && p <= L.h - 2 && yb >= rowEnd)
+            *reinterpret_cast<uint32_t*>(dstLevel + (uint32_t)(__umul24((uint32_t)yb, (uint32_t)L.pyrPitch) + (uint32_t)x4)) = out;
         prevB = b;
 #pragma unroll
         for (int k = 0; k < 4; k++) Hp[k] = Hb[k];
@@ -1570,12 +1566,17 @@ hipError_t drfe_launch_orb(drfe_ctx* c, const uint8_t* d_gray, size_t frameStrid
     }
     for (int l = 1; l < nl; l++) {
         const DevLevel& L = g.lv[l];
-        dim3 grid((L.pyrPitch / 4 + 63) / 64, (L.h + 2 * DRFE_EDGE + 4 * PYR_ROWS - 1) / (4 * PYR_ROWS), nframes);
-        if (L.resizeLds)
-            hipLaunchKernelGGL(k_pyr_resize_lds, grid, dim3(64, 4), 0, s, L, g.lv[l - 1], g.pyrSlotBytes, c->d_taps, c->d_pyr,
-                               drfe_div_magic(grid.x * grid.y), drfe_div_magic(grid.x));
-        else
+        if (L.resizeLds) {
+            typedef void (*ResizeTileFn)(const DevLevel, const DevLevel, int, const ResizeTap*, uint8_t*, uint32_t);
+            static const ResizeTileFn fns[DRFE_RESIZE_MAX_FILL] = {k_pyr_resize_tile<1>, k_pyr_resize_tile<2>, k_pyr_resize_tile<3>,
+                k_pyr_resize_tile<4>, k_pyr_resize_tile<5>, k_pyr_resize_tile<6>, k_pyr_resize_tile<7>, k_pyr_resize_tile<8>};
+            const dim3 grid(L.rzBlocks, nframes);
+            hipLaunchKernelGGL(fns[L.rzFill - 1], grid, dim3(DRFE_RESIZE_BLOCK), (size_t)(L.rzRows * L.rzWq * 16 + 16), s, L,
+                               g.lv[l - 1], g.pyrSlotBytes, c->d_taps, c->d_pyr, drfe_div_magic(grid.x));
+        } else {
+            const dim3 grid((L.pyrPitch / 4 + 63) / 64, (L.h + 2 * DRFE_EDGE + 4 * PYR_ROWS - 1) / (4 * PYR_ROWS), nframes);
             hipLaunchKernelGGL(k_pyr_resize, grid, dim3(64, 4), 0, s, L, g.lv[l - 1], g.pyrSlotBytes, c->d_taps, c->d_pyr);
+        }
     }
     prof_end(c, DRFE_STAGE_PYRAMID, s);
 
