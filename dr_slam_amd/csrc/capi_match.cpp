@@ -428,6 +428,11 @@ int drfe_match_consecutive_batch(drfe_ctx* c, const float* Tcw, const float* Twc
         c->err = "match: needs an extracted batch of >= 2 frames with stereo/grid computed";
         return DRFE_ERR_STATE;
     }
+    if (c->maxKp > DRFE_MATCH_LAST_MAX_QUERIES) {    /* the per-pair counts live on the device: the slot size decides */
+        c->err = "match: the slot size (drfe_orb_max_keypoints = " + std::to_string(c->maxKp) +
+                 ") exceeds the 4096 map points the consecutive matcher resolves per pair";
+        return DRFE_ERR_CAPACITY;
+    }
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     /* pairs + poses staged in pinned memory the context owns: the call returns without waiting for the stream */
@@ -471,6 +476,10 @@ int drfe_search_by_projection_last(drfe_ctx* c, int cur_slot, int last_slot, con
     HIPCHK(c, hipMemcpy(&counts[0], c->d_kpCount + cur_slot, sizeof(int), hipMemcpyDeviceToHost));
     HIPCHK(c, hipMemcpy(&counts[1], c->d_kpCount + last_slot, sizeof(int), hipMemcpyDeviceToHost));
     if (n_cur != counts[0] || n_last != counts[1]) { c->err = "search_by_projection_last: N mismatch"; return DRFE_ERR_INVALID; }
+    if (n_last > DRFE_MATCH_LAST_MAX_QUERIES) {
+        c->err = "search_by_projection_last: more than 4096 map points in the last frame";
+        return DRFE_ERR_CAPACITY;
+    }
     MatchBuffers* m = drfe_match_buffers(c);
     if (!m) return DRFE_ERR_HIP;
     MatchPair P;

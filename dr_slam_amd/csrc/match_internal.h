@@ -3,6 +3,9 @@
 #define DRFE_MATCH_INTERNAL_H
 #include "drfe_internal.h"
 
+/* map points one SearchByProjection(Cur, Last) resolves: k_resolve_last holds them in registers, RS_THREADS x RS_MAX_T */
+#define DRFE_MATCH_LAST_MAX_QUERIES 4096
+
 /* one matcher invocation: queries (map points) against the keypoints of slot `curSlot` */
 struct MatchPair {
     int curSlot, lastSlot;

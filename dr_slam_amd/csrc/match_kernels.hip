@@ -471,6 +471,7 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) { return drfe_wave_
                                                      at once, which it waits for while other batches' kernels fill the device (1.6 ms per launch with three
                                                      batches in flight against 0.09 alone); 512 x 8 is faster alone too (match stage 0.229 -> 0.209 ms) and
                                                      gave +3 % on the step, 256 x 16 the same step but 0.239 ms alone */
+static_assert(RS_THREADS * RS_MAX_T == DRFE_MATCH_LAST_MAX_QUERIES, "the C-ABI checks this limit before launching");
 __global__ __launch_bounds__(RS_THREADS) void k_resolve_last(const MatchPair* __restrict__ pairs,
                                                              const MatchQuery* __restrict__ queries,
                                                              const drfe_keypoint* __restrict__ kps,

@@ -235,6 +235,8 @@ typedef struct drfe_map_point {
  * NULL) / results kept in ctx: per slot s, int32[max_keypoints]: index of the last-frame keypoint
  * matched to current keypoint i, or -1.  nnratio unused by this overload (no ratio test in the
  * reference); check_ori = mbCheckOrientation. */
+/* DRFE_ERR_CAPACITY when a slot can hold more than 4096 keypoints (nfeatures > 4064 at 8 levels): one pair's map points
+ * must fit the claim resolution.  drfe_search_by_projection_last has the same limit on n_last. */
 int drfe_match_consecutive_batch(drfe_ctx* ctx, const float* Tcw, const float* Twc, const drfe_camera* cam,
                                  float th, int mono, int check_ori, int nframes, void* stream);
 int drfe_match_download(drfe_ctx* ctx, int slot, int32_t* cur_to_last, int cap, int* nmatches);
