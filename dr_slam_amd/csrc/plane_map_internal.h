@@ -1,0 +1,84 @@
+/* plane_map_internal.h — the device-resident plane maps shared by plane association (plane_match.cpp) and map upkeep
+ * (map_plane.cpp).  Map plane j of all maps owns the arena points [beg[j], beg[j] + cnt[j]) inside its slot of cap[j] points;
+ * the host keeps the exact count of every plane (updates report it back), so the association batch sizes its work list from
+ * it.  DESIGN.md sections 12 and 13. */
+#ifndef DRFE_PLANE_MAP_INTERNAL_H
+#define DRFE_PLANE_MAP_INTERNAL_H
+
+#include "post_internal.h"
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#define HIPCHK(c, call)                                                                         \
+    do {                                                                                        \
+        hipError_t e__ = (call);                                                                \
+        if (e__ != hipSuccess) {                                                                \
+            (c)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
+            return DRFE_ERR_HIP;                                                                \
+        }                                                                                       \
+    } while (0)
+
+struct DevBuf {                     /* grow-only device (or pinned host) allocation */
+    void* p = nullptr;
+    size_t cap = 0;
+};
+
+static inline int drfe_pm_grow(drfe_ctx* c, DevBuf& b, size_t bytes, bool pinned = false)
+{
+    bytes = std::max<size_t>(bytes, 16);
+    if (b.cap >= bytes && b.p) return DRFE_OK;
+    if (b.p) (void)(pinned ? hipHostFree(b.p) : hipFree(b.p));
+    b.p = nullptr;
+    b.cap = 0;
+    if (pinned) HIPCHK(c, hipHostMalloc(&b.p, bytes, 0));
+    else HIPCHK(c, hipMalloc(&b.p, bytes));
+    b.cap = bytes;
+    return DRFE_OK;
+}
+
+static inline size_t drfe_align16(size_t n) { return (n + 15) & ~(size_t)15; }
+
+struct PmBuffers {
+    /* the resident maps: per plane coefficients, bad flag and the slot of its cloud in the arena (device copies of the host
+     * mirrors below; cloudEnd is also written by the update's commit kernel) */
+    DevBuf mapCoefs, mapBad, cloudBeg, cloudEnd, cloud, points;
+    std::vector<int32_t> planeOff, pointOff;
+    std::vector<float> coefsH;
+    std::vector<uint8_t> badH;
+    std::vector<int32_t> begH, cntH, capH;
+    std::vector<int64_t> mapChunks;   /* work items of one frame plane against all planes of map s */
+    int maps = 0;
+    /* one batch: the packed inputs / index outputs (io), the pair arrays, the work list, the accumulators, the flags */
+    DevBuf io, hio, angle, key, work, acc, flags;
+    hipEvent_t staged = nullptr, done = nullptr;
+    int frames = 0, planes = 0, flagged = 0;
+    std::vector<int32_t> frameOff, frameMap;
+    size_t offMap = 0, offPar = 0, offVer = 0;   /* byte offsets of the three index outputs in io */
+    /* map upkeep (map_plane.cpp): frame clouds of a call, one round's staging, gather input and voxel-grid scratch */
+    DevBuf upSrc, upPose, upRec, upHost, upIn, upOut, upRecs, upTmp, upPosL, upPosR, upList, upCounts, upMove;
+    int64_t upStats[4] = {0, 0, 0, 0};   /* voxel jobs on the device, jobs redone on the host, rounds, arena repacks */
+};
+
+/* Map upkeep launches (map_plane_kernels.hip).  A segment is one piece of a voxel job's input: `n` points written to
+ * in[dst, dst + n), read from src[src ..] and moved into world by pose `pose` (MP_SEG_FRAME: the frame form's Tcw,
+ * MP_SEG_KEYFRAME: the observation form's Twc), or copied from the arena (MP_SEG_RESIDENT). */
+enum { MP_SEG_FRAME = 0, MP_SEG_KEYFRAME = 1, MP_SEG_RESIDENT = 2 };
+struct MpSeg { int32_t form, pose, src, n, dst, pad[3]; };
+/* a round's job: voxel counts[k] centroids of in / out offset inOff go to arena[dstBeg ..] of plane `plane` (cap = its slot) */
+struct MpCommit { int32_t plane, inOff, dstBeg, cap; };
+hipError_t drfe_launch_map_plane_gather(const MpSeg* segs, int nseg, int maxN, const float* poses, const float* src,
+                                        const float* arena, float* in, hipStream_t s);
+hipError_t drfe_launch_map_plane_commit(const MpCommit* jobs, int njobs, int maxN, const int* counts, const float* out, float* arena,
+                                        int32_t* cloudEnd, hipStream_t s);
+/* moves[k] = (old begin, new begin, points) of plane k */
+hipError_t drfe_launch_map_plane_move(const int4* moves, int nplanes, int maxN, const float* from, float* to, hipStream_t s);
+
+/* per-plane arrays and work-list sizes from the host mirrors (after an upload, an edit or an update) */
+int drfe_pm_push_planes(drfe_ctx* c, PmBuffers* b);
+/* the match batch's work-list sizes (mapChunks) from the host's cloud sizes */
+void drfe_pm_chunks(PmBuffers* b);
+void drfe_pm_free_upkeep(PmBuffers* b);
+
+#endif

@@ -2,7 +2,7 @@
  * src/PlaneMatcher.cpp:11-226; Map::FlagMatchedPlanePoints, src/Map.cc:406-431) behind the C-ABI of include/drfe.h: the
  * single-frame host entries, the device-resident maps and the batch entry over them (plane_match_kernels.hip).  Both sides
  * evaluate plane_match_core.h; DESIGN.md section 12. */
-#include "post_internal.h"
+#include "plane_map_internal.h"
 #include "plane_match_core.h"
 
 #include <algorithm>
@@ -10,50 +10,7 @@
 #include <string>
 #include <vector>
 
-#define HIPCHK(c, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
-            return DRFE_ERR_HIP;                                                                \
-        }                                                                                       \
-    } while (0)
-
 namespace {
-
-struct DevBuf {                     /* grow-only device (or pinned host) allocation */
-    void* p = nullptr;
-    size_t cap = 0;
-};
-
-int grow(drfe_ctx* c, DevBuf& b, size_t bytes, bool pinned = false)
-{
-    bytes = std::max<size_t>(bytes, 16);
-    if (b.cap >= bytes && b.p) return DRFE_OK;
-    if (b.p) (void)(pinned ? hipHostFree(b.p) : hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-    if (pinned) HIPCHK(c, hipHostMalloc(&b.p, bytes, 0));
-    else HIPCHK(c, hipMalloc(&b.p, bytes));
-    b.cap = bytes;
-    return DRFE_OK;
-}
-
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-struct PmBuffers {
-    /* the uploaded maps (drfe_plane_map_upload): device copies and the host's view of their shape */
-    DevBuf mapCoefs, mapBad, cloudOff, cloud, points;
-    std::vector<int32_t> planeOff, pointOff, cloudOffH;
-    std::vector<int64_t> mapChunks;  /* work items of one frame plane against all planes of map s */
-    int maps = 0;
-    /* one batch: the packed inputs / index outputs (io), the pair arrays, the work list, the accumulators, the flags */
-    DevBuf io, hio, angle, key, work, acc, flags;
-    hipEvent_t staged = nullptr, done = nullptr;
-    int frames = 0, planes = 0, flagged = 0;
-    std::vector<int32_t> frameOff;
-    size_t offMap = 0, offPar = 0, offVer = 0;   /* byte offsets of the three index outputs in io */
-};
 
 bool offsets_ok(const int32_t* off, int n, int64_t total_cap = -1)
 {
@@ -71,8 +28,9 @@ void drfe_plane_match_free(drfe_ctx* c)
     if (!b) return;
     if (b->staged) (void)hipEventSynchronize(b->staged);
     if (b->done) (void)hipEventSynchronize(b->done);
-    DevBuf* dev[] = {&b->mapCoefs, &b->mapBad, &b->cloudOff, &b->cloud, &b->points, &b->io, &b->angle, &b->key, &b->work,
-                     &b->acc, &b->flags};
+    drfe_pm_free_upkeep(b);
+    DevBuf* dev[] = {&b->mapCoefs, &b->mapBad, &b->cloudBeg, &b->cloudEnd, &b->cloud, &b->points, &b->io, &b->angle, &b->key,
+                     &b->work, &b->acc, &b->flags};
     for (DevBuf* d : dev)
         if (d->p) (void)hipFree(d->p);
     if (b->hio.p) (void)hipHostFree(b->hio.p);
@@ -186,27 +144,20 @@ int drfe_plane_map_upload(drfe_ctx* c, int n_maps, const int32_t* plane_offsets,
     if (!b) { b = new PmBuffers(); c->pm = b; }
     if (b->done) HIPCHK(c, hipEventSynchronize(b->done));      /* a batch may still read the previous maps */
     int rc;
-    if ((rc = grow(c, b->mapCoefs, (size_t)nPlanes * 16)) || (rc = grow(c, b->mapBad, (size_t)nPlanes)) ||
-        (rc = grow(c, b->cloudOff, ((size_t)nPlanes + 1) * 4)) || (rc = grow(c, b->cloud, nCloud * 12)) ||
-        (rc = grow(c, b->points, nPoints * 12)))
-        return rc;
-    std::vector<int32_t> coff((size_t)nPlanes + 1, 0);
-    if (nPlanes > 0) std::memcpy(coff.data(), cloud_offsets, coff.size() * 4);
-    if (nPlanes > 0) {
-        HIPCHK(c, hipMemcpy(b->mapCoefs.p, map_coefs, (size_t)nPlanes * 16, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(b->mapBad.p, map_bad, (size_t)nPlanes, hipMemcpyHostToDevice));
-    }
-    HIPCHK(c, hipMemcpy(b->cloudOff.p, coff.data(), coff.size() * 4, hipMemcpyHostToDevice));
+    if ((rc = drfe_pm_grow(c, b->cloud, nCloud * 12)) || (rc = drfe_pm_grow(c, b->points, nPoints * 12))) return rc;
     if (nCloud) HIPCHK(c, hipMemcpy(b->cloud.p, cloud_xyz, nCloud * 12, hipMemcpyHostToDevice));
     if (nPoints) HIPCHK(c, hipMemcpy(b->points.p, points_xyz, nPoints * 12, hipMemcpyHostToDevice));
     b->maps = n_maps;
     b->planeOff.assign(plane_offsets, plane_offsets + n_maps + 1);
     b->pointOff.assign(point_offsets, point_offsets + n_maps + 1);
-    b->cloudOffH.swap(coff);
-    b->mapChunks.assign(n_maps, 0);
-    for (int s = 0; s < n_maps; s++)
-        for (int j = plane_offsets[s]; j < plane_offsets[s + 1]; j++)
-            b->mapChunks[s] += (b->cloudOffH[j + 1] - b->cloudOffH[j] + PM_CHUNK - 1) / PM_CHUNK;
+    b->coefsH.assign(map_coefs, map_coefs + 4 * (size_t)nPlanes);
+    b->badH.assign(map_bad, map_bad + nPlanes);
+    b->begH.assign(cloud_offsets, cloud_offsets + nPlanes);       /* the uploaded CSR becomes the first slot layout */
+    b->cntH.resize(nPlanes);
+    for (int j = 0; j < nPlanes; j++) b->cntH[j] = cloud_offsets[j + 1] - cloud_offsets[j];
+    b->capH = b->cntH;
+    std::fill(b->upStats, b->upStats + 4, 0);
+    if ((rc = drfe_pm_push_planes(c, b))) return rc;
     b->frames = 0;                    /* results of an earlier batch referred to the previous maps */
     return DRFE_OK;
 }
@@ -240,18 +191,18 @@ int drfe_plane_match_batch(drfe_ctx* c, const drfe_plane_match_params* params, i
     }
     /* packed inputs: Tcw [F x 16], coefs [Q x 4], per frame plane (frame, map, first pair) + pair total, the maps' plane and
      * point offsets, then the three index arrays (priors in, results out) */
-    const size_t oT = 0, oC = align16(oT + (size_t)nframes * 64), oQ = align16(oC + (size_t)Q * 16),
-                 oO = align16(oQ + ((size_t)Q * 3 + 1) * 4), oMap = align16(oO + ((size_t)b->maps + 1) * 8),
-                 oPar = align16(oMap + (size_t)Q * 4), oVer = align16(oPar + (size_t)Q * 4), oEnd = align16(oVer + (size_t)Q * 4);
+    const size_t oT = 0, oC = drfe_align16(oT + (size_t)nframes * 64), oQ = drfe_align16(oC + (size_t)Q * 16),
+                 oO = drfe_align16(oQ + ((size_t)Q * 3 + 1) * 4), oMap = drfe_align16(oO + ((size_t)b->maps + 1) * 8),
+                 oPar = drfe_align16(oMap + (size_t)Q * 4), oVer = drfe_align16(oPar + (size_t)Q * 4), oEnd = drfe_align16(oVer + (size_t)Q * 4);
     HIPCHK(c, hipSetDevice(c->device));
     if (!b->staged) HIPCHK(c, hipEventCreateWithFlags(&b->staged, hipEventDisableTiming));
     if (!b->done) HIPCHK(c, hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
     HIPCHK(c, hipEventSynchronize(b->staged));          /* the previous batch's staging is free again */
     const size_t nPoints = (size_t)b->pointOff[b->maps];
     int rc;
-    if ((rc = grow(c, b->hio, oEnd, true)) || (rc = grow(c, b->io, oEnd)) || (rc = grow(c, b->angle, (size_t)pairs * 4)) ||
-        (rc = grow(c, b->key, (size_t)pairs * 4)) || (rc = grow(c, b->work, (size_t)workCap * sizeof(int4))) ||
-        (rc = grow(c, b->acc, (4 + 2 * (size_t)nframes) * 4)) || (rc = grow(c, b->flags, nPoints)))
+    if ((rc = drfe_pm_grow(c, b->hio, oEnd, true)) || (rc = drfe_pm_grow(c, b->io, oEnd)) || (rc = drfe_pm_grow(c, b->angle, (size_t)pairs * 4)) ||
+        (rc = drfe_pm_grow(c, b->key, (size_t)pairs * 4)) || (rc = drfe_pm_grow(c, b->work, (size_t)workCap * sizeof(int4))) ||
+        (rc = drfe_pm_grow(c, b->acc, (4 + 2 * (size_t)nframes) * 4)) || (rc = drfe_pm_grow(c, b->flags, nPoints)))
         return rc;
     char* h = static_cast<char*>(b->hio.p);
     std::memcpy(h + oT, Tcw, (size_t)nframes * 64);
@@ -297,7 +248,8 @@ int drfe_plane_match_batch(drfe_ctx* c, const drfe_plane_match_params* params, i
     L.pointOff = L.planeOff + b->maps + 1;
     L.mapCoefs = (const float*)b->mapCoefs.p;
     L.mapBad = (const uint8_t*)b->mapBad.p;
-    L.cloudOff = (const int32_t*)b->cloudOff.p;
+    L.cloudBeg = (const int32_t*)b->cloudBeg.p;
+    L.cloudEnd = (const int32_t*)b->cloudEnd.p;
     L.cloud = (const float*)b->cloud.p;
     L.points = (const float*)b->points.p;
     L.angle = (float*)b->angle.p;
@@ -319,6 +271,7 @@ int drfe_plane_match_batch(drfe_ctx* c, const drfe_plane_match_params* params, i
     b->planes = Q;
     b->flagged = flag_points != 0;
     b->frameOff.assign(plane_offsets, plane_offsets + nframes + 1);
+    b->frameMap.assign(frame_map, frame_map + nframes);
     b->offMap = oMap; b->offPar = oPar; b->offVer = oVer;
     return DRFE_OK;
 }

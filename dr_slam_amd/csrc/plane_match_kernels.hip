@@ -33,7 +33,7 @@ __global__ __launch_bounds__(PM_THREADS) void k_pm_gate(PmLaunch L)
         const float a = pm_angle(pM, L.mapCoefs + 4 * (size_t)gj);
         L.angle[pr + j] = a;
         if (L.mapBad[gj] || !pm_gate(a, L.params.aTh)) continue;
-        const int nch = (L.cloudOff[gj + 1] - L.cloudOff[gj] + PM_CHUNK - 1) / PM_CHUNK;
+        const int nch = (L.cloudEnd[gj] - L.cloudBeg[gj] + PM_CHUNK - 1) / PM_CHUNK;
         if (nch == 0) continue;
         const uint32_t base = atomicAdd(L.counter, (uint32_t)nch);
         for (int c = 0; c < nch; c++)
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(PM_THREADS) void k_pm_dist(PmLaunch L)
         const int4 w = L.work[it];
         float pM[4];
         pm_world_coef(L.Tcw + 16 * (size_t)L.qFrame[w.x], L.coefs + 4 * (size_t)w.x, pM);
-        const int lo = L.cloudOff[w.y] + w.w * PM_CHUNK, hi = min(lo + PM_CHUNK, L.cloudOff[w.y + 1]);
+        const int lo = L.cloudBeg[w.y] + w.w * PM_CHUNK, hi = min(lo + PM_CHUNK, L.cloudEnd[w.y]);
         uint32_t k = PM_NO_DISTANCE_BITS;
         for (int p = lo + (int)threadIdx.x; p < hi; p += PM_THREADS) {
             const float* xyz = L.cloud + 3 * (size_t)p;

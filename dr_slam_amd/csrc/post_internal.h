@@ -33,7 +33,7 @@ void drfe_manhattan_free(drfe_ctx* c);
 /* Plane association of a batch of frames against device-resident maps (plane_match_kernels.hip, driven by plane_match.cpp).
  * Frame plane q (of Q) belongs to frame qFrame[q] and map qMap[q]; its pairs with the map's planes are angle / key
  * [qPair[q], qPair[q] + planes of the map).  Map s owns planes [planeOff[s], planeOff[s + 1]) and points
- * [pointOff[s], pointOff[s + 1]).  Expects key memset to 0xFF, counter / nmatches / npairs to 0 and (flagPoints) flags to 0. */
+ * [pointOff[s], pointOff[s + 1]).  workCap bounds the chunks of the gated clouds (the host's exact cloud sizes).  Expects key memset to 0xFF, counter / nmatches / npairs to 0 and (flagPoints) flags to 0. */
 #define PM_CHUNK 2048             /* cloud points per work item of the distance pass (256 lanes x 8) */
 #define PM_FLAG_POINTS 2048       /* map points per workgroup of the flag sweep */
 struct PmLaunch {
@@ -42,7 +42,7 @@ struct PmLaunch {
     int32_t *mapOut, *parOut, *verOut;
     const float* mapCoefs;
     const uint8_t* mapBad;
-    const int32_t* cloudOff;
+    const int32_t *cloudBeg, *cloudEnd;     /* map plane j's cloud: cloud points [cloudBeg[j], cloudEnd[j]) */
     const float *cloud, *points;
     float* angle;
     uint32_t* key;

@@ -44,6 +44,8 @@ SYMBOLS = (
     "drfe_manhattan_track_host", "drfe_manhattan_track_batch", "drfe_manhattan_download", "drfe_debug_manhattan_math",
     "drfe_plane_match_host", "drfe_plane_flag_points_host", "drfe_plane_match_status_host", "drfe_plane_map_upload",
     "drfe_plane_match_batch", "drfe_plane_match_download", "drfe_plane_flags_download",
+    "drfe_map_plane_update_host", "drfe_map_plane_rebuild_host", "drfe_plane_map_update_batch", "drfe_plane_map_rebuild_batch",
+    "drfe_plane_map_edit", "drfe_plane_map_cloud_download", "drfe_plane_map_update_stats",
 )
 
 FRUSTUM_POINT_DTYPE = np.dtype([("world", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"),
@@ -224,6 +226,13 @@ def load() -> C.CDLL:
     L.drfe_plane_match_batch.argtypes = [vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, vp]
     L.drfe_plane_match_download.argtypes = [vp, i32, vp, vp, vp, C.POINTER(i32), C.POINTER(i32)]
     L.drfe_plane_flags_download.argtypes = [vp, i32, vp]
+    L.drfe_map_plane_update_host.argtypes = [vp, vp, i32, vp, i32, vp, i32, C.POINTER(i32)]
+    L.drfe_map_plane_rebuild_host.argtypes = [i32, vp, vp, vp, vp, i32, C.POINTER(i32)]
+    L.drfe_plane_map_update_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.drfe_plane_map_rebuild_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.drfe_plane_map_edit.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.drfe_plane_map_cloud_download.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32)]
+    L.drfe_plane_map_update_stats.argtypes = [vp, vp]
     L.drfe_lsd_segments_host.argtypes = [vp, vp, vp, i32, i32, f64, vp, i32, C.POINTER(i32)]
     L.drfe_lsd_configure.argtypes = [vp, i32]
     L.drfe_lsd_configure_rect.argtypes = [vp, i32]
@@ -413,6 +422,36 @@ def plane_match_status_host(Tcw, coefs, matched_coefs, matched, mf_contrast, Rwc
     if rc != 0:
         raise DrfeError(f"drfe_plane_match_status_host failed ({rc})")
     return bool(st.value)
+
+
+def map_plane_update_host(Tcw, frame_xyz, map_xyz):
+    """MapPlane::UpdateCoefficientsAndPoints(F, i) (host entry): VoxelGrid(0.05) of frame_xyz [n, 3] moved into world by
+    Isometry3d(toSE3Quat(Tcw)).inverse(), followed by the plane's cloud map_xyz [m, 3].  Returns the new cloud [k, 3]."""
+    L = load()
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+    fx = np.ascontiguousarray(frame_xyz, np.float32).reshape(-1, 3)
+    mx = np.ascontiguousarray(map_xyz, np.float32).reshape(-1, 3)
+    out = np.zeros((len(fx) + len(mx), 3), np.float32)
+    n = C.c_int()
+    rc = L.drfe_map_plane_update_host(_p(T), _p(fx), len(fx), _p(mx), len(mx), _p(out), len(out), C.byref(n))
+    if rc != 0:
+        raise DrfeError(f"drfe_map_plane_update_host failed ({rc})")
+    return out[:n.value].copy()
+
+
+def map_plane_rebuild_host(Twc, clouds):
+    """MapPlane::UpdateCoefficientsAndPoints() (host entry): VoxelGrid(0.05) of the observations' clouds (list of [n, 3]) moved
+    by their Twc (list of 4x4, widened element by element), concatenated in the order given.  Returns the new cloud [k, 3]."""
+    L = load()
+    T = np.ascontiguousarray(np.asarray(Twc, np.float32).reshape(-1, 16), np.float32)
+    off, xyz = _clouds_csr(clouds)
+    assert len(T) == len(clouds)
+    out = np.zeros((max(len(xyz), 1), 3), np.float32)
+    n = C.c_int()
+    rc = L.drfe_map_plane_rebuild_host(len(clouds), _p(T), _p(off), _p(xyz), _p(out), len(xyz), C.byref(n))
+    if rc != 0:
+        raise DrfeError(f"drfe_map_plane_rebuild_host failed ({rc})")
+    return out[:n.value].copy()
 
 
 def manhattan_math(which, x):
@@ -1437,6 +1476,56 @@ class Context:
         out = np.zeros(max(self._plane_points[map_id], 1), np.uint8)
         self._chk(self.L.drfe_plane_flags_download(self.h, map_id, _p(out)), "drfe_plane_flags_download")
         return out[:self._plane_points[map_id]]
+
+    def plane_map_update_batch(self, frame_map, Tcw, clouds, map_idx=None, stream: int = 0):
+        """MapPlane::UpdateCoefficientsAndPoints(F, i) on the resident maps: frame f (Tcw [F, 4, 4], clouds[f] = list of its
+        planes' voxel clouds [n, 3]) updates the planes of map frame_map[f] named by map_idx[f] (plane-local, -1 = none);
+        map_idx None = the decisions of the most recent plane_match_batch over the same frames."""
+        F = len(frame_map)
+        fm = np.ascontiguousarray(frame_map, np.int32)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(F, 16)
+        off = np.zeros(F + 1, np.int32)
+        off[1:] = np.cumsum([len(c) for c in clouds])
+        coff, xyz = _clouds_csr([p for c in clouds for p in c])
+        mi = None if map_idx is None else np.ascontiguousarray(
+            np.concatenate([_priors(map_idx[f], off[f + 1] - off[f]) for f in range(F)]) if off[-1] else np.zeros(0), np.int32)
+        self._chk(self.L.drfe_plane_map_update_batch(self.h, F, _p(fm), _p(T), _p(off), _p(coff), _p(xyz), _p(mi), C.c_void_p(stream)),
+                  "drfe_plane_map_update_batch")
+
+    def plane_map_rebuild_batch(self, jobs, stream: int = 0):
+        """MapPlane::UpdateCoefficientsAndPoints() on the resident maps: jobs = list of (map, plane, observations), each
+        observation a (Twc 4x4, cloud [n, 3]) pair in the order the caller iterates them"""
+        jm = np.ascontiguousarray([j[0] for j in jobs], np.int32)
+        jp = np.ascontiguousarray([j[1] for j in jobs], np.int32)
+        ooff = np.zeros(len(jobs) + 1, np.int32)
+        ooff[1:] = np.cumsum([len(j[2]) for j in jobs])
+        obs = [o for j in jobs for o in j[2]]
+        T = np.ascontiguousarray(np.asarray([o[0] for o in obs], np.float32).reshape(-1, 16), np.float32)
+        coff, xyz = _clouds_csr([o[1] for o in obs])
+        self._chk(self.L.drfe_plane_map_rebuild_batch(self.h, len(jobs), _p(jm), _p(jp), _p(ooff), _p(T), _p(coff), _p(xyz),
+                                                      C.c_void_p(stream)), "drfe_plane_map_rebuild_batch")
+
+    def plane_map_edit(self, map_id: int, plane_index, coefs=None, bad=None):
+        """SetWorldPos / SetBadFlag of existing planes; an index equal to the plane count appends a plane with an empty cloud"""
+        pi = np.ascontiguousarray(plane_index, np.int32).reshape(-1)
+        cf = None if coefs is None else np.ascontiguousarray(coefs, np.float32).reshape(len(pi), 4)
+        bd = None if bad is None else np.ascontiguousarray(bad, np.uint8).reshape(len(pi))
+        self._chk(self.L.drfe_plane_map_edit(self.h, map_id, len(pi), _p(pi), _p(cf), _p(bd)), "drfe_plane_map_edit")
+
+    def plane_map_cloud_download(self, map_id: int, plane: int):
+        """the current cloud [n, 3] of one resident map plane"""
+        n = C.c_int()
+        self._chk(self.L.drfe_plane_map_cloud_download(self.h, map_id, plane, None, 0, C.byref(n)), "drfe_plane_map_cloud_download")
+        out = np.zeros((max(n.value, 1), 3), np.float32)
+        self._chk(self.L.drfe_plane_map_cloud_download(self.h, map_id, plane, _p(out), n.value, C.byref(n)),
+                  "drfe_plane_map_cloud_download")
+        return out[:n.value].copy()
+
+    def plane_map_update_stats(self):
+        """dict(device_jobs, host_jobs, rounds, repacks) since plane_map_upload"""
+        st = np.zeros(4, np.int64)
+        self._chk(self.L.drfe_plane_map_update_stats(self.h, _p(st)), "drfe_plane_map_update_stats")
+        return dict(zip(("device_jobs", "host_jobs", "rounds", "repacks"), st.tolist()))
 
     # --- measurement -------------------------------------------------------------------------------
     def profile_enable(self, on=True):

@@ -883,6 +883,48 @@ int drfe_plane_match_download(drfe_ctx* ctx, int frame, int32_t* map_idx, int32_
  * that map in the call (0 everywhere for a map no frame used); one byte per map point (synchronises). */
 int drfe_plane_flags_download(drfe_ctx* ctx, int map, uint8_t* flags);
 
+/* MapPlane::UpdateCoefficientsAndPoints (src/MapPlane.cc:298-371): a map plane's cloud (mvPlanePoints, xyz floats) becomes
+ * pcl::VoxelGrid(0.05) of new points followed by its current cloud, or of its keyframe observations alone.  The SAC
+ * segmentation the reference runs afterwards writes only locals and has no counterpart.  DESIGN.md section 13.
+ *
+ * Per-frame form (pMP->UpdateCoefficientsAndPoints(F, i)), on the host: frame_xyz (n_frame points, F.mvPlanePoints[i]) moved
+ * into world by Isometry3d(Converter::toSE3Quat(Tcw)).inverse() - the rotation's quaternion round trip, not the plain
+ * transpose - then map_xyz (n_map points, the plane's cloud) after them, then the voxel grid.  *n_out = the output's points;
+ * DRFE_ERR_CAPACITY when that exceeds cap (n_frame + n_map always suffices). */
+int drfe_map_plane_update_host(const float* Tcw, const float* frame_xyz, int n_frame, const float* map_xyz, int n_map, float* out_xyz,
+                               int cap, int* n_out);
+/* Observation form (pMP->UpdateCoefficientsAndPoints()), on the host: for each of n_obs observations (KF, idx) in the order
+ * given (the reference iterates GetObservations(), a std::map keyed by KeyFrame*), the cloud KF->mvPlanePoints[idx] = points
+ * [obs_cloud_offsets[o], obs_cloud_offsets[o + 1]) of obs_xyz moved by Twc + 16 o (KF->GetPoseInverse(), widened element by
+ * element), concatenated, then the voxel grid. */
+int drfe_map_plane_rebuild_host(int n_obs, const float* Twc, const int32_t* obs_cloud_offsets, const float* obs_xyz, float* out_xyz,
+                                int cap, int* n_out);
+/* The per-frame form on the resident maps of drfe_plane_map_upload: frame f (pose Tcw + 16 f, planes [plane_offsets[f],
+ * plane_offsets[f + 1]), frame plane q's cloud = points [cloud_offsets[q], cloud_offsets[q + 1]) of cloud_xyz) updates the
+ * planes of map frame_map[f] that map_idx[q] names (plane-local, -1 = none; the reference's test is mvpMapPlanes[i] != NULL,
+ * priors included, isBad() not read).  map_idx NULL = the decisions of the most recent drfe_plane_match_batch, which must have
+ * had the same frame_map and plane_offsets (DRFE_ERR_STATE otherwise).  Updates of one map plane apply in call order (frame,
+ * then frame plane); clouds grow without bound on the device.  Host inputs, `stream` as drfe_plane_match_batch; the call
+ * returns once the clouds are updated (it reads each round's voxel counts back, 4 bytes per update). */
+int drfe_plane_map_update_batch(drfe_ctx* ctx, int nframes, const int32_t* frame_map, const float* Tcw, const int32_t* plane_offsets,
+                                const int32_t* cloud_offsets, const float* cloud_xyz, const int32_t* map_idx, void* stream);
+/* The observation form on the resident maps: job k replaces the cloud of plane job_plane[k] of map job_map[k] with the voxel
+ * grid of its observations [obs_offsets[k], obs_offsets[k + 1]) (pose Twc + 16 o, cloud [cloud_offsets[o], cloud_offsets[o + 1])
+ * of cloud_xyz), in the order given.  Same stream and return rules as drfe_plane_map_update_batch. */
+int drfe_plane_map_rebuild_batch(drfe_ctx* ctx, int njobs, const int32_t* job_map, const int32_t* job_plane, const int32_t* obs_offsets,
+                                 const float* Twc, const int32_t* cloud_offsets, const float* cloud_xyz, void* stream);
+/* Edits n planes of resident map `map`: plane_index[k] < the map's plane count sets that plane's coefficients (coefs + 4 k,
+ * MapPlane::SetWorldPos; coefs may be NULL) and bad flag (bad[k], SetBadFlag; bad may be NULL); plane_index[k] == the count
+ * appends a plane (coefs required, bad NULL = 0) with an empty cloud, for drfe_plane_map_rebuild_batch to fill.  All-or-nothing
+ * validation; synchronises. */
+int drfe_plane_map_edit(drfe_ctx* ctx, int map, int n, const int32_t* plane_index, const float* coefs, const uint8_t* bad);
+/* The current cloud of plane `plane` of map `map` (synchronises): *n = its points; xyz NULL asks for the size only;
+ * DRFE_ERR_CAPACITY when *n > cap. */
+int drfe_plane_map_cloud_download(drfe_ctx* ctx, int map, int plane, float* xyz, int cap, int* n);
+/* Counters since drfe_plane_map_upload: stats[0] voxel jobs the device finished, [1] jobs redone on the host (grid overflow or
+ * the sort's heap-sort branch), [2] rounds, [3] arena repacks (clouds that outgrew their slots). */
+int drfe_plane_map_update_stats(drfe_ctx* ctx, int64_t* stats /* 4 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

@@ -11,6 +11,7 @@
  *   drfe::TrackManhattanFrame          src/Tracking.cc:1336          - Tracking's Manhattan-frame tracker (host entry)
  *   Planar_SLAM::PlaneMatcher          include/PlaneMatcher.h:10-31  - SearchMapByCoefficients and bMatchStatus (host entries)
  *   drfe::FlagMatchedPlanePoints       src/Map.cc:406-431            - Map::FlagMatchedPlanePoints (host entry)
+ *   drfe::UpdateCoefficientsAndPoints  src/MapPlane.cc:298-371       - both forms of MapPlane's cloud upkeep (host entries)
  * With -DDRFE_WITH_OPENCV the container types are OpenCV's (cv::Mat, cv::KeyPoint, cv::line_descriptor::KeyLine);
  * without it (this image has no OpenCV) minimal stand-ins with the same member names and memory layout are used, so the
  * header is compiled and exercised here (tests/native/adaptor_caller.cpp, run by tests/test_gpu_native.py).
@@ -1668,6 +1669,86 @@ inline int FlagMatchedPlanePoints(FrameT& pF, const MapPointSet& mspMapPoints, c
     for (size_t p = 0; p < pts.size(); p++)
         if (flags[p]) pts[p]->SetAssociatedWithPlaneFlag(true);
     return n;
+}
+
+/* MapPlane::UpdateCoefficientsAndPoints (src/MapPlane.cc:298-371) over drfe_map_plane_update_host / drfe_map_plane_rebuild_host:
+ * the map plane's mvPlanePoints is replaced by a new cloud of the same type (a smart pointer is reseated, so holders of the old
+ * cloud keep it, as in the reference; through a raw pointer the pointee is overwritten).  Reads
+ *   Frame:    mTcw (4x4 float), mvPlanePoints[id].points[k].x / y / z
+ *   KeyFrame: GetPoseInverse() (4x4 float), mvPlanePoints[idx].points
+ *   MapPlane: mvPlanePoints (pointer to a cloud with .points), GetObservations() (pairs (KeyFrame*, index), iterated in order)
+ * New points are value-initialised and get x / y / z; a PCL cloud also gets width = n, height = 1, is_dense.  The reference's
+ * SAC segmentation afterwards writes only locals and has no counterpart.  Call sites: DESIGN.md section 13, INTEGRATION.md. */
+namespace drfe_detail_mp {
+template <class M> inline void pose16(const M& m, float T[16])
+{
+    for (int r = 0; r < 4; r++)
+        for (int c = 0; c < 4; c++) T[r * 4 + c] = m.template ptr<float>(r)[c];
+}
+template <class CloudT> inline void append_xyz(const CloudT& cl, std::vector<float>& xyz)
+{
+    for (const auto& p : cl.points) {
+        xyz.push_back(p.x); xyz.push_back(p.y); xyz.push_back(p.z);
+    }
+}
+template <class C> inline auto set_shape(C& c, size_t n, int) -> decltype(c.width = 0, c.height = 0, c.is_dense = true, void())
+{
+    c.width = (decltype(c.width))n; c.height = 1; c.is_dense = true;
+}
+template <class C> inline void set_shape(C&, size_t, long) {}
+template <class C> inline void reseat(C*& p, C&& fresh) { *p = std::move(fresh); }
+template <class P, class C> inline void reseat(P& p, C&& fresh) { p = P(new C(std::move(fresh))); }
+template <class MapPlaneT> inline void replace_cloud(MapPlaneT& pMP, const std::vector<float>& xyz, int n)
+{
+    typedef typename std::remove_reference<decltype(*pMP.mvPlanePoints)>::type CloudT;
+    typedef typename std::decay<decltype(pMP.mvPlanePoints->points[0])>::type PointT;
+    CloudT fresh;
+    fresh.points.assign((size_t)n, PointT());
+    for (int k = 0; k < n; k++) {
+        fresh.points[k].x = xyz[3 * (size_t)k]; fresh.points[k].y = xyz[3 * (size_t)k + 1]; fresh.points[k].z = xyz[3 * (size_t)k + 2];
+    }
+    set_shape(fresh, (size_t)n, 0);
+    reseat(pMP.mvPlanePoints, std::move(fresh));
+}
+}  // namespace drfe_detail_mp
+
+/* pMP->UpdateCoefficientsAndPoints(F, id) (src/MapPlane.cc:336-371) */
+template <class MapPlaneT, class FrameT>
+inline void UpdateCoefficientsAndPoints(MapPlaneT& pMP, const FrameT& F, int id)
+{
+    float Tcw[16];
+    drfe_detail_mp::pose16(F.mTcw, Tcw);
+    std::vector<float> fx, mx;
+    drfe_detail_mp::append_xyz(F.mvPlanePoints[id], fx);
+    drfe_detail_mp::append_xyz(*pMP.mvPlanePoints, mx);
+    const int nf = (int)(fx.size() / 3), nm = (int)(mx.size() / 3);
+    std::vector<float> out(3 * ((size_t)nf + nm) + 3);
+    int n = 0;
+    if (drfe_map_plane_update_host(Tcw, fx.data(), nf, mx.data(), nm, out.data(), nf + nm, &n) != DRFE_OK)
+        throw std::runtime_error("drfe_map_plane_update_host failed");
+    drfe_detail_mp::replace_cloud(pMP, out, n);
+}
+
+/* pMP->UpdateCoefficientsAndPoints() (src/MapPlane.cc:298-334): the observations in GetObservations()'s iteration order */
+template <class MapPlaneT>
+inline void UpdateCoefficientsAndPoints(MapPlaneT& pMP)
+{
+    const auto observations = pMP.GetObservations();
+    std::vector<float> Twc, xyz;
+    std::vector<int32_t> off(1, 0);
+    for (const auto& ob : observations) {
+        float T[16];
+        drfe_detail_mp::pose16(ob.first->GetPoseInverse(), T);
+        Twc.insert(Twc.end(), T, T + 16);
+        drfe_detail_mp::append_xyz(ob.first->mvPlanePoints[ob.second], xyz);
+        off.push_back((int32_t)(xyz.size() / 3));
+    }
+    const int nobs = (int)off.size() - 1, total = off.back();
+    std::vector<float> out(3 * (size_t)total + 3);
+    int n = 0;
+    if (drfe_map_plane_rebuild_host(nobs, Twc.data(), off.data(), xyz.data(), out.data(), total, &n) != DRFE_OK)
+        throw std::runtime_error("drfe_map_plane_rebuild_host failed");
+    drfe_detail_mp::replace_cloud(pMP, out, n);
 }
 }  // namespace drfe
 
