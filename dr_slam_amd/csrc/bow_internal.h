@@ -16,14 +16,14 @@ struct VocDev {
 struct BowGroup { int kfBegin, kfEnd, fBegin, fEnd; };   /* one vocabulary node common to both FeatureVectors */
 
 struct BowState {
-    VocDev voc;
-    int scoring, weighting;
-    void* d_vocBlob[5];       /* owning pointers of the five arrays */
-    int* d_word; double* d_weight; int* d_nid;            /* [slot][maxKp] transform outputs */
-    int levelsup;
-    uint8_t* slotDone; int nSlots;                         /* [max_batch]: 1 = the slot's descriptors went through the transform (at `levelsup`) since they were last written */
-    BowGroup* d_groups; int* d_kfIdx; int* d_fIdx; int* d_kfMP; int* d_fMP; int* d_match; int* d_counters; int* d_hist;
-    uint16_t* d_entries;
+    VocDev voc = {};          /* views of the five arrays below */
+    int scoring = 0, weighting = 0;
+    DevBuf<uint8_t> d_vocDesc; DevBuf<double> d_vocWeight; DevBuf<int> d_vocWordId, d_vocChildBegin, d_vocChildren;
+    DevBuf<int> d_word; DevBuf<double> d_weight; DevBuf<int> d_nid;     /* [slot][maxKp] transform outputs */
+    int levelsup = 0;
+    uint8_t* slotDone = nullptr; int nSlots = 0;           /* [max_batch]: 1 = the slot's descriptors went through the transform (at `levelsup`) since they were last written */
+    DevBuf<BowGroup> d_groups; DevBuf<int> d_kfIdx, d_fIdx, d_kfMP, d_fMP, d_match, d_counters, d_hist;
+    DevBuf<uint16_t> d_entries;
 };
 
 hipError_t drfe_launch_bow_transform(drfe_ctx* c, const VocDev& voc, int levelsup, int nframes, int* d_word,

@@ -23,15 +23,6 @@ static const int8_t kPatternHost[1024] = {
 #include "../../include/drfe_orb_pattern.inc"
 };
 
-#define HIPCHK(c, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
-            return DRFE_ERR_HIP;                                                                \
-        }                                                                                       \
-    } while (0)
-
 template <class T>
 static hipError_t dalloc(T** p, size_t n)
 {
@@ -732,7 +723,7 @@ static void frame_lane_release_graph(FrameLane& L)
 
 void drfe_frame_lanes_free(drfe_ctx* c)
 {
-    auto* v = static_cast<std::vector<FrameLane>*>(c->frameLanes);
+    auto* v = c->frameLanes;
     if (!v) return;
     for (FrameLane& L : *v) {
         frame_lane_release_graph(L);
@@ -828,7 +819,7 @@ static int frame_submit_impl(drfe_ctx* c, int slot, const uint8_t* gray, int w, 
         if (!v) return DRFE_ERR_INVALID;
         c->frameLanes = v;
     }
-    FrameLane& L = (*static_cast<std::vector<FrameLane>*>(c->frameLanes))[(size_t)slot];
+    FrameLane& L = (*c->frameLanes)[(size_t)slot];
     if (L.pending) { c->err = "drfe_frame_submit: the slot's previous submission has not been collected"; return DRFE_ERR_STATE; }
     /* geometry tables first: an upload synchronises the device and invalidates every slot */
     int rc = upload_geometry(c, w, h);
@@ -918,7 +909,7 @@ int drfe_frame_collect(drfe_ctx* c, int slot, drfe_keypoint* kps, uint8_t* desc,
 {
     if (!c || !n_out) return DRFE_ERR_INVALID;
     *n_out = 0;
-    auto* v = static_cast<std::vector<FrameLane>*>(c->frameLanes);
+    auto* v = c->frameLanes;
     if (slot < 0 || slot >= c->cfg.max_batch || !v || !(*v)[(size_t)slot].pending) {
         c->err = "drfe_frame_collect: nothing submitted to this slot";
         return DRFE_ERR_STATE;
@@ -952,7 +943,7 @@ int drfe_frame_collect_tracked(drfe_ctx* c, int slot, drfe_keypoint* kps, uint8_
                                int* n_out, int32_t* cur_to_last, int* n_matches)
 {
     if (!c || !n_out || !n_matches) return DRFE_ERR_INVALID;
-    auto* v = static_cast<std::vector<FrameLane>*>(c->frameLanes);
+    auto* v = c->frameLanes;
     if (slot < 0 || slot >= c->cfg.max_batch || !v || !(*v)[(size_t)slot].pending || !(*v)[(size_t)slot].tracked) {
         c->err = "drfe_frame_collect_tracked: no tracked submission in this slot";
         return DRFE_ERR_STATE;

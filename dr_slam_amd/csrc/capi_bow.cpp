@@ -8,25 +8,10 @@
 #include <map>
 #include <new>
 
-#define HIPCHK(c, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
-            return DRFE_ERR_HIP;                                                                \
-        }                                                                                       \
-    } while (0)
-
 void drfe_bow_free(drfe_ctx* c)
 {
     BowState* b = c->bow;
     if (!b) return;
-    for (void* p : b->d_vocBlob)
-        if (p) (void)hipFree(p);
-    void* ptrs[] = {b->d_word, b->d_weight, b->d_nid, b->d_groups, b->d_kfIdx, b->d_fIdx, b->d_kfMP, b->d_fMP, b->d_match,
-                    b->d_counters, b->d_hist, b->d_entries};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
     delete[] b->slotDone;
     delete b;
     c->bow = nullptr;
@@ -53,7 +38,6 @@ int drfe_voc_upload(drfe_ctx* c, int k, int L, int scoring, int weighting, int n
     drfe_bow_free(c);
     BowState* b = new (std::nothrow) BowState();
     if (!b) return DRFE_ERR_INVALID;
-    std::memset(b, 0, sizeof(*b));
     c->bow = b;
     b->nSlots = c->cfg.max_batch;
     b->slotDone = new (std::nothrow) uint8_t[(size_t)b->nSlots]();
@@ -75,33 +59,33 @@ int drfe_voc_upload(drfe_ctx* c, int k, int L, int scoring, int weighting, int n
         if (is_leaf[i]) wordId[i] = nwords++;
     }
     const size_t n = (size_t)n_nodes;
-    uint8_t* d_desc; double* d_w; int *d_word, *d_cb, *d_ch;
-    HIPCHK(c, hipMalloc((void**)&d_desc, n * 32)); b->d_vocBlob[0] = d_desc;
-    HIPCHK(c, hipMalloc((void**)&d_w, n * 8)); b->d_vocBlob[1] = d_w;
-    HIPCHK(c, hipMalloc((void**)&d_word, n * 4)); b->d_vocBlob[2] = d_word;
-    HIPCHK(c, hipMalloc((void**)&d_cb, (n + 1) * 4)); b->d_vocBlob[3] = d_cb;
-    HIPCHK(c, hipMalloc((void**)&d_ch, n * 4)); b->d_vocBlob[4] = d_ch;
-    HIPCHK(c, hipMemcpy(d_desc, desc, n * 32, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_w, weight, n * 8, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_word, wordId.data(), n * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_cb, cnt.data(), (n + 1) * 4, hipMemcpyHostToDevice));
-    HIPCHK(c, hipMemcpy(d_ch, children.data(), (n - 1) * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, b->d_vocDesc.alloc(n * 32));
+    HIPCHK(c, b->d_vocWeight.alloc(n));
+    HIPCHK(c, b->d_vocWordId.alloc(n));
+    HIPCHK(c, b->d_vocChildBegin.alloc(n + 1));
+    HIPCHK(c, b->d_vocChildren.alloc(n));
+    HIPCHK(c, hipMemcpy(b->d_vocDesc, desc, n * 32, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(b->d_vocWeight, weight, n * 8, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(b->d_vocWordId, wordId.data(), n * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(b->d_vocChildBegin, cnt.data(), (n + 1) * 4, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(b->d_vocChildren, children.data(), (n - 1) * 4, hipMemcpyHostToDevice));
     b->voc.k = k; b->voc.L = L; b->voc.nNodes = n_nodes;
-    b->voc.desc = d_desc; b->voc.weight = d_w; b->voc.wordId = d_word; b->voc.childBegin = d_cb; b->voc.children = d_ch;
+    b->voc.desc = b->d_vocDesc; b->voc.weight = b->d_vocWeight; b->voc.wordId = b->d_vocWordId;
+    b->voc.childBegin = b->d_vocChildBegin; b->voc.children = b->d_vocChildren;
     b->scoring = scoring; b->weighting = weighting;
     const size_t B = (size_t)c->cfg.max_batch, M = (size_t)c->maxKp;
-    HIPCHK(c, hipMalloc((void**)&b->d_word, B * M * 4));
-    HIPCHK(c, hipMalloc((void**)&b->d_weight, B * M * 8));
-    HIPCHK(c, hipMalloc((void**)&b->d_nid, B * M * 4));
-    HIPCHK(c, hipMalloc((void**)&b->d_groups, M * sizeof(BowGroup)));
-    HIPCHK(c, hipMalloc((void**)&b->d_kfIdx, M * 4));
-    HIPCHK(c, hipMalloc((void**)&b->d_fIdx, M * 4));
-    HIPCHK(c, hipMalloc((void**)&b->d_kfMP, M * 4));
-    HIPCHK(c, hipMalloc((void**)&b->d_fMP, M * 4));
-    HIPCHK(c, hipMalloc((void**)&b->d_match, M * 4));
-    HIPCHK(c, hipMalloc((void**)&b->d_counters, 8));
-    HIPCHK(c, hipMalloc((void**)&b->d_hist, 30 * 4));
-    HIPCHK(c, hipMalloc((void**)&b->d_entries, M * 4));
+    HIPCHK(c, b->d_word.alloc(B * M));
+    HIPCHK(c, b->d_weight.alloc(B * M));
+    HIPCHK(c, b->d_nid.alloc(B * M));
+    HIPCHK(c, b->d_groups.alloc(M));
+    HIPCHK(c, b->d_kfIdx.alloc(M));
+    HIPCHK(c, b->d_fIdx.alloc(M));
+    HIPCHK(c, b->d_kfMP.alloc(M));
+    HIPCHK(c, b->d_fMP.alloc(M));
+    HIPCHK(c, b->d_match.alloc(M));
+    HIPCHK(c, b->d_counters.alloc(2));
+    HIPCHK(c, b->d_hist.alloc(30));
+    HIPCHK(c, b->d_entries.alloc(M * 2));
     return DRFE_OK;
 }
 

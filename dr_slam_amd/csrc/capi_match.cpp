@@ -10,15 +10,6 @@
 #include <new>
 #include <thread>
 
-#define HIPCHK(c, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
-            return DRFE_ERR_HIP;                                                                \
-        }                                                                                       \
-    } while (0)
-
 template <class T>
 static hipError_t dalloc(T** p, size_t n)
 {
@@ -47,7 +38,6 @@ MatchBuffers* drfe_match_buffers(drfe_ctx* c)
     if (c->mb) return c->mb;
     MatchBuffers* m = new (std::nothrow) MatchBuffers();
     if (!m) return nullptr;
-    std::memset(m, 0, sizeof(*m));
     c->mb = m;
     const size_t B = (size_t)c->cfg.max_batch, Q = B * (size_t)c->maxKp;
     m->queryCap = Q;

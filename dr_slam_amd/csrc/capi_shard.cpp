@@ -60,7 +60,7 @@ struct drfe_shard {
     ncclComm_t comm = nullptr;
     hipStream_t stream = nullptr;
     int nranks = 1, rank = 0, device = 0;
-    void* d_buf = nullptr; size_t cap = 0;
+    DevBuf<uint8_t> d_buf;                  /* grow-only device staging */
     std::string err;
 };
 
@@ -106,18 +106,13 @@ void drfe_shard_destroy(drfe_shard* s)
     if (!s) return;
     (void)hipSetDevice(s->device);
     if (s->comm) (void)rccl().CommDestroy(s->comm);
-    if (s->d_buf) (void)hipFree(s->d_buf);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     delete s;
 }
 
 static int shard_scratch(drfe_shard* s, size_t bytes)
 {
-    if (s->cap >= bytes) return DRFE_OK;
-    if (s->d_buf) (void)hipFree(s->d_buf);
-    s->d_buf = nullptr; s->cap = 0;
-    if (hipMalloc(&s->d_buf, bytes) != hipSuccess) { s->err = "drfe_shard: device staging buffer"; return DRFE_ERR_HIP; }
-    s->cap = bytes;
+    if (s->d_buf.grow(bytes) != hipSuccess) { s->err = "drfe_shard: device staging buffer"; return DRFE_ERR_HIP; }
     return DRFE_OK;
 }
 
@@ -150,7 +145,7 @@ int drfe_shard_reduce_report(drfe_shard* s, double* max_inout, int n_max, long l
     if (bytes == 0) return DRFE_OK;
     int rc = shard_scratch(s, bytes);
     if (rc != DRFE_OK) return rc;
-    double* dm = static_cast<double*>(s->d_buf);
+    double* dm = reinterpret_cast<double*>(s->d_buf.get());
     long long* ds = reinterpret_cast<long long*>(dm + n_max);
     hipError_t e = hipSuccess;
     if (n_max) e = hipMemcpyAsync(dm, max_inout, (size_t)n_max * 8, hipMemcpyHostToDevice, s->stream);

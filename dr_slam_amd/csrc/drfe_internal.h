@@ -27,6 +27,7 @@ static inline int roctxRangePop() { return 0; }
 
 #include "../../include/drfe.h"
 #include "../../include/drfe_debug.h"
+#include "hip_buf.h"
 
 #define DRFE_MAX_LEVELS 16
 #define DRFE_EDGE 19          /* EDGE_THRESHOLD, reference src/ORBextractor.cc:72 */
@@ -172,19 +173,19 @@ struct drfe_ctx {
 
     struct MatchBuffers* mb;  /* lazily allocated matcher scratch (match_internal.h) */
     struct PlanesScratch* ps; /* lazily allocated plane-path scratch (planes_internal.h) */
-    void* planeLanes;         /* std::vector<PlaneLane>*: lanes of drfe_planes_ahc_batch (planes_ahc.cpp) */
+    std::vector<struct PlaneLane>* planeLanes;   /* lanes of drfe_planes_ahc_batch (planes_ahc.cpp) */
     struct BowState* bow;     /* vocabulary + BoW scratch (bow_internal.h), set by drfe_voc_upload */
     struct LinesScratch* ls;  /* line-path scratch (lines_internal.h) */
-    void* lineHost;           /* LineHost*: host buffers of the single-frame line entry */
+    struct LineHost* lineHost;  /* host buffers of the single-frame line entry */
     struct OrbOneShot* oneShot; /* captured hipGraph of the single-frame ORB entry (capi.cpp) */
-    void* cape;               /* CapeScratch*: device buffers of drfe_planes_cape (planes_internal.h) */
-    void* capeBatch;          /* CapeBatchArena*: device path of drfe_planes_cape_batch (planes_cape.cpp) */
+    struct CapeScratch* cape; /* device buffers of drfe_planes_cape (planes_internal.h) */
+    struct CapeBatchArena* capeBatch;   /* device path of drfe_planes_cape_batch (planes_cape.cpp) */
     int planesDeviceCape;     /* drfe_planes_configure_cape: 1 = CAPE::process on the device in the batch entry (default) */
-    void* capeLanes;          /* std::vector<CapeLane>*: lanes of drfe_planes_cape_batch (planes_cape.cpp) */
-    void* sn;                 /* SnBuffers*: surface-normal scratch (post_internal.h) */
-    void* mf;                 /* MfBuffers*: drfe_manhattan_track_batch's buffers (manhattan.cpp) */
-    void* pm;                 /* PmBuffers*: drfe_plane_map_upload's maps and drfe_plane_match_batch's buffers (plane_match.cpp) */
-    void* lineWorkers;        /* std::vector<LineWorker>*: lanes of drfe_lsd_extract_batch (lines_lsd.cpp) */
+    std::vector<struct CapeLane>* capeLanes;   /* lanes of drfe_planes_cape_batch (planes_cape.cpp) */
+    struct SnBuffers* sn;     /* surface-normal scratch (post_internal.h) */
+    struct MfBuffers* mf;     /* drfe_manhattan_track_batch's buffers (manhattan.cpp) */
+    struct PmBuffers* pm;     /* drfe_plane_map_upload's maps and drfe_plane_match_batch's buffers (plane_map_internal.h) */
+    std::vector<struct LineWorker>* lineWorkers;   /* lanes of drfe_lsd_extract_batch (lines_lsd.cpp) */
     struct LinesScratch* lsBatch; /* frame slots of drfe_lsd_extract_batch's device region growing (lines_lsd.cpp) */
     int lsdDeviceGrow;        /* drfe_lsd_configure: 1 = the batch entry grows regions on the device (default) */
     int lsdDeviceNfa;         /* drfe_lsd_configure_nfa: 1 = rect_improve's decisions on the device in the batch entry (default) */
@@ -195,11 +196,11 @@ struct drfe_ctx {
     long long ahcStats[4];    /* drfe_planes_ahc_stats: frames through the device extractor, of those redone on the host, plane voxel grids on the device, of those redone on the host */
     int lsdRectMode;          /* drfe_lsd_configure_rect: rect_nfa's reading, 0 = literal OpenCV 3.4 (default), 1 = real-valued */
     int planesDeviceAhc;      /* drfe_planes_configure_extractor: 1 = drfe_planes_ahc_post_batch runs the extractor on the device (default) */
-    void* ahcArena;           /* AhcArena*: frame slots of the device extractor (planes_ahc.cpp) */
+    struct AhcArena* ahcArena;  /* frame slots of the device extractor (planes_ahc.cpp) */
     int planesDeviceRefit;    /* drfe_planes_configure_refit: 1 = gates + RANSAC refit on the device behind the device voxel grids (default) */
     long long ahcRefitStats[2];
     int planesDeviceVoxel;    /* drfe_planes_configure: where drfe_planes_ahc_post_batch runs the voxel grids (default 1: device, behind the device extractor) */
-    void* frameLanes;         /* std::vector<FrameLane>*: per-slot staging of drfe_frame_submit / drfe_frame_collect (capi.cpp) */
+    std::vector<struct FrameLane>* frameLanes;   /* per-slot staging of drfe_frame_submit / drfe_frame_collect (capi.cpp) */
 
     /* profiling */
     bool profile;

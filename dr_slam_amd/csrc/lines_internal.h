@@ -5,34 +5,36 @@
 
 struct LineTaps { int n; int t[9]; };   /* 8.8 fixed-point Gaussian taps */
 
+struct RectCand; struct LbdLine; struct LsdRect; struct LsdGrowFrame; struct LsdSegOut;
+
 /* device arrays of `frames` consecutive frame slots (dense: slot f of an array starts at f x the per-frame element count) */
 struct LinesScratch {
-    int w, h, sw, sh;               /* input and 0.8-scaled sizes */
-    int frames;                     /* frame slots (1 for the single-frame entry) */
-    uint8_t* d_img; uint8_t* d_blur; uint8_t* d_scaled;
-    uint16_t* d_tmp16;
-    double* d_modgrad; double* d_angles;
-    float2* d_cs;                   /* (cos, sin) of float(angle) per scaled pixel, 0 where the angle is undefined */
-    float2* d_cs0;                  /* batch arena: float(cos(angle)), float(sin(angle)) per scaled pixel - a seed's direction (k_lsd_keys) */
-    unsigned long long* d_meta;     /* per slot two words: [0] bits of the largest gradient magnitude, [1] smallest gradient bin of a pixel with an angle */
-    int16_t* d_gx; int16_t* d_gy;
-    struct RectCand* d_cands; int2* d_counts; size_t candCap;   /* grow-only scratch of the NFA rounds (one lane's) */
-    struct RectCand* h_cands; int2* h_counts;                   /* their pinned mirrors: no staging / pinning inside the copy calls */
-    struct LbdLine* d_lbdLines; uint8_t* d_lbdOut; size_t lbdCap;
+    int w = 0, h = 0, sw = 0, sh = 0;   /* input and 0.8-scaled sizes */
+    int frames = 0;                 /* frame slots (1 for the single-frame entry) */
+    DevBuf<uint8_t> d_img, d_blur, d_scaled;
+    DevBuf<uint16_t> d_tmp16;
+    DevBuf<double> d_modgrad, d_angles;
+    DevBuf<float2> d_cs;            /* (cos, sin) of float(angle) per scaled pixel, 0 where the angle is undefined */
+    DevBuf<float2> d_cs0;           /* batch arena: float(cos(angle)), float(sin(angle)) per scaled pixel - a seed's direction (k_lsd_keys) */
+    DevBuf<unsigned long long> d_meta;   /* per slot two words: [0] bits of the largest gradient magnitude, [1] smallest gradient bin of a pixel with an angle */
+    DevBuf<int16_t> d_gx, d_gy;
+    DevBuf<RectCand> d_cands; DevBuf<int2> d_counts; size_t candCap = 0;   /* grow-only scratch of the NFA rounds (one lane's) */
+    PinnedBuf<RectCand> h_cands; PinnedBuf<int2> h_counts;                 /* their pinned mirrors: no staging / pinning inside the copy calls */
+    DevBuf<LbdLine> d_lbdLines; DevBuf<uint8_t> d_lbdOut; size_t lbdCap = 0;
     /* device region growing (batch entry): per slot the ordering keys / sorted ordering, member list, shrink scratch,
      * accepted rectangles, (count, status); the launch's frame table; pinned host mirrors */
-    uint32_t* d_order; uint32_t* d_reg; uint32_t* d_tmp; struct LsdRect* d_rects; int* d_out; struct LsdGrowFrame* d_frames;
-    uint32_t* d_notdef;             /* one bit per scaled pixel: no level-line angle (k_lsd_notdef): the start of the growth kernels' `used` map */
-    uint32_t* d_regMw; uint32_t* d_tmpMw; uint32_t* d_gbmMw; int regCapMw;      /* k_lsd_grow_mw: member list / shrink scratch of each of a frame's four wavefronts (regCapMw entries each) */
-    int* d_ordStatus; int* h_ordStatus;   /* k_lsd_order's status word per slot */
-    uint32_t* h_order; unsigned long long* h_meta; struct LsdRect* h_rects; int* h_out; struct LsdGrowFrame* h_frames;
-    int rectCap;
+    DevBuf<uint32_t> d_order, d_reg, d_tmp; DevBuf<LsdRect> d_rects; DevBuf<int> d_out; DevBuf<LsdGrowFrame> d_frames;
+    DevBuf<uint32_t> d_notdef;      /* one bit per scaled pixel: no level-line angle (k_lsd_notdef): the start of the growth kernels' `used` map */
+    DevBuf<uint32_t> d_regMw, d_tmpMw, d_gbmMw; int regCapMw = 0;   /* k_lsd_grow_mw: member list / shrink scratch of each of a frame's four wavefronts (regCapMw entries each) */
+    DevBuf<int> d_ordStatus; PinnedBuf<int> h_ordStatus;   /* k_lsd_order's status word per slot */
+    PinnedBuf<uint32_t> h_order; PinnedBuf<unsigned long long> h_meta; PinnedBuf<LsdRect> h_rects; PinnedBuf<int> h_out; PinnedBuf<LsdGrowFrame> h_frames;
+    int rectCap = 0;
     /* rect_improve + NFA on the device: validated segments per rectangle slot, pinned mirror, the host-filled log-gamma table */
-    struct LsdSegOut* d_segs; struct LsdSegOut* h_segs; double* d_lgamma; int lgammaN;
+    DevBuf<LsdSegOut> d_segs; PinnedBuf<LsdSegOut> h_segs; DevBuf<double> d_lgamma; int lgammaN = 0;
     /* key lines on the device (k_lsd_keylines + k_lbd batch form): klCap slots per frame; pinned mirrors of what the caller receives */
-    int klCap;
-    drfe_keyline* d_kl; double* d_klLineF; struct LbdLine* d_klLbd; uint8_t* d_klDesc; int* d_klOut;
-    drfe_keyline* h_kl; double* h_klLineF; uint8_t* h_klDesc; int* h_klOut;
+    int klCap = 0;
+    DevBuf<drfe_keyline> d_kl; DevBuf<double> d_klLineF; DevBuf<LbdLine> d_klLbd; DevBuf<uint8_t> d_klDesc; DevBuf<int> d_klOut;
+    PinnedBuf<drfe_keyline> h_kl; PinnedBuf<double> h_klLineF; PinnedBuf<uint8_t> h_klDesc; PinnedBuf<int> h_klOut;
 };
 
 /* one rectangle whose aligned pixels are to be counted: the fields cv::LineSegmentDetectorImpl::rect_nfa reads */

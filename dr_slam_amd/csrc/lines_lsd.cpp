@@ -29,15 +29,6 @@
 #include <cstring>
 #include <new>
 
-#define HIPCHK(c, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
-            return DRFE_ERR_HIP;                                                                \
-        }                                                                                       \
-    } while (0)
-
 namespace {
 
 const double kNotDef = -1024.0, kTwoPi = 2.0 * M_PI, kThreeHalfPi = 3.0 * M_PI / 2.0, kDeg2Rad = M_PI / 180.0;
@@ -607,28 +598,17 @@ static hipError_t lane_sync(LineWorker* c)
     return c->pollEv ? drfe_pool_sync(c->stream, c->pollEv) : hipStreamSynchronize(c->stream);
 }
 
-static void scratch_free(LinesScratch*& s)
-{
-    if (!s) return;
-    void* ptrs[] = {s->d_img, s->d_blur, s->d_scaled, s->d_tmp16, s->d_modgrad, s->d_angles, s->d_cs, s->d_cs0, s->d_meta, s->d_gx, s->d_gy, s->d_cands, s->d_counts,
-                    s->d_lbdLines, s->d_lbdOut, s->d_order, s->d_reg, s->d_tmp, s->d_notdef, s->d_regMw, s->d_tmpMw, s->d_gbmMw, s->d_rects, s->d_out, s->d_frames, s->d_ordStatus, s->d_segs, s->d_lgamma, s->d_kl, s->d_klLineF, s->d_klLbd, s->d_klDesc, s->d_klOut};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    void* hptrs[] = {s->h_order, s->h_meta, s->h_rects, s->h_out, s->h_frames, s->h_ordStatus, s->h_cands, s->h_counts, s->h_segs, s->h_kl, s->h_klLineF, s->h_klDesc, s->h_klOut};
-    for (void* p : hptrs) if (p) (void)hipHostFree(p);
-    delete s;
-    s = nullptr;
-}
-
 void drfe_lines_free(drfe_ctx* c)
 {
-    scratch_free(c->ls);
-    scratch_free(c->lsBatch);
-    delete static_cast<LineHost*>(c->lineHost);
+    delete c->ls;
+    c->ls = nullptr;
+    delete c->lsBatch;
+    c->lsBatch = nullptr;
+    delete c->lineHost;
     c->lineHost = nullptr;
-    auto* pool = static_cast<std::vector<LineWorker>*>(c->lineWorkers);
-    if (pool) {
+    if (auto* pool = c->lineWorkers) {
         for (LineWorker& w : *pool) {
-            scratch_free(w.ls);
+            delete w.ls;
             delete w.host;
             if (w.ownsStream && w.stream) (void)hipStreamDestroy(w.stream);
             if (w.pollEv) (void)hipEventDestroy(w.pollEv);
@@ -644,64 +624,56 @@ void drfe_lines_free(drfe_ctx* c)
  * images = false: a lane that only needs the NFA / LBD scratch (its frames live in the batch arena) */
 static int ensure_lines(std::string& err, LinesScratch*& ls, int w, int h, int frames, bool images, bool grow)
 {
-    struct E { std::string& err; } e{err};
-#define LCHK(call)                                                                              \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) { e.err = std::string(#call) + ": " + hipGetErrorString(e__); return DRFE_ERR_HIP; } \
-    } while (0)
     if (ls && ls->w == w && ls->h == h && ls->frames >= frames && (!images || ls->d_img) && (!grow || ls->d_order)) return DRFE_OK;
-    scratch_free(ls);
-    LinesScratch* s = new (std::nothrow) LinesScratch();
+    delete ls;
+    LinesScratch* s = ls = new (std::nothrow) LinesScratch();
     if (!s) return DRFE_ERR_INVALID;
-    std::memset(s, 0, sizeof(*s));
-    ls = s;
-    s->w = w; s->h = h; s->frames = frames;
-    s->sw = (int)std::rint(w * 0.8); s->sh = (int)std::rint(h * 0.8);   /* saturate_cast<int>(size * inv_scale) */
-    const size_t F = (size_t)frames, n = (size_t)w * h * F, ns = (size_t)s->sw * s->sh * F;
+    const int sw = (int)std::rint(w * 0.8), sh = (int)std::rint(h * 0.8);   /* saturate_cast<int>(size * inv_scale) */
+    const size_t F = (size_t)frames, n = (size_t)w * h * F, ns = (size_t)sw * sh * F, bits = ((size_t)sw * sh + 31) / 32;
     if (images) {
-        LCHK(hipMalloc((void**)&s->d_img, n));
-        LCHK(hipMalloc((void**)&s->d_blur, n));
-        LCHK(hipMalloc((void**)&s->d_scaled, ns));
-        LCHK(hipMalloc((void**)&s->d_tmp16, n * 2));
-        LCHK(hipMalloc((void**)&s->d_modgrad, ns * 8));
-        LCHK(hipMalloc((void**)&s->d_angles, ns * 8));
-        LCHK(hipMalloc((void**)&s->d_cs, ns * 8));
-        LCHK(hipMalloc((void**)&s->d_meta, 16 * F));
-        LCHK(hipMalloc((void**)&s->d_gx, n * 2));
-        LCHK(hipMalloc((void**)&s->d_gy, n * 2));
+        HIPCHK_TO(err, s->d_img.alloc(n));
+        HIPCHK_TO(err, s->d_blur.alloc(n));
+        HIPCHK_TO(err, s->d_scaled.alloc(ns));
+        HIPCHK_TO(err, s->d_tmp16.alloc(n));
+        HIPCHK_TO(err, s->d_modgrad.alloc(ns));
+        HIPCHK_TO(err, s->d_angles.alloc(ns));
+        HIPCHK_TO(err, s->d_cs.alloc(ns));
+        HIPCHK_TO(err, s->d_meta.alloc(2 * F));
+        HIPCHK_TO(err, s->d_gx.alloc(n));
+        HIPCHK_TO(err, s->d_gy.alloc(n));
     }
+    /* accepted regions scale with the field: 4096 at 512 x 384 (~1500 seen), 16384 at 1024 x 768 (~5800 seen on a 1280 x 960 frame) */
+    const int rectCap = grow ? std::max(LSD_RECT_CAP, sw * sh / 48) : 0;
+    /* the multi-wave growth: each of a frame's four wavefronts owns half a field's worth of member-list entries (a region
+     * beyond that hands the frame to the host) */
+    const int regCapMw = grow ? sw * sh / 2 : 0;
     if (grow) {
-        const size_t nk = (size_t)(s->sw - 1) * (s->sh - 1) * F;
-        /* accepted regions scale with the field: 4096 at 512 x 384 (~1500 seen), 16384 at 1024 x 768 (~5800 seen on a 1280 x 960 frame) */
-        s->rectCap = std::max(LSD_RECT_CAP, s->sw * s->sh / 48);
-        LCHK(hipMalloc((void**)&s->d_order, nk * 4));
-        LCHK(hipMalloc((void**)&s->d_reg, ns * 4));
-        LCHK(hipMalloc((void**)&s->d_cs0, ns * 8));
-        LCHK(hipMalloc((void**)&s->d_tmp, ns * 4));
-        LCHK(hipMalloc((void**)&s->d_notdef, (((size_t)s->sw * s->sh + 31) / 32) * 4 * F));
-        /* the multi-wave growth: each of a frame's four wavefronts owns half a field's worth of member-list entries (a region
-         * beyond that hands the frame to the host) */
-        s->regCapMw = s->sw * s->sh / 2;
-        LCHK(hipMalloc((void**)&s->d_regMw, F * 4 * (size_t)s->regCapMw * 4));
-        LCHK(hipMalloc((void**)&s->d_tmpMw, F * 4 * (size_t)s->regCapMw * 4));
-        LCHK(hipMalloc((void**)&s->d_gbmMw, F * (((size_t)s->sw * s->sh + 31) / 32) * 4));
-        LCHK(hipMalloc((void**)&s->d_rects, F * s->rectCap * sizeof(LsdRect)));
-        LCHK(hipMalloc((void**)&s->d_out, F * DRFE_LSD_OUT_INTS * sizeof(int)));
-        LCHK(hipMalloc((void**)&s->d_frames, F * sizeof(LsdGrowFrame)));
-        LCHK(hipMalloc((void**)&s->d_ordStatus, F * sizeof(int)));
-        LCHK(hipHostMalloc((void**)&s->h_ordStatus, F * sizeof(int), hipHostMallocDefault));
-        LCHK(hipHostMalloc((void**)&s->h_meta, 16 * F, hipHostMallocDefault));
-        LCHK(hipHostMalloc((void**)&s->h_rects, F * s->rectCap * sizeof(LsdRect), hipHostMallocDefault));
-        LCHK(hipHostMalloc((void**)&s->h_out, F * DRFE_LSD_OUT_INTS * sizeof(int), hipHostMallocDefault));
-        LCHK(hipHostMalloc((void**)&s->h_frames, F * sizeof(LsdGrowFrame), hipHostMallocDefault));
-        LCHK(hipMalloc((void**)&s->d_segs, F * s->rectCap * sizeof(LsdSegOut)));
-        LCHK(hipHostMalloc((void**)&s->h_segs, F * s->rectCap * sizeof(LsdSegOut), hipHostMallocDefault));
+        const size_t nk = (size_t)(sw - 1) * (sh - 1) * F;
+        HIPCHK_TO(err, s->d_order.alloc(nk));
+        HIPCHK_TO(err, s->d_reg.alloc(ns));
+        HIPCHK_TO(err, s->d_cs0.alloc(ns));
+        HIPCHK_TO(err, s->d_tmp.alloc(ns));
+        HIPCHK_TO(err, s->d_notdef.alloc(bits * F));
+        HIPCHK_TO(err, s->d_regMw.alloc(F * 4 * (size_t)regCapMw));
+        HIPCHK_TO(err, s->d_tmpMw.alloc(F * 4 * (size_t)regCapMw));
+        HIPCHK_TO(err, s->d_gbmMw.alloc(F * bits));
+        HIPCHK_TO(err, s->d_rects.alloc(F * rectCap));
+        HIPCHK_TO(err, s->d_out.alloc(F * DRFE_LSD_OUT_INTS));
+        HIPCHK_TO(err, s->d_frames.alloc(F));
+        HIPCHK_TO(err, s->d_ordStatus.alloc(F));
+        HIPCHK_TO(err, s->h_ordStatus.alloc(F));
+        HIPCHK_TO(err, s->h_meta.alloc(2 * F));
+        HIPCHK_TO(err, s->h_rects.alloc(F * rectCap));
+        HIPCHK_TO(err, s->h_out.alloc(F * DRFE_LSD_OUT_INTS));
+        HIPCHK_TO(err, s->h_frames.alloc(F));
+        HIPCHK_TO(err, s->d_segs.alloc(F * rectCap));
+        HIPCHK_TO(err, s->h_segs.alloc(F * rectCap));
         /* log_gamma at the integers, by the host's libm (RectValidator::fillTables fills and uploads it on first use) */
-        s->lgammaN = 0;
-        LCHK(hipMalloc((void**)&s->d_lgamma, ((size_t)s->sw * s->sh + 2) * sizeof(double)));
+        HIPCHK_TO(err, s->d_lgamma.alloc((size_t)sw * sh + 2));
     }
-#undef LCHK
+    /* the geometry last: a scratch whose allocations did not all succeed never passes the reuse test above */
+    s->sw = sw; s->sh = sh; s->rectCap = rectCap; s->regCapMw = regCapMw;
+    s->w = w; s->h = h; s->frames = frames;
     return DRFE_OK;
 }
 
@@ -738,18 +710,13 @@ static RectValidator::CountFn device_counts(LineWorker* c, const FrameView& v, i
         struct Acc { std::chrono::steady_clock::time_point w; double c; ~Acc() { g_countsWallUs += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w).count(); g_countsCpuUs += thread_cpu_us() - c; } } acc{tw0, tc0};
         out.resize(nc);
         if (nc > s->candCap) {
-            if (s->d_cands) (void)hipFree(s->d_cands);
-            if (s->d_counts) (void)hipFree(s->d_counts);
-            if (s->h_cands) (void)hipHostFree(s->h_cands);
-            if (s->h_counts) (void)hipHostFree(s->h_counts);
-            s->d_cands = nullptr; s->d_counts = nullptr; s->h_cands = nullptr; s->h_counts = nullptr;
-            s->candCap = std::max<size_t>(nc * 2, 4096);
-            if (hipMalloc((void**)&s->d_cands, s->candCap * sizeof(RectCand)) != hipSuccess ||
-                hipMalloc((void**)&s->d_counts, s->candCap * sizeof(int2)) != hipSuccess ||
-                hipHostMalloc((void**)&s->h_cands, s->candCap * sizeof(RectCand), hipHostMallocDefault) != hipSuccess ||
-                hipHostMalloc((void**)&s->h_counts, s->candCap * sizeof(int2), hipHostMallocDefault) != hipSuccess) {
-                s->candCap = 0; c->err = "lsd_extract: hipMalloc of the NFA scratch failed"; countRc = DRFE_ERR_HIP; return false;
+            s->candCap = 0;
+            const size_t cap = std::max<size_t>(nc * 2, 4096);
+            if (s->d_cands.alloc(cap) != hipSuccess || s->d_counts.alloc(cap) != hipSuccess || s->h_cands.alloc(cap) != hipSuccess ||
+                s->h_counts.alloc(cap) != hipSuccess) {
+                c->err = "lsd_extract: hipMalloc of the NFA scratch failed"; countRc = DRFE_ERR_HIP; return false;
             }
+            s->candCap = cap;
         }
         std::memcpy(s->h_cands, cands.data(), nc * sizeof(RectCand));
         hipError_t e = hipMemcpyAsync(s->d_cands, s->h_cands, nc * sizeof(RectCand), hipMemcpyHostToDevice, st);
@@ -822,12 +789,11 @@ static int keylines_and_descriptors(LineWorker* c, const FrameView& v, const std
      * reference's do */
     if (nl > 0 && ldesc) {
         if ((size_t)nl > s->lbdCap) {
-            if (s->d_lbdLines) (void)hipFree(s->d_lbdLines);
-            if (s->d_lbdOut) (void)hipFree(s->d_lbdOut);
-            s->d_lbdLines = nullptr; s->d_lbdOut = nullptr;
-            s->lbdCap = std::max<size_t>((size_t)nl, 64);
-            HIPCHK(c, hipMalloc((void**)&s->d_lbdLines, s->lbdCap * sizeof(LbdLine)));
-            HIPCHK(c, hipMalloc((void**)&s->d_lbdOut, s->lbdCap * 32));
+            s->lbdCap = 0;
+            const size_t cap = std::max<size_t>((size_t)nl, 64);
+            HIPCHK(c, s->d_lbdLines.alloc(cap));
+            HIPCHK(c, s->d_lbdOut.alloc(cap * 32));
+            s->lbdCap = cap;
         }
         std::vector<LbdLine> ll(nl);
         for (int i = 0; i < nl; i++) {
@@ -981,20 +947,15 @@ static int batch_launch_grow(BatchJob& J, int ch, std::string& err)
         g.meta = J.deviceOrder ? A->d_meta + 2 * (size_t)f : nullptr;
         g.minSeedBin = J.deviceOrder ? 0u : 1024u - (uint32_t)(A->h_meta[2 * (size_t)f + 1] & 0xFFFFFFFFull);
     }
-#define BCHK(call)                                                                              \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(e__); return DRFE_ERR_HIP; } \
-    } while (0)
     if (J.deviceOrder) {
         /* std::sort's permutation on the device, in place; the member-list arrays serve as its scratch (the growth that
          * follows on the same stream overwrites them) */
-        BCHK(drfe_launch_lsd_order(A->d_order + nk * f0, nk, (int)nk, A->d_reg + ns * f0, A->d_tmp + ns * f0, ns, A->d_ordStatus + f0, 1, nf, st));
+        HIPCHK_TO(err, drfe_launch_lsd_order(A->d_order + nk * f0, nk, (int)nk, A->d_reg + ns * f0, A->d_tmp + ns * f0, ns, A->d_ordStatus + f0, 1, nf, st));
         if (ch == 0 && J.stageEv[4]) (void)hipEventRecord(J.stageEv[4], st);
         if (ch == 0 && J.clk[4]) (void)hipEventRecord(J.clk[4], st);
     } else
-        BCHK(hipMemcpyAsync(A->d_order + nk * f0, A->h_order + nk * f0, nk * 4 * nf, hipMemcpyHostToDevice, st));
-    BCHK(hipMemcpyAsync(A->d_frames + f0, A->h_frames + f0, sizeof(LsdGrowFrame) * nf, hipMemcpyHostToDevice, st));
+        HIPCHK_TO(err, hipMemcpyAsync(A->d_order + nk * f0, A->h_order + nk * f0, nk * 4 * nf, hipMemcpyHostToDevice, st));
+    HIPCHK_TO(err, hipMemcpyAsync(A->d_frames + f0, A->h_frames + f0, sizeof(LsdGrowFrame) * nf, hipMemcpyHostToDevice, st));
     /* Region growing: one wavefront per frame (k_lsd_grow: the least wave-time per frame - what counts when calls of hundreds of
      * frames run side by side and the device is full) or four (k_lsd_grow_mw: speculation with in-order commit, 75 -> 45 ms per
      * frame - what counts when the call cannot fill the device by itself).  Measured on one MI355X (profiles/r05a_path_saturation.txt):
@@ -1003,17 +964,17 @@ static int batch_launch_grow(BatchJob& J, int ch, std::string& err)
     static const int growWavesEnv = [] { const char* e = std::getenv("DRFE_LSD_GROW_WAVES"); return e ? std::atoi(e) : 0; }();
     const int growMode = J.c->lsdDeviceGrow;          /* drfe_lsd_configure: 2 / 3 force a kernel */
     const bool growMw = growMode == 3 || growWavesEnv == 4 || (growMode != 2 && growWavesEnv != 1 && J.nframes <= 256);
-    BCHK(drfe_launch_lsd_grow(A->d_frames + f0, nf, A->sw, A->sh, J.prec, J.p, J.minReg, 0.7, A->rectCap, st, growMw ? A->regCapMw : 0));
+    HIPCHK_TO(err, drfe_launch_lsd_grow(A->d_frames + f0, nf, A->sw, A->sh, J.prec, J.p, J.minReg, 0.7, A->rectCap, st, growMw ? A->regCapMw : 0));
     if (ch == 0 && J.clk[5]) (void)hipEventRecord(J.clk[5], st);
     /* rect_improve + the NFA decisions of every accepted rectangle, behind the growth on the same stream: no host round trip */
     if (J.deviceNfa)
-        BCHK(drfe_launch_rect_improve(A->d_frames + f0, nf, A->sw, A->sh, lsd_walk_mode(J.rectMode), J.nfaTab, A->rectCap, A->d_segs + (size_t)A->rectCap * f0, st));
+        HIPCHK_TO(err, drfe_launch_rect_improve(A->d_frames + f0, nf, A->sw, A->sh, lsd_walk_mode(J.rectMode), J.nfaTab, A->rectCap, A->d_segs + (size_t)A->rectCap * f0, st));
     if (ch == 0 && J.clk[6] && J.deviceNfa) (void)hipEventRecord(J.clk[6], st);
     if (J.deviceNfa && J.deviceKl) {
         const size_t k0 = (size_t)A->klCap * f0, px = (size_t)A->w * A->h;
-        BCHK(drfe_launch_lsd_keylines(A->d_frames + f0, A->d_segs + (size_t)A->rectCap * f0, A->rectCap, nf, A->w, A->h, J.maxLines, A->klCap,
+        HIPCHK_TO(err, drfe_launch_lsd_keylines(A->d_frames + f0, A->d_segs + (size_t)A->rectCap * f0, A->rectCap, nf, A->w, A->h, J.maxLines, A->klCap,
                                       A->d_kl + k0, A->d_klLineF + 3 * k0, A->d_klLbd + k0, A->d_klOut + 4 * (size_t)f0, st));
-        BCHK(drfe_launch_lbd_batch(A->d_klLbd + k0, A->d_klOut + 4 * (size_t)f0, A->klCap, nf, A->d_gx + px * f0, A->d_gy + px * f0, A->w, A->h, lbdTables(),
+        HIPCHK_TO(err, drfe_launch_lbd_batch(A->d_klLbd + k0, A->d_klOut + 4 * (size_t)f0, A->klCap, nf, A->d_gx + px * f0, A->d_gy + px * f0, A->w, A->h, lbdTables(),
                                    A->d_klDesc + 32 * k0, st));
         if (ch == 0 && J.clk[7]) (void)hipEventRecord(J.clk[7], st);
     }
@@ -1021,8 +982,7 @@ static int batch_launch_grow(BatchJob& J, int ch, std::string& err)
      * copies behind it (measured: the plane path's kernels and CAPE's transfers stalled for the whole growth); the worker that
      * sees the event fetches the chunk's status words */
     if (ch == 0 && J.stageEv[5]) (void)hipEventRecord(J.stageEv[5], st);
-    BCHK(hipEventRecord(J.growDone[ch], st));
-#undef BCHK
+    HIPCHK_TO(err, hipEventRecord(J.growDone[ch], st));
     return DRFE_OK;
 }
 
@@ -1223,30 +1183,24 @@ static int lsd_extract_batch_device(drfe_ctx* c, std::vector<LineWorker>* pool, 
     J.pendingFinish = nframes;
     J.deviceOrder = std::getenv("DRFE_LSD_HOST_ORDER") == nullptr;
     if (!J.deviceOrder && !A->h_order)           /* the host-ordering experiment's pinned key mirror (0.4 GB per 512 frames): on demand */
-        HIPCHK(c, hipHostMalloc((void**)&A->h_order, (size_t)(A->sw - 1) * (A->sh - 1) * (size_t)A->frames * 4, hipHostMallocDefault));
+        HIPCHK(c, A->h_order.alloc((size_t)(A->sw - 1) * (A->sh - 1) * (size_t)A->frames));
     J.rectMode = c->lsdRectMode;
     const RectValidator val(A->sw, A->sh, J.rectMode);
     J.prec = M_PI * 22.5 / 180; J.p = 22.5 / 180; J.minReg = (int)val.minReg(J.p);
     J.deviceNfa = c->lsdDeviceNfa && std::getenv("DRFE_LSD_HOST_NFA") == nullptr;
     J.deviceKl = J.deviceNfa && std::getenv("DRFE_LSD_HOST_KEYLINES") == nullptr;
     if (J.deviceKl && (A->klCap < max_lines || A->klCap == 0)) {
-        void* dp[] = {A->d_kl, A->d_klLineF, A->d_klLbd, A->d_klDesc, A->d_klOut};
-        for (void* q : dp) if (q) (void)hipFree(q);
-        void* hp[] = {A->h_kl, A->h_klLineF, A->h_klDesc, A->h_klOut};
-        for (void* q : hp) if (q) (void)hipHostFree(q);
-        A->d_kl = nullptr; A->d_klLineF = nullptr; A->d_klLbd = nullptr; A->d_klDesc = nullptr; A->d_klOut = nullptr;
-        A->h_kl = nullptr; A->h_klLineF = nullptr; A->h_klDesc = nullptr; A->h_klOut = nullptr;
         A->klCap = 0;                 /* committed below, once every buffer exists: a failed allocation leaves "no buffers" behind */
         const size_t kn = (size_t)max_lines * A->frames;
-        HIPCHK(c, hipMalloc((void**)&A->d_kl, kn * sizeof(drfe_keyline)));
-        HIPCHK(c, hipMalloc((void**)&A->d_klLineF, kn * 3 * sizeof(double)));
-        HIPCHK(c, hipMalloc((void**)&A->d_klLbd, kn * sizeof(LbdLine)));
-        HIPCHK(c, hipMalloc((void**)&A->d_klDesc, kn * 32));
-        HIPCHK(c, hipMalloc((void**)&A->d_klOut, (size_t)A->frames * 4 * sizeof(int)));
-        HIPCHK(c, hipHostMalloc((void**)&A->h_kl, kn * sizeof(drfe_keyline), hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc((void**)&A->h_klLineF, kn * 3 * sizeof(double), hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc((void**)&A->h_klDesc, kn * 32, hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc((void**)&A->h_klOut, (size_t)A->frames * 4 * sizeof(int), hipHostMallocDefault));
+        HIPCHK(c, A->d_kl.alloc(kn));
+        HIPCHK(c, A->d_klLineF.alloc(kn * 3));
+        HIPCHK(c, A->d_klLbd.alloc(kn));
+        HIPCHK(c, A->d_klDesc.alloc(kn * 32));
+        HIPCHK(c, A->d_klOut.alloc((size_t)A->frames * 4));
+        HIPCHK(c, A->h_kl.alloc(kn));
+        HIPCHK(c, A->h_klLineF.alloc(kn * 3));
+        HIPCHK(c, A->h_klDesc.alloc(kn * 32));
+        HIPCHK(c, A->h_klOut.alloc((size_t)A->frames * 4));
         A->klCap = max_lines;
     }
     if (J.deviceNfa) {
@@ -1384,7 +1338,7 @@ int drfe_lsd_extract(drfe_ctx* c, const uint8_t* gray, int w, int h, size_t stri
     LineWorker lw;
     lw.ls = c->ls;
     lw.stream = c->stream;
-    lw.host = static_cast<LineHost*>(c->lineHost);
+    lw.host = c->lineHost;
     lw.rectMode = c->lsdRectMode;
     const int rc = lsd_extract_core(&lw, c->device, gray, w, h, stride, max_lines, lines, ldesc, line_f, cap, n_lines, n_detected);
     c->ls = lw.ls;
@@ -1468,7 +1422,7 @@ int drfe_lsd_extract_batch(drfe_ctx* c, const uint8_t* gray, size_t frame_stride
     int T = n_threads > 0 ? n_threads : std::max(1, drfe_default_host_threads() * 5 / 4);
     T = std::max(1, std::min(T, nframes));
     HIPCHK(c, hipSetDevice(c->device));
-    auto* pool = static_cast<std::vector<LineWorker>*>(c->lineWorkers);
+    auto* pool = c->lineWorkers;
     if (!pool) { pool = new std::vector<LineWorker>(); c->lineWorkers = pool; }
     while ((int)pool->size() < T) {
         LineWorker lw;
@@ -1549,18 +1503,17 @@ int drfe_debug_device_order_sort_depth(drfe_ctx* c, uint32_t* keys, size_t n, in
 {
     if (!c || !keys || !status || n < 1 || n > (1u << 22)) { if (c) c->err = "debug_device_order_sort: invalid argument"; return DRFE_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
-    uint32_t *d = nullptr, *pl = nullptr, *pr = nullptr;
-    int* ds = nullptr;
-    hipError_t e = hipMalloc((void**)&d, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&pl, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&pr, n * 4);
-    if (e == hipSuccess) e = hipMalloc((void**)&ds, 4);
+    DevBuf<uint32_t> d, pl, pr;
+    DevBuf<int> ds;
+    hipError_t e = d.alloc(n);
+    if (e == hipSuccess) e = pl.alloc(n);
+    if (e == hipSuccess) e = pr.alloc(n);
+    if (e == hipSuccess) e = ds.alloc(1);
     if (e == hipSuccess) e = hipMemcpyAsync(d, keys, n * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = drfe_launch_lsd_order(d, n, (int)n, pl, pr, n, ds, 1, 1, c->stream, depth_limit);
     if (e == hipSuccess) e = hipMemcpyAsync(keys, d, n * 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(status, ds, 4, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d); (void)hipFree(pl); (void)hipFree(pr); (void)hipFree(ds);
     if (e != hipSuccess) { c->err = std::string("debug_device_order_sort: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
     return DRFE_OK;
 }

@@ -9,15 +9,6 @@
 #include <string>
 #include <vector>
 
-#define HIPCHK(c, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
-            return DRFE_ERR_HIP;                                                                \
-        }                                                                                       \
-    } while (0)
-
 namespace {
 
 /* One TrackManhattanFrame call on the host: the conic pass over all three axes, the threshold, then the mean-shift pass
@@ -84,45 +75,31 @@ void track_once(float R[9], const drfe_surface_normal* recs, int n, const double
     ci->svd = mf_assemble(R, ci->found) ? 1 : 0;
 }
 
-struct DevBuf {                     /* grow-only device (or pinned host) allocation */
-    void* p = nullptr;
-    size_t cap = 0;
-};
+}  // namespace
 
 struct MfBuffers {                 /* drfe_manhattan_track_batch's buffers */
-    DevBuf R0, R, info, rbits, dirs, loff, lbits, cone, sums;        /* device */
-    DevBuf hR0, hDirs, hLoff;      /* pinned staging of the host inputs */
+    DevBuf<float> R0, R;
+    DevBuf<drfe_manhattan_info> info;
+    DevBuf<uint16_t> rbits, lbits;
+    DevBuf<double> dirs, sums;
+    DevBuf<int32_t> loff;
+    DevBuf<uint8_t> cone;
+    PinnedBuf<float> hR0;          /* pinned staging of the host inputs */
+    PinnedBuf<double> hDirs;
+    PinnedBuf<int32_t> hLoff;
     hipEvent_t staged = nullptr;   /* the staging copies of the previous batch are done */
     int frames = 0, nrec = 0;      /* the most recent batch */
     std::vector<int32_t> lineOff;  /* its line offsets */
 };
 
-int grow(drfe_ctx* c, DevBuf& b, size_t bytes, bool pinned = false)
-{
-    if (b.cap >= bytes && b.p) return DRFE_OK;
-    if (b.p) (void)(pinned ? hipHostFree(b.p) : hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-    if (pinned) HIPCHK(c, hipHostMalloc(&b.p, bytes, 0));
-    else HIPCHK(c, hipMalloc(&b.p, bytes));
-    b.cap = bytes;
-    return DRFE_OK;
-}
-
-}  // namespace
-
 void drfe_manhattan_free(drfe_ctx* c)
 {
-    MfBuffers* b = static_cast<MfBuffers*>(c->mf);
+    MfBuffers* b = c->mf;
     if (!b) return;
-    if (b->staged) (void)hipEventSynchronize(b->staged);
-    DevBuf* dev[] = {&b->R0, &b->R, &b->info, &b->rbits, &b->dirs, &b->loff, &b->lbits, &b->cone, &b->sums};
-    for (DevBuf* d : dev)
-        if (d->p) (void)hipFree(d->p);
-    DevBuf* host[] = {&b->hR0, &b->hDirs, &b->hLoff};
-    for (DevBuf* h : host)
-        if (h->p) (void)hipHostFree(h->p);
-    if (b->staged) (void)hipEventDestroy(b->staged);
+    if (b->staged) {
+        (void)hipEventSynchronize(b->staged);
+        (void)hipEventDestroy(b->staged);
+    }
     delete b;
     c->mf = nullptr;
 }
@@ -157,7 +134,7 @@ int drfe_manhattan_track_batch(drfe_ctx* c, const float* R0, int nseq, int seq_l
         c->err = "manhattan_track_batch: invalid argument";
         return DRFE_ERR_INVALID;
     }
-    SnBuffers* sn = static_cast<SnBuffers*>(c->sn);
+    SnBuffers* sn = c->sn;
     const size_t frames = (size_t)nseq * seq_len;
     if (!sn || !sn->d_recs || frames > (size_t)sn->lastFrames) {
         c->err = "manhattan_track_batch: the most recent drfe_surface_normals_batch holds fewer frames";
@@ -176,34 +153,34 @@ int drfe_manhattan_track_batch(drfe_ctx* c, const float* R0, int nseq, int seq_l
     }
     const size_t nLines = (size_t)loff[frames];
     HIPCHK(c, hipSetDevice(c->device));
-    MfBuffers* b = static_cast<MfBuffers*>(c->mf);
+    MfBuffers* b = c->mf;
     if (!b) { b = new MfBuffers(); c->mf = b; }
     if (!b->staged) HIPCHK(c, hipEventCreateWithFlags(&b->staged, hipEventDisableTiming));
     HIPCHK(c, hipEventSynchronize(b->staged));         /* the previous batch's staging is free again */
     const size_t scratch = (size_t)nrec + maxLines;     /* entries per sequence: the frame's records, then its lines */
-    int rc;
-    if ((rc = grow(c, b->R0, (size_t)nseq * 9 * sizeof(float))) || (rc = grow(c, b->R, frames * 9 * sizeof(float))) ||
-        (rc = grow(c, b->info, frames * sizeof(drfe_manhattan_info))) || (rc = grow(c, b->loff, (frames + 1) * sizeof(int32_t))) ||
-        (rc = grow(c, b->rbits, frames * (size_t)nrec * sizeof(uint16_t))) ||
-        (rc = grow(c, b->dirs, std::max<size_t>(nLines, 1) * 3 * sizeof(double))) ||
-        (rc = grow(c, b->lbits, std::max<size_t>(nLines, 1) * sizeof(uint16_t))) ||
-        (rc = grow(c, b->cone, (size_t)nseq * scratch)) || (rc = grow(c, b->sums, (size_t)nseq * scratch * 3 * sizeof(double))) ||
-        (rc = grow(c, b->hR0, (size_t)nseq * 9 * sizeof(float), true)) ||
-        (rc = grow(c, b->hLoff, (frames + 1) * sizeof(int32_t), true)) ||
-        (rc = grow(c, b->hDirs, std::max<size_t>(nLines, 1) * 3 * sizeof(double), true)))
-        return rc;
-    std::memcpy(b->hR0.p, R0, (size_t)nseq * 9 * sizeof(float));
-    std::memcpy(b->hLoff.p, loff.data(), loff.size() * sizeof(int32_t));
-    if (nLines) std::memcpy(b->hDirs.p, line_dirs, nLines * 3 * sizeof(double));
+    const size_t nDirs = std::max<size_t>(nLines, 1);
+    HIPCHK(c, b->R0.grow((size_t)nseq * 9));
+    HIPCHK(c, b->R.grow(frames * 9));
+    HIPCHK(c, b->info.grow(frames));
+    HIPCHK(c, b->loff.grow(frames + 1));
+    HIPCHK(c, b->rbits.grow(frames * (size_t)nrec));
+    HIPCHK(c, b->dirs.grow(nDirs * 3));
+    HIPCHK(c, b->lbits.grow(nDirs));
+    HIPCHK(c, b->cone.grow((size_t)nseq * scratch));
+    HIPCHK(c, b->sums.grow((size_t)nseq * scratch * 3));
+    HIPCHK(c, b->hR0.grow((size_t)nseq * 9));
+    HIPCHK(c, b->hLoff.grow(frames + 1));
+    HIPCHK(c, b->hDirs.grow(nDirs * 3));
+    std::memcpy(b->hR0, R0, (size_t)nseq * 9 * sizeof(float));
+    std::memcpy(b->hLoff, loff.data(), loff.size() * sizeof(int32_t));
+    if (nLines) std::memcpy(b->hDirs, line_dirs, nLines * 3 * sizeof(double));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, hipMemcpyAsync(b->R0.p, b->hR0.p, (size_t)nseq * 9 * sizeof(float), hipMemcpyHostToDevice, s));
-    HIPCHK(c, hipMemcpyAsync(b->loff.p, b->hLoff.p, loff.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    if (nLines) HIPCHK(c, hipMemcpyAsync(b->dirs.p, b->hDirs.p, nLines * 3 * sizeof(double), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(b->R0, b->hR0, (size_t)nseq * 9 * sizeof(float), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(b->loff, b->hLoff, loff.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    if (nLines) HIPCHK(c, hipMemcpyAsync(b->dirs, b->hDirs, nLines * 3 * sizeof(double), hipMemcpyHostToDevice, s));
     HIPCHK(c, hipEventRecord(b->staged, s));
-    hipError_t e = drfe_launch_manhattan(sn->d_recs, nrec, (const float*)b->R0.p, nseq, seq_len, (const double*)b->dirs.p,
-                                         (const int32_t*)b->loff.p, n_calls, (uint8_t*)b->cone.p, (double*)b->sums.p, scratch,
-                                         (float*)b->R.p, (drfe_manhattan_info*)b->info.p, (uint16_t*)b->rbits.p,
-                                         (uint16_t*)b->lbits.p, s);
+    hipError_t e = drfe_launch_manhattan(sn->d_recs, nrec, b->R0, nseq, seq_len, b->dirs, b->loff, n_calls, b->cone, b->sums,
+                                         scratch, b->R, b->info, b->rbits, b->lbits, s);
     if (e != hipSuccess) { c->err = std::string("manhattan_track_batch: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
     b->frames = (int)frames;
     b->nrec = nrec;
@@ -214,16 +191,16 @@ int drfe_manhattan_track_batch(drfe_ctx* c, const float* R0, int nseq, int seq_l
 int drfe_manhattan_download(drfe_ctx* c, int frame, float* R, drfe_manhattan_info* info, uint16_t* rec_bits, uint16_t* line_bits)
 {
     if (!c) return DRFE_ERR_INVALID;
-    MfBuffers* b = static_cast<MfBuffers*>(c->mf);
+    MfBuffers* b = c->mf;
     if (!b || frame < 0 || frame >= b->frames) { c->err = "manhattan_download: no such frame"; return DRFE_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipDeviceSynchronize());
-    if (R) HIPCHK(c, hipMemcpy(R, (const float*)b->R.p + (size_t)frame * 9, 9 * sizeof(float), hipMemcpyDeviceToHost));
-    if (info) HIPCHK(c, hipMemcpy(info, (const drfe_manhattan_info*)b->info.p + frame, sizeof(*info), hipMemcpyDeviceToHost));
+    if (R) HIPCHK(c, hipMemcpy(R, b->R + (size_t)frame * 9, 9 * sizeof(float), hipMemcpyDeviceToHost));
+    if (info) HIPCHK(c, hipMemcpy(info, b->info + frame, sizeof(*info), hipMemcpyDeviceToHost));
     if (rec_bits)
-        HIPCHK(c, hipMemcpy(rec_bits, (const uint16_t*)b->rbits.p + (size_t)frame * b->nrec, (size_t)b->nrec * sizeof(uint16_t), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(rec_bits, b->rbits + (size_t)frame * b->nrec, (size_t)b->nrec * sizeof(uint16_t), hipMemcpyDeviceToHost));
     const int l0 = b->lineOff[frame], nl = b->lineOff[frame + 1] - l0;
-    if (line_bits && nl > 0) HIPCHK(c, hipMemcpy(line_bits, (const uint16_t*)b->lbits.p + l0, (size_t)nl * sizeof(uint16_t), hipMemcpyDeviceToHost));
+    if (line_bits && nl > 0) HIPCHK(c, hipMemcpy(line_bits, b->lbits + l0, (size_t)nl * sizeof(uint16_t), hipMemcpyDeviceToHost));
     return DRFE_OK;
 }
 

@@ -66,23 +66,18 @@ int repack(drfe_ctx* c, PmBuffers* b, const std::vector<int64_t>& need, hipStrea
         maxN = std::max(maxN, b->cntH[j]);
     }
     if (total > INT32_MAX) { c->err = "plane_map: the clouds outgrow 2^31 points"; return DRFE_ERR_CAPACITY; }
-    DevBuf arena;
-    int rc;
-    if ((rc = drfe_pm_grow(c, arena, (size_t)total * 12)) || (rc = drfe_pm_grow(c, b->upMove, mv.size() * sizeof(int4)))) {
-        if (arena.p) (void)hipFree(arena.p);
-        return rc;
-    }
+    DevBuf<float> arena;
+    HIPCHK(c, drfe_pm_reserve(arena, (size_t)total * 3));
+    HIPCHK(c, drfe_pm_reserve(b->upMove, mv.size()));
     hipError_t e = hipSuccess;
-    if (!mv.empty()) e = hipMemcpyAsync(b->upMove.p, mv.data(), mv.size() * sizeof(int4), hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = drfe_launch_map_plane_move((const int4*)b->upMove.p, (int)mv.size(), maxN, (const float*)b->cloud.p, (float*)arena.p, s);
+    if (!mv.empty()) e = hipMemcpyAsync(b->upMove, mv.data(), mv.size() * sizeof(int4), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = drfe_launch_map_plane_move(b->upMove, (int)mv.size(), maxN, b->cloud, arena, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) {
-        (void)hipFree(arena.p);
         c->err = std::string("plane_map repack: ") + hipGetErrorString(e);
         return DRFE_ERR_HIP;
     }
-    if (b->cloud.p) (void)hipFree(b->cloud.p);
-    b->cloud = arena;
+    b->cloud = std::move(arena);
     b->begH.swap(beg);
     b->capH.swap(cap);
     b->upStats[3]++;
@@ -106,9 +101,10 @@ int run_jobs(drfe_ctx* c, PmBuffers* b, const std::vector<Job>& jobs, const std:
         }
     }
     int rc;
-    if ((rc = drfe_pm_grow(c, b->upSrc, nsrc * 12)) || (rc = drfe_pm_grow(c, b->upPose, (size_t)nposes * 64))) return rc;
-    if (nsrc) HIPCHK(c, hipMemcpyAsync(b->upSrc.p, src, nsrc * 12, hipMemcpyHostToDevice, s));
-    if (nposes) HIPCHK(c, hipMemcpyAsync(b->upPose.p, poses, (size_t)nposes * 64, hipMemcpyHostToDevice, s));
+    HIPCHK(c, drfe_pm_reserve(b->upSrc, nsrc * 3));
+    HIPCHK(c, drfe_pm_reserve(b->upPose, (size_t)nposes * 16));
+    if (nsrc) HIPCHK(c, hipMemcpyAsync(b->upSrc, src, nsrc * 12, hipMemcpyHostToDevice, s));
+    if (nposes) HIPCHK(c, hipMemcpyAsync(b->upPose, poses, (size_t)nposes * 64, hipMemcpyHostToDevice, s));
     std::vector<float> hin, hout;
     for (const std::vector<int>& R : rounds) {
         const int nj = (int)R.size();
@@ -155,29 +151,33 @@ int run_jobs(drfe_ctx* c, PmBuffers* b, const std::vector<Job>& jobs, const std:
         const size_t oS = 0, oJ = drfe_align16(rs.size() * sizeof(MpSeg)), oC = drfe_align16(oJ + (size_t)nj * sizeof(int2)),
                      oK = drfe_align16(oC + (size_t)nj * sizeof(MpCommit)), oEnd = drfe_align16(oK + (size_t)nj * 4);
         const size_t N = (size_t)total;
-        if ((rc = drfe_pm_grow(c, b->upRec, oK)) || (rc = drfe_pm_grow(c, b->upHost, oEnd, true)) || (rc = drfe_pm_grow(c, b->upIn, N * 12)) ||
-            (rc = drfe_pm_grow(c, b->upOut, N * 12)) || (rc = drfe_pm_grow(c, b->upRecs, N * 8)) || (rc = drfe_pm_grow(c, b->upTmp, N * 8)) ||
-            (rc = drfe_pm_grow(c, b->upPosL, N * 4)) || (rc = drfe_pm_grow(c, b->upPosR, N * 4)) ||
-            (rc = drfe_pm_grow(c, b->upList, ((size_t)nj + 2) * 4)) || (rc = drfe_pm_grow(c, b->upCounts, (size_t)nj * 4)))
-            return rc;
-        char* h = static_cast<char*>(b->upHost.p);
+        HIPCHK(c, drfe_pm_reserve(b->upRec, oK));
+        HIPCHK(c, drfe_pm_reserve(b->upHost, oEnd));
+        HIPCHK(c, drfe_pm_reserve(b->upIn, N * 3));
+        HIPCHK(c, drfe_pm_reserve(b->upOut, N * 3));
+        HIPCHK(c, drfe_pm_reserve(b->upRecs, N));
+        HIPCHK(c, drfe_pm_reserve(b->upTmp, N));
+        HIPCHK(c, drfe_pm_reserve(b->upPosL, N));
+        HIPCHK(c, drfe_pm_reserve(b->upPosR, N));
+        HIPCHK(c, drfe_pm_reserve(b->upList, (size_t)nj + 2));
+        HIPCHK(c, drfe_pm_reserve(b->upCounts, (size_t)nj));
+        char* h = b->upHost;
         if (!rs.empty()) std::memcpy(h + oS, rs.data(), rs.size() * sizeof(MpSeg));
         std::memcpy(h + oJ, vj.data(), (size_t)nj * sizeof(int2));
         std::memcpy(h + oC, cm.data(), (size_t)nj * sizeof(MpCommit));
-        char* d = static_cast<char*>(b->upRec.p);
+        char* d = b->upRec;
         HIPCHK(c, hipMemcpyAsync(d, h, oK, hipMemcpyHostToDevice, s));
-        hipError_t e = drfe_launch_map_plane_gather((const MpSeg*)(d + oS), (int)rs.size(), maxSeg, (const float*)b->upPose.p,
-                                                    (const float*)b->upSrc.p, (const float*)b->cloud.p, (float*)b->upIn.p, s);
+        hipError_t e = drfe_launch_map_plane_gather((const MpSeg*)(d + oS), (int)rs.size(), maxSeg, b->upPose, b->upSrc,
+                                                    b->cloud, b->upIn, s);
         if (e == hipSuccess)
-            e = drfe_launch_voxel_grid((const float*)b->upIn.p, (const int2*)(d + oJ), nj, (int*)b->upList.p, (unsigned long long*)b->upRecs.p,
-                                       (unsigned long long*)b->upTmp.p, (uint32_t*)b->upPosL.p, (uint32_t*)b->upPosR.p, (float*)b->upOut.p,
-                                       (int*)b->upCounts.p, kLeaf, s);
+            e = drfe_launch_voxel_grid(b->upIn, (const int2*)(d + oJ), nj, b->upList, b->upRecs, b->upTmp, b->upPosL, b->upPosR,
+                                       b->upOut, b->upCounts, kLeaf, s);
         if (e == hipSuccess)
-            e = drfe_launch_map_plane_commit((const MpCommit*)(d + oC), nj, maxJob, (const int*)b->upCounts.p, (const float*)b->upOut.p,
-                                             (float*)b->cloud.p, (int32_t*)b->cloudEnd.p, s);
+            e = drfe_launch_map_plane_commit((const MpCommit*)(d + oC), nj, maxJob, b->upCounts, b->upOut, b->cloud,
+                                             b->cloudEnd, s);
         if (e != hipSuccess) { c->err = std::string("plane_map update: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
         int* counts = reinterpret_cast<int*>(h + oK);
-        HIPCHK(c, hipMemcpyAsync(counts, b->upCounts.p, (size_t)nj * 4, hipMemcpyDeviceToHost, s));
+        HIPCHK(c, hipMemcpyAsync(counts, b->upCounts, (size_t)nj * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
         for (int i = 0; i < nj; i++) {
             const int j = cm[i].plane;
@@ -187,13 +187,13 @@ int run_jobs(drfe_ctx* c, PmBuffers* b, const std::vector<Job>& jobs, const std:
                 continue;
             }
             hin.resize(3 * (size_t)n[i]);
-            if (n[i]) HIPCHK(c, hipMemcpy(hin.data(), (const float*)b->upIn.p + 3 * (size_t)vj[i].x, (size_t)n[i] * 12, hipMemcpyDeviceToHost));
+            if (n[i]) HIPCHK(c, hipMemcpy(hin.data(), b->upIn + 3 * (size_t)vj[i].x, (size_t)n[i] * 12, hipMemcpyDeviceToHost));
             if ((rc = voxel_host(hin.data(), (size_t)n[i], hout))) { c->err = "plane_map update: host voxel grid failed"; return rc; }
             const int m = (int)(hout.size() / 3);
             if (m > cm[i].cap) { c->err = "plane_map update: voxel output exceeds its slot"; return DRFE_ERR_CAPACITY; }
-            if (m) HIPCHK(c, hipMemcpy((float*)b->cloud.p + 3 * (size_t)cm[i].dstBeg, hout.data(), (size_t)m * 12, hipMemcpyHostToDevice));
+            if (m) HIPCHK(c, hipMemcpy(b->cloud + 3 * (size_t)cm[i].dstBeg, hout.data(), (size_t)m * 12, hipMemcpyHostToDevice));
             const int32_t end = cm[i].dstBeg + m;
-            HIPCHK(c, hipMemcpy((int32_t*)b->cloudEnd.p + j, &end, 4, hipMemcpyHostToDevice));
+            HIPCHK(c, hipMemcpy(b->cloudEnd + j, &end, 4, hipMemcpyHostToDevice));
             b->cntH[j] = m;
             b->upStats[1]++;
         }
@@ -205,7 +205,7 @@ int run_jobs(drfe_ctx* c, PmBuffers* b, const std::vector<Job>& jobs, const std:
 
 PmBuffers* maps_of(drfe_ctx* c, const char* who)
 {
-    PmBuffers* b = static_cast<PmBuffers*>(c->pm);
+    PmBuffers* b = c->pm;
     if (!b || b->maps < 1) { c->err = std::string(who) + ": no maps uploaded (drfe_plane_map_upload)"; return nullptr; }
     return b;
 }
@@ -215,17 +215,17 @@ PmBuffers* maps_of(drfe_ctx* c, const char* who)
 int drfe_pm_push_planes(drfe_ctx* c, PmBuffers* b)
 {
     const size_t P = b->cntH.size();
-    int rc;
-    if ((rc = drfe_pm_grow(c, b->mapCoefs, P * 16)) || (rc = drfe_pm_grow(c, b->mapBad, P)) || (rc = drfe_pm_grow(c, b->cloudBeg, P * 4)) ||
-        (rc = drfe_pm_grow(c, b->cloudEnd, P * 4)))
-        return rc;
+    HIPCHK(c, drfe_pm_reserve(b->mapCoefs, P * 4));
+    HIPCHK(c, drfe_pm_reserve(b->mapBad, P));
+    HIPCHK(c, drfe_pm_reserve(b->cloudBeg, P));
+    HIPCHK(c, drfe_pm_reserve(b->cloudEnd, P));
     std::vector<int32_t> end(P);
     for (size_t j = 0; j < P; j++) end[j] = b->begH[j] + b->cntH[j];
     if (P) {
-        HIPCHK(c, hipMemcpy(b->mapCoefs.p, b->coefsH.data(), P * 16, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(b->mapBad.p, b->badH.data(), P, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(b->cloudBeg.p, b->begH.data(), P * 4, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(b->cloudEnd.p, end.data(), P * 4, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(b->mapCoefs, b->coefsH.data(), P * 16, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(b->mapBad, b->badH.data(), P, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(b->cloudBeg, b->begH.data(), P * 4, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemcpy(b->cloudEnd, end.data(), P * 4, hipMemcpyHostToDevice));
     }
     drfe_pm_chunks(b);
     return DRFE_OK;
@@ -236,15 +236,6 @@ void drfe_pm_chunks(PmBuffers* b)
     b->mapChunks.assign(b->maps, 0);
     for (int s = 0; s < b->maps; s++)
         for (int j = b->planeOff[s]; j < b->planeOff[s + 1]; j++) b->mapChunks[s] += (b->cntH[j] + PM_CHUNK - 1) / PM_CHUNK;
-}
-
-void drfe_pm_free_upkeep(PmBuffers* b)
-{
-    DevBuf* dev[] = {&b->upSrc, &b->upPose, &b->upRec, &b->upIn, &b->upOut, &b->upRecs, &b->upTmp, &b->upPosL, &b->upPosR,
-                     &b->upList, &b->upCounts, &b->upMove};
-    for (DevBuf* d : dev)
-        if (d->p) (void)hipFree(d->p);
-    if (b->upHost.p) (void)hipHostFree(b->upHost.p);
 }
 
 extern "C" {
@@ -311,7 +302,7 @@ int drfe_plane_map_update_batch(drfe_ctx* c, int nframes, const int32_t* frame_m
             c->err = "plane_map_update_batch: map_idx NULL needs the frames of the most recent drfe_plane_match_batch";
             return DRFE_ERR_STATE;
         }
-        if (Q) HIPCHK(c, hipMemcpy(mi.data(), static_cast<const char*>(b->io.p) + b->offMap, (size_t)Q * 4, hipMemcpyDeviceToHost));
+        if (Q) HIPCHK(c, hipMemcpy(mi.data(), b->io + b->offMap, (size_t)Q * 4, hipMemcpyDeviceToHost));
     }
     std::vector<Job> jobs;
     std::vector<MpSeg> segs;
@@ -414,7 +405,7 @@ int drfe_plane_map_cloud_download(drfe_ctx* c, int map, int plane, float* xyz, i
     *n = b->cntH[g];
     if (!xyz) return DRFE_OK;
     if (*n > cap) { c->err = "plane_map_cloud_download: buffer too small"; return DRFE_ERR_CAPACITY; }
-    if (*n) HIPCHK(c, hipMemcpy(xyz, (const float*)b->cloud.p + 3 * (size_t)b->begH[g], (size_t)*n * 12, hipMemcpyDeviceToHost));
+    if (*n) HIPCHK(c, hipMemcpy(xyz, b->cloud + 3 * (size_t)b->begH[g], (size_t)*n * 12, hipMemcpyDeviceToHost));
     return DRFE_OK;
 }
 

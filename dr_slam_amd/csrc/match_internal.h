@@ -27,22 +27,25 @@ struct MatchQuery {
     uint32_t desc[8];
 };
 
+/* The matcher scratch.  Plain pointers on purpose: the launchers read it by value, and the per-frame flow (capi.cpp,
+ * frame_enqueue) launches on a copy whose pair and map-point pointers it points into its own upload block, so the struct
+ * is a copyable view and drfe_match_buffers_free releases what drfe_match_buffers allocated. */
 struct MatchBuffers {
-    MatchPair* d_pairs;
-    MatchQuery* d_queries;
-    drfe_map_point* d_mps;
-    float* d_scale;           /* mvScaleFactors */
-    uint32_t* d_candIdx;      /* [query][DRFE_MATCH_MAX_CAND]: keypoint index | octave << 24 */
-    uint32_t* d_candKey;      /* distance << 22 | visit position */
-    int* d_candCnt;
-    uint2* d_candBest;        /* per query: (min key, its keypoint index | octave << 24) */
-    uint16_t* d_hist;         /* rotation histogram entries per pair: (bin, idx) */
-    uint8_t* d_initObs;       /* [maxKp] staging of caller-supplied claim flags */
-    int32_t* d_bfIdx; int32_t* d_bfDist; uint8_t* d_bfQ; uint8_t* d_bfT; size_t bfCap; /* elements / bytes */
-    size_t queryCap;          /* queries the buffers hold */
+    MatchPair* d_pairs = nullptr;
+    MatchQuery* d_queries = nullptr;
+    drfe_map_point* d_mps = nullptr;
+    float* d_scale = nullptr;           /* mvScaleFactors */
+    uint32_t* d_candIdx = nullptr;      /* [query][DRFE_MATCH_MAX_CAND]: keypoint index | octave << 24 */
+    uint32_t* d_candKey = nullptr;      /* distance << 22 | visit position */
+    int* d_candCnt = nullptr;
+    uint2* d_candBest = nullptr;        /* per query: (min key, its keypoint index | octave << 24) */
+    uint16_t* d_hist = nullptr;         /* rotation histogram entries per pair: (bin, idx) */
+    uint8_t* d_initObs = nullptr;       /* [maxKp] staging of caller-supplied claim flags */
+    int32_t* d_bfIdx = nullptr; int32_t* d_bfDist = nullptr; uint8_t* d_bfQ = nullptr; uint8_t* d_bfT = nullptr; size_t bfCap = 0;   /* elements / bytes */
+    size_t queryCap = 0;                /* queries the buffers hold */
     /* pinned staging ring of drfe_match_consecutive_batch: pairs + poses of a batch travel from here, so the call needs
      * no stream synchronisation; an event per slot guards its reuse two calls later */
-    void* h_stage[2]; hipEvent_t stageEv[2]; size_t stageBytes; int stageNext;
+    void* h_stage[2] = {nullptr, nullptr}; hipEvent_t stageEv[2] = {nullptr, nullptr}; size_t stageBytes = 0; int stageNext = 0;
 };
 
 hipError_t drfe_launch_window_match(drfe_ctx* c, const MatchBuffers& mb, const drfe_camera& cam, int npairs,

@@ -11,31 +11,11 @@
 #include <string>
 #include <vector>
 
-#define HIPCHK(c, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
-            return DRFE_ERR_HIP;                                                                \
-        }                                                                                       \
-    } while (0)
-
-struct DevBuf {                     /* grow-only device (or pinned host) allocation */
-    void* p = nullptr;
-    size_t cap = 0;
-};
-
-static inline int drfe_pm_grow(drfe_ctx* c, DevBuf& b, size_t bytes, bool pinned = false)
+/* Every buffer of the maps and batches holds at least 16 bytes: grow `b` to n elements, or to 16 bytes if that is more. */
+template <class T, bool Pinned>
+static inline hipError_t drfe_pm_reserve(HipBuf<T, Pinned>& b, size_t n)
 {
-    bytes = std::max<size_t>(bytes, 16);
-    if (b.cap >= bytes && b.p) return DRFE_OK;
-    if (b.p) (void)(pinned ? hipHostFree(b.p) : hipFree(b.p));
-    b.p = nullptr;
-    b.cap = 0;
-    if (pinned) HIPCHK(c, hipHostMalloc(&b.p, bytes, 0));
-    else HIPCHK(c, hipMalloc(&b.p, bytes));
-    b.cap = bytes;
-    return DRFE_OK;
+    return b.grow(std::max(n, 16 / sizeof(T)));
 }
 
 static inline size_t drfe_align16(size_t n) { return (n + 15) & ~(size_t)15; }
@@ -43,7 +23,9 @@ static inline size_t drfe_align16(size_t n) { return (n + 15) & ~(size_t)15; }
 struct PmBuffers {
     /* the resident maps: per plane coefficients, bad flag and the slot of its cloud in the arena (device copies of the host
      * mirrors below; cloudEnd is also written by the update's commit kernel) */
-    DevBuf mapCoefs, mapBad, cloudBeg, cloudEnd, cloud, points;
+    DevBuf<float> mapCoefs, cloud, points;          /* 4 per plane, xyz per cloud point, xyz per map point */
+    DevBuf<uint8_t> mapBad;
+    DevBuf<int32_t> cloudBeg, cloudEnd;
     std::vector<int32_t> planeOff, pointOff;
     std::vector<float> coefsH;
     std::vector<uint8_t> badH;
@@ -51,13 +33,25 @@ struct PmBuffers {
     std::vector<int64_t> mapChunks;   /* work items of one frame plane against all planes of map s */
     int maps = 0;
     /* one batch: the packed inputs / index outputs (io), the pair arrays, the work list, the accumulators, the flags */
-    DevBuf io, hio, angle, key, work, acc, flags;
+    DevBuf<char> io;
+    PinnedBuf<char> hio;
+    DevBuf<float> angle;
+    DevBuf<uint32_t> key;
+    DevBuf<int4> work;
+    DevBuf<int32_t> acc;                          /* counter [4], nmatches [frames], npairs [frames] */
+    DevBuf<uint8_t> flags;
     hipEvent_t staged = nullptr, done = nullptr;
     int frames = 0, planes = 0, flagged = 0;
     std::vector<int32_t> frameOff, frameMap;
     size_t offMap = 0, offPar = 0, offVer = 0;   /* byte offsets of the three index outputs in io */
     /* map upkeep (map_plane.cpp): frame clouds of a call, one round's staging, gather input and voxel-grid scratch */
-    DevBuf upSrc, upPose, upRec, upHost, upIn, upOut, upRecs, upTmp, upPosL, upPosR, upList, upCounts, upMove;
+    DevBuf<float> upSrc, upPose, upIn, upOut;
+    DevBuf<char> upRec;
+    PinnedBuf<char> upHost;
+    DevBuf<unsigned long long> upRecs, upTmp;
+    DevBuf<uint32_t> upPosL, upPosR;
+    DevBuf<int> upList, upCounts;
+    DevBuf<int4> upMove;
     int64_t upStats[4] = {0, 0, 0, 0};   /* voxel jobs on the device, jobs redone on the host, rounds, arena repacks */
 };
 
@@ -79,6 +73,5 @@ hipError_t drfe_launch_map_plane_move(const int4* moves, int nplanes, int maxN, 
 int drfe_pm_push_planes(drfe_ctx* c, PmBuffers* b);
 /* the match batch's work-list sizes (mapChunks) from the host's cloud sizes */
 void drfe_pm_chunks(PmBuffers* b);
-void drfe_pm_free_upkeep(PmBuffers* b);
 
 #endif

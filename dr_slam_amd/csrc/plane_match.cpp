@@ -24,16 +24,10 @@ bool offsets_ok(const int32_t* off, int n, int64_t total_cap = -1)
 
 void drfe_plane_match_free(drfe_ctx* c)
 {
-    PmBuffers* b = static_cast<PmBuffers*>(c->pm);
+    PmBuffers* b = c->pm;
     if (!b) return;
     if (b->staged) (void)hipEventSynchronize(b->staged);
     if (b->done) (void)hipEventSynchronize(b->done);
-    drfe_pm_free_upkeep(b);
-    DevBuf* dev[] = {&b->mapCoefs, &b->mapBad, &b->cloudBeg, &b->cloudEnd, &b->cloud, &b->points, &b->io, &b->angle, &b->key,
-                     &b->work, &b->acc, &b->flags};
-    for (DevBuf* d : dev)
-        if (d->p) (void)hipFree(d->p);
-    if (b->hio.p) (void)hipHostFree(b->hio.p);
     if (b->staged) (void)hipEventDestroy(b->staged);
     if (b->done) (void)hipEventDestroy(b->done);
     delete b;
@@ -140,13 +134,13 @@ int drfe_plane_map_upload(drfe_ctx* c, int n_maps, const int32_t* plane_offsets,
     }
     const size_t nCloud = nPlanes > 0 ? (size_t)cloud_offsets[nPlanes] : 0;
     HIPCHK(c, hipSetDevice(c->device));
-    PmBuffers* b = static_cast<PmBuffers*>(c->pm);
+    PmBuffers* b = c->pm;
     if (!b) { b = new PmBuffers(); c->pm = b; }
     if (b->done) HIPCHK(c, hipEventSynchronize(b->done));      /* a batch may still read the previous maps */
-    int rc;
-    if ((rc = drfe_pm_grow(c, b->cloud, nCloud * 12)) || (rc = drfe_pm_grow(c, b->points, nPoints * 12))) return rc;
-    if (nCloud) HIPCHK(c, hipMemcpy(b->cloud.p, cloud_xyz, nCloud * 12, hipMemcpyHostToDevice));
-    if (nPoints) HIPCHK(c, hipMemcpy(b->points.p, points_xyz, nPoints * 12, hipMemcpyHostToDevice));
+    HIPCHK(c, drfe_pm_reserve(b->cloud, nCloud * 3));
+    HIPCHK(c, drfe_pm_reserve(b->points, nPoints * 3));
+    if (nCloud) HIPCHK(c, hipMemcpy(b->cloud, cloud_xyz, nCloud * 12, hipMemcpyHostToDevice));
+    if (nPoints) HIPCHK(c, hipMemcpy(b->points, points_xyz, nPoints * 12, hipMemcpyHostToDevice));
     b->maps = n_maps;
     b->planeOff.assign(plane_offsets, plane_offsets + n_maps + 1);
     b->pointOff.assign(point_offsets, point_offsets + n_maps + 1);
@@ -157,7 +151,7 @@ int drfe_plane_map_upload(drfe_ctx* c, int n_maps, const int32_t* plane_offsets,
     for (int j = 0; j < nPlanes; j++) b->cntH[j] = cloud_offsets[j + 1] - cloud_offsets[j];
     b->capH = b->cntH;
     std::fill(b->upStats, b->upStats + 4, 0);
-    if ((rc = drfe_pm_push_planes(c, b))) return rc;
+    if (int rc = drfe_pm_push_planes(c, b)) return rc;
     b->frames = 0;                    /* results of an earlier batch referred to the previous maps */
     return DRFE_OK;
 }
@@ -167,7 +161,7 @@ int drfe_plane_match_batch(drfe_ctx* c, const drfe_plane_match_params* params, i
                            const int32_t* par_idx, const int32_t* ver_idx, int flag_points, void* stream)
 {
     if (!c) return DRFE_ERR_INVALID;
-    PmBuffers* b = static_cast<PmBuffers*>(c->pm);
+    PmBuffers* b = c->pm;
     if (!b || b->maps < 1) { c->err = "plane_match_batch: no maps uploaded (drfe_plane_map_upload)"; return DRFE_ERR_STATE; }
     if (!params || nframes < 1 || !frame_map || !Tcw || !plane_offsets || plane_offsets[0] != 0 || !offsets_ok(plane_offsets, nframes)) {
         c->err = "plane_match_batch: invalid argument";
@@ -199,12 +193,14 @@ int drfe_plane_match_batch(drfe_ctx* c, const drfe_plane_match_params* params, i
     if (!b->done) HIPCHK(c, hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
     HIPCHK(c, hipEventSynchronize(b->staged));          /* the previous batch's staging is free again */
     const size_t nPoints = (size_t)b->pointOff[b->maps];
-    int rc;
-    if ((rc = drfe_pm_grow(c, b->hio, oEnd, true)) || (rc = drfe_pm_grow(c, b->io, oEnd)) || (rc = drfe_pm_grow(c, b->angle, (size_t)pairs * 4)) ||
-        (rc = drfe_pm_grow(c, b->key, (size_t)pairs * 4)) || (rc = drfe_pm_grow(c, b->work, (size_t)workCap * sizeof(int4))) ||
-        (rc = drfe_pm_grow(c, b->acc, (4 + 2 * (size_t)nframes) * 4)) || (rc = drfe_pm_grow(c, b->flags, nPoints)))
-        return rc;
-    char* h = static_cast<char*>(b->hio.p);
+    HIPCHK(c, drfe_pm_reserve(b->hio, oEnd));
+    HIPCHK(c, drfe_pm_reserve(b->io, oEnd));
+    HIPCHK(c, drfe_pm_reserve(b->angle, (size_t)pairs));
+    HIPCHK(c, drfe_pm_reserve(b->key, (size_t)pairs));
+    HIPCHK(c, drfe_pm_reserve(b->work, (size_t)workCap));
+    HIPCHK(c, drfe_pm_reserve(b->acc, 4 + 2 * (size_t)nframes));
+    HIPCHK(c, drfe_pm_reserve(b->flags, nPoints));
+    char* h = b->hio;
     std::memcpy(h + oT, Tcw, (size_t)nframes * 64);
     if (Q) std::memcpy(h + oC, coefs, (size_t)Q * 16);
     int32_t* qf = reinterpret_cast<int32_t*>(h + oQ);
@@ -229,12 +225,12 @@ int drfe_plane_match_batch(drfe_ctx* c, const drfe_plane_match_params* params, i
         else std::fill(outs[k], outs[k] + Q, -1);
     }
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, hipMemcpyAsync(b->io.p, b->hio.p, oEnd, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(b->io, b->hio, oEnd, hipMemcpyHostToDevice, s));
     HIPCHK(c, hipEventRecord(b->staged, s));
-    HIPCHK(c, hipMemsetAsync(b->acc.p, 0, (4 + 2 * (size_t)nframes) * 4, s));
-    if (pairs) HIPCHK(c, hipMemsetAsync(b->key.p, 0xFF, (size_t)pairs * 4, s));
-    if (flag_points && nPoints) HIPCHK(c, hipMemsetAsync(b->flags.p, 0, nPoints, s));
-    char* d = static_cast<char*>(b->io.p);
+    HIPCHK(c, hipMemsetAsync(b->acc, 0, (4 + 2 * (size_t)nframes) * 4, s));
+    if (pairs) HIPCHK(c, hipMemsetAsync(b->key, 0xFF, (size_t)pairs * 4, s));
+    if (flag_points && nPoints) HIPCHK(c, hipMemsetAsync(b->flags, 0, nPoints, s));
+    char* d = b->io;
     PmLaunch L;
     L.Tcw = reinterpret_cast<const float*>(d + oT);
     L.coefs = reinterpret_cast<const float*>(d + oC);
@@ -246,20 +242,20 @@ int drfe_plane_match_batch(drfe_ctx* c, const drfe_plane_match_params* params, i
     L.verOut = reinterpret_cast<int32_t*>(d + oVer);
     L.planeOff = reinterpret_cast<const int32_t*>(d + oO);
     L.pointOff = L.planeOff + b->maps + 1;
-    L.mapCoefs = (const float*)b->mapCoefs.p;
-    L.mapBad = (const uint8_t*)b->mapBad.p;
-    L.cloudBeg = (const int32_t*)b->cloudBeg.p;
-    L.cloudEnd = (const int32_t*)b->cloudEnd.p;
-    L.cloud = (const float*)b->cloud.p;
-    L.points = (const float*)b->points.p;
-    L.angle = (float*)b->angle.p;
-    L.key = (uint32_t*)b->key.p;
-    L.work = (int4*)b->work.p;
+    L.mapCoefs = b->mapCoefs;
+    L.mapBad = b->mapBad;
+    L.cloudBeg = b->cloudBeg;
+    L.cloudEnd = b->cloudEnd;
+    L.cloud = b->cloud;
+    L.points = b->points;
+    L.angle = b->angle;
+    L.key = b->key;
+    L.work = b->work;
     L.workCap = (int)workCap;
-    L.counter = (uint32_t*)b->acc.p;
-    L.nmatches = (int32_t*)b->acc.p + 4;
+    L.counter = reinterpret_cast<uint32_t*>(b->acc.get());
+    L.nmatches = b->acc + 4;
     L.npairs = L.nmatches + nframes;
-    L.flags = (uint8_t*)b->flags.p;
+    L.flags = b->flags;
     L.Q = Q;
     L.maxPts = maxPts;
     L.params = *params;
@@ -280,25 +276,25 @@ int drfe_plane_match_download(drfe_ctx* c, int frame, int32_t* map_idx, int32_t*
                               int* n_pairs)
 {
     if (!c) return DRFE_ERR_INVALID;
-    PmBuffers* b = static_cast<PmBuffers*>(c->pm);
+    PmBuffers* b = c->pm;
     if (!b || frame < 0 || frame >= b->frames) { c->err = "plane_match_download: no such frame"; return DRFE_ERR_INVALID; }
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipEventSynchronize(b->done));
     const int q0 = b->frameOff[frame], P = b->frameOff[frame + 1] - q0;
-    const char* d = static_cast<const char*>(b->io.p);
+    const char* d = b->io;
     int32_t* dst[3] = {map_idx, par_idx, ver_idx};
     const size_t off[3] = {b->offMap, b->offPar, b->offVer};
     for (int k = 0; k < 3; k++)
         if (dst[k] && P > 0) HIPCHK(c, hipMemcpy(dst[k], d + off[k] + (size_t)q0 * 4, (size_t)P * 4, hipMemcpyDeviceToHost));
-    if (nmatches) HIPCHK(c, hipMemcpy(nmatches, (const int32_t*)b->acc.p + 4 + frame, 4, hipMemcpyDeviceToHost));
-    if (n_pairs) HIPCHK(c, hipMemcpy(n_pairs, (const int32_t*)b->acc.p + 4 + b->frames + frame, 4, hipMemcpyDeviceToHost));
+    if (nmatches) HIPCHK(c, hipMemcpy(nmatches, b->acc + 4 + frame, 4, hipMemcpyDeviceToHost));
+    if (n_pairs) HIPCHK(c, hipMemcpy(n_pairs, b->acc + 4 + b->frames + frame, 4, hipMemcpyDeviceToHost));
     return DRFE_OK;
 }
 
 int drfe_plane_flags_download(drfe_ctx* c, int map, uint8_t* flags)
 {
     if (!c) return DRFE_ERR_INVALID;
-    PmBuffers* b = static_cast<PmBuffers*>(c->pm);
+    PmBuffers* b = c->pm;
     if (!b || b->frames < 1 || !b->flagged || map < 0 || map >= b->maps || !flags) {
         c->err = "plane_flags_download: no flags of such a map (drfe_plane_match_batch with flag_points)";
         return DRFE_ERR_INVALID;
@@ -306,7 +302,7 @@ int drfe_plane_flags_download(drfe_ctx* c, int map, uint8_t* flags)
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipEventSynchronize(b->done));
     const int p0 = b->pointOff[map], n = b->pointOff[map + 1] - p0;
-    if (n > 0) HIPCHK(c, hipMemcpy(flags, (const uint8_t*)b->flags.p + p0, (size_t)n, hipMemcpyDeviceToHost));
+    if (n > 0) HIPCHK(c, hipMemcpy(flags, b->flags + p0, (size_t)n, hipMemcpyDeviceToHost));
     return DRFE_OK;
 }
 

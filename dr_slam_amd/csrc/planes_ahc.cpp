@@ -40,15 +40,6 @@
 #include <vector>
 #include <string>
 
-#define HIPCHK(c, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
-            return DRFE_ERR_HIP;                                                                \
-        }                                                                                       \
-    } while (0)
-
 namespace {
 
 struct Node {
@@ -281,36 +272,21 @@ struct PlaneLane {
     PlanesScratch* ps = nullptr;
     hipStream_t stream = nullptr;
     struct VoxelDevice* vox = nullptr;      /* drfe_planes_ahc_post_batch: the lane's device voxel grid (post_internal.h) */
-    float* h_coarse = nullptr; size_t coarseCap = 0;   /* pinned: a frame's voxel clouds as the device extractor's pipeline left them */
+    PinnedBuf<float> h_coarse;              /* a frame's voxel clouds (xyz) as the device extractor's pipeline left them */
 };
-
-static void scratch_free(PlanesScratch*& p)
-{
-    if (!p) return;
-    if (p->d_blocks) (void)hipFree(p->d_blocks);
-    if (p->d_depth) (void)hipFree(p->d_depth);
-    delete p;
-    p = nullptr;
-}
 
 void drfe_planes_free(drfe_ctx* c)
 {
-    scratch_free(c->ps);
-    if (CapeScratch* cs = static_cast<CapeScratch*>(c->cape)) {
-        void* ptrs[] = {cs->d_depth, cs->d_cells, cs->d_seg, cs->d_tab};
-        for (void* p : ptrs)
-            if (p) (void)hipFree(p);
-        delete cs;
-        c->cape = nullptr;
-    }
+    delete c->ps;
+    c->ps = nullptr;
+    delete c->cape;
+    c->cape = nullptr;
     drfe_ahc_arena_free(c);
-    auto* pool = static_cast<std::vector<PlaneLane>*>(c->planeLanes);
-    if (pool) {
+    if (auto* pool = c->planeLanes) {
         for (PlaneLane& l : *pool) {
-            scratch_free(l.ps);
+            delete l.ps;
             if (l.stream) (void)hipStreamDestroy(l.stream);
             drfe_voxel_device_free(l.vox);
-            if (l.h_coarse) (void)hipHostFree(l.h_coarse);
         }
         delete pool;
         c->planeLanes = nullptr;
@@ -322,22 +298,10 @@ template <class Ctx> static int ensure_scratch(Ctx* c, int w, int h)
     if (!c->ps) {
         c->ps = new (std::nothrow) PlanesScratch();
         if (!c->ps) return DRFE_ERR_INVALID;
-        std::memset(c->ps, 0, sizeof(PlanesScratch));
     }
     PlanesScratch* p = c->ps;
-    const size_t nb = (size_t)(w / AHC_WIN) * (h / AHC_WIN), px = (size_t)w * h;
-    if (p->blocksCap < nb) {
-        if (p->d_blocks) (void)hipFree(p->d_blocks);
-        p->d_blocks = nullptr; p->blocksCap = 0;
-        HIPCHK(c, hipMalloc((void**)&p->d_blocks, nb * sizeof(AhcBlockRec)));
-        p->blocksCap = nb;
-    }
-    if (p->depthCap < px) {
-        if (p->d_depth) (void)hipFree(p->d_depth);
-        p->d_depth = nullptr; p->depthCap = 0;
-        HIPCHK(c, hipMalloc((void**)&p->d_depth, px * sizeof(uint16_t)));
-        p->depthCap = px;
-    }
+    HIPCHK(c, p->d_blocks.grow((size_t)(w / AHC_WIN) * (h / AHC_WIN)));
+    HIPCHK(c, p->d_depth.grow((size_t)w * h));
     return DRFE_OK;
 }
 
@@ -675,13 +639,13 @@ int drfe_planes_ahc_batch(drfe_ctx* c, const uint16_t* depth, size_t frame_strid
     int T = n_threads > 0 ? n_threads : std::max(1, drfe_default_host_threads() * 5 / 4);
     T = std::max(1, std::min(T, nframes));
     HIPCHK(c, hipSetDevice(c->device));
-    auto* pool = static_cast<std::vector<PlaneLane>*>(c->planeLanes);
+    auto* pool = c->planeLanes;
     if (!pool) { pool = new std::vector<PlaneLane>(); c->planeLanes = pool; }
     while ((int)pool->size() < T) {
         PlaneLane l;
         l.device = c->device;
         HIPCHK(c, hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
-        pool->push_back(l);
+        pool->push_back(std::move(l));
     }
     /* the extractor on the device, one wavefront per frame (drfe_planes_configure_extractor; same limits as the post batch) */
     if (c->planesDeviceAhc && nframes > 1 && drfe_ahc_device_fits(w, h) && !std::getenv("DRFE_AHC_HOST"))
@@ -760,38 +724,25 @@ struct AhcArena {
     int w = 0, h = 0, frames = 0, cap = 0;
     bool ready = false;       /* every allocation succeeded: a half-built arena is freed, not reused */
     AhcDevParams P;
-    uint16_t* d_depth = nullptr; AhcBlockRec* d_blocks = nullptr;
-    uint8_t* d_scratch = nullptr; size_t slotBytes = 0;      /* per-frame scratch + outputs, one block per slot */
-    AhcDevFrame* d_frames = nullptr; AhcDevFrame* h_frames = nullptr;
-    int* h_out = nullptr; drfe_plane* h_planes = nullptr; int* h_memberOff = nullptr;
-    uint16_t* h_depth = nullptr;                              /* pinned staging of the caller's depth images */
+    DevBuf<uint16_t> d_depth; DevBuf<AhcBlockRec> d_blocks;
+    DevBuf<uint8_t> d_scratch; size_t slotBytes = 0;         /* per-frame scratch + outputs, one block per slot */
+    DevBuf<AhcDevFrame> d_frames; PinnedBuf<AhcDevFrame> h_frames;
+    PinnedBuf<int> h_out; PinnedBuf<drfe_plane> h_planes; PinnedBuf<int> h_memberOff;
+    PinnedBuf<uint16_t> h_depth;                              /* pinned staging of the caller's depth images */
     /* pcl::VoxelGrid behind the extractor (voxel_kernels.hip): every frame's plane clouds, the sort's scratch, centroids, jobs */
-    float* d_vpts = nullptr; unsigned long long* d_vrecs = nullptr; unsigned long long* d_vtmp = nullptr; uint32_t* d_vposL = nullptr;
-    uint32_t* d_vposR = nullptr; float* d_vout = nullptr; int2* d_jobs = nullptr; int* d_vcounts = nullptr; int* d_vlist = nullptr;
-    int2* h_jobs = nullptr; int* h_vcounts = nullptr;
+    DevBuf<float> d_vpts; DevBuf<unsigned long long> d_vrecs, d_vtmp; DevBuf<uint32_t> d_vposL, d_vposR;
+    DevBuf<float> d_vout; DevBuf<int2> d_jobs; DevBuf<int> d_vcounts, d_vlist;
+    PinnedBuf<int2> h_jobs; PinnedBuf<int> h_vcounts;
     /* gates + RANSAC refit behind the voxel grids (refit_kernels.hip): per plane slot the post record and its status */
-    drfe_plane_post* d_post = nullptr; int* d_postStatus = nullptr; uint32_t* d_mtState = nullptr;
-    drfe_plane_post* h_post = nullptr; int* h_postStatus = nullptr;
+    DevBuf<drfe_plane_post> d_post; DevBuf<int> d_postStatus; DevBuf<uint32_t> d_mtState;
+    PinnedBuf<drfe_plane_post> h_post; PinnedBuf<int> h_postStatus;
     /* offsets of the outputs inside a slot */
     size_t offPlanes = 0, offSeg = 0, offMemberOff = 0, offMemberIdx = 0, offOut = 0;
 };
 
-static void arena_free(AhcArena*& a)
-{
-    if (!a) return;
-    void* d[] = {a->d_depth, a->d_blocks, a->d_scratch, a->d_frames, a->d_vpts, a->d_vrecs, a->d_vtmp, a->d_vposL, a->d_vposR, a->d_vout, a->d_jobs, a->d_vcounts, a->d_vlist,
-                 a->d_post, a->d_postStatus, a->d_mtState};
-    for (void* p : d) if (p) (void)hipFree(p);
-    void* hp[] = {a->h_frames, a->h_out, a->h_planes, a->h_memberOff, a->h_depth, a->h_jobs, a->h_vcounts, a->h_post, a->h_postStatus};
-    for (void* p : hp) if (p) (void)hipHostFree(p);
-    delete a;
-    a = nullptr;
-}
-
 void drfe_ahc_arena_free(drfe_ctx* c)
 {
-    AhcArena* a = static_cast<AhcArena*>(c->ahcArena);
-    arena_free(a);
+    delete c->ahcArena;
     c->ahcArena = nullptr;
 }
 
@@ -799,13 +750,12 @@ void drfe_ahc_arena_free(drfe_ctx* c)
 
 static int ensure_arena(drfe_ctx* c, int w, int h, int frames, const float* K4, float depth_factor, float max_point_dist)
 {
-    AhcArena* a = static_cast<AhcArena*>(c->ahcArena);
-    if (a && (!a->ready || a->w != w || a->h != h || a->frames < frames)) { arena_free(a); c->ahcArena = nullptr; }
+    AhcArena* a = c->ahcArena;
+    if (a && (!a->ready || a->w != w || a->h != h || a->frames < frames)) { drfe_ahc_arena_free(c); a = nullptr; }
     if (!a) {
         a = new (std::nothrow) AhcArena();
         if (!a) return DRFE_ERR_INVALID;
         c->ahcArena = a;
-        a->w = w; a->h = h; a->frames = frames;
         const int Nw = w / AHC_WIN, Nh = h / AHC_WIN, NB = Nw * Nh;
         const size_t npx = (size_t)w * h;
         AhcDevParams& P = a->P;
@@ -828,37 +778,37 @@ static int ensure_arena(drfe_ctx* c, int w, int h, int frames, const float* K4, 
         a->offMemberIdx = take(npx * 4); a->offOut = take(16);
         a->slotBytes = off;
         const size_t F = (size_t)frames;
-        HIPCHK(c, hipMalloc((void**)&a->d_depth, npx * 2 * F));
-        HIPCHK(c, hipMalloc((void**)&a->d_blocks, (size_t)NB * sizeof(AhcBlockRec) * F));
-        HIPCHK(c, hipMalloc((void**)&a->d_scratch, a->slotBytes * F));
-        HIPCHK(c, hipMalloc((void**)&a->d_frames, sizeof(AhcDevFrame) * F));
-        HIPCHK(c, hipHostMalloc((void**)&a->h_frames, sizeof(AhcDevFrame) * F, hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc((void**)&a->h_out, 16 * F, hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc((void**)&a->h_planes, (size_t)P.planeCap * sizeof(drfe_plane) * F, hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc((void**)&a->h_memberOff, ((size_t)P.planeCap + 1) * 4 * F, hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc((void**)&a->h_depth, npx * 2 * F, hipHostMallocDefault));
+        HIPCHK(c, a->d_depth.alloc(npx * F));
+        HIPCHK(c, a->d_blocks.alloc((size_t)NB * F));
+        HIPCHK(c, a->d_scratch.alloc(a->slotBytes * F));
+        HIPCHK(c, a->d_frames.alloc(F));
+        HIPCHK(c, a->h_frames.alloc(F));
+        HIPCHK(c, a->h_out.alloc(4 * F));
+        HIPCHK(c, a->h_planes.alloc((size_t)P.planeCap * F));
+        HIPCHK(c, a->h_memberOff.alloc(((size_t)P.planeCap + 1) * F));
+        HIPCHK(c, a->h_depth.alloc(npx * F));
         if (npx * F > (size_t)0x7fffffff) { c->err = "planes_ahc_post_batch: batch too large"; return DRFE_ERR_CAPACITY; }
-        HIPCHK(c, hipMalloc((void**)&a->d_vpts, npx * 12 * F));
-        HIPCHK(c, hipMalloc((void**)&a->d_vrecs, npx * 8 * F));
-        HIPCHK(c, hipMalloc((void**)&a->d_vtmp, npx * 8 * F));
-        HIPCHK(c, hipMalloc((void**)&a->d_vposL, npx * 4 * F));
-        HIPCHK(c, hipMalloc((void**)&a->d_vposR, npx * 4 * F));
-        HIPCHK(c, hipMalloc((void**)&a->d_vout, npx * 12 * F));
-        HIPCHK(c, hipMalloc((void**)&a->d_jobs, sizeof(int2) * P.planeCap * F));
-        HIPCHK(c, hipMalloc((void**)&a->d_vcounts, sizeof(int) * P.planeCap * F));
-        HIPCHK(c, hipMalloc((void**)&a->d_vlist, sizeof(int) * (P.planeCap * F + 2 * 16)));      /* job order of each chunk (<= 16 chunks) */
-        HIPCHK(c, hipHostMalloc((void**)&a->h_jobs, sizeof(int2) * P.planeCap * F, hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc((void**)&a->h_vcounts, sizeof(int) * P.planeCap * F, hipHostMallocDefault));
-        HIPCHK(c, hipMalloc((void**)&a->d_post, sizeof(drfe_plane_post) * P.planeCap * F));
-        HIPCHK(c, hipMalloc((void**)&a->d_postStatus, sizeof(int) * P.planeCap * F));
-        HIPCHK(c, hipHostMalloc((void**)&a->h_post, sizeof(drfe_plane_post) * P.planeCap * F, hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc((void**)&a->h_postStatus, sizeof(int) * P.planeCap * F, hipHostMallocDefault));
+        HIPCHK(c, a->d_vpts.alloc(npx * 3 * F));
+        HIPCHK(c, a->d_vrecs.alloc(npx * F));
+        HIPCHK(c, a->d_vtmp.alloc(npx * F));
+        HIPCHK(c, a->d_vposL.alloc(npx * F));
+        HIPCHK(c, a->d_vposR.alloc(npx * F));
+        HIPCHK(c, a->d_vout.alloc(npx * 3 * F));
+        HIPCHK(c, a->d_jobs.alloc(P.planeCap * F));
+        HIPCHK(c, a->d_vcounts.alloc(P.planeCap * F));
+        HIPCHK(c, a->d_vlist.alloc(P.planeCap * F + 2 * 16));      /* job order of each chunk (<= 16 chunks) */
+        HIPCHK(c, a->h_jobs.alloc(P.planeCap * F));
+        HIPCHK(c, a->h_vcounts.alloc(P.planeCap * F));
+        HIPCHK(c, a->d_post.alloc(P.planeCap * F));
+        HIPCHK(c, a->d_postStatus.alloc(P.planeCap * F));
+        HIPCHK(c, a->h_post.alloc(P.planeCap * F));
+        HIPCHK(c, a->h_postStatus.alloc(P.planeCap * F));
         {
             /* std::mt19937(12345): the state after seeding (its first draw twists it) */
             uint32_t mt[624];
             mt[0] = 12345u;
             for (int i = 1; i < 624; i++) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
-            HIPCHK(c, hipMalloc((void**)&a->d_mtState, sizeof(mt)));
+            HIPCHK(c, a->d_mtState.alloc(624));
             HIPCHK(c, hipMemcpy(a->d_mtState, mt, sizeof(mt), hipMemcpyHostToDevice));
         }
         for (size_t f = 0; f < F; f++) {
@@ -875,6 +825,7 @@ static int ensure_arena(drfe_ctx* c, int w, int h, int frames, const float* K4, 
             g.ptsBase = (int)(npx * f); g.pts = a->d_vpts + 3 * npx * f; g.jobs = a->d_jobs + (size_t)P.planeCap * f;
         }
         HIPCHK(c, hipMemcpy(a->d_frames, a->h_frames, sizeof(AhcDevFrame) * F, hipMemcpyHostToDevice));
+        a->w = w; a->h = h; a->frames = frames;
         a->ready = true;
     }
     AhcDevParams& P = a->P;
@@ -1028,12 +979,9 @@ static void ahc_batch_worker(AhcBatchJob& J, PlaneLane* l)
                 const size_t span = spanEnd - first;
                 size_t extra = 0;
                 for (int i = 0; i < nP; i++) if (vc[i] < 0) extra += (size_t)jobs[i].y;
-                if (e == hipSuccess && l->coarseCap < span + extra) {
-                    if (l->h_coarse) (void)hipHostFree(l->h_coarse);
-                    l->h_coarse = nullptr; l->coarseCap = 0;
+                if (e == hipSuccess && l->h_coarse.capacity() < 3 * (span + extra)) {
                     const size_t capPts = std::max<size_t>(span + extra + (span + extra) / 2, 1 << 15);
-                    e = hipHostMalloc((void**)&l->h_coarse, capPts * 12, hipHostMallocDefault);
-                    if (e == hipSuccess) l->coarseCap = capPts;
+                    e = l->h_coarse.alloc(3 * capPts);
                 }
                 if (e == hipSuccess && span > 0) e = hipMemcpyAsync(l->h_coarse, A->d_vout + 3 * first, span * 12, hipMemcpyDeviceToHost, l->stream);
                 at = span;
@@ -1102,7 +1050,7 @@ static int planes_ahc_post_batch_device(drfe_ctx* c, std::vector<PlaneLane>* poo
     DrfeRange range("drfe:planes batch (upload, block fits, clustering, flood fill, clouds, voxel grids; gates + refit on the pool)");
     int rc = ensure_arena(c, w, h, nframes, K4, depth_factor, max_point_dist);
     if (rc != DRFE_OK) return rc;
-    AhcArena* A = static_cast<AhcArena*>(c->ahcArena);
+    AhcArena* A = c->ahcArena;
     AhcBatchJob J;
     J.c = c; J.A = A; J.pool = pool; J.depth = depth; J.frameStride = frame_stride; J.stride = stride; J.w = w; J.h = h; J.nframes = nframes; J.cap = cap;
     J.K4 = K4; J.depthFactor = depth_factor; J.maxPointDist = max_point_dist; J.distThreshold = dist_threshold;
@@ -1296,13 +1244,13 @@ int drfe_planes_ahc_post_batch(drfe_ctx* c, const uint16_t* depth, size_t frame_
     int T = n_threads > 0 ? n_threads : std::max(1, drfe_default_host_threads() * 5 / 4);
     T = std::max(1, std::min(T, nframes));
     HIPCHK(c, hipSetDevice(c->device));
-    auto* pool = static_cast<std::vector<PlaneLane>*>(c->planeLanes);
+    auto* pool = c->planeLanes;
     if (!pool) { pool = new std::vector<PlaneLane>(); c->planeLanes = pool; }
     while ((int)pool->size() < T) {
         PlaneLane l;
         l.device = c->device;
         HIPCHK(c, hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
-        pool->push_back(l);
+        pool->push_back(std::move(l));
     }
     /* the extractor itself on the device (drfe_planes_configure_extractor; frames of up to 12 800 init blocks and 2^21 pixels:
      * 1280 x 960 included - the kernels' queue capacity and pixel index) */

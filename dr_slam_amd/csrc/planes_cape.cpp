@@ -21,15 +21,6 @@
 #include <cmath>
 #include <cstring>
 
-#define HIPCHK(c, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
-            return DRFE_ERR_HIP;                                                                \
-        }                                                                                       \
-    } while (0)
-
 namespace {
 
 struct PSeg {
@@ -84,7 +75,7 @@ struct CapeLane {
     std::string err;
     int device = 0;
     hipStream_t stream = nullptr;
-    void* cape = nullptr;
+    CapeScratch* cape = nullptr;
     hipEvent_t pollEv = nullptr;      /* drfe_pool_sync: the batch's threads sleep between polls instead of spinning */
 };
 
@@ -106,28 +97,14 @@ static int planes_cape_core(Ctx* c, const float* depth_m, int w, int h, size_t s
     HIPCHK(c, hipSetDevice(c->device));
     const int nh = w / patch, nv = h / patch, ncell = nh * nv, npx = w * h;
     /* device stage: buffers owned by the context (no allocation per frame) */
-    CapeScratch* cs = static_cast<CapeScratch*>(c->cape);
-    if (!cs) { cs = new (std::nothrow) CapeScratch(); if (!cs) return DRFE_ERR_INVALID; std::memset(cs, 0, sizeof(*cs)); c->cape = cs; }
-    if (cs->depthCap < (size_t)npx) {
-        if (cs->d_depth) (void)hipFree(cs->d_depth);
-        if (cs->d_seg) (void)hipFree(cs->d_seg);
-        if (cs->h_depth) (void)hipHostFree(cs->h_depth);
-        if (cs->h_seg) (void)hipHostFree(cs->h_seg);
-        cs->d_depth = nullptr; cs->d_seg = nullptr; cs->h_depth = nullptr; cs->h_seg = nullptr; cs->depthCap = cs->segCap = 0;
-        HIPCHK(c, hipMalloc((void**)&cs->d_depth, (size_t)npx * sizeof(float)));
-        HIPCHK(c, hipMalloc((void**)&cs->d_seg, (size_t)npx));
-        HIPCHK(c, hipHostMalloc((void**)&cs->h_depth, (size_t)npx * sizeof(float), hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc((void**)&cs->h_seg, (size_t)npx, hipHostMallocDefault));
-        cs->depthCap = cs->segCap = (size_t)npx;
-    }
-    if (cs->cellCap < (size_t)ncell) {
-        if (cs->d_cells) (void)hipFree(cs->d_cells);
-        if (cs->h_cells) (void)hipHostFree(cs->h_cells);
-        cs->d_cells = nullptr; cs->h_cells = nullptr; cs->cellCap = 0;
-        HIPCHK(c, hipMalloc((void**)&cs->d_cells, (size_t)ncell * sizeof(CapeCellRec)));
-        HIPCHK(c, hipHostMalloc((void**)&cs->h_cells, (size_t)ncell * sizeof(CapeCellRec), hipHostMallocDefault));
-        cs->cellCap = (size_t)ncell;
-    }
+    CapeScratch* cs = c->cape;
+    if (!cs) { cs = new (std::nothrow) CapeScratch(); if (!cs) return DRFE_ERR_INVALID; c->cape = cs; }
+    HIPCHK(c, cs->d_depth.grow((size_t)npx));
+    HIPCHK(c, cs->d_seg.grow((size_t)npx));
+    HIPCHK(c, cs->h_depth.grow((size_t)npx));
+    HIPCHK(c, cs->h_seg.grow((size_t)npx));
+    HIPCHK(c, cs->d_cells.grow((size_t)ncell));
+    HIPCHK(c, cs->h_cells.grow((size_t)ncell));
     float* d_depth = cs->d_depth;
     CapeCellRec* d_cells = cs->d_cells;
     const float sinCos = (float)std::sqrt(1 - (double)cos_angle_max * (double)cos_angle_max);
@@ -296,17 +273,12 @@ static int planes_cape_core(Ctx* c, const float* depth_m, int w, int h, size_t s
     }
     *n_planes = nFinal;
     const size_t tabBytes = ((rp.size() * sizeof(CapeRefinePlane) + 15) & ~(size_t)15) + (size_t)ncell + boundary.size() + 16;
-    if (cs->tabCap < tabBytes) {
-        if (cs->d_tab) (void)hipFree(cs->d_tab);
-        cs->d_tab = nullptr; cs->tabCap = 0;
-        HIPCHK(c, hipMalloc((void**)&cs->d_tab, tabBytes * 2));
-        cs->tabCap = tabBytes * 2;
-    }
+    if (cs->d_tab.capacity() < tabBytes) HIPCHK(c, cs->d_tab.alloc(tabBytes * 2));
     const size_t offGrid = (rp.size() * sizeof(CapeRefinePlane) + 15) & ~(size_t)15, offBnd = offGrid + (size_t)ncell;
     if (!rp.empty()) HIPCHK(c, hipMemcpyAsync(cs->d_tab, rp.data(), rp.size() * sizeof(CapeRefinePlane), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(cs->d_tab + offGrid, gridEroded.data(), (size_t)ncell, hipMemcpyHostToDevice, c->stream));
     if (!boundary.empty()) HIPCHK(c, hipMemcpyAsync(cs->d_tab + offBnd, boundary.data(), boundary.size(), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, drfe_launch_cape_refine(cs->d_depth, (size_t)w, w, h, K4, patch, reinterpret_cast<const CapeRefinePlane*>(cs->d_tab), nFinal,
+    HIPCHK(c, drfe_launch_cape_refine(cs->d_depth, (size_t)w, w, h, K4, patch, reinterpret_cast<const CapeRefinePlane*>(cs->d_tab.get()), nFinal,
                                       cs->d_tab + offGrid, cs->d_tab + offBnd, cs->d_seg, c->stream));
     HIPCHK(c, cape_sync(c));
     HIPCHK(c, hipMemcpyAsync(cs->h_seg, cs->d_seg, (size_t)npx, hipMemcpyDeviceToHost, c->stream));
@@ -315,54 +287,37 @@ static int planes_cape_core(Ctx* c, const float* depth_m, int w, int h, size_t s
     return DRFE_OK;
 }
 
-static void cape_scratch_free(void*& p)
-{
-    CapeScratch* cs = static_cast<CapeScratch*>(p);
-    if (!cs) return;
-    void* ptrs[] = {cs->d_depth, cs->d_cells, cs->d_seg, cs->d_tab};
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    void* hptrs[] = {cs->h_depth, cs->h_cells, cs->h_seg};
-    for (void* q : hptrs) if (q) (void)hipHostFree(q);
-    delete cs;
-    p = nullptr;
-}
-
 /* device arena of drfe_planes_cape_batch's device path (grow-only, kept by the context) */
 struct CapeBatchArena {
     int frames = 0, w = 0, h = 0, ncell = 0;
     bool withSeg = false;
-    float* d_depth = nullptr; CapeCellRec* d_cells = nullptr; drfe_cape_plane* d_planes = nullptr; uint8_t* d_tabs = nullptr;
-    CapeFrameOut* d_out = nullptr; uint8_t* d_seg = nullptr;
-    float* h_stage[2] = {nullptr, nullptr}; hipEvent_t stageFree[2] = {nullptr, nullptr};      /* pinned upload staging, CAPE_STAGE_FRAMES frames each */
-    drfe_cape_plane* h_planes = nullptr; CapeFrameOut* h_out = nullptr; uint8_t* h_seg = nullptr;
+    DevBuf<float> d_depth; DevBuf<CapeCellRec> d_cells; DevBuf<drfe_cape_plane> d_planes; DevBuf<uint8_t> d_tabs;
+    DevBuf<CapeFrameOut> d_out; DevBuf<uint8_t> d_seg;
+    PinnedBuf<float> h_stage[2]; hipEvent_t stageFree[2] = {nullptr, nullptr};      /* pinned upload staging, CAPE_STAGE_FRAMES frames each */
+    PinnedBuf<drfe_cape_plane> h_planes; PinnedBuf<CapeFrameOut> h_out; PinnedBuf<uint8_t> h_seg;
     hipStream_t stream = nullptr, copyStream = nullptr;
     hipEvent_t kernelsDone = nullptr;
     bool ready = false;       /* every allocation below succeeded: a half-built arena (an allocation failed) is never reused */
 };
 #define CAPE_STAGE_FRAMES 32
 
-static void cape_batch_free(void*& p)
+static void cape_batch_free(CapeBatchArena*& A)
 {
-    CapeBatchArena* A = static_cast<CapeBatchArena*>(p);
     if (!A) return;
-    void* dp[] = {A->d_depth, A->d_cells, A->d_planes, A->d_tabs, A->d_out, A->d_seg};
-    for (void* q : dp) if (q) (void)hipFree(q);
-    void* hp[] = {A->h_stage[0], A->h_stage[1], A->h_planes, A->h_out, A->h_seg};
-    for (void* q : hp) if (q) (void)hipHostFree(q);
     for (hipEvent_t e : A->stageFree) if (e) (void)hipEventDestroy(e);
     if (A->stream) (void)hipStreamDestroy(A->stream);
     if (A->copyStream) (void)hipStreamDestroy(A->copyStream);
     if (A->kernelsDone) (void)hipEventDestroy(A->kernelsDone);
     delete A;
-    p = nullptr;
+    A = nullptr;
 }
 
 void drfe_cape_lanes_free(drfe_ctx* c)
 {
     cape_batch_free(c->capeBatch);
-    auto* pool = static_cast<std::vector<CapeLane>*>(c->capeLanes);
+    auto* pool = c->capeLanes;
     if (!pool) return;
-    for (CapeLane& l : *pool) { cape_scratch_free(l.cape); if (l.stream) (void)hipStreamDestroy(l.stream); if (l.pollEv) (void)hipEventDestroy(l.pollEv); }
+    for (CapeLane& l : *pool) { delete l.cape; if (l.stream) (void)hipStreamDestroy(l.stream); if (l.pollEv) (void)hipEventDestroy(l.pollEv); }
     delete pool;
     c->capeLanes = nullptr;
 }
@@ -376,30 +331,30 @@ static int planes_cape_batch_device(drfe_ctx* c, const float* depth_m, size_t fr
 {
     const int nh = w / patch, nv = h / patch, ncell = nh * nv;
     const size_t npx = (size_t)w * h, tabStride = drfe_cape_tab_bytes(ncell);
-    CapeBatchArena* A = static_cast<CapeBatchArena*>(c->capeBatch);
+    CapeBatchArena* A = c->capeBatch;
     if (!A || !A->ready || A->frames < nframes || A->w != w || A->h != h || A->ncell != ncell || (seg && !A->withSeg)) {
         cape_batch_free(c->capeBatch);
         A = new (std::nothrow) CapeBatchArena();
         if (!A) return DRFE_ERR_INVALID;
         c->capeBatch = A;
-        A->frames = nframes; A->w = w; A->h = h; A->ncell = ncell; A->withSeg = seg != nullptr;
         const size_t F = (size_t)nframes;
-        HIPCHK(c, hipMalloc((void**)&A->d_depth, F * npx * sizeof(float)));
-        HIPCHK(c, hipMalloc((void**)&A->d_cells, F * ncell * sizeof(CapeCellRec)));
-        HIPCHK(c, hipMalloc((void**)&A->d_planes, F * CAPE_DEV_MAXP * sizeof(drfe_cape_plane)));
-        HIPCHK(c, hipMalloc((void**)&A->d_tabs, F * tabStride));
-        HIPCHK(c, hipMalloc((void**)&A->d_out, F * sizeof(CapeFrameOut)));
-        HIPCHK(c, hipMalloc((void**)&A->d_seg, F * npx));
+        HIPCHK(c, A->d_depth.alloc(F * npx));
+        HIPCHK(c, A->d_cells.alloc(F * ncell));
+        HIPCHK(c, A->d_planes.alloc(F * CAPE_DEV_MAXP));
+        HIPCHK(c, A->d_tabs.alloc(F * tabStride));
+        HIPCHK(c, A->d_out.alloc(F));
+        HIPCHK(c, A->d_seg.alloc(F * npx));
         for (int k = 0; k < 2; k++) {
-            HIPCHK(c, hipHostMalloc((void**)&A->h_stage[k], (size_t)CAPE_STAGE_FRAMES * npx * sizeof(float), hipHostMallocDefault));
+            HIPCHK(c, A->h_stage[k].alloc((size_t)CAPE_STAGE_FRAMES * npx));
             HIPCHK(c, hipEventCreateWithFlags(&A->stageFree[k], hipEventDisableTiming));
         }
-        HIPCHK(c, hipHostMalloc((void**)&A->h_planes, F * CAPE_DEV_MAXP * sizeof(drfe_cape_plane), hipHostMallocDefault));
-        HIPCHK(c, hipHostMalloc((void**)&A->h_out, F * sizeof(CapeFrameOut), hipHostMallocDefault));
-        if (seg) HIPCHK(c, hipHostMalloc((void**)&A->h_seg, F * npx, hipHostMallocDefault));
+        HIPCHK(c, A->h_planes.alloc(F * CAPE_DEV_MAXP));
+        HIPCHK(c, A->h_out.alloc(F));
+        if (seg) HIPCHK(c, A->h_seg.alloc(F * npx));
         HIPCHK(c, hipStreamCreateWithFlags(&A->stream, hipStreamNonBlocking));
         HIPCHK(c, hipStreamCreateWithFlags(&A->copyStream, hipStreamNonBlocking));
         HIPCHK(c, hipEventCreateWithFlags(&A->kernelsDone, hipEventDisableTiming));
+        A->frames = nframes; A->w = w; A->h = h; A->ncell = ncell; A->withSeg = seg != nullptr;
         A->ready = true;
     }
     hipStream_t st = A->stream, cs = A->copyStream;
@@ -508,7 +463,7 @@ int drfe_planes_cape_batch(drfe_ctx* c, const float* depth_m, size_t frame_strid
         deviceDone = true;
         if (hostFrames.empty()) return DRFE_OK;
     }
-    auto* pool = static_cast<std::vector<CapeLane>*>(c->capeLanes);
+    auto* pool = c->capeLanes;
     if (!pool) { pool = new std::vector<CapeLane>(); c->capeLanes = pool; }
     while ((int)pool->size() < T) {
         CapeLane l;

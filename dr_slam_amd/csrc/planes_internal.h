@@ -21,17 +21,19 @@ struct CapeCellRec {          /* CAPE PlaneSeg of one PATCH x PATCH cell (src/CA
 };
 
 struct PlanesScratch {
-    AhcBlockRec* d_blocks; size_t blocksCap;   /* device, [slot][Nw*Nh] */
-    uint16_t* d_depth; size_t depthCap;        /* staging for the host-buffer API */
+    DevBuf<AhcBlockRec> d_blocks;     /* device, [slot][Nw*Nh] */
+    DevBuf<uint16_t> d_depth;         /* staging for the host-buffer API */
 };
 
 /* device scratch of drfe_planes_cape, kept by the context between frames (grow-only) */
 struct CapeScratch {
-    float* d_depth; size_t depthCap;           /* w*h metres */
-    CapeCellRec* d_cells; size_t cellCap;
-    uint8_t* d_seg; size_t segCap;             /* w*h labels */
-    uint8_t* d_tab; size_t tabCap;             /* CapeRefinePlane[n] | gridEroded[ncell] | boundary[n][ncell] */
-    float* h_depth; CapeCellRec* h_cells; uint8_t* h_seg;   /* pinned mirrors (sized with the device buffers): the copy calls neither stage nor pin */
+    DevBuf<float> d_depth;            /* w*h metres */
+    DevBuf<CapeCellRec> d_cells;
+    DevBuf<uint8_t> d_seg;            /* w*h labels */
+    DevBuf<uint8_t> d_tab;            /* CapeRefinePlane[n] | gridEroded[ncell] | boundary[n][ncell] */
+    PinnedBuf<float> h_depth;         /* pinned mirrors (sized with the device buffers): the copy calls neither stage nor pin */
+    PinnedBuf<CapeCellRec> h_cells;
+    PinnedBuf<uint8_t> h_seg;
 };
 
 /* ---- CAPE's cell stage on the device (cape_frame_kernels.hip): histogram seeding, cell growing, merging, masks ---- */

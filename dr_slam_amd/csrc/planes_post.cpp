@@ -18,15 +18,6 @@
 #include <string>
 #include <vector>
 
-#define HIPCHK(c, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e__ = (call);                                                                \
-        if (e__ != hipSuccess) {                                                                \
-            (c)->err = std::string(#call) + ": " + hipGetErrorString(e__);                      \
-            return DRFE_ERR_HIP;                                                                \
-        }                                                                                       \
-    } while (0)
-
 namespace {
 
 struct Pt { float x, y, z; };
@@ -353,22 +344,16 @@ struct VoxelDevice {
     hipStream_t stream = nullptr;
     hipEvent_t ev = nullptr;
     size_t cap = 0;               /* points the buffers hold */
-    float* d_pts = nullptr; unsigned long long* d_recs = nullptr; unsigned long long* d_tmp = nullptr;
-    uint32_t* d_posL = nullptr; uint32_t* d_posR = nullptr; float* d_out = nullptr;
-    int2* d_jobs = nullptr; int* d_counts = nullptr; int* d_list = nullptr;
-    float* h_pts = nullptr; float* h_out = nullptr; int2* h_jobs = nullptr; int* h_counts = nullptr;
+    DevBuf<float> d_pts, d_out;
+    DevBuf<unsigned long long> d_recs, d_tmp;
+    DevBuf<uint32_t> d_posL, d_posR;
+    DevBuf<int2> d_jobs;
+    DevBuf<int> d_counts, d_list;
+    PinnedBuf<float> h_pts, h_out;
+    PinnedBuf<int2> h_jobs;
+    PinnedBuf<int> h_counts;
 };
 #define VOX_MAX_JOBS 256
-
-static void voxel_buffers_free(VoxelDevice* v)
-{
-    void* d[] = {v->d_pts, v->d_recs, v->d_tmp, v->d_posL, v->d_posR, v->d_out};
-    for (void* p : d) if (p) (void)hipFree(p);
-    if (v->h_pts) (void)hipHostFree(v->h_pts);
-    if (v->h_out) (void)hipHostFree(v->h_out);
-    v->d_pts = nullptr; v->d_recs = nullptr; v->d_tmp = nullptr; v->d_posL = nullptr; v->d_posR = nullptr; v->d_out = nullptr;
-    v->h_pts = nullptr; v->h_out = nullptr; v->cap = 0;
-}
 
 VoxelDevice* drfe_voxel_device_create(int device, std::string* err)
 {
@@ -376,10 +361,9 @@ VoxelDevice* drfe_voxel_device_create(int device, std::string* err)
     if (!v) return nullptr;
     v->device = device;
     bool ok = hipSetDevice(device) == hipSuccess && hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreateWithFlags(&v->ev, hipEventDisableTiming) == hipSuccess &&
-              hipMalloc((void**)&v->d_jobs, VOX_MAX_JOBS * sizeof(int2)) == hipSuccess && hipMalloc((void**)&v->d_list, (VOX_MAX_JOBS + 2) * sizeof(int)) == hipSuccess && hipMalloc((void**)&v->d_counts, VOX_MAX_JOBS * sizeof(int)) == hipSuccess &&
-              hipHostMalloc((void**)&v->h_jobs, VOX_MAX_JOBS * sizeof(int2), hipHostMallocDefault) == hipSuccess &&
-              hipHostMalloc((void**)&v->h_counts, VOX_MAX_JOBS * sizeof(int), hipHostMallocDefault) == hipSuccess;
+              hipEventCreateWithFlags(&v->ev, hipEventDisableTiming) == hipSuccess && v->d_jobs.alloc(VOX_MAX_JOBS) == hipSuccess &&
+              v->d_list.alloc(VOX_MAX_JOBS + 2) == hipSuccess && v->d_counts.alloc(VOX_MAX_JOBS) == hipSuccess &&
+              v->h_jobs.alloc(VOX_MAX_JOBS) == hipSuccess && v->h_counts.alloc(VOX_MAX_JOBS) == hipSuccess;
     if (!ok) { if (err) *err = "voxel grid lane: allocation failed"; drfe_voxel_device_free(v); return nullptr; }
     return v;
 }
@@ -387,12 +371,6 @@ VoxelDevice* drfe_voxel_device_create(int device, std::string* err)
 void drfe_voxel_device_free(VoxelDevice* v)
 {
     if (!v) return;
-    voxel_buffers_free(v);
-    if (v->d_jobs) (void)hipFree(v->d_jobs);
-    if (v->d_counts) (void)hipFree(v->d_counts);
-    if (v->d_list) (void)hipFree(v->d_list);
-    if (v->h_jobs) (void)hipHostFree(v->h_jobs);
-    if (v->h_counts) (void)hipHostFree(v->h_counts);
     if (v->ev) (void)hipEventDestroy(v->ev);
     if (v->stream) (void)hipStreamDestroy(v->stream);
     delete v;
@@ -413,13 +391,11 @@ static bool voxel_downsample_device(VoxelDevice* v, const std::vector<Pt>* input
     hipError_t e = hipSetDevice(v->device);
     if (e != hipSuccess) return fail("hipSetDevice", e);
     if (v->cap < total) {
-        voxel_buffers_free(v);
+        v->cap = 0;
         const size_t cap = std::max<size_t>(total + total / 4, 1 << 16);
-        if ((e = hipMalloc((void**)&v->d_pts, cap * 12)) != hipSuccess || (e = hipMalloc((void**)&v->d_recs, cap * 8)) != hipSuccess ||
-            (e = hipMalloc((void**)&v->d_tmp, cap * 8)) != hipSuccess || (e = hipMalloc((void**)&v->d_posL, cap * 4)) != hipSuccess ||
-            (e = hipMalloc((void**)&v->d_posR, cap * 4)) != hipSuccess || (e = hipMalloc((void**)&v->d_out, cap * 12)) != hipSuccess ||
-            (e = hipHostMalloc((void**)&v->h_pts, cap * 12, hipHostMallocDefault)) != hipSuccess ||
-            (e = hipHostMalloc((void**)&v->h_out, cap * 12, hipHostMallocDefault)) != hipSuccess)
+        if ((e = v->d_pts.alloc(cap * 3)) != hipSuccess || (e = v->d_recs.alloc(cap)) != hipSuccess || (e = v->d_tmp.alloc(cap)) != hipSuccess ||
+            (e = v->d_posL.alloc(cap)) != hipSuccess || (e = v->d_posR.alloc(cap)) != hipSuccess || (e = v->d_out.alloc(cap * 3)) != hipSuccess ||
+            (e = v->h_pts.alloc(cap * 3)) != hipSuccess || (e = v->h_out.alloc(cap * 3)) != hipSuccess)
             return fail("buffer allocation", e);
         v->cap = cap;
     }
@@ -610,19 +586,19 @@ int drfe_planes_cape_postprocess(drfe_ctx* c, const float* depth_m, int w, int h
 
 static int sn_ensure(drfe_ctx* c, int w, int h, int frames, bool needStage)
 {
-    SnBuffers* b = static_cast<SnBuffers*>(c->sn);
-    if (!b) { b = new SnBuffers(); std::memset(b, 0, sizeof(*b)); c->sn = b; }
-    if (b->frames >= (size_t)frames && b->w == (size_t)w && b->h == (size_t)h && (!needStage || b->d_depth)) return DRFE_OK;
+    SnBuffers* b = c->sn;
+    if (b && b->frames >= (size_t)frames && b->w == (size_t)w && b->h == (size_t)h && (!needStage || b->d_depth)) return DRFE_OK;
     drfe_post_free(c);
-    b = new SnBuffers(); std::memset(b, 0, sizeof(*b)); c->sn = b;
+    b = new SnBuffers();
+    c->sn = b;
     const size_t W = drfe_sn_w(w), H = drfe_sn_h(h), N = W * H, NI = (W + 1) * (H + 1), F = (size_t)frames;
-    HIPCHK(c, hipMalloc((void**)&b->d_cloud, F * N * 3 * sizeof(float)));
-    HIPCHK(c, hipMalloc((void**)&b->d_dist, F * N * sizeof(float)));
-    HIPCHK(c, hipMalloc((void**)&b->d_integ, F * NI * 6 * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&b->d_cnt, F * NI * 2 * sizeof(unsigned)));
-    HIPCHK(c, hipMalloc((void**)&b->d_normals, F * N * 3 * sizeof(float)));
-    HIPCHK(c, hipMalloc((void**)&b->d_recs, F * (W / 2) * (H / 2) * sizeof(drfe_surface_normal)));
-    if (needStage) HIPCHK(c, hipMalloc(&b->d_depth, (size_t)w * h * sizeof(float)));
+    HIPCHK(c, b->d_cloud.alloc(F * N * 3));
+    HIPCHK(c, b->d_dist.alloc(F * N));
+    HIPCHK(c, b->d_integ.alloc(F * NI * 6));
+    HIPCHK(c, b->d_cnt.alloc(F * NI * 2));
+    HIPCHK(c, b->d_normals.alloc(F * N * 3));
+    HIPCHK(c, b->d_recs.alloc(F * (W / 2) * (H / 2)));
+    if (needStage) HIPCHK(c, b->d_depth.alloc((size_t)w * h));
     b->frames = F; b->w = (size_t)w; b->h = (size_t)h;
     return DRFE_OK;
 }
@@ -635,7 +611,7 @@ int drfe_surface_normals(drfe_ctx* c, const float* depth_m, int w, int h, size_t
     HIPCHK(c, hipSetDevice(c->device));
     int rc = sn_ensure(c, w, h, 1, true);
     if (rc != DRFE_OK) return rc;
-    SnBuffers* b = static_cast<SnBuffers*>(c->sn);
+    SnBuffers* b = c->sn;
     const size_t W = drfe_sn_w(w), H = drfe_sn_h(h), nrec = (W / 2) * (H / 2);
     *n_out = (int)nrec;
     if (out && (size_t)cap < nrec) { c->err = "surface_normals: output buffer too small"; return DRFE_ERR_CAPACITY; }
@@ -659,7 +635,7 @@ int drfe_surface_normals_batch(drfe_ctx* c, const uint16_t* d_depth, size_t fram
     HIPCHK(c, hipSetDevice(c->device));
     int rc = sn_ensure(c, w, h, nframes, false);
     if (rc != DRFE_OK) return rc;
-    SnBuffers* b = static_cast<SnBuffers*>(c->sn);
+    SnBuffers* b = c->sn;
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
     hipError_t e = drfe_launch_surface_normals(d_depth, 1, depth_factor, frame_stride, row_stride, w, h, K4, max_point_dist, nframes, *b, s);
     if (e != hipSuccess) { c->err = std::string("surface_normals_batch: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
@@ -670,7 +646,7 @@ int drfe_surface_normals_batch(drfe_ctx* c, const uint16_t* d_depth, size_t fram
 int drfe_surface_normals_download(drfe_ctx* c, int slot, drfe_surface_normal* out, int cap, int* n_out)
 {
     if (!c) return DRFE_ERR_INVALID;
-    SnBuffers* b = static_cast<SnBuffers*>(c->sn);
+    SnBuffers* b = c->sn;
     if (!b || slot < 0 || (size_t)slot >= b->frames || !n_out) { c->err = "surface_normals_download: no such slot"; return DRFE_ERR_INVALID; }
     const size_t W = drfe_sn_w((int)b->w), H = drfe_sn_h((int)b->h), nrec = (W / 2) * (H / 2);
     *n_out = (int)nrec;
@@ -686,11 +662,6 @@ int drfe_surface_normals_download(drfe_ctx* c, int slot, drfe_surface_normal* ou
 
 void drfe_post_free(drfe_ctx* c)
 {
-    SnBuffers* b = static_cast<SnBuffers*>(c->sn);
-    if (!b) return;
-    void* ptrs[] = {b->d_cloud, b->d_dist, b->d_integ, b->d_cnt, b->d_normals, b->d_recs, b->d_depth};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    delete b;
+    delete c->sn;
     c->sn = nullptr;
 }

@@ -8,15 +8,15 @@ static inline int drfe_sn_w(int w) { return (w + 2) / 3; }
 static inline int drfe_sn_h(int h) { return (h + 2) / 3; }
 
 struct SnBuffers {            /* device scratch of the surface-normal pass, [frame][...] */
-    float* d_cloud;           /* W*H x 3 */
-    float* d_dist;            /* W*H: depth-change seeds, then the chamfer distance */
-    double* d_integ;          /* (W+1)*(H+1) x 6 */
-    unsigned* d_cnt;          /* (W+1)*(H+1) x 2 */
-    float* d_normals;         /* W*H x 3 */
-    drfe_surface_normal* d_recs;   /* (W/2)*(H/2) */
-    void* d_depth;            /* staging of the host-buffer entry point */
-    size_t frames, w, h;      /* capacity */
-    int lastFrames;           /* frames of the most recent drfe_surface_normals_batch (drfe_manhattan_track_batch reads them) */
+    DevBuf<float> d_cloud;    /* W*H x 3 */
+    DevBuf<float> d_dist;     /* W*H: depth-change seeds, then the chamfer distance */
+    DevBuf<double> d_integ;   /* (W+1)*(H+1) x 6 */
+    DevBuf<unsigned> d_cnt;   /* (W+1)*(H+1) x 2 */
+    DevBuf<float> d_normals;  /* W*H x 3 */
+    DevBuf<drfe_surface_normal> d_recs;   /* (W/2)*(H/2) */
+    DevBuf<float> d_depth;    /* staging of the host-buffer entry point */
+    size_t frames = 0, w = 0, h = 0;      /* capacity */
+    int lastFrames = 0;       /* frames of the most recent drfe_surface_normals_batch (drfe_manhattan_track_batch reads them) */
 };
 
 hipError_t drfe_launch_surface_normals(const void* d_depth, int isU16, float factor, size_t frameStride, size_t rowStride, int w,
