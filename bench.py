@@ -7,8 +7,11 @@ SearchByProjection(frame k, frame k-1) for every consecutive pair of the batch (
 N>1: one process per GPU (torch.distributed, backend nccl == RCCL), every rank runs its own sequence —
 no data-path collective; timing is barrier + synchronize on both sides, max over ranks.
 
-Prints ONE JSON line (rank 0) with the contract fields plus `roofline` (dominant kernel, HIP-event
-timed) and `cpu_baseline` (the CPU oracle timed on this host, single thread, bounded sample).
+Prints ONE JSON line (rank 0) with the contract fields.  A plain run does only what those need: it sets up, warms up, times the
+steps and writes --dump-outputs.  `--full` adds everything else the bench measures or checks: per-stage kernel times and
+`roofline` (dominant kernel, HIP-event timed), the slot parity check against the CPU oracle and, at one rank, the other scenes,
+the host-fed rates, `cpu_baseline` (the CPU oracle timed on this host, single thread, bounded sample), config 3's whole
+front-end and the per-frame latency (config 5: its line / plane report); --no-extras / --no-cpu-baseline trim that.
 """
 from __future__ import annotations
 
@@ -729,6 +732,64 @@ def per_frame_latency(cam_name, frames: int = 240, discard: int = 20):
                     "holding hundreds of frames at once (full_frontend), not one.  Compare with cpu_baseline.shapes.ii_orb_lsd_ahc_3threads."}
 
 
+def stage_roofline(fe, cam, B: int, config: int, stage_ms: dict):
+    """--full: HBM roofline of the step's dominant kernel - its stage's algorithmic bytes for the batch over
+    its per-stage HIP-event time - with its HBM traffic and VALU issue utilisation from the committed counter passes.
+    -> (roofline, algorithmic bytes per frame by stage)"""
+    # FAST runs as two launches (k_fast_cells_cols<8> over the cells of <= 8 rows per lane, <12> over the rest): each has its
+    # own event pair and its share of the FAST read (every pixel of the detection region belongs to exactly one cell)
+    cells, px = fe.ctx.fast_partition(cam.w, cam.h)
+    algo_bytes = dict(ALGO_BYTES)
+    if (cam.w, cam.h) != (640, 480):
+        # SURVEY.md section 8(d)'s per-frame figures are functions of the level sizes: the same formulas on this geometry
+        lv = [fe.ctx.pyramid_level(0, l).shape for l in range(fe.ctx.nlevels)]          # bordered (h + 38, w + 38)
+        interior = [(h - 38) * (w - 38) for h, w in lv]
+        algo_bytes["pyramid"] = cam.w * cam.h + sum(h * w for h, w in lv) + sum(interior[:-1])
+        algo_bytes["fast"] = sum(interior)
+        algo_bytes["blur"] = 2 * sum(interior)
+    tot = float(px.sum())
+    fast_all = algo_bytes["fast"]
+    algo_bytes["fast"] = fast_all * float(px[0]) / tot
+    algo_bytes["fast_b"] = fast_all * float(px[1]) / tot
+    cand = {k: stage_ms[k] for k in algo_bytes if stage_ms.get(k, 0.0) > 0}
+    dom = max(stage_ms, key=lambda k: stage_ms[k])
+    roof_stage = dom if dom in cand else max(cand, key=lambda k: cand[k])
+    algo = algo_bytes[roof_stage] * B
+    achieved = algo / (stage_ms[roof_stage] * 1e-3) / 1e9
+    # HBM traffic and VALU utilisation of that kernel from the committed PMC passes (rocprofv3 --pmc, separate runs;
+    # cannot be collected from inside this process). Only valid for the same batch size.
+    traffic, traffic_src, valu, valu_cyc = None, None, None, 4.0
+    kname = {"pyramid": "k_pyr_resize_lds", "fast": "k_fast_cells_cols<8>" if cells[1] else "k_fast_cells",
+             "fast_b": "k_fast_cells_cols<12>", "blur": "k_blur", "desc": "k_orient_desc",
+             "match": "k_window_candidates"}[roof_stage]
+    try:
+        # the newest committed counter passes of this configuration and batch size
+        cands = ["r05_pmc_traffic_c5_b%d.json", "r04_pmc_traffic_c5_b%d.json", "r02_pmc_traffic_c5_b%d.json"] if config == 5 else \
+                ["r06_pmc_traffic_b%d.json", "r05_pmc_traffic_b%d.json", "r04_pmc_traffic_b%d.json", "r03_pmc_traffic_b%d.json", "r02_pmc_traffic_b%d.json"]
+        pmc_name = next((c % B for c in cands if os.path.exists(os.path.join(ROOT, "profiles", c % B))), cands[-1] % B)
+        pmc = json.load(open(os.path.join(ROOT, "profiles", pmc_name)))
+        if pmc.get("batch") == B and kname in pmc["kernels"] and roof_stage != "pyramid":
+            k = pmc["kernels"][kname]
+            traffic = float(k["HBM_BYTES_per_launch"])
+            traffic_src = "profiles/%s (2 x FETCH_SIZE + WRITE_SIZE: the gfx950 half-count correction, calibrated, see its _about)" % pmc_name
+            valu = k.get("valu_issue_utilisation")
+            valu_cyc = k.get("cycles_per_valu_instruction", 4.0)
+    except Exception:
+        pass
+    roofline = {"bound": "hbm", "limited_by": "valu issue (byte-wise image work: %s of the kernel's cycles issue VALU "
+                                              "instructions; see profiles/)" % ("%.0f %%" % (100 * valu) if valu else "most"),
+                "kernel": kname, "kernel_stage": roof_stage, "dominant_stage": dom,
+                "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
+                "traffic": traffic, "traffic_source": traffic_src,
+                "kernel_ms": stage_ms[roof_stage],
+                "algorithmic_bytes_per_launch": algo,
+                "valu_issue_utilisation": valu,
+                "valu_source": "SQ_INSTS_VALU x %.2f cycles (the kernel's own mix priced with the measured per-instruction issue costs: "
+                               "profiles/r03_valu_issue.txt, tools/valu_mix.py) / 1024 SIMDs against SQ_BUSY_CYCLES / 32 "
+                               "(tools/pmc_traffic.py)" % valu_cyc}
+    return roofline, algo_bytes
+
+
 def launch(args) -> int:
     """`--gpus N` without a launcher around us: start N fresh rank processes (one per GPU) BEFORE this process makes
     any GPU call - the parent never initialises HIP, it only counts devices - and pass rank 0's JSON line through.
@@ -829,8 +890,13 @@ def main():
                     help="untimed steps of the TIMED loop's own shape (all contexts in flight) before the warm-up: the device's clocks and the contexts the "
                          "single-context preload never touched settle under the load the timed region will apply (measured: 20 timed steps straight after "
                          "the preload 2.06-2.10 ms per step, after 300 such steps 1.92; a 1000-step run 1.88); 0 under a profiler")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the host-fed rate and the config-3 full front-end block")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-stage kernel times and the roofline, the slot parity check against the CPU oracle and, "
+                         "at one rank, the other scenes, host-fed rates, CPU baseline, config 3's whole front-end and the per-frame latency "
+                         "(config 5: its line / plane report)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other scenes, the host-fed rates and the config-3 full front-end block "
+                                                                  "(config 5: its line / plane report)")
     ap.add_argument("--bow", action="store_true", help="also run the vocabulary tree descent in every step")
     ap.add_argument("--full-frontend", action="store_true",
                     help="at --gpus N > 1: after the headline, every rank also runs BASELINE config 3's whole front-end (ORB + LSD + AHC + CAPE + match) on "
@@ -962,16 +1028,17 @@ def main():
         one_at_a_time = {"value": B * n1 / (time.perf_counter() - t1), "unit": "frames/s", "steps": n1,
                          "note": "one context, one batch at a time (measured before the timed loop): what the sum of the per-stage "
                                  "kernel times corresponds to"}
-    # per-stage kernel time: HIP events around every stage on the launch stream
-    fe.ctx.profile_enable(True)
+    # --full: per-stage kernel time, HIP events around every stage on the launch stream
     acc = {}
     reps = max(3, min(args.steps, 10))
-    for _ in range(reps):
-        step(0)                                     # one context, one stream: clean per-kernel times
-        ms = fe.ctx.profile_stage_ms()
-        for k, v in ms.items():
-            acc[k] = acc.get(k, 0.0) + v
-    fe.ctx.profile_enable(False)
+    if args.full:
+        fe.ctx.profile_enable(True)
+        for _ in range(reps):
+            step(0)                                 # one context, one stream: clean per-kernel times
+            ms = fe.ctx.profile_stage_ms()
+            for k, v in ms.items():
+                acc[k] = acc.get(k, 0.0) + v
+        fe.ctx.profile_enable(False)
 
     for _ in range(max(0, args.settle)):            # untimed, the timed loop's own load pattern
         step()
@@ -1003,12 +1070,12 @@ def main():
         if not os.environ.get("DRFE_BENCH_NO_SANITY"):      # kernel experiments with deliberately wrong results
             assert counts.min() > 500 and nm > 100, (counts.min(), nm)
 
-    # Parity at the bench's own size (outside the timed region): the contexts still hold the last batches of the timed loop -
-    # batch-512 results produced with `nfl` batches in flight.  16 random slots of every context are compared with the CPU
+    # --full: parity at the bench's own size (outside the timed region): the contexts still hold the last batches of the timed
+    # loop - batch-512 results produced with `nfl` batches in flight.  16 random slots of every context are compared with the CPU
     # oracle (the checker, never the thing measured): keypoint records and descriptors of slot s and s - 1, match array of s.
     # A mismatch fails the run.
     parity_checked = 0
-    if not os.environ.get("DRFE_BENCH_NO_SANITY"):
+    if args.full and not os.environ.get("DRFE_BENCH_NO_SANITY"):
         from oracle.spot_check import SlotChecker
         from dr_slam_amd.sharding import pingpong_order
         checker = SlotChecker(cam)
@@ -1022,47 +1089,6 @@ def main():
 
     out = None
     if rank == 0:
-        stage_ms = {k: v / reps for k, v in acc.items()}
-        # FAST runs as two launches (k_fast_cells_cols<8> over the cells of <= 8 rows per lane, <12> over the rest): each has its
-        # own event pair and its share of the FAST read (every pixel of the detection region belongs to exactly one cell)
-        cells, px = fe.ctx.fast_partition(cam.w, cam.h)
-        algo_bytes = dict(ALGO_BYTES)
-        if (cam.w, cam.h) != (640, 480):
-            # SURVEY.md section 8(d)'s per-frame figures are functions of the level sizes: the same formulas on this geometry
-            lv = [fe.ctx.pyramid_level(0, l).shape for l in range(fe.ctx.nlevels)]          # bordered (h + 38, w + 38)
-            interior = [(h - 38) * (w - 38) for h, w in lv]
-            algo_bytes["pyramid"] = cam.w * cam.h + sum(h * w for h, w in lv) + sum(interior[:-1])
-            algo_bytes["fast"] = sum(interior)
-            algo_bytes["blur"] = 2 * sum(interior)
-        tot = float(px.sum())
-        fast_all = algo_bytes["fast"]
-        algo_bytes["fast"] = fast_all * float(px[0]) / tot
-        algo_bytes["fast_b"] = fast_all * float(px[1]) / tot
-        cand = {k: stage_ms[k] for k in algo_bytes if stage_ms.get(k, 0.0) > 0}
-        dom = max(stage_ms, key=lambda k: stage_ms[k])
-        roof_stage = dom if dom in cand else max(cand, key=lambda k: cand[k])
-        algo = algo_bytes[roof_stage] * B
-        achieved = algo / (stage_ms[roof_stage] * 1e-3) / 1e9
-        # HBM traffic and VALU utilisation of that kernel from the committed PMC passes (rocprofv3 --pmc, separate runs;
-        # cannot be collected from inside this process). Only valid for the same batch size.
-        traffic, traffic_src, valu, valu_cyc = None, None, None, 4.0
-        kname = {"pyramid": "k_pyr_resize_lds", "fast": "k_fast_cells_cols<8>" if cells[1] else "k_fast_cells",
-                 "fast_b": "k_fast_cells_cols<12>", "blur": "k_blur", "desc": "k_orient_desc",
-                 "match": "k_window_candidates"}[roof_stage]
-        try:
-            # the newest committed counter passes of this configuration and batch size
-            cands = ["r05_pmc_traffic_c5_b%d.json", "r04_pmc_traffic_c5_b%d.json", "r02_pmc_traffic_c5_b%d.json"] if config == 5 else \
-                    ["r06_pmc_traffic_b%d.json", "r05_pmc_traffic_b%d.json", "r04_pmc_traffic_b%d.json", "r03_pmc_traffic_b%d.json", "r02_pmc_traffic_b%d.json"]
-            pmc_name = next((c % B for c in cands if os.path.exists(os.path.join(ROOT, "profiles", c % B))), cands[-1] % B)
-            pmc = json.load(open(os.path.join(ROOT, "profiles", pmc_name)))
-            if pmc.get("batch") == B and kname in pmc["kernels"] and roof_stage != "pyramid":
-                k = pmc["kernels"][kname]
-                traffic = float(k["HBM_BYTES_per_launch"])
-                traffic_src = "profiles/%s (2 x FETCH_SIZE + WRITE_SIZE: the gfx950 half-count correction, calibrated, see its _about)" % pmc_name
-                valu = k.get("valu_issue_utilisation")
-                valu_cyc = k.get("cycles_per_valu_instruction", 4.0)
-        except Exception:
-            pass
         fps = total_frames / el
         out = {
             "metric": "RGB-D frames/sec (extract+match) at %dx%d" % (cam.w, cam.h),
@@ -1073,19 +1099,11 @@ def main():
                        "frames_per_step": world * B, "batches_in_flight_per_gpu": nfl, "distinct_resident_input_batches_per_gpu": nfl,
                        "sequence_frames_per_rank": len(base),
                        "sharding": "one sequence per GPU, no data-path collective"},
-            "stage_ms_per_batch": {k: round(v, 4) for k, v in stage_ms.items()},
-            "roofline": {"bound": "hbm", "limited_by": "valu issue (byte-wise image work: %s of the kernel's cycles issue VALU "
-                                                       "instructions; see profiles/)" % ("%.0f %%" % (100 * valu) if valu else "most"),
-                         "kernel": kname, "kernel_stage": roof_stage, "dominant_stage": dom,
-                         "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
-                         "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel_ms": stage_ms[roof_stage],
-                         "algorithmic_bytes_per_launch": algo,
-                         "valu_issue_utilisation": valu,
-                         "valu_source": "SQ_INSTS_VALU x %.2f cycles (the kernel's own mix priced with the measured per-instruction issue costs: "
-                                        "profiles/r03_valu_issue.txt, tools/valu_mix.py) / 1024 SIMDs against SQ_BUSY_CYCLES / 32 "
-                                        "(tools/pmc_traffic.py)" % valu_cyc},
         }
+        if args.full:
+            stage_ms = {k: v / reps for k, v in acc.items()}
+            out["stage_ms_per_batch"] = {k: round(v, 4) for k, v in stage_ms.items()}
+            out["roofline"], algo_bytes = stage_roofline(fe, cam, B, config, stage_ms)
         if one_at_a_time:
             out["one_batch_at_a_time"] = one_at_a_time
         if dumped:
@@ -1093,42 +1111,43 @@ def main():
         if exchange:
             out["initial_exchange"] = exchange
         out["render"] = {"frames": len(base), "workers": workers, "seconds": round(t_render, 2)}
-        out["parity"] = "bit-exact vs the in-repo CPU oracle; the oracle restates OpenCV 3.4 / Eigen 3.3.7 / PCL 1.9 and is UNPINNED " \
-                        "against the real libraries (none can be built here)"
-        out["parity_checked_slots"] = parity_checked
-        out["parity_check"] = "after the timed loop: %d random slots of each of the %d contexts' last batch (batch %d, %d in flight) " \
-                              "against the CPU oracle - keypoint records, descriptors, SearchByProjection match arrays, identical " \
-                              "bytes; a mismatch fails the run" % (min(16, B - 1), nfl, B, nfl)
-        if config == 5:
-            out["algorithmic_bytes_per_frame"] = {k: int(v) for k, v in algo_bytes.items()}
-            if not args.no_extras:
-                out["aux_per_frame"] = config5_aux(fe.ctx, base, cam)
-        if world == 1 and not args.no_extras and config != 5:
-            out["other_scenes"] = scene_stage_times(B, local_rank)
-            out["other_scenes"]["_about"] = "the same path on the other textures the configs name, one context, one batch at a time: compare with " \
-                                            "stage_ms_per_batch / one_batch_at_a_time of this line (room_boxes)"
-            fps_hf, ms_hf = host_fed_rate(fe, gray, depth, Tcw, Twc, B, max(4, min(args.steps, 10)), dev)
-            out["value_host_fed"] = fps_hf
-            out["host_fed"] = {"ms_per_step": ms_hf, "h2d_bytes_per_step": int(gray.nbytes + depth.nbytes),
-                               "d2h_bytes_per_step": int(B * fe.ctx.max_kp * (28 + 32 + 4) + 8 * B),
-                               "note": "pinned gray + depth H2D on a copy stream overlapped with the previous batch, keypoints / "
-                                       "descriptors / matches D2H; link-bound"}
-            fe2 = FrontEnd(cam, max_batch=B, device=local_rank)
-            fps_sp, ms_sp, thr = host_fed_sparse_rate([fe, fe2], gray, depth, Tcw, Twc, B, max(4, min(args.steps, 10)), dev)
-            fe2.ctx.close()
-            out["host_fed_sparse_depth"] = {"value": fps_sp, "unit": "frames/s", "ms_per_step": ms_sp,
-                                            "h2d_bytes_per_step": int(gray.nbytes + B * fe.ctx.max_kp * 2),
-                                            "d2h_bytes_per_step": int(B * fe.ctx.max_kp * (28 + 32 + 4 + 4) + 12 * B),
-                                            "gather_threads": thr,
-                                            "note": "gray frames only cross the link; the host gathers one raw depth value per keypoint "
-                                                    "(sparse-depth glue), two contexts alternate"}
-        if not args.no_cpu_baseline and world == 1:      # the CPU baseline is reported by the N=1 run only
-            out["cpu_baseline"] = cpu_baseline(base, cam, frames=70 if config == 5 else 220, only_orb=config == 5)
-        if world == 1 and not args.no_extras and config != 5:
-            pipe.close()
-            del gray_t, depth_t, gray_ts, depth_ts
-            out["full_frontend"] = full_frontend("ICL")
-            out["per_frame_latency"] = per_frame_latency("ICL")
+        if args.full:
+            out["parity"] = "bit-exact vs the in-repo CPU oracle; the oracle restates OpenCV 3.4 / Eigen 3.3.7 / PCL 1.9 and is UNPINNED " \
+                            "against the real libraries (none can be built here)"
+            out["parity_checked_slots"] = parity_checked
+            out["parity_check"] = "after the timed loop: %d random slots of each of the %d contexts' last batch (batch %d, %d in flight) " \
+                                  "against the CPU oracle - keypoint records, descriptors, SearchByProjection match arrays, identical " \
+                                  "bytes; a mismatch fails the run" % (min(16, B - 1), nfl, B, nfl)
+            if config == 5:
+                out["algorithmic_bytes_per_frame"] = {k: int(v) for k, v in algo_bytes.items()}
+                if not args.no_extras:
+                    out["aux_per_frame"] = config5_aux(fe.ctx, base, cam)
+            if world == 1 and not args.no_extras and config != 5:
+                out["other_scenes"] = scene_stage_times(B, local_rank)
+                out["other_scenes"]["_about"] = "the same path on the other textures the configs name, one context, one batch at a time: compare with " \
+                                                "stage_ms_per_batch / one_batch_at_a_time of this line (room_boxes)"
+                fps_hf, ms_hf = host_fed_rate(fe, gray, depth, Tcw, Twc, B, max(4, min(args.steps, 10)), dev)
+                out["value_host_fed"] = fps_hf
+                out["host_fed"] = {"ms_per_step": ms_hf, "h2d_bytes_per_step": int(gray.nbytes + depth.nbytes),
+                                   "d2h_bytes_per_step": int(B * fe.ctx.max_kp * (28 + 32 + 4) + 8 * B),
+                                   "note": "pinned gray + depth H2D on a copy stream overlapped with the previous batch, keypoints / "
+                                           "descriptors / matches D2H; link-bound"}
+                fe2 = FrontEnd(cam, max_batch=B, device=local_rank)
+                fps_sp, ms_sp, thr = host_fed_sparse_rate([fe, fe2], gray, depth, Tcw, Twc, B, max(4, min(args.steps, 10)), dev)
+                fe2.ctx.close()
+                out["host_fed_sparse_depth"] = {"value": fps_sp, "unit": "frames/s", "ms_per_step": ms_sp,
+                                                "h2d_bytes_per_step": int(gray.nbytes + B * fe.ctx.max_kp * 2),
+                                                "d2h_bytes_per_step": int(B * fe.ctx.max_kp * (28 + 32 + 4 + 4) + 12 * B),
+                                                "gather_threads": thr,
+                                                "note": "gray frames only cross the link; the host gathers one raw depth value per keypoint "
+                                                        "(sparse-depth glue), two contexts alternate"}
+            if not args.no_cpu_baseline and world == 1:      # the CPU baseline is reported by the N=1 run only
+                out["cpu_baseline"] = cpu_baseline(base, cam, frames=70 if config == 5 else 220, only_orb=config == 5)
+            if world == 1 and not args.no_extras and config != 5:
+                pipe.close()
+                del gray_t, depth_t, gray_ts, depth_ts
+                out["full_frontend"] = full_frontend("ICL")
+                out["per_frame_latency"] = per_frame_latency("ICL")
     if world > 1 and args.full_frontend:
         # the whole front-end, sharded: every rank on its own device (the rehearsal: all on device 0) with its share of the host's CPUs
         pipe.close()

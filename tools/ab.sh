@@ -5,7 +5,7 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 ARGS=${AB_ARGS:-}
 for r in 1 2 3; do
   for l in "$@"; do
-    python tools/bench_variant.py build/$l --no-cpu-baseline --no-extras --distinct 16 $ARGS 2>/dev/null | python -c "
+    python tools/bench_variant.py build/$l --full --no-cpu-baseline --no-extras --distinct 16 $ARGS 2>/dev/null | python -c "
 import sys,json
 for x in sys.stdin:
     if x.startswith('{'):
