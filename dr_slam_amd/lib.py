@@ -46,6 +46,8 @@ SYMBOLS = (
     "drfe_plane_match_batch", "drfe_plane_match_download", "drfe_plane_flags_download",
     "drfe_map_plane_update_host", "drfe_map_plane_rebuild_host", "drfe_plane_map_update_batch", "drfe_plane_map_rebuild_batch",
     "drfe_plane_map_edit", "drfe_plane_map_cloud_download", "drfe_plane_map_update_stats",
+    "drfe_map_point_upkeep_host", "drfe_map_line_upkeep_host", "drfe_map_point_upkeep_batch", "drfe_map_line_upkeep_batch",
+    "drfe_map_upkeep_stats",
 )
 
 FRUSTUM_POINT_DTYPE = np.dtype([("world", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"),
@@ -93,6 +95,26 @@ class Config(C.Structure):
     _fields_ = [("device", C.c_int32), ("max_width", C.c_int32), ("max_height", C.c_int32),
                 ("max_batch", C.c_int32), ("nfeatures", C.c_int32), ("scale_factor", C.c_float),
                 ("nlevels", C.c_int32), ("ini_th_fast", C.c_int32), ("min_th_fast", C.c_int32)]
+
+
+class UpkeepKeyframes(C.Structure):
+    _fields_ = [("n", C.c_int32), ("n_levels", C.c_int32), ("center", C.c_void_p), ("bad", C.c_void_p),
+                ("scale_factors", C.c_void_p)]                                       # drfe_upkeep_keyframes
+
+
+class UpkeepItems(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pad", C.c_int32), ("bad", C.c_void_p), ("obs_offsets", C.c_void_p), ("obs_kf", C.c_void_p),
+                ("obs_desc", C.c_void_p), ("world", C.c_void_p), ("ref_kf", C.c_void_p), ("ref_level", C.c_void_p)]   # drfe_upkeep_items
+
+
+class UpkeepOut(C.Structure):
+    _fields_ = [("best_obs", C.c_void_p), ("desc", C.c_void_p), ("normal", C.c_void_p), ("max_distance", C.c_void_p),
+                ("min_distance", C.c_void_p), ("status", C.c_void_p), ("frustum", C.c_void_p)]              # drfe_upkeep_out
+
+
+UPKEEP_DESCRIPTOR, UPKEEP_NORMAL = 1, 2
+UPKEEP_DEVICE_ROWS = 2048
+UPKEEP_STATS = ("calls", "items", "desc_b4", "desc_b16", "desc_b64", "desc_wg", "desc_host", "normals")
 
 
 class Camera(C.Structure):
@@ -233,6 +255,11 @@ def load() -> C.CDLL:
     L.drfe_plane_map_edit.argtypes = [vp, i32, i32, vp, vp, vp]
     L.drfe_plane_map_cloud_download.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32)]
     L.drfe_plane_map_update_stats.argtypes = [vp, vp]
+    L.drfe_map_point_upkeep_host.argtypes = [i32, vp, vp, vp]
+    L.drfe_map_line_upkeep_host.argtypes = [i32, vp, vp, vp]
+    L.drfe_map_point_upkeep_batch.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.drfe_map_line_upkeep_batch.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.drfe_map_upkeep_stats.argtypes = [vp, vp]
     L.drfe_lsd_segments_host.argtypes = [vp, vp, vp, i32, i32, f64, vp, i32, C.POINTER(i32)]
     L.drfe_lsd_configure.argtypes = [vp, i32]
     L.drfe_lsd_configure_rect.argtypes = [vp, i32]
@@ -452,6 +479,61 @@ def map_plane_rebuild_host(Twc, clouds):
     if rc != 0:
         raise DrfeError(f"drfe_map_plane_rebuild_host failed ({rc})")
     return out[:n.value].copy()
+
+
+def _upkeep_call(fn, head, line, scene, what, frustum):
+    """Packs a scene (dict: kf_center [K, 3], kf_bad [K] or None, scale_factors [L], bad [n] or None, obs_offsets [n + 1],
+    obs_kf [T], obs_desc [T, 32], world [n, 3] float32 (points) / [n, 6] float64 (lines), ref_kf [n], ref_level [n]) into the
+    drfe_upkeep_* records, calls fn(*head, what, kfs, items, out) and returns the outputs as a dict."""
+    a = {}
+
+    def arr(key, dt, shape=None):
+        v = scene.get(key)
+        if v is None:
+            return None
+        v = np.ascontiguousarray(v, dt)
+        a[key] = v if shape is None else v.reshape(shape)
+        return a[key]
+    off = arr("obs_offsets", np.int32, -1)
+    n = len(off) - 1 if off is not None else 0
+    cen = arr("kf_center", np.float32, (-1, 3))
+    sc = arr("scale_factors", np.float32, -1)
+    kfb = arr("kf_bad", np.uint8, -1)
+    kfs = UpkeepKeyframes(len(cen), len(sc), _p(cen), _p(kfb), _p(sc))
+    items = UpkeepItems(n, 0, _p(arr("bad", np.uint8, -1)), _p(off), _p(arr("obs_kf", np.int32, -1)),
+                        _p(arr("obs_desc", np.uint8, (-1, 32))),
+                        _p(arr("world", np.float64 if line else np.float32, (-1, 6 if line else 3))),
+                        _p(arr("ref_kf", np.int32, -1)), _p(arr("ref_level", np.int32, -1)))
+    r = dict(best_obs=np.zeros(n, np.int32), desc=np.zeros((n, 32), np.uint8),
+             normal=np.zeros((n, 3), np.float64 if line else np.float32), max_distance=np.zeros(n, np.float32),
+             min_distance=np.zeros(n, np.float32), status=np.zeros(n, np.uint8))
+    if frustum:
+        r["frustum"] = np.zeros(n, FRUSTUM_LINE_DTYPE if line else FRUSTUM_POINT_DTYPE)
+    out = UpkeepOut(_p(r["best_obs"]), _p(r["desc"]), _p(r["normal"]), _p(r["max_distance"]), _p(r["min_distance"]),
+                    _p(r["status"]), _p(r.get("frustum")))
+    rc = fn(*head, int(what), C.byref(kfs), C.byref(items), C.byref(out), *([None] if head else []))
+    return rc, r
+
+
+def map_point_upkeep_host(scene, what=3, frustum=True):
+    """MapPoint::ComputeDistinctiveDescriptors (what & 1) + UpdateNormalAndDepth (what & 2) of n map points on the host
+    (DESIGN.md section 14); scene as _upkeep_call.  Returns dict(best_obs, desc, normal, max_distance, min_distance, status,
+    frustum)."""
+    L = load()
+    rc, r = _upkeep_call(L.drfe_map_point_upkeep_host, (), False, scene, what, frustum)
+    if rc != 0:
+        raise DrfeError(f"drfe_map_point_upkeep_host failed ({rc})")
+    return r
+
+
+def map_line_upkeep_host(scene, what=3, frustum=True):
+    """MapLine::ComputeDistinctiveDescriptors (what & 1) + UpdateAverageDir (what & 2) of n map lines on the host; as
+    map_point_upkeep_host with world [n, 6] float64 and a float64 normal."""
+    L = load()
+    rc, r = _upkeep_call(L.drfe_map_line_upkeep_host, (), True, scene, what, frustum)
+    if rc != 0:
+        raise DrfeError(f"drfe_map_line_upkeep_host failed ({rc})")
+    return r
 
 
 def manhattan_math(which, x):
@@ -1526,6 +1608,24 @@ class Context:
         st = np.zeros(4, np.int64)
         self._chk(self.L.drfe_plane_map_update_stats(self.h, _p(st)), "drfe_plane_map_update_stats")
         return dict(zip(("device_jobs", "host_jobs", "rounds", "repacks"), st.tolist()))
+
+    def map_point_upkeep_batch(self, scene, what=3, frustum=True):
+        """map_point_upkeep_host on the device (drfe_map_point_upkeep_batch): same outputs, same bits"""
+        rc, r = _upkeep_call(self.L.drfe_map_point_upkeep_batch, (self.h,), False, scene, what, frustum)
+        self._chk(rc, "drfe_map_point_upkeep_batch")
+        return r
+
+    def map_line_upkeep_batch(self, scene, what=3, frustum=True):
+        """map_line_upkeep_host on the device (drfe_map_line_upkeep_batch)"""
+        rc, r = _upkeep_call(self.L.drfe_map_line_upkeep_batch, (self.h,), True, scene, what, frustum)
+        self._chk(rc, "drfe_map_line_upkeep_batch")
+        return r
+
+    def map_upkeep_stats(self):
+        """dict(calls, items, desc_b4, desc_b16, desc_b64, desc_wg, desc_host, normals) since the context was created"""
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_map_upkeep_stats(self.h, _p(st)), "drfe_map_upkeep_stats")
+        return dict(zip(UPKEEP_STATS, st.tolist()))
 
     # --- measurement -------------------------------------------------------------------------------
     def profile_enable(self, on=True):

@@ -925,6 +925,70 @@ int drfe_plane_map_cloud_download(drfe_ctx* ctx, int map, int plane, float* xyz,
  * the sort's heap-sort branch), [2] rounds, [3] arena repacks (clouds that outgrew their slots). */
 int drfe_plane_map_update_stats(drfe_ctx* ctx, int64_t* stats /* 4 */);
 
+/* Map-point and map-line upkeep: MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth (src/MapPoint.cc:288-350,
+ * 376-411) and MapLine::ComputeDistinctiveDescriptors + UpdateAverageDir (src/MapLine.cpp:241-318, 320-362) for n independent
+ * items.  Each item lists its observations in the caller's order (the reference iterates a std::map<KeyFrame*, size_t>, so
+ * pointer order; the adaptor passes GetObservations()'s order): the order decides the tie-break and the float sums.
+ * DESIGN.md section 14.
+ *
+ * `what`: DRFE_UPKEEP_DESCRIPTOR, DRFE_UPKEEP_NORMAL or both (the two halves are independent).
+ * Descriptor: a bad item, one without observations, or one whose observations all name bad keyframes is unchanged; otherwise
+ *   the rows of the observations of non-bad keyframes, in order, and the first row with the strictly least median Hamming
+ *   distance to the rows (its own 0 included; median = element (N - 1) / 2 of the sorted row).  best_obs = that row's index in
+ *   the item's observation list (bad-keyframe observations counted), desc = its 32 bytes.
+ * Normal (every observation counts, bad keyframes too): points sum (X - Ow) / |X - Ow| in float as OpenCV evaluates it, lines
+ *   the endpoints' middle minus Ow normalised in double; divided by the observation count; max = |P - Ow_ref| * scale[ref_level],
+ *   min = max / scale[n_levels - 1] (P = X, or the float middle of a line).  A bad item or one without observations is unchanged.
+ * Every output slot is written: an unchanged half leaves best_obs = -1 and zero bytes / normal / distances; status[i] holds the
+ * DRFE_UPKEEP_* bits of the halves computed.  frustum (optional) gets drfe_frustum_point / drfe_frustum_line records as
+ * Frame::isInFrustum reads them (world, normal, 0.8f * min, 1.2f * max) for items whose normal was computed, zero records
+ * otherwise; with desc they feed drfe_frame_is_in_frustum, drfe_search_by_projection_map and drfe_fuse_search as they stand. */
+enum { DRFE_UPKEEP_DESCRIPTOR = 1, DRFE_UPKEEP_NORMAL = 2 };
+typedef struct drfe_upkeep_keyframes {
+    int32_t n;                   /* keyframes the observations and ref_kf index */
+    int32_t n_levels;            /* mnScaleLevels */
+    const float* center;         /* 3 per keyframe: GetCameraCenter() */
+    const uint8_t* bad;          /* 1 per keyframe: isBad(); NULL = none bad */
+    const float* scale_factors;  /* mvScaleFactors, n_levels entries */
+} drfe_upkeep_keyframes;
+typedef struct drfe_upkeep_items {
+    int32_t n;                   /* items */
+    int32_t pad;
+    const uint8_t* bad;          /* 1 per item: isBad(); NULL = none bad */
+    const int32_t* obs_offsets;  /* n + 1: item i observes [obs_offsets[i], obs_offsets[i + 1]); obs_offsets[0] == 0 */
+    const int32_t* obs_kf;       /* keyframe of each observation */
+    const uint8_t* obs_desc;     /* 32 bytes per observation: pKF->mDescriptors.row(idx) / mLineDescriptors.row(idx) */
+    const void* world;           /* per item: float[3] GetWorldPos() of a point, double[6] (head, tail) of a line */
+    const int32_t* ref_kf;       /* per item: GetReferenceKeyFrame() as a keyframe index */
+    const int32_t* ref_level;    /* per item: the octave of pRefKF->mvKeysUn / mvKeyLines[observations[pRefKF]] (index 0 when
+                                  * the ref keyframe is not among the observations: operator[] on the copy inserts 0) */
+} drfe_upkeep_items;
+typedef struct drfe_upkeep_out {
+    int32_t* best_obs;           /* per item; NULL = not wanted (as every output but status) */
+    uint8_t* desc;               /* 32 per item */
+    void* normal;                /* per item: float[3] (points) or double[3] (lines) */
+    float* max_distance;
+    float* min_distance;
+    uint8_t* status;             /* per item, required */
+    void* frustum;               /* per item: drfe_frustum_point (points) or drfe_frustum_line (lines) */
+} drfe_upkeep_out;
+/* On the host, no context.  DRFE_ERR_INVALID on an argument out of range (offsets, keyframe indices, ref_level of an item
+ * whose normal is computed). */
+int drfe_map_point_upkeep_host(int what, const drfe_upkeep_keyframes* kfs, const drfe_upkeep_items* items, drfe_upkeep_out* out);
+int drfe_map_line_upkeep_host(int what, const drfe_upkeep_keyframes* kfs, const drfe_upkeep_items* items, drfe_upkeep_out* out);
+/* The same on the device: host inputs staged with one copy, the kernels, the results back with one copy; returns with the
+ * outputs written (`stream` NULL = the context's).  Same bits as the host entries.  An item with more than
+ * DRFE_UPKEEP_DEVICE_ROWS descriptor rows has its descriptor computed by the host entry's code during the call (counted). */
+#define DRFE_UPKEEP_DEVICE_ROWS 2048
+int drfe_map_point_upkeep_batch(drfe_ctx* ctx, int what, const drfe_upkeep_keyframes* kfs, const drfe_upkeep_items* items,
+                                drfe_upkeep_out* out, void* stream);
+int drfe_map_line_upkeep_batch(drfe_ctx* ctx, int what, const drfe_upkeep_keyframes* kfs, const drfe_upkeep_items* items,
+                               drfe_upkeep_out* out, void* stream);
+/* Counters since the context was created: stats[0] batch calls, [1] items, [2..5] descriptors computed on the device by
+ * bucket (rows <= 4: four lanes per item, <= 16: sixteen lanes, <= 64: one wavefront, <= DRFE_UPKEEP_DEVICE_ROWS: one
+ * workgroup), [6] descriptors handed back to the host, [7] normals computed on the device. */
+int drfe_map_upkeep_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

@@ -12,6 +12,8 @@
  *   Planar_SLAM::PlaneMatcher          include/PlaneMatcher.h:10-31  - SearchMapByCoefficients and bMatchStatus (host entries)
  *   drfe::FlagMatchedPlanePoints       src/Map.cc:406-431            - Map::FlagMatchedPlanePoints (host entry)
  *   drfe::UpdateCoefficientsAndPoints  src/MapPlane.cc:298-371       - both forms of MapPlane's cloud upkeep (host entries)
+ *   drfe::UpkeepMapPoint / UpkeepMapLine / MapUpkeep  src/MapPoint.cc:288-411, src/MapLine.cpp:241-362 - descriptor and
+ *                                      normal upkeep of map points and lines (host entries; MapUpkeep: the device batch)
  * With -DDRFE_WITH_OPENCV the container types are OpenCV's (cv::Mat, cv::KeyPoint, cv::line_descriptor::KeyLine);
  * without it (this image has no OpenCV) minimal stand-ins with the same member names and memory layout are used, so the
  * header is compiled and exercised here (tests/native/adaptor_caller.cpp, run by tests/test_gpu_native.py).
@@ -25,6 +27,7 @@
 #include <cassert>
 #include <cmath>
 #include <cstring>
+#include <map>
 #include <memory>
 #include <mutex>
 #include <set>
@@ -1750,6 +1753,214 @@ inline void UpdateCoefficientsAndPoints(MapPlaneT& pMP)
         throw std::runtime_error("drfe_map_plane_rebuild_host failed");
     drfe_detail_mp::replace_cloud(pMP, out, n);
 }
+/* MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth (src/MapPoint.cc:288-411) and MapLine::ComputeDistinctiveDescriptors
+ * / UpdateAverageDir (src/MapLine.cpp:241-362) over drfe_map_point_upkeep_host / drfe_map_line_upkeep_host and the batch entries.
+ * Reads only public accessors:
+ *   MapPoint / MapLine: isBad(), GetObservations() (pairs (KeyFrame*, index), iterated in order; a std::map), GetReferenceKeyFrame(),
+ *                       GetWorldPos() (3x1 float Mat / Vector6d)
+ *   KeyFrame:           isBad(), GetCameraCenter() (3x1 float Mat), mDescriptors / mLineDescriptors (rows of 32 bytes),
+ *                       mvKeysUn / mvKeyLines (.octave), mvScaleFactors, mnScaleLevels
+ * observations[pRefKF] is operator[] on the reference's copy: a ref keyframe missing from the observations reads keypoint 0.
+ * MapPoint's mDescriptor / mNormalVector / mfMaxDistance / mfMinDistance are protected, so a point's results are returned
+ * (INTEGRATION.md section 4g shows the two method bodies); MapLine's members are public and written here under its mutexes.
+ * DESIGN.md section 14. */
+struct MapPointUpkeep {
+    int status = 0;                  /* DRFE_UPKEEP_* bits of the halves computed (0: the point is unchanged) */
+    int best_obs = -1;               /* the winning observation's position in GetObservations()'s order */
+    uint8_t descriptor[32] = {0};
+    float normal[3] = {0, 0, 0};
+    float max_distance = 0, min_distance = 0;
+};
+struct MapLineUpkeep {
+    int status = 0;
+    int best_obs = -1;
+    uint8_t descriptor[32] = {0};
+    double normal[3] = {0, 0, 0};
+    float max_distance = 0, min_distance = 0;
+};
+namespace drfe_detail_mu {
+template <class KF> inline const uint8_t* row_of(KF* kf, size_t idx, std::false_type) { return kf->mDescriptors.template ptr<uint8_t>((int)idx); }
+template <class KF> inline const uint8_t* row_of(KF* kf, size_t idx, std::true_type) { return kf->mLineDescriptors.template ptr<uint8_t>((int)idx); }
+template <class KF> inline int octave_of(KF* kf, size_t idx, std::false_type) { return kf->mvKeysUn[idx].octave; }
+template <class KF> inline int octave_of(KF* kf, size_t idx, std::true_type) { return kf->mvKeyLines[idx].octave; }
+template <class P> inline void world_of(const P& m, std::vector<float>& wf, std::vector<double>&, std::false_type)
+{
+    for (int k = 0; k < 3; k++) wf.push_back(m.template ptr<float>(k)[0]);
+}
+template <class P> inline void world_of(const P& v, std::vector<float>&, std::vector<double>& wd, std::true_type)
+{
+    for (int k = 0; k < 6; k++) wd.push_back(v(k));
+}
+
+/* the flat inputs of one call: a keyframe table built from the keyframes the items name, items in the caller's order */
+struct Scene {
+    std::map<const void*, int32_t> index;
+    std::vector<float> center, scale, worldF;
+    std::vector<double> worldD;
+    std::vector<uint8_t> kfBad, bad, desc;
+    std::vector<int32_t> off{0}, obsKf, refKf, refLevel;
+    int nLevels = 0;
+    template <class KF> int32_t kf(KF* p)
+    {
+        const auto r = index.emplace((const void*)p, (int32_t)kfBad.size());
+        if (r.second) {
+            const auto C = p->GetCameraCenter();
+            for (int k = 0; k < 3; k++) center.push_back(C.template ptr<float>(k)[0]);
+            kfBad.push_back(p->isBad() ? 1 : 0);
+        }
+        return r.first->second;
+    }
+    /* item x (null: a bad item without observations, left unchanged) */
+    template <class Line, class ItemT> void add(ItemT* x)
+    {
+        const bool isBad = !x || x->isBad();
+        bad.push_back(isBad ? 1 : 0);
+        int32_t ref = 0, level = 0;
+        if (x) {
+            const auto observations = x->GetObservations();
+            for (const auto& ob : observations) {
+                obsKf.push_back(kf(ob.first));
+                const uint8_t* r = row_of(ob.first, ob.second, Line());
+                desc.insert(desc.end(), r, r + 32);
+            }
+            world_of(x->GetWorldPos(), worldF, worldD, Line());
+            auto* pRef = x->GetReferenceKeyFrame();
+            if (!isBad && !observations.empty() && pRef) {
+                ref = kf(pRef);
+                const auto f = observations.find(pRef);
+                level = octave_of(pRef, f == observations.end() ? (size_t)0 : f->second, Line());
+                if (!nLevels) {
+                    nLevels = pRef->mnScaleLevels;
+                    scale.assign(pRef->mvScaleFactors.begin(), pRef->mvScaleFactors.begin() + nLevels);
+                }
+            }
+        } else {
+            for (int k = 0; k < (Line::value ? 0 : 3); k++) worldF.push_back(0.f);
+            for (int k = 0; k < (Line::value ? 6 : 0); k++) worldD.push_back(0.0);
+        }
+        off.push_back((int32_t)obsKf.size());
+        refKf.push_back(ref);
+        refLevel.push_back(level);
+    }
+    drfe_upkeep_keyframes keyframes() const
+    {
+        return drfe_upkeep_keyframes{(int32_t)kfBad.size(), nLevels ? nLevels : 1, center.data(), kfBad.data(), nLevels ? scale.data() : &one};
+    }
+    drfe_upkeep_items items(bool line) const
+    {
+        return drfe_upkeep_items{(int32_t)bad.size(), 0, bad.data(), off.data(), obsKf.data(), desc.data(),
+                                 line ? (const void*)worldD.data() : (const void*)worldF.data(), refKf.data(), refLevel.data()};
+    }
+    float one = 1.f;
+};
+template <class R> inline drfe_upkeep_out out_of(std::vector<R>& r, std::vector<int32_t>& best, std::vector<uint8_t>& desc, std::vector<uint8_t>& st,
+                                                 std::vector<float>& mx, std::vector<float>& mn, std::vector<double>& nd, std::vector<float>& nf)
+{
+    const size_t n = r.size();
+    best.resize(n); desc.resize(32 * n); st.resize(n); mx.resize(n); mn.resize(n); nd.resize(3 * n); nf.resize(3 * n);
+    return drfe_upkeep_out{best.data(), desc.data(), nullptr, mx.data(), mn.data(), st.data(), nullptr};
+}
+/* runs fn over the items and fills one result per item */
+template <class Line, class R, class ItemT, class Fn>
+inline std::vector<R> run(const std::vector<ItemT*>& v, int what, Fn fn)
+{
+    Scene s;
+    for (ItemT* x : v) s.add<Line>(x);
+    std::vector<R> r(v.size());
+    std::vector<int32_t> best; std::vector<uint8_t> desc, st; std::vector<float> mx, mn, nf; std::vector<double> nd;
+    drfe_upkeep_out o = out_of(r, best, desc, st, mx, mn, nd, nf);
+    o.normal = Line::value ? (void*)nd.data() : (void*)nf.data();
+    const drfe_upkeep_keyframes k = s.keyframes();
+    const drfe_upkeep_items it = s.items(Line::value);
+    fn(what, &k, &it, &o);
+    for (size_t i = 0; i < r.size(); i++) {
+        r[i].status = st[i];
+        r[i].best_obs = best[i];
+        std::memcpy(r[i].descriptor, &desc[32 * i], 32);
+        for (int c = 0; c < 3; c++) r[i].normal[c] = Line::value ? (decltype(r[i].normal[0]))nd[3 * i + c] : (decltype(r[i].normal[0]))nf[3 * i + c];
+        r[i].max_distance = mx[i];
+        r[i].min_distance = mn[i];
+    }
+    return r;
+}
+/* the reference's writes of MapLine's public members, under its mutexes */
+template <class MapLineT> inline void apply_line(MapLineT& ml, const MapLineUpkeep& r)
+{
+    if (r.status & DRFE_UPKEEP_DESCRIPTOR) {
+        std::unique_lock<std::mutex> lock(ml.mMutexFeatures);
+        drfe_cv::Mat d = drfe_cv::mat_u8(1, 32);
+        std::memcpy(d.data, r.descriptor, 32);
+        ml.mLDescriptor = d;
+    }
+    if (r.status & DRFE_UPKEEP_NORMAL) {
+        std::unique_lock<std::mutex> lock(ml.mMutexPos);
+        ml.mfMaxDistance = r.max_distance;
+        ml.mfMinDistance = r.min_distance;
+        for (int k = 0; k < 3; k++) ml.mNormalVector(k) = r.normal[k];
+    }
+}
+}  // namespace drfe_detail_mu
+
+/* pMP->ComputeDistinctiveDescriptors() (what = DRFE_UPKEEP_DESCRIPTOR), pMP->UpdateNormalAndDepth() (DRFE_UPKEEP_NORMAL) or
+ * both, on the host: the results for the caller to assign */
+template <class MapPointT>
+inline MapPointUpkeep UpkeepMapPoint(MapPointT& mp, int what = DRFE_UPKEEP_DESCRIPTOR | DRFE_UPKEEP_NORMAL)
+{
+    const std::vector<MapPointT*> v(1, &mp);
+    return drfe_detail_mu::run<std::false_type, MapPointUpkeep>(v, what, [](int w, const drfe_upkeep_keyframes* k, const drfe_upkeep_items* it, drfe_upkeep_out* o) {
+        if (drfe_map_point_upkeep_host(w, k, it, o) != DRFE_OK) throw std::runtime_error("drfe_map_point_upkeep_host failed");
+    })[0];
+}
+
+/* pML->ComputeDistinctiveDescriptors() / UpdateAverageDir() on the host, written into the line's public members */
+template <class MapLineT>
+inline MapLineUpkeep UpkeepMapLine(MapLineT& ml, int what = DRFE_UPKEEP_DESCRIPTOR | DRFE_UPKEEP_NORMAL)
+{
+    const std::vector<MapLineT*> v(1, &ml);
+    const MapLineUpkeep r = drfe_detail_mu::run<std::true_type, MapLineUpkeep>(v, what, [](int w, const drfe_upkeep_keyframes* k, const drfe_upkeep_items* it, drfe_upkeep_out* o) {
+        if (drfe_map_line_upkeep_host(w, k, it, o) != DRFE_OK) throw std::runtime_error("drfe_map_line_upkeep_host failed");
+    })[0];
+    drfe_detail_mu::apply_line(ml, r);
+    return r;
+}
+
+/* The device batch for the loops over many points or lines (LocalMapping::ProcessNewKeyFrame, SearchInNeighbors, keyframe
+ * creation, loop correction, map load).  Owns its own drfe_ctx: a context is not re-entrant, and LocalMapping runs on its own
+ * thread, so an extractor's or matcher's context must not be borrowed.  Null entries are left unchanged (status 0). */
+class MapUpkeep {
+public:
+    explicit MapUpkeep(int device = 0) : mCtx(Planar_SLAM::drfe_detail::make_ctx(1, 1.2f, 1, 20, 7, 64, 64, 1, device)) {}
+    drfe_ctx* ctx() const { return mCtx.get(); }
+    template <class MapPointT>
+    std::vector<MapPointUpkeep> Points(const std::vector<MapPointT*>& v, int what = DRFE_UPKEEP_DESCRIPTOR | DRFE_UPKEEP_NORMAL)
+    {
+        drfe_ctx* c = mCtx.get();
+        std::lock_guard<std::mutex> lock(mMutex);
+        return drfe_detail_mu::run<std::false_type, MapPointUpkeep>(v, what, [c](int w, const drfe_upkeep_keyframes* k, const drfe_upkeep_items* it, drfe_upkeep_out* o) {
+            Planar_SLAM::drfe_detail::check(drfe_map_point_upkeep_batch(c, w, k, it, o, nullptr), c, "drfe_map_point_upkeep_batch");
+        });
+    }
+    /* the lines' members written as UpkeepMapLine does */
+    template <class MapLineT>
+    std::vector<MapLineUpkeep> Lines(const std::vector<MapLineT*>& v, int what = DRFE_UPKEEP_DESCRIPTOR | DRFE_UPKEEP_NORMAL)
+    {
+        drfe_ctx* c = mCtx.get();
+        std::vector<MapLineUpkeep> r;
+        {
+            std::lock_guard<std::mutex> lock(mMutex);
+            r = drfe_detail_mu::run<std::true_type, MapLineUpkeep>(v, what, [c](int w, const drfe_upkeep_keyframes* k, const drfe_upkeep_items* it, drfe_upkeep_out* o) {
+                Planar_SLAM::drfe_detail::check(drfe_map_line_upkeep_batch(c, w, k, it, o, nullptr), c, "drfe_map_line_upkeep_batch");
+            });
+        }
+        for (size_t i = 0; i < v.size(); i++)
+            if (v[i]) drfe_detail_mu::apply_line(*v[i], r[i]);
+        return r;
+    }
+
+private:
+    Planar_SLAM::drfe_detail::CtxPtr mCtx;
+    std::mutex mMutex;
+};
 }  // namespace drfe
 
 #endif /* DRFE_ADAPTOR_HPP */
