@@ -64,6 +64,7 @@ static int upload_geometry(drfe_ctx* c, int w, int h)
     /* no slot holds a frame of this geometry yet: a slot-addressed call on a slot that drfe_frame_submit has not filled
      * (lastBatch only remembers the highest one) finds zero keypoints instead of another geometry's leftovers */
     HIPCHK(c, hipMemset(c->d_kpCount, 0, sizeof(int) * (size_t)c->cfg.max_batch));
+    drfe_bow_slots_invalidate(c, 0, c->cfg.max_batch);
     return DRFE_OK;
 }
 
@@ -355,6 +356,7 @@ int drfe_orb_extract_batch(drfe_ctx* c, const uint8_t* d_gray, size_t frame_stri
     HIPCHK(c, drfe_launch_orb(c, d_gray, frame_stride, row_stride, nframes, s));
     c->lastBatch = nframes;
     c->glueValid = false;
+    drfe_bow_slots_invalidate(c, 0, nframes);         /* new descriptors: the slots' words are stale until transformed again */
     return DRFE_OK;
 }
 
@@ -570,6 +572,7 @@ int drfe_orb_extract(drfe_ctx* c, const uint8_t* gray, int w, int h, size_t stri
     OrbOneShot* o = c->oneShot;
     if (o && o->exec && !o->disabled && !c->profile && o->w == w && o->h == h) {
         for (int y = 0; y < h; y++) std::memcpy(o->h_in + (size_t)y * w, gray + (size_t)y * stride, (size_t)w);
+        drfe_bow_slot_invalidate(c, 0);
         HIPCHK(c, hipGraphLaunch(o->exec, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->lastBatch = 1;
@@ -878,6 +881,7 @@ static int frame_submit_impl(drfe_ctx* c, int slot, const uint8_t* gray, int w, 
             else { if (g) (void)hipGraphDestroy(g); L.exec = nullptr; L.graphOff = true; (void)hipGetLastError(); }
         } else { L.graphOff = true; (void)hipGetLastError(); }
     }
+    drfe_bow_slot_invalidate(c, slot);                /* the submission rewrites the slot's descriptors */
     if (L.exec && !c->profile) HIPCHK(c, hipGraphLaunch(L.exec, s));
     else HIPCHK(c, frame_enqueue(c, L, slot, w, h, s));
     HIPCHK(c, hipEventRecord(L.done, s));

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <map>
 #include <new>
+#include <string>
 
 void drfe_bow_free(drfe_ctx* c)
 {
@@ -23,6 +24,11 @@ void drfe_bow_slot_invalidate(drfe_ctx* c, int slot)
     if (b && slot >= 0 && slot < b->nSlots) b->slotDone[slot] = 0;
 }
 
+void drfe_bow_slots_invalidate(drfe_ctx* c, int first, int count)
+{
+    for (int s = first; s < first + count; s++) drfe_bow_slot_invalidate(c, s);
+}
+
 extern "C" {
 
 int drfe_voc_upload(drfe_ctx* c, int k, int L, int scoring, int weighting, int n_nodes, const int32_t* parent,
@@ -34,14 +40,6 @@ int drfe_voc_upload(drfe_ctx* c, int k, int L, int scoring, int weighting, int n
         c->err = "voc_upload: not a valid vocabulary header";
         return DRFE_ERR_INVALID;
     }
-    HIPCHK(c, hipSetDevice(c->device));
-    drfe_bow_free(c);
-    BowState* b = new (std::nothrow) BowState();
-    if (!b) return DRFE_ERR_INVALID;
-    c->bow = b;
-    b->nSlots = c->cfg.max_batch;
-    b->slotDone = new (std::nothrow) uint8_t[(size_t)b->nSlots]();
-    if (!b->slotDone) return DRFE_ERR_INVALID;
     /* children lists in node-id order, as the loader's m_nodes[pid].children.push_back(nid) builds them */
     std::vector<int> cnt(n_nodes + 1, 0), children(n_nodes - 1), wordId(n_nodes, -1);
     for (int i = 1; i < n_nodes; i++) {
@@ -52,12 +50,29 @@ int drfe_voc_upload(drfe_ctx* c, int k, int L, int scoring, int weighting, int n
         if (cnt[i + 1] > 32) { c->err = "voc_upload: more than 32 children per node"; return DRFE_ERR_INVALID; }
         cnt[i + 1] += cnt[i];
     }
+    /* the descent stops where a node has no children (isLeaf() is children.empty(), TemplatedVocabulary.h) while word ids
+     * follow the file's leaf flags (:1409-1420): a file where the two disagree is not one DBoW2 writes */
+    for (int i = 1; i < n_nodes; i++)
+        if ((is_leaf[i] != 0) != (cnt[i + 1] == cnt[i])) {
+            c->err = "voc_upload: node " + std::to_string(i) + (is_leaf[i] ? " is flagged a leaf but has children"
+                                                                            : " is flagged internal but has no children");
+            return DRFE_ERR_INVALID;
+        }
     std::vector<int> fill(cnt.begin(), cnt.end() - 1);
     int nwords = 0;
     for (int i = 1; i < n_nodes; i++) {
         children[fill[parent[i]]++] = i;
         if (is_leaf[i]) wordId[i] = nwords++;
     }
+    /* the tree is checked before the previous vocabulary goes: a rejected file leaves the context as it was */
+    HIPCHK(c, hipSetDevice(c->device));
+    drfe_bow_free(c);
+    BowState* b = new (std::nothrow) BowState();
+    if (!b) return DRFE_ERR_INVALID;
+    c->bow = b;
+    b->nSlots = c->cfg.max_batch;
+    b->slotDone = new (std::nothrow) uint8_t[(size_t)b->nSlots]();
+    if (!b->slotDone) return DRFE_ERR_INVALID;
     const size_t n = (size_t)n_nodes;
     HIPCHK(c, b->d_vocDesc.alloc(n * 32));
     HIPCHK(c, b->d_vocWeight.alloc(n));

@@ -318,6 +318,7 @@ hipError_t drfe_long_kernel_stream(hipStream_t* s, int part);
 int drfe_default_host_threads();
 void drfe_cape_lanes_free(drfe_ctx* c);                   /* planes_cape.cpp */
 void drfe_bow_slot_invalidate(drfe_ctx* c, int slot);     /* capi_bow.cpp: the slot's descriptors changed (drfe_frame_load) */
+void drfe_bow_slots_invalidate(drfe_ctx* c, int first, int count);   /* ... of slots [first, first + count): every other writer */
 void drfe_one_shot_free(drfe_ctx* c);                    /* capi.cpp: the captured single-frame ORB graph */
 void drfe_frame_lanes_free(drfe_ctx* c);                 /* capi.cpp: staging + graphs of the per-frame pipelined flow */
 

@@ -586,7 +586,9 @@ const char* drfe_shard_last_error(const drfe_shard* shard /* NULL: the calling t
 /* Upload a vocabulary in the node format of TemplatedVocabulary::loadFromTextFile
  * (Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1338-1424): node 0 is the root; for node i >= 1
  * parent[i], is_leaf[i], 32 descriptor bytes, weight.  Children of a node are ordered by node id and
- * word ids are assigned to leaves in node order, exactly as the loader does.  k <= 20, L <= 10. */
+ * word ids are assigned to leaves in node order, exactly as the loader does.  k <= 20, L <= 10, at most 32
+ * children per node.  DRFE_ERR_INVALID when is_leaf[i] disagrees with whether node i has children (a file
+ * DBoW2 never writes); a rejected table leaves the previous vocabulary in place. */
 int drfe_voc_upload(drfe_ctx* ctx, int k, int L, int scoring, int weighting, int n_nodes, const int32_t* parent,
                     const uint8_t* desc, const double* weight, const uint8_t* is_leaf);
 /* Device part of TemplatedVocabulary::transform(features, BowVector, FeatureVector, levelsup) for the
@@ -594,7 +596,10 @@ int drfe_voc_upload(drfe_ctx* ctx, int k, int L, int scoring, int weighting, int
  * L-levelsup.  Asynchronous on `stream`. */
 int drfe_bow_transform_batch(drfe_ctx* ctx, int levelsup, int nframes, void* stream);
 /* The same for the frame in ONE slot (drfe_frame_submit / drfe_frame_load): Frame::ComputeBoW / KeyFrame::ComputeBoW.  The transform
- * is a pure function of descriptors and vocabulary: a keyframe loaded from the host gets the mFeatVec it stored at creation. */
+ * is a pure function of descriptors and vocabulary: a keyframe loaded from the host gets the mFeatVec it stored at creation.
+ * Every call that writes a slot's descriptors (drfe_orb_extract, drfe_orb_extract_batch, drfe_frame_submit(_tracked),
+ * drfe_frame_load, drfe_pipeline_submit) drops the slot's transform: the BoW calls then return DRFE_ERR_STATE for that
+ * slot until it is transformed again. */
 int drfe_bow_transform_slot(drfe_ctx* ctx, int levelsup, int slot, void* stream);
 /* Per-feature results of a slot.  The caller folds them into BowVector / FeatureVector (std::map) in
  * feature order — addWeight's float64 sums depend on that order (BowVector.cpp). */
