@@ -3,6 +3,7 @@
  * copies their results.  There is no CPU fallback — a missing GPU / HIP failure is DRFE_ERR_HIP. */
 #include "drfe_internal.h"
 #include "map_upkeep_internal.h"
+#include "triangulate_internal.h"
 #include <atomic>
 #include "post_internal.h"
 #include "match_internal.h"
@@ -148,6 +149,7 @@ void drfe_destroy(drfe_ctx* c)
     drfe_manhattan_free(c);
     drfe_plane_match_free(c);
     drfe_map_upkeep_free(c);
+    drfe_triangulate_free(c);
     drfe_post_free(c);
     drfe_one_shot_free(c);
     drfe_frame_lanes_free(c);

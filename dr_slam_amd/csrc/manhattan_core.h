@@ -11,6 +11,7 @@
 #define DRFE_MANHATTAN_CORE_H
 
 #include "../../include/drfe_math.h"
+#include "jacobi_svd_core.h"
 
 DRFE_HD void mf_axis_rows(const float R[9], int a, float M[9])
 {
@@ -97,8 +98,8 @@ DRFE_HD void mf_cross(const float a[3], const float b[3], float c[3])
 }
 
 /* cv::SVD::compute(A, W, U, VT) of a 3x3 CV_32F (JacobiSVDImpl_<float>, m = n = n1 = 3, minval = FLT_MIN,
- * eps = 2 * FLT_EPSILON, at most 30 sweeps; At = A^T), then U * VT through the small-matrix gemm (float dots, + 0).
- * hypot(p, beta) is canonicalised to sqrt(p * p + beta * beta) (glibc's last bit is host dependent). */
+ * eps = 2 * FLT_EPSILON, at most 30 sweeps; At = A^T: the shared drfe_jacobi_svd<3>), then U * VT through the small-matrix
+ * gemm (float dots, + 0). */
 DRFE_HD void mf_svd_polar(float R[9])
 {
     const float eps = 2.0f * 1.1920928955078125e-07f;
@@ -107,67 +108,7 @@ DRFE_HD void mf_svd_polar(float R[9])
     double W[3];
     for (int i = 0; i < 3; i++)
         for (int k = 0; k < 3; k++) At[i * 3 + k] = R[k * 3 + i];
-    for (int i = 0; i < 3; i++) {
-        double sd = 0;
-        for (int k = 0; k < 3; k++) { const float t = At[i * 3 + k]; sd += (double)t * t; }
-        W[i] = sd;
-        for (int k = 0; k < 3; k++) Vt[i * 3 + k] = 0.f;
-        Vt[i * 3 + i] = 1.f;
-    }
-    for (int iter = 0; iter < 30; iter++) {
-        bool changed = false;
-        for (int i = 0; i < 2; i++)
-            for (int j = i + 1; j < 3; j++) {
-                float *Ai = At + i * 3, *Aj = At + j * 3;
-                double a = W[i], p = 0, b = W[j];
-                for (int k = 0; k < 3; k++) p += (double)Ai[k] * Aj[k];
-                if (fabs(p) <= (double)eps * sqrt(a * b)) continue;
-                p *= 2;
-                const double beta = a - b, gamma = sqrt(p * p + beta * beta);
-                float c, s;
-                if (beta < 0) {
-                    const double delta = (gamma - beta) * 0.5;
-                    s = (float)sqrt(delta / gamma);
-                    c = (float)(p / (gamma * s * 2));
-                } else {
-                    c = (float)sqrt((gamma + beta) / (gamma * 2));
-                    s = (float)(p / (gamma * c * 2));
-                }
-                a = b = 0;
-                for (int k = 0; k < 3; k++) {
-                    const float t0 = c * Ai[k] + s * Aj[k];
-                    const float t1 = -s * Ai[k] + c * Aj[k];
-                    Ai[k] = t0; Aj[k] = t1;
-                    a += (double)t0 * t0; b += (double)t1 * t1;
-                }
-                W[i] = a; W[j] = b;
-                changed = true;
-                float *Vi = Vt + i * 3, *Vj = Vt + j * 3;
-                for (int k = 0; k < 3; k++) {
-                    const float t0 = c * Vi[k] + s * Vj[k];
-                    const float t1 = -s * Vi[k] + c * Vj[k];
-                    Vi[k] = t0; Vj[k] = t1;
-                }
-            }
-        if (!changed) break;
-    }
-    for (int i = 0; i < 3; i++) {
-        double sd = 0;
-        for (int k = 0; k < 3; k++) { const float t = At[i * 3 + k]; sd += (double)t * t; }
-        W[i] = sqrt(sd);
-    }
-    for (int i = 0; i < 2; i++) {
-        int j = i;
-        for (int k = i + 1; k < 3; k++)
-            if (W[j] < W[k]) j = k;
-        if (i != j) {
-            const double tw = W[i]; W[i] = W[j]; W[j] = tw;
-            for (int k = 0; k < 3; k++) {
-                float t = At[i * 3 + k]; At[i * 3 + k] = At[j * 3 + k]; At[j * 3 + k] = t;
-                t = Vt[i * 3 + k]; Vt[i * 3 + k] = Vt[j * 3 + k]; Vt[j * 3 + k] = t;
-            }
-        }
-    }
+    drfe_jacobi_svd<3>(At, W, Vt);
     /* left singular vectors; a singular value <= FLT_MIN gets cv::RNG(0x12345678)'s random vector, orthogonalised */
     uint64_t rng = 0x12345678u;
     for (int i = 0; i < 3; i++) {

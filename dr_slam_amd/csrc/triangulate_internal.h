@@ -1,0 +1,21 @@
+/* triangulate_internal.h — the records triangulate.cpp stages for triangulate_kernels.hip. */
+#ifndef DRFE_TRIANGULATE_INTERNAL_H
+#define DRFE_TRIANGULATE_INTERNAL_H
+
+#include "drfe_internal.h"
+#include "triangulate_core.h"
+
+/* one match: kf1 (-1 when its pair is skipped), kf2, idx1, idx2 */
+struct TriMatch { int32_t kf1, kf2, idx1, idx2; };
+
+struct TriLaunch {
+    TriView V;
+    const TriMatch* match;
+    int n, line;
+    uint8_t *status, *branch;
+    float* x3d;                        /* 3 / 6 per match */
+};
+hipError_t drfe_launch_triangulate(const TriLaunch& L, hipStream_t s);
+void drfe_triangulate_free(drfe_ctx* c);
+
+#endif

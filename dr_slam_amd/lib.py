@@ -48,6 +48,8 @@ SYMBOLS = (
     "drfe_plane_map_edit", "drfe_plane_map_cloud_download", "drfe_plane_map_update_stats",
     "drfe_map_point_upkeep_host", "drfe_map_line_upkeep_host", "drfe_map_point_upkeep_batch", "drfe_map_line_upkeep_batch",
     "drfe_map_upkeep_stats",
+    "drfe_triangulate_points_host", "drfe_triangulate_lines_host", "drfe_triangulate_points_batch", "drfe_triangulate_lines_batch",
+    "drfe_triangulate_stats", "drfe_debug_triangulate_math",
 )
 
 FRUSTUM_POINT_DTYPE = np.dtype([("world", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"),
@@ -115,6 +117,45 @@ class UpkeepOut(C.Structure):
 UPKEEP_DESCRIPTOR, UPKEEP_NORMAL = 1, 2
 UPKEEP_DEVICE_ROWS = 2048
 UPKEEP_STATS = ("calls", "items", "desc_b4", "desc_b16", "desc_b64", "desc_wg", "desc_host", "normals")
+
+TRI_KF_DTYPE = np.dtype([("Tcw", np.float32, 12), ("Twc", np.float32, 12), ("Ow", np.float32, 3), ("fx", np.float32),
+                         ("fy", np.float32), ("cx", np.float32), ("cy", np.float32), ("invfx", np.float32), ("invfy", np.float32),
+                         ("mb", np.float32), ("mbf", np.float32), ("scale_factor", np.float32)])   # drfe_tri_keyframe
+
+
+class TriKeyframes(C.Structure):
+    _fields_ = [("n", C.c_int32), ("n_levels", C.c_int32), ("kf", C.c_void_p), ("scale_factors", C.c_void_p),
+                ("level_sigma2", C.c_void_p)]                                        # drfe_tri_keyframes
+
+
+class TriKeypoints(C.Structure):
+    _fields_ = [("offsets", C.c_void_p), ("un", C.c_void_p), ("raw", C.c_void_p), ("octave", C.c_void_p),
+                ("u_right", C.c_void_p), ("depth", C.c_void_p)]                      # drfe_tri_keypoints
+
+
+class TriKeylines(C.Structure):
+    _fields_ = [("offsets", C.c_void_p), ("ends", C.c_void_p), ("octave", C.c_void_p), ("depth", C.c_void_p),
+                ("lines3d", C.c_void_p)]                                             # drfe_tri_keylines
+
+
+class TriPairs(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pad", C.c_int32), ("kf1", C.c_void_p), ("kf2", C.c_void_p), ("match_offsets", C.c_void_p),
+                ("matches", C.c_void_p)]                                             # drfe_tri_pairs
+
+
+class TriOut(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("branch", C.c_void_p), ("x3d", C.c_void_p), ("pair_skipped", C.c_void_p),
+                ("accepted", C.c_void_p)]                                            # drfe_tri_out
+
+
+# status codes (DRFE_TRI_*): points and lines share 0-2; the flag marks a line match whose idx2 is past KF1's key lines
+TRI_ACCEPTED, TRI_BASELINE, TRI_NO_PARALLAX = 0, 1, 2
+TRI_POINT_CODES = ("accepted", "baseline", "no_parallax", "w_zero", "z1", "z2", "reproj1", "reproj2", "dist", "scale")
+TRI_LINE_CODES = ("accepted", "baseline", "no_stereo", "z_sp1", "z_ep1", "z_sp2", "z_ep2", "reproj_sp1", "reproj_ep1",
+                  "reproj_sp2", "reproj_ep2", "dist", "scale")
+TRI_IDX2_PAST_KF1 = 0x80
+TRI_BRANCH_NONE, TRI_BRANCH_SVD, TRI_BRANCH_STEREO1, TRI_BRANCH_STEREO2 = 0, 1, 2, 3
+TRI_STATS = ("calls", "pairs", "pairs_skipped", "matches", "svd", "stereo1", "stereo2", "accepted")
 
 
 class Camera(C.Structure):
@@ -260,6 +301,12 @@ def load() -> C.CDLL:
     L.drfe_map_point_upkeep_batch.argtypes = [vp, i32, vp, vp, vp, vp]
     L.drfe_map_line_upkeep_batch.argtypes = [vp, i32, vp, vp, vp, vp]
     L.drfe_map_upkeep_stats.argtypes = [vp, vp]
+    L.drfe_triangulate_points_host.argtypes = [i32, vp, vp, vp, vp]
+    L.drfe_triangulate_lines_host.argtypes = [i32, vp, vp, vp, vp]
+    L.drfe_triangulate_points_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.drfe_triangulate_lines_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    L.drfe_triangulate_stats.argtypes = [vp, vp]
+    L.drfe_debug_triangulate_math.argtypes = [i32, vp, vp, i32, vp]
     L.drfe_lsd_segments_host.argtypes = [vp, vp, vp, i32, i32, f64, vp, i32, C.POINTER(i32)]
     L.drfe_lsd_configure.argtypes = [vp, i32]
     L.drfe_lsd_configure_rect.argtypes = [vp, i32]
@@ -534,6 +581,72 @@ def map_line_upkeep_host(scene, what=3, frustum=True):
     if rc != 0:
         raise DrfeError(f"drfe_map_line_upkeep_host failed ({rc})")
     return r
+
+
+def _tri_call(fn, head, line, scene, monocular=0):
+    """Packs a scene (dict: kf [K] TRI_KF_DTYPE, scale_factors [K, L], level_sigma2 [K, L], offsets [K + 1]; points: un [F, 2],
+    raw [F, 2], octave [F], u_right [F], depth [F]; lines: ends [F, 4], octave [F], depth [F], lines3d [F, 6] float64; pairs:
+    kf1 [P], kf2 [P], match_offsets [P + 1], matches [M, 2]) into the drfe_tri_* records, calls
+    fn(*head, monocular, kfs, features, pairs, out) and returns the outputs as a dict (status, branch, x3d [M, 3 | 6],
+    pair_skipped, accepted)."""
+    keep = []
+
+    def arr(key, dt, shape=-1):
+        v = scene.get(key)
+        if v is None:
+            return None
+        v = np.ascontiguousarray(np.asarray(v, dt).reshape(shape))
+        keep.append(v)
+        return v
+    kf = np.ascontiguousarray(scene["kf"], TRI_KF_DTYPE)
+    keep.append(kf)
+    sc = arr("scale_factors", np.float32, (len(kf), -1))
+    sg = arr("level_sigma2", np.float32, (len(kf), -1))
+    kfs = TriKeyframes(len(kf), sc.shape[1] if sc is not None and len(kf) else 1, _p(kf), _p(sc), _p(sg))
+    off = arr("offsets", np.int32)
+    if line:
+        feats = TriKeylines(_p(off), _p(arr("ends", np.float32, (-1, 4))), _p(arr("octave", np.int32)), _p(arr("depth", np.float32)),
+                            _p(arr("lines3d", np.float64, (-1, 6))))
+    else:
+        feats = TriKeypoints(_p(off), _p(arr("un", np.float32, (-1, 2))), _p(arr("raw", np.float32, (-1, 2))),
+                             _p(arr("octave", np.int32)), _p(arr("u_right", np.float32)), _p(arr("depth", np.float32)))
+    mo = arr("match_offsets", np.int32)
+    P = len(mo) - 1
+    M = int(mo[-1])
+    pairs = TriPairs(P, 0, _p(arr("kf1", np.int32)), _p(arr("kf2", np.int32)), _p(mo), _p(arr("matches", np.int32, (-1, 2))))
+    r = dict(status=np.zeros(M, np.uint8), branch=np.zeros(M, np.uint8), x3d=np.zeros((M, 6 if line else 3), np.float32),
+             pair_skipped=np.zeros(P, np.uint8), accepted=np.zeros(P, np.int32))
+    out = TriOut(_p(r["status"]), _p(r["branch"]), _p(r["x3d"]), _p(r["pair_skipped"]), _p(r["accepted"]))
+    rc = fn(*head, int(monocular), C.byref(kfs), C.byref(feats), C.byref(pairs), C.byref(out), *([None] if head else []))
+    return rc, r
+
+
+def triangulate_points_host(scene, monocular=0):
+    """LocalMapping::CreateNewMapPoints' per-match body on the host (drfe_triangulate_points_host, DESIGN.md section 15);
+    scene as _tri_call"""
+    rc, r = _tri_call(load().drfe_triangulate_points_host, (), False, scene, monocular)
+    if rc != 0:
+        raise DrfeError(f"drfe_triangulate_points_host failed ({rc})")
+    return r
+
+
+def triangulate_lines_host(scene, monocular=0):
+    """LocalMapping::CreateNewMapLines2's per-match body on the host (drfe_triangulate_lines_host)"""
+    rc, r = _tri_call(load().drfe_triangulate_lines_host, (), True, scene, monocular)
+    if rc != 0:
+        raise DrfeError(f"drfe_triangulate_lines_host failed ({rc})")
+    return r
+
+
+def triangulate_math(which, y, x=None):
+    """drfe_atan2f(y, x) (0), drfe_cosf(y) (1), drfe_cosf(2 * drfe_atan2f(y / 2, x)) (2) of include/drfe_math.h, float32"""
+    L = load()
+    y = np.ascontiguousarray(y, np.float32)
+    x = np.ascontiguousarray(np.zeros_like(y) if x is None else x, np.float32)
+    out = np.zeros_like(y)
+    if L.drfe_debug_triangulate_math(which, _p(y), _p(x), len(y), _p(out)) != 0:
+        raise DrfeError("drfe_debug_triangulate_math failed")
+    return out
 
 
 def manhattan_math(which, x):
@@ -1626,6 +1739,24 @@ class Context:
         st = np.zeros(8, np.int64)
         self._chk(self.L.drfe_map_upkeep_stats(self.h, _p(st)), "drfe_map_upkeep_stats")
         return dict(zip(UPKEEP_STATS, st.tolist()))
+
+    def triangulate_points_batch(self, scene, monocular=0):
+        """triangulate_points_host on the device (drfe_triangulate_points_batch): same outputs, same bits"""
+        rc, r = _tri_call(self.L.drfe_triangulate_points_batch, (self.h,), False, scene, monocular)
+        self._chk(rc, "drfe_triangulate_points_batch")
+        return r
+
+    def triangulate_lines_batch(self, scene, monocular=0):
+        """triangulate_lines_host on the device (drfe_triangulate_lines_batch)"""
+        rc, r = _tri_call(self.L.drfe_triangulate_lines_batch, (self.h,), True, scene, monocular)
+        self._chk(rc, "drfe_triangulate_lines_batch")
+        return r
+
+    def triangulate_stats(self):
+        """dict(calls, pairs, pairs_skipped, matches, svd, stereo1, stereo2, accepted) since the context was created"""
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_triangulate_stats(self.h, _p(st)), "drfe_triangulate_stats")
+        return dict(zip(TRI_STATS, st.tolist()))
 
     # --- measurement -------------------------------------------------------------------------------
     def profile_enable(self, on=True):

@@ -994,6 +994,98 @@ int drfe_map_line_upkeep_batch(drfe_ctx* ctx, int what, const drfe_upkeep_keyfra
  * workgroup), [6] descriptors handed back to the host, [7] normals computed on the device. */
 int drfe_map_upkeep_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
 
+/* Map-point and map-line triangulation: the per-match body of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:383-538)
+ * and CreateNewMapLines2 (:875-1026), RGB-D / stereo branch (mbMonocular == false; `monocular` != 0 is rejected), with
+ * KeyFrame::UnprojectStereo and obtain3DLine (src/KeyFrame.cc:788-815).  DESIGN.md section 15.
+ *
+ * A pair is (KF1 = the current keyframe, KF2 = a neighbour) with its matches (idx1, idx2) in vMatchedIndices order; the matching
+ * (SearchForTriangulation), object creation and AddObservation stay with the caller.  A pair is skipped when
+ * (float)cv::norm(Ow2 - Ow1) < KF2's mb.  Per match: the status (DRFE_TRI_ACCEPTED or the code of the `continue` that fired,
+ * one per site, in the reference's order), the branch taken, and the point (x3d[3]) or the line's endpoints (sp, ep: x3d[6],
+ * the floats that the reference's Vector6d widens) of an accepted match, zeros otherwise.
+ * Points: stereo = mvuRight >= 0; a stereo keypoint must have mvDepth > 0 (UnprojectStereo's empty Mat would throw in the
+ *   reference), else DRFE_ERR_INVALID.
+ * Lines: only the stereo branches create a line; bStereo2 reads KF1's mvDepthLine[idx2], as the reference.  When idx2 is past
+ *   KF1's key lines the reference reads out of bounds: the entries take bStereo2 = false and set DRFE_TRI_IDX2_PAST_KF1 in the
+ *   status (the one deliberate deviation). */
+enum {
+    DRFE_TRI_ACCEPTED = 0,
+    DRFE_TRI_BASELINE = 1,        /* the pair was skipped: baseline < pKF2->mb */
+    DRFE_TRI_NO_PARALLAX = 2,     /* points: no stereo and too little parallax; lines: neither end stereo */
+    /* points */
+    DRFE_TRI_W_ZERO = 3,          /* x3D(3) == 0 */
+    DRFE_TRI_Z1 = 4, DRFE_TRI_Z2 = 5, DRFE_TRI_REPROJ1 = 6, DRFE_TRI_REPROJ2 = 7,
+    DRFE_TRI_DIST = 8,            /* dist1 == 0 || dist2 == 0 */
+    DRFE_TRI_SCALE = 9,           /* scale consistency */
+    /* lines */
+    DRFE_TRI_L_Z_SP1 = 3, DRFE_TRI_L_Z_EP1 = 4, DRFE_TRI_L_Z_SP2 = 5, DRFE_TRI_L_Z_EP2 = 6,
+    DRFE_TRI_L_REPROJ_SP1 = 7, DRFE_TRI_L_REPROJ_EP1 = 8, DRFE_TRI_L_REPROJ_SP2 = 9, DRFE_TRI_L_REPROJ_EP2 = 10,
+    DRFE_TRI_L_DIST = 11, DRFE_TRI_L_SCALE = 12,
+    DRFE_TRI_IDX2_PAST_KF1 = 0x80 /* flag (lines): idx2 >= KF1's key-line count, bStereo2 taken as false */
+};
+enum { DRFE_TRI_BRANCH_NONE = 0, DRFE_TRI_BRANCH_SVD = 1, DRFE_TRI_BRANCH_STEREO1 = 2, DRFE_TRI_BRANCH_STEREO2 = 3 };
+typedef struct drfe_tri_keyframe {
+    float Tcw[12];               /* [Rcw | tcw], 3x4 row-major: GetRotation(), GetTranslation() */
+    float Twc[12];               /* the stored Twc's top three rows (UnprojectStereo and obtain3DLine read it) */
+    float Ow[3];                 /* GetCameraCenter() */
+    float fx, fy, cx, cy, invfx, invfy;
+    float mb, mbf;
+    float scale_factor;          /* mfScaleFactor */
+} drfe_tri_keyframe;
+typedef struct drfe_tri_keyframes {
+    int32_t n;                   /* keyframes the pairs index */
+    int32_t n_levels;            /* mnScaleLevels */
+    const drfe_tri_keyframe* kf;
+    const float* scale_factors;  /* n x n_levels: mvScaleFactors */
+    const float* level_sigma2;   /* n x n_levels: mvLevelSigma2 */
+} drfe_tri_keyframes;
+typedef struct drfe_tri_keypoints {
+    const int32_t* offsets;      /* n + 1: keyframe k's keypoints are [offsets[k], offsets[k + 1]) of the arrays below */
+    const float* un;             /* 2 per keypoint: mvKeysUn[i].pt */
+    const float* raw;            /* 2 per keypoint: mvKeys[i].pt (UnprojectStereo reads the distorted keys) */
+    const int32_t* octave;       /* mvKeysUn[i].octave */
+    const float* u_right;        /* mvuRight */
+    const float* depth;          /* mvDepth */
+} drfe_tri_keypoints;
+typedef struct drfe_tri_keylines {
+    const int32_t* offsets;      /* n + 1, as for keypoints */
+    const float* ends;           /* 4 per line: startPointX, startPointY, endPointX, endPointY of mvKeyLines[i] */
+    const int32_t* octave;       /* mvKeyLines[i].octave */
+    const float* depth;          /* mvDepthLine */
+    const double* lines3d;       /* 6 per line: mvLines3D[i] (camera frame) */
+} drfe_tri_keylines;
+typedef struct drfe_tri_pairs {
+    int32_t n;                   /* pairs */
+    int32_t pad;
+    const int32_t* kf1;          /* per pair: the current keyframe */
+    const int32_t* kf2;          /* per pair: the neighbour */
+    const int32_t* match_offsets;/* n + 1: pair p's matches are [match_offsets[p], match_offsets[p + 1]); [0] == 0 */
+    const int32_t* matches;      /* 2 per match: idx1 (KF1), idx2 (KF2) */
+} drfe_tri_pairs;
+typedef struct drfe_tri_out {
+    uint8_t* status;             /* per match, required */
+    uint8_t* branch;             /* per match: DRFE_TRI_BRANCH_*; NULL = not wanted (as every output but status) */
+    float* x3d;                  /* per match: 3 floats (points) or 6 (lines: sp, ep) */
+    uint8_t* pair_skipped;       /* per pair */
+    int32_t* accepted;           /* per pair: matches accepted */
+} drfe_tri_out;
+/* On the host, no context.  DRFE_ERR_INVALID on an argument out of range (keyframe, feature or octave indices, offsets). */
+int drfe_triangulate_points_host(int monocular, const drfe_tri_keyframes* kfs, const drfe_tri_keypoints* kps,
+                                 const drfe_tri_pairs* pairs, drfe_tri_out* out);
+int drfe_triangulate_lines_host(int monocular, const drfe_tri_keyframes* kfs, const drfe_tri_keylines* kls,
+                                const drfe_tri_pairs* pairs, drfe_tri_out* out);
+/* The same on the device, one lane per match: the inputs staged with one copy, the results back with one copy; returns with the
+ * outputs written (`stream` NULL = the context's).  Same bits as the host entries.  The pairs of one call must not depend on
+ * each other's results (the caller keeps CreateNewMap*'s loop over the neighbours of one keyframe: points made for neighbour i
+ * change which keypoints SearchForTriangulation may use for neighbour i + 1). */
+int drfe_triangulate_points_batch(drfe_ctx* ctx, int monocular, const drfe_tri_keyframes* kfs, const drfe_tri_keypoints* kps,
+                                  const drfe_tri_pairs* pairs, drfe_tri_out* out, void* stream);
+int drfe_triangulate_lines_batch(drfe_ctx* ctx, int monocular, const drfe_tri_keyframes* kfs, const drfe_tri_keylines* kls,
+                                 const drfe_tri_pairs* pairs, drfe_tri_out* out, void* stream);
+/* Counters since the context was created, points and lines together: stats[0] batch calls, [1] pairs, [2] pairs skipped,
+ * [3] matches, [4] SVD branch, [5] stereo branch of KF1, [6] of KF2, [7] accepted. */
+int drfe_triangulate_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

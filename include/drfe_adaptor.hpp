@@ -14,6 +14,8 @@
  *   drfe::UpdateCoefficientsAndPoints  src/MapPlane.cc:298-371       - both forms of MapPlane's cloud upkeep (host entries)
  *   drfe::UpkeepMapPoint / UpkeepMapLine / MapUpkeep  src/MapPoint.cc:288-411, src/MapLine.cpp:241-362 - descriptor and
  *                                      normal upkeep of map points and lines (host entries; MapUpkeep: the device batch)
+ *   drfe::TriangulateNewMapPoints / TriangulateNewMapLines / Triangulation  src/LocalMapping.cc:383-538, 875-1026 - the
+ *                                      per-match triangulation of CreateNewMapPoints / CreateNewMapLines2 (Triangulation: device)
  * With -DDRFE_WITH_OPENCV the container types are OpenCV's (cv::Mat, cv::KeyPoint, cv::line_descriptor::KeyLine);
  * without it (this image has no OpenCV) minimal stand-ins with the same member names and memory layout are used, so the
  * header is compiled and exercised here (tests/native/adaptor_caller.cpp, run by tests/test_gpu_native.py).
@@ -1961,6 +1963,166 @@ private:
     Planar_SLAM::drfe_detail::CtxPtr mCtx;
     std::mutex mMutex;
 };
+
+/* LocalMapping::CreateNewMapPoints / CreateNewMapLines2's per-match body (src/LocalMapping.cc:383-538, 875-1026; RGB-D / stereo,
+ * mbMonocular == false) over drfe_triangulate_points_host / drfe_triangulate_lines_host and the batch entries.  Reads
+ *   KeyFrame: GetPose() (4x4 float Mat: Tcw), GetPoseInverse() (Twc, what UnprojectStereo / obtain3DLine read), GetCameraCenter(),
+ *             fx, fy, cx, cy, invfx, invfy, mb, mbf, mfScaleFactor, mnScaleLevels, mvScaleFactors, mvLevelSigma2,
+ *             points: mvKeysUn, mvKeys (.pt, .octave), mvuRight, mvDepth; lines: mvKeyLines, mvDepthLine, mvLines3D
+ * and returns the accepted matches in vMatchedIndices order with the point (or the line's endpoints), so the reference loop body
+ * shrinks to object creation.  The baseline test is the caller's loop's too: a skipped pair returns
+ * nothing.  DESIGN.md section 15. */
+struct TriangulatedPoint { size_t idx1, idx2; float x3D[3]; };
+struct TriangulatedLine { size_t idx1, idx2; float sp[3], ep[3]; };
+namespace drfe_detail_tri {
+template <class M> inline void rows34(const M& m, float o[12])
+{
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 4; c++) o[r * 4 + c] = m.template ptr<float>(r)[c];
+}
+/* the flat inputs of one call: keyframes in first-use order, their features, the pairs */
+struct Call {
+    std::map<const void*, int32_t> index;
+    std::vector<drfe_tri_keyframe> kf;
+    std::vector<float> scale, sigma2, a, b, c, d;      /* points: un, raw, u_right, depth; lines: ends, depth */
+    std::vector<double> l3;
+    std::vector<int32_t> off{0}, octave, kf1, kf2, moff{0}, matches;
+    int nLevels = 0;
+    template <class KF> int32_t add(KF* p, bool line)
+    {
+        const auto r = index.emplace((const void*)p, (int32_t)kf.size());
+        if (!r.second) return r.first->second;
+        drfe_tri_keyframe k;
+        rows34(p->GetPose(), k.Tcw);
+        rows34(p->GetPoseInverse(), k.Twc);
+        const auto O = p->GetCameraCenter();
+        for (int q = 0; q < 3; q++) k.Ow[q] = O.template ptr<float>(q)[0];
+        k.fx = p->fx; k.fy = p->fy; k.cx = p->cx; k.cy = p->cy; k.invfx = p->invfx; k.invfy = p->invfy;
+        k.mb = p->mb; k.mbf = p->mbf; k.scale_factor = p->mfScaleFactor;
+        kf.push_back(k);
+        if (!nLevels) nLevels = p->mnScaleLevels;
+        for (int q = 0; q < nLevels; q++) { scale.push_back(p->mvScaleFactors[q]); sigma2.push_back(p->mvLevelSigma2[q]); }
+        if (line) {
+            for (size_t i = 0; i < p->mvKeyLines.size(); i++) {
+                const auto& kl = p->mvKeyLines[i];
+                a.insert(a.end(), {kl.startPointX, kl.startPointY, kl.endPointX, kl.endPointY});
+                octave.push_back(kl.octave);
+                b.push_back(p->mvDepthLine[i]);
+                for (int q = 0; q < 6; q++) l3.push_back(p->mvLines3D[i](q));
+            }
+        } else {
+            for (size_t i = 0; i < p->mvKeysUn.size(); i++) {
+                a.insert(a.end(), {p->mvKeysUn[i].pt.x, p->mvKeysUn[i].pt.y});
+                b.insert(b.end(), {p->mvKeys[i].pt.x, p->mvKeys[i].pt.y});
+                octave.push_back(p->mvKeysUn[i].octave);
+                c.push_back(p->mvuRight[i]);
+                d.push_back(p->mvDepth[i]);
+            }
+        }
+        off.push_back((int32_t)octave.size());
+        return r.first->second;
+    }
+    template <class KF, class Pairs> void pair(KF* p1, KF* p2, const Pairs& vMatchedIndices, bool line)
+    {
+        kf1.push_back(add(p1, line));
+        kf2.push_back(add(p2, line));
+        for (const auto& m : vMatchedIndices) { matches.push_back((int32_t)m.first); matches.push_back((int32_t)m.second); }
+        moff.push_back((int32_t)(matches.size() / 2));
+    }
+    drfe_tri_keyframes keyframes() const
+    {
+        return drfe_tri_keyframes{(int32_t)kf.size(), nLevels, kf.data(), scale.data(), sigma2.data()};
+    }
+    drfe_tri_keypoints keypoints() const { return drfe_tri_keypoints{off.data(), a.data(), b.data(), octave.data(), c.data(), d.data()}; }
+    drfe_tri_keylines keylines() const { return drfe_tri_keylines{off.data(), a.data(), octave.data(), b.data(), l3.data()}; }
+    drfe_tri_pairs pairs() const { return drfe_tri_pairs{(int32_t)kf1.size(), 0, kf1.data(), kf2.data(), moff.data(), matches.data()}; }
+};
+inline void set_world(TriangulatedPoint& r, const float* x) { std::memcpy(r.x3D, x, 3 * sizeof(float)); }
+inline void set_world(TriangulatedLine& r, const float* x) { std::memcpy(r.sp, x, 3 * sizeof(float)); std::memcpy(r.ep, x + 3, 3 * sizeof(float)); }
+/* runs fn(keyframes, features, pairs, out) and returns the accepted matches of each pair in order */
+template <class R, bool Line, class Fn> inline std::vector<std::vector<R>> run(const Call& cl, Fn fn)
+{
+    const size_t M = cl.matches.size() / 2;
+    std::vector<uint8_t> st(M);
+    std::vector<float> x((Line ? 6 : 3) * M + 1);
+    drfe_tri_out o{st.data(), nullptr, x.data(), nullptr, nullptr};
+    const drfe_tri_keyframes k = cl.keyframes();
+    const drfe_tri_pairs p = cl.pairs();
+    fn(&k, &p, &o);
+    std::vector<std::vector<R>> out(cl.kf1.size());
+    for (size_t q = 0; q < cl.kf1.size(); q++)
+        for (int32_t m = cl.moff[q]; m < cl.moff[q + 1]; m++) {
+            if ((st[m] & 0x7F) != DRFE_TRI_ACCEPTED) continue;
+            R r;
+            r.idx1 = (size_t)cl.matches[2 * (size_t)m];
+            r.idx2 = (size_t)cl.matches[2 * (size_t)m + 1];
+            set_world(r, &x[(Line ? 6 : 3) * (size_t)m]);
+            out[q].push_back(r);
+        }
+    return out;
+}
+}  // namespace drfe_detail_tri
+
+/* the accepted (idx1, idx2, x3D) of CreateNewMapPoints for one pair (pKF1 = mpCurrentKeyFrame, pKF2 = the neighbour), on the host */
+template <class KF, class Pairs>
+inline std::vector<TriangulatedPoint> TriangulateNewMapPoints(KF* pKF1, KF* pKF2, const Pairs& vMatchedIndices)
+{
+    drfe_detail_tri::Call cl;
+    cl.pair(pKF1, pKF2, vMatchedIndices, false);
+    return drfe_detail_tri::run<TriangulatedPoint, false>(cl, [&cl](const drfe_tri_keyframes* k, const drfe_tri_pairs* p, drfe_tri_out* o) {
+        const drfe_tri_keypoints f = cl.keypoints();
+        if (drfe_triangulate_points_host(0, k, &f, p, o) != DRFE_OK) throw std::runtime_error("drfe_triangulate_points_host failed");
+    })[0];
+}
+
+/* the accepted (idx1, idx2, sp, ep) of CreateNewMapLines2 for one pair, on the host */
+template <class KF, class Pairs>
+inline std::vector<TriangulatedLine> TriangulateNewMapLines(KF* pKF1, KF* pKF2, const Pairs& vMatchedIndices)
+{
+    drfe_detail_tri::Call cl;
+    cl.pair(pKF1, pKF2, vMatchedIndices, true);
+    return drfe_detail_tri::run<TriangulatedLine, true>(cl, [&cl](const drfe_tri_keyframes* k, const drfe_tri_pairs* p, drfe_tri_out* o) {
+        const drfe_tri_keylines f = cl.keylines();
+        if (drfe_triangulate_lines_host(0, k, &f, p, o) != DRFE_OK) throw std::runtime_error("drfe_triangulate_lines_host failed");
+    })[0];
+}
+
+/* The device batch: many independent pairs in one call (other keyframes, other sequences; not the neighbours of one keyframe
+ * in turn, whose matching depends on the points made for the previous neighbour).  Owns its own drfe_ctx, as MapUpkeep. */
+class Triangulation {
+public:
+    explicit Triangulation(int device = 0) : mCtx(Planar_SLAM::drfe_detail::make_ctx(1, 1.2f, 1, 20, 7, 64, 64, 1, device)) {}
+    drfe_ctx* ctx() const { return mCtx.get(); }
+    template <class KF, class Pairs>
+    std::vector<std::vector<TriangulatedPoint>> Points(const std::vector<KF*>& kf1, const std::vector<KF*>& kf2, const std::vector<Pairs>& matches)
+    {
+        drfe_detail_tri::Call cl;
+        for (size_t q = 0; q < kf1.size(); q++) cl.pair(kf1[q], kf2[q], matches[q], false);
+        drfe_ctx* c = mCtx.get();
+        std::lock_guard<std::mutex> lock(mMutex);
+        return drfe_detail_tri::run<TriangulatedPoint, false>(cl, [&cl, c](const drfe_tri_keyframes* k, const drfe_tri_pairs* p, drfe_tri_out* o) {
+            const drfe_tri_keypoints f = cl.keypoints();
+            Planar_SLAM::drfe_detail::check(drfe_triangulate_points_batch(c, 0, k, &f, p, o, nullptr), c, "drfe_triangulate_points_batch");
+        });
+    }
+    template <class KF, class Pairs>
+    std::vector<std::vector<TriangulatedLine>> Lines(const std::vector<KF*>& kf1, const std::vector<KF*>& kf2, const std::vector<Pairs>& matches)
+    {
+        drfe_detail_tri::Call cl;
+        for (size_t q = 0; q < kf1.size(); q++) cl.pair(kf1[q], kf2[q], matches[q], true);
+        drfe_ctx* c = mCtx.get();
+        std::lock_guard<std::mutex> lock(mMutex);
+        return drfe_detail_tri::run<TriangulatedLine, true>(cl, [&cl, c](const drfe_tri_keyframes* k, const drfe_tri_pairs* p, drfe_tri_out* o) {
+            const drfe_tri_keylines f = cl.keylines();
+            Planar_SLAM::drfe_detail::check(drfe_triangulate_lines_batch(c, 0, k, &f, p, o, nullptr), c, "drfe_triangulate_lines_batch");
+        });
+    }
+
+private:
+    Planar_SLAM::drfe_detail::CtxPtr mCtx;
+    std::mutex mMutex;
+};
+
 }  // namespace drfe
 
 #endif /* DRFE_ADAPTOR_HPP */

@@ -40,6 +40,10 @@ int drfe_debug_order_sort(void* recs, size_t n, int kind, int mode, int depth_li
  * drfe_exp(x[i]) (which 1) or drfe_tanf((float)x[i]) widened to double (which 2).  Host code. */
 int drfe_debug_manhattan_math(int which, const double* x, int n, double* out);
 
+/* Test hook of include/drfe_math.h's canonical libm of triangulation: out[i] = drfe_atan2f(y[i], x[i]) (which 0),
+ * drfe_cosf(y[i]) (which 1) or the stereo parallax drfe_cosf(2 * drfe_atan2f(y[i] / 2, x[i])) (which 2).  Host code. */
+int drfe_debug_triangulate_math(int which, const float* y, const float* x, int n, float* out);
+
 #ifdef __cplusplus
 }
 #endif

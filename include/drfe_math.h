@@ -12,6 +12,8 @@
  *                            build canonicalises on this routine.
  *   drfe_logf             <- log(float) of MapPoint::PredictScale / MapLine::PredictScale (reference
  *                            src/MapPoint.cc:456, src/MapLine.cpp:389) — same libm caveat, same remedy.
+ *   drfe_cosf, drfe_atan2f <- cos(float) / atan2(float, float) of LocalMapping::CreateNewMapPoints' stereo parallax
+ *                            (reference src/LocalMapping.cc:406-409), correctly rounded on [0, pi] / y >= 0, x > 0.
  *   drfe_asin, drfe_exp,  <- asin(double), exp(double) and tan(float) of the Manhattan-frame tracker
  *   drfe_tanf                (reference src/Tracking.cc:1103, :1539, :1156) — same libm caveat, same remedy;
  *                            within 1 ulp of glibc over the domains the tracker uses (tests/test_manhattan_cpu.py).
@@ -59,12 +61,10 @@ DRFE_HD float drfe_fast_atan2(float y, float x)
     return a;
 }
 
-/* cos/sin of a float32 angle in radians, evaluated in float64 (Cody-Waite pi/2 reduction + Taylor
- * polynomials, |r| <= pi/4, truncation error < 1e-19) and rounded once to float32.  Valid for
- * |rad| < 1e4 (the path only produces [0, 2*pi]). */
-DRFE_HD void drfe_sincos(float rad, float* s_out, float* c_out)
+/* sin and cos of a double x, |x| < 1e4, in float64: Cody-Waite pi/2 reduction + Taylor polynomials, |r| <= pi/4, truncation
+ * error < 1e-19.  The core of drfe_sincos and drfe_cosf. */
+DRFE_HD void drfe_sincos_d(double x, double* s_out, double* c_out)
 {
-    const double x = (double)rad;
     const double two_over_pi = 0.63661977236758134308;
     const double pio2_hi = 1.57079632673412561417e+00; /* 33 significant bits */
     const double pio2_lo = 6.07710050650619224932e-11;
@@ -102,8 +102,52 @@ DRFE_HD void drfe_sincos(float rad, float* s_out, float* c_out)
     case 2: s = -sn; c = -cs; break;
     default: s = -cs; c = sn; break;
     }
+    *s_out = s;
+    *c_out = c;
+}
+
+/* cos/sin of a float32 angle in radians, evaluated in float64 (drfe_sincos_d) and rounded once to float32.  Valid for
+ * |rad| < 1e4 (the path only produces [0, 2*pi]). */
+DRFE_HD void drfe_sincos(float rad, float* s_out, float* c_out)
+{
+    double s, c;
+    drfe_sincos_d((double)rad, &s, &c);
     *s_out = (float)s;
     *c_out = (float)c;
+}
+
+/* cos(float) of LocalMapping::CreateNewMapPoints' stereo parallax (reference src/LocalMapping.cc:406-409) on [0, pi]:
+ * drfe_sincos_d's cosine rounded once to float32.  The reduced argument of a float near pi/2 or pi keeps ~1e-19 relative
+ * error (a float is at least 4e-8 from either), so the float is the correctly rounded one (tests/test_triangulate_cpu.py). */
+DRFE_HD float drfe_cosf(float xf)
+{
+    double s, c;
+    drfe_sincos_d((double)xf, &s, &c);
+    return (float)c;
+}
+
+/* atan of a double r in [0, 1] in float64: two half-angle steps r <- r / (1 + sqrt(1 + r^2)) bring r below tan(pi/16)
+ * = 0.199, then the Maclaurin series r - r * (z * P(z)), z = r^2, to the r^27 term (truncation < 1e-19 relative), times 4. */
+DRFE_HD double drfe_atan_unit_d(double r)
+{
+    r = r / (1.0 + sqrt(1.0 + r * r));
+    r = r / (1.0 + sqrt(1.0 + r * r));
+    const double z = r * r;
+    double p = 1.0 / 27.0;                                /* (-1)^k / (2k + 1), k = 13 .. 1 */
+    p = p * z - 1.0 / 25.0; p = p * z + 1.0 / 23.0; p = p * z - 1.0 / 21.0; p = p * z + 1.0 / 19.0;
+    p = p * z - 1.0 / 17.0; p = p * z + 1.0 / 15.0; p = p * z - 1.0 / 13.0; p = p * z + 1.0 / 11.0;
+    p = p * z - 1.0 / 9.0;  p = p * z + 1.0 / 7.0;  p = p * z - 1.0 / 5.0;  p = p * z + 1.0 / 3.0;
+    return 4.0 * (r - r * (z * p));
+}
+
+/* atan2(float, float) of the same site for y >= 0, x > 0 (mb / 2 and a depth): the quotient of the smaller by the larger in
+ * float64, drfe_atan_unit_d, pi/2 minus it (split in two doubles) when y > x, rounded once to float32. */
+DRFE_HD float drfe_atan2f(float yf, float xf)
+{
+    const double y = (double)yf, x = (double)xf;
+    if (y <= x) return (float)drfe_atan_unit_d(y / x);
+    const double pio2_hi = 1.57079632679489655800e+00, pio2_lo = 6.12323399573676603587e-17;
+    return (float)((pio2_hi - drfe_atan_unit_d(x / y)) + pio2_lo);
 }
 
 /* 256-bit Hamming distance: the reference's 8x32-bit SWAR popcount (src/ORBmatcher.cc:1712-1728,
