@@ -1,6 +1,7 @@
 /* capi_match.cpp — C-ABI entry points of the Frame glue and the matchers (include/drfe.h). */
 #include "drfe_internal.h"
 #include "match_internal.h"
+#include "stage_layout.h"
 #include "../../include/drfe_math.h"
 
 #include <algorithm>
@@ -133,13 +134,15 @@ static int frustum_run(drfe_ctx* c, const In* in, int n, Out* out, Launch launch
     if (n == 0) return DRFE_OK;
     HIPCHK(c, hipSetDevice(c->device));
     uint8_t* d = nullptr;
-    const size_t oIn = 0, oOut = (sizeof(In) * (size_t)n + 63) & ~(size_t)63, total = oOut + sizeof(Out) * (size_t)n;
-    HIPCHK(c, call_scratch(c, total, &d));
+    StageLayout<64> lay;
+    const auto sIn = lay.add<In>(n);
+    const auto sOut = lay.add<Out>(n);
+    HIPCHK(c, call_scratch(c, lay.bytes(), &d));
     hipStream_t s = c->stream;
-    hipError_t e = hipMemcpyAsync(d + oIn, in, sizeof(In) * (size_t)n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + oOut, out, sizeof(Out) * (size_t)n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = launch(reinterpret_cast<const In*>(d + oIn), reinterpret_cast<Out*>(d + oOut), s);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d + oOut, sizeof(Out) * (size_t)n, hipMemcpyDeviceToHost, s);
+    hipError_t e = hipMemcpyAsync(sIn.at(d), in, sIn.bytes(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(sOut.at(d), out, sOut.bytes(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = launch(sIn.at(d), sOut.at(d), s);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, sOut.at(d), sOut.bytes(), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { c->err = std::string("is_in_frustum: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
     return DRFE_OK;
@@ -710,28 +713,31 @@ static int line_search_run(drfe_ctx* c, const std::vector<LineQuery>* hostQ, con
         claim[i] = cur_ml[i] >= 0 ? (uint8_t)(1 | ((cur_obs ? cur_obs[i] : 1) ? 2 : 0)) : 0;
     }
     /* one scratch block: queries | map lines | Tcw | current lines | descriptors | claims | cur_ml | count */
-    const size_t oQ = 0, oL = oQ + sizeof(LineQuery) * n, oT = oL + (last ? sizeof(drfe_map_line) * n : 0),
-                 oC = oT + 64, oD = oC + sizeof(LineCur) * n_cur, oK = oD + (size_t)n_cur * 32,
-                 oM = (oK + n_cur + 15) & ~(size_t)15, oN = oM + sizeof(int) * n_cur, total = oN + 16;
+    StageLayout<64> lay;
+    const auto sQ = lay.add<LineQuery>(n);
+    const auto sL = lay.add<drfe_map_line>(hostQ ? 0 : n);
+    const auto sT = lay.add<float>(hostQ ? 0 : 16);
+    const auto sC = lay.add<LineCur>(n_cur);
+    const auto sD = lay.add<uint8_t>((size_t)n_cur * 32), sK = lay.add<uint8_t>(n_cur);
+    const auto sM = lay.add<int>(n_cur), sN = lay.add<int>(1);
     uint8_t* d = nullptr;
-    HIPCHK(c, call_scratch(c, total, &d));
+    HIPCHK(c, call_scratch(c, lay.bytes(), &d));
     hipStream_t s = c->stream;
     hipError_t e = hipSuccess;
-    auto up = [&](size_t off, const void* src, size_t bytes) { if (e == hipSuccess && bytes) e = hipMemcpyAsync(d + off, src, bytes, hipMemcpyHostToDevice, s); };
-    if (hostQ) up(oQ, hostQ->data(), sizeof(LineQuery) * n);
-    else { up(oL, last, sizeof(drfe_map_line) * n); up(oT, TcwCur, 64); }
-    up(oC, lc.data(), sizeof(LineCur) * n_cur);
-    up(oD, cur_desc, (size_t)n_cur * 32);
-    up(oK, claim.data(), n_cur);
-    up(oM, cur_ml, sizeof(int) * n_cur);
+    auto up = [&](const auto& sec, const void* src) { if (e == hipSuccess && sec.n) e = hipMemcpyAsync(sec.at(d), src, sec.bytes(), hipMemcpyHostToDevice, s); };
+    if (hostQ) up(sQ, hostQ->data());
+    up(sL, last);
+    up(sT, TcwCur);
+    up(sC, lc.data());
+    up(sD, cur_desc);
+    up(sK, claim.data());
+    up(sM, cur_ml);
     if (e == hipSuccess && !hostQ)
-        e = drfe_launch_line_projection(reinterpret_cast<const drfe_map_line*>(d + oL), n, reinterpret_cast<const float*>(d + oT),
-                                        *cam, fwd, bwd, m->d_scale, th, reinterpret_cast<LineQuery*>(d + oQ), s);
+        e = drfe_launch_line_projection(sL.at(d), n, sT.at(d), *cam, fwd, bwd, m->d_scale, th, sQ.at(d), s);
     if (e == hipSuccess)
-        e = drfe_launch_line_search(reinterpret_cast<const LineQuery*>(d + oQ), n, reinterpret_cast<const LineCur*>(d + oC), d + oD,
-                                    n_cur, nnratio, d + oK, reinterpret_cast<int*>(d + oM), reinterpret_cast<int*>(d + oN), s);
-    if (e == hipSuccess) e = hipMemcpyAsync(cur_ml, d + oM, sizeof(int) * n_cur, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(nmatches, d + oN, sizeof(int), hipMemcpyDeviceToHost, s);
+        e = drfe_launch_line_search(sQ.at(d), n, sC.at(d), sD.at(d), n_cur, nnratio, sK.at(d), sM.at(d), sN.at(d), s);
+    if (e == hipSuccess) e = hipMemcpyAsync(cur_ml, sM.at(d), sM.bytes(), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(nmatches, sN.at(d), sN.bytes(), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { c->err = std::string("lsd_search_by_projection: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
     return DRFE_OK;
@@ -810,6 +816,21 @@ int drfe_frame_is_in_frustum_lines(drfe_ctx* c, const float* Tcw, const drfe_cam
 }
 
 
+/* the search parameters every fuse-style matcher takes from the context: pose, Ow = -Rcw.t()*tcw (double accumulation), scales */
+static FuseParams fuse_params(drfe_ctx* c, const float* T, const drfe_camera& cam, float th, int mode)
+{
+    FrustumPose fp;
+    frustum_pose(c, T, &cam, 0.f, &fp);
+    FuseParams P;
+    std::memset(&P, 0, sizeof(P));
+    std::memcpy(P.T, fp.T, 64);
+    std::memcpy(P.Ow, fp.Ow, 12);
+    P.bf = cam.bf; P.logScale = fp.logScale; P.th = th; P.nLevels = c->cfg.nlevels;
+    P.sim3 = mode;
+    for (int l = 0; l < c->cfg.nlevels; l++) { P.scale[l] = c->scale[l]; P.invSigma2[l] = c->invSigma2[l]; }
+    return P;
+}
+
 /* ---- ORBmatcher::Fuse(KeyFrame*, vector<MapPoint*>, th): search part -------------------------------- */
 static int fuse_search_impl(drfe_ctx* c, int slot, const float* Tcw, int sim3, const drfe_frustum_point* pts,
                             const uint8_t* descs, const uint8_t* skip, int n, float th, int32_t* best_idx, int32_t* best_dist,
@@ -823,30 +844,23 @@ static int fuse_search_impl(drfe_ctx* c, int slot, const float* Tcw, int sim3, c
     int rc = drfe_stream_sync(c);
     if (rc != DRFE_OK) return rc;
     const drfe_camera cam = c->cam;                       /* the glue call's camera: bounds and grid of this slot */
-    FrustumPose fp;
-    frustum_pose(c, Tcw, &cam, 0.f, &fp);
-    FuseParams P;
-    std::memset(&P, 0, sizeof(P));
-    std::memcpy(P.T, fp.T, 64);
-    std::memcpy(P.Ow, fp.Ow, 12);                         /* `-Rcw.t()*tcw` of the Scw overloads: double accumulation */
+    FuseParams P = fuse_params(c, Tcw, cam, th, sim3);    /* the Scw overloads keep its Ow */
     if (sim3 == 0) camera_centre_kf(Tcw, P.Ow);           /* pKF->GetCameraCenter(), src/ORBmatcher.cc:840 */
-    P.bf = cam.bf; P.logScale = fp.logScale; P.th = th; P.nLevels = c->cfg.nlevels;
-    P.sim3 = sim3;
     if (sR2) { std::memcpy(P.sR2, sR2, 36); std::memcpy(P.t2, t2, 12); }
-    for (int l = 0; l < c->cfg.nlevels; l++) { P.scale[l] = c->scale[l]; P.invSigma2[l] = c->invSigma2[l]; }
     uint8_t* d = nullptr;
-    const size_t oP = 0, oD = (sizeof(drfe_frustum_point) * (size_t)n + 63) & ~(size_t)63, oS = oD + (((size_t)n * 32 + 63) & ~(size_t)63),
-                 oI = oS + (((size_t)n + 63) & ~(size_t)63), oB = oI + sizeof(int) * (size_t)n, total = oB + sizeof(int) * (size_t)n;
-    HIPCHK(c, call_scratch(c, total, &d));
+    StageLayout<64> lay;
+    const auto sP = lay.add<drfe_frustum_point>(n);
+    const auto sD = lay.add<uint8_t>((size_t)n * 32), sS = lay.add<uint8_t>(skip ? n : 0);
+    const auto sI = lay.add<int>(n), sB = lay.add<int>(n);
+    HIPCHK(c, call_scratch(c, lay.bytes(), &d));
     hipStream_t s = c->stream;
-    hipError_t e = hipMemcpyAsync(d + oP, pts, sizeof(drfe_frustum_point) * (size_t)n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + oD, descs, (size_t)n * 32, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && skip) e = hipMemcpyAsync(d + oS, skip, (size_t)n, hipMemcpyHostToDevice, s);
+    hipError_t e = hipMemcpyAsync(sP.at(d), pts, sP.bytes(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(sD.at(d), descs, sD.bytes(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && skip) e = hipMemcpyAsync(sS.at(d), skip, sS.bytes(), hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
-        e = drfe_launch_fuse_search(c, slot, reinterpret_cast<const drfe_frustum_point*>(d + oP), d + oD, skip ? d + oS : nullptr, n, P,
-                                    cam, reinterpret_cast<int*>(d + oI), reinterpret_cast<int*>(d + oB), s);
-    if (e == hipSuccess) e = hipMemcpyAsync(best_idx, d + oI, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(best_dist, d + oB, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s);
+        e = drfe_launch_fuse_search(c, slot, sP.at(d), sD.at(d), skip ? sS.at(d) : nullptr, n, P, cam, sI.at(d), sB.at(d), s);
+    if (e == hipSuccess) e = hipMemcpyAsync(best_idx, sI.at(d), sI.bytes(), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(best_dist, sB.at(d), sB.bytes(), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { c->err = std::string("fuse_search: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
     return DRFE_OK;
@@ -934,35 +948,27 @@ static int first_come_search(drfe_ctx* c, const char* who, int slot, const float
     if (n_kp != slotCount) { c->err = std::string(who) + ": n_kp is not the slot's keypoint count"; return DRFE_ERR_INVALID; }
     if (n == 0 || n_kp == 0) return DRFE_OK;
     const drfe_camera cam = c->cam;
-    FrustumPose fp;
-    frustum_pose(c, T, &cam, 0.f, &fp);                                                 /* Ow = -Rcw.t()*tcw in both callers */
-    FuseParams P;
-    std::memset(&P, 0, sizeof(P));
-    std::memcpy(P.T, fp.T, 64);
-    std::memcpy(P.Ow, fp.Ow, 12);
-    P.bf = cam.bf; P.logScale = fp.logScale; P.th = th; P.nLevels = c->cfg.nlevels;
-    P.sim3 = mode; P.listTh = listTh;
-    for (int l = 0; l < c->cfg.nlevels; l++) { P.scale[l] = c->scale[l]; P.invSigma2[l] = c->invSigma2[l]; }
-    auto up = [](size_t v) { return (v + 63) & ~(size_t)63; };
-    const size_t oP = 0, oD = up(sizeof(drfe_frustum_point) * (size_t)n), oS = oD + up((size_t)n * 32), oT = oS + up((size_t)n),
-                 oI = oT + up((size_t)n_kp), oB = oI + up(sizeof(int) * (size_t)n), oC = oB + up(sizeof(int) * (size_t)n),
-                 oL = oC + up(sizeof(int) * (size_t)n), total = oL + sizeof(int2) * (size_t)n * FUSE_LIST_K;
+    FuseParams P = fuse_params(c, T, cam, th, mode);      /* Ow = -Rcw.t()*tcw in both callers */
+    P.listTh = listTh;
+    StageLayout<64> lay;
+    const auto sP = lay.add<drfe_frustum_point>(n);
+    const auto sD = lay.add<uint8_t>((size_t)n * 32), sS = lay.add<uint8_t>(skip ? n : 0), sT = lay.add<uint8_t>(n_kp);
+    const auto sI = lay.add<int>(n), sB = lay.add<int>(n), sC = lay.add<int>(n);
+    const auto sL = lay.add<int2>((size_t)n * FUSE_LIST_K);
     uint8_t* d = nullptr;
-    HIPCHK(c, call_scratch(c, total, &d));
+    HIPCHK(c, call_scratch(c, lay.bytes(), &d));
     hipStream_t s = c->stream;
-    std::vector<int2> list((size_t)n * FUSE_LIST_K);
+    std::vector<int2> list(sL.n);
     std::vector<int> count(n);
-    auto P_ = [&](size_t o) { return d + o; };
-    hipError_t e = hipMemcpyAsync(P_(oP), pts, sizeof(drfe_frustum_point) * (size_t)n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(P_(oD), descs, (size_t)n * 32, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && skip) e = hipMemcpyAsync(P_(oS), skip, (size_t)n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(P_(oT), taken.data(), (size_t)n_kp, hipMemcpyHostToDevice, s);
+    hipError_t e = hipMemcpyAsync(sP.at(d), pts, sP.bytes(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(sD.at(d), descs, sD.bytes(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && skip) e = hipMemcpyAsync(sS.at(d), skip, sS.bytes(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(sT.at(d), taken.data(), sT.bytes(), hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
-        e = drfe_launch_fuse_search(c, slot, reinterpret_cast<const drfe_frustum_point*>(P_(oP)), P_(oD), skip ? P_(oS) : nullptr, n, P, cam,
-                                    reinterpret_cast<int*>(P_(oI)), reinterpret_cast<int*>(P_(oB)), s, P_(oT),
-                                    reinterpret_cast<int2*>(P_(oL)), reinterpret_cast<int*>(P_(oC)));
-    if (e == hipSuccess) e = hipMemcpyAsync(list.data(), P_(oL), sizeof(int2) * list.size(), hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(count.data(), P_(oC), sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s);
+        e = drfe_launch_fuse_search(c, slot, sP.at(d), sD.at(d), skip ? sS.at(d) : nullptr, n, P, cam, sI.at(d), sB.at(d), s, sT.at(d),
+                                    sL.at(d), sC.at(d));
+    if (e == hipSuccess) e = hipMemcpyAsync(list.data(), sL.at(d), sL.bytes(), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(count.data(), sC.at(d), sC.bytes(), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     /* DRFE_TEST_LIST_K=1..FUSE_LIST_K shortens the lists the host trusts so that tests reach the ask-again path */
     int listK = FUSE_LIST_K;
@@ -977,13 +983,12 @@ static int first_come_search(drfe_ctx* c, const char* who, int slot, const float
         if (pk < 0 && count[i] > held) {
             /* every listed candidate was claimed and there were more: search this point again with today's claims */
             int one[2] = {-1, 256};
-            e = hipMemcpyAsync(P_(oT), taken.data(), (size_t)n_kp, hipMemcpyHostToDevice, s);
+            e = hipMemcpyAsync(sT.at(d), taken.data(), sT.bytes(), hipMemcpyHostToDevice, s);
             if (e == hipSuccess)
-                e = drfe_launch_fuse_search(c, slot, reinterpret_cast<const drfe_frustum_point*>(P_(oP)) + i, P_(oD) + (size_t)i * 32,
-                                            skip ? P_(oS) + i : nullptr, 1, P, cam, reinterpret_cast<int*>(P_(oI)),
-                                            reinterpret_cast<int*>(P_(oB)), s, P_(oT), nullptr, nullptr);
-            if (e == hipSuccess) e = hipMemcpyAsync(&one[0], P_(oI), sizeof(int), hipMemcpyDeviceToHost, s);
-            if (e == hipSuccess) e = hipMemcpyAsync(&one[1], P_(oB), sizeof(int), hipMemcpyDeviceToHost, s);
+                e = drfe_launch_fuse_search(c, slot, sP.at(d) + i, sD.at(d) + (size_t)i * 32, skip ? sS.at(d) + i : nullptr, 1, P, cam,
+                                            sI.at(d), sB.at(d), s, sT.at(d), nullptr, nullptr);
+            if (e == hipSuccess) e = hipMemcpyAsync(&one[0], sI.at(d), sizeof(int), hipMemcpyDeviceToHost, s);
+            if (e == hipSuccess) e = hipMemcpyAsync(&one[1], sB.at(d), sizeof(int), hipMemcpyDeviceToHost, s);
             if (e == hipSuccess) e = hipStreamSynchronize(s);
             if (e == hipSuccess && one[0] >= 0 && one[1] <= listTh) pk = one[0];
         }
@@ -1206,29 +1211,28 @@ static int lsd_fuse_impl(drfe_ctx* c, const char* who, const FrustumPose& P, con
     for (int i = 0; i < n_kf; i++) {
         lc[i].ptX = kf_lines[i].pt_x; lc[i].ptY = kf_lines[i].pt_y; lc[i].angle = kf_lines[i].angle; lc[i].octave = kf_lines[i].octave;
     }
-    auto up = [](size_t v) { return (v + 63) & ~(size_t)63; };
-    const size_t rows = dist_rows ? sizeof(int) * (size_t)n * (size_t)n_kf : 0;
-    const size_t oL = 0, oD = up(sizeof(drfe_frustum_line) * (size_t)n), oS = oD + up((size_t)n * 32), oK = oS + up((size_t)n),
-                 oKD = oK + up(sizeof(LineCur) * (size_t)n_kf), oI = oKD + up((size_t)n_kf * 32), oB = oI + up(sizeof(int) * (size_t)n),
-                 oR = oB + up(sizeof(int) * (size_t)n), total = oR + rows;
+    StageLayout<64> lay;
+    const auto sL = lay.add<drfe_frustum_line>(n);
+    const auto sD = lay.add<uint8_t>((size_t)n * 32), sS = lay.add<uint8_t>(skip ? n : 0);
+    const auto sK = lay.add<LineCur>(n_kf);
+    const auto sKD = lay.add<uint8_t>((size_t)n_kf * 32);
+    const auto sI = lay.add<int>(n), sB = lay.add<int>(n), sR = lay.add<int>(dist_rows ? (size_t)n * n_kf : 0);
     uint8_t* d = nullptr;
-    HIPCHK(c, call_scratch(c, total, &d));
+    HIPCHK(c, call_scratch(c, lay.bytes(), &d));
     hipStream_t s = c->stream;
-    hipError_t e = hipMemcpyAsync(d + oL, lines, sizeof(drfe_frustum_line) * (size_t)n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(d + oD, descs, (size_t)n * 32, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && skip) e = hipMemcpyAsync(d + oS, skip, (size_t)n, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n_kf) e = hipMemcpyAsync(d + oK, lc.data(), sizeof(LineCur) * (size_t)n_kf, hipMemcpyHostToDevice, s);
-    if (e == hipSuccess && n_kf) e = hipMemcpyAsync(d + oKD, kf_desc, (size_t)n_kf * 32, hipMemcpyHostToDevice, s);
+    hipError_t e = hipMemcpyAsync(sL.at(d), lines, sL.bytes(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(sD.at(d), descs, sD.bytes(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && skip) e = hipMemcpyAsync(sS.at(d), skip, sS.bytes(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && n_kf) e = hipMemcpyAsync(sK.at(d), lc.data(), sK.bytes(), hipMemcpyHostToDevice, s);
+    if (e == hipSuccess && n_kf) e = hipMemcpyAsync(sKD.at(d), kf_desc, sKD.bytes(), hipMemcpyHostToDevice, s);
     if (e == hipSuccess)
-        e = drfe_launch_line_fuse_search(reinterpret_cast<const drfe_frustum_line*>(d + oL), d + oD, skip ? d + oS : nullptr, n, P, *cam,
-                                         m->d_scale, th, reinterpret_cast<const LineCur*>(d + oK), d + oKD, n_kf,
-                                         reinterpret_cast<int*>(d + oI), reinterpret_cast<int*>(d + oB), s, sim3,
-                                         rows ? reinterpret_cast<int*>(d + oR) : nullptr);
-    if (e == hipSuccess) e = hipMemcpyAsync(best_idx, d + oI, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(best_dist, d + oB, sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess && rows) {
-        dist_rows->resize((size_t)n * (size_t)n_kf);
-        e = hipMemcpyAsync(dist_rows->data(), d + oR, rows, hipMemcpyDeviceToHost, s);
+        e = drfe_launch_line_fuse_search(sL.at(d), sD.at(d), skip ? sS.at(d) : nullptr, n, P, *cam, m->d_scale, th, sK.at(d), sKD.at(d),
+                                         n_kf, sI.at(d), sB.at(d), s, sim3, sR.n ? sR.at(d) : nullptr);
+    if (e == hipSuccess) e = hipMemcpyAsync(best_idx, sI.at(d), sI.bytes(), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(best_dist, sB.at(d), sB.bytes(), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && sR.n) {
+        dist_rows->resize(sR.n);
+        e = hipMemcpyAsync(dist_rows->data(), sR.at(d), sR.bytes(), hipMemcpyDeviceToHost, s);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) { c->err = std::string(who) + ": " + hipGetErrorString(e); return DRFE_ERR_HIP; }

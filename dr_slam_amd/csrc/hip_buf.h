@@ -73,4 +73,18 @@ private:
 template <class T> using DevBuf = HipBuf<T, false>;
 template <class T> using PinnedBuf = HipBuf<T, true>;
 
+/* StagePair: the pinned and device blocks of an entry that stages its inputs in one copy and its results in one copy back */
+struct StagePair {
+    PinnedBuf<char> hin, hout;
+    DevBuf<char> din, dout;
+    hipError_t grow(size_t in, size_t out)
+    {
+        hipError_t e = hin.grow(in);
+        if (e == hipSuccess) e = din.grow(in);
+        if (e == hipSuccess) e = hout.grow(out);
+        if (e == hipSuccess) e = dout.grow(out);
+        return e;
+    }
+};
+
 #endif

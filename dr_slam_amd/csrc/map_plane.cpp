@@ -148,11 +148,14 @@ int run_jobs(drfe_ctx* c, PmBuffers* b, const std::vector<Job>& jobs, const std:
             }
             maxJob = std::max(maxJob, (int)n[i]);
         }
-        const size_t oS = 0, oJ = drfe_align16(rs.size() * sizeof(MpSeg)), oC = drfe_align16(oJ + (size_t)nj * sizeof(int2)),
-                     oK = drfe_align16(oC + (size_t)nj * sizeof(MpCommit)), oEnd = drfe_align16(oK + (size_t)nj * 4);
+        StageLayout<16> lay;
+        const auto sS = lay.add<MpSeg>(rs.size());
+        const auto sJ = lay.add<int2>((size_t)nj);
+        const auto sC = lay.add<MpCommit>((size_t)nj);
+        const auto sK = lay.add<int>((size_t)nj);       /* the counts come back here: host block only, the copy up ends at sK.off */
         const size_t N = (size_t)total;
-        HIPCHK(c, drfe_pm_reserve(b->upRec, oK));
-        HIPCHK(c, drfe_pm_reserve(b->upHost, oEnd));
+        HIPCHK(c, drfe_pm_reserve(b->upRec, sK.off));
+        HIPCHK(c, drfe_pm_reserve(b->upHost, lay.bytes()));
         HIPCHK(c, drfe_pm_reserve(b->upIn, N * 3));
         HIPCHK(c, drfe_pm_reserve(b->upOut, N * 3));
         HIPCHK(c, drfe_pm_reserve(b->upRecs, N));
@@ -162,21 +165,19 @@ int run_jobs(drfe_ctx* c, PmBuffers* b, const std::vector<Job>& jobs, const std:
         HIPCHK(c, drfe_pm_reserve(b->upList, (size_t)nj + 2));
         HIPCHK(c, drfe_pm_reserve(b->upCounts, (size_t)nj));
         char* h = b->upHost;
-        if (!rs.empty()) std::memcpy(h + oS, rs.data(), rs.size() * sizeof(MpSeg));
-        std::memcpy(h + oJ, vj.data(), (size_t)nj * sizeof(int2));
-        std::memcpy(h + oC, cm.data(), (size_t)nj * sizeof(MpCommit));
-        char* d = b->upRec;
-        HIPCHK(c, hipMemcpyAsync(d, h, oK, hipMemcpyHostToDevice, s));
-        hipError_t e = drfe_launch_map_plane_gather((const MpSeg*)(d + oS), (int)rs.size(), maxSeg, b->upPose, b->upSrc,
-                                                    b->cloud, b->upIn, s);
+        sS.put(h, rs.data());
+        sJ.put(h, vj.data());
+        sC.put(h, cm.data());
+        const char* d = b->upRec;
+        HIPCHK(c, hipMemcpyAsync(b->upRec, h, sK.off, hipMemcpyHostToDevice, s));
+        hipError_t e = drfe_launch_map_plane_gather(sS.at(d), (int)rs.size(), maxSeg, b->upPose, b->upSrc, b->cloud, b->upIn, s);
         if (e == hipSuccess)
-            e = drfe_launch_voxel_grid(b->upIn, (const int2*)(d + oJ), nj, b->upList, b->upRecs, b->upTmp, b->upPosL, b->upPosR,
+            e = drfe_launch_voxel_grid(b->upIn, sJ.at(d), nj, b->upList, b->upRecs, b->upTmp, b->upPosL, b->upPosR,
                                        b->upOut, b->upCounts, kLeaf, s);
         if (e == hipSuccess)
-            e = drfe_launch_map_plane_commit((const MpCommit*)(d + oC), nj, maxJob, b->upCounts, b->upOut, b->cloud,
-                                             b->cloudEnd, s);
+            e = drfe_launch_map_plane_commit(sC.at(d), nj, maxJob, b->upCounts, b->upOut, b->cloud, b->cloudEnd, s);
         if (e != hipSuccess) { c->err = std::string("plane_map update: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
-        int* counts = reinterpret_cast<int*>(h + oK);
+        int* counts = sK.at(h);
         HIPCHK(c, hipMemcpyAsync(counts, b->upCounts, (size_t)nj * 4, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipStreamSynchronize(s));
         for (int i = 0; i < nj; i++) {

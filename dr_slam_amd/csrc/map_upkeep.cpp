@@ -5,6 +5,7 @@
 #include "map_upkeep_internal.h"
 #include "map_upkeep_core.h"
 #include "hip_buf.h"
+#include "stage_layout.h"
 
 #include <algorithm>
 #include <cstring>
@@ -13,8 +14,7 @@
 #include <vector>
 
 struct MuBuffers {
-    PinnedBuf<char> hin, hout;         /* staging: one copy each way */
-    DevBuf<char> din, dout;
+    StagePair io;                      /* staging: one copy each way */
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -25,8 +25,6 @@ void drfe_map_upkeep_free(drfe_ctx* c)
 }
 
 namespace {
-
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 bool kf_bad(const drfe_upkeep_keyframes* k, int32_t kf) { return k->bad && k->bad[kf]; }
 
@@ -222,69 +220,72 @@ int upkeep_batch(drfe_ctx* c, int what, const drfe_upkeep_keyframes* k, const dr
     }
     if (R > INT32_MAX / 32) { c->err = "map_upkeep: too many descriptor rows in one call"; return DRFE_ERR_CAPACITY; }
     /* staging layout (16-byte aligned sections) */
-    const size_t wsz = Line ? 48 : 12, nsz = Line ? 24 : 12, fsz = Line ? sizeof(drfe_frustum_line) : sizeof(drfe_frustum_point);
-    const size_t oItems = 0, oCent = align16(oItems + (size_t)n * sizeof(MuItem)), oScale = align16(oCent + (size_t)k->n * 12),
-                 oWorld = align16(oScale + (wantNormal ? (size_t)k->n_levels * 4 : 0)),
-                 oObsKf = align16(oWorld + (wantNormal ? (size_t)n * wsz : 0)), oRows = align16(oObsKf + (wantNormal ? (size_t)T * 4 : 0)),
-                 oRowObs = align16(oRows + (size_t)R * 32), oLists = align16(oRowObs + (size_t)R * 4);
-    size_t oList[MU_BUCKETS], inEnd = oLists;
-    for (int bk = 0; bk < MU_BUCKETS; bk++) { oList[bk] = inEnd; inEnd = align16(inEnd + lists[bk].size() * 4); }
-    const size_t pBest = 0, pDesc = align16((size_t)n * 4), pNormal = align16(pDesc + (size_t)n * 32), pMax = align16(pNormal + (size_t)n * nsz),
-                 pMin = align16(pMax + (size_t)n * 4), pStatus = align16(pMin + (size_t)n * 4), pFrustum = align16(pStatus + (size_t)n),
-                 outEnd = align16(pFrustum + (o->frustum ? (size_t)n * fsz : 0));
+    using W = std::conditional_t<Line, double, float>;          /* world coordinates and normals */
+    using Fr = std::conditional_t<Line, drfe_frustum_line, drfe_frustum_point>;
+    const size_t nn = (size_t)n, nNormal = wantNormal ? 1 : 0;
+    StageLayout<16> in, out;
+    const auto sItems = in.add<MuItem>(nn);
+    const auto sCent = in.add<float>(nNormal * k->n * 3), sScale = in.add<float>(nNormal * k->n_levels);
+    const auto sWorld = in.add<W>(nNormal * nn * (Line ? 6 : 3));
+    const auto sObsKf = in.add<int32_t>(nNormal * T);
+    const auto sRows = in.add<uint4>((size_t)R * 2);
+    const auto sRowObs = in.add<int32_t>((size_t)R);
+    Section<int32_t> sList[MU_BUCKETS];
+    for (int bk = 0; bk < MU_BUCKETS; bk++) sList[bk] = in.add<int32_t>(lists[bk].size());
+    const auto sBest = out.add<int32_t>(nn);
+    const auto sDesc = out.add<uint4>(nn * 2);
+    const auto sNormal = out.add<W>(nn * 3);
+    const auto sMax = out.add<float>(nn), sMin = out.add<float>(nn);
+    const auto sStatus = out.add<uint8_t>(nn);
+    const auto sFrustum = out.add<Fr>(o->frustum ? nn : 0);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, b->hin.grow(inEnd));
-    HIPCHK(c, b->din.grow(inEnd));
-    HIPCHK(c, b->hout.grow(outEnd));
-    HIPCHK(c, b->dout.grow(outEnd));
-    char* h = b->hin;
-    std::memcpy(h + oItems, items.data(), (size_t)n * sizeof(MuItem));
-    if (wantNormal) {
-        if (k->n) std::memcpy(h + oCent, k->center, (size_t)k->n * 12);
-        std::memcpy(h + oScale, k->scale_factors, (size_t)k->n_levels * 4);
-        std::memcpy(h + oWorld, it->world, (size_t)n * wsz);
-        if (T) std::memcpy(h + oObsKf, it->obs_kf, (size_t)T * 4);
-    }
+    HIPCHK(c, b->io.grow(in.bytes(), out.bytes()));
+    char* h = b->io.hin;
+    sItems.put(h, items.data());
+    sCent.put(h, k->center);
+    sScale.put(h, k->scale_factors);
+    sWorld.put(h, it->world);
+    sObsKf.put(h, it->obs_kf);
     for (int bk = 0; bk < MU_BUCKETS; bk++) {
-        if (!lists[bk].empty()) std::memcpy(h + oList[bk], lists[bk].data(), lists[bk].size() * 4);
+        sList[bk].put(h, lists[bk].data());
         for (int i : lists[bk]) {
             const MuItem& m = items[(size_t)i];
-            char* rd = h + oRows + 32 * (size_t)m.row0;
-            int32_t* ro = reinterpret_cast<int32_t*>(h + oRowObs) + m.row0;
+            uint4* rd = sRows.at(h) + 2 * (size_t)m.row0;
+            int32_t* ro = sRowObs.at(h) + m.row0;
             for (int q = m.obs0, r = 0; q < m.obs0 + m.nobs; q++) {
                 if (kf_bad(k, it->obs_kf[q])) continue;
-                std::memcpy(rd + 32 * (size_t)r, it->obs_desc + 32 * (size_t)q, 32);
+                std::memcpy(rd + 2 * (size_t)r, it->obs_desc + 32 * (size_t)q, 32);
                 ro[r++] = q - m.obs0;
             }
         }
     }
-    char* d = b->din;
-    char* dO = b->dout;
-    HIPCHK(c, hipMemcpyAsync(d, h, inEnd, hipMemcpyHostToDevice, s));
+    const char* d = b->io.din;
+    char* dO = b->io.dout;
+    HIPCHK(c, hipMemcpyAsync(b->io.din, h, in.bytes(), hipMemcpyHostToDevice, s));
     MuLaunch L{};
-    L.items = reinterpret_cast<const MuItem*>(d + oItems);
+    L.items = sItems.at(d);
     L.n = n; L.what = what; L.line = Line ? 1 : 0; L.nLevels = k->n_levels;
-    L.kfCenter = reinterpret_cast<const float*>(d + oCent);
-    L.scale = reinterpret_cast<const float*>(d + oScale);
-    L.world = d + oWorld;
-    L.obsKf = reinterpret_cast<const int32_t*>(d + oObsKf);
-    L.rows = reinterpret_cast<const uint4*>(d + oRows);
-    L.rowObs = reinterpret_cast<const int32_t*>(d + oRowObs);
+    L.kfCenter = sCent.at(d);
+    L.scale = sScale.at(d);
+    L.world = sWorld.at(d);
+    L.obsKf = sObsKf.at(d);
+    L.rows = sRows.at(d);
+    L.rowObs = sRowObs.at(d);
     for (int bk = 0; bk < MU_BUCKETS; bk++) {
-        L.list[bk] = reinterpret_cast<const int32_t*>(d + oList[bk]);
+        L.list[bk] = sList[bk].at(d);
         L.count[bk] = (int)lists[bk].size();
     }
     L.maxRowsWg = maxWg;
-    L.best = reinterpret_cast<int32_t*>(dO + pBest);
-    L.desc = reinterpret_cast<uint4*>(dO + pDesc);
-    L.normal = dO + pNormal;
-    L.maxD = reinterpret_cast<float*>(dO + pMax);
-    L.minD = reinterpret_cast<float*>(dO + pMin);
-    L.status = reinterpret_cast<uint8_t*>(dO + pStatus);
-    L.frustum = o->frustum ? dO + pFrustum : nullptr;
+    L.best = sBest.at(dO);
+    L.desc = sDesc.at(dO);
+    L.normal = sNormal.at(dO);
+    L.maxD = sMax.at(dO);
+    L.minD = sMin.at(dO);
+    L.status = sStatus.at(dO);
+    L.frustum = o->frustum ? sFrustum.at(dO) : nullptr;
     hipError_t e = drfe_launch_map_upkeep(L, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(b->hout, dO, outEnd, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(b->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) { c->err = std::string("map_upkeep batch: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
     /* the host's share while the device works: descriptors of items above the row cap */
     std::vector<uint32_t> rows;
@@ -297,14 +298,14 @@ int upkeep_batch(drfe_ctx* c, int what, const drfe_upkeep_keyframes* k, const dr
         std::memcpy(&descH[32 * q], &rows[8 * (size_t)r], 32);
     }
     HIPCHK(c, hipStreamSynchronize(s));
-    const char* ho = b->hout;
-    if (o->best_obs) std::memcpy(o->best_obs, ho + pBest, (size_t)n * 4);
-    if (o->desc) std::memcpy(o->desc, ho + pDesc, (size_t)n * 32);
-    if (o->normal) std::memcpy(o->normal, ho + pNormal, (size_t)n * nsz);
-    if (o->max_distance) std::memcpy(o->max_distance, ho + pMax, (size_t)n * 4);
-    if (o->min_distance) std::memcpy(o->min_distance, ho + pMin, (size_t)n * 4);
-    std::memcpy(o->status, ho + pStatus, (size_t)n);
-    if (o->frustum) std::memcpy(o->frustum, ho + pFrustum, (size_t)n * fsz);
+    const char* ho = b->io.hout;
+    sBest.get(ho, o->best_obs);
+    sDesc.get(ho, o->desc);
+    sNormal.get(ho, o->normal);
+    sMax.get(ho, o->max_distance);
+    sMin.get(ho, o->min_distance);
+    sStatus.get(ho, o->status);
+    sFrustum.get(ho, o->frustum);
     for (size_t q = 0; q < hostDesc.size(); q++) {
         if (o->best_obs) o->best_obs[hostDesc[q]] = bestH[q];
         if (o->desc) std::memcpy(o->desc + 32 * (size_t)hostDesc[q], &descH[32 * q], 32);

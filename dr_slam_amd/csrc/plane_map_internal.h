@@ -6,6 +6,7 @@
 #define DRFE_PLANE_MAP_INTERNAL_H
 
 #include "post_internal.h"
+#include "stage_layout.h"
 
 #include <algorithm>
 #include <string>
@@ -17,8 +18,6 @@ static inline hipError_t drfe_pm_reserve(HipBuf<T, Pinned>& b, size_t n)
 {
     return b.grow(std::max(n, 16 / sizeof(T)));
 }
-
-static inline size_t drfe_align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 struct PmBuffers {
     /* the resident maps: per plane coefficients, bad flag and the slot of its cloud in the arena (device copies of the host

@@ -185,25 +185,27 @@ int drfe_plane_match_batch(drfe_ctx* c, const drfe_plane_match_params* params, i
     }
     /* packed inputs: Tcw [F x 16], coefs [Q x 4], per frame plane (frame, map, first pair) + pair total, the maps' plane and
      * point offsets, then the three index arrays (priors in, results out) */
-    const size_t oT = 0, oC = drfe_align16(oT + (size_t)nframes * 64), oQ = drfe_align16(oC + (size_t)Q * 16),
-                 oO = drfe_align16(oQ + ((size_t)Q * 3 + 1) * 4), oMap = drfe_align16(oO + ((size_t)b->maps + 1) * 8),
-                 oPar = drfe_align16(oMap + (size_t)Q * 4), oVer = drfe_align16(oPar + (size_t)Q * 4), oEnd = drfe_align16(oVer + (size_t)Q * 4);
+    const size_t nOff = (size_t)b->maps + 1;
+    StageLayout<16> lay;
+    const auto sT = lay.add<float>((size_t)nframes * 16), sC = lay.add<float>((size_t)Q * 4);
+    const auto sQ = lay.add<int32_t>((size_t)Q * 3 + 1), sO = lay.add<int32_t>(nOff * 2);
+    const auto sMap = lay.add<int32_t>((size_t)Q), sPar = lay.add<int32_t>((size_t)Q), sVer = lay.add<int32_t>((size_t)Q);
     HIPCHK(c, hipSetDevice(c->device));
     if (!b->staged) HIPCHK(c, hipEventCreateWithFlags(&b->staged, hipEventDisableTiming));
     if (!b->done) HIPCHK(c, hipEventCreateWithFlags(&b->done, hipEventDisableTiming));
     HIPCHK(c, hipEventSynchronize(b->staged));          /* the previous batch's staging is free again */
     const size_t nPoints = (size_t)b->pointOff[b->maps];
-    HIPCHK(c, drfe_pm_reserve(b->hio, oEnd));
-    HIPCHK(c, drfe_pm_reserve(b->io, oEnd));
+    HIPCHK(c, drfe_pm_reserve(b->hio, lay.bytes()));
+    HIPCHK(c, drfe_pm_reserve(b->io, lay.bytes()));
     HIPCHK(c, drfe_pm_reserve(b->angle, (size_t)pairs));
     HIPCHK(c, drfe_pm_reserve(b->key, (size_t)pairs));
     HIPCHK(c, drfe_pm_reserve(b->work, (size_t)workCap));
     HIPCHK(c, drfe_pm_reserve(b->acc, 4 + 2 * (size_t)nframes));
     HIPCHK(c, drfe_pm_reserve(b->flags, nPoints));
     char* h = b->hio;
-    std::memcpy(h + oT, Tcw, (size_t)nframes * 64);
-    if (Q) std::memcpy(h + oC, coefs, (size_t)Q * 16);
-    int32_t* qf = reinterpret_cast<int32_t*>(h + oQ);
+    sT.put(h, Tcw);
+    sC.put(h, coefs);
+    int32_t* qf = sQ.at(h);
     int32_t* qm = qf + Q;
     int32_t* qp = qm + Q;
     int32_t pairAt = 0;
@@ -216,32 +218,32 @@ int drfe_plane_match_batch(drfe_ctx* c, const drfe_plane_match_params* params, i
             pairAt += b->planeOff[m + 1] - b->planeOff[m];
         }
     qp[Q] = pairAt;
-    std::memcpy(h + oO, b->planeOff.data(), ((size_t)b->maps + 1) * 4);
-    std::memcpy(h + oO + ((size_t)b->maps + 1) * 4, b->pointOff.data(), ((size_t)b->maps + 1) * 4);
-    int32_t* outs[3] = {reinterpret_cast<int32_t*>(h + oMap), reinterpret_cast<int32_t*>(h + oPar), reinterpret_cast<int32_t*>(h + oVer)};
+    std::memcpy(sO.at(h), b->planeOff.data(), nOff * 4);
+    std::memcpy(sO.at(h) + nOff, b->pointOff.data(), nOff * 4);
+    int32_t* outs[3] = {sMap.at(h), sPar.at(h), sVer.at(h)};
     const int32_t* priors[3] = {map_idx, par_idx, ver_idx};
     for (int k = 0; k < 3; k++) {
         if (priors[k]) std::memcpy(outs[k], priors[k], (size_t)Q * 4);
         else std::fill(outs[k], outs[k] + Q, -1);
     }
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, hipMemcpyAsync(b->io, b->hio, oEnd, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(b->io, b->hio, lay.bytes(), hipMemcpyHostToDevice, s));
     HIPCHK(c, hipEventRecord(b->staged, s));
     HIPCHK(c, hipMemsetAsync(b->acc, 0, (4 + 2 * (size_t)nframes) * 4, s));
     if (pairs) HIPCHK(c, hipMemsetAsync(b->key, 0xFF, (size_t)pairs * 4, s));
     if (flag_points && nPoints) HIPCHK(c, hipMemsetAsync(b->flags, 0, nPoints, s));
     char* d = b->io;
     PmLaunch L;
-    L.Tcw = reinterpret_cast<const float*>(d + oT);
-    L.coefs = reinterpret_cast<const float*>(d + oC);
-    L.qFrame = reinterpret_cast<const int32_t*>(d + oQ);
+    L.Tcw = sT.at(d);
+    L.coefs = sC.at(d);
+    L.qFrame = sQ.at(d);
     L.qMap = L.qFrame + Q;
     L.qPair = L.qMap + Q;
-    L.mapOut = reinterpret_cast<int32_t*>(d + oMap);
-    L.parOut = reinterpret_cast<int32_t*>(d + oPar);
-    L.verOut = reinterpret_cast<int32_t*>(d + oVer);
-    L.planeOff = reinterpret_cast<const int32_t*>(d + oO);
-    L.pointOff = L.planeOff + b->maps + 1;
+    L.mapOut = sMap.at(d);
+    L.parOut = sPar.at(d);
+    L.verOut = sVer.at(d);
+    L.planeOff = sO.at(d);
+    L.pointOff = L.planeOff + nOff;
     L.mapCoefs = b->mapCoefs;
     L.mapBad = b->mapBad;
     L.cloudBeg = b->cloudBeg;
@@ -268,7 +270,7 @@ int drfe_plane_match_batch(drfe_ctx* c, const drfe_plane_match_params* params, i
     b->flagged = flag_points != 0;
     b->frameOff.assign(plane_offsets, plane_offsets + nframes + 1);
     b->frameMap.assign(frame_map, frame_map + nframes);
-    b->offMap = oMap; b->offPar = oPar; b->offVer = oVer;
+    b->offMap = sMap.off; b->offPar = sPar.off; b->offVer = sVer.off;
     return DRFE_OK;
 }
 

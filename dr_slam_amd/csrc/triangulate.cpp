@@ -3,14 +3,14 @@
  * entries (triangulate_kernels.hip) and their counters.  Both sides evaluate triangulate_core.h; DESIGN.md section 15. */
 #include "triangulate_internal.h"
 #include "hip_buf.h"
+#include "stage_layout.h"
 
 #include <cstring>
 #include <string>
 #include <vector>
 
 struct TriBuffers {
-    PinnedBuf<char> hin, hout;         /* staging: one copy each way */
-    DevBuf<char> din, dout;
+    StagePair io;                      /* staging: one copy each way */
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -21,8 +21,6 @@ void drfe_triangulate_free(drfe_ctx* c)
 }
 
 namespace {
-
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
 /* the feature arrays of either kind, for validation and staging */
 struct Feats {
@@ -155,73 +153,71 @@ int tri_batch(drfe_ctx* c, int monocular, const drfe_tri_keyframes* k, const Fea
     b->stats[3] += M;
     std::vector<uint8_t> skip((size_t)p->n);
     for (int i = 0; i < p->n; i++) skip[(size_t)i] = tr_pair_skipped(k->kf[p->kf1[i]], k->kf[p->kf2[i]]) ? 1 : 0;
-    const int w = Line ? 6 : 3;
-    const size_t oKf = 0, oScale = align16(oKf + (size_t)K * sizeof(drfe_tri_keyframe)), oSig = align16(oScale + (size_t)K * L * 4),
-                 oOff = align16(oSig + (size_t)K * L * 4), oOct = align16(oOff + ((size_t)K + 1) * 4), oA = align16(oOct + (size_t)F * 4),
-                 oB = align16(oA + (size_t)F * (Line ? 16 : 8)), oC = align16(oB + (size_t)F * (Line ? 4 : 8)),
-                 oD = align16(oC + (size_t)F * (Line ? 48 : 4)), oMatch = align16(oD + (size_t)F * (Line ? 0 : 4)),
-                 inEnd = align16(oMatch + (size_t)M * sizeof(TriMatch));
-    const size_t pStatus = 0, pBranch = align16((size_t)M), pX = align16(pBranch + (size_t)M), outEnd = align16(pX + (size_t)M * w * 4);
+    const size_t nF = (size_t)F;
+    StageLayout<16> in, out;
+    const auto sKf = in.add<drfe_tri_keyframe>((size_t)K);
+    const auto sScale = in.add<float>((size_t)K * L), sSig = in.add<float>((size_t)K * L);
+    const auto sOff = in.add<int32_t>((size_t)K + 1), sOct = in.add<int32_t>(nF);
+    const auto sA = in.add<float>(nF * (Line ? 4 : 2)), sB = in.add<float>(nF * (Line ? 1 : 2));   /* points: un, raw; lines: ends, depth */
+    const auto sRight = in.add<float>(Line ? 0 : nF), sDepth = in.add<float>(Line ? 0 : nF);
+    const auto sL3 = in.add<double>(Line ? nF * 6 : 0);
+    const auto sMatch = in.add<TriMatch>((size_t)M);
+    const auto sStatus = out.add<uint8_t>((size_t)M), sBranch = out.add<uint8_t>((size_t)M);
+    const auto sX = out.add<float>((size_t)M * (Line ? 6 : 3));
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, b->hin.grow(inEnd));
-    HIPCHK(c, b->din.grow(inEnd));
-    HIPCHK(c, b->hout.grow(outEnd));
-    HIPCHK(c, b->dout.grow(outEnd));
-    char* h = b->hin;
-    std::memcpy(h + oKf, k->kf, (size_t)K * sizeof(drfe_tri_keyframe));
-    std::memcpy(h + oScale, k->scale_factors, (size_t)K * L * 4);
-    std::memcpy(h + oSig, k->level_sigma2, (size_t)K * L * 4);
-    std::memcpy(h + oOff, f.off, ((size_t)K + 1) * 4);
-    if (F > 0) {
-        std::memcpy(h + oOct, f.octave, (size_t)F * 4);
-        std::memcpy(h + oA, f.a, (size_t)F * (Line ? 16 : 8));
-        std::memcpy(h + oB, f.b, (size_t)F * (Line ? 4 : 8));
-        if (Line) std::memcpy(h + oC, f.l3, (size_t)F * 48);
-        else { std::memcpy(h + oC, f.c, (size_t)F * 4); std::memcpy(h + oD, f.d, (size_t)F * 4); }
-    }
-    TriMatch* rec = reinterpret_cast<TriMatch*>(h + oMatch);
+    HIPCHK(c, b->io.grow(in.bytes(), out.bytes()));
+    char* h = b->io.hin;
+    sKf.put(h, k->kf);
+    sScale.put(h, k->scale_factors);
+    sSig.put(h, k->level_sigma2);
+    sOff.put(h, f.off);
+    sOct.put(h, f.octave);
+    sA.put(h, f.a);
+    sB.put(h, f.b);
+    sRight.put(h, f.c);
+    sDepth.put(h, f.d);
+    sL3.put(h, f.l3);
+    TriMatch* rec = sMatch.at(h);
     for (int i = 0; i < p->n; i++)
         for (int m = p->match_offsets[i]; m < p->match_offsets[i + 1]; m++)
             rec[m] = TriMatch{skip[(size_t)i] ? -1 : p->kf1[i], p->kf2[i], p->matches[2 * (size_t)m], p->matches[2 * (size_t)m + 1]};
-    char* d = b->din;
-    char* dO = b->dout;
-    HIPCHK(c, hipMemcpyAsync(d, h, inEnd, hipMemcpyHostToDevice, s));
+    const char* d = b->io.din;
+    char* dO = b->io.dout;
+    HIPCHK(c, hipMemcpyAsync(b->io.din, h, in.bytes(), hipMemcpyHostToDevice, s));
     TriLaunch Lc{};
-    Lc.V.kf = reinterpret_cast<const drfe_tri_keyframe*>(d + oKf);
-    Lc.V.scale = reinterpret_cast<const float*>(d + oScale);
-    Lc.V.sigma2 = reinterpret_cast<const float*>(d + oSig);
+    Lc.V.kf = sKf.at(d);
+    Lc.V.scale = sScale.at(d);
+    Lc.V.sigma2 = sSig.at(d);
     Lc.V.nLevels = L;
-    Lc.V.off = reinterpret_cast<const int32_t*>(d + oOff);
-    Lc.V.octave = reinterpret_cast<const int32_t*>(d + oOct);
+    Lc.V.off = sOff.at(d);
+    Lc.V.octave = sOct.at(d);
     if (Line) {
-        Lc.V.ends = reinterpret_cast<const float*>(d + oA);
-        Lc.V.depthLine = reinterpret_cast<const float*>(d + oB);
-        Lc.V.lines3d = reinterpret_cast<const double*>(d + oC);
+        Lc.V.ends = sA.at(d);
+        Lc.V.depthLine = sB.at(d);
+        Lc.V.lines3d = sL3.at(d);
     } else {
-        Lc.V.un = reinterpret_cast<const float*>(d + oA);
-        Lc.V.raw = reinterpret_cast<const float*>(d + oB);
-        Lc.V.uRight = reinterpret_cast<const float*>(d + oC);
-        Lc.V.depth = reinterpret_cast<const float*>(d + oD);
+        Lc.V.un = sA.at(d);
+        Lc.V.raw = sB.at(d);
+        Lc.V.uRight = sRight.at(d);
+        Lc.V.depth = sDepth.at(d);
     }
-    Lc.match = reinterpret_cast<const TriMatch*>(d + oMatch);
+    Lc.match = sMatch.at(d);
     Lc.n = M;
     Lc.line = Line ? 1 : 0;
-    Lc.status = reinterpret_cast<uint8_t*>(dO + pStatus);
-    Lc.branch = reinterpret_cast<uint8_t*>(dO + pBranch);
-    Lc.x3d = reinterpret_cast<float*>(dO + pX);
+    Lc.status = sStatus.at(dO);
+    Lc.branch = sBranch.at(dO);
+    Lc.x3d = sX.at(dO);
     hipError_t e = drfe_launch_triangulate(Lc, s);
-    if (e == hipSuccess && M > 0) e = hipMemcpyAsync(b->hout, dO, outEnd, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess && M > 0) e = hipMemcpyAsync(b->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) { c->err = std::string("triangulate batch: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
     HIPCHK(c, hipStreamSynchronize(s));
-    const char* ho = b->hout;
-    const uint8_t* st = reinterpret_cast<const uint8_t*>(ho + pStatus);
-    const uint8_t* br = reinterpret_cast<const uint8_t*>(ho + pBranch);
-    if (M > 0) {
-        std::memcpy(o->status, st, (size_t)M);
-        if (o->branch) std::memcpy(o->branch, br, (size_t)M);
-        if (o->x3d) std::memcpy(o->x3d, ho + pX, (size_t)M * w * 4);
-    }
+    const char* ho = b->io.hout;
+    const uint8_t* st = sStatus.at(ho);
+    const uint8_t* br = sBranch.at(ho);
+    sStatus.get(ho, o->status);
+    sBranch.get(ho, o->branch);
+    sX.get(ho, o->x3d);
     finish_pairs(p, skip, st, br, o, b->stats);
     return DRFE_OK;
 }

@@ -118,15 +118,17 @@ def test_rectangle_edges(ctx, oracle_mod):
 
 
 @pytest.mark.parametrize("seed,motion,th", [(1, 0.0, 15.0), (2, 0.5, 15.0), (3, -0.5, 15.0), (4, 0.0, 7.0), (5, 0.0, 30.0),
-                                            (11, 0.0, 15.0), (12, 0.2, 20.0)])
+                                            (11, 0.0, 15.0), (12, 0.2, 20.0), (13, 0.0, 15.0)])
 def test_lsd_search_by_projection(ctx, oracle_mod, seed, motion, th):
-    """LSDmatcher::SearchByProjection, both overloads (row a-15): device replay vs the oracle, identical claims."""
+    """LSDmatcher::SearchByProjection, both overloads (row a-15): device replay vs the oracle, identical claims.  Seed 13 runs
+    with odd counts: the 68-byte query records then end off a multiple of 8, so every later piece of the call's scratch block
+    relies on its own alignment."""
     import os
     import line_scenarios as LS
     from dr_slam_amd import lib
     O = oracle_mod
-    sc = LS.make(seed, lib.KEYLINE_DTYPE, lib.MAPLINE_DTYPE, lib.TRACKED_LINE_DTYPE, n_cur=40 if seed < 10 else 150,
-                 n_last=48 if seed < 10 else 200, motion=motion)
+    n_cur, n_last = (39, 47) if seed == 13 else (40, 48) if seed < 10 else (150, 200)
+    sc = LS.make(seed, lib.KEYLINE_DTYPE, lib.MAPLINE_DTYPE, lib.TRACKED_LINE_DTYPE, n_cur=n_cur, n_last=n_last, motion=motion)
     cam = lib.Camera(**LS.CAM) if hasattr(lib, "Camera") else None
     assert cam is not None
     n, ml = ctx.lsd_search_by_projection_last(sc["Tcw_cur"], sc["Tcw_last"], cam, sc["last"], sc["cur"], sc["cur_desc"], th,
