@@ -4,6 +4,7 @@
 #include "drfe_internal.h"
 #include "map_upkeep_internal.h"
 #include "triangulate_internal.h"
+#include "sim3_internal.h"
 #include <atomic>
 #include "post_internal.h"
 #include "match_internal.h"
@@ -150,6 +151,7 @@ void drfe_destroy(drfe_ctx* c)
     drfe_plane_match_free(c);
     drfe_map_upkeep_free(c);
     drfe_triangulate_free(c);
+    drfe_sim3_free(c);
     drfe_post_free(c);
     drfe_one_shot_free(c);
     drfe_frame_lanes_free(c);

@@ -16,6 +16,7 @@
  * because the reference shares the process-wide state between its extraction threads. */
 #include "../../include/drfe.h"
 #include "ahc_math.h"
+#include "glibc_rand.h"
 
 #include <algorithm>
 #include <cmath>
@@ -24,37 +25,6 @@
 #include <vector>
 
 namespace {
-
-/* glibc random_r TYPE_3 (x^31 + x^3 + 1), what rand() runs: r[i] = r[i-31] + r[i-3], output >> 1; the seed
- * expands through the 16807 Lehmer step and the first 310 outputs are discarded. */
-struct GlibcRand {
-    uint32_t r[34];
-    int pos;
-    explicit GlibcRand(uint32_t seed)
-    {
-        std::vector<uint32_t> t(344);
-        int32_t w = seed ? (int32_t)seed : 1;
-        t[0] = (uint32_t)w;
-        for (int i = 1; i < 31; i++) {
-            const int32_t hi = w / 127773, lo = w % 127773;
-            w = 16807 * lo - 2836 * hi;
-            if (w < 0) w += 2147483647;
-            t[i] = (uint32_t)w;
-        }
-        for (int i = 31; i < 34; i++) t[i] = t[i - 31];
-        for (int i = 34; i < 344; i++) t[i] = t[i - 31] + t[i - 3];
-        for (int i = 0; i < 34; i++) r[i] = t[310 + i];   /* the last 34 values: enough history for i-31 */
-        pos = 0;
-    }
-    int next()
-    {
-        /* ring of 34: newest at (pos+33)%34; r[i-31] is 31 back from the new element, r[i-3] three back */
-        const uint32_t v = r[(pos + 34 - 31) % 34] + r[(pos + 34 - 3) % 34];
-        r[pos] = v;
-        pos = (pos + 1) % 34;
-        return (int)(v >> 1);
-    }
-};
 
 struct P3 { double x, y, z; };
 inline P3 operator-(const P3& a, const P3& b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }

@@ -50,6 +50,8 @@ SYMBOLS = (
     "drfe_map_upkeep_stats",
     "drfe_triangulate_points_host", "drfe_triangulate_lines_host", "drfe_triangulate_points_batch", "drfe_triangulate_lines_batch",
     "drfe_triangulate_stats", "drfe_debug_triangulate_math",
+    "drfe_sim3_ransac_host", "drfe_sim3_ransac_batch", "drfe_sim3_stats", "drfe_debug_sim3_atan2", "drfe_debug_sim3_rand",
+    "drfe_debug_sim3_horn", "drfe_debug_sim3_hand_back",
 )
 
 FRUSTUM_POINT_DTYPE = np.dtype([("world", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"),
@@ -156,6 +158,23 @@ TRI_LINE_CODES = ("accepted", "baseline", "no_stereo", "z_sp1", "z_ep1", "z_sp2"
 TRI_IDX2_PAST_KF1 = 0x80
 TRI_BRANCH_NONE, TRI_BRANCH_SVD, TRI_BRANCH_STEREO1, TRI_BRANCH_STEREO2 = 0, 1, 2, 3
 TRI_STATS = ("calls", "pairs", "pairs_skipped", "matches", "svd", "stereo1", "stereo2", "accepted")
+
+
+class Sim3Problems(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pad", C.c_int32), ("Tcw1", C.c_void_p), ("Tcw2", C.c_void_p), ("K1", C.c_void_p),
+                ("K2", C.c_void_p), ("fix_scale", C.c_void_p), ("probability", C.c_void_p), ("min_inliers", C.c_void_p),
+                ("max_iterations", C.c_void_p), ("seed", C.c_void_p), ("offsets", C.c_void_p), ("Xw1", C.c_void_p),
+                ("Xw2", C.c_void_p), ("sigma2_1", C.c_void_p), ("sigma2_2", C.c_void_p)]    # drfe_sim3_problems
+
+
+class Sim3Out(C.Structure):
+    _fields_ = [("iterations", C.c_void_p), ("hypotheses", C.c_void_p), ("sample", C.c_void_p), ("R12", C.c_void_p),
+                ("t12", C.c_void_p), ("s12", C.c_void_p), ("T12", C.c_void_p), ("inliers", C.c_void_p), ("returns", C.c_void_p),
+                ("best", C.c_void_p), ("mask", C.c_void_p)]                          # drfe_sim3_out
+
+
+SIM3_MAX_CORR, SIM3_MAX_ITERATIONS = 4096, 300
+SIM3_STATS = ("calls", "solvers", "hypotheses", "correspondences", "solvers_lds", "solvers_global", "uncertified", "solvers_empty")
 
 
 class Camera(C.Structure):
@@ -307,6 +326,13 @@ def load() -> C.CDLL:
     L.drfe_triangulate_lines_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.drfe_triangulate_stats.argtypes = [vp, vp]
     L.drfe_debug_triangulate_math.argtypes = [i32, vp, vp, i32, vp]
+    L.drfe_sim3_ransac_host.argtypes = [vp, vp]
+    L.drfe_sim3_ransac_batch.argtypes = [vp, vp, vp, vp]
+    L.drfe_sim3_stats.argtypes = [vp, vp]
+    L.drfe_debug_sim3_atan2.argtypes = [vp, vp, i32, vp, vp]
+    L.drfe_debug_sim3_rand.argtypes = [C.c_uint32, i32, vp]
+    L.drfe_debug_sim3_horn.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+    L.drfe_debug_sim3_hand_back.argtypes = [vp, i32]
     L.drfe_lsd_segments_host.argtypes = [vp, vp, vp, i32, i32, f64, vp, i32, C.POINTER(i32)]
     L.drfe_lsd_configure.argtypes = [vp, i32]
     L.drfe_lsd_configure_rect.argtypes = [vp, i32]
@@ -647,6 +673,97 @@ def triangulate_math(which, y, x=None):
     if L.drfe_debug_triangulate_math(which, _p(y), _p(x), len(y), _p(out)) != 0:
         raise DrfeError("drfe_debug_triangulate_math failed")
     return out
+
+
+def _sim3_pack(problems):
+    """Packs a problem set (dict: Tcw1 [n, 12], Tcw2 [n, 12], K1 [n, 4], K2 [n, 4] (fx, fy, cx, cy), fix_scale [n], probability [n],
+    min_inliers [n], max_iterations [n], seed [n], offsets [n + 1], Xw1 [M, 3], Xw2 [M, 3], sigma2_1 [M], sigma2_2 [M]) into
+    drfe_sim3_problems and allocates the table: (problems record, out record, the table as a dict, the arrays to keep alive).  The
+    table: per solver iterations, hypotheses, row0, words, mask0; per row sample [3], R12 [9], t12 [3], s12, T12 [12], inliers,
+    returns, best; mask (uint64 words).  Solver s's rows are row0[s] + h, its mask words mask0[s] + h * words[s] + (i // 64)
+    (sim3_table slices them)."""
+    keep = []
+
+    def arr(key, dt, shape=-1):
+        v = np.ascontiguousarray(np.asarray(problems[key], dt).reshape(shape))
+        keep.append(v)
+        return v
+    off = arr("offsets", np.int32)
+    n = len(off) - 1
+    maxit = arr("max_iterations", np.int32)
+    P = Sim3Problems(n, 0, _p(arr("Tcw1", np.float32, (-1, 12))), _p(arr("Tcw2", np.float32, (-1, 12))),
+                     _p(arr("K1", np.float32, (-1, 4))), _p(arr("K2", np.float32, (-1, 4))), _p(arr("fix_scale", np.uint8)),
+                     _p(arr("probability", np.float64)), _p(arr("min_inliers", np.int32)), _p(maxit), _p(arr("seed", np.uint32)),
+                     _p(off), _p(arr("Xw1", np.float32, (-1, 3))), _p(arr("Xw2", np.float32, (-1, 3))),
+                     _p(arr("sigma2_1", np.float32)), _p(arr("sigma2_2", np.float32)))
+    cap = np.maximum(maxit.astype(np.int64), 1)
+    words = (np.diff(off.astype(np.int64)) + 63) // 64
+    row0 = np.concatenate([[0], np.cumsum(cap)])
+    mask0 = np.concatenate([[0], np.cumsum(cap * words)])
+    rows, W = int(row0[-1]), int(mask0[-1])
+    r = dict(iterations=np.zeros(n, np.int32), hypotheses=np.zeros(n, np.int32), row0=row0[:-1], words=words, mask0=mask0[:-1],
+             sample=np.zeros((rows, 3), np.int32), R12=np.zeros((rows, 9), np.float32), t12=np.zeros((rows, 3), np.float32),
+             s12=np.zeros(rows, np.float32), T12=np.zeros((rows, 12), np.float32), inliers=np.zeros(rows, np.int32),
+             returns=np.zeros(rows, np.uint8), best=np.zeros(rows, np.int32), mask=np.zeros(W, np.uint64))
+    out = Sim3Out(*[_p(r[k]) for k in ("iterations", "hypotheses", "sample", "R12", "t12", "s12", "T12", "inliers", "returns",
+                                       "best", "mask")])
+    return P, out, r, keep
+
+
+def _sim3_call(fn, head, problems):
+    """fn(*head, problems, out) over _sim3_pack's records: (return code, table)"""
+    P, out, r, _keep = _sim3_pack(problems)
+    rc = fn(*head, C.byref(P), C.byref(out), *([None] if head else []))
+    return rc, r
+
+
+def sim3_ransac_host(problems):
+    """Sim3Solver's whole hypothesis table of every solver on the host (drfe_sim3_ransac_host, DESIGN.md section 16);
+    problems and result as _sim3_call"""
+    rc, r = _sim3_call(load().drfe_sim3_ransac_host, (), problems)
+    if rc != 0:
+        raise DrfeError(f"drfe_sim3_ransac_host failed ({rc})")
+    return r
+
+
+def sim3_table(result, s):
+    """Solver s's filled rows of a sim3_ransac_* result: dict(iterations, sample, R12, t12, s12, T12, inliers, returns, best,
+    mask [hypotheses, words])"""
+    a, n, w = int(result["row0"][s]), int(result["hypotheses"][s]), int(result["words"][s])
+    t = {k: result[k][a:a + n] for k in ("sample", "R12", "t12", "s12", "T12", "inliers", "returns", "best")}
+    m0 = int(result["mask0"][s])
+    t["mask"] = result["mask"][m0:m0 + n * w].reshape(n, w)
+    t["iterations"] = int(result["iterations"][s])
+    return t
+
+
+def sim3_atan2(y, x):
+    """dr_slam_amd/csrc/cr_atan2.h's correctly rounded atan2 over float64 arrays (y >= 0): (values, certified)"""
+    y = np.ascontiguousarray(y, np.float64)
+    x = np.ascontiguousarray(x, np.float64)
+    out, ok = np.zeros_like(y), np.zeros(len(y), np.int32)
+    if load().drfe_debug_sim3_atan2(_p(y), _p(x), len(y), _p(out), _p(ok)) != 0:
+        raise DrfeError("drfe_debug_sim3_atan2 failed")
+    return out, ok
+
+
+def sim3_rand(seed, n):
+    """the first n values of glibc's rand() after srand(seed), from dr_slam_amd/csrc/glibc_rand.h"""
+    out = np.zeros(n, np.int32)
+    if load().drfe_debug_sim3_rand(int(seed), n, _p(out)) != 0:
+        raise DrfeError("drfe_debug_sim3_rand failed")
+    return out
+
+
+def sim3_horn(P1, P2, fix_scale, libm=False):
+    """sim3_core.h's ComputeSim3 over samples P1, P2 [n, 3, 3] (one point per column): ([n, 37] = R12, t12, s12, T12, T21;
+    certified [n]); libm: atan2, sin, cos from the host's libm"""
+    P1 = np.ascontiguousarray(P1, np.float32).reshape(-1, 9)
+    P2 = np.ascontiguousarray(P2, np.float32).reshape(-1, 9)
+    out, ok = np.zeros((len(P1), 37), np.float32), np.zeros(len(P1), np.int32)
+    if load().drfe_debug_sim3_horn(_p(P1), _p(P2), len(P1), int(fix_scale), int(libm), _p(out), _p(ok)) != 0:
+        raise DrfeError("drfe_debug_sim3_horn failed")
+    return out, ok
 
 
 def manhattan_math(which, x):
@@ -1757,6 +1874,23 @@ class Context:
         st = np.zeros(8, np.int64)
         self._chk(self.L.drfe_triangulate_stats(self.h, _p(st)), "drfe_triangulate_stats")
         return dict(zip(TRI_STATS, st.tolist()))
+
+    def sim3_ransac_batch(self, problems):
+        """sim3_ransac_host on the device (drfe_sim3_ransac_batch): same table, same bits"""
+        rc, r = _sim3_call(self.L.drfe_sim3_ransac_batch, (self.h,), problems)
+        self._chk(rc, "drfe_sim3_ransac_batch")
+        return r
+
+    def sim3_hand_back(self, every):
+        """test hook: the host finishes every `every`-th hypothesis of a batch call as if the device had not certified it"""
+        self._chk(self.L.drfe_debug_sim3_hand_back(self.h, int(every)), "drfe_debug_sim3_hand_back")
+
+    def sim3_stats(self):
+        """dict(calls, solvers, hypotheses, correspondences, solvers_lds, solvers_global, uncertified, solvers_empty) since the
+        context was created"""
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_sim3_stats(self.h, _p(st)), "drfe_sim3_stats")
+        return dict(zip(SIM3_STATS, st.tolist()))
 
     # --- measurement -------------------------------------------------------------------------------
     def profile_enable(self, on=True):

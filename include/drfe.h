@@ -1086,6 +1086,63 @@ int drfe_triangulate_lines_batch(drfe_ctx* ctx, int monocular, const drfe_tri_ke
  * [3] matches, [4] SVD branch, [5] stereo branch of KF1, [6] of KF2, [7] accepted. */
 int drfe_triangulate_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
 
+/* Sim3Solver (src/Sim3Solver.cc), the RANSAC between SearchByBoW(KF, KF) and SearchBySim3 in LoopClosing::ComputeSim3
+ * (src/LoopClosing.cc:277-446): every hypothesis of every solver of a call at once.  DESIGN.md section 16.
+ *
+ * A solver is two keyframes and its compacted correspondences (those the constructor keeps, in i1 order; isBad,
+ * GetIndexInKeyFrame and mvnIndices1 stay with the caller).  The inlier count of a hypothesis does not depend on an earlier one,
+ * so the entries fill the whole table: row h of a solver is what iteration h of iterate() computes, `best` and `returns` what its
+ * bookkeeping makes of the counts of rows 0 .. h, and the reference's iterate(nIterations, ..) is a walk over the table.
+ * The one deviation: rand() is process-wide and unseeded in the reference; here each solver draws from a glibc rand() stream of
+ * its own, srand(seed), and iteration h uses draws 3h .. 3h + 2.
+ * Caps: DRFE_SIM3_MAX_CORR correspondences per solver, DRFE_SIM3_MAX_ITERATIONS for max_iterations; above them the call is
+ * refused (DRFE_ERR_INVALID), as are decreasing offsets, min_inliers < 0 and a sigma2 with 9.210 * sigma2 outside [0, 2^63). */
+enum { DRFE_SIM3_MAX_CORR = 4096, DRFE_SIM3_MAX_ITERATIONS = 300 };
+typedef struct drfe_sim3_problems {
+    int32_t n;                   /* solvers */
+    int32_t pad;
+    const float* Tcw1;           /* n x 12: [Rcw | tcw] of pKF1, 3x4 row-major */
+    const float* Tcw2;           /* n x 12: of pKF2 */
+    const float* K1;             /* n x 4: fx, fy, cx, cy of pKF1->mK */
+    const float* K2;             /* n x 4 */
+    const uint8_t* fix_scale;    /* n: mbFixScale */
+    const double* probability;   /* n: SetRansacParameters' arguments */
+    const int32_t* min_inliers;  /* n */
+    const int32_t* max_iterations; /* n: <= DRFE_SIM3_MAX_ITERATIONS; below 1 counts as 1, as the reference clamps */
+    const uint32_t* seed;        /* n */
+    const int32_t* offsets;      /* n + 1: solver s's correspondences are [offsets[s], offsets[s + 1]); [0] == 0 */
+    const float* Xw1;            /* 3 per correspondence: pMP1->GetWorldPos() */
+    const float* Xw2;            /* 3 per correspondence: pMP2->GetWorldPos() */
+    const float* sigma2_1;       /* per correspondence: pKF1->mvLevelSigma2[kp1.octave] */
+    const float* sigma2_2;
+} drfe_sim3_problems;
+/* Every pointer is required.  Solver s owns the rows [row0(s), row0(s) + cap(s)), cap(s) = max(1, max_iterations[s]), row0 the
+ * prefix sum of cap; its masks start at word mask0(s), the prefix sum of cap(s) * words(s), words(s) = ceil(N(s) / 64), row h at
+ * mask0(s) + h * words(s), correspondence i in bit i % 64 of word i / 64.  Rows from hypotheses[s] on are zero. */
+typedef struct drfe_sim3_out {
+    int32_t* iterations;         /* n: mRansacMaxIts after SetRansacParameters' clamp */
+    int32_t* hypotheses;         /* n: rows filled: iterations[s], or 0 when N < min_inliers (iterate returns at once with
+                                    bNoMore) or N < 3 (the reference would index an empty vector) */
+    int32_t* sample;             /* rows x 3: the sampled correspondences in draw order */
+    float* R12;                  /* rows x 9: mR12i */
+    float* t12;                  /* rows x 3: mt12i */
+    float* s12;                  /* rows: ms12i */
+    float* T12;                  /* rows x 12: the upper 3x4 of mT12i */
+    int32_t* inliers;            /* rows: mnInliersi */
+    uint8_t* returns;            /* rows: 1 = iterate hands the transform back at this iteration */
+    int32_t* best;               /* rows: the iteration that holds mBest* after this one */
+    uint64_t* mask;              /* mvbInliersi */
+} drfe_sim3_out;
+/* On the host, no context. */
+int drfe_sim3_ransac_host(const drfe_sim3_problems* problems, drfe_sim3_out* out);
+/* The same on the device: the inputs staged with one copy, four launches, the table back with one copy; returns with the outputs
+ * written (`stream` NULL = the context's).  Same bits as the host entry. */
+int drfe_sim3_ransac_batch(drfe_ctx* ctx, const drfe_sim3_problems* problems, drfe_sim3_out* out, void* stream);
+/* Counters since the context was created: stats[0] batch calls, [1] solvers, [2] hypotheses, [3] correspondences, [4] solvers
+ * whose correspondences the counting kernel kept in LDS, [5] solvers it read from global memory, [6] hypotheses the device
+ * could not certify (atan2, sin / cos) and the host finished, [7] solvers without a hypothesis. */
+int drfe_sim3_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

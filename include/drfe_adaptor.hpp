@@ -16,6 +16,8 @@
  *                                      normal upkeep of map points and lines (host entries; MapUpkeep: the device batch)
  *   drfe::TriangulateNewMapPoints / TriangulateNewMapLines / Triangulation  src/LocalMapping.cc:383-538, 875-1026 - the
  *                                      per-match triangulation of CreateNewMapPoints / CreateNewMapLines2 (Triangulation: device)
+ *   Planar_SLAM::Sim3Solver / drfe::Sim3Batch  include/Sim3Solver.h:35-130 - the loop closer's Sim3 RANSAC as a walk over a
+ *                                      finished hypothesis table (host entry; Sim3Batch: every solver of a call on the device)
  * With -DDRFE_WITH_OPENCV the container types are OpenCV's (cv::Mat, cv::KeyPoint, cv::line_descriptor::KeyLine);
  * without it (this image has no OpenCV) minimal stand-ins with the same member names and memory layout are used, so the
  * header is compiled and exercised here (tests/native/adaptor_caller.cpp, run by tests/test_gpu_native.py).
@@ -2115,6 +2117,231 @@ public:
         return drfe_detail_tri::run<TriangulatedLine, true>(cl, [&cl, c](const drfe_tri_keyframes* k, const drfe_tri_pairs* p, drfe_tri_out* o) {
             const drfe_tri_keylines f = cl.keylines();
             Planar_SLAM::drfe_detail::check(drfe_triangulate_lines_batch(c, 0, k, &f, p, o, nullptr), c, "drfe_triangulate_lines_batch");
+        });
+    }
+
+private:
+    Planar_SLAM::drfe_detail::CtxPtr mCtx;
+    std::mutex mMutex;
+};
+
+}  // namespace drfe
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Sim3Solver (include/Sim3Solver.h:35-130, src/Sim3Solver.cc) over drfe_sim3_ransac_host / drfe_sim3_ransac_batch: the first
+ * iterate() or find() fills the solver's whole hypothesis table, every call after that walks it with the reference's cursor,
+ * bNoMore and vbInliers[mvnIndices1[i]] semantics.  drfe::Sim3Batch fills the tables of many solvers with one device call.
+ * The reference draws from the process-wide rand(); a solver here owns its stream (SetSeed, default 0).  DESIGN.md section 16. */
+namespace drfe {
+class Sim3Batch;
+namespace drfe_detail_sim3 {
+inline drfe_cv::Mat mat32(int rows, int cols, const float* v)
+{
+#ifdef DRFE_WITH_OPENCV
+    drfe_cv::Mat m(rows, cols, CV_32F);
+#else
+    drfe_cv::Mat m(rows, cols, 4);
+#endif
+    for (int r = 0; r < rows; r++) std::memcpy(m.template ptr<float>(r), v + (size_t)r * cols, (size_t)cols * sizeof(float));
+    return m;
+}
+/* one solver's inputs and, once filled, its table */
+struct Problem {
+    float Tcw1[12], Tcw2[12], K1[4], K2[4];
+    uint8_t fixScale = 1;
+    double probability = 0.99;
+    int32_t minInliers = 6, maxIterations = 300;
+    uint32_t seed = 0;
+    std::vector<float> Xw1, Xw2, sig1, sig2;
+    bool filled = false;
+    int32_t iterations = 0, hypotheses = 0, words = 0;
+    std::vector<int32_t> sample, inliers, best;
+    std::vector<float> R12, t12, s12, T12;
+    std::vector<uint8_t> returns;
+    std::vector<uint64_t> mask;
+    int n() const { return (int)sig1.size(); }
+};
+/* fills the tables of `ps` through fn(const drfe_sim3_problems*, drfe_sim3_out*) */
+template <class Fn> inline void fill(const std::vector<Problem*>& ps, Fn fn)
+{
+    const size_t n = ps.size();
+    std::vector<float> Tcw1, Tcw2, K1, K2, Xw1, Xw2, sig1, sig2;
+    std::vector<uint8_t> fix;
+    std::vector<double> prob;
+    std::vector<int32_t> minI, maxI, off{0};
+    std::vector<uint32_t> seed;
+    std::vector<size_t> row0, mask0;
+    size_t rows = 0, words = 0;
+    for (Problem* p : ps) {
+        Tcw1.insert(Tcw1.end(), p->Tcw1, p->Tcw1 + 12); Tcw2.insert(Tcw2.end(), p->Tcw2, p->Tcw2 + 12);
+        K1.insert(K1.end(), p->K1, p->K1 + 4); K2.insert(K2.end(), p->K2, p->K2 + 4);
+        fix.push_back(p->fixScale); prob.push_back(p->probability); minI.push_back(p->minInliers); maxI.push_back(p->maxIterations);
+        seed.push_back(p->seed);
+        Xw1.insert(Xw1.end(), p->Xw1.begin(), p->Xw1.end()); Xw2.insert(Xw2.end(), p->Xw2.begin(), p->Xw2.end());
+        sig1.insert(sig1.end(), p->sig1.begin(), p->sig1.end()); sig2.insert(sig2.end(), p->sig2.begin(), p->sig2.end());
+        off.push_back((int32_t)sig1.size());
+        const size_t cap = (size_t)(p->maxIterations > 1 ? p->maxIterations : 1);
+        p->words = (p->n() + 63) / 64;
+        row0.push_back(rows); mask0.push_back(words);
+        rows += cap; words += cap * (size_t)p->words;
+    }
+    const drfe_sim3_problems in{(int32_t)n, 0, Tcw1.data(), Tcw2.data(), K1.data(), K2.data(), fix.data(), prob.data(), minI.data(),
+                                maxI.data(), seed.data(), off.data(), Xw1.data(), Xw2.data(), sig1.data(), sig2.data()};
+    std::vector<int32_t> its(n + 1), hyp(n + 1), sample(3 * rows + 1), inl(rows + 1), best(rows + 1);
+    std::vector<float> R(9 * rows + 1), t(3 * rows + 1), s(rows + 1), T(12 * rows + 1);
+    std::vector<uint8_t> ret(rows + 1);
+    std::vector<uint64_t> mask(words + 1);
+    drfe_sim3_out out{its.data(), hyp.data(), sample.data(), R.data(), t.data(), s.data(), T.data(), inl.data(), ret.data(), best.data(),
+                      mask.data()};
+    fn(&in, &out);
+    for (size_t q = 0; q < n; q++) {
+        Problem* p = ps[q];
+        const size_t h = (size_t)hyp[q], a = row0[q];
+        p->iterations = its[q];
+        p->hypotheses = hyp[q];
+        p->sample.assign(sample.begin() + 3 * a, sample.begin() + 3 * (a + h));
+        p->R12.assign(R.begin() + 9 * a, R.begin() + 9 * (a + h));
+        p->t12.assign(t.begin() + 3 * a, t.begin() + 3 * (a + h));
+        p->s12.assign(s.begin() + a, s.begin() + a + h);
+        p->T12.assign(T.begin() + 12 * a, T.begin() + 12 * (a + h));
+        p->inliers.assign(inl.begin() + a, inl.begin() + a + h);
+        p->best.assign(best.begin() + a, best.begin() + a + h);
+        p->returns.assign(ret.begin() + a, ret.begin() + a + h);
+        p->mask.assign(mask.begin() + mask0[q], mask.begin() + mask0[q] + h * (size_t)p->words);
+        p->filled = true;
+    }
+}
+inline void fill_host(const std::vector<Problem*>& ps)
+{
+    fill(ps, [](const drfe_sim3_problems* in, drfe_sim3_out* out) {
+        if (drfe_sim3_ransac_host(in, out) != DRFE_OK) throw std::runtime_error("drfe_sim3_ransac_host failed");
+    });
+}
+}  // namespace drfe_detail_sim3
+}  // namespace drfe
+
+namespace Planar_SLAM {
+
+template <class KeyFrameT, class MapPointT>
+class Sim3Solver {
+public:
+    /* :41-116.  The map-graph part (isBad, GetIndexInKeyFrame, mvnIndices1) runs here, the arithmetic in the entries. */
+    Sim3Solver(KeyFrameT* pKF1, KeyFrameT* pKF2, const std::vector<MapPointT*>& vpMatched12, const bool bFixScale = true)
+        : mN1((int)vpMatched12.size())
+    {
+        mP.fixScale = bFixScale ? 1 : 0;
+        const std::vector<MapPointT*> vpKeyFrameMP1 = pKF1->GetMapPointMatches();
+        drfe::drfe_detail_tri::rows34(pKF1->GetPose(), mP.Tcw1);
+        drfe::drfe_detail_tri::rows34(pKF2->GetPose(), mP.Tcw2);
+        const float k1[4] = {pKF1->fx, pKF1->fy, pKF1->cx, pKF1->cy}, k2[4] = {pKF2->fx, pKF2->fy, pKF2->cx, pKF2->cy};
+        std::memcpy(mP.K1, k1, sizeof(k1));
+        std::memcpy(mP.K2, k2, sizeof(k2));
+        for (int i1 = 0; i1 < mN1; i1++) {
+            if (!vpMatched12[i1]) continue;
+            MapPointT* pMP1 = vpKeyFrameMP1[i1];
+            MapPointT* pMP2 = vpMatched12[i1];
+            if (!pMP1) continue;
+            if (pMP1->isBad() || pMP2->isBad()) continue;
+            const int indexKF1 = pMP1->GetIndexInKeyFrame(pKF1), indexKF2 = pMP2->GetIndexInKeyFrame(pKF2);
+            if (indexKF1 < 0 || indexKF2 < 0) continue;
+            mP.sig1.push_back(pKF1->mvLevelSigma2[pKF1->mvKeysUn[indexKF1].octave]);
+            mP.sig2.push_back(pKF2->mvLevelSigma2[pKF2->mvKeysUn[indexKF2].octave]);
+            const auto X1 = pMP1->GetWorldPos();
+            const auto X2 = pMP2->GetWorldPos();
+            for (int q = 0; q < 3; q++) {
+                mP.Xw1.push_back(X1.template ptr<float>(q)[0]);
+                mP.Xw2.push_back(X2.template ptr<float>(q)[0]);
+            }
+            mvnIndices1.push_back((size_t)i1);
+        }
+        SetRansacParameters();
+    }
+    /* the deviation: the stream this solver draws from (the reference shares the process's rand()) */
+    void SetSeed(uint32_t seed) { mP.seed = seed; mP.filled = false; mCursor = 0; mBest = -1; }
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300)
+    {
+        mP.probability = probability;
+        mP.minInliers = minInliers;
+        mP.maxIterations = maxIterations;
+        mP.filled = false;
+        mCursor = 0;                    /* mnIterations = 0.  (The reference keeps mnBestInliers across a second call; here a call after iterate() starts a fresh table.) */
+    }
+    drfe_cv::Mat find(std::vector<bool>& vbInliers12, int& nInliers)
+    {
+        bool bFlag;
+        Fill();
+        return iterate(mP.iterations, bFlag, vbInliers12, nInliers);
+    }
+    /* :144-211 as a walk over the table */
+    drfe_cv::Mat iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers)
+    {
+        bNoMore = false;
+        vbInliers = std::vector<bool>((size_t)mN1, false);
+        nInliers = 0;
+        if (mP.n() < mP.minInliers) { bNoMore = true; return drfe_cv::Mat(); }
+        Fill();
+        int nCurrentIterations = 0;
+        while (mCursor < mP.hypotheses && nCurrentIterations < nIterations) {
+            const int h = mCursor;
+            nCurrentIterations++;
+            mCursor++;
+            mBest = mP.best[(size_t)h];
+            if (mP.returns[(size_t)h]) {
+                nInliers = mP.inliers[(size_t)h];
+                const uint64_t* m = &mP.mask[(size_t)h * (size_t)mP.words];
+                for (int i = 0; i < mP.n(); i++)
+                    if ((m[i >> 6] >> (i & 63)) & 1) vbInliers[mvnIndices1[(size_t)i]] = true;
+                return drfe::drfe_detail_sim3::mat32(4, 4, T44(h).data());
+            }
+        }
+        if (mCursor >= mP.hypotheses) bNoMore = true;
+        return drfe_cv::Mat();
+    }
+    drfe_cv::Mat GetEstimatedRotation() const { return mBest < 0 ? drfe_cv::Mat() : drfe::drfe_detail_sim3::mat32(3, 3, &mP.R12[9 * (size_t)mBest]); }
+    drfe_cv::Mat GetEstimatedTranslation() const { return mBest < 0 ? drfe_cv::Mat() : drfe::drfe_detail_sim3::mat32(3, 1, &mP.t12[3 * (size_t)mBest]); }
+    float GetEstimatedScale() const { return mBest < 0 ? 0.f : mP.s12[(size_t)mBest]; }
+    /* beyond the reference: the compacted correspondences, and the table itself */
+    const std::vector<size_t>& Indices1() const { return mvnIndices1; }
+    const drfe::drfe_detail_sim3::Problem& Table() { Fill(); return mP; }
+
+private:
+    friend class drfe::Sim3Batch;
+    void Fill()
+    {
+        if (mP.filled) return;
+        drfe::drfe_detail_sim3::fill_host({&mP});
+    }
+    std::vector<float> T44(int h) const
+    {
+        std::vector<float> T(16, 0.f);
+        std::memcpy(T.data(), &mP.T12[12 * (size_t)h], 12 * sizeof(float));
+        T[15] = 1.f;
+        return T;
+    }
+    drfe::drfe_detail_sim3::Problem mP;
+    std::vector<size_t> mvnIndices1;
+    int mN1, mCursor = 0, mBest = -1;
+};
+
+}  // namespace Planar_SLAM
+
+namespace drfe {
+
+/* The device batch: the tables of all solvers of one ComputeSim3 call (or of many) filled by one drfe_sim3_ransac_batch call; the
+ * solvers' iterate() / find() then only walk.  Owns its own drfe_ctx, as Triangulation. */
+class Sim3Batch {
+public:
+    explicit Sim3Batch(int device = 0) : mCtx(Planar_SLAM::drfe_detail::make_ctx(1, 1.2f, 1, 20, 7, 64, 64, 1, device)) {}
+    drfe_ctx* ctx() const { return mCtx.get(); }
+    template <class SolverT> void Fill(const std::vector<SolverT*>& solvers)
+    {
+        std::vector<drfe_detail_sim3::Problem*> ps;
+        for (SolverT* s : solvers)
+            if (s) ps.push_back(&s->mP);
+        drfe_ctx* c = mCtx.get();
+        std::lock_guard<std::mutex> lock(mMutex);
+        drfe_detail_sim3::fill(ps, [c](const drfe_sim3_problems* in, drfe_sim3_out* out) {
+            Planar_SLAM::drfe_detail::check(drfe_sim3_ransac_batch(c, in, out, nullptr), c, "drfe_sim3_ransac_batch");
         });
     }
 

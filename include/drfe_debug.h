@@ -44,6 +44,19 @@ int drfe_debug_manhattan_math(int which, const double* x, int n, double* out);
  * drfe_cosf(y[i]) (which 1) or the stereo parallax drfe_cosf(2 * drfe_atan2f(y[i] / 2, x[i])) (which 2).  Host code. */
 int drfe_debug_triangulate_math(int which, const float* y, const float* x, int n, float* out);
 
+/* Test hooks of the Sim3 solver.  _atan2: out[i] = dr_slam_amd/csrc/cr_atan2.h's correctly rounded atan2(y[i], x[i]), y >= 0;
+ * ok[i] = 0 where it was not certified.  _rand: the first n values of rand() after srand(seed), from
+ * dr_slam_amd/csrc/glibc_rand.h.  Host code. */
+int drfe_debug_sim3_atan2(const double* y, const double* x, int n, double* out, int32_t* ok);
+int drfe_debug_sim3_rand(uint32_t seed, int n, int32_t* out);
+/* _horn: sim3_core.h's ComputeSim3 on n samples (P1, P2: 3x3 row-major, one point per column), out = 37 floats per sample (R12 9,
+ * t12 3, s12, T12 12, T21 12); libm != 0 takes atan2, sin and cos from the host's libm, the way a hypothesis that was not
+ * certified is finished; ok[i] = 0 where the core refused.  Host code.
+ * _hand_back: every > 0 makes drfe_sim3_ransac_batch treat every `every`-th hypothesis of a call as not certified by the device,
+ * so that the host finishes it (0 = off): the table must not change. */
+int drfe_debug_sim3_horn(const float* P1, const float* P2, int n, int fix_scale, int libm, float* out, int32_t* ok);
+int drfe_debug_sim3_hand_back(drfe_ctx* ctx, int every);
+
 #ifdef __cplusplus
 }
 #endif
