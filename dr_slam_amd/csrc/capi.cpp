@@ -5,6 +5,7 @@
 #include "map_upkeep_internal.h"
 #include "triangulate_internal.h"
 #include "sim3_internal.h"
+#include "pnp_internal.h"
 #include <atomic>
 #include "post_internal.h"
 #include "match_internal.h"
@@ -152,6 +153,7 @@ void drfe_destroy(drfe_ctx* c)
     drfe_map_upkeep_free(c);
     drfe_triangulate_free(c);
     drfe_sim3_free(c);
+    drfe_pnp_free(c);
     drfe_post_free(c);
     drfe_one_shot_free(c);
     drfe_frame_lanes_free(c);

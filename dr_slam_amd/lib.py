@@ -52,6 +52,7 @@ SYMBOLS = (
     "drfe_triangulate_stats", "drfe_debug_triangulate_math",
     "drfe_sim3_ransac_host", "drfe_sim3_ransac_batch", "drfe_sim3_stats", "drfe_debug_sim3_atan2", "drfe_debug_sim3_rand",
     "drfe_debug_sim3_horn", "drfe_debug_sim3_hand_back",
+    "drfe_pnp_ransac_host", "drfe_pnp_ransac_batch", "drfe_pnp_stats", "drfe_debug_pnp_svd", "drfe_debug_pnp_inliers", "drfe_debug_pnp_inliers_device",
 )
 
 FRUSTUM_POINT_DTYPE = np.dtype([("world", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"),
@@ -167,6 +168,20 @@ class Sim3Problems(C.Structure):
                 ("Xw2", C.c_void_p), ("sigma2_1", C.c_void_p), ("sigma2_2", C.c_void_p)]    # drfe_sim3_problems
 
 
+class PnpProblems(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "K", "probability", "min_inliers", "max_iterations", "epsilon", "th2", "tail", "seed", "offsets", "p2d", "Xw",
+        "sigma2")]                                                                   # drfe_pnp_problems
+
+
+PNP_OUT_FIELDS = ("iterations", "min_inliers", "hypotheses", "refines", "sample", "R", "t", "inliers", "mask", "best", "returns",
+                  "refined_R", "refined_t", "refined_inliers", "refined_mask")
+
+
+class PnpOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in PNP_OUT_FIELDS]                             # drfe_pnp_out
+
+
 class Sim3Out(C.Structure):
     _fields_ = [("iterations", C.c_void_p), ("hypotheses", C.c_void_p), ("sample", C.c_void_p), ("R12", C.c_void_p),
                 ("t12", C.c_void_p), ("s12", C.c_void_p), ("T12", C.c_void_p), ("inliers", C.c_void_p), ("returns", C.c_void_p),
@@ -175,6 +190,7 @@ class Sim3Out(C.Structure):
 
 SIM3_MAX_CORR, SIM3_MAX_ITERATIONS = 4096, 300
 SIM3_STATS = ("calls", "solvers", "hypotheses", "correspondences", "solvers_lds", "solvers_global", "uncertified", "solvers_empty")
+PNP_STATS = ("calls", "solvers", "hypotheses", "correspondences", "refine_jobs", "refine_points", "solvers_global", "solvers_empty")
 
 
 class Camera(C.Structure):
@@ -333,6 +349,12 @@ def load() -> C.CDLL:
     L.drfe_debug_sim3_rand.argtypes = [C.c_uint32, i32, vp]
     L.drfe_debug_sim3_horn.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.drfe_debug_sim3_hand_back.argtypes = [vp, i32]
+    L.drfe_pnp_ransac_host.argtypes = [vp, vp]
+    L.drfe_pnp_ransac_batch.argtypes = [vp, vp, vp, vp]
+    L.drfe_pnp_stats.argtypes = [vp, vp]
+    L.drfe_debug_pnp_svd.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.drfe_debug_pnp_inliers.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp]
+    L.drfe_debug_pnp_inliers_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp]
     L.drfe_lsd_segments_host.argtypes = [vp, vp, vp, i32, i32, f64, vp, i32, C.POINTER(i32)]
     L.drfe_lsd_configure.argtypes = [vp, i32]
     L.drfe_lsd_configure_rect.argtypes = [vp, i32]
@@ -735,6 +757,95 @@ def sim3_table(result, s):
     t["mask"] = result["mask"][m0:m0 + n * w].reshape(n, w)
     t["iterations"] = int(result["iterations"][s])
     return t
+
+
+def _pnp_pack(problems):
+    """Packs a problem set (dict: K [n, 4] (fx, fy, cx, cy), probability [n], min_inliers [n], max_iterations [n], epsilon [n],
+    th2 [n], tail [n], seed [n], offsets [n + 1], p2d [M, 2], Xw [M, 3], sigma2 [M]) into drfe_pnp_problems and allocates the
+    table: (problems record, out record, the table as a dict, the arrays to keep alive).  The table: per solver iterations,
+    min_inliers, hypotheses, refines, row0, words, mask0; per row sample [4], R [9], t [3], inliers, best, returns, refined_R,
+    refined_t, refined_inliers; mask and refined_mask (uint64 words).  Solver s's rows are row0[s] + h, its mask words
+    mask0[s] + h * words[s] + (i // 64) (pnp_table slices them)."""
+    keep = []
+
+    def arr(key, dt, shape=-1):
+        v = np.ascontiguousarray(np.asarray(problems[key], dt).reshape(shape))
+        keep.append(v)
+        return v
+    off = arr("offsets", np.int32)
+    n = len(off) - 1
+    maxit, tail = arr("max_iterations", np.int32), arr("tail", np.int32)
+    P = PnpProblems(n, 0, _p(arr("K", np.float32, (-1, 4))), _p(arr("probability", np.float64)), _p(arr("min_inliers", np.int32)),
+                    _p(maxit), _p(arr("epsilon", np.float32)), _p(arr("th2", np.float32)), _p(tail), _p(arr("seed", np.uint32)),
+                    _p(off), _p(arr("p2d", np.float32, (-1, 2))), _p(arr("Xw", np.float32, (-1, 3))), _p(arr("sigma2", np.float32)))
+    cap = np.maximum(maxit.astype(np.int64), 1) + np.clip(tail.astype(np.int64), 0, None)
+    words = (np.clip(np.diff(off.astype(np.int64)), 0, None) + 63) // 64
+    row0 = np.concatenate([[0], np.cumsum(cap)])
+    mask0 = np.concatenate([[0], np.cumsum(cap * words)])
+    rows, W = int(row0[-1]), int(mask0[-1])
+    r = dict(iterations=np.zeros(n, np.int32), min_inliers=np.zeros(n, np.int32), hypotheses=np.zeros(n, np.int32),
+             refines=np.zeros(n, np.int32), row0=row0[:-1], words=words, mask0=mask0[:-1],
+             sample=np.zeros((rows, 4), np.int32), R=np.zeros((rows, 9), np.float64), t=np.zeros((rows, 3), np.float64),
+             inliers=np.zeros(rows, np.int32), mask=np.zeros(W, np.uint64), best=np.zeros(rows, np.int32),
+             returns=np.zeros(rows, np.uint8), refined_R=np.zeros((rows, 9), np.float64), refined_t=np.zeros((rows, 3), np.float64),
+             refined_inliers=np.zeros(rows, np.int32), refined_mask=np.zeros(W, np.uint64))
+    out = PnpOut(*[_p(r[k]) for k in PNP_OUT_FIELDS])
+    return P, out, r, keep
+
+
+def _pnp_call(fn, head, problems):
+    """fn(*head, problems, out) over _pnp_pack's records: (return code, table)"""
+    P, out, r, _keep = _pnp_pack(problems)
+    rc = fn(*head, C.byref(P), C.byref(out), *([None] if head else []))
+    return rc, r
+
+
+def pnp_ransac_host(problems):
+    """PnPsolver's whole table of every solver on the host (drfe_pnp_ransac_host); problems and result as
+    _pnp_pack"""
+    rc, r = _pnp_call(load().drfe_pnp_ransac_host, (), problems)
+    if rc != 0:
+        raise DrfeError(f"drfe_pnp_ransac_host failed ({rc})")
+    return r
+
+
+def pnp_table(result, s):
+    """Solver s's filled rows of a pnp_ransac_* result: dict(iterations, min_inliers, refines, sample, R, t, inliers, best,
+    returns, refined_R, refined_t, refined_inliers, mask [rows, words], refined_mask [rows, words])"""
+    a, n, w = int(result["row0"][s]), int(result["hypotheses"][s]), int(result["words"][s])
+    t = {k: result[k][a:a + n] for k in ("sample", "R", "t", "inliers", "best", "returns", "refined_R", "refined_t",
+                                         "refined_inliers")}
+    m0 = int(result["mask0"][s])
+    for k in ("mask", "refined_mask"):
+        t[k] = result[k][m0:m0 + n * w].reshape(n, w)
+    for k in ("iterations", "min_inliers", "refines"):
+        t[k] = int(result[k][s])
+    return t
+
+
+def pnp_svd(A):
+    """pnp_core.h's double Jacobi SVD of a row-major m x n matrix (n <= m <= 12): (w [n], ut [n, m], vt [n, n])"""
+    A = np.ascontiguousarray(A, np.float64)
+    m, n = A.shape
+    w, ut, vt = np.zeros(n), np.zeros((n, m)), np.zeros((n, n))
+    if load().drfe_debug_pnp_svd(_p(A), m, n, _p(w), _p(ut), _p(vt)) != 0:
+        raise DrfeError("drfe_debug_pnp_svd failed")
+    return w, ut, vt
+
+
+def pnp_inliers(R, t, K, p2d, Xw, max_err, ctx=None):
+    """pnp_core.h's CheckInliers under the double pose R [9], t [3]: bool [n]; with a Context through the device's sweep"""
+    R, t = np.ascontiguousarray(R, np.float64).reshape(9), np.ascontiguousarray(t, np.float64).reshape(3)
+    K = np.ascontiguousarray(K, np.float32).reshape(4)
+    p2d, Xw = np.ascontiguousarray(p2d, np.float32).reshape(-1, 2), np.ascontiguousarray(Xw, np.float32).reshape(-1, 3)
+    me = np.ascontiguousarray(max_err, np.float32)
+    out = np.zeros(len(me), np.uint8)
+    if ctx is not None:
+        ctx._chk(ctx.L.drfe_debug_pnp_inliers_device(ctx.h, _p(R), _p(t), _p(K), _p(p2d), _p(Xw), _p(me), len(me), _p(out)),
+                 "drfe_debug_pnp_inliers_device")
+    elif load().drfe_debug_pnp_inliers(_p(R), _p(t), _p(K), _p(p2d), _p(Xw), _p(me), len(me), _p(out)) != 0:
+        raise DrfeError("drfe_debug_pnp_inliers failed")
+    return out.astype(bool)
 
 
 def sim3_atan2(y, x):
@@ -1880,6 +1991,19 @@ class Context:
         rc, r = _sim3_call(self.L.drfe_sim3_ransac_batch, (self.h,), problems)
         self._chk(rc, "drfe_sim3_ransac_batch")
         return r
+
+    def pnp_ransac_batch(self, problems):
+        """pnp_ransac_host on the device (drfe_pnp_ransac_batch): same table, same bits"""
+        rc, r = _pnp_call(self.L.drfe_pnp_ransac_batch, (self.h,), problems)
+        self._chk(rc, "drfe_pnp_ransac_batch")
+        return r
+
+    def pnp_stats(self):
+        """dict(calls, solvers, hypotheses, correspondences, refine_jobs, refine_points, solvers_global, solvers_empty) since the
+        context was created; solvers - solvers_empty - solvers_global were counted from LDS"""
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_pnp_stats(self.h, _p(st)), "drfe_pnp_stats")
+        return dict(zip(PNP_STATS, st.tolist()))
 
     def sim3_hand_back(self, every):
         """test hook: the host finishes every `every`-th hypothesis of a batch call as if the device had not certified it"""

@@ -1143,6 +1143,74 @@ int drfe_sim3_ransac_batch(drfe_ctx* ctx, const drfe_sim3_problems* problems, dr
  * could not certify (atan2, sin / cos) and the host finished, [7] solvers without a hypothesis. */
 int drfe_sim3_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
 
+/* PnPsolver (src/PnPsolver.cc), the RANSAC between SearchByBoW(KF, F) and the relocalisation SearchByProjection in
+ * Tracking::Relocalization (src/Tracking.cc:3540-3700): every row of every solver of a call at once.  DESIGN.md section 17.
+ *
+ * A solver is a frame's intrinsics and its compacted correspondences (those the constructor keeps, in match order; isBad and
+ * mvKeyPointIndices stay with the caller).  Row h of a solver is what iteration h of iterate() computes from draws 4h .. 4h + 3 of
+ * the solver's own glibc rand() stream, srand(seed) (the deviation of section 16: the reference's stream is process-wide).
+ * iterate's loop is `while (mnIterations < mRansacMaxIts || nCurrentIterations < nIterations)`, so a call that starts at or above
+ * mRansacMaxIts still runs nIterations rows: a solver's table has iterations + tail rows, tail the caller's.  best[h] is the row
+ * that holds mBest* after row h (-1: none), Refine() runs over the inliers of every distinct best row and its result is stored
+ * at that row; returns[h] says iterate hands the refined pose of best[h] back at row h.  minSet is 4.
+ * Caps: DRFE_PNP_MAX_CORR correspondences per solver, DRFE_PNP_MAX_ITERATIONS for max_iterations, DRFE_PNP_MAX_TAIL for tail,
+ * 65 535 solvers, DRFE_PNP_MAX_ROWS rows and DRFE_PNP_MAX_MASK_WORDS mask words per call; above them the call is refused
+ * (DRFE_ERR_INVALID), as are decreasing offsets, min_inliers < 0, tail < 0
+ * and a sigma2 * th2 that is not finite. */
+enum { DRFE_PNP_MAX_CORR = 4096, DRFE_PNP_MAX_ITERATIONS = 300, DRFE_PNP_MAX_TAIL = 300 };
+/* per call, over all its solvers: rows of the caller's table (the sum of cap(s)) and words of one of its two masks (128 MiB) */
+enum { DRFE_PNP_MAX_ROWS = 1048576, DRFE_PNP_MAX_MASK_WORDS = 16777216 };
+/* solvers in a call from which drfe::PnPBatch uses the device entry (the measured crossover) */
+enum { DRFE_PNP_DEVICE_FROM = 4 };
+typedef struct drfe_pnp_problems {
+    int32_t n;                   /* solvers */
+    int32_t pad;
+    const float* K;              /* n x 4: fx, fy, cx, cy of the frame (widened to the double fu, fv, uc, vc) */
+    const double* probability;   /* n: SetRansacParameters' arguments */
+    const int32_t* min_inliers;  /* n */
+    const int32_t* max_iterations; /* n: <= DRFE_PNP_MAX_ITERATIONS; below 1 counts as 1, as the reference clamps */
+    const float* epsilon;        /* n */
+    const float* th2;            /* n */
+    const int32_t* tail;         /* n: rows past mRansacMaxIts, 0 .. DRFE_PNP_MAX_TAIL */
+    const uint32_t* seed;        /* n */
+    const int32_t* offsets;      /* n + 1: solver s's correspondences are [offsets[s], offsets[s + 1]); [0] == 0 */
+    const float* p2d;            /* 2 per correspondence: F.mvKeysUn[i].pt */
+    const float* Xw;             /* 3 per correspondence: pMP->GetWorldPos() */
+    const float* sigma2;         /* per correspondence: F.mvLevelSigma2[kp.octave] */
+} drfe_pnp_problems;
+/* Every pointer is required.  Solver s owns the rows [row0(s), row0(s) + cap(s)), cap(s) = max(1, max_iterations[s]) + tail[s],
+ * row0 the prefix sum of cap; its masks (and refined masks) start at word mask0(s), the prefix sum of cap(s) * words(s),
+ * words(s) = ceil(N(s) / 64), row h at mask0(s) + h * words(s), correspondence i in bit i % 64 of word i / 64.  Rows from
+ * hypotheses[s] on are zero, as are the refined_* fields of a row that is no row's best.  Every NaN of R, t, refined_R and
+ * refined_t is the quiet NaN 0x7FF8000000000000. */
+typedef struct drfe_pnp_out {
+    int32_t* iterations;         /* n: mRansacMaxIts after SetRansacParameters' clamp */
+    int32_t* min_inliers;        /* n: mRansacMinInliers after SetRansacParameters' adjustment */
+    int32_t* hypotheses;         /* n: rows filled: iterations[s] + tail[s], or 0 when N < min_inliers (iterate returns at once
+                                    with bNoMore) */
+    int32_t* refines;            /* n: rows Refine ran over */
+    int32_t* sample;             /* rows x 4: the sampled correspondences in draw order */
+    double* R;                   /* rows x 9: mRi */
+    double* t;                   /* rows x 3: mti */
+    int32_t* inliers;            /* rows: mnInliersi */
+    uint64_t* mask;              /* mvbInliersi */
+    int32_t* best;               /* rows: the row that holds mBest* after this one, -1 before the first */
+    uint8_t* returns;            /* rows: 1 = iterate hands the refined pose of best back at this row */
+    double* refined_R;           /* rows x 9: mRi after Refine over the inliers of this row */
+    double* refined_t;           /* rows x 3 */
+    int32_t* refined_inliers;    /* rows: mnRefinedInliers */
+    uint64_t* refined_mask;      /* mvbRefinedInliers, laid out as mask */
+} drfe_pnp_out;
+/* On the host, no context. */
+int drfe_pnp_ransac_host(const drfe_pnp_problems* problems, drfe_pnp_out* out);
+/* The same on the device: the inputs staged with one copy, six launches, the table back with one copy; returns with the outputs
+ * written (`stream` NULL = the context's).  Same bits as the host entry. */
+int drfe_pnp_ransac_batch(drfe_ctx* ctx, const drfe_pnp_problems* problems, drfe_pnp_out* out, void* stream);
+/* Counters since the context was created: stats[0] batch calls, [1] solvers, [2] rows, [3] correspondences, [4] refine jobs,
+ * [5] correspondences the refine jobs ran over, [6] solvers whose correspondences the counting kernel read from global memory
+ * (the others with rows were kept in LDS), [7] solvers without a row. */
+int drfe_pnp_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

@@ -16,6 +16,8 @@
  *                                      normal upkeep of map points and lines (host entries; MapUpkeep: the device batch)
  *   drfe::TriangulateNewMapPoints / TriangulateNewMapLines / Triangulation  src/LocalMapping.cc:383-538, 875-1026 - the
  *                                      per-match triangulation of CreateNewMapPoints / CreateNewMapLines2 (Triangulation: device)
+ *   Planar_SLAM::PnPsolver / drfe::PnPBatch  include/PnPsolver.h - relocalisation's EPnP RANSAC as a walk over a finished
+ *                                      table with Refine's results (host entry; PnPBatch: every solver of a call at once)
  *   Planar_SLAM::Sim3Solver / drfe::Sim3Batch  include/Sim3Solver.h:35-130 - the loop closer's Sim3 RANSAC as a walk over a
  *                                      finished hypothesis table (host entry; Sim3Batch: every solver of a call on the device)
  * With -DDRFE_WITH_OPENCV the container types are OpenCV's (cv::Mat, cv::KeyPoint, cv::line_descriptor::KeyLine);
@@ -2347,6 +2349,246 @@ public:
 
 private:
     Planar_SLAM::drfe_detail::CtxPtr mCtx;
+    std::mutex mMutex;
+};
+
+}  // namespace drfe
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * PnPsolver (include/PnPsolver.h, src/PnPsolver.cc) over drfe_pnp_ransac_host / drfe_pnp_ransac_batch: the first iterate() or
+ * find() fills the solver's whole table, every call after that walks it with the reference's cursor, its `||` loop condition,
+ * bNoMore and vbInliers[mvKeyPointIndices[i]] semantics.  A table has iterations + tail rows (tail: SetTail, default 5, what
+ * Relocalization's iterate(5, ..) can read past mRansacMaxIts in one call); a walk that runs off them refills the table on the
+ * host with a larger tail - the seed fixes every row, so the rows already walked do not change.  drfe::PnPBatch fills the tables
+ * of many solvers with one call.  The reference draws from the process-wide rand(); a solver here owns its stream (SetSeed,
+ * default 0).  DESIGN.md section 17. */
+namespace drfe {
+class PnPBatch;
+namespace drfe_detail_pnp {
+/* one solver's inputs and, once filled, its table */
+struct Problem {
+    float K[4];
+    double probability = 0.99;
+    int32_t minInliers = 8, maxIterations = 300, tail = 5;
+    float epsilon = 0.4f, th2 = 5.991f;
+    uint32_t seed = 0;
+    std::vector<float> p2d, Xw, sig;
+    bool filled = false;
+    int32_t iterations = 0, minInliersAdj = 0, hypotheses = 0, refines = 0, words = 0;
+    std::vector<int32_t> sample, inliers, best, refInliers;
+    std::vector<double> R, t, refR, refT;
+    std::vector<uint8_t> returns;
+    std::vector<uint64_t> mask, refMask;
+    int n() const { return (int)sig.size(); }
+};
+/* fills the tables of `ps` through fn(const drfe_pnp_problems*, drfe_pnp_out*) */
+template <class Fn> inline void fill(const std::vector<Problem*>& ps, Fn fn)
+{
+    const size_t n = ps.size();
+    std::vector<float> K, eps, th2, p2d, Xw, sig;
+    std::vector<double> prob;
+    std::vector<int32_t> minI, maxI, tail, off{0};
+    std::vector<uint32_t> seed;
+    std::vector<size_t> row0, mask0;
+    size_t rows = 0, words = 0;
+    for (Problem* p : ps) {
+        K.insert(K.end(), p->K, p->K + 4);
+        prob.push_back(p->probability); minI.push_back(p->minInliers); maxI.push_back(p->maxIterations); tail.push_back(p->tail);
+        eps.push_back(p->epsilon); th2.push_back(p->th2); seed.push_back(p->seed);
+        p2d.insert(p2d.end(), p->p2d.begin(), p->p2d.end()); Xw.insert(Xw.end(), p->Xw.begin(), p->Xw.end());
+        sig.insert(sig.end(), p->sig.begin(), p->sig.end());
+        off.push_back((int32_t)sig.size());
+        const size_t cap = (size_t)(p->maxIterations > 1 ? p->maxIterations : 1) + (size_t)(p->tail > 0 ? p->tail : 0);
+        p->words = (p->n() + 63) / 64;
+        row0.push_back(rows); mask0.push_back(words);
+        rows += cap; words += cap * (size_t)p->words;
+    }
+    const drfe_pnp_problems in{(int32_t)n, 0, K.data(), prob.data(), minI.data(), maxI.data(), eps.data(), th2.data(), tail.data(),
+                               seed.data(), off.data(), p2d.data(), Xw.data(), sig.data()};
+    std::vector<int32_t> its(n + 1), mins(n + 1), hyp(n + 1), refs(n + 1), sample(4 * rows + 1), inl(rows + 1), best(rows + 1),
+        rinl(rows + 1);
+    std::vector<double> R(9 * rows + 1), t(3 * rows + 1), rR(9 * rows + 1), rt(3 * rows + 1);
+    std::vector<uint8_t> ret(rows + 1);
+    std::vector<uint64_t> mask(words + 1), rmask(words + 1);
+    drfe_pnp_out out{its.data(), mins.data(), hyp.data(), refs.data(), sample.data(), R.data(), t.data(), inl.data(), mask.data(),
+                     best.data(), ret.data(), rR.data(), rt.data(), rinl.data(), rmask.data()};
+    fn(&in, &out);
+    for (size_t q = 0; q < n; q++) {
+        Problem* p = ps[q];
+        const size_t h = (size_t)hyp[q], a = row0[q], mw = h * (size_t)p->words;
+        p->iterations = its[q]; p->minInliersAdj = mins[q]; p->hypotheses = hyp[q]; p->refines = refs[q];
+        p->sample.assign(sample.begin() + 4 * a, sample.begin() + 4 * (a + h));
+        p->R.assign(R.begin() + 9 * a, R.begin() + 9 * (a + h));
+        p->t.assign(t.begin() + 3 * a, t.begin() + 3 * (a + h));
+        p->refR.assign(rR.begin() + 9 * a, rR.begin() + 9 * (a + h));
+        p->refT.assign(rt.begin() + 3 * a, rt.begin() + 3 * (a + h));
+        p->inliers.assign(inl.begin() + a, inl.begin() + a + h);
+        p->refInliers.assign(rinl.begin() + a, rinl.begin() + a + h);
+        p->best.assign(best.begin() + a, best.begin() + a + h);
+        p->returns.assign(ret.begin() + a, ret.begin() + a + h);
+        p->mask.assign(mask.begin() + mask0[q], mask.begin() + mask0[q] + mw);
+        p->refMask.assign(rmask.begin() + mask0[q], rmask.begin() + mask0[q] + mw);
+        p->filled = true;
+    }
+}
+inline void fill_host(const std::vector<Problem*>& ps)
+{
+    fill(ps, [](const drfe_pnp_problems* in, drfe_pnp_out* out) {
+        if (drfe_pnp_ransac_host(in, out) != DRFE_OK) throw std::runtime_error("drfe_pnp_ransac_host failed");
+    });
+}
+}  // namespace drfe_detail_pnp
+}  // namespace drfe
+
+namespace Planar_SLAM {
+
+template <class FrameT, class MapPointT>
+class PnPsolver {
+public:
+    /* :67-110.  The map-graph part (isBad, mvKeyPointIndices) runs here, the arithmetic in the entries. */
+    PnPsolver(const FrameT& F, const std::vector<MapPointT*>& vpMapPointMatches) : mNMatches(vpMapPointMatches.size())
+    {
+        for (size_t i = 0, iend = vpMapPointMatches.size(); i < iend; i++) {
+            MapPointT* pMP = vpMapPointMatches[i];
+            if (!pMP || pMP->isBad()) continue;
+            const auto& kp = F.mvKeysUn[i];
+            mP.p2d.push_back(kp.pt.x);
+            mP.p2d.push_back(kp.pt.y);
+            mP.sig.push_back(F.mvLevelSigma2[kp.octave]);
+            const auto Pos = pMP->GetWorldPos();
+            for (int q = 0; q < 3; q++) mP.Xw.push_back(Pos.template ptr<float>(q)[0]);
+            mvKeyPointIndices.push_back(i);
+        }
+        const float k[4] = {F.fx, F.fy, F.cx, F.cy};
+        std::memcpy(mP.K, k, sizeof(k));
+        SetRansacParameters();
+    }
+    /* the deviation: the stream this solver draws from (the reference shares the process's rand()) */
+    void SetSeed(uint32_t seed) { mP.seed = seed; Reset(); }
+    /* rows a table holds past mRansacMaxIts: what one iterate(nIterations, ..) of the caller can read there */
+    void SetTail(int tail) { mP.tail = tail; Reset(); }
+    void SetRansacParameters(double probability = 0.99, int minInliers = 8, int maxIterations = 300, int minSet = 4, float epsilon = 0.4,
+                             float th2 = 5.991)
+    {
+        if (minSet != 4) throw std::invalid_argument("PnPsolver: minSet is 4");     /* the reference's only caller and its default */
+        mP.probability = probability;
+        mP.minInliers = minInliers;
+        mP.maxIterations = maxIterations;
+        mP.epsilon = epsilon;
+        mP.th2 = th2;
+        Reset();
+    }
+    drfe_cv::Mat find(std::vector<bool>& vbInliers, int& nInliers)
+    {
+        bool bFlag;
+        Fill();
+        return iterate(mP.iterations, bFlag, vbInliers, nInliers);
+    }
+    /* :165-258 as a walk over the table */
+    drfe_cv::Mat iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers)
+    {
+        bNoMore = false;
+        vbInliers.clear();
+        nInliers = 0;
+        Fill();
+        if (mP.n() < mP.minInliersAdj) { bNoMore = true; return drfe_cv::Mat(); }
+        int nCurrentIterations = 0;
+        while (mCursor < mP.iterations || nCurrentIterations < nIterations) {
+            if (mCursor >= mP.hypotheses) Refill(nIterations - nCurrentIterations);
+            const size_t h = (size_t)mCursor;
+            nCurrentIterations++;
+            mCursor++;
+            if (mP.returns[h]) {
+                const size_t b = (size_t)mP.best[h];
+                nInliers = mP.refInliers[b];
+                Inliers(&mP.refMask[b * (size_t)mP.words], vbInliers);
+                return T44(&mP.refR[9 * b], &mP.refT[3 * b]);
+            }
+        }
+        if (mCursor >= mP.iterations) {
+            bNoMore = true;
+            const int b = mCursor > 0 ? mP.best[(size_t)mCursor - 1] : -1;
+            if (b >= 0) {
+                nInliers = mP.inliers[(size_t)b];
+                Inliers(&mP.mask[(size_t)b * (size_t)mP.words], vbInliers);
+                return T44(&mP.R[9 * (size_t)b], &mP.t[3 * (size_t)b]);
+            }
+        }
+        return drfe_cv::Mat();
+    }
+    /* beyond the reference: the compacted correspondences, the table itself, and how many times a walk ran off it */
+    const std::vector<size_t>& KeyPointIndices() const { return mvKeyPointIndices; }
+    const drfe::drfe_detail_pnp::Problem& Table() { Fill(); return mP; }
+    int Refills() const { return mRefills; }
+
+private:
+    friend class drfe::PnPBatch;
+    void Reset() { mP.filled = false; mCursor = 0; }
+    void Fill()
+    {
+        if (mP.filled) return;
+        drfe::drfe_detail_pnp::fill_host({&mP});
+    }
+    void Refill(int need)
+    {
+        if (mP.tail >= DRFE_PNP_MAX_TAIL) throw std::runtime_error("PnPsolver: iterate() past DRFE_PNP_MAX_TAIL rows after mRansacMaxIts");
+        int tail = mP.tail * 2 > mP.tail + need ? mP.tail * 2 : mP.tail + need;
+        mP.tail = tail < DRFE_PNP_MAX_TAIL ? tail : DRFE_PNP_MAX_TAIL;
+        mP.filled = false;
+        mRefills++;
+        Fill();
+    }
+    void Inliers(const uint64_t* m, std::vector<bool>& vbInliers) const
+    {
+        vbInliers = std::vector<bool>(mNMatches, false);
+        for (int i = 0; i < mP.n(); i++)
+            if ((m[i >> 6] >> (i & 63)) & 1) vbInliers[mvKeyPointIndices[(size_t)i]] = true;
+    }
+    /* Rcw.convertTo(CV_32F), tcw.convertTo(CV_32F) into cv::Mat::eye(4, 4, CV_32F) */
+    static drfe_cv::Mat T44(const double* R, const double* t)
+    {
+        float T[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1};
+        for (int r = 0; r < 3; r++) {
+            for (int q = 0; q < 3; q++) T[r * 4 + q] = (float)R[r * 3 + q];
+            T[r * 4 + 3] = (float)t[r];
+        }
+        return drfe::drfe_detail_sim3::mat32(4, 4, T);
+    }
+    drfe::drfe_detail_pnp::Problem mP;
+    std::vector<size_t> mvKeyPointIndices;
+    size_t mNMatches;
+    int mCursor = 0, mRefills = 0;
+};
+
+}  // namespace Planar_SLAM
+
+namespace drfe {
+
+/* The batch: the tables of all solvers of one Relocalization call (or of many) filled by one call; the solvers' iterate() /
+ * find() then only walk.  A call of fewer than `deviceFrom` solvers goes to the host entry (same bits): below the crossover
+ * measured in DESIGN.md section 17 the device's fixed cost per call is larger than the host's whole work.  Owns its own
+ * drfe_ctx, as Sim3Batch. */
+class PnPBatch {
+public:
+    explicit PnPBatch(int device = 0, int deviceFrom = DRFE_PNP_DEVICE_FROM)
+        : mCtx(Planar_SLAM::drfe_detail::make_ctx(1, 1.2f, 1, 20, 7, 64, 64, 1, device)), mDeviceFrom(deviceFrom) {}
+    drfe_ctx* ctx() const { return mCtx.get(); }
+    template <class SolverT> void Fill(const std::vector<SolverT*>& solvers)
+    {
+        std::vector<drfe_detail_pnp::Problem*> ps;
+        for (SolverT* s : solvers)
+            if (s) ps.push_back(&s->mP);
+        if ((int)ps.size() < mDeviceFrom) { drfe_detail_pnp::fill_host(ps); return; }
+        drfe_ctx* c = mCtx.get();
+        std::lock_guard<std::mutex> lock(mMutex);
+        drfe_detail_pnp::fill(ps, [c](const drfe_pnp_problems* in, drfe_pnp_out* out) {
+            Planar_SLAM::drfe_detail::check(drfe_pnp_ransac_batch(c, in, out, nullptr), c, "drfe_pnp_ransac_batch");
+        });
+    }
+
+private:
+    Planar_SLAM::drfe_detail::CtxPtr mCtx;
+    int mDeviceFrom;
     std::mutex mMutex;
 };
 

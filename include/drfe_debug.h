@@ -56,6 +56,17 @@ int drfe_debug_sim3_rand(uint32_t seed, int n, int32_t* out);
  * so that the host finishes it (0 = off): the table must not change. */
 int drfe_debug_sim3_horn(const float* P1, const float* P2, int n, int fix_scale, int libm, float* out, int32_t* ok);
 int drfe_debug_sim3_hand_back(drfe_ctx* ctx, int every);
+/* Test hooks of the PnP solver (test-only, like everything in this header: no integration calls them).
+ * pnp_core.h's double Jacobi SVD of a row-major m x n matrix (n <= m <= 12) on the host: w [n], the left singular vectors as
+ * rows ut [n x m], the right ones as rows vt [n x n].  For tests. */
+int drfe_debug_pnp_svd(const double* A, int m, int n, double* w, double* ut, double* vt);
+/* pnp_core.h's CheckInliers under the pose R [9], t [3] (double) and K = fx, fy, cx, cy over n correspondences: out[i] = 1 for an
+ * inlier.  Host code. */
+int drfe_debug_pnp_inliers(const double* R, const double* t, const float* K, const float* p2d, const float* Xw, const float* max_err,
+                           int n, uint8_t* out);
+/* The same through the device's inlier sweep (pnp_kernels.hip's pnp_sweep, one wavefront; n <= DRFE_PNP_MAX_CORR): same bytes. */
+int drfe_debug_pnp_inliers_device(drfe_ctx* ctx, const double* R, const double* t, const float* K, const float* p2d, const float* Xw,
+                                  const float* max_err, int n, uint8_t* out);
 
 #ifdef __cplusplus
 }
