@@ -1,24 +1,13 @@
 /* pnp.cpp — PnPsolver (reference src/PnPsolver.cc) behind the C-ABI of include/drfe.h: the host entry (no context), the batch
  * entry (pnp_kernels.hip) and its counters.  Both sides evaluate pnp_core.h; what is sequential and cheap — SetRansacParameters
- * (the host's libm, :121-157) and the sampling (a glibc rand() stream per solver, :188-201) — runs once, here, for both.
- * DESIGN.md section 17. */
+ * (the host's libm, :121-157) and the sampling (a glibc rand() stream per solver, :188-201) — runs once, on the host, for both.
+ * The table's scaffold (plan, sampling, scatter, common counters) is ransac_table.h, shared with sim3.cpp; here are the argument
+ * checks and caps, the adjusted mRansacMinInliers, the records and the rows on the host.  DESIGN.md section 17. */
 #include "pnp_internal.h"
-#include "glibc_rand.h"
-#include "hip_buf.h"
 #include "stage_layout.h"
 #include "../../include/drfe_debug.h"
 
-#include <climits>
-#include <cmath>
-#include <cstring>
-#include <string>
-#include <vector>
-
-struct PnpBuffers {
-    StagePair io;                      /* staging: one copy each way */
-    DevBuf<char> scratch;              /* the refine jobs of every solver */
-    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-};
+struct PnpBuffers : RansacBuffers {};  /* scratch: the refine jobs of every solver */
 
 void drfe_pnp_free(drfe_ctx* c)
 {
@@ -30,19 +19,13 @@ namespace {
 
 enum { PNP_MAX_SOLVERS = 65535 };      /* the counting kernel's grid has one row per solver */
 
-/* where a solver's rows lie in the caller's table and in the compact one of a call */
-struct Plan {
-    std::vector<int32_t> iterations, minInliers, hyp, hyp0, words, row0;
-    std::vector<int64_t> mask0Out, mask0;  /* the caller's (cap rows), the compact one (hyp rows) */
-    std::vector<int32_t> sample;           /* 4 per row, compact */
+struct Plan : RansacPlan<4, DRFE_PNP_MAX_CORR> {
+    std::vector<int32_t> minInliers;       /* per solver, after SetRansacParameters */
     std::vector<PnpCorr> corr;             /* per correspondence of the call */
-    int nHyp = 0, maxHyp = 0, rows = 0;
-    int64_t maskWords = 0, maskWordsOut = 0;
 };
 
 /* SetRansacParameters (:121-152) with minSet = 4: the adjusted mRansacMinInliers and mRansacMaxIts.  float products and
- * quotients, the count in double through the host's libm, int conversions as cvttss2si / cvttsd2si (NaN and out-of-range give
- * INT_MIN) */
+ * quotients, the int conversion as cvttss2si (NaN and out-of-range give INT_MIN) */
 void ransac_parameters(int N, double probability, int minInliers, int maxIterations, float epsilon, int* minOut, int* itOut)
 {
     const float prod = (float)N * epsilon;
@@ -50,31 +33,8 @@ void ransac_parameters(int N, double probability, int minInliers, int maxIterati
     if (nMinInliers < minInliers) nMinInliers = minInliers;
     if (nMinInliers < 4) nMinInliers = 4;
     if (epsilon < (float)nMinInliers / N) epsilon = (float)nMinInliers / N;
-    int nIterations;
-    if (nMinInliers == N) nIterations = 1;
-    else {
-        const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3.0)));
-        nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : INT_MIN;
-    }
-    const int m = nIterations < maxIterations ? nIterations : maxIterations;
     *minOut = nMinInliers;
-    *itOut = m > 1 ? m : 1;
-}
-
-/* one iteration's sample (:188-201): four RandomInt draws from a list that shrinks by swap-with-back */
-void draw_sample(GlibcRand& rng, std::vector<int32_t>& avail, int N, int32_t out[4])
-{
-    /* vAvailableIndices = mvAllIndices: only the entries a previous iteration touched differ from the identity */
-    int size = N;
-    int touched[4];
-    for (int q = 0; q < 4; q++) {
-        const int randi = rng.random_int(0, size - 1);
-        out[q] = avail[(size_t)randi];
-        avail[(size_t)randi] = avail[(size_t)size - 1];
-        touched[q] = randi;
-        size--;
-    }
-    for (int q = 0; q < 4; q++) avail[(size_t)touched[q]] = touched[q];
+    *itOut = ransac_iteration_count(nMinInliers == N, epsilon, probability, maxIterations);
 }
 
 int cap_of(const drfe_pnp_problems* p, int s) { return (p->max_iterations[s] > 1 ? p->max_iterations[s] : 1) + p->tail[s]; }
@@ -87,15 +47,13 @@ int make_plan(const drfe_pnp_problems* p, const drfe_pnp_out* o, Plan& P, std::s
     const int n = p->n;
     if (n == 0) return DRFE_OK;
     if (!p->K || !p->probability || !p->min_inliers || !p->max_iterations || !p->epsilon || !p->th2 || !p->tail || !p->seed ||
-        !p->offsets || p->offsets[0] != 0)
+        !p->offsets)
         return DRFE_ERR_INVALID;
     if (!o->iterations || !o->min_inliers || !o->hypotheses || !o->refines || !o->sample || !o->R || !o->t || !o->inliers ||
         !o->mask || !o->best || !o->returns || !o->refined_R || !o->refined_t || !o->refined_inliers || !o->refined_mask)
         return DRFE_ERR_INVALID;
     for (int s = 0; s < n; s++) {
-        const int64_t N = (int64_t)p->offsets[s + 1] - p->offsets[s];
-        if (N < 0) { err = "pnp: decreasing offsets"; return DRFE_ERR_INVALID; }
-        if (N > DRFE_PNP_MAX_CORR) { err = "pnp: more than DRFE_PNP_MAX_CORR correspondences in a solver"; return DRFE_ERR_INVALID; }
+        if (!ransac_offsets_ok(p->offsets, s, DRFE_PNP_MAX_CORR, "pnp", "DRFE_PNP_MAX_CORR", err)) return DRFE_ERR_INVALID;
         if (p->max_iterations[s] > DRFE_PNP_MAX_ITERATIONS) { err = "pnp: max_iterations above DRFE_PNP_MAX_ITERATIONS"; return DRFE_ERR_INVALID; }
         if (p->tail[s] < 0 || p->tail[s] > DRFE_PNP_MAX_TAIL) { err = "pnp: tail outside [0, DRFE_PNP_MAX_TAIL]"; return DRFE_ERR_INVALID; }
         if (p->min_inliers[s] < 0) { err = "pnp: negative min_inliers"; return DRFE_ERR_INVALID; }
@@ -121,34 +79,12 @@ int make_plan(const drfe_pnp_problems* p, const drfe_pnp_out* o, Plan& P, std::s
             c.maxErr = p->sigma2[i] * p->th2[s];
             if (!std::isfinite(c.maxErr)) { err = "pnp: sigma2 * th2 is not finite"; return DRFE_ERR_INVALID; }
         }
-    P.iterations.resize((size_t)n); P.minInliers.resize((size_t)n); P.hyp.resize((size_t)n); P.hyp0.resize((size_t)n);
-    P.words.resize((size_t)n); P.row0.resize((size_t)n); P.mask0.resize((size_t)n); P.mask0Out.resize((size_t)n);
-    std::vector<int32_t> avail((size_t)DRFE_PNP_MAX_CORR);
-    for (int i = 0; i < DRFE_PNP_MAX_CORR; i++) avail[(size_t)i] = i;
     for (int s = 0; s < n; s++) {
         const int N = p->offsets[s + 1] - p->offsets[s];
         int it, mi;
         ransac_parameters(N, p->probability[s], p->min_inliers[s], p->max_iterations[s], p->epsilon[s], &mi, &it);
-        const int hyp = N < mi ? 0 : it + p->tail[s];
-        const int words = (N + 63) / 64;
-        P.iterations[(size_t)s] = it;
-        P.minInliers[(size_t)s] = mi;
-        P.hyp[(size_t)s] = hyp;
-        P.hyp0[(size_t)s] = P.nHyp;
-        P.words[(size_t)s] = words;
-        P.row0[(size_t)s] = P.rows;
-        P.mask0[(size_t)s] = P.maskWords;
-        P.mask0Out[(size_t)s] = P.maskWordsOut;
-        P.nHyp += hyp;
-        P.rows += cap_of(p, s);
-        P.maskWords += (int64_t)hyp * words;
-        P.maskWordsOut += (int64_t)cap_of(p, s) * words;
-        if (hyp > P.maxHyp) P.maxHyp = hyp;
-        if (hyp > 0) {
-            GlibcRand rng(p->seed[s]);
-            P.sample.resize(4 * (size_t)P.nHyp);
-            for (int h = 0; h < hyp; h++) draw_sample(rng, avail, N, &P.sample[4 * ((size_t)P.hyp0[(size_t)s] + h)]);
-        }
+        P.minInliers.push_back(mi);
+        P.add_solver(N, it, N < mi ? 0 : it + p->tail[s], cap_of(p, s), p->seed[s]);
     }
     return DRFE_OK;
 }
@@ -173,9 +109,7 @@ void begin_out(const drfe_pnp_problems* p, const Plan& P, drfe_pnp_out* o)
         o->min_inliers[s] = P.minInliers[(size_t)s];
         o->hypotheses[s] = P.hyp[(size_t)s];
         o->refines[s] = 0;
-        if (P.hyp[(size_t)s])
-            std::memcpy(o->sample + 4 * (size_t)P.row0[(size_t)s], &P.sample[4 * (size_t)P.hyp0[(size_t)s]],
-                        4 * (size_t)P.hyp[(size_t)s] * sizeof(int32_t));
+        P.scatter(s, o->sample, P.sample.data(), 4);
     }
 }
 
@@ -209,7 +143,7 @@ void host_solver(const drfe_pnp_problems* p, const Plan& P, int s, drfe_pnp_out*
     double K[4];
     solver_K(p, s, K);
     for (int h = 0; h < hyp; h++) {
-        const int32_t* smp = &P.sample[4 * ((size_t)P.hyp0[(size_t)s] + h)];
+        const int32_t* smp = P.sample_of(s, h);
         const PnpSel sel{corr, smp, nullptr, 4, 4, smp[0]};
         o->inliers[row0 + h] = host_pose_and_count(sel, N, K, o->R + 9 * (row0 + h), o->t + 3 * (row0 + h),
                                                    o->mask + P.mask0Out[(size_t)s] + (size_t)h * words, words);
@@ -253,16 +187,11 @@ int drfe_pnp_ransac_batch(drfe_ctx* c, const drfe_pnp_problems* p, drfe_pnp_out*
     if (rc) return rc;
     PnpBuffers* b = c->pnp;
     if (!b) { b = new PnpBuffers(); c->pnp = b; }
-    b->stats[0]++;
+    P.count_call(b->stats, p->offsets);
     if (p->n == 0) return DRFE_OK;
     const int n = p->n, M = p->offsets[n], H = P.nHyp;
-    b->stats[1] += n;
-    b->stats[2] += H;
-    b->stats[3] += M;
-    for (int s = 0; s < n; s++) {
-        if (!P.hyp[(size_t)s]) b->stats[7]++;
-        else if (p->offsets[s + 1] - p->offsets[s] > DRFE_PNP_LDS_CORR) b->stats[6]++;
-    }
+    for (int s = 0; s < n; s++)
+        if (P.hyp[(size_t)s] && p->offsets[s + 1] - p->offsets[s] > DRFE_PNP_LDS_CORR) b->stats[6]++;
     begin_out(p, P, o);
     if (H == 0) return DRFE_OK;
     const size_t nM = (size_t)M, nH = (size_t)H, nW = (size_t)P.maskWords;
@@ -282,19 +211,11 @@ int drfe_pnp_ransac_batch(drfe_ctx* c, const drfe_pnp_problems* p, drfe_pnp_out*
     HIPCHK(c, b->scratch.grow(scr.bytes()));
     char* h = b->io.hin;
     PnpSolverRec* sol = sSolver.at(h);
-    int32_t* hypSolver = sHypSolver.at(h);
     for (int s = 0; s < n; s++) {
-        PnpSolverRec& S = sol[s];
-        solver_K(p, s, S.K);
-        S.minInliers = P.minInliers[(size_t)s];
-        S.n = p->offsets[s + 1] - p->offsets[s];
-        S.corr0 = p->offsets[s];
-        S.hyp = P.hyp[(size_t)s];
-        S.hyp0 = P.hyp0[(size_t)s];
-        S.words = P.words[(size_t)s];
-        S.mask0 = P.mask0[(size_t)s];
-        for (int q = 0; q < S.hyp; q++) hypSolver[S.hyp0 + q] = s;
+        solver_K(p, s, sol[s].K);
+        sol[s].head = P.head(s, p->offsets, P.minInliers[(size_t)s]);
     }
+    P.fill_hyp_solver(sHypSolver.at(h));
     sCorr.put(h, P.corr.data());
     sSample.put(h, P.sample.data());
     const char* d = b->io.din;
@@ -313,25 +234,21 @@ int drfe_pnp_ransac_batch(drfe_ctx* c, const drfe_pnp_problems* p, drfe_pnp_out*
     L.inliers = sInl.at(dO); L.best = sBest.at(dO); L.refInliers = sRefInl.at(dO); L.nJobs = sJobsN.at(dO);
     L.returns = sRet.at(dO);
     L.mask = sMask.at(dO); L.refMask = sRefMask.at(dO);
-    hipError_t e = drfe_launch_pnp(L, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(b->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) { c->err = std::string("pnp batch: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
-    HIPCHK(c, hipStreamSynchronize(st));
+    if (const int e = ransac_finish(c, "pnp", drfe_launch_pnp(L, st), b->io, out.bytes(), st)) return e;
     const char* ho = b->io.hout;
     for (int s = 0; s < n; s++) {
-        const size_t hy = (size_t)P.hyp[(size_t)s], h0 = (size_t)P.hyp0[(size_t)s], r0 = (size_t)P.row0[(size_t)s];
+        const size_t hy = (size_t)P.hyp[(size_t)s], r0 = (size_t)P.row0[(size_t)s];
         if (!hy) continue;
-        const size_t mw = hy * (size_t)P.words[(size_t)s] * sizeof(uint64_t);
-        std::memcpy(o->R + 9 * r0, sR.at(ho) + 9 * h0, hy * 9 * sizeof(double));
-        std::memcpy(o->t + 3 * r0, sT.at(ho) + 3 * h0, hy * 3 * sizeof(double));
-        std::memcpy(o->refined_R + 9 * r0, sRefR.at(ho) + 9 * h0, hy * 9 * sizeof(double));
-        std::memcpy(o->refined_t + 3 * r0, sRefT.at(ho) + 3 * h0, hy * 3 * sizeof(double));
-        std::memcpy(o->inliers + r0, sInl.at(ho) + h0, hy * sizeof(int32_t));
-        std::memcpy(o->refined_inliers + r0, sRefInl.at(ho) + h0, hy * sizeof(int32_t));
-        std::memcpy(o->best + r0, sBest.at(ho) + h0, hy * sizeof(int32_t));
-        std::memcpy(o->returns + r0, sRet.at(ho) + h0, hy);
-        std::memcpy(o->mask + P.mask0Out[(size_t)s], sMask.at(ho) + P.mask0[(size_t)s], mw);
-        std::memcpy(o->refined_mask + P.mask0Out[(size_t)s], sRefMask.at(ho) + P.mask0[(size_t)s], mw);
+        P.scatter(s, o->R, sR.at(ho), 9);
+        P.scatter(s, o->t, sT.at(ho), 3);
+        P.scatter(s, o->refined_R, sRefR.at(ho), 9);
+        P.scatter(s, o->refined_t, sRefT.at(ho), 3);
+        P.scatter(s, o->inliers, sInl.at(ho));
+        P.scatter(s, o->refined_inliers, sRefInl.at(ho));
+        P.scatter(s, o->best, sBest.at(ho));
+        P.scatter(s, o->returns, sRet.at(ho));
+        P.scatter_mask(s, o->mask, sMask.at(ho));
+        P.scatter_mask(s, o->refined_mask, sRefMask.at(ho));
         o->refines[s] = sJobsN.at(ho)[s];
         b->stats[4] += o->refines[s];
         /* a refine job's points: the count of every row that became the best one */
@@ -347,8 +264,7 @@ int drfe_pnp_ransac_batch(drfe_ctx* c, const drfe_pnp_problems* p, drfe_pnp_out*
 int drfe_pnp_stats(drfe_ctx* c, int64_t* stats)
 {
     if (!c || !stats) return DRFE_ERR_INVALID;
-    if (c->pnp) std::memcpy(stats, c->pnp->stats, sizeof(c->pnp->stats));
-    else std::memset(stats, 0, 8 * sizeof(int64_t));
+    ransac_stats(c->pnp, stats);
     return DRFE_OK;
 }
 

@@ -3,22 +3,17 @@
 #define DRFE_PNP_INTERNAL_H
 
 #include "drfe_internal.h"
+#include "ransac_table.h"
 #include "pnp_core.h"
 
-/* correspondences of a solver the counting kernel keeps in LDS (24 bytes each: 48 KiB, which leaves a CU's 160 KiB room for
- * three such workgroups); above it reads them from global memory */
+/* the counting kernel's LDS bound and rows per workgroup (ransac_device.h); a PnpCorr is 24 bytes */
 #define DRFE_PNP_LDS_CORR 2048
-/* hypotheses per workgroup of the counting kernel (four wavefronts, eight each) */
 #define DRFE_PNP_CHUNK 32
 
 /* one solver on the device */
 struct PnpSolverRec {
     double K[4];                   /* fu, fv, uc, vc */
-    int32_t minInliers;            /* after SetRansacParameters */
-    int32_t n, corr0;              /* correspondences: count, first */
-    int32_t hyp, hyp0;             /* rows: count, first (compact over the call) */
-    int32_t words;                 /* mask words per row */
-    int64_t mask0;                 /* first mask word (compact over the call) */
+    RansacSolverHead head;         /* minInliers after SetRansacParameters */
 };
 
 struct PnpLaunch {

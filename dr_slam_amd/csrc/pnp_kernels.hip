@@ -3,8 +3,7 @@
  *   k_pnp_solve4   one lane per row: EPnP's compute_pose on its four sampled correspondences.  The 12x12 that the Jacobi SVD
  *                  rotates lives in LDS, element-major over the 64 lanes (72 KiB a workgroup, two workgroups a CU).
  *   k_pnp_count    workgroups over (solver, 32 rows), one wavefront per row at a time: CheckInliers over the correspondences 64
- *                  at a time, the ballot of the test is the mask word, its popcount adds to the count.  A solver of at most
- *                  DRFE_PNP_LDS_CORR correspondences is first copied into LDS; a larger one is read from global memory.
+ *                  at a time (ransac_device.h).
  *   k_pnp_best     one lane per solver: best[] over its counts in row order, and the rows Refine has to run over.
  *   k_pnp_jobs     one workgroup: the solvers' job counts summed by prefix into one compact job list of the call.
  *   k_pnp_refine   one wavefront per refine job (a bounded grid strides over the list): compute_pose over the inliers of the
@@ -17,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "pnp_internal.h"
+#include "ransac_device.h"
 
 #define PNP_THREADS 256
 /* workgroups of the refine launch: two fit a CU (72 KiB of LDS each), 256 CUs, four rounds' worth; they stride over the job list */
@@ -56,7 +56,7 @@ __global__ __launch_bounds__(64) void k_pnp_solve4(const PnpLaunch L)
     if (w >= L.nHyp) return;
     const PnpSolverRec& S = L.solver[L.hypSolver[w]];
     const int32_t* smp = L.sample + 4 * (size_t)w;
-    const PnpSel sel{L.corr + S.corr0, smp, nullptr, 4, 4, smp[0]};
+    const PnpSel sel{L.corr + S.head.corr0, smp, nullptr, 4, 4, smp[0]};
     double R[9], t[3];
     pnp_compute_pose(PnpSerial(), sel, S.K, PnpStrided{big + threadIdx.x, 64}, R, t);
     for (int k = 0; k < 9; k++) L.R[9 * (size_t)w + k] = pnp_canon(R[k]);
@@ -64,54 +64,31 @@ __global__ __launch_bounds__(64) void k_pnp_solve4(const PnpLaunch L)
 }
 
 /* CheckInliers of one row by one wavefront */
-__device__ void pnp_sweep(const PnpCorr* corr, int N, const double R[9], const double t[3], const double K[4], int lane,
-                          uint64_t* mask, int32_t* countOut)
+__device__ __forceinline__ void pnp_sweep(const PnpCorr* corr, int N, const double R[9], const double t[3], const double K[4],
+                                          int lane, uint64_t* mask, int32_t* countOut)
 {
-    int count = 0;
-    for (int base = 0; base < N; base += 64) {
-        const int i = base + lane;
-        const bool ok = i < N && pnp_inlier(corr[i < N ? i : 0], R, t, K);
-        const unsigned long long word = __ballot(ok);
-        count += __popcll(word);
-        if (lane == 0) mask[base >> 6] = word;
-    }
-    if (lane == 0) *countOut = count;
+    ransac_sweep(corr, N, lane, mask, countOut, [&](const PnpCorr& c) { return pnp_inlier(c, R, t, K); });
 }
 
 __global__ __launch_bounds__(PNP_THREADS) void k_pnp_count(const PnpLaunch L)
 {
     __shared__ PnpCorr lds[DRFE_PNP_LDS_CORR];
     const PnpSolverRec& S = L.solver[blockIdx.y];
-    const int h0 = blockIdx.x * DRFE_PNP_CHUNK;
-    if (h0 >= S.hyp) return;                         /* uniform over the workgroup */
-    const int N = S.n;
-    const PnpCorr* corr = L.corr + S.corr0;
-    if (N <= DRFE_PNP_LDS_CORR) {
-        /* 6 dwords per record: a straight dword copy */
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(corr);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(lds);
-        for (int k = threadIdx.x; k < N * 6; k += PNP_THREADS) dst[k] = src[k];
-        __syncthreads();
-        corr = lds;
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int perWave = DRFE_PNP_CHUNK / (PNP_THREADS / 64);
-    for (int j = 0; j < perWave; j++) {
-        const int h = h0 + wave * perWave + j;
-        if (h >= S.hyp) break;                       /* uniform over the wavefront */
-        const size_t w = (size_t)S.hyp0 + h;
+    const int lane = threadIdx.x & 63;
+    ransac_count_rows<DRFE_PNP_CHUNK, PNP_THREADS>(S.head, L.corr + S.head.corr0, lds,
+                                                    [&](const PnpCorr* corr, int N, int h, size_t w) {
         double R[9], t[3];
         for (int k = 0; k < 9; k++) R[k] = L.R[9 * w + k];
         for (int k = 0; k < 3; k++) t[k] = L.t[3 * w + k];
-        pnp_sweep(corr, N, R, t, S.K, lane, L.mask + S.mask0 + (size_t)h * S.words, L.inliers + w);
-    }
+        pnp_sweep(corr, N, R, t, S.K, lane, L.mask + S.head.mask0 + (size_t)h * S.head.words, L.inliers + w);
+    });
 }
 
 __global__ __launch_bounds__(64) void k_pnp_best(const PnpLaunch L)
 {
     const int s = blockIdx.x * 64 + threadIdx.x;
     if (s >= L.nSolvers) return;
-    const PnpSolverRec& S = L.solver[s];
+    const RansacSolverHead& S = L.solver[s].head;
     L.nJobs[s] = pnp_walk_best(L.inliers + S.hyp0, S.hyp, S.minInliers, L.best + S.hyp0, L.jobs + S.hyp0);
 }
 
@@ -134,7 +111,7 @@ __global__ __launch_bounds__(PNP_THREADS) void k_pnp_jobs(const PnpLaunch L)
     __syncthreads();
     int32_t at = base[threadIdx.x];
     for (int s = s0; s < s1; s++) {
-        const PnpSolverRec& S = L.solver[s];
+        const RansacSolverHead& S = L.solver[s].head;
         for (int j = 0; j < L.nJobs[s]; j++, at++) {
             L.jobSolver[at] = s;
             L.jobRow[at] = L.jobs[S.hyp0 + j];
@@ -149,20 +126,20 @@ __global__ __launch_bounds__(64) void k_pnp_refine(const PnpLaunch L)
     for (int job = blockIdx.x; job < total; job += gridDim.x) {     /* uniform over the workgroup, which is one wavefront */
         const PnpSolverRec& S = L.solver[L.jobSolver[job]];
         const int h = L.jobRow[job];
-        const size_t w = (size_t)S.hyp0 + h;
-        const uint64_t* rowMask = L.mask + S.mask0 + (size_t)h * S.words;
+        const size_t w = (size_t)S.head.hyp0 + h;
+        const uint64_t* rowMask = L.mask + S.head.mask0 + (size_t)h * S.head.words;
         int first = 0;
-        for (int q = 0; q < S.words; q++)
+        for (int q = 0; q < S.head.words; q++)
             if (rowMask[q]) { first = q * 64 + __ffsll((unsigned long long)rowMask[q]) - 1; break; }
-        const PnpCorr* corr = L.corr + S.corr0;
-        const PnpSel sel{corr, nullptr, rowMask, S.n, L.inliers[w], first};
+        const PnpCorr* corr = L.corr + S.head.corr0;
+        const PnpSel sel{corr, nullptr, rowMask, S.head.n, L.inliers[w], first};
         double R[9], t[3];
         pnp_compute_pose(PnpWave{lane}, sel, S.K, PnpStrided{big + lane, 64}, R, t);
         if (lane == 0) {
             for (int k = 0; k < 9; k++) L.refR[9 * w + k] = pnp_canon(R[k]);
             for (int k = 0; k < 3; k++) L.refT[3 * w + k] = pnp_canon(t[k]);
         }
-        pnp_sweep(corr, S.n, R, t, S.K, lane, L.refMask + S.mask0 + (size_t)h * S.words, L.refInliers + w);
+        pnp_sweep(corr, S.head.n, R, t, S.K, lane, L.refMask + S.head.mask0 + (size_t)h * S.head.words, L.refInliers + w);
     }
 }
 
@@ -170,7 +147,7 @@ __global__ __launch_bounds__(64) void k_pnp_returns(const PnpLaunch L)
 {
     const int s = blockIdx.x * 64 + threadIdx.x;
     if (s >= L.nSolvers) return;
-    const PnpSolverRec& S = L.solver[s];
+    const RansacSolverHead& S = L.solver[s].head;
     pnp_walk_returns(L.inliers + S.hyp0, L.best + S.hyp0, L.refInliers + S.hyp0, S.hyp, S.minInliers, L.returns + S.hyp0);
 }
 

@@ -1,23 +1,13 @@
 /* sim3.cpp — Sim3Solver (reference src/Sim3Solver.cc) behind the C-ABI of include/drfe.h: the host entry (no context), the batch
  * entry (sim3_kernels.hip) and its counters.  Both sides evaluate sim3_core.h; what is sequential and cheap — SetRansacParameters'
- * iteration count (the host's libm, :118-142) and the sampling (a glibc rand() stream per solver, :167-181) — runs once, here, for
- * both.  DESIGN.md section 16. */
+ * iteration count (the host's libm, :118-142) and the sampling (a glibc rand() stream per solver, :167-181) — runs once, on the
+ * host, for both.  The table's scaffold (plan, sampling, scatter, common counters) is ransac_table.h, shared with pnp.cpp; here are
+ * the argument checks, the records, the rows on the host and the hand-back path.  DESIGN.md section 16. */
 #include "sim3_internal.h"
-#include "glibc_rand.h"
-#include "hip_buf.h"
 #include "stage_layout.h"
 #include "../../include/drfe_debug.h"
 
-#include <climits>
-#include <cmath>
-#include <cstring>
-#include <string>
-#include <vector>
-
-struct Sim3Buffers {
-    StagePair io;                      /* staging: one copy each way */
-    DevBuf<char> scratch;              /* Sim3Corr per correspondence, T21 per hypothesis */
-    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+struct Sim3Buffers : RansacBuffers {   /* scratch: Sim3Corr per correspondence, T21 per hypothesis */
     int handBackEvery = 0;             /* drfe_debug_sim3_hand_back: treat every k-th hypothesis of a call as not certified */
 };
 
@@ -31,45 +21,7 @@ namespace {
 
 enum { SIM3_MAX_SOLVERS = 65535 };     /* the counting kernel's grid has one row per solver */
 
-/* where a solver's rows lie in the caller's table and in the compact one of a call */
-struct Plan {
-    std::vector<int32_t> iterations, hyp, hyp0, words, row0;
-    std::vector<int64_t> mask0Out, mask0;  /* the caller's (cap rows), the compact one (hyp rows) */
-    std::vector<int32_t> sample;           /* 3 per hypothesis, compact */
-    int nHyp = 0, maxHyp = 0, rows = 0;
-    int64_t maskWords = 0, maskWordsOut = 0;
-};
-
-/* SetRansacParameters (:118-142): float epsilon, the count in double through the host's libm, int conversion as cvttsd2si
- * (NaN and out-of-range give INT_MIN), clamped to [1, maxIterations] */
-int ransac_iterations(int N, double probability, int minInliers, int maxIterations)
-{
-    int nIterations;
-    if (minInliers == N) nIterations = 1;
-    else {
-        const float epsilon = (float)minInliers / N;
-        const double v = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double)epsilon, 3.0)));
-        nIterations = (v >= -2147483648.0 && v < 2147483648.0) ? (int)v : INT_MIN;
-    }
-    const int m = nIterations < maxIterations ? nIterations : maxIterations;
-    return m > 1 ? m : 1;
-}
-
-/* one iteration's sample (:167-181): three RandomInt draws from a list that shrinks by swap-with-back */
-void draw_sample(GlibcRand& rng, std::vector<int32_t>& avail, int N, int32_t out[3])
-{
-    /* vAvailableIndices = mvAllIndices: only the entries a previous iteration touched differ from the identity */
-    int size = N;
-    int touched[3];
-    for (int q = 0; q < 3; q++) {
-        const int randi = rng.random_int(0, size - 1);
-        out[q] = avail[(size_t)randi];
-        avail[(size_t)randi] = avail[(size_t)size - 1];
-        touched[q] = randi;
-        size--;
-    }
-    for (int q = 0; q < 3; q++) avail[(size_t)touched[q]] = touched[q];
-}
+using Plan = RansacPlan<3, DRFE_SIM3_MAX_CORR>;
 
 int cap_of(const drfe_sim3_problems* p, int s) { return p->max_iterations[s] > 1 ? p->max_iterations[s] : 1; }
 
@@ -81,15 +33,13 @@ int make_plan(const drfe_sim3_problems* p, const drfe_sim3_out* o, Plan& P, std:
     const int n = p->n;
     if (n == 0) return DRFE_OK;
     if (!p->Tcw1 || !p->Tcw2 || !p->K1 || !p->K2 || !p->fix_scale || !p->probability || !p->min_inliers || !p->max_iterations ||
-        !p->seed || !p->offsets || p->offsets[0] != 0)
+        !p->seed || !p->offsets)
         return DRFE_ERR_INVALID;
     if (!o->iterations || !o->hypotheses || !o->sample || !o->R12 || !o->t12 || !o->s12 || !o->T12 || !o->inliers || !o->returns ||
         !o->best || !o->mask)
         return DRFE_ERR_INVALID;
     for (int s = 0; s < n; s++) {
-        const int64_t N = (int64_t)p->offsets[s + 1] - p->offsets[s];
-        if (N < 0) { err = "sim3: decreasing offsets"; return DRFE_ERR_INVALID; }
-        if (N > DRFE_SIM3_MAX_CORR) { err = "sim3: more than DRFE_SIM3_MAX_CORR correspondences in a solver"; return DRFE_ERR_INVALID; }
+        if (!ransac_offsets_ok(p->offsets, s, DRFE_SIM3_MAX_CORR, "sim3", "DRFE_SIM3_MAX_CORR", err)) return DRFE_ERR_INVALID;
         if (p->max_iterations[s] > DRFE_SIM3_MAX_ITERATIONS) { err = "sim3: max_iterations above DRFE_SIM3_MAX_ITERATIONS"; return DRFE_ERR_INVALID; }
         if (p->min_inliers[s] < 0) { err = "sim3: negative min_inliers"; return DRFE_ERR_INVALID; }
     }
@@ -100,32 +50,12 @@ int make_plan(const drfe_sim3_problems* p, const drfe_sim3_out* o, Plan& P, std:
             const double b = 9.210 * (double)sg[i];
             if (!(b >= 0.0 && b < 9223372036854775808.0)) { err = "sim3: 9.210 * sigma2 outside [0, 2^63)"; return DRFE_ERR_INVALID; }
         }
-    P.iterations.resize((size_t)n); P.hyp.resize((size_t)n); P.hyp0.resize((size_t)n); P.words.resize((size_t)n);
-    P.row0.resize((size_t)n); P.mask0.resize((size_t)n); P.mask0Out.resize((size_t)n);
-    std::vector<int32_t> avail((size_t)DRFE_SIM3_MAX_CORR);
-    for (int i = 0; i < DRFE_SIM3_MAX_CORR; i++) avail[(size_t)i] = i;
     for (int s = 0; s < n; s++) {
-        const int N = p->offsets[s + 1] - p->offsets[s];
-        const int it = ransac_iterations(N, p->probability[s], p->min_inliers[s], p->max_iterations[s]);
-        const int hyp = (N < p->min_inliers[s] || N < 3) ? 0 : it;
-        const int words = (N + 63) / 64;
-        P.iterations[(size_t)s] = it;
-        P.hyp[(size_t)s] = hyp;
-        P.hyp0[(size_t)s] = P.nHyp;
-        P.words[(size_t)s] = words;
-        P.row0[(size_t)s] = P.rows;
-        P.mask0[(size_t)s] = P.maskWords;
-        P.mask0Out[(size_t)s] = P.maskWordsOut;
-        P.nHyp += hyp;
-        P.rows += cap_of(p, s);
-        P.maskWords += (int64_t)hyp * words;
-        P.maskWordsOut += (int64_t)cap_of(p, s) * words;
-        if (hyp > P.maxHyp) P.maxHyp = hyp;
-        if (hyp > 0) {
-            GlibcRand rng(p->seed[s]);
-            P.sample.resize(3 * (size_t)P.nHyp);
-            for (int h = 0; h < hyp; h++) draw_sample(rng, avail, N, &P.sample[3 * ((size_t)P.hyp0[(size_t)s] + h)]);
-        }
+        /* SetRansacParameters (:118-142): float epsilon */
+        const int N = p->offsets[s + 1] - p->offsets[s], minInliers = p->min_inliers[s];
+        const bool single = minInliers == N;
+        const int it = ransac_iteration_count(single, single ? 0.f : (float)minInliers / N, p->probability[s], p->max_iterations[s]);
+        P.add_solver(N, it, (N < minInliers || N < 3) ? 0 : it, cap_of(p, s), p->seed[s]);
     }
     return DRFE_OK;
 }
@@ -146,9 +76,7 @@ void begin_out(const drfe_sim3_problems* p, const Plan& P, drfe_sim3_out* o)
     for (int s = 0; s < p->n; s++) {
         o->iterations[s] = P.iterations[(size_t)s];
         o->hypotheses[s] = P.hyp[(size_t)s];
-        if (P.hyp[(size_t)s])
-            std::memcpy(o->sample + 3 * (size_t)P.row0[(size_t)s], &P.sample[3 * (size_t)P.hyp0[(size_t)s]],
-                        3 * (size_t)P.hyp[(size_t)s] * sizeof(int32_t));
+        P.scatter(s, o->sample, P.sample.data(), 3);
     }
 }
 
@@ -167,7 +95,7 @@ void solver_corrs(const drfe_sim3_problems* p, int s, std::vector<Sim3Corr>& cor
 void host_row(const drfe_sim3_problems* p, const Plan& P, int s, int h, const std::vector<Sim3Corr>& corr, drfe_sim3_out* o)
 {
     const size_t row = (size_t)P.row0[(size_t)s] + h;
-    const int32_t* smp = &P.sample[3 * ((size_t)P.hyp0[(size_t)s] + h)];
+    const int32_t* smp = P.sample_of(s, h);
     float P1[9], P2[9];
     for (int q = 0; q < 3; q++)
         for (int r = 0; r < 3; r++) {
@@ -227,16 +155,11 @@ int drfe_sim3_ransac_batch(drfe_ctx* c, const drfe_sim3_problems* p, drfe_sim3_o
     if (rc) return rc;
     Sim3Buffers* b = c->sim3;
     if (!b) { b = new Sim3Buffers(); c->sim3 = b; }
-    b->stats[0]++;
+    P.count_call(b->stats, p->offsets);
     if (p->n == 0) return DRFE_OK;
     const int n = p->n, M = p->offsets[n], H = P.nHyp;
-    b->stats[1] += n;
-    b->stats[2] += H;
-    b->stats[3] += M;
-    for (int s = 0; s < n; s++) {
-        if (!P.hyp[(size_t)s]) b->stats[7]++;
-        else b->stats[p->offsets[s + 1] - p->offsets[s] <= DRFE_SIM3_LDS_CORR ? 4 : 5]++;
-    }
+    for (int s = 0; s < n; s++)
+        if (P.hyp[(size_t)s]) b->stats[p->offsets[s + 1] - p->offsets[s] <= DRFE_SIM3_LDS_CORR ? 4 : 5]++;
     begin_out(p, P, o);
     if (H == 0) return DRFE_OK;
     const size_t nM = (size_t)M, nH = (size_t)H;
@@ -258,7 +181,6 @@ int drfe_sim3_ransac_batch(drfe_ctx* c, const drfe_sim3_problems* p, drfe_sim3_o
     char* h = b->io.hin;
     Sim3Solver* sol = sSolver.at(h);
     int32_t* corrSolver = sCorrSolver.at(h);
-    int32_t* hypSolver = sHypSolver.at(h);
     for (int s = 0; s < n; s++) {
         Sim3Solver& S = sol[s];
         std::memcpy(S.Tcw1, p->Tcw1 + 12 * (size_t)s, sizeof(S.Tcw1));
@@ -266,17 +188,11 @@ int drfe_sim3_ransac_batch(drfe_ctx* c, const drfe_sim3_problems* p, drfe_sim3_o
         std::memcpy(S.K1, p->K1 + 4 * (size_t)s, sizeof(S.K1));
         std::memcpy(S.K2, p->K2 + 4 * (size_t)s, sizeof(S.K2));
         S.fixScale = p->fix_scale[s] ? 1 : 0;
-        S.minInliers = p->min_inliers[s];
-        S.n = p->offsets[s + 1] - p->offsets[s];
-        S.corr0 = p->offsets[s];
-        S.hyp = P.hyp[(size_t)s];
-        S.hyp0 = P.hyp0[(size_t)s];
-        S.words = P.words[(size_t)s];
         S.pad = 0;
-        S.mask0 = P.mask0[(size_t)s];
+        S.head = P.head(s, p->offsets, p->min_inliers[s]);
         for (int i = p->offsets[s]; i < p->offsets[s + 1]; i++) corrSolver[i] = s;
-        for (int q = 0; q < S.hyp; q++) hypSolver[S.hyp0 + q] = s;
     }
+    P.fill_hyp_solver(sHypSolver.at(h));
     sXw1.put(h, p->Xw1);
     sXw2.put(h, p->Xw2);
     sSig1.put(h, p->sigma2_1);
@@ -298,24 +214,20 @@ int drfe_sim3_ransac_batch(drfe_ctx* c, const drfe_sim3_problems* p, drfe_sim3_o
     L.R12 = sR.at(dO); L.t12 = sT.at(dO); L.s12 = sS.at(dO); L.T12 = sT12.at(dO);
     L.inliers = sInl.at(dO); L.best = sBest.at(dO); L.returns = sRet.at(dO); L.uncertified = sUnc.at(dO);
     L.mask = sMask.at(dO);
-    hipError_t e = drfe_launch_sim3(L, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(b->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) { c->err = std::string("sim3 batch: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
-    HIPCHK(c, hipStreamSynchronize(st));
+    if (const int e = ransac_finish(c, "sim3", drfe_launch_sim3(L, st), b->io, out.bytes(), st)) return e;
     const char* ho = b->io.hout;
     const uint8_t* unc = sUnc.at(ho);
     std::vector<Sim3Corr> corr;
     for (int s = 0; s < n; s++) {
-        const size_t hy = (size_t)P.hyp[(size_t)s], h0 = (size_t)P.hyp0[(size_t)s], r0 = (size_t)P.row0[(size_t)s];
-        if (!hy) continue;
-        std::memcpy(o->R12 + 9 * r0, sR.at(ho) + 9 * h0, hy * 9 * sizeof(float));
-        std::memcpy(o->t12 + 3 * r0, sT.at(ho) + 3 * h0, hy * 3 * sizeof(float));
-        std::memcpy(o->s12 + r0, sS.at(ho) + h0, hy * sizeof(float));
-        std::memcpy(o->T12 + 12 * r0, sT12.at(ho) + 12 * h0, hy * 12 * sizeof(float));
-        std::memcpy(o->inliers + r0, sInl.at(ho) + h0, hy * sizeof(int32_t));
-        std::memcpy(o->best + r0, sBest.at(ho) + h0, hy * sizeof(int32_t));
-        std::memcpy(o->returns + r0, sRet.at(ho) + h0, hy);
-        std::memcpy(o->mask + P.mask0Out[(size_t)s], sMask.at(ho) + P.mask0[(size_t)s], hy * (size_t)P.words[(size_t)s] * sizeof(uint64_t));
+        const size_t hy = (size_t)P.hyp[(size_t)s], h0 = (size_t)P.hyp0[(size_t)s];
+        P.scatter(s, o->R12, sR.at(ho), 9);
+        P.scatter(s, o->t12, sT.at(ho), 3);
+        P.scatter(s, o->s12, sS.at(ho));
+        P.scatter(s, o->T12, sT12.at(ho), 12);
+        P.scatter(s, o->inliers, sInl.at(ho));
+        P.scatter(s, o->best, sBest.at(ho));
+        P.scatter(s, o->returns, sRet.at(ho));
+        P.scatter_mask(s, o->mask, sMask.at(ho));
         /* what the device could not certify: the host core finishes the row, then redoes the solver's bookkeeping */
         int handed = 0;
         for (size_t q = 0; q < hy; q++)
@@ -335,8 +247,7 @@ int drfe_sim3_ransac_batch(drfe_ctx* c, const drfe_sim3_problems* p, drfe_sim3_o
 int drfe_sim3_stats(drfe_ctx* c, int64_t* stats)
 {
     if (!c || !stats) return DRFE_ERR_INVALID;
-    if (c->sim3) std::memcpy(stats, c->sim3->stats, sizeof(c->sim3->stats));
-    else std::memset(stats, 0, 8 * sizeof(int64_t));
+    ransac_stats(c->sim3, stats);
     return DRFE_OK;
 }
 

@@ -3,22 +3,18 @@
 #define DRFE_SIM3_INTERNAL_H
 
 #include "drfe_internal.h"
+#include "ransac_table.h"
 #include "sim3_core.h"
 
-/* correspondences of a solver the counting kernel keeps in LDS (48 bytes each: 48 KiB of a workgroup's 64); above it reads
- * them from global memory */
+/* the counting kernel's LDS bound and rows per workgroup (ransac_device.h); a Sim3Corr is 48 bytes */
 #define DRFE_SIM3_LDS_CORR 1024
-/* hypotheses per workgroup of the counting kernel (four wavefronts, eight each) */
 #define DRFE_SIM3_CHUNK 32
 
 /* one solver on the device */
 struct Sim3Solver {
     float Tcw1[12], Tcw2[12], K1[4], K2[4];
-    int32_t fixScale, minInliers;
-    int32_t n, corr0;              /* correspondences: count, first */
-    int32_t hyp, hyp0;             /* hypotheses: count, first (compact over the call) */
-    int32_t words, pad;            /* mask words per hypothesis */
-    int64_t mask0;                 /* first mask word (compact over the call) */
+    int32_t fixScale, pad;
+    RansacSolverHead head;         /* minInliers as the caller gave it */
 };
 
 struct Sim3Launch {

@@ -4,14 +4,14 @@
  *   k_sim3_horn     one lane per hypothesis: ComputeSim3 on its three sampled correspondences (Horn, the 4x4 Jacobi, Rodrigues in
  *                   float64); leaves R12, t12, s12, T12 in the table and T21 in scratch.
  *   k_sim3_count    workgroups over (solver, 32 hypotheses), one wavefront per hypothesis at a time: CheckInliers over the
- *                   correspondences 64 at a time, the ballot of the test is the mask word, its popcount adds to the count.  A solver
- *                   of at most DRFE_SIM3_LDS_CORR correspondences is first copied into LDS; a larger one is read from global memory.
+ *                   correspondences 64 at a time (ransac_device.h).
  *   k_sim3_walk     one lane per solver: iterate's `>=` / `>` bookkeeping over its <= 300 counts in iteration order.
  * No float atomics and no sum across lanes: every float sum has the reference's order inside one lane.  -ffp-contract=off, as
  * the host entry. */
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "sim3_internal.h"
+#include "ransac_device.h"
 
 #define SIM3_THREADS 256
 
@@ -30,7 +30,7 @@ __global__ __launch_bounds__(64) void k_sim3_horn(const Sim3Launch L)
     const Sim3Solver& S = L.solver[L.hypSolver[w]];
     float P1[9], P2[9];
     for (int q = 0; q < 3; q++) {
-        const Sim3Corr& c = L.corr[S.corr0 + L.sample[3 * (size_t)w + q]];
+        const Sim3Corr& c = L.corr[S.head.corr0 + L.sample[3 * (size_t)w + q]];
         for (int r = 0; r < 3; r++) {
             P1[r * 3 + q] = c.c1[r];
             P2[r * 3 + q] = c.c2[r];
@@ -52,48 +52,24 @@ __global__ __launch_bounds__(SIM3_THREADS) void k_sim3_count(const Sim3Launch L)
 {
     __shared__ Sim3Corr lds[DRFE_SIM3_LDS_CORR];
     const Sim3Solver& S = L.solver[blockIdx.y];
-    const int h0 = blockIdx.x * DRFE_SIM3_CHUNK;
-    if (h0 >= S.hyp) return;                         /* uniform over the workgroup */
-    const int N = S.n;
-    const bool inLds = N <= DRFE_SIM3_LDS_CORR;
-    const Sim3Corr* corr = L.corr + S.corr0;
-    if (inLds) {
-        /* 12 dwords per record: a straight dword copy */
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(corr);
-        uint32_t* dst = reinterpret_cast<uint32_t*>(lds);
-        for (int k = threadIdx.x; k < N * 12; k += SIM3_THREADS) dst[k] = src[k];
-        __syncthreads();
-        corr = lds;
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int perWave = DRFE_SIM3_CHUNK / (SIM3_THREADS / 64);
-    for (int j = 0; j < perWave; j++) {
-        const int h = h0 + wave * perWave + j;
-        if (h >= S.hyp) break;                       /* uniform over the wavefront */
-        const size_t w = (size_t)S.hyp0 + h;
+    const int lane = threadIdx.x & 63;
+    ransac_count_rows<DRFE_SIM3_CHUNK, SIM3_THREADS>(S.head, L.corr + S.head.corr0, lds,
+                                                    [&](const Sim3Corr* corr, int N, int h, size_t w) {
         float T12[12], T21[12];
         for (int k = 0; k < 12; k++) {
             T12[k] = L.T12[12 * w + k];
             T21[k] = L.T21[12 * w + k];
         }
-        uint64_t* mask = L.mask + S.mask0 + (size_t)h * S.words;
-        int count = 0;
-        for (int base = 0; base < N; base += 64) {
-            const int i = base + lane;
-            const bool ok = i < N && s3_inlier(corr[i < N ? i : 0], T12, T21, S.K1, S.K2);
-            const unsigned long long word = __ballot(ok);
-            count += __popcll(word);
-            if (lane == 0) mask[base >> 6] = word;
-        }
-        if (lane == 0) L.inliers[w] = count;
-    }
+        ransac_sweep(corr, N, lane, L.mask + S.head.mask0 + (size_t)h * S.head.words, L.inliers + w,
+                     [&](const Sim3Corr& c) { return s3_inlier(c, T12, T21, S.K1, S.K2); });
+    });
 }
 
 __global__ __launch_bounds__(64) void k_sim3_walk(const Sim3Launch L)
 {
     const int s = blockIdx.x * 64 + threadIdx.x;
     if (s >= L.nSolvers) return;
-    const Sim3Solver& S = L.solver[s];
+    const RansacSolverHead& S = L.solver[s].head;
     s3_walk(L.inliers + S.hyp0, S.hyp, S.minInliers, L.returns + S.hyp0, L.best + S.hyp0);
 }
 

@@ -1,7 +1,8 @@
 """An independent restatement of PnPsolver for the tests: the reference's control flow with its per-point
 arrays (pws, us, alphas, pcs) kept as the reference keeps them, IEEE double as Python floats (the same format and roundings as
 numpy.float64 scalars, math.sqrt correctly rounded), float32 steps as numpy.float32; its own Jacobi SVD, back-substitution,
-Householder QR, MulTransposed order and cv::RNG; glibc's rand() from sim3_numpy; and a TableWalker with iterate's `||` loop."""
+Householder QR, MulTransposed order and cv::RNG; glibc's rand() and the sampling from ransac_numpy; and a TableWalker with
+iterate's `||` loop."""
 import math
 import os
 import sys
@@ -9,14 +10,13 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from sim3_numpy import GlibcRand, _clog  # noqa: E402
+from ransac_numpy import GlibcRand, iteration_count, sample_sets, trunc32 as _trunc32  # noqa: E402
 
 F = np.float32
 DBL_EPS = 2.220446049250313e-16
 DBL_MIN = 2.2250738585072014e-308
 MAX_CORR, MAX_ITERATIONS, MAX_TAIL, LDS_CORR = 4096, 300, 300, 2048
 QNAN = np.frombuffer(np.uint64(0x7FF8000000000000).tobytes(), np.float64)[0]
-INT_MIN = -2147483648
 
 
 def _div(a, b):
@@ -42,11 +42,6 @@ def _sqrtn(a):
 
 # ------------------------------------------------------------------------------------------------------------------------------
 # SetRansacParameters, sampling
-def _trunc32(v):
-    v = float(v)
-    return int(v) if (v == v and -2147483648.0 <= v < 2147483648.0) else INT_MIN
-
-
 def ransac_parameters(N, probability, min_inliers, max_iterations, epsilon):
     """(mRansacMinInliers, mRansacMaxIts) after SetRansacParameters with minSet = 4"""
     eps = F(epsilon)
@@ -56,30 +51,11 @@ def ransac_parameters(N, probability, min_inliers, max_iterations, epsilon):
         q = F(n_min) / F(N)
         if eps < q:
             eps = q
-    if n_min == N:
-        n_it = 1
-    else:
-        e = float(eps)
-        with np.errstate(all="ignore"):
-            p3 = float(np.power(np.float64(e), np.float64(3.0)))
-        a, b = _clog(1 - float(probability)), _clog(1 - p3)
-        v = _div(a, b)
-        v = math.ceil(v) if math.isfinite(v) else v
-        n_it = _trunc32(v)
-    return n_min, max(1, min(n_it, int(max_iterations)))
+    return n_min, iteration_count(n_min == N, eps, probability, max_iterations)
 
 
 def sample_quads(seed, N, rows):
-    rng = GlibcRand(seed)
-    out = np.zeros((rows, 4), np.int32)
-    for h in range(rows):
-        avail = list(range(N))
-        for q in range(4):
-            r = rng.random_int(0, len(avail) - 1)
-            out[h, q] = avail[r]
-            avail[r] = avail[-1]
-            avail.pop()
-    return out
+    return sample_sets(seed, N, rows, 4)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -1,10 +1,16 @@
 """An independent restatement of Sim3Solver (reference src/Sim3Solver.cc) in numpy: every step in float32 / float64 scalars or
 element-wise arrays in the order DESIGN.md section 16 reads the reference's OpenCV calls, its own Jacobi and Rodrigues, sin / cos /
-atan2 through mpmath rounded once, glibc's rand() restated in Python integers.  Plus a scene generator, the reference's iterate() run
-literally (Solver), and a walk over a finished table (TableWalker).  Used by tests/test_sim3_cpu.py and tests/test_gpu_sim3.py."""
+atan2 through mpmath rounded once, glibc's rand() and the sampling from ransac_numpy.  Plus a scene generator, the reference's
+iterate() run literally (Solver), and a walk over a finished table (TableWalker).  Used by tests/test_sim3_cpu.py and
+tests/test_gpu_sim3.py."""
 import math
+import os
+import sys
 
 import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from ransac_numpy import GlibcRand, iteration_count, sample_sets  # noqa: E402
 
 F = np.float32
 D = np.float64
@@ -15,76 +21,20 @@ MAX_CORR, MAX_ITERATIONS = 4096, 300
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-# rand()
-class GlibcRand:
-    """glibc random_r TYPE_3: r[i] = r[i - 31] + r[i - 3] mod 2^32, output >> 1, seeded through the 16807 Lehmer step, 310
-    outputs discarded"""
-
-    def __init__(self, seed):
-        seed = int(seed) & 0xFFFFFFFF
-        w = seed if seed else 1
-        if w >= 1 << 31:
-            w -= 1 << 32
-        r = [w & 0xFFFFFFFF]
-        for _ in range(1, 31):
-            hi, lo = int(w / 127773), int(math.fmod(w, 127773))      # C division truncates
-            w = 16807 * lo - 2836 * hi
-            if w < 0:
-                w += 2147483647
-            r.append(w & 0xFFFFFFFF)
-        for i in range(31, 34):
-            r.append(r[i - 31])
-        for i in range(34, 344):
-            r.append((r[i - 31] + r[i - 3]) & 0xFFFFFFFF)
-        self.r = r
-
-    def rand(self):
-        v = (self.r[-31] + self.r[-3]) & 0xFFFFFFFF
-        self.r.append(v)
-        del self.r[0]
-        return v >> 1
-
-    def random_int(self, lo, hi):
-        """DUtils::Random::RandomInt"""
-        d = hi - lo + 1
-        return int((float(self.rand()) / (2147483647.0 + 1.0)) * d) + lo
-
-
+# SetRansacParameters, sampling
 def sample_triples(seed, N, iterations):
-    rng = GlibcRand(seed)
-    out = np.zeros((iterations, 3), np.int32)
-    for h in range(iterations):
-        avail = list(range(N))
-        for q in range(3):
-            r = rng.random_int(0, len(avail) - 1)
-            out[h, q] = avail[r]
-            avail[r] = avail[-1]
-            avail.pop()
-    return out
+    return sample_sets(seed, N, iterations, 3)
+
+
+def ransac_iterations(N, probability, min_inliers, max_iterations):
+    """SetRansacParameters: the clamped mRansacMaxIts"""
+    with np.errstate(all="ignore"):
+        eps = F(min_inliers) / F(N)
+    return iteration_count(min_inliers == N, eps, probability, max_iterations)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
 # libm
-def _clog(x):
-    if x != x or x < 0:
-        return math.nan
-    return -math.inf if x == 0 else math.log(x)
-
-
-def ransac_iterations(N, probability, min_inliers, max_iterations):
-    """SetRansacParameters: the clamped mRansacMaxIts (the int conversion of a NaN or an out-of-range double is INT_MIN)"""
-    if min_inliers == N:
-        n_it = 1
-    else:
-        with np.errstate(all="ignore"):
-            eps = F(min_inliers) / F(N)
-        a, b = _clog(1 - float(probability)), _clog(1 - math.pow(float(eps), 3.0)) if math.isfinite(float(eps)) else math.nan
-        with np.errstate(all="ignore"):
-            v = float(np.ceil(D(a) / D(b)))
-        n_it = int(v) if (v == v and -2147483648.0 <= v < 2147483648.0) else -2147483648
-    return max(1, min(n_it, int(max_iterations)))
-
-
 def _mp():
     import mpmath
     mpmath.mp.prec = 400
