@@ -6,6 +6,7 @@
 #include "triangulate_internal.h"
 #include "sim3_internal.h"
 #include "pnp_internal.h"
+#include "line3d_internal.h"
 #include <atomic>
 #include "post_internal.h"
 #include "match_internal.h"
@@ -154,6 +155,7 @@ void drfe_destroy(drfe_ctx* c)
     drfe_triangulate_free(c);
     drfe_sim3_free(c);
     drfe_pnp_free(c);
+    drfe_line3d_free(c);
     drfe_post_free(c);
     drfe_one_shot_free(c);
     drfe_frame_lanes_free(c);

@@ -53,6 +53,7 @@ SYMBOLS = (
     "drfe_sim3_ransac_host", "drfe_sim3_ransac_batch", "drfe_sim3_stats", "drfe_debug_sim3_atan2", "drfe_debug_sim3_rand",
     "drfe_debug_sim3_horn", "drfe_debug_sim3_hand_back",
     "drfe_pnp_ransac_host", "drfe_pnp_ransac_batch", "drfe_pnp_stats", "drfe_debug_pnp_svd", "drfe_debug_pnp_inliers", "drfe_debug_pnp_inliers_device",
+    "drfe_lines_is_good_batch", "drfe_line3d_chunk_frames", "drfe_line3d_stats",
 )
 
 FRUSTUM_POINT_DTYPE = np.dtype([("world", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"),
@@ -191,6 +192,19 @@ class Sim3Out(C.Structure):
 SIM3_MAX_CORR, SIM3_MAX_ITERATIONS = 4096, 300
 SIM3_STATS = ("calls", "solvers", "hypotheses", "correspondences", "solvers_lds", "solvers_global", "uncertified", "solvers_empty")
 PNP_STATS = ("calls", "solvers", "hypotheses", "correspondences", "refine_jobs", "refine_points", "solvers_global", "solvers_empty")
+LINE3D_STATS = ("calls", "frames", "lines", "ransac_lines", "iterations", "coincident_pairs", "verify_rejections", "accepted")
+LINE3D_MAX_CAP = 4096
+
+
+class Line3dFrames(C.Structure):
+    _fields_ = [("nframes", C.c_int32), ("cap", C.c_int32), ("lines", C.c_void_p), ("n_lines", C.c_void_p), ("depth", C.c_void_p),
+                ("frame_stride", C.c_size_t), ("stride", C.c_size_t), ("w", C.c_int32), ("h", C.c_int32),
+                ("depth_on_device", C.c_int32), ("k_as_f64", C.c_int32), ("K", C.c_float * 9), ("cx", C.c_float),
+                ("cy", C.c_float), ("invfx", C.c_float), ("invfy", C.c_float), ("seeds", C.c_void_p)]   # drfe_line3d_frames
+
+
+class Line3dOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ("depth_line", "lines3d", "n_inliers", "n_good")]              # drfe_line3d_out
 
 
 class Camera(C.Structure):
@@ -352,6 +366,9 @@ def load() -> C.CDLL:
     L.drfe_pnp_ransac_host.argtypes = [vp, vp]
     L.drfe_pnp_ransac_batch.argtypes = [vp, vp, vp, vp]
     L.drfe_pnp_stats.argtypes = [vp, vp]
+    L.drfe_lines_is_good_batch.argtypes = [vp, vp, vp, vp]
+    L.drfe_line3d_chunk_frames.argtypes = [i32]
+    L.drfe_line3d_stats.argtypes = [vp, vp]
     L.drfe_debug_pnp_svd.argtypes = [vp, i32, i32, vp, vp, vp]
     L.drfe_debug_pnp_inliers.argtypes = [vp, vp, vp, vp, vp, vp, i32, vp]
     L.drfe_debug_pnp_inliers_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp]
@@ -912,6 +929,32 @@ def lines_is_good(lines, depth_f32, K9, cx, cy, invfx, invfy, k_as_f64=False, se
     if rc != 0:
         raise RuntimeError(f"drfe_lines_is_good failed ({rc})")
     return dl[:n], l3[:n], ni[:n], good.value
+
+
+def line3d_chunk_frames(cap):
+    """frames of `cap` key lines that Context.lines_is_good_batch lifts at once; a larger call runs in chunks of that many"""
+    return load().drfe_line3d_chunk_frames(int(cap))
+
+
+def line3d_frames(lines, n_lines, depth, K9, cx, cy, invfx, invfy, k_as_f64=True, seeds=None, w=None):
+    """drfe_line3d_frames and zeroed drfe_line3d_out over lines [F, cap] KEYLINE_DTYPE, n_lines [F], depth [F, h, stride]
+    (float32 numpy, or a torch tensor on the device: depth_on_device) of images w wide (default: stride), seeds [F] or None:
+    (frames, out, results (depth_line [F, cap] = -1, lines3d [F, cap, 6], n_inliers [F, cap], n_good [F]), keep-alive)"""
+    kl = np.ascontiguousarray(lines, KEYLINE_DTYPE)
+    F, cap = kl.shape
+    nl = np.ascontiguousarray(n_lines, np.int32)
+    on_device = not isinstance(depth, np.ndarray)
+    d = depth.contiguous() if on_device else np.ascontiguousarray(depth, np.float32)
+    assert len(nl) == F and d.shape[0] == F and len(d.shape) == 3 and (not on_device or "float32" in str(d.dtype))
+    sd = None if seeds is None else np.ascontiguousarray(seeds, np.uint32)
+    h, stride = int(d.shape[1]), int(d.shape[2])
+    fr = Line3dFrames(F, cap, _p(kl), _p(nl), C.c_void_p(d.data_ptr()) if on_device else _p(d), h * stride, stride,
+                      stride if w is None else int(w), h, int(on_device), int(bool(k_as_f64)),
+                      (C.c_float * 9)(*np.asarray(K9, np.float32).reshape(9).tolist()), float(cx), float(cy), float(invfx),
+                      float(invfy), _p(sd))
+    r = (np.full((F, cap), -1, np.float32), np.zeros((F, cap, 6), np.float64), np.zeros((F, cap), np.int32), np.zeros(F, np.int32))
+    out = Line3dOut(*[_p(a) for a in r])
+    return fr, out, r, (kl, nl, d, sd)
 
 
 class Shard:
@@ -2004,6 +2047,21 @@ class Context:
         st = np.zeros(8, np.int64)
         self._chk(self.L.drfe_pnp_stats(self.h, _p(st)), "drfe_pnp_stats")
         return dict(zip(PNP_STATS, st.tolist()))
+
+    def lines_is_good_batch(self, lines, n_lines, depth, K9, cx, cy, invfx, invfy, k_as_f64=True, seeds=None, w=None):
+        """lines_is_good for the key lines of F frames in one device call (drfe_lines_is_good_batch, arguments as line3d_frames):
+        (depth_line [F, cap], lines3d [F, cap, 6], n_inliers [F, cap], n_good [F]); frame f's first n_lines[f] entries are, byte for
+        byte, what lines_is_good gives with seed = seeds[f] (default 1), the others -1 / 0"""
+        fr, out, r, _keep = line3d_frames(lines, n_lines, depth, K9, cx, cy, invfx, invfy, k_as_f64, seeds, w)
+        self._chk(self.L.drfe_lines_is_good_batch(self.h, C.byref(fr), C.byref(out), None), "drfe_lines_is_good_batch")
+        return r
+
+    def line3d_stats(self):
+        """dict(calls, frames, lines, ransac_lines, iterations, coincident_pairs, verify_rejections, accepted) since the context
+        was created"""
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_line3d_stats(self.h, _p(st)), "drfe_line3d_stats")
+        return dict(zip(LINE3D_STATS, st.tolist()))
 
     def sim3_hand_back(self, every):
         """test hook: the host finishes every `every`-th hypothesis of a batch call as if the device had not certified it"""

@@ -415,6 +415,44 @@ int drfe_lines_is_good(const drfe_keyline* lines, int n, const float* depth, int
                        const float* K, int k_as_f64, float cx, float cy, float invfx, float invfy, uint32_t seed,
                        float* depth_line, double* lines3d, int32_t* n_inliers, int* n_good);
 
+/* The same for the key lines of nframes frames in one device call: frame f's key lines at lines[f * cap],
+ * n_lines[f] <= cap of them - the layout drfe_lsd_extract_batch writes - and its CV_32F depth image at depth + f * frame_stride
+ * (strides in floats).  depth_on_device: depth is a device pointer and nothing of it is uploaded.  One camera per call.
+ * seeds[f] is frame f's srand() state; seeds == NULL: 1 for every frame.  cap <= DRFE_LINE3D_MAX_CAP. */
+enum { DRFE_LINE3D_MAX_CAP = 4096 };
+/* frames in a call from which drfe::Line3DBatch uses the device entry.  The crossover has not been measured (DESIGN.md section
+ * 18), so by default it stays on the host entry */
+enum { DRFE_LINE3D_DEVICE_FROM = 2147483647 };
+typedef struct drfe_line3d_frames {
+    int32_t nframes, cap;
+    const drfe_keyline* lines;   /* nframes x cap */
+    const int32_t* n_lines;      /* nframes */
+    const float* depth;
+    size_t frame_stride, stride; /* floats between two frames, between two rows (>= w) */
+    int32_t w, h;
+    int32_t depth_on_device, k_as_f64;
+    float K[9];                  /* mK as the reference passes it */
+    float cx, cy, invfx, invfy;
+    const uint32_t* seeds;       /* nframes, or NULL */
+} drfe_line3d_frames;
+/* Frame f's results at f * cap, its first n_lines[f] entries written; n_inliers may be NULL. */
+typedef struct drfe_line3d_out {
+    float* depth_line;           /* nframes x cap: mvDepthLine */
+    double* lines3d;             /* nframes x cap x 6: mvLines3D */
+    int32_t* n_inliers;          /* nframes x cap */
+    int32_t* n_good;             /* nframes */
+} drfe_line3d_out;
+/* Frame f's outputs are byte for byte what drfe_lines_is_good writes for it with seeds[f], in both k_as_f64 modes.  The key
+ * lines and a rand() table staged with one copy (a host depth image goes up as it lies), three launches, the results back with
+ * one copy; returns with the outputs written (`stream` NULL = the context's).  A call of more frames than
+ * drfe_line3d_chunk_frames(cap) runs in chunks of that many. */
+int drfe_lines_is_good_batch(drfe_ctx* ctx, const drfe_line3d_frames* in, drfe_line3d_out* out, void* stream);
+int drfe_line3d_chunk_frames(int cap);
+/* Counters since the context was created: stats[0] batch calls, [1] frames, [2] key lines, [3] key lines that ran the RANSAC
+ * (at least 10 lifted samples), [4] RANSAC iterations run, [5] of those with a coincident pair, [6] candidate sets verify3dLine
+ * rejected, [7] accepted lines. */
+int drfe_line3d_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
+
 /* LSDmatcher::SearchByProjection, src/LSDmatcher.cpp:20-139 (Frame, Frame) and :141-211 (Frame,
  * vector<MapLine*>), with Frame::GetLinesInArea (src/Frame.cc:781-813): project the 3-D end points with
  * Tcw (float cv::Mat path), collect the current key lines whose midpoint lies within the radius and

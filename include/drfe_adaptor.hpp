@@ -20,6 +20,8 @@
  *                                      table with Refine's results (host entry; PnPBatch: every solver of a call at once)
  *   Planar_SLAM::Sim3Solver / drfe::Sim3Batch  include/Sim3Solver.h:35-130 - the loop closer's Sim3 RANSAC as a walk over a
  *                                      finished hypothesis table (host entry; Sim3Batch: every solver of a call on the device)
+ *   drfe::Line3DBatch                  src/Frame.cc:481-558          - Frame::isLineGood's mvDepthLine / mvLines3D for the
+ *                                      frames of a batch (one device call; the host entry below the crossover)
  * With -DDRFE_WITH_OPENCV the container types are OpenCV's (cv::Mat, cv::KeyPoint, cv::line_descriptor::KeyLine);
  * without it (this image has no OpenCV) minimal stand-ins with the same member names and memory layout are used, so the
  * header is compiled and exercised here (tests/native/adaptor_caller.cpp, run by tests/test_gpu_native.py).
@@ -2589,6 +2591,81 @@ public:
 private:
     Planar_SLAM::drfe_detail::CtxPtr mCtx;
     int mDeviceFrom;
+    std::mutex mMutex;
+};
+
+/* Frame::isLineGood (src/Frame.cc:481-558) for the frames of a batch: mvDepthLine and mvLines3D of every frame from its
+ * mvKeylinesUn and its CV_32F depth image, by one drfe_lines_is_good_batch call.  A call of fewer than
+ * `deviceFrom` frames loops the host entry drfe_lines_is_good (same bits).  The frames share one camera and one image size (the
+ * first frame's mK, cx, cy, invfx, invfy); kAsF64 = 0 is the reference as shipped, 1 the lifting as it was meant (include/drfe.h);
+ * seeds[f] is frame f's srand() state, 1 without.  Returns the accepted lines.  Owns its own drfe_ctx, as Sim3Batch.
+ * FrameT: mvKeylinesUn, mK (CV_32F 3x3, continuous), cx, cy, invfx, invfy, mvDepthLine (vector<float>), mvLines3D (vector of
+ * Vector6d: operator()(int)). */
+class Line3DBatch {
+public:
+    explicit Line3DBatch(int device = 0, int deviceFrom = DRFE_LINE3D_DEVICE_FROM, int kAsF64 = 0)
+        : mCtx(Planar_SLAM::drfe_detail::make_ctx(1, 1.2f, 1, 20, 7, 64, 64, 1, device)), mDeviceFrom(deviceFrom), mKAsF64(kAsF64) {}
+    drfe_ctx* ctx() const { return mCtx.get(); }
+    template <class FrameT>
+    int Fill(const std::vector<FrameT*>& frames, const std::vector<drfe_cv::Mat>& depth, const std::vector<uint32_t>* seeds = nullptr)
+    {
+        const size_t F = frames.size();
+        if (!F) return 0;
+        if (depth.size() != F || (seeds && seeds->size() != F)) throw std::invalid_argument("Line3DBatch::Fill: one depth image and one seed per frame");
+        const int w = depth[0].cols, h = depth[0].rows;
+        size_t cap = 1;
+        for (const FrameT* f : frames) cap = std::max(cap, f->mvKeylinesUn.size());
+        std::vector<drfe_keyline> kl(F * cap);
+        std::vector<int32_t> n(F), good(F, 0);
+        std::vector<float> depthLine(F * cap);
+        std::vector<double> l3(F * cap * 6);
+        for (size_t f = 0; f < F; f++) {
+            if (depth[f].cols != w || depth[f].rows != h || depth[f].empty()) throw std::invalid_argument("Line3DBatch::Fill: depth images of one size");
+            n[f] = (int32_t)frames[f]->mvKeylinesUn.size();
+            for (int i = 0; i < n[f]; i++) kl[f * cap + i] = Planar_SLAM::drfe_detail::keyline_of(frames[f]->mvKeylinesUn[i]);
+        }
+        const FrameT& F0 = *frames[0];
+        const float* K = reinterpret_cast<const float*>(F0.mK.data);
+        if (F < (size_t)mDeviceFrom) {
+            for (size_t f = 0; f < F; f++) {
+                const int rc = drfe_lines_is_good(&kl[f * cap], n[f], depth[f].template ptr<float>(0), w, h, depth[f].step / sizeof(float), K,
+                                                  mKAsF64, F0.cx, F0.cy, F0.invfx, F0.invfy, seeds ? (*seeds)[f] : 1u, &depthLine[f * cap],
+                                                  &l3[f * cap * 6], nullptr, &good[f]);
+                if (rc != DRFE_OK) throw std::runtime_error("drfe_lines_is_good: invalid argument");
+            }
+        } else {
+            std::lock_guard<std::mutex> lock(mMutex);
+            mDepth.resize(F * (size_t)w * h);          /* the images of a batch lie anywhere: packed here, uploaded by the call */
+            for (size_t f = 0; f < F; f++)
+                for (int r = 0; r < h; r++) std::memcpy(&mDepth[(f * h + r) * w], depth[f].template ptr<float>(r), (size_t)w * sizeof(float));
+            drfe_line3d_frames in = {};
+            in.nframes = (int32_t)F; in.cap = (int32_t)cap; in.lines = kl.data(); in.n_lines = n.data();
+            in.depth = mDepth.data(); in.frame_stride = (size_t)w * h; in.stride = (size_t)w; in.w = w; in.h = h;
+            in.depth_on_device = 0; in.k_as_f64 = mKAsF64;
+            std::memcpy(in.K, K, sizeof(in.K));
+            in.cx = F0.cx; in.cy = F0.cy; in.invfx = F0.invfx; in.invfy = F0.invfy;
+            in.seeds = seeds ? seeds->data() : nullptr;
+            drfe_line3d_out out = {depthLine.data(), l3.data(), nullptr, good.data()};
+            Planar_SLAM::drfe_detail::check(drfe_lines_is_good_batch(mCtx.get(), &in, &out, nullptr), mCtx.get(), "drfe_lines_is_good_batch");
+        }
+        int total = 0;
+        for (size_t f = 0; f < F; f++) {
+            FrameT& fr = *frames[f];
+            fr.mvDepthLine.resize((size_t)n[f]);
+            fr.mvLines3D.resize((size_t)n[f]);
+            for (int i = 0; i < n[f]; i++) {
+                fr.mvDepthLine[i] = depthLine[f * cap + i];
+                for (int q = 0; q < 6; q++) fr.mvLines3D[i](q) = l3[(f * cap + i) * 6 + q];
+            }
+            total += good[f];
+        }
+        return total;
+    }
+
+private:
+    Planar_SLAM::drfe_detail::CtxPtr mCtx;
+    int mDeviceFrom, mKAsF64;
+    std::vector<float> mDepth;
     std::mutex mMutex;
 };
 
