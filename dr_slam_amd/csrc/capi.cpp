@@ -6,6 +6,7 @@
 #include "triangulate_internal.h"
 #include "sim3_internal.h"
 #include "pnp_internal.h"
+#include "init_internal.h"
 #include "line3d_internal.h"
 #include <atomic>
 #include "post_internal.h"
@@ -155,6 +156,7 @@ void drfe_destroy(drfe_ctx* c)
     drfe_triangulate_free(c);
     drfe_sim3_free(c);
     drfe_pnp_free(c);
+    drfe_init_free(c);
     drfe_line3d_free(c);
     drfe_post_free(c);
     drfe_one_shot_free(c);

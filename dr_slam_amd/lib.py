@@ -52,6 +52,8 @@ SYMBOLS = (
     "drfe_triangulate_stats", "drfe_debug_triangulate_math",
     "drfe_sim3_ransac_host", "drfe_sim3_ransac_batch", "drfe_sim3_stats", "drfe_debug_sim3_atan2", "drfe_debug_sim3_rand",
     "drfe_debug_sim3_horn", "drfe_debug_sim3_hand_back",
+    "drfe_init_ransac_host", "drfe_init_ransac_batch", "drfe_init_stats",
+    "drfe_debug_init_cos_keys", "drfe_debug_init_null_vectors", "drfe_debug_init_check_rt",
     "drfe_pnp_ransac_host", "drfe_pnp_ransac_batch", "drfe_pnp_stats", "drfe_debug_pnp_svd", "drfe_debug_pnp_inliers", "drfe_debug_pnp_inliers_device",
     "drfe_lines_is_good_batch", "drfe_line3d_chunk_frames", "drfe_line3d_stats",
 )
@@ -181,6 +183,27 @@ PNP_OUT_FIELDS = ("iterations", "min_inliers", "hypotheses", "refines", "sample"
 
 class PnpOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in PNP_OUT_FIELDS]                             # drfe_pnp_out
+
+
+class InitProblems(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "K", "sigma", "max_iterations", "seed", "key1_offsets", "key2_offsets", "keys1", "keys2",
+        "matches12")]                                                                # drfe_init_problems
+
+
+INIT_OUT_FIELDS = ("N", "iterations", "hypotheses", "SH", "SF", "RH", "branch", "motions", "ok", "flags", "R21", "t21", "vP3D",
+                   "vbTriangulated", "sample", "H21", "F21", "score_h", "score_f", "best_h", "best_f", "mask_h", "mask_f",
+                   "motion_R", "motion_t", "motion_good", "motion_cos", "motion_parallax", "motion_status", "motion_vbGood",
+                   "motion_vP3D")
+INIT_BRANCH_NONE, INIT_BRANCH_H, INIT_BRANCH_F = 0, 1, 2
+INIT_TOO_FEW, INIT_NO_MODEL, INIT_H_DEGENERATE = 1, 2, 4
+INIT_MOTION_NAN_COS = 1
+INIT_MAX_KEYS, INIT_MAX_ITERATIONS, INIT_MAX_SOLVERS, INIT_MAX_ROWS, INIT_MAX_MASK_WORDS = 4096, 300, 65535, 1 << 20, 1 << 24
+INIT_STATS = ("calls", "solvers", "rows", "matches", "branch_h", "branch_f", "ok", "empty")
+
+
+class InitOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in INIT_OUT_FIELDS]                            # drfe_init_out
 
 
 class Sim3Out(C.Structure):
@@ -364,6 +387,12 @@ def load() -> C.CDLL:
     L.drfe_debug_sim3_horn.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     L.drfe_debug_sim3_hand_back.argtypes = [vp, i32]
     L.drfe_pnp_ransac_host.argtypes = [vp, vp]
+    L.drfe_init_ransac_host.argtypes = [vp, vp]
+    L.drfe_init_ransac_batch.argtypes = [vp, vp, vp, vp]
+    L.drfe_init_stats.argtypes = [vp, vp]
+    L.drfe_debug_init_cos_keys.argtypes = [vp, i32, vp, vp]
+    L.drfe_debug_init_null_vectors.argtypes = [vp, i32, vp, vp]
+    L.drfe_debug_init_check_rt.argtypes = [vp, vp, vp, vp, C.c_float, vp, i32, vp, vp, vp, vp, vp, vp]
     L.drfe_pnp_ransac_batch.argtypes = [vp, vp, vp, vp]
     L.drfe_pnp_stats.argtypes = [vp, vp]
     L.drfe_lines_is_good_batch.argtypes = [vp, vp, vp, vp]
@@ -838,6 +867,125 @@ def pnp_table(result, s):
     for k in ("iterations", "min_inliers", "refines"):
         t[k] = int(result[k][s])
     return t
+
+
+def _init_pack(problems):
+    """Packs a problem set (dict: K [n, 9] (mK row-major), sigma [n], max_iterations [n], seed [n], key1_offsets [n + 1],
+    key2_offsets [n + 1], keys1 [M1, 2], keys2 [M2, 2], matches12 [M1]) into drfe_init_problems and allocates the outputs:
+    (problems record, out record, the outputs as a dict, the arrays to keep alive).  The outputs: the fields of drfe_init_out
+    under their names, plus per solver row0, words, mask0 (N is filled by the call, so words and mask0 are computed here from
+    matches12).  Solver s's rows are row0[s] + h, its mask words mask0[s] + h * words[s] + (i // 64), its motion hypothesis m
+    entry [s, m] of the motion_* arrays and the slice [8 * key1_offsets[s] + m * nKeys1, + nKeys1) of motion_vbGood / motion_vP3D
+    (init_table slices them)."""
+    keep = []
+
+    def arr(key, dt, shape=-1):
+        v = np.ascontiguousarray(np.asarray(problems[key], dt).reshape(shape))
+        keep.append(v)
+        return v
+    o1, o2 = arr("key1_offsets", np.int32), arr("key2_offsets", np.int32)
+    n = len(o1) - 1
+    maxit, m12 = arr("max_iterations", np.int32), arr("matches12", np.int32)
+    P = InitProblems(n, 0, _p(arr("K", np.float32, (-1, 9))), _p(arr("sigma", np.float32)), _p(maxit), _p(arr("seed", np.uint32)),
+                     _p(o1), _p(o2), _p(arr("keys1", np.float32, (-1, 2))), _p(arr("keys2", np.float32, (-1, 2))), _p(m12))
+    cap = np.clip(maxit.astype(np.int64), 0, None)
+    N = np.array([int((m12[max(int(o1[s]), 0):max(int(o1[s + 1]), 0)] >= 0).sum()) for s in range(n)], np.int64)
+    words = (N + 63) // 64
+    row0 = np.concatenate([[0], np.cumsum(cap)])
+    mask0 = np.concatenate([[0], np.cumsum(cap * words)])
+    rows, W, M1 = int(row0[-1]), int(mask0[-1]), max(int(o1[-1]), 0) if n else 0
+    i32, f32 = np.int32, np.float32
+    r = dict(N=np.zeros(n, i32), iterations=np.zeros(n, i32), hypotheses=np.zeros(n, i32), SH=np.zeros(n, f32), SF=np.zeros(n, f32),
+             RH=np.zeros(n, f32), branch=np.zeros(n, i32), motions=np.zeros(n, i32), ok=np.zeros(n, i32), flags=np.zeros(n, i32),
+             R21=np.zeros((n, 9), f32), t21=np.zeros((n, 3), f32), vP3D=np.zeros((M1, 3), f32), vbTriangulated=np.zeros(M1, np.uint8),
+             sample=np.zeros((rows, 8), i32), H21=np.zeros((rows, 9), f32), F21=np.zeros((rows, 9), f32),
+             score_h=np.zeros(rows, f32), score_f=np.zeros(rows, f32), best_h=np.zeros(rows, i32), best_f=np.zeros(rows, i32),
+             mask_h=np.zeros(W, np.uint64), mask_f=np.zeros(W, np.uint64), motion_R=np.zeros((n, 8, 9), f32),
+             motion_t=np.zeros((n, 8, 3), f32), motion_good=np.zeros((n, 8), i32), motion_cos=np.zeros((n, 8), f32),
+             motion_parallax=np.zeros((n, 8), f32), motion_status=np.zeros((n, 8), i32), motion_vbGood=np.zeros(8 * M1, np.uint8),
+             motion_vP3D=np.zeros((8 * M1, 3), f32))
+    out = InitOut(*[_p(r[k]) for k in INIT_OUT_FIELDS])
+    r.update(row0=row0[:-1], words=words, mask0=mask0[:-1], key1_offsets=o1.copy())
+    return P, out, r, keep
+
+
+def _init_call(fn, head, problems):
+    """fn(*head, problems, out) over _init_pack's records: (return code, outputs)"""
+    P, out, r, _keep = _init_pack(problems)
+    rc = fn(*head, C.byref(P), C.byref(out), *([None] if head else []))
+    return rc, r
+
+
+def init_ransac_host(problems):
+    """Initializer::Initialize of every solver on the host (drfe_init_ransac_host, DESIGN.md section 19); problems and result as
+    _init_pack"""
+    rc, r = _init_call(load().drfe_init_ransac_host, (), problems)
+    if rc != 0:
+        raise DrfeError(f"drfe_init_ransac_host failed ({rc})")
+    return r
+
+
+def init_table(result, s):
+    """Solver s of an init_ransac_* result: its scalars as Python numbers, R21 [9], t21 [3], vP3D [nKeys1, 3], vbTriangulated
+    [nKeys1], its filled rows (sample, H21, F21, score_h, score_f, best_h, best_f, mask_h / mask_f [rows, words]) and its motion
+    hypotheses (motion_R [m, 9], motion_t [m, 3], motion_good, motion_cos, motion_parallax, motion_status [m], motion_vbGood
+    [m, nKeys1], motion_vP3D [m, nKeys1, 3])"""
+    a, n, w = int(result["row0"][s]), int(result["hypotheses"][s]), int(result["words"][s])
+    t = {k: result[k][a:a + n] for k in ("sample", "H21", "F21", "score_h", "score_f", "best_h", "best_f")}
+    m0 = int(result["mask0"][s])
+    for k in ("mask_h", "mask_f"):
+        t[k] = result[k][m0:m0 + n * w].reshape(n, w)
+    for k in ("N", "iterations", "hypotheses", "branch", "motions", "ok", "flags"):
+        t[k] = int(result[k][s])
+    for k in ("SH", "SF", "RH"):
+        t[k] = result[k][s]
+    k1, k2 = int(result["key1_offsets"][s]), int(result["key1_offsets"][s + 1])
+    nk, nm = k2 - k1, t["motions"]
+    t["R21"], t["t21"], t["vP3D"], t["vbTriangulated"] = result["R21"][s], result["t21"][s], result["vP3D"][k1:k2], result["vbTriangulated"][k1:k2]
+    for k in ("motion_R", "motion_t", "motion_good", "motion_cos", "motion_parallax", "motion_status"):
+        t[k] = result[k][s, :nm]
+    t["motion_vbGood"] = result["motion_vbGood"][8 * k1:8 * k1 + nm * nk].reshape(nm, nk)
+    t["motion_vP3D"] = result["motion_vP3D"][8 * k1:8 * k1 + nm * nk].reshape(nm, nk, 3)
+    return t
+
+
+def init_cos_keys(c):
+    """init_core.h's order of CheckRT's accepted cosines: (keys uint32 [n], the cosine each key stands for [n])"""
+    c = np.ascontiguousarray(c, np.float32)
+    key, value = np.zeros(len(c), np.uint32), np.zeros(len(c), np.float32)
+    if load().drfe_debug_init_cos_keys(_p(c), len(c), _p(key), _p(value)) != 0:
+        raise DrfeError("drfe_debug_init_cos_keys failed")
+    return key, value
+
+
+def init_null_vectors(points):
+    """init_core.h's float Jacobi SVD on samples of eight normalised matches [n, 8, 4] (x1 y1 x2 y2): vt.row(8) of ComputeH21's
+    16x9 system and of ComputeF21's 8x9 system, [n, 9] each"""
+    points = np.ascontiguousarray(points, np.float32).reshape(-1, 8, 4)
+    h, f = np.zeros((len(points), 9), np.float32), np.zeros((len(points), 9), np.float32)
+    if load().drfe_debug_init_null_vectors(_p(points), len(points), _p(h), _p(f)) != 0:
+        raise DrfeError("drfe_debug_init_null_vectors failed")
+    return h, f
+
+
+def init_check_rt(K, R, t, sigma, matches, ctx=None):
+    """CheckRT of one motion hypothesis over matches [n, 4] (u1 v1 u2 v2), every one an inlier and match i's reference key i:
+    dict(good, cos, parallax, status, vbGood [n], vP3D [n, 3]); with a Context through the device's CheckRT kernel"""
+    K, R, t = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (K, R, t))
+    assert K.size == 9 and R.size == 9 and t.size == 3
+    m = np.ascontiguousarray(matches, np.float32).reshape(-1, 4)
+    n = len(m)
+    good, status = np.zeros(1, np.int32), np.zeros(1, np.int32)
+    cos, par = np.zeros(1, np.float32), np.zeros(1, np.float32)
+    vb, X = np.zeros(n, np.uint8), np.zeros((n, 3), np.float32)
+    L = ctx.L if ctx is not None else load()
+    rc = L.drfe_debug_init_check_rt(ctx.h if ctx is not None else None, _p(K), _p(R), _p(t), float(sigma), _p(m), n, _p(good), _p(cos),
+                                    _p(par), _p(status), _p(vb), _p(X))
+    if ctx is not None:
+        ctx._chk(rc, "drfe_debug_init_check_rt")
+    elif rc != 0:
+        raise DrfeError("drfe_debug_init_check_rt failed")
+    return dict(good=int(good[0]), cos=cos[0], parallax=par[0], status=int(status[0]), vbGood=vb, vP3D=X)
 
 
 def pnp_svd(A):
@@ -2040,6 +2188,18 @@ class Context:
         rc, r = _pnp_call(self.L.drfe_pnp_ransac_batch, (self.h,), problems)
         self._chk(rc, "drfe_pnp_ransac_batch")
         return r
+
+    def init_ransac_batch(self, problems):
+        """init_ransac_host on the device (drfe_init_ransac_batch): same outputs, same bits"""
+        rc, r = _init_call(self.L.drfe_init_ransac_batch, (self.h,), problems)
+        self._chk(rc, "drfe_init_ransac_batch")
+        return r
+
+    def init_stats(self):
+        """drfe_init_stats as a dict over INIT_STATS"""
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_init_stats(self.h, _p(st)), "drfe_init_stats")
+        return dict(zip(INIT_STATS, (int(v) for v in st)))
 
     def pnp_stats(self):
         """dict(calls, solvers, hypotheses, correspondences, refine_jobs, refine_points, solvers_global, solvers_empty) since the

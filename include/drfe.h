@@ -1249,6 +1249,95 @@ int drfe_pnp_ransac_batch(drfe_ctx* ctx, const drfe_pnp_problems* problems, drfe
  * (the others with rows were kept in LDS), [7] solvers without a row. */
 int drfe_pnp_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
 
+/* Initializer (src/Initializer.cc), the RANSAC behind ORBmatcher::SearchForInitialization in Tracking::MonocularInitialization
+ * (src/Tracking.cc:1657-1760): the point-only Initialize(CurrentFrame, vMatches12, R21, t21, vP3D, vbTriangulated) of every solver
+ * of a call at once.  DESIGN.md section 19.
+ *
+ * A solver is one Initializer object plus one Initialize call: mK, sigma, the iteration count, every undistorted key of the
+ * reference and of the current frame (Normalize sums over all of them) and vMatches12, one int32 per reference key.  Its matches
+ * are the reference keys with vMatches12 >= 0 in index order, N of them.  Row h of a solver is iteration h of FindHomography and
+ * of FindFundamental on the same eight matches, draws 8h .. 8h + 7 of the solver's own glibc rand() stream, srand(seed) (the
+ * deviation of section 16: the reference calls srand(0) once per process, so seed 0 reproduces a process's first Initialize).
+ * best_h[h] / best_f[h] is the row that holds the model after row h (strict `>`, -1: none).  Then RH, the branch, the 8 (H) or
+ * 4 (F) motion hypotheses with what CheckRT makes of each, and the reference's choice among them.
+ * What the reference leaves undefined is refused or flagged: N < 8 (RandomInt(0, -1)) gives no rows and ok = 0; SH + SF == 0
+ * (RH is NaN and ReconstructF would multiply an empty F21) gives ok = 0 and DRFE_INIT_NO_MODEL; a CheckRT whose accepted cosines
+ * hold a NaN (std::sort on NaN) sets DRFE_INIT_MOTION_NAN_COS on the hypothesis, which orders a NaN above every number.
+ * Caps: DRFE_INIT_MAX_KEYS keys per frame, DRFE_INIT_MAX_ITERATIONS, 65 535 solvers, DRFE_INIT_MAX_ROWS rows and
+ * DRFE_INIT_MAX_MASK_WORDS words of one mask per call; above them the call is refused (DRFE_ERR_INVALID), as are decreasing
+ * offsets, a negative max_iterations and a match that is not -1 or an index into the current frame's keys. */
+enum { DRFE_INIT_MAX_KEYS = 4096, DRFE_INIT_MAX_ITERATIONS = 300, DRFE_INIT_MAX_SOLVERS = 65535 };
+enum { DRFE_INIT_MAX_ROWS = 1048576, DRFE_INIT_MAX_MASK_WORDS = 16777216 };
+/* branch[s] */
+enum { DRFE_INIT_BRANCH_NONE = 0, DRFE_INIT_BRANCH_H = 1, DRFE_INIT_BRANCH_F = 2 };
+/* flags[s] */
+enum { DRFE_INIT_TOO_FEW = 1, DRFE_INIT_NO_MODEL = 2, DRFE_INIT_H_DEGENERATE = 4 /* ReconstructH left at d1/d2, d2/d3 */ };
+/* motion_status[s][m] */
+enum { DRFE_INIT_MOTION_NAN_COS = 1 };
+/* solvers in a call from which Planar_SLAM::Initializer uses the device entry.  The crossover has not been measured on an MI355X
+ * yet, so it is INT32_MAX: the adaptor stays on the host entry unless its caller says UseDevice(true). */
+enum { DRFE_INIT_DEVICE_FROM = 2147483647 };
+typedef struct drfe_init_problems {
+    int32_t n;                   /* solvers */
+    int32_t pad;
+    const float* K;              /* n x 9: mK, row-major CV_32F */
+    const float* sigma;          /* n: the constructor's sigma (the reference passes 1.0) */
+    const int32_t* max_iterations; /* n: 0 .. DRFE_INIT_MAX_ITERATIONS (the reference passes 200) */
+    const uint32_t* seed;        /* n */
+    const int32_t* key1_offsets; /* n + 1: solver s's reference keys are [key1_offsets[s], key1_offsets[s + 1]); [0] == 0 */
+    const int32_t* key2_offsets; /* n + 1: its current frame's keys */
+    const float* keys1;          /* 2 per reference key: mvKeysUn[i].pt */
+    const float* keys2;          /* 2 per current key */
+    const int32_t* matches12;    /* per reference key: -1 or an index into the solver's current keys */
+} drfe_init_problems;
+/* Every pointer is required.  Solver s owns the rows [row0(s), row0(s) + max_iterations[s]), row0 the prefix sum; its masks
+ * start at word mask0(s), the prefix sum of max_iterations[s] * words(s), words(s) = ceil(N(s) / 64), row h at mask0(s) + h *
+ * words(s), match i in bit i % 64 of word i / 64 (the layout of drfe_sim3_out.mask).  Rows from hypotheses[s] on are zero.
+ * Motion hypothesis m of solver s is entry 8 s + m; its per-key arrays start at 8 * key1_offsets[s] + m * nKeys1(s).
+ * Every NaN stored is the quiet NaN 0x7FC00000. */
+typedef struct drfe_init_out {
+    int32_t* N;                  /* n: matches */
+    int32_t* iterations;         /* n: mMaxIterations */
+    int32_t* hypotheses;         /* n: rows filled: iterations[s], or 0 when N < 8 */
+    float* SH;                   /* n */
+    float* SF;                   /* n */
+    float* RH;                   /* n: SH / (SH + SF) */
+    int32_t* branch;             /* n: DRFE_INIT_BRANCH_* */
+    int32_t* motions;            /* n: 8, 4, or 0 */
+    int32_t* ok;                 /* n: Initialize's return value */
+    int32_t* flags;              /* n: DRFE_INIT_TOO_FEW | .. */
+    float* R21;                  /* n x 9; zero unless ok */
+    float* t21;                  /* n x 3 */
+    float* vP3D;                 /* 3 per reference key, at key1_offsets; zero unless ok */
+    uint8_t* vbTriangulated;     /* per reference key */
+    int32_t* sample;             /* rows x 8: the sampled matches in draw order */
+    float* H21;                  /* rows x 9: H21i */
+    float* F21;                  /* rows x 9: F21i */
+    float* score_h;              /* rows: currentScore of CheckHomography */
+    float* score_f;              /* rows: of CheckFundamental */
+    int32_t* best_h;             /* rows */
+    int32_t* best_f;             /* rows */
+    uint64_t* mask_h;            /* vbCurrentInliers of CheckHomography */
+    uint64_t* mask_f;            /* of CheckFundamental */
+    float* motion_R;             /* n x 8 x 9 */
+    float* motion_t;             /* n x 8 x 3 */
+    int32_t* motion_good;        /* n x 8: nGood */
+    float* motion_cos;           /* n x 8: vCosParallax[min(50, size - 1)] after the sort, -0 as +0; 0 when nGood == 0 */
+    float* motion_parallax;      /* n x 8 */
+    int32_t* motion_status;      /* n x 8: DRFE_INIT_MOTION_* */
+    uint8_t* motion_vbGood;      /* 8 per reference key: vbGood as CheckRT leaves it */
+    float* motion_vP3D;          /* 8 x 3 per reference key: vP3D as CheckRT leaves it (written for a point CheckRT counts, also one
+                                    with cosParallax >= 0.99998 whose vbGood stays false) */
+} drfe_init_out;
+/* On the host, no context. */
+int drfe_init_ransac_host(const drfe_init_problems* problems, drfe_init_out* out);
+/* The same on the device: the inputs staged with one copy, five launches, the results back with one copy; returns with the
+ * outputs written (`stream` NULL = the context's).  Same bits as the host entry. */
+int drfe_init_ransac_batch(drfe_ctx* ctx, const drfe_init_problems* problems, drfe_init_out* out, void* stream);
+/* Counters since the context was created: stats[0] batch calls, [1] solvers, [2] rows, [3] matches, [4] solvers that took the
+ * homography branch, [5] the fundamental branch, [6] solvers with ok, [7] solvers without a row. */
+int drfe_init_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

@@ -20,6 +20,8 @@
  *                                      table with Refine's results (host entry; PnPBatch: every solver of a call at once)
  *   Planar_SLAM::Sim3Solver / drfe::Sim3Batch  include/Sim3Solver.h:35-130 - the loop closer's Sim3 RANSAC as a walk over a
  *                                      finished hypothesis table (host entry; Sim3Batch: every solver of a call on the device)
+ *   Planar_SLAM::Initializer           include/Initializer.h         - monocular initialisation's H / F RANSAC and reconstruction
+ *                                      (the point-only Initialize; one device call, or the host entry)
  *   drfe::Line3DBatch                  src/Frame.cc:481-558          - Frame::isLineGood's mvDepthLine / mvLines3D for the
  *                                      frames of a batch (one device call; the host entry below the crossover)
  * With -DDRFE_WITH_OPENCV the container types are OpenCV's (cv::Mat, cv::KeyPoint, cv::line_descriptor::KeyLine);
@@ -2560,6 +2562,93 @@ private:
     std::vector<size_t> mvKeyPointIndices;
     size_t mNMatches;
     int mCursor = 0, mRefills = 0;
+};
+
+/* ---------------------------------------------------------------------------------------------------------------------------
+ * Initializer (include/Initializer.h, src/Initializer.cc) over drfe_init_ransac_host / drfe_init_ransac_batch: the reference's
+ * constructor (ReferenceFrame, sigma, iterations) and its point-only Initialize(CurrentFrame, vMatches12, R21, t21, vP3D,
+ * vbTriangulated).  One Initialize is one solver of one call; it goes to the device entry when a call of one solver reaches
+ * DRFE_INIT_DEVICE_FROM (not measured yet, so the constant is INT32_MAX), to the host entry otherwise (same
+ * bits); UseDevice() overrides the constant.  The device entry runs on the thread's bound context (ORBmatcher::BindThread) or on one the object
+ * makes on first use.  The reference seeds rand() with srand(0) once per process; here every Initialize draws from srand(seed)
+ * (SetSeed, default 0: a process's first Initialize).  FrameT: mK (CV_32F 3x3, continuous), mvKeysUn.  DESIGN.md section 19. */
+template <class FrameT>
+class Initializer {
+public:
+    Initializer(const FrameT& ReferenceFrame, float sigma = 1.0, int iterations = 200)
+        : mSigma(sigma), mMaxIterations(iterations), mUseDevice(1 >= DRFE_INIT_DEVICE_FROM)
+    {
+        std::memcpy(mK, reinterpret_cast<const float*>(ReferenceFrame.mK.data), sizeof(mK));
+        for (const auto& k : ReferenceFrame.mvKeysUn) { mKeys1.push_back(k.pt.x); mKeys1.push_back(k.pt.y); }
+    }
+    void SetSeed(uint32_t seed) { mSeed = seed; }
+    void UseDevice(bool on) { mUseDevice = on; }
+    /* what the last Initialize left besides its results: DRFE_INIT_BRANCH_*, DRFE_INIT_* flags, RH */
+    int Branch() const { return mBranch; }
+    int Flags() const { return mFlags; }
+    float RH() const { return mRH; }
+
+    template <class Point3T>
+    bool Initialize(const FrameT& CurrentFrame, const std::vector<int>& vMatches12, drfe_cv::Mat& R21, drfe_cv::Mat& t21,
+                    std::vector<Point3T>& vP3D, std::vector<bool>& vbTriangulated)
+    {
+        const int32_t n1 = (int32_t)(mKeys1.size() / 2), n2 = (int32_t)CurrentFrame.mvKeysUn.size();
+        if ((int32_t)vMatches12.size() > n1) throw std::invalid_argument("Initializer::Initialize: more matches than reference keys");
+        std::vector<float> keys2;
+        for (const auto& k : CurrentFrame.mvKeysUn) { keys2.push_back(k.pt.x); keys2.push_back(k.pt.y); }
+        std::vector<int32_t> m12((size_t)n1, -1);
+        for (size_t i = 0; i < vMatches12.size(); i++) m12[i] = vMatches12[i] >= 0 ? vMatches12[i] : -1;
+        const int32_t it = mMaxIterations > 0 ? mMaxIterations : 0, off1[2] = {0, n1}, off2[2] = {0, n2};
+        int N = 0;
+        for (int32_t m : m12) N += m >= 0;
+        const size_t rows = (size_t)it, words = rows * (size_t)((N + 63) / 64), k1 = (size_t)n1;
+        drfe_init_problems P = {1, 0, mK, &mSigma, &it, &mSeed, off1, off2, mKeys1.data(), keys2.data(), m12.data()};
+        int32_t sc[7] = {0};
+        float SH, SF, R[9], t[3], mcos[8], mpar[8], mR[72], mt[24];
+        int32_t mgood[8], mstatus[8];
+        std::vector<float> p3d(3 * k1 + 1), H(9 * rows + 1), F(9 * rows + 1), sh(rows + 1), sf(rows + 1), mp3d(24 * k1 + 1);
+        std::vector<uint8_t> tri(k1 + 1), mvb(8 * k1 + 1);
+        std::vector<int32_t> sample(8 * rows + 1), bh(rows + 1), bf(rows + 1);
+        std::vector<uint64_t> mh(words + 1), mf(words + 1);
+        drfe_init_out O = {&sc[0], &sc[1], &sc[2], &SH, &SF, &mRH, &sc[3], &sc[4], &sc[5], &sc[6], R, t, p3d.data(), tri.data(),
+                           sample.data(), H.data(), F.data(), sh.data(), sf.data(), bh.data(), bf.data(), mh.data(), mf.data(),
+                           mR, mt, mgood, mcos, mpar, mstatus, mvb.data(), mp3d.data()};
+        if (mUseDevice) {
+            drfe_ctx* c = drfe_detail::thread_ctx();
+            if (!c) {
+                if (!mCtx) mCtx = drfe_detail::make_ctx(1, 1.2f, 1, 20, 7, 64, 64, 1, 0);
+                c = mCtx.get();
+            }
+            drfe_detail::check(drfe_init_ransac_batch(c, &P, &O, nullptr), c, "drfe_init_ransac_batch");
+        } else if (drfe_init_ransac_host(&P, &O) != DRFE_OK)
+            throw std::runtime_error("drfe_init_ransac_host: invalid argument");
+        mBranch = sc[3];
+        mFlags = sc[6];
+        if (!sc[5]) {
+            /* ReconstructF empties R21 and t21 before it decides; ReconstructH leaves them */
+            if (mBranch == DRFE_INIT_BRANCH_F) { R21 = drfe_cv::Mat(); t21 = drfe_cv::Mat(); }
+            return false;
+        }
+        R21 = drfe::drfe_detail_sim3::mat32(3, 3, R);
+        t21 = drfe::drfe_detail_sim3::mat32(3, 1, t);
+        vP3D.resize(k1);
+        vbTriangulated.assign(k1, false);
+        for (size_t i = 0; i < k1; i++) {
+            vP3D[i].x = p3d[3 * i]; vP3D[i].y = p3d[3 * i + 1]; vP3D[i].z = p3d[3 * i + 2];
+            vbTriangulated[i] = tri[i] != 0;
+        }
+        return true;
+    }
+
+private:
+    float mK[9], mSigma;
+    int mMaxIterations;
+    uint32_t mSeed = 0;
+    bool mUseDevice;
+    int mBranch = 0, mFlags = 0;
+    float mRH = 0;
+    std::vector<float> mKeys1;
+    drfe_detail::CtxPtr mCtx;
 };
 
 }  // namespace Planar_SLAM

@@ -67,6 +67,19 @@ int drfe_debug_pnp_inliers(const double* R, const double* t, const float* K, con
 /* The same through the device's inlier sweep (pnp_kernels.hip's pnp_sweep, one wavefront; n <= DRFE_PNP_MAX_CORR): same bytes. */
 int drfe_debug_pnp_inliers_device(drfe_ctx* ctx, const double* R, const double* t, const float* K, const float* p2d, const float* Xw,
                                   const float* max_err, int n, uint8_t* out);
+/* Test hooks of the Initializer (dr_slam_amd/csrc/init_core.h).
+ * _cos_keys: key[i] = the unsigned key the accepted cosine c[i] is ordered by (-0 as +0, a NaN 0xFFFFFFFF, above every number),
+ * value[i] = the cosine that key stands for.  Host code.
+ * _null_vectors: for n samples of eight normalised matches (x1 y1 x2 y2 each, 32 floats a sample), h = vt.row(8) of ComputeH21's
+ * 16x9 system and fpre = vt.row(8) of ComputeF21's 8x9 system, 9 floats each, as the float Jacobi SVD leaves them.  Host code.
+ * _check_rt: CheckRT of one motion hypothesis R [9], t [3] under K [9] and sigma over n <= DRFE_INIT_MAX_KEYS matches (u1 v1 u2 v2
+ * each), every one an inlier, match i's reference key being i: nGood, the selected cosine, the parallax, the DRFE_INIT_MOTION_*
+ * status, vbGood [n] and vP3D [3 n].  ctx == NULL: the host entry's routine; otherwise the device's CheckRT kernel.  This is how
+ * tests reach a point triangulated onto the first camera's centre, whose cosine is 0 / 0. */
+int drfe_debug_init_cos_keys(const float* c, int n, uint32_t* key, float* value);
+int drfe_debug_init_null_vectors(const float* points, int n, float* h, float* fpre);
+int drfe_debug_init_check_rt(drfe_ctx* ctx, const float* K, const float* R, const float* t, float sigma, const float* matches, int n,
+                             int32_t* good, float* cos_selected, float* parallax, int32_t* status, uint8_t* vbGood, float* vP3D);
 
 #ifdef __cplusplus
 }

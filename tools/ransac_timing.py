@@ -1,11 +1,13 @@
-"""Per-call time of a device RANSAC (drfe_sim3_ransac_batch, drfe_pnp_ransac_batch) next to its host entry (drfe_*_ransac_host, one
-CPU thread) on the same planted scenes, 30 % outliers: 1, 4, 16, 64 and 512 solvers,
+"""Per-call time of a device RANSAC (drfe_sim3_ransac_batch, drfe_pnp_ransac_batch, drfe_init_ransac_batch) next to its host entry
+(drfe_*_ransac_host, one CPU thread) on the same planted scenes, 30 % outliers (init: 20 %): 1, 4, 16, 64 and 512 solvers,
   --solver sim3  of 100 and of 1 000 correspondences (tests/sim3_numpy.py: min_inliers 20, 300 iterations each),
-  --solver pnp   of 30, 100 and 1 000 (tests/pnp_numpy.py: SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991), tail 5).
+  --solver pnp   of 30, 100 and 1 000 (tests/pnp_numpy.py: SetRansacParameters(0.99, 10, 300, 4, 0.5, 5.991), tail 5),
+  --solver init  of 100, 300 and 1 000 matches (tests/initializer_numpy.py: sigma 1.0, 200 iterations, general and planar scenes
+                 in turn, a tenth more keys than matches in each frame).
 The clock is around the C entry alone (the records are packed once, outside it); the device call returns with the table in host
 memory, so wall time is its cost, staging and both copies included.  Every timed shape is called once before it is timed, and a
 configuration is repeated until at least --seconds have been timed.  Device == host is checked.  Prints one JSON line per
-configuration and writes them to --out (profiles/<solver>_timing.jsonl)."""
+configuration and writes them to --out (profiles/sim3_timing.jsonl, profiles/pnp_timing.jsonl, profiles/initializer_timing.jsonl)."""
 import argparse
 import ctypes as C
 import json
@@ -30,11 +32,18 @@ def pnp_scene(pn, rng, N, i):
                             outlier_frac=0.3, noise=0.3)[0]
 
 
+def init_scene(sn, rng, N, i):
+    return sn.planted(rng, N, planar=bool(i & 1) and sn.PLANAR["planar"], baseline=sn.PLANAR["baseline"] if i & 1 else 0.35,
+                      extra1=N // 10, extra2=N // 10, max_iterations=200, seed=i)
+
+
 # module of scenes, correspondences per solver, scene, the row's fields after `correspondences` from the host table
 SOLVERS = {
     "sim3": ("sim3_numpy", (100, 1000), sim3_scene, lambda t: dict(iterations=300, hypotheses=int(t["hypotheses"].sum()))),
     "pnp": ("pnp_numpy", (30, 100, 1000), pnp_scene,
             lambda t: dict(hypotheses=int(t["hypotheses"].sum()), refines=int(t["refines"].sum()))),
+    "init": ("initializer_numpy", (100, 300, 1000), init_scene,
+             lambda t: dict(hypotheses=int(t["hypotheses"].sum()), branch_h=int((t["branch"] == 1).sum()), ok=int(t["ok"].sum()))),
 }
 
 
@@ -57,7 +66,7 @@ def main():
     ap.add_argument("--out")
     args = ap.parse_args()
     name = args.solver
-    out = args.out or os.path.join(ROOT, "profiles", name + "_timing.jsonl")
+    out = args.out or os.path.join(ROOT, "profiles", ("initializer" if name == "init" else name) + "_timing.jsonl")
     module, sizes, scene, extra = SOLVERS[name]
     sn = __import__(module)
     from dr_slam_amd import lib
