@@ -8,6 +8,7 @@
 #include "pnp_internal.h"
 #include "init_internal.h"
 #include "line3d_internal.h"
+#include "pose_opt_internal.h"
 #include <atomic>
 #include "post_internal.h"
 #include "match_internal.h"
@@ -158,6 +159,7 @@ void drfe_destroy(drfe_ctx* c)
     drfe_pnp_free(c);
     drfe_init_free(c);
     drfe_line3d_free(c);
+    drfe_pose_opt_free(c);
     drfe_post_free(c);
     drfe_one_shot_free(c);
     drfe_frame_lanes_free(c);

@@ -190,6 +190,7 @@ struct drfe_ctx {
     struct Sim3Buffers* sim3 = nullptr; /* Sim3 RANSAC staging, scratch and counters (sim3.cpp) */
     struct PnpBuffers* pnp = nullptr;   /* PnP RANSAC staging, scratch and counters (pnp.cpp) */
     struct InitBuffers* init = nullptr; /* Initializer RANSAC staging, scratch and counters (init.cpp) */
+    struct PoseOptBuffers* pose_opt = nullptr; /* PoseOptimization staging, scratch and counters (pose_opt.cpp) */
     struct Line3dBuffers* line3d = nullptr;   /* isLineGood batch staging, scratch and counters (lines_3d_batch.cpp) */
     std::vector<struct LineWorker>* lineWorkers;   /* lanes of drfe_lsd_extract_batch (lines_lsd.cpp) */
     struct LinesScratch* lsBatch; /* frame slots of drfe_lsd_extract_batch's device region growing (lines_lsd.cpp) */

@@ -16,14 +16,12 @@
  *   coefficient / sqrt(z)); the Isometry3d cast sets linear = q.toRotationMatrix(), translation = t; inverse() of an isometry
  *   is linear^T and (-linear^T) * t.
  * Eigen leaves the association of the trace, the 4-term squaredNorm and the 3-term products open: they are read left to right
- * here (canonical, as DESIGN.md section 9 does for Eigen's reductions).  -(a * t0) - ... equals -(a * t0 + ...) exactly. */
-DRFE_HD void mp_pose_update(const float Tcw[16], double T[16])
+ * here (canonical, as DESIGN.md section 9 does for Eigen's reductions).  -(a * t0) - ... equals -(a * t0 + ...) exactly.
+ * The quaternion pieces stand alone because pose_opt_core.h runs the same ones. */
+
+/* Eigen 3.3.7's Quaterniond(Matrix3d) (quaternion_assign_impl<3, 3>): q is x y z w, Eigen's coeffs() order */
+DRFE_HD void mp_quat_from_matrix(const double m[3][3], double q[4])
 {
-    double m[3][3];
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) m[r][c] = (double)Tcw[r * 4 + c];
-    const double t0 = (double)Tcw[3], t1 = (double)Tcw[7], t2 = (double)Tcw[11];
-    double q[4];                                  /* x y z w, Eigen's coeffs() order */
     double tr = m[0][0] + m[1][1] + m[2][2];
     if (tr > 0.0) {
         tr = sqrt(tr + 1.0);
@@ -44,6 +42,11 @@ DRFE_HD void mp_pose_update(const float Tcw[16], double T[16])
         q[j] = (m[j][i] + m[i][j]) * tr;
         q[k] = (m[k][i] + m[i][k]) * tr;
     }
+}
+
+/* g2o::SE3Quat::normalizeRotation: the four coefficients negated when w < 0, then Quaternion::normalize */
+DRFE_HD void mp_quat_normalize_rotation(double q[4])
+{
     if (q[3] < 0.0)
         for (int c = 0; c < 4; c++) q[c] = -q[c];
     const double z = q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3];
@@ -51,14 +54,37 @@ DRFE_HD void mp_pose_update(const float Tcw[16], double T[16])
         const double s = sqrt(z);
         for (int c = 0; c < 4; c++) q[c] = q[c] / s;
     }
-    /* Quaternion::toRotationMatrix */
+}
+
+/* Quaternion::toRotationMatrix */
+DRFE_HD void mp_quat_to_matrix(const double q[4], double R[3][3])
+{
     const double tx = 2.0 * q[0], ty = 2.0 * q[1], tz = 2.0 * q[2];
     const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
     const double txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
     const double tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    const double R[3][3] = {{1.0 - (tyy + tzz), txy - twz, txz + twy},
-                            {txy + twz, 1.0 - (txx + tzz), tyz - twx},
-                            {txz - twy, tyz + twx, 1.0 - (txx + tyy)}};
+    R[0][0] = 1.0 - (tyy + tzz); R[0][1] = txy - twz; R[0][2] = txz + twy;
+    R[1][0] = txy + twz; R[1][1] = 1.0 - (txx + tzz); R[1][2] = tyz - twx;
+    R[2][0] = txz - twy; R[2][1] = tyz + twx; R[2][2] = 1.0 - (txx + tyy);
+}
+
+/* Converter::toSE3Quat(Tcw): the quaternion (x y z w) and translation of g2o::SE3Quat(R, t) over the widened float pose */
+DRFE_HD void mp_to_se3quat(const float Tcw[16], double q[4], double t[3])
+{
+    double m[3][3];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) m[r][c] = (double)Tcw[r * 4 + c];
+    t[0] = (double)Tcw[3]; t[1] = (double)Tcw[7]; t[2] = (double)Tcw[11];
+    mp_quat_from_matrix(m, q);
+    mp_quat_normalize_rotation(q);
+}
+
+DRFE_HD void mp_pose_update(const float Tcw[16], double T[16])
+{
+    double q[4], t[3], R[3][3];                   /* x y z w, Eigen's coeffs() order */
+    mp_to_se3quat(Tcw, q, t);
+    mp_quat_to_matrix(q, R);
+    const double t0 = t[0], t1 = t[1], t2 = t[2];
     /* inverse: R^T and -(R^T t) */
     for (int r = 0; r < 3; r++) {
         for (int c = 0; c < 3; c++) T[r * 4 + c] = R[c][r];

@@ -56,6 +56,8 @@ SYMBOLS = (
     "drfe_debug_init_cos_keys", "drfe_debug_init_null_vectors", "drfe_debug_init_check_rt",
     "drfe_pnp_ransac_host", "drfe_pnp_ransac_batch", "drfe_pnp_stats", "drfe_debug_pnp_svd", "drfe_debug_pnp_inliers", "drfe_debug_pnp_inliers_device",
     "drfe_lines_is_good_batch", "drfe_line3d_chunk_frames", "drfe_line3d_stats",
+    "drfe_pose_opt_host", "drfe_pose_opt_batch", "drfe_pose_opt_stats", "drfe_debug_cr_cube", "drfe_debug_pose_opt_ldlt",
+    "drfe_debug_pose_opt_hand_back", "drfe_debug_pose_opt_plane_error",
 )
 
 FRUSTUM_POINT_DTYPE = np.dtype([("world", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"),
@@ -183,6 +185,26 @@ PNP_OUT_FIELDS = ("iterations", "min_inliers", "hypotheses", "refines", "sample"
 
 class PnpOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in PNP_OUT_FIELDS]                             # drfe_pnp_out
+
+
+class PoseOptProblems(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "Tcw", "K", "bf", "b_struct", "point_offsets", "obs", "u_right", "inv_sigma2", "Xw", "line_offsets", "line_fn",
+        "line_ends", "plane_offsets", "plane_meas", "plane_world", "plane_mask")] + [
+        ("plane_settings", C.c_double * 7)]                                          # drfe_pose_opt_problems
+
+
+POSE_OPT_OUT_FIELDS = ("Tcw", "returns", "rounds", "iterations", "trials", "diag", "point_outlier", "line_outlier", "plane_outlier",
+                       "par_plane_outlier", "ver_plane_outlier")
+POSE_OPT_DIAG = ("rejected", "last_rejected", "nbad_stops", "small_theta", "big_theta", "empty_rounds")
+POSE_OPT_MAX_FRAMES, POSE_OPT_MAX_POINTS, POSE_OPT_MAX_LINES, POSE_OPT_MAX_PLANES = 4096, 8192, 1024, 64
+POSE_OPT_PLANE_MATCHED, POSE_OPT_PLANE_PARALLEL, POSE_OPT_PLANE_VERTICAL = 1, 2, 4
+POSEOPT_DEVICE_FROM = 64
+POSE_OPT_STATS = ("calls", "frames", "point_edges", "line_plane_edges", "iterations", "trials", "handed_back", "frames_too_few")
+
+
+class PoseOptOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in POSE_OPT_OUT_FIELDS]                        # drfe_pose_opt_out
 
 
 class InitProblems(C.Structure):
@@ -394,6 +416,13 @@ def load() -> C.CDLL:
     L.drfe_debug_init_null_vectors.argtypes = [vp, i32, vp, vp]
     L.drfe_debug_init_check_rt.argtypes = [vp, vp, vp, vp, C.c_float, vp, i32, vp, vp, vp, vp, vp, vp]
     L.drfe_pnp_ransac_batch.argtypes = [vp, vp, vp, vp]
+    L.drfe_pose_opt_host.argtypes = [vp, vp]
+    L.drfe_pose_opt_batch.argtypes = [vp, vp, vp, vp]
+    L.drfe_pose_opt_stats.argtypes = [vp, vp]
+    L.drfe_debug_cr_cube.argtypes = [vp, i32, vp, vp]
+    L.drfe_debug_pose_opt_ldlt.argtypes = [vp, vp, vp, vp]
+    L.drfe_debug_pose_opt_hand_back.argtypes = [vp, i32]
+    L.drfe_debug_pose_opt_plane_error.argtypes = [i32, vp, vp, vp, vp]
     L.drfe_pnp_stats.argtypes = [vp, vp]
     L.drfe_lines_is_good_batch.argtypes = [vp, vp, vp, vp]
     L.drfe_line3d_chunk_frames.argtypes = [i32]
@@ -867,6 +896,80 @@ def pnp_table(result, s):
     for k in ("iterations", "min_inliers", "refines"):
         t[k] = int(result[k][s])
     return t
+
+
+def _pose_opt_pack(problems):
+    """Packs a set of frames (dict: Tcw [n, 16], K [n, 4] (fx, fy, cx, cy), bf [n], b_struct [n], point_offsets [n + 1], obs [P, 2],
+    u_right [P], inv_sigma2 [P], Xw [P, 3], line_offsets [n + 1], line_fn [L, 3], line_ends [L, 6]; optional plane_offsets [n + 1],
+    plane_meas [S, 4], plane_world [S, 12], plane_mask [S], plane_settings [7]) into drfe_pose_opt_problems and allocates the
+    outputs: (problems record, out record, the outputs as a dict, the arrays to keep alive).  The outputs: per frame Tcw [16],
+    returns, rounds, iterations, trials, diag [8] (POSE_OPT_DIAG names the first six); per point, line and plane slot the outlier
+    flags."""
+    keep = []
+
+    def arr(key, dt, shape=-1, default=None):
+        v = np.asarray(problems.get(key, default), dt)
+        v = np.ascontiguousarray(v.reshape(shape) if v.size else np.zeros((0,) + (shape[1:] if isinstance(shape, tuple) else ()), dt))
+        keep.append(v)
+        return v
+    poff = arr("point_offsets", np.int32)
+    n = len(poff) - 1
+    loff = arr("line_offsets", np.int32, default=np.zeros(n + 1, np.int32))
+    soff = arr("plane_offsets", np.int32, default=np.zeros(n + 1, np.int32))
+    nP, nL, nS = (max(int(o[-1]), 0) if len(o) else 0 for o in (poff, loff, soff))
+    z = np.zeros(0)
+    P = PoseOptProblems(n, 0, _p(arr("Tcw", np.float32, (-1, 16))), _p(arr("K", np.float32, (-1, 4))), _p(arr("bf", np.float32)),
+                        _p(arr("b_struct", np.uint8, default=np.zeros(n, np.uint8))), _p(poff),
+                        _p(arr("obs", np.float32, (-1, 2), z)), _p(arr("u_right", np.float32, -1, z)),
+                        _p(arr("inv_sigma2", np.float32, -1, z)), _p(arr("Xw", np.float32, (-1, 3), z)), _p(loff),
+                        _p(arr("line_fn", np.float64, (-1, 3), z)), _p(arr("line_ends", np.float64, (-1, 6), z)), _p(soff),
+                        _p(arr("plane_meas", np.float32, (-1, 4), z)), _p(arr("plane_world", np.float32, (-1, 12), z)),
+                        _p(arr("plane_mask", np.uint8, -1, z)),
+                        (C.c_double * 7)(*np.asarray(problems.get("plane_settings", np.zeros(7)), np.float64).tolist()))
+    r = dict(Tcw=np.zeros((n, 16), np.float32), returns=np.zeros(n, np.int32), rounds=np.zeros(n, np.int32),
+             iterations=np.zeros(n, np.int32), trials=np.zeros(n, np.int32), diag=np.zeros((n, 8), np.int32),
+             point_outlier=np.zeros(nP, np.uint8), line_outlier=np.zeros(nL, np.uint8), plane_outlier=np.zeros(nS, np.uint8),
+             par_plane_outlier=np.zeros(nS, np.uint8), ver_plane_outlier=np.zeros(nS, np.uint8))
+    out = PoseOptOut(*[_p(r[k]) for k in POSE_OPT_OUT_FIELDS])
+    return P, out, r, keep
+
+
+def pose_opt_host(problems):
+    """Optimizer::PoseOptimization of every frame on the host (drfe_pose_opt_host, DESIGN.md section 20); problems and result as
+    _pose_opt_pack"""
+    P, out, r, _keep = _pose_opt_pack(problems)
+    rc = load().drfe_pose_opt_host(C.byref(P), C.byref(out))
+    if rc != 0:
+        raise DrfeError(f"drfe_pose_opt_host failed ({rc})")
+    return r
+
+
+def cr_cube(x):
+    """cr_cube.h's correctly rounded x^3: (values [n], certified [n])"""
+    x = np.ascontiguousarray(np.asarray(x, np.float64).reshape(-1))
+    out, ok = np.zeros(len(x), np.float64), np.zeros(len(x), np.uint8)
+    if load().drfe_debug_cr_cube(_p(x), len(x), _p(out), _p(ok)) != 0:
+        raise DrfeError("drfe_debug_cr_cube failed")
+    return out, ok.astype(bool)
+
+
+def pose_opt_plane_error(kind, meas, world, Tcw):
+    """pose_opt_core.h's computeError of one plane edge (kind 3 matched, 4 parallel, 5 vertical) under the float pose Tcw: e [3]"""
+    meas, world, Tcw = (np.ascontiguousarray(np.asarray(v, np.float32).reshape(-1)) for v in (meas, world, Tcw))
+    e = np.zeros(3, np.float64)
+    if load().drfe_debug_pose_opt_plane_error(int(kind), _p(meas), _p(world), _p(Tcw), _p(e)) != 0:
+        raise DrfeError("drfe_debug_pose_opt_plane_error failed")
+    return e
+
+
+def pose_opt_ldlt(A, b):
+    """pose_opt_core.h's Eigen::LDLT of the symmetric 6x6 A (its lower triangle) and solve of A x = b: (isPositive, x)"""
+    A = np.ascontiguousarray(np.asarray(A, np.float64).reshape(6, 6))
+    b = np.ascontiguousarray(np.asarray(b, np.float64).reshape(6))
+    x, pos = np.zeros(6, np.float64), np.zeros(1, np.int32)
+    if load().drfe_debug_pose_opt_ldlt(_p(A), _p(b), _p(x), _p(pos)) != 0:
+        raise DrfeError("drfe_debug_pose_opt_ldlt failed")
+    return bool(pos[0]), x
 
 
 def _init_pack(problems):
@@ -2188,6 +2291,22 @@ class Context:
         rc, r = _pnp_call(self.L.drfe_pnp_ransac_batch, (self.h,), problems)
         self._chk(rc, "drfe_pnp_ransac_batch")
         return r
+
+    def pose_opt_batch(self, problems):
+        """pose_opt_host on the device (drfe_pose_opt_batch): same outputs, same bits"""
+        P, out, r, _keep = _pose_opt_pack(problems)
+        self._chk(self.L.drfe_pose_opt_batch(self.h, C.byref(P), C.byref(out), None), "drfe_pose_opt_batch")
+        return r
+
+    def pose_opt_stats(self):
+        """drfe_pose_opt_stats as a dict over POSE_OPT_STATS"""
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_pose_opt_stats(self.h, _p(st)), "drfe_pose_opt_stats")
+        return dict(zip(POSE_OPT_STATS, st.tolist()))
+
+    def pose_opt_hand_back(self, every):
+        """test hook: the host runs every `every`-th frame of a batch call again as if the device had not certified it"""
+        self._chk(self.L.drfe_debug_pose_opt_hand_back(self.h, int(every)), "drfe_debug_pose_opt_hand_back")
 
     def init_ransac_batch(self, problems):
         """init_ransac_host on the device (drfe_init_ransac_batch): same outputs, same bits"""

@@ -1338,6 +1338,70 @@ int drfe_init_ransac_batch(drfe_ctx* ctx, const drfe_init_problems* problems, dr
  * homography branch, [5] the fundamental branch, [6] solvers with ok, [7] solvers without a row. */
 int drfe_init_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
 
+/* Optimizer::PoseOptimization(Frame*, bool bStruct) (src/Optimizer.cc:601-1338), the motion-only optimisation between two
+ * matchers of every Track* function and after PnP in Relocalization: every frame of a call at once.  DESIGN.md section 20.
+ *
+ * A frame is its pose mTcw, its intrinsics, mbf, and its matched features compacted in index order: the key points with a map
+ * point (uRight < 0: monocular edge, else stereo), the key lines with a map line (two edges, start then end), the plane slots.
+ * The four rounds of Levenberg-Marquardt, the classification after each, and what g2o and Eigen run under them are restated;
+ * parity with a g2o / Eigen 3.3.7 build is not pinned yet.
+ * A plane slot is a detected plane of the frame with up to three map planes: the matched one (EdgePlaneOnlyPose) and, read only
+ * with bStruct, a parallel and a vertical one (EdgeParallelPlaneOnlyPose, EdgeVerticalPlaneOnlyPose).
+ * Caps: DRFE_POSE_OPT_MAX_FRAMES frames per call, DRFE_POSE_OPT_MAX_POINTS points, DRFE_POSE_OPT_MAX_LINES lines and
+ * DRFE_POSE_OPT_MAX_PLANES plane slots per frame; above them the call is refused (DRFE_ERR_INVALID), as are decreasing offsets. */
+enum { DRFE_POSE_OPT_MAX_FRAMES = 4096, DRFE_POSE_OPT_MAX_POINTS = 8192, DRFE_POSE_OPT_MAX_LINES = 1024,
+       DRFE_POSE_OPT_MAX_PLANES = 64 };
+/* frames in a call from which drfe::PoseOptBatch uses the device entry (the measured crossover) */
+enum { DRFE_POSEOPT_DEVICE_FROM = 64 };
+/* plane_mask[slot] */
+enum { DRFE_POSE_OPT_PLANE_MATCHED = 1, DRFE_POSE_OPT_PLANE_PARALLEL = 2, DRFE_POSE_OPT_PLANE_VERTICAL = 4 };
+typedef struct drfe_pose_opt_problems {
+    int32_t n;                   /* frames */
+    int32_t pad;
+    const float* Tcw;            /* n x 16: pFrame->mTcw, row-major */
+    const float* K;              /* n x 4: fx, fy, cx, cy */
+    const float* bf;             /* n: mbf */
+    const uint8_t* b_struct;     /* n: bStruct */
+    const int32_t* point_offsets; /* n + 1: frame f's points are [point_offsets[f], point_offsets[f + 1]); [0] == 0 */
+    const float* obs;            /* 2 per point: mvKeysUn[i].pt */
+    const float* u_right;        /* per point: mvuRight[i]; below 0 the point is monocular */
+    const float* inv_sigma2;     /* per point: mvInvLevelSigma2[kpUn.octave] */
+    const float* Xw;             /* 3 per point: pMP->GetWorldPos() */
+    const int32_t* line_offsets; /* n + 1 */
+    const double* line_fn;       /* 3 per line: mvKeyLineFunctions[i] */
+    const double* line_ends;     /* 6 per line: pML->mWorldPos, start then end */
+    const int32_t* plane_offsets; /* n + 1 */
+    const float* plane_meas;     /* 4 per slot: mvPlaneCoefficients[i] */
+    const float* plane_world;    /* 12 per slot: GetWorldPos() of the matched, the parallel and the vertical map plane */
+    const uint8_t* plane_mask;   /* per slot: DRFE_POSE_OPT_PLANE_* of the map planes present */
+    double plane_settings[7];    /* Plane.AngleInfo, DistanceInfo, ParallelInfo, VerticalInfo, Chi, VPChi, reserved (0) */
+} drfe_pose_opt_problems;
+/* The three offset tables are required; an array may be NULL when no frame has an element of it.  diag may be NULL. */
+typedef struct drfe_pose_opt_out {
+    float* Tcw;                  /* n x 16: the pose SetPose receives; the input pose when the call returns 0 before the loop */
+    int32_t* returns;            /* n: nInitialCorrespondences - nBad, or 0 with fewer than 3 correspondences */
+    int32_t* rounds;             /* n: rounds of the outer loop run (0 .. 4) */
+    int32_t* iterations;         /* n: Levenberg iterations over all rounds */
+    int32_t* trials;             /* n: trial steps (linear solves) over all rounds */
+    int32_t* diag;               /* n x 8: [0] rejected trials, [1] rounds whose last trial was rejected, [2] rounds stopped by
+                                    _nBad >= 3, [3] updates with theta < 1e-5, [4] with theta >= 1e-5, [5] rounds without an
+                                    active edge, [6] [7] 0 */
+    uint8_t* point_outlier;      /* per point: mvbOutlier */
+    uint8_t* line_outlier;       /* per line: mvbLineOutlier */
+    uint8_t* plane_outlier;      /* per slot: mvbPlaneOutlier */
+    uint8_t* par_plane_outlier;  /* per slot: mvbParPlaneOutlier */
+    uint8_t* ver_plane_outlier;  /* per slot: mvbVerPlaneOutlier */
+} drfe_pose_opt_out;
+/* On the host, no context. */
+int drfe_pose_opt_host(const drfe_pose_opt_problems* problems, drfe_pose_opt_out* out);
+/* The same on the device: the inputs staged with one copy, one launch (a workgroup per frame runs its four rounds), the results
+ * back with one copy; returns with the outputs written (`stream` NULL = the context's).  Same bits as the host entry. */
+int drfe_pose_opt_batch(drfe_ctx* ctx, const drfe_pose_opt_problems* problems, drfe_pose_opt_out* out, void* stream);
+/* Counters since the context was created: stats[0] batch calls, [1] frames, [2] point edges, [3] line and plane edges, [4] Levenberg
+ * iterations, [5] trial steps, [6] frames the device could not certify (sin / cos, atan2, x^3) and the host finished, [7] frames that
+ * returned before the loop (fewer than 3 correspondences). */
+int drfe_pose_opt_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

@@ -2760,4 +2760,185 @@ private:
 
 }  // namespace drfe
 
+namespace drfe {
+
+/* Optimizer::PoseOptimization (src/Optimizer.cc:601-1338) for one frame or for the frames of a batch (Relocalization's candidates,
+ * the frames of a batched tracker): Add() flattens what the reference reads of a frame, Run() optimises every added frame by one
+ * drfe_pose_opt_batch call (or, below `deviceFrom` frames, by the host entry: same bits) and writes back what the reference
+ * writes: SetPose(Tcw), mvbOutlier, mvbLineOutlier, mvbPlaneOutlier, mvbParPlaneOutlier, mvbVerPlaneOutlier (only the entries of
+ * matched features, as the reference).  Result(i) is the i-th added frame's return value.  An object belongs to one thread.  The plane settings are the reference's
+ * Config values (Plane.AngleInfo, DistanceInfo, ParallelInfo, VerticalInfo, Chi, VPChi).  DESIGN.md section 20.
+ * FrameT: mTcw (4x4 float), fx fy cx cy mbf, N, mvKeysUn, mvuRight, mvInvLevelSigma2, mvpMapPoints, mvbOutlier, NL,
+ * mvKeyLineFunctions (three doubles through operator()), mvpMapLines, mvbLineOutlier, mnPlaneNum, mvPlaneCoefficients,
+ * mvpMapPlanes, mvpParallelPlanes, mvpVerticalPlanes, mvbPlaneOutlier, mvbParPlaneOutlier, mvbVerPlaneOutlier, SetPose(Mat).
+ * MapPoint / MapPlane: GetWorldPos() (3x1 / 4x1 float); MapLine: mWorldPos (six doubles through operator()). */
+struct PlaneSettings { double angleInfo = 0.5, distanceInfo = 50, parallelInfo = 0.1, verticalInfo = 0.1, chi = 100, vpChi = 50; };
+
+template <class FrameT>
+class PoseOptBatch {
+public:
+    explicit PoseOptBatch(const PlaneSettings& settings = PlaneSettings(), int device = 0, int deviceFrom = DRFE_POSEOPT_DEVICE_FROM)
+        : mSettings(settings), mDevice(device), mDeviceFrom(deviceFrom) { Clear(); }
+    /* true / false: the device / the host entry whatever the number of frames */
+    void UseDevice(bool on) { mDeviceFrom = on ? 0 : 2147483647; }
+    void SetSettings(const PlaneSettings& s) { mSettings = s; }
+    void Clear()
+    {
+        mFrames.clear(); mStruct.clear(); mTcw.clear(); mK.clear(); mBf.clear();
+        mObs.clear(); mUr.clear(); mInvSigma2.clear(); mXw.clear(); mPointIdx.clear();
+        mLineFn.clear(); mLineEnds.clear(); mLineIdx.clear();
+        mPlaneMeas.clear(); mPlaneWorld.clear(); mPlaneMask.clear();
+        mPointOff.assign(1, 0); mLineOff.assign(1, 0); mPlaneOff.assign(1, 0);
+        mReturns.clear();
+    }
+    size_t size() const { return mFrames.size(); }
+    void Add(FrameT* pFrame, bool bStruct)
+    {
+        using Planar_SLAM::drfe_detail::mat_f;
+        FrameT& F = *pFrame;
+        mFrames.push_back(pFrame);
+        mStruct.push_back(bStruct ? 1 : 0);
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++) mTcw.push_back(mat_f(F.mTcw, r, c));
+        mK.push_back(F.fx); mK.push_back(F.fy); mK.push_back(F.cx); mK.push_back(F.cy);
+        mBf.push_back(F.mbf);
+        for (int i = 0; i < F.N; i++) {
+            auto* pMP = F.mvpMapPoints[(size_t)i];
+            if (!pMP) continue;
+            const auto& kp = F.mvKeysUn[(size_t)i];
+            mObs.push_back(kp.pt.x); mObs.push_back(kp.pt.y);
+            mUr.push_back(F.mvuRight[(size_t)i]);
+            mInvSigma2.push_back(F.mvInvLevelSigma2[(size_t)kp.octave]);
+            const auto Xw = pMP->GetWorldPos();
+            for (int k = 0; k < 3; k++) mXw.push_back(mat_f(Xw, k));
+            mPointIdx.push_back(i);
+        }
+        mPointOff.push_back((int32_t)mPointIdx.size());
+        for (int i = 0; i < F.NL; i++) {
+            auto* pML = F.mvpMapLines[(size_t)i];
+            if (!pML) continue;
+            for (int k = 0; k < 3; k++) mLineFn.push_back(F.mvKeyLineFunctions[(size_t)i](k));
+            for (int k = 0; k < 6; k++) mLineEnds.push_back(pML->mWorldPos(k));
+            mLineIdx.push_back(i);
+        }
+        mLineOff.push_back((int32_t)mLineIdx.size());
+        for (int i = 0; i < F.mnPlaneNum; i++) {           /* every detected plane is a slot; an empty one has mask 0 */
+            uint8_t mask = 0;
+            float world[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+            auto put = [&](decltype(F.mvpMapPlanes[0]) pMP, int which) {
+                if (!pMP) return;
+                const auto W = pMP->GetWorldPos();
+                for (int k = 0; k < 4; k++) world[4 * which + k] = mat_f(W, k);
+                mask |= (uint8_t)(1 << which);
+            };
+            put(F.mvpMapPlanes[(size_t)i], 0);
+            put(F.mvpParallelPlanes[(size_t)i], 1);
+            put(F.mvpVerticalPlanes[(size_t)i], 2);
+            for (int k = 0; k < 4; k++) mPlaneMeas.push_back(mat_f(F.mvPlaneCoefficients[(size_t)i], k));
+            mPlaneWorld.insert(mPlaneWorld.end(), world, world + 12);
+            mPlaneMask.push_back(mask);
+        }
+        mPlaneOff.push_back((int32_t)mPlaneMask.size());
+    }
+    /* optimises every added frame and writes the frames back; the batch is empty afterwards but for Result() */
+    void Run()
+    {
+        const size_t n = mFrames.size();
+        std::vector<float> Tcw(16 * n);
+        std::vector<int32_t> rounds(n), its(n), trials(n);
+        std::vector<uint8_t> po(mPointIdx.size() + 1), lo(mLineIdx.size() + 1), pl(mPlaneMask.size() + 1), pp(mPlaneMask.size() + 1),
+            pv(mPlaneMask.size() + 1);
+        mReturns.assign(n, 0);
+        drfe_pose_opt_problems in = {};
+        in.n = (int32_t)n;
+        in.Tcw = mTcw.data(); in.K = mK.data(); in.bf = mBf.data(); in.b_struct = mStruct.data();
+        in.point_offsets = mPointOff.data(); in.obs = mObs.data(); in.u_right = mUr.data(); in.inv_sigma2 = mInvSigma2.data();
+        in.Xw = mXw.data();
+        in.line_offsets = mLineOff.data(); in.line_fn = mLineFn.data(); in.line_ends = mLineEnds.data();
+        in.plane_offsets = mPlaneOff.data(); in.plane_meas = mPlaneMeas.data(); in.plane_world = mPlaneWorld.data();
+        in.plane_mask = mPlaneMask.data();
+        const double st[7] = {mSettings.angleInfo, mSettings.distanceInfo, mSettings.parallelInfo, mSettings.verticalInfo, mSettings.chi,
+                              mSettings.vpChi, 0.0};
+        std::memcpy(in.plane_settings, st, sizeof(st));
+        drfe_pose_opt_out out = {Tcw.data(), mReturns.data(), rounds.data(), its.data(), trials.data(), nullptr,
+                                 po.data(), lo.data(), pl.data(), pp.data(), pv.data()};
+        struct ClearOnExit {                           /* also when an entry refuses the call: the batch never keeps stale frames */
+            PoseOptBatch* b; std::vector<int32_t>* ret;
+            ~ClearOnExit() { std::vector<int32_t> r; r.swap(*ret); b->Clear(); b->mReturns.swap(r); }
+        } clearOnExit{this, &mReturns};
+        if (n) {
+            if ((int64_t)n < (int64_t)mDeviceFrom) {
+                if (drfe_pose_opt_host(&in, &out) != DRFE_OK) { mReturns.clear(); throw std::runtime_error("drfe_pose_opt_host: invalid argument"); }
+            } else {
+                if (!mCtx) mCtx = Planar_SLAM::drfe_detail::make_ctx(1, 1.2f, 1, 20, 7, 64, 64, 1, mDevice);
+                Planar_SLAM::drfe_detail::check(drfe_pose_opt_batch(mCtx.get(), &in, &out, nullptr), mCtx.get(), "drfe_pose_opt_batch");
+            }
+        }
+        for (size_t f = 0; f < n; f++) {
+            FrameT& F = *mFrames[f];
+            for (int32_t k = mPointOff[f]; k < mPointOff[f + 1]; k++) F.mvbOutlier[(size_t)mPointIdx[(size_t)k]] = po[(size_t)k] != 0;
+            for (int32_t k = mLineOff[f]; k < mLineOff[f + 1]; k++) F.mvbLineOutlier[(size_t)mLineIdx[(size_t)k]] = lo[(size_t)k] != 0;
+            for (int32_t k = mPlaneOff[f]; k < mPlaneOff[f + 1]; k++) {
+                const size_t i = (size_t)(k - mPlaneOff[f]);
+                const uint8_t m = mPlaneMask[(size_t)k];
+                if (m & DRFE_POSE_OPT_PLANE_MATCHED) F.mvbPlaneOutlier[i] = pl[(size_t)k] != 0;
+                if (mStruct[f] && (m & DRFE_POSE_OPT_PLANE_PARALLEL)) F.mvbParPlaneOutlier[i] = pp[(size_t)k] != 0;
+                if (mStruct[f] && (m & DRFE_POSE_OPT_PLANE_VERTICAL)) F.mvbVerPlaneOutlier[i] = pv[(size_t)k] != 0;
+            }
+            const int nInitial = (mPointOff[f + 1] - mPointOff[f]) + (mLineOff[f + 1] - mLineOff[f]) + PlaneEdges(f);
+            if (nInitial >= 3) {                       /* below three correspondences the reference returns before SetPose */
+                F.SetPose(drfe_detail_sim3::mat32(4, 4, &Tcw[16 * f]));
+            }
+        }
+    }
+    int Result(size_t i) const { return mReturns.at(i); }
+    drfe_ctx* ctx() const { return mCtx.get(); }
+
+private:
+    int PlaneEdges(size_t f) const
+    {
+        int e = 0;
+        for (int32_t k = mPlaneOff[f]; k < mPlaneOff[f + 1]; k++) {
+            const uint8_t m = mPlaneMask[(size_t)k];
+            e += (m & 1) + (mStruct[f] ? ((m >> 1) & 1) + ((m >> 2) & 1) : 0);
+        }
+        return e;
+    }
+    PlaneSettings mSettings;
+    int mDevice, mDeviceFrom;
+    Planar_SLAM::drfe_detail::CtxPtr mCtx;
+    std::vector<FrameT*> mFrames;
+    std::vector<uint8_t> mStruct, mPlaneMask;
+    std::vector<float> mTcw, mK, mBf, mObs, mUr, mInvSigma2, mXw, mPlaneMeas, mPlaneWorld;
+    std::vector<double> mLineFn, mLineEnds;
+    std::vector<int32_t> mPointOff, mLineOff, mPlaneOff, mPointIdx, mLineIdx, mReturns;
+};
+
+}  // namespace drfe
+
+namespace Planar_SLAM {
+
+/* include/Optimizer.h: the one entry of the reference's Optimizer this library builds.  The reference reads the plane settings
+ * from its Config singleton; here they are set once (SetPlaneSettings), as is the choice of the entry: a single frame is below
+ * DRFE_POSEOPT_DEVICE_FROM (the measured crossover), so it takes the host entry unless UseDevice(true). */
+class Optimizer {
+public:
+    static drfe::PlaneSettings& Settings() { static drfe::PlaneSettings s; return s; }
+    static void SetPlaneSettings(const drfe::PlaneSettings& s) { Settings() = s; }
+    static bool& DeviceFlag() { static bool on = 1 >= DRFE_POSEOPT_DEVICE_FROM; return on; }
+    static void UseDevice(bool on) { DeviceFlag() = on; }
+    template <class FrameT> static int PoseOptimization(FrameT* pFrame, bool bStruct)
+    {
+        static thread_local drfe::PoseOptBatch<FrameT> batch;       /* keeps its context between calls */
+        batch.SetSettings(Settings());
+        batch.UseDevice(DeviceFlag());
+        batch.Clear();
+        batch.Add(pFrame, bStruct);
+        batch.Run();
+        return batch.Result(0);
+    }
+};
+
+}  // namespace Planar_SLAM
+
 #endif /* DRFE_ADAPTOR_HPP */

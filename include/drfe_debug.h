@@ -80,6 +80,18 @@ int drfe_debug_init_cos_keys(const float* c, int n, uint32_t* key, float* value)
 int drfe_debug_init_null_vectors(const float* points, int n, float* h, float* fpre);
 int drfe_debug_init_check_rt(drfe_ctx* ctx, const float* K, const float* R, const float* t, float sigma, const float* matches, int n,
                              int32_t* good, float* cos_selected, float* parallax, int32_t* status, uint8_t* vbGood, float* vP3D);
+/* Test hooks of PoseOptimization (dr_slam_amd/csrc/pose_opt_core.h, cr_cube.h).  Host code.
+ * _cr_cube: out[i] = the correctly rounded x[i]^3 and ok[i] = 1, or ok[i] = 0 where cr_cube.h cannot certify the rounding.
+ * _pose_opt_ldlt: pose_opt_core.h's Eigen::LDLT of the symmetric 6x6 A (row-major, the lower triangle is read) and its solve of
+ * A x = b: returns isPositive() in *positive; x is written only then.
+ * _plane_error: computeError of one plane edge (kind 3 EdgePlaneOnlyPose, 4 EdgeParallelPlaneOnlyPose, 5 EdgeVerticalPlaneOnlyPose)
+ * with the measured and the world plane as float[4] coefficients under the pose Tcw: e[3] (e[2] = 0 for kinds 4 and 5).
+ * _hand_back: every > 0 makes drfe_pose_opt_batch treat every `every`-th frame of a call as not certified by the device, so that
+ * the host core runs it again; 0 turns it off. */
+int drfe_debug_cr_cube(const double* x, int n, double* out, uint8_t* ok);
+int drfe_debug_pose_opt_ldlt(const double* A, const double* b, double* x, int32_t* positive);
+int drfe_debug_pose_opt_plane_error(int kind, const float* meas, const float* world, const float* Tcw, double* e);
+int drfe_debug_pose_opt_hand_back(drfe_ctx* ctx, int every);
 
 #ifdef __cplusplus
 }
