@@ -160,11 +160,19 @@ DRFE_HD void po_plane_angles(PoCtx& ctx, const double nor[3], const double m[3],
 /* computeError of EdgePlaneOnlyPose / EdgeParallelPlaneOnlyPose / EdgeVerticalPlaneOnlyPose: localPlane = Isometry3D(estimate) *
  * Xw (operator*, Plane3D.h:189-202; rotation() of an isometry is its linear part), then ominus / ominus_par / ominus_ver of the
  * measurement */
+DRFE_HD void po_plane_ominus(PoCtx& ctx, const PoEdge& E, double l[4], const double t[3], double e[3]);
 DRFE_HD void po_plane_error(PoCtx& ctx, const PoEdge& E, const double q[4], const double t[3], double e[3])
 {
     double R[3][3], l[4];
     mp_quat_to_matrix(q, R);
     for (int i = 0; i < 3; i++) l[i] = (R[i][0] * E.X[0] + R[i][1] * E.X[1]) + R[i][2] * E.X[2];
+    po_plane_ominus(ctx, E, l, t, e);
+}
+
+/* what follows the normal l[0..2] of the local plane, shared with the translation-only plane edges (trans_opt_core.h, whose
+ * operator+ leaves the normal as it is): d - t . n, the four negated below zero, the Plane3D constructor, then the edge's ominus */
+DRFE_HD void po_plane_ominus(PoCtx& ctx, const PoEdge& E, double l[4], const double t[3], double e[3])
+{
     l[3] = E.X[3] - ((t[0] * l[0] + t[1] * l[1]) + t[2] * l[2]);
     if (l[3] < 0.0)
         for (int k = 0; k < 4; k++) l[k] = -l[k];
@@ -200,11 +208,18 @@ DRFE_HD void po_plane_error(PoCtx& ctx, const PoEdge& E, const double q[4], cons
 }
 
 /* computeError of the edge under the estimate (q, t); e[2] of a mono edge is not read and set to 0 */
+DRFE_HD void po_project_error(const PoEdge& E, const PoCam& C, const double p[3], double e[3]);
 DRFE_HD void po_edge_error(PoCtx& ctx, const PoEdge& E, const PoCam& C, const double q[4], const double t[3], double e[3])
 {
     if (po_is_plane(E.kind)) { po_plane_error(ctx, E, q, t, e); return; }
     double p[3];
     po_map(q, t, E.X, p);
+    po_project_error(E, C, p, e);
+}
+
+/* the measurement less cam_project of the camera point p, of a point or line edge: shared with the translation-only edges */
+DRFE_HD void po_project_error(const PoEdge& E, const PoCam& C, const double p[3], double e[3])
+{
     if (E.kind == PO_STEREO) {
         /* EdgeStereoSE3ProjectXYZOnlyPose::cam_project: `const float invz = 1.0f / trans_xyz[2]` divides in double, rounds to float */
         const double invz = (double)(float)(1.0 / p[2]);

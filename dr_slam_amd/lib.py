@@ -58,6 +58,8 @@ SYMBOLS = (
     "drfe_lines_is_good_batch", "drfe_line3d_chunk_frames", "drfe_line3d_stats",
     "drfe_pose_opt_host", "drfe_pose_opt_batch", "drfe_pose_opt_stats", "drfe_debug_cr_cube", "drfe_debug_pose_opt_ldlt",
     "drfe_debug_pose_opt_hand_back", "drfe_debug_pose_opt_plane_error",
+    "drfe_trans_opt_host", "drfe_trans_opt_batch", "drfe_trans_opt_stats", "drfe_debug_trans_opt_hand_back",
+    "drfe_debug_trans_opt_plane_error",
 )
 
 FRUSTUM_POINT_DTYPE = np.dtype([("world", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"),
@@ -423,6 +425,11 @@ def load() -> C.CDLL:
     L.drfe_debug_pose_opt_ldlt.argtypes = [vp, vp, vp, vp]
     L.drfe_debug_pose_opt_hand_back.argtypes = [vp, i32]
     L.drfe_debug_pose_opt_plane_error.argtypes = [i32, vp, vp, vp, vp]
+    L.drfe_trans_opt_host.argtypes = [vp, vp]
+    L.drfe_trans_opt_batch.argtypes = [vp, vp, vp, vp]
+    L.drfe_trans_opt_stats.argtypes = [vp, vp]
+    L.drfe_debug_trans_opt_hand_back.argtypes = [vp, i32]
+    L.drfe_debug_trans_opt_plane_error.argtypes = [i32, vp, vp, vp, vp]
     L.drfe_pnp_stats.argtypes = [vp, vp]
     L.drfe_lines_is_good_batch.argtypes = [vp, vp, vp, vp]
     L.drfe_line3d_chunk_frames.argtypes = [i32]
@@ -942,6 +949,29 @@ def pose_opt_host(problems):
     if rc != 0:
         raise DrfeError(f"drfe_pose_opt_host failed ({rc})")
     return r
+
+
+TRANSOPT_DEVICE_FROM = 64                            # DRFE_TRANSOPT_DEVICE_FROM
+
+
+def trans_opt_host(problems):
+    """Optimizer::TranslationOptimization of every frame on the host (drfe_trans_opt_host, DESIGN.md section 21); problems and
+    result as _pose_opt_pack: the map geometry stays in world coordinates, the entry rotates it"""
+    P, out, r, _keep = _pose_opt_pack(problems)
+    rc = load().drfe_trans_opt_host(C.byref(P), C.byref(out))
+    if rc != 0:
+        raise DrfeError(f"drfe_trans_opt_host failed ({rc})")
+    return r
+
+
+def trans_opt_plane_error(kind, meas, world, Tcw):
+    """trans_opt_core.h's computeError of one translation-only plane edge (kind 3 matched, 4 parallel, 5 vertical): the world plane
+    rotated by the float R_cw of Tcw, then the error under Tcw's translation: e [3]"""
+    meas, world, Tcw = (np.ascontiguousarray(np.asarray(v, np.float32).reshape(-1)) for v in (meas, world, Tcw))
+    e = np.zeros(3, np.float64)
+    if load().drfe_debug_trans_opt_plane_error(int(kind), _p(meas), _p(world), _p(Tcw), _p(e)) != 0:
+        raise DrfeError("drfe_debug_trans_opt_plane_error failed")
+    return e
 
 
 def cr_cube(x):
@@ -2307,6 +2337,22 @@ class Context:
     def pose_opt_hand_back(self, every):
         """test hook: the host runs every `every`-th frame of a batch call again as if the device had not certified it"""
         self._chk(self.L.drfe_debug_pose_opt_hand_back(self.h, int(every)), "drfe_debug_pose_opt_hand_back")
+
+    def trans_opt_batch(self, problems):
+        """trans_opt_host on the device (drfe_trans_opt_batch): same outputs, same bits"""
+        P, out, r, _keep = _pose_opt_pack(problems)
+        self._chk(self.L.drfe_trans_opt_batch(self.h, C.byref(P), C.byref(out), None), "drfe_trans_opt_batch")
+        return r
+
+    def trans_opt_stats(self):
+        """drfe_trans_opt_stats as a dict over POSE_OPT_STATS"""
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_trans_opt_stats(self.h, _p(st)), "drfe_trans_opt_stats")
+        return dict(zip(POSE_OPT_STATS, st.tolist()))
+
+    def trans_opt_hand_back(self, every):
+        """test hook: the host runs every `every`-th frame of a trans_opt_batch call again as if the device had handed it back"""
+        self._chk(self.L.drfe_debug_trans_opt_hand_back(self.h, int(every)), "drfe_debug_trans_opt_hand_back")
 
     def init_ransac_batch(self, problems):
         """init_ransac_host on the device (drfe_init_ransac_batch): same outputs, same bits"""

@@ -1402,6 +1402,30 @@ int drfe_pose_opt_batch(drfe_ctx* ctx, const drfe_pose_opt_problems* problems, d
  * returned before the loop (fewer than 3 correspondences). */
 int drfe_pose_opt_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
 
+/* Optimizer::TranslationOptimization(Frame*, bool bStruct) (src/Optimizer.cc:3211-3980), the step of the decoupled mode after the
+ * Manhattan rotation is written into mTcw (TranslationWithMotionModel, TranslationEstimation): only the translation is optimised.
+ * Every frame of a call at once.  DESIGN.md section 21.
+ *
+ * The records, the caps and the diagnostics are drfe_pose_opt's.  Xw, line_ends and plane_world stay in world coordinates: the
+ * entry rotates them once by the float R_cw of the input Tcw, as the reference does.  What differs from PoseOptimization: the
+ * edges read only the estimate's translation; `returns` is the number of points less the point and plane outliers of the last
+ * round (lines and planes do not add to it, line outliers do not take from it, so it can be negative); a frame with fewer than
+ * three points returns 0 with its input pose after zero rounds, whatever its lines and planes.  Parity with a g2o / Eigen 3.3.7
+ * build is not pinned yet. */
+/* frames in a call from which drfe::TransOptBatch uses the device entry (the measured crossover) */
+enum { DRFE_TRANSOPT_DEVICE_FROM = 64 };
+/* On the host, no context. */
+int drfe_trans_opt_host(const drfe_pose_opt_problems* problems, drfe_pose_opt_out* out);
+/* The same on the device: the caller's arrays staged as they are with one copy, one launch (a workgroup per frame forms its
+ * edges and runs its four rounds), the results back with one copy; returns with the outputs written (`stream` NULL = the
+ * context's).  Same bits as the host entry. */
+int drfe_trans_opt_batch(drfe_ctx* ctx, const drfe_pose_opt_problems* problems, drfe_pose_opt_out* out, void* stream);
+/* Counters since the context was created: stats[0] batch calls, [1] frames, [2] point edges, [3] line and plane edges (no plane
+ * edge exists in a frame that returns before the loop), [4] Levenberg iterations, [5] trial steps, [6] frames the device handed
+ * back to the host (a sin / cos, atan2 or x^3 it could not certify, or a term of H or b that is not finite), [7] frames that
+ * returned before the loop (fewer than 3 points). */
+int drfe_trans_opt_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

@@ -2774,10 +2774,15 @@ namespace drfe {
  * MapPoint / MapPlane: GetWorldPos() (3x1 / 4x1 float); MapLine: mWorldPos (six doubles through operator()). */
 struct PlaneSettings { double angleInfo = 0.5, distanceInfo = 50, parallelInfo = 0.1, verticalInfo = 0.1, chi = 100, vpChi = 50; };
 
-template <class FrameT>
+/* TransOnly: the same batch over Optimizer::TranslationOptimization (src/Optimizer.cc:3211-3980, drfe_trans_opt_host / _batch,
+ * DESIGN.md section 21), spelled drfe::TransOptBatch<FrameT>.  It reads and writes the same members; the map geometry goes in
+ * world coordinates and the entry rotates it by mTcw's rotation; only the points count towards the three correspondences below
+ * which the reference returns before SetPose; it switches entries at DRFE_TRANSOPT_DEVICE_FROM. */
+template <class FrameT, bool TransOnly = false>
 class PoseOptBatch {
 public:
-    explicit PoseOptBatch(const PlaneSettings& settings = PlaneSettings(), int device = 0, int deviceFrom = DRFE_POSEOPT_DEVICE_FROM)
+    explicit PoseOptBatch(const PlaneSettings& settings = PlaneSettings(), int device = 0,
+                          int deviceFrom = TransOnly ? (int)DRFE_TRANSOPT_DEVICE_FROM : (int)DRFE_POSEOPT_DEVICE_FROM)
         : mSettings(settings), mDevice(device), mDeviceFrom(deviceFrom) { Clear(); }
     /* true / false: the device / the host entry whatever the number of frames */
     void UseDevice(bool on) { mDeviceFrom = on ? 0 : 2147483647; }
@@ -2868,10 +2873,17 @@ public:
         } clearOnExit{this, &mReturns};
         if (n) {
             if ((int64_t)n < (int64_t)mDeviceFrom) {
-                if (drfe_pose_opt_host(&in, &out) != DRFE_OK) { mReturns.clear(); throw std::runtime_error("drfe_pose_opt_host: invalid argument"); }
+                const int rc = TransOnly ? drfe_trans_opt_host(&in, &out) : drfe_pose_opt_host(&in, &out);
+                if (rc != DRFE_OK) {
+                    mReturns.clear();
+                    throw std::runtime_error(TransOnly ? "drfe_trans_opt_host: invalid argument" : "drfe_pose_opt_host: invalid argument");
+                }
             } else {
                 if (!mCtx) mCtx = Planar_SLAM::drfe_detail::make_ctx(1, 1.2f, 1, 20, 7, 64, 64, 1, mDevice);
-                Planar_SLAM::drfe_detail::check(drfe_pose_opt_batch(mCtx.get(), &in, &out, nullptr), mCtx.get(), "drfe_pose_opt_batch");
+                if (TransOnly)
+                    Planar_SLAM::drfe_detail::check(drfe_trans_opt_batch(mCtx.get(), &in, &out, nullptr), mCtx.get(), "drfe_trans_opt_batch");
+                else
+                    Planar_SLAM::drfe_detail::check(drfe_pose_opt_batch(mCtx.get(), &in, &out, nullptr), mCtx.get(), "drfe_pose_opt_batch");
             }
         }
         for (size_t f = 0; f < n; f++) {
@@ -2885,7 +2897,7 @@ public:
                 if (mStruct[f] && (m & DRFE_POSE_OPT_PLANE_PARALLEL)) F.mvbParPlaneOutlier[i] = pp[(size_t)k] != 0;
                 if (mStruct[f] && (m & DRFE_POSE_OPT_PLANE_VERTICAL)) F.mvbVerPlaneOutlier[i] = pv[(size_t)k] != 0;
             }
-            const int nInitial = (mPointOff[f + 1] - mPointOff[f]) + (mLineOff[f + 1] - mLineOff[f]) + PlaneEdges(f);
+            const int nInitial = (mPointOff[f + 1] - mPointOff[f]) + (TransOnly ? 0 : (mLineOff[f + 1] - mLineOff[f]) + PlaneEdges(f));
             if (nInitial >= 3) {                       /* below three correspondences the reference returns before SetPose */
                 F.SetPose(drfe_detail_sim3::mat32(4, 4, &Tcw[16 * f]));
             }
@@ -2914,19 +2926,22 @@ private:
     std::vector<int32_t> mPointOff, mLineOff, mPlaneOff, mPointIdx, mLineIdx, mReturns;
 };
 
+template <class FrameT> using TransOptBatch = PoseOptBatch<FrameT, true>;
+
 }  // namespace drfe
 
 namespace Planar_SLAM {
 
-/* include/Optimizer.h: the one entry of the reference's Optimizer this library builds.  The reference reads the plane settings
+/* include/Optimizer.h: the two entries of the reference's Optimizer this library builds.  The reference reads the plane settings
  * from its Config singleton; here they are set once (SetPlaneSettings), as is the choice of the entry: a single frame is below
- * DRFE_POSEOPT_DEVICE_FROM (the measured crossover), so it takes the host entry unless UseDevice(true). */
+ * DRFE_POSEOPT_DEVICE_FROM and DRFE_TRANSOPT_DEVICE_FROM (the measured crossovers), so it takes the host entry unless
+ * UseDevice(true). */
 class Optimizer {
 public:
     static drfe::PlaneSettings& Settings() { static drfe::PlaneSettings s; return s; }
     static void SetPlaneSettings(const drfe::PlaneSettings& s) { Settings() = s; }
     static bool& DeviceFlag() { static bool on = 1 >= DRFE_POSEOPT_DEVICE_FROM; return on; }
-    static void UseDevice(bool on) { DeviceFlag() = on; }
+    static void UseDevice(bool on) { DeviceFlag() = on; TransDeviceFlag() = on; }
     template <class FrameT> static int PoseOptimization(FrameT* pFrame, bool bStruct)
     {
         static thread_local drfe::PoseOptBatch<FrameT> batch;       /* keeps its context between calls */
@@ -2937,6 +2952,20 @@ public:
         batch.Run();
         return batch.Result(0);
     }
+    /* TranslationWithMotionModel / TranslationEstimation: mTcw holds the Manhattan rotation, only t is optimised */
+    template <class FrameT> static int TranslationOptimization(FrameT* pFrame, bool bStruct)
+    {
+        static thread_local drfe::TransOptBatch<FrameT> batch;      /* keeps its context between calls */
+        batch.SetSettings(Settings());
+        batch.UseDevice(TransDeviceFlag());
+        batch.Clear();
+        batch.Add(pFrame, bStruct);
+        batch.Run();
+        return batch.Result(0);
+    }
+
+private:
+    static bool& TransDeviceFlag() { static bool on = 1 >= DRFE_TRANSOPT_DEVICE_FROM; return on; }
 };
 
 }  // namespace Planar_SLAM

@@ -92,6 +92,14 @@ int drfe_debug_cr_cube(const double* x, int n, double* out, uint8_t* ok);
 int drfe_debug_pose_opt_ldlt(const double* A, const double* b, double* x, int32_t* positive);
 int drfe_debug_pose_opt_plane_error(int kind, const float* meas, const float* world, const float* Tcw, double* e);
 int drfe_debug_pose_opt_hand_back(drfe_ctx* ctx, int every);
+/* Test hooks of TranslationOptimization (dr_slam_amd/csrc/trans_opt_core.h).  Host code.
+ * _plane_error: computeError of one translation-only plane edge (kind 3 EdgePlaneOnlyTranslation, 4
+ * EdgeParallelPlaneOnlyTranslation, 5 EdgeVerticalPlaneOnlyTranslation): the world plane's normal rotated by the float R_cw of
+ * Tcw, localPlane = w2n + Xc under Tcw's translation, then ominus / ominus_par / ominus_ver: e[3] (e[2] = 0 for kinds 4 and 5).
+ * _hand_back: every > 0 makes drfe_trans_opt_batch treat every `every`-th frame of a call as handed back by the device, so that
+ * the host core runs it again; 0 turns it off. */
+int drfe_debug_trans_opt_plane_error(int kind, const float* meas, const float* world, const float* Tcw, double* e);
+int drfe_debug_trans_opt_hand_back(drfe_ctx* ctx, int every);
 
 #ifdef __cplusplus
 }
