@@ -127,7 +127,7 @@ static inline void sort(uint32_t* a, size_t n, std::vector<uint32_t>& tmp, int m
     else lsd_order_scalar::partition_phase(a, n, depthOverride, skipBelow);
     stable_by_bin(a, n, tmp);
 }
-static inline void reference_sort(uint32_t* a, size_t n, int depthOverride) { lsd_order_scalar::reference_sort(a, n, depthOverride); }
+static inline void reference_sort(uint32_t* a, size_t n, int depthOverride, size_t* longestHeap = nullptr) { lsd_order_scalar::reference_sort(a, n, depthOverride, longestHeap); }
 
 }  // namespace lsd_order
 
@@ -147,7 +147,7 @@ static inline void sort(uint64_t* a, size_t n, int mode = -1, int depthOverride 
     else voxel_order_scalar::partition_phase(a, n, depthOverride);
     voxel_order_scalar::insertion_pass(a, n);
 }
-static inline void reference_sort(uint64_t* a, size_t n, int depthOverride) { voxel_order_scalar::reference_sort(a, n, depthOverride); }
+static inline void reference_sort(uint64_t* a, size_t n, int depthOverride, size_t* longestHeap = nullptr) { voxel_order_scalar::reference_sort(a, n, depthOverride, longestHeap); }
 
 }  // namespace voxel_order
 #endif

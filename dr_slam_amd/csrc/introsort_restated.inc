@@ -165,8 +165,9 @@ static inline void insertion_pass(rec_t* a, size_t n)
 }
 
 /* the plain transcription of std::__introsort_loop / std::__final_insertion_sort with a settable depth limit: the checker of
- * the heap-sort branch in tests (at the natural depth limit it is compared with std::sort itself) */
-static inline void reference_sort(rec_t* a, size_t n, int depthOverride)
+ * the heap-sort branch in tests (at the natural depth limit it is compared with std::sort itself).  *longestHeap = the longest range
+ * that ran out of depth and went to std::__partial_sort, 0 if none did */
+static inline void reference_sort(rec_t* a, size_t n, int depthOverride, size_t* longestHeap = nullptr)
 {
     const Before before;
     struct R {
@@ -181,22 +182,27 @@ static inline void reference_sort(rec_t* a, size_t n, int depthOverride)
                 ++first;
             }
         }
-        static void loop(rec_t* a, size_t first, size_t last, int depth, const Before& before)
+        static void loop(rec_t* a, size_t first, size_t last, int depth, const Before& before, size_t* longestHeap)
         {
             while (last - first > 16) {
-                if (depth == 0) { std::partial_sort(a + first, a + last, a + last, before); return; }
+                if (depth == 0) {
+                    if (longestHeap && last - first > *longestHeap) *longestHeap = last - first;
+                    std::partial_sort(a + first, a + last, a + last, before);
+                    return;
+                }
                 --depth;
                 median_to_first(a, first, first + 1, first + (last - first) / 2, last - 1);
                 const size_t cut = partition(a, first + 1, last, first, before);
-                loop(a, cut, last, depth, before);
+                loop(a, cut, last, depth, before, longestHeap);
                 last = cut;
             }
         }
     };
+    if (longestHeap) *longestHeap = 0;
     if (n < 2) return;
     int lg = 0;
     for (size_t v = n; v > 1; v >>= 1) lg++;
-    R::loop(a, 0, n, depthOverride >= 0 ? depthOverride : 2 * lg, before);
+    R::loop(a, 0, n, depthOverride >= 0 ? depthOverride : 2 * lg, before, longestHeap);
     insertion_pass(a, n);
 }
 #endif

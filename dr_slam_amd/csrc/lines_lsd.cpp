@@ -1549,6 +1549,17 @@ int drfe_debug_order_sort(void* recs, size_t n, int kind, int mode, int depth_li
     return DRFE_OK;
 }
 
+/* Test hook of introsort_restated.h: drfe_debug_order_sort's mode 3 (the plain transcription, depth_limit >= 0 replaces 2 lg n) that
+ * also reports the longest range that ran out of depth and went to std::__partial_sort (0 if none did).  The device sorts make the
+ * same partitions, so they hand an input back exactly when *longest > 1024 (introsort_device.h: ORD_HEAP_MAX). */
+int drfe_debug_order_sort_heap_max(void* recs, size_t n, int kind, int depth_limit, size_t* longest)
+{
+    if (!recs || !longest || kind < 0 || kind > 1) return DRFE_ERR_INVALID;
+    if (kind == 0) lsd_order::reference_sort(static_cast<uint32_t*>(recs), n, depth_limit, longest);
+    else voxel_order::reference_sort(static_cast<uint64_t*>(recs), n, depth_limit, longest);
+    return DRFE_OK;
+}
+
 /* parity taps of the device passes (tests) */
 int drfe_lsd_stages(drfe_ctx* c, uint8_t* scaled, double* modgrad, double* angles, int16_t* gx, int16_t* gy, int* sw, int* sh)
 {

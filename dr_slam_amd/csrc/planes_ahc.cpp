@@ -748,6 +748,13 @@ void drfe_ahc_arena_free(drfe_ctx* c)
 
 #define AHC_DEV_PLANE_CAP 64
 
+/* std::mt19937(12345): the state after seeding (its first draw twists it) */
+static void refit_mt_seed(uint32_t mt[624])
+{
+    mt[0] = 12345u;
+    for (int i = 1; i < 624; i++) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
+}
+
 static int ensure_arena(drfe_ctx* c, int w, int h, int frames, const float* K4, float depth_factor, float max_point_dist)
 {
     AhcArena* a = c->ahcArena;
@@ -804,10 +811,8 @@ static int ensure_arena(drfe_ctx* c, int w, int h, int frames, const float* K4, 
         HIPCHK(c, a->h_post.alloc(P.planeCap * F));
         HIPCHK(c, a->h_postStatus.alloc(P.planeCap * F));
         {
-            /* std::mt19937(12345): the state after seeding (its first draw twists it) */
             uint32_t mt[624];
-            mt[0] = 12345u;
-            for (int i = 1; i < 624; i++) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
+            refit_mt_seed(mt);
             HIPCHK(c, a->d_mtState.alloc(624));
             HIPCHK(c, hipMemcpy(a->d_mtState, mt, sizeof(mt), hipMemcpyHostToDevice));
         }
@@ -1293,3 +1298,74 @@ int drfe_planes_ahc_post_batch(drfe_ctx* c, const uint16_t* depth, size_t frame_
 }
 
 } /* extern "C" */
+
+/* Test hook of refit_kernels.hip (include/drfe_debug.h): hand-built planes and voxel clouds through k_plane_refit, or through the
+ * host loop that checks it.  The kernel reads `planes` and `out` of its frame record and nothing else, so one fabricated record
+ * with these two set stands for the frame; the generator state is the context's arena's when there is one (the same words
+ * otherwise). */
+extern "C" int drfe_debug_plane_refit(drfe_ctx* c, int on_device, const drfe_plane* planes, int n_planes, const float* coarse_xyz, const int32_t* coarse_offsets,
+                                      const int32_t* vcounts_override, float max_point_dist, double dist_threshold, drfe_plane_post* post, int32_t* status)
+{
+    if ((on_device && !c) || !planes || n_planes < 1 || !coarse_offsets || !post || !status || coarse_offsets[0] != 0 || (!coarse_xyz && coarse_offsets[n_planes] > 0)) {
+        if (c) c->err = "debug_plane_refit: invalid argument";
+        return DRFE_ERR_INVALID;
+    }
+    for (int i = 0; i < n_planes; i++)
+        if (coarse_offsets[i + 1] < coarse_offsets[i]) { if (c) c->err = "debug_plane_refit: offsets must not decrease"; return DRFE_ERR_INVALID; }
+    /* a count >= 0 given by the caller replaces the cloud's (not beyond it); a negative one marks the grid as handed back (device only) */
+    std::vector<int> cnt(n_planes), devCnt(n_planes + 1, 0);
+    for (int i = 0; i < n_planes; i++) {
+        const int n = coarse_offsets[i + 1] - coarse_offsets[i];
+        cnt[i] = vcounts_override && vcounts_override[i] >= 0 ? std::min(n, vcounts_override[i]) : n;
+        devCnt[i] = vcounts_override && vcounts_override[i] < 0 ? vcounts_override[i] : cnt[i];
+    }
+    std::memset(post, 0, sizeof(drfe_plane_post) * n_planes);
+    if (!on_device) {
+        std::string local;
+        std::vector<const float*> cptr(n_planes);
+        std::vector<int32_t> voff(n_planes + 1);
+        for (int i = 0; i < n_planes; i++) cptr[i] = coarse_xyz + 3 * (size_t)coarse_offsets[i];
+        int nAcc = 0, planeNum = 0;
+        const int rc = drfe_ahc_post_from_coarse(c ? &c->err : &local, planes, n_planes, cptr.data(), cnt.data(), max_point_dist, dist_threshold, post, nullptr, voff.data(), 0,
+                                                 &nAcc, &planeNum);
+        for (int i = 0; i < n_planes; i++) status[i] = 0;
+        status[n_planes] = -1;
+        return rc;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    const int njobs = n_planes + 1;
+    const size_t total = (size_t)coarse_offsets[n_planes];
+    DevBuf<drfe_plane> d_planes; DevBuf<int> d_out, d_cnt, d_status; DevBuf<AhcDevFrame> d_frame; DevBuf<int2> d_jobs; DevBuf<float> d_xyz;
+    DevBuf<uint32_t> d_mt; DevBuf<drfe_plane_post> d_post;
+    HIPCHK(c, d_planes.alloc(n_planes)); HIPCHK(c, d_out.alloc(2)); HIPCHK(c, d_cnt.alloc(njobs)); HIPCHK(c, d_status.alloc(njobs));
+    HIPCHK(c, d_frame.alloc(1)); HIPCHK(c, d_jobs.alloc(njobs)); HIPCHK(c, d_xyz.alloc(std::max<size_t>(3 * total, 3))); HIPCHK(c, d_post.alloc(njobs));
+    const uint32_t* mtState = c->ahcArena && c->ahcArena->ready ? (const uint32_t*)c->ahcArena->d_mtState : nullptr;
+    if (!mtState) {
+        uint32_t mt[624];
+        refit_mt_seed(mt);
+        HIPCHK(c, d_mt.alloc(624));
+        HIPCHK(c, hipMemcpy(d_mt, mt, sizeof(mt), hipMemcpyHostToDevice));
+        mtState = d_mt;
+    }
+    AhcDevFrame fr;
+    std::memset(&fr, 0, sizeof(fr));
+    fr.planes = d_planes; fr.out = d_out;
+    const int out2[2] = {n_planes, 0};
+    std::vector<int2> jobs(njobs);
+    for (int i = 0; i < n_planes; i++) jobs[i] = make_int2(coarse_offsets[i], cnt[i]);
+    jobs[n_planes] = make_int2(0, 0);
+    HIPCHK(c, hipMemcpy(d_planes, planes, sizeof(drfe_plane) * n_planes, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_out, out2, sizeof(out2), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_frame, &fr, sizeof(fr), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_jobs, jobs.data(), sizeof(int2) * njobs, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(d_cnt, devCnt.data(), sizeof(int) * njobs, hipMemcpyHostToDevice));
+    if (total) HIPCHK(c, hipMemcpy(d_xyz, coarse_xyz, 12 * total, hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemset(d_post, 0, sizeof(drfe_plane_post) * njobs));
+    HIPCHK(c, hipMemset(d_status, 0x7f, sizeof(int) * njobs));
+    hipError_t e = drfe_launch_plane_refit(d_frame, d_jobs, d_cnt, d_xyz, mtState, njobs, njobs, max_point_dist, dist_threshold, std::log(1.0 - 0.99), d_post, d_status, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { c->err = std::string("debug_plane_refit: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
+    HIPCHK(c, hipMemcpy(post, d_post, sizeof(drfe_plane_post) * n_planes, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(status, d_status, sizeof(int) * njobs, hipMemcpyDeviceToHost));
+    return DRFE_OK;
+}

@@ -376,6 +376,35 @@ void drfe_voxel_device_free(VoxelDevice* v)
     delete v;
 }
 
+/* room for `total` points in the lane's buffers */
+static hipError_t voxel_device_reserve(VoxelDevice* v, size_t total)
+{
+    if (v->cap >= total) return hipSuccess;
+    v->cap = 0;
+    const size_t cap = std::max<size_t>(total + total / 4, 1 << 16);
+    hipError_t e;
+    if ((e = v->d_pts.alloc(cap * 3)) != hipSuccess || (e = v->d_recs.alloc(cap)) != hipSuccess || (e = v->d_tmp.alloc(cap)) != hipSuccess ||
+        (e = v->d_posL.alloc(cap)) != hipSuccess || (e = v->d_posR.alloc(cap)) != hipSuccess || (e = v->d_out.alloc(cap * 3)) != hipSuccess ||
+        (e = v->h_pts.alloc(cap * 3)) != hipSuccess || (e = v->h_out.alloc(cap * 3)) != hipSuccess)
+        return e;
+    v->cap = cap;
+    return hipSuccess;
+}
+
+/* the np jobs of h_jobs over the `total` points of h_pts through k_voxel_jobs_order + k_voxel_grid: counts to h_counts, centroids to
+ * h_out.  Tests only: depthLimit / workgroups as drfe_launch_voxel_grid takes them, recs = the sorted records of every job */
+static hipError_t voxel_device_run(VoxelDevice* v, int np, size_t total, float leaf, int depthLimit = -1, int workgroups = 0, uint64_t* recs = nullptr)
+{
+    hipError_t e = hipMemcpyAsync(v->d_pts, v->h_pts, total * 12, hipMemcpyHostToDevice, v->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(v->d_jobs, v->h_jobs, np * sizeof(int2), hipMemcpyHostToDevice, v->stream);
+    if (e == hipSuccess) e = drfe_launch_voxel_grid(v->d_pts, v->d_jobs, np, v->d_list, v->d_recs, v->d_tmp, v->d_posL, v->d_posR, v->d_out, v->d_counts, leaf, v->stream, depthLimit, workgroups);
+    if (e == hipSuccess) e = hipMemcpyAsync(v->h_counts, v->d_counts, np * sizeof(int), hipMemcpyDeviceToHost, v->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(v->h_out, v->d_out, total * 12, hipMemcpyDeviceToHost, v->stream);
+    if (e == hipSuccess && recs) e = hipMemcpyAsync(recs, v->d_recs, total * 8, hipMemcpyDeviceToHost, v->stream);
+    if (e == hipSuccess) e = drfe_pool_sync(v->stream, v->ev);
+    return e;
+}
+
 /* pcl::VoxelGrid(0.05) of every plane's cloud in one launch; coarse[i] filled for the planes the device finished, done[i] = 0
  * for those it handed back (grid overflow, heap-sort branch) or that did not fit */
 static bool voxel_downsample_device(VoxelDevice* v, const std::vector<Pt>* inputs, int np, std::vector<Pt>* coarse,
@@ -390,28 +419,14 @@ static bool voxel_downsample_device(VoxelDevice* v, const std::vector<Pt>* input
     auto fail = [&](const char* what, hipError_t e) { if (err) *err = std::string("voxel grid lane: ") + what + ": " + hipGetErrorString(e); return false; };
     hipError_t e = hipSetDevice(v->device);
     if (e != hipSuccess) return fail("hipSetDevice", e);
-    if (v->cap < total) {
-        v->cap = 0;
-        const size_t cap = std::max<size_t>(total + total / 4, 1 << 16);
-        if ((e = v->d_pts.alloc(cap * 3)) != hipSuccess || (e = v->d_recs.alloc(cap)) != hipSuccess || (e = v->d_tmp.alloc(cap)) != hipSuccess ||
-            (e = v->d_posL.alloc(cap)) != hipSuccess || (e = v->d_posR.alloc(cap)) != hipSuccess || (e = v->d_out.alloc(cap * 3)) != hipSuccess ||
-            (e = v->h_pts.alloc(cap * 3)) != hipSuccess || (e = v->h_out.alloc(cap * 3)) != hipSuccess)
-            return fail("buffer allocation", e);
-        v->cap = cap;
-    }
+    if ((e = voxel_device_reserve(v, total)) != hipSuccess) return fail("buffer allocation", e);
     size_t off = 0;
     for (int i = 0; i < np; i++) {
         v->h_jobs[i] = make_int2((int)off, (int)inputs[i].size());
         if (!inputs[i].empty()) std::memcpy(v->h_pts + 3 * off, inputs[i].data(), inputs[i].size() * sizeof(Pt));
         off += inputs[i].size();
     }
-    e = hipMemcpyAsync(v->d_pts, v->h_pts, total * 12, hipMemcpyHostToDevice, v->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(v->d_jobs, v->h_jobs, np * sizeof(int2), hipMemcpyHostToDevice, v->stream);
-    if (e == hipSuccess) e = drfe_launch_voxel_grid(v->d_pts, v->d_jobs, np, v->d_list, v->d_recs, v->d_tmp, v->d_posL, v->d_posR, v->d_out, v->d_counts, 0.05f, v->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(v->h_counts, v->d_counts, np * sizeof(int), hipMemcpyDeviceToHost, v->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(v->h_out, v->d_out, total * 12, hipMemcpyDeviceToHost, v->stream);
-    if (e == hipSuccess) e = drfe_pool_sync(v->stream, v->ev);
-    if (e != hipSuccess) return fail("launch", e);
+    if ((e = voxel_device_run(v, np, total, 0.05f)) != hipSuccess) return fail("launch", e);
     for (int i = 0; i < np; i++) {
         const int cnt = v->h_counts[i];
         if (cnt < 0) continue;                            /* handed back */
@@ -420,6 +435,40 @@ static bool voxel_downsample_device(VoxelDevice* v, const std::vector<Pt>* input
         done[i] = 1;
     }
     return true;
+}
+
+/* Test hook of voxel_kernels.hip (include/drfe_debug.h): n_clouds hand-built clouds in CSR form through one VoxelDevice lane, the
+ * code path of voxel_downsample_device, with the kernel's raw counts */
+extern "C" int drfe_debug_device_voxel_grid(drfe_ctx* c, const float* xyz, const int32_t* offsets, int n_clouds, float leaf, int depth_limit, int workgroups,
+                                            float* out_xyz, int32_t* out_counts, uint64_t* out_recs)
+{
+    if (!c) return DRFE_ERR_INVALID;
+    if (!offsets || n_clouds < 1 || n_clouds > VOX_MAX_JOBS || !(leaf > 0.f) || !out_xyz || !out_counts || offsets[0] != 0 || (!xyz && offsets[n_clouds] > 0)) {
+        c->err = "debug_device_voxel_grid: invalid argument";
+        return DRFE_ERR_INVALID;
+    }
+    for (int i = 0; i < n_clouds; i++)
+        if (offsets[i + 1] < offsets[i]) { c->err = "debug_device_voxel_grid: offsets must not decrease"; return DRFE_ERR_INVALID; }
+    const size_t total = (size_t)offsets[n_clouds];
+    for (int i = 0; i < n_clouds; i++) out_counts[i] = 0;
+    if (total == 0) return DRFE_OK;
+    VoxelDevice* v = drfe_voxel_device_create(c->device, &c->err);
+    if (!v) return DRFE_ERR_HIP;
+    hipError_t e = voxel_device_reserve(v, total);
+    if (e == hipSuccess) {
+        for (int i = 0; i < n_clouds; i++) v->h_jobs[i] = make_int2(offsets[i], offsets[i + 1] - offsets[i]);
+        std::memcpy(v->h_pts, xyz, total * 12);
+        std::memset(v->h_out, 0, total * 12);
+        e = hipMemsetAsync(v->d_out, 0, total * 12, v->stream);
+        if (e == hipSuccess && out_recs) e = hipMemsetAsync(v->d_recs, 0, total * 8, v->stream);
+        if (e == hipSuccess) e = voxel_device_run(v, n_clouds, total, leaf, depth_limit, workgroups, out_recs);
+    }
+    if (e == hipSuccess) {
+        std::memcpy(out_xyz, v->h_out, total * 12);
+        for (int i = 0; i < n_clouds; i++) out_counts[i] = v->h_counts[i];
+    } else c->err = std::string("debug_device_voxel_grid: ") + hipGetErrorString(e);
+    drfe_voxel_device_free(v);
+    return e == hipSuccess ? DRFE_OK : DRFE_ERR_HIP;
 }
 
 

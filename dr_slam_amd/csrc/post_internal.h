@@ -60,9 +60,12 @@ void drfe_plane_match_free(drfe_ctx* c);
 #include <string>
 /* pcl::VoxelGrid for njobs point clouds at once (voxel_kernels.hip): job j = points [jobs[j].x, jobs[j].x + jobs[j].y) of d_pts
  * (xyz packed); d_list: njobs + 2 ints of scratch (the job order); scratch arrays span all points; centroids of job j to d_out at the job's offset, their number to d_counts[j]
- * (-1: grid overflows int32, PCL keeps the input cloud; -2: the sort needs the heap-sort branch: run the job on the host) */
+ * (-1: grid overflows int32, PCL keeps the input cloud; -2: the sort needs the heap-sort branch: run the job on the host; <= -9: a loop
+ * bound of the sort).  d_recs holds job j's sorted leaf << 32 | point records at the job's offset afterwards.  Tests only:
+ * depthLimit >= 0 replaces introsort's 2 lg n, workgroups > 0 caps the launch's grid below the resident count. */
 hipError_t drfe_launch_voxel_grid(const float* d_pts, const int2* d_jobs, int njobs, int* d_list, unsigned long long* d_recs, unsigned long long* d_tmp,
-                                  uint32_t* d_posL, uint32_t* d_posR, float* d_out, int* d_counts, float leafSize, hipStream_t s);
+                                  uint32_t* d_posL, uint32_t* d_posR, float* d_out, int* d_counts, float leafSize, hipStream_t s, int depthLimit = -1,
+                                  int workgroups = 0);
 /* Gates + Frame::MaxPointDistanceFromPlane (RANSAC + least-squares refit) of njobs planes on the centroids k_voxel_grid left
  * (refit_kernels.hip): job j = plane j % planeCap of frame j / planeCap of the extractor's frame table; d_post[j] / d_status[j]
  * (0 final, 1 not certified: refit on the host, 2 the voxel grid came back: grid + refit on the host, -1 no such plane).

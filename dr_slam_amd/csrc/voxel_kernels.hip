@@ -89,7 +89,7 @@ extern "C" __global__ __launch_bounds__(VOX_T) VOX_OCC void k_voxel_grid(const f
                                                                  const int* __restrict__ list, int* __restrict__ ctl,
                                                                  unsigned long long* __restrict__ recs, unsigned long long* __restrict__ tmp,
                                                                  uint32_t* __restrict__ posL, uint32_t* __restrict__ posR,
-                                                                 float* __restrict__ out, int* __restrict__ counts, float leafSize)
+                                                                 float* __restrict__ out, int* __restrict__ counts, float leafSize, int depthLimit)
 {
     extern __shared__ uint32_t dyn[];
     __shared__ isd::Shared<VOX_T> sh;
@@ -154,7 +154,7 @@ extern "C" __global__ __launch_bounds__(VOX_T) VOX_OCC void k_voxel_grid(const f
     for (unsigned v = (unsigned)n; v > 1; v >>= 1) lg++;
     __syncthreads();
     VOX_TP(0);
-    const int st = __builtin_amdgcn_readfirstlane(isd::sort<VOX_T, VoxTraits>(a, n, posL + off, posR + off, tmp + off, dyn, sh, 2 * lg, keyBits));
+    const int st = __builtin_amdgcn_readfirstlane(isd::sort<VOX_T, VoxTraits>(a, n, posL + off, posR + off, tmp + off, dyn, sh, depthLimit >= 0 ? depthLimit : 2 * lg, keyBits));
 #ifdef VOX_PROFILE
     if (st != 0 && tid == 0) { atomicAdd(&g_voxTail[3], wall_clock64() - voxT0); atomicAdd(&g_voxTail[4], 1ull); atomicAdd(&g_voxXcd[17], ~0ull); }
 #endif
@@ -202,7 +202,7 @@ extern "C" __global__ __launch_bounds__(VOX_T) VOX_OCC void k_voxel_grid(const f
 }
 
 hipError_t drfe_launch_voxel_grid(const float* d_pts, const int2* d_jobs, int njobs, int* d_list, unsigned long long* d_recs, unsigned long long* d_tmp,
-                                  uint32_t* d_posL, uint32_t* d_posR, float* d_out, int* d_counts, float leafSize, hipStream_t s)
+                                  uint32_t* d_posL, uint32_t* d_posR, float* d_out, int* d_counts, float leafSize, hipStream_t s, int depthLimit, int workgroups)
 {
     if (njobs <= 0) return hipSuccess;
     static int resident = 0;
@@ -219,8 +219,10 @@ hipError_t drfe_launch_voxel_grid(const float* d_pts, const int2* d_jobs, int nj
         resident = perCu * (cus > 0 ? cus : 256);
     }
     hipLaunchKernelGGL(k_voxel_jobs_order, dim3(1), dim3(1024), 0, s, d_jobs, njobs, d_list + 2, d_list, d_counts);
-    hipLaunchKernelGGL(k_voxel_grid, dim3(njobs < resident ? njobs : resident), dim3(VOX_T), ORD_DYN_LDS_BYTES(VOX_T), s, d_pts, d_jobs, (const int*)(d_list + 2), d_list,
-                       d_recs, d_tmp, d_posL, d_posR, d_out, d_counts, leafSize);
+    /* tests cap the grid so that one workgroup takes job after job (drfe_debug_device_voxel_grid) */
+    const int grid = workgroups > 0 && workgroups < resident ? workgroups : resident;
+    hipLaunchKernelGGL(k_voxel_grid, dim3(njobs < grid ? njobs : grid), dim3(VOX_T), ORD_DYN_LDS_BYTES(VOX_T), s, d_pts, d_jobs, (const int*)(d_list + 2), d_list,
+                       d_recs, d_tmp, d_posL, d_posR, d_out, d_counts, leafSize, depthLimit);
     return hipGetLastError();
 }
 

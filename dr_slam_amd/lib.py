@@ -37,7 +37,7 @@ SYMBOLS = (
     "drfe_search_by_bow", "drfe_search_by_bow_kf", "drfe_search_for_triangulation", "drfe_lsd_extract", "drfe_lsd_extract_batch", "drfe_lsd_stages", "drfe_lines_is_good", "drfe_lsd_search_by_descriptor", "drfe_lsd_search_for_triangulation", "drfe_lsd_search_by_projection_last",
     "drfe_lsd_search_by_projection_map", "drfe_plane_voxel_grid", "drfe_plane_refit", "drfe_planes_ahc_postprocess",
     "drfe_planes_cape_postprocess", "drfe_surface_normals", "drfe_surface_normals_batch", "drfe_surface_normals_download", "drfe_batch_download_async", "drfe_orb_fast_partition", "drfe_lsd_segments_host", "drfe_orb_keypoint_pixels_async", "drfe_gather_keypoint_depth",
-    "drfe_frame_stereo_grid_batch_kpdepth", "drfe_planes_ahc_post_batch", "drfe_planes_ahc_from_blocks", "drfe_debug_ahc_trials", "drfe_debug_order_sort", "drfe_search_for_initialization", "drfe_lsd_fuse_search_sim3", "drfe_lsd_search_by_projection_kf",
+    "drfe_frame_stereo_grid_batch_kpdepth", "drfe_planes_ahc_post_batch", "drfe_planes_ahc_from_blocks", "drfe_debug_ahc_trials", "drfe_debug_order_sort", "drfe_debug_order_sort_heap_max", "drfe_debug_device_voxel_grid", "drfe_debug_plane_refit", "drfe_search_for_initialization", "drfe_lsd_fuse_search_sim3", "drfe_lsd_search_by_projection_kf",
     "drfe_lsd_search_by_sim3", "drfe_frame_submit", "drfe_frame_collect", "drfe_pipeline_create", "drfe_pipeline_destroy",
     "drfe_pipeline_depth", "drfe_pipeline_context", "drfe_pipeline_last_error", "drfe_pipeline_submit", "drfe_pipeline_sync",
     "drfe_lsd_configure", "drfe_lsd_configure_rect", "drfe_shard_unique_id", "drfe_shard_create", "drfe_shard_destroy", "drfe_shard_broadcast", "drfe_shard_reduce_report", "drfe_shard_sequences_of_rank", "drfe_shard_last_error", "drfe_planes_configure_cape", "drfe_planes_cape_stats", "drfe_lsd_configure_nfa", "drfe_lsd_stats", "drfe_lsd_segments_host_mode", "drfe_debug_cr_sincos", "drfe_debug_device_order_sort", "drfe_debug_device_order_sort_depth", "drfe_batch_status_async", "drfe_batch_check", "drfe_frame_submit_tracked", "drfe_frame_collect_tracked", "drfe_planes_cape_batch", "drfe_planes_configure", "drfe_planes_configure_extractor", "drfe_planes_ahc_stats", "drfe_planes_configure_refit", "drfe_planes_refit_stats", "drfe_frame_load", "drfe_bow_transform_slot", "drfe_long_kernel_clock", "drfe_long_kernel_ms",
@@ -368,6 +368,9 @@ def load() -> C.CDLL:
     L.drfe_planes_ahc_post_batch.argtypes = [vp, vp, sz, i32, i32, sz, i32, vp, f32, f32, f64, vp, i32, vp, vp, vp, vp, vp, i32]
     L.drfe_debug_ahc_trials.argtypes = [vp, vp, i32, i32, vp]
     L.drfe_debug_order_sort.argtypes = [vp, sz, i32, i32, i32, C.c_uint32]
+    L.drfe_debug_order_sort_heap_max.argtypes = [vp, sz, i32, i32, C.POINTER(sz)]
+    L.drfe_debug_device_voxel_grid.argtypes = [vp, vp, vp, i32, f32, i32, i32, vp, vp, vp]
+    L.drfe_debug_plane_refit.argtypes = [vp, i32, vp, i32, vp, vp, vp, f32, f64, vp, vp]
     L.drfe_planes_ahc_from_blocks.argtypes = [vp, vp, vp, i32, i32, sz, vp, f32, vp, i32, C.POINTER(i32), vp, vp, vp]
     L.drfe_planes_cape_postprocess.argtypes = [vp, vp, i32, i32, sz, vp, vp, vp, i32, f32, f64, vp, vp, vp, i32,
                                                C.POINTER(i32), C.POINTER(i32)]
@@ -537,6 +540,43 @@ def plane_refit(coef4, xyz, dist_threshold):
     if rc != 0:
         raise DrfeError(f"drfe_plane_refit failed ({rc})")
     return bool(v.value), c
+
+
+def debug_order_sort_heap_max(recs, kind, depth_limit=-1):
+    """Test hook: uint32 keys (kind 0) / uint64 records (kind 1) through the plain transcription of libstdc++'s introsort
+    (drfe_debug_order_sort mode 3) -> (sorted copy, longest range that reached std::__partial_sort or 0).  Host code."""
+    L = load()
+    r = np.ascontiguousarray(recs, np.uint32 if kind == 0 else np.uint64).copy()
+    longest = C.c_size_t(0)
+    rc = L.drfe_debug_order_sort_heap_max(_p(r), len(r), kind, depth_limit, C.byref(longest))
+    if rc != 0:
+        raise DrfeError(f"drfe_debug_order_sort_heap_max failed ({rc})")
+    return r, int(longest.value)
+
+
+def _csr(clouds):
+    off = np.zeros(len(clouds) + 1, np.int32)
+    off[1:] = np.cumsum([len(c) for c in clouds])
+    xyz = np.ascontiguousarray(np.concatenate([np.asarray(c, np.float32).reshape(-1, 3) for c in clouds]) if len(clouds) else np.zeros((0, 3)), np.float32)
+    return xyz, off
+
+
+def debug_plane_refit(ctx, on_device, planes, clouds, max_point_dist, dist_threshold, vcounts_override=None):
+    """Test hook: gates + refit of hand-built PLANE_DTYPE records, one [n, 3] voxel cloud each, through k_plane_refit (on_device,
+    ctx a Context) or the host loop (ctx may be None) -> (post [n_planes] PLANE_POST_DTYPE, status [n_planes + 1]: 0 final,
+    1 not certified, 2 grid came back, -1 no such plane - the job past the last plane)."""
+    L = load()
+    pl = np.ascontiguousarray(planes, PLANE_DTYPE)
+    xyz, off = _csr(clouds)
+    assert len(clouds) == len(pl) >= 1
+    ov = None if vcounts_override is None else np.ascontiguousarray(vcounts_override, np.int32)
+    post = np.zeros(len(pl), PLANE_POST_DTYPE)
+    status = np.full(len(pl) + 1, 99, np.int32)
+    rc = L.drfe_debug_plane_refit(ctx.h if ctx is not None else None, 1 if on_device else 0, _p(pl), len(pl), _p(xyz), _p(off), _p(ov) if ov is not None else None,
+                                  np.float32(max_point_dist), float(dist_threshold), _p(post), _p(status))
+    if rc != 0:
+        raise DrfeError(f"drfe_debug_plane_refit failed ({rc}): {ctx.last_error() if ctx is not None else ''}")
+    return post, status
 
 
 def manhattan_track_host(R, recs, line_dirs=None, n_calls=3):
@@ -1866,6 +1906,20 @@ class Context:
     def planes_configure_refit(self, on_device=True):
         """Where planes_ahc_post_batch runs gates + RANSAC refit: the device behind the device voxel grids (default) or the host pool."""
         self._chk(self.L.drfe_planes_configure_refit(self.h, 1 if on_device else 0), "drfe_planes_configure_refit")
+
+    def debug_device_voxel_grid(self, clouds, leaf=0.05, depth_limit=-1, workgroups=0, recs=True):
+        """Test hook: up to 256 [n, 3] float32 clouds through one device voxel-grid lane (k_voxel_jobs_order + k_voxel_grid) ->
+        (counts [n_clouds] as the kernel wrote them: >= 0 centroids, -1 grid beyond int32, -2 heap-sort hand-back, <= -9 a loop
+        bound; centroids: list of [count, 3] arrays, empty where count <= 0; records: list of the sorted leaf << 32 | point uint64
+        arrays, or None)."""
+        xyz, off = _csr(clouds)
+        out = np.zeros_like(xyz)
+        counts = np.zeros(len(clouds), np.int32)
+        rec = np.zeros(len(xyz), np.uint64) if recs else None
+        self._chk(self.L.drfe_debug_device_voxel_grid(self.h, _p(xyz), _p(off), len(clouds), np.float32(leaf), depth_limit, workgroups, _p(out), _p(counts),
+                                                      _p(rec) if recs else None), "drfe_debug_device_voxel_grid")
+        cent = [out[off[i]:off[i] + max(0, int(counts[i]))].copy() for i in range(len(clouds))]
+        return counts, cent, ([rec[off[i]:off[i + 1]].copy() for i in range(len(clouds))] if recs else None)
 
     def planes_refit_stats(self):
         out = np.zeros(2, np.int64)

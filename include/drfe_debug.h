@@ -35,6 +35,32 @@ int drfe_debug_ahc_trials(const double* sums9, const int32_t* N, int n, int mode
  * and come out in std::sort's order, the rest follows unsorted within its bins' ranges (what the product asks for: pixels
  * without a level-line angle never seed a region).  DRFE_ERR_STATE if this CPU lacks AVX2 (mode 2).  Host code. */
 int drfe_debug_order_sort(void* recs, size_t n, int kind, int mode, int depth_limit, uint32_t skip_below);
+/* The same records through mode 3 (the plain transcription; depth_limit as above), which also reports in *longest the longest range
+ * that ran out of depth and reached std::__partial_sort, 0 if none did.  The device sorts partition identically and leave ranges
+ * above 1024 records (introsort_device.h: ORD_HEAP_MAX) to the host: they hand an input back if and only if *longest > 1024.
+ * Host code. */
+int drfe_debug_order_sort_heap_max(void* recs, size_t n, int kind, int depth_limit, size_t* longest);
+
+/* Test hook of voxel_kernels.hip (the uint64 / 256-thread instantiation of introsort_device.h): n_clouds hand-built clouds in CSR
+ * form (cloud i = points [offsets[i], offsets[i + 1]) of xyz, n_clouds <= 256) through one device voxel-grid lane, k_voxel_jobs_order
+ * + k_voxel_grid, the code path of the batch post-processing.  out_xyz (as large as xyz): cloud i's centroids from offsets[i] on;
+ * out_counts[i]: the kernel's raw count - their number, or -1 (the grid exceeds int32: PCL keeps the input), -2 (a range above 1024
+ * records reached the heap-sort branch: the caller's host path), <= -9 (a loop bound of the sort: never).  out_recs (optional, as
+ * many as points): cloud i's sorted leaf << 32 | point records.  depth_limit >= 0 replaces introsort's 2 lg n (compare with
+ * drfe_debug_order_sort, kind 1, mode 3), -1 is the natural limit.  workgroups > 0 caps the launch's grid, so that one workgroup
+ * takes job after job; 0 is the product's resident count. */
+int drfe_debug_device_voxel_grid(drfe_ctx* ctx, const float* xyz, const int32_t* offsets, int n_clouds, float leaf, int depth_limit, int workgroups,
+                                 float* out_xyz, int32_t* out_counts, uint64_t* out_recs);
+
+/* Test hook of the gates and the RANSAC refit behind the voxel grids (Frame::MaxPointDistanceFromPlane): n_planes hand-built
+ * extractor planes, each with a hand-built voxel cloud (plane i = points [coarse_offsets[i], coarse_offsets[i + 1]) of coarse_xyz).
+ * on_device = 1: refit_kernels.hip's k_plane_refit over n_planes + 1 jobs of one fabricated frame (the last job is past the
+ * frame's planes); status[n_planes + 1] is the kernel's raw status: 0 post[i] is final, 1 not certified (the product refits on the
+ * host), 2 the plane's voxel grid came back, -1 no such plane; post[i] is written where status is 0 or 2.  vcounts_override
+ * (optional, n_planes): the voxel count the kernel is told, a negative one marks the grid as handed back.  on_device = 0:
+ * planes_post.cpp's host loop on the same data, status 0 (-1 for the last).  ctx may be NULL then. */
+int drfe_debug_plane_refit(drfe_ctx* ctx, int on_device, const drfe_plane* planes, int n_planes, const float* coarse_xyz, const int32_t* coarse_offsets,
+                           const int32_t* vcounts_override, float max_point_dist, double dist_threshold, drfe_plane_post* post, int32_t* status);
 
 /* Test hook of include/drfe_math.h's canonical libm of the Manhattan-frame tracker: out[i] = drfe_asin(x[i]) (which 0),
  * drfe_exp(x[i]) (which 1) or drfe_tanf((float)x[i]) widened to double (which 2).  Host code. */

@@ -340,7 +340,8 @@ def test_every_cap_is_refused_not_truncated():
 def test_native_caller_on_the_host_entry(tmp_path, which):
     """tests/native/initializer_caller.cpp: Planar_SLAM::Initializer with the reference's constructor and Initialize signature,
     forced to the host entry, against the ctypes path"""
-    exe = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "initializer_caller")
+    import native_build
+    exe = native_build.caller("initializer_caller")          # built here if the tests directory holds no build products
     s = dict(planar=inp.planted_planar(20), too_few=inp.planted(np.random.default_rng(2), 5, extra1=2, max_iterations=3),
              short_baseline=inp.planted(np.random.default_rng(1), 85, extra1=4, extra2=2, max_iterations=20, baseline=0.01))[which]
     (tmp_path / "in.bin").write_bytes(inp.caller_blob(s))

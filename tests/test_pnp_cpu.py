@@ -293,7 +293,8 @@ def test_native_candidate_loop_on_the_host_entry(tmp_path, verdicts):
     tail when a walk runs off it) against the walk over the ctypes host tables"""
     import os
     import subprocess
-    exe = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "pnp_caller")
+    import native_build
+    exe = native_build.caller("pnp_caller")          # built here if the tests directory holds no build products
     blob, problems, indices, n_keys = pn.caller_scene(np.random.default_rng(61), verdicts)
     (tmp_path / "in.bin").write_bytes(blob)
     p = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin"), "host"], capture_output=True, text=True, timeout=300)

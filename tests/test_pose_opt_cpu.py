@@ -222,7 +222,8 @@ def test_native_caller_on_the_host_entry(tmp_path, mode):
     """tests/native/pose_opt_caller.cpp: Planar_SLAM::Optimizer::PoseOptimization frame by frame, then drfe::PoseOptBatch over all
     frames, forced to the host entry or left at DRFE_POSEOPT_DEVICE_FROM (64 frames: these four go to the host entry), against the ctypes path"""
     import subprocess
-    exe = os.path.join(ROOT, "tests", "native", "pose_opt_caller")
+    import native_build
+    exe = native_build.caller("pose_opt_caller")          # built here if the tests directory holds no build products
     frames = pn.caller_frames()
     (tmp_path / "in.bin").write_bytes(pn.caller_blob(frames))
     p = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin"), mode], capture_output=True, text=True, timeout=300)

@@ -285,7 +285,8 @@ def test_invalid_shapes_are_refused():
 def test_native_candidate_loop_on_the_host(tmp_path, fix_scale):
     """tests/native/sim3_caller.cpp without a device: Planar_SLAM::Sim3Solver's reference signatures over the host entry give what
     the walk over the ctypes table gives, through the adaptor's own compaction (bad, missing and unlisted map points)"""
-    exe = os.path.join(os.path.dirname(os.path.abspath(__file__)), "native", "sim3_caller")
+    import native_build
+    exe = native_build.caller("sim3_caller")          # built here if the tests directory holds no build products
     blob, problems, indices, n1 = sn.caller_scene(np.random.default_rng(61 + fix_scale), fix_scale)
     (tmp_path / "in.bin").write_bytes(blob)
     p = subprocess.run([exe, str(tmp_path / "in.bin"), str(tmp_path / "out.bin"), "host"], capture_output=True, text=True, timeout=300)

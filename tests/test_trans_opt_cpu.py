@@ -258,7 +258,8 @@ def test_native_caller_on_the_host_entry(tmp_path, mode):
     over all frames, forced to the host entry or left at DRFE_TRANSOPT_DEVICE_FROM (these four frames go to the host entry),
     against the ctypes path"""
     import subprocess
-    exe = os.path.join(ROOT, "tests", "native", "trans_opt_caller")
+    import native_build
+    exe = native_build.caller("trans_opt_caller")          # built here if the tests directory holds no build products
     frames = tn.caller_frames()
     assert len(frames) < lib.TRANSOPT_DEVICE_FROM
     (tmp_path / "in.bin").write_bytes(pn.caller_blob(frames))
