@@ -10,6 +10,7 @@
 #include "line3d_internal.h"
 #include "pose_opt_internal.h"
 #include "trans_opt_internal.h"
+#include "sim3_opt_internal.h"
 #include <atomic>
 #include "post_internal.h"
 #include "match_internal.h"
@@ -162,6 +163,7 @@ void drfe_destroy(drfe_ctx* c)
     drfe_line3d_free(c);
     drfe_pose_opt_free(c);
     drfe_trans_opt_free(c);
+    drfe_sim3_opt_free(c);
     drfe_post_free(c);
     drfe_one_shot_free(c);
     drfe_frame_lanes_free(c);

@@ -192,6 +192,7 @@ struct drfe_ctx {
     struct InitBuffers* init = nullptr; /* Initializer RANSAC staging, scratch and counters (init.cpp) */
     struct PoseOptBuffers* pose_opt = nullptr; /* PoseOptimization staging, scratch and counters (pose_opt.cpp) */
     struct TransOptBuffers* trans_opt = nullptr; /* TranslationOptimization staging, scratch and counters (trans_opt.cpp) */
+    struct Sim3OptBuffers* sim3_opt = nullptr; /* OptimizeSim3 staging, scratch and counters (sim3_opt.cpp) */
     struct Line3dBuffers* line3d = nullptr;   /* isLineGood batch staging, scratch and counters (lines_3d_batch.cpp) */
     std::vector<struct LineWorker>* lineWorkers;   /* lanes of drfe_lsd_extract_batch (lines_lsd.cpp) */
     struct LinesScratch* lsBatch; /* frame slots of drfe_lsd_extract_batch's device region growing (lines_lsd.cpp) */

@@ -395,12 +395,14 @@ DRFE_HD void po_lm_init(PoLM& S, int libm)
 
 /* Eigen::LDLT<MatrixXd>::compute of the 6x6 whose lower triangle is A (full storage, row-major; the upper triangle is not
  * read), in place (ldlt_inplace<Lower>::unblocked, Eigen 3.3.7), then solve(b) into x when isPositive().  Returns isPositive().
- * Dot products and the rank update's products are summed over the inner index from 0 up. */
-DRFE_HD int po_ldlt_solve(double A[6][6], const double b[6], double x[6])
+ * Dot products and the rank update's products are summed over the inner index from 0 up.  The size is a template argument: the
+ * 7x7 of the Sim3 vertex (sim3_opt_core.h) runs the same statements. */
+template <int N>
+DRFE_HD int po_ldlt_solve_n(double A[N][N], const double b[N], double x[N])
 {
-    const int n = 6;
-    int tr[6];
-    double temp[6];
+    const int n = N;
+    int tr[N];
+    double temp[N];
     int sign = 0;                                  /* 0 ZeroSign, 1 PositiveSemiDef, -1 NegativeSemiDef, 2 Indefinite */
     bool early = false;                            /* (found_zero_pivot only decides info(), which g2o does not read) */
     for (int k = 0; k < n && !early; k++) {
@@ -450,7 +452,7 @@ DRFE_HD int po_ldlt_solve(double A[6][6], const double b[6], double x[6])
     }
     if (!(sign == 1 || sign == 0)) return 0;
     /* LDLT::_solve_impl: P b; L^-1 (column by column); D^-1 with the tolerance 1 / highest(); L^-T (row by row); P^T */
-    double d[6];
+    double d[N];
     for (int i = 0; i < n; i++) d[i] = b[i];
     for (int k = 0; k < n; k++) { const double s = d[k]; d[k] = d[tr[k]]; d[tr[k]] = s; }
     for (int i = 0; i < n; i++)
@@ -470,6 +472,7 @@ DRFE_HD int po_ldlt_solve(double A[6][6], const double b[6], double x[6])
     for (int i = 0; i < n; i++) x[i] = d[i];
     return 1;
 }
+DRFE_HD int po_ldlt_solve(double A[6][6], const double b[6], double x[6]) { return po_ldlt_solve_n<6>(A, b, x); }
 
 /* VertexSE3Expmap::oplusImpl: estimate = SE3Quat::exp(u) * estimate (types/se3quat.h:227-261, :104-110) */
 DRFE_HD int po_oplus(PoCtx& ctx, double q[4], double t[3], const double u[6])

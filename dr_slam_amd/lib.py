@@ -60,6 +60,8 @@ SYMBOLS = (
     "drfe_debug_pose_opt_hand_back", "drfe_debug_pose_opt_plane_error",
     "drfe_trans_opt_host", "drfe_trans_opt_batch", "drfe_trans_opt_stats", "drfe_debug_trans_opt_hand_back",
     "drfe_debug_trans_opt_plane_error",
+    "drfe_sim3_opt_host", "drfe_sim3_opt_batch", "drfe_sim3_opt_stats", "drfe_debug_sim3_opt_ldlt", "drfe_debug_sim3_opt_step",
+    "drfe_debug_sim3_opt_hand_back",
 )
 
 FRUSTUM_POINT_DTYPE = np.dtype([("world", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"),
@@ -207,6 +209,23 @@ POSE_OPT_STATS = ("calls", "frames", "point_edges", "line_plane_edges", "iterati
 
 class PoseOptOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in POSE_OPT_OUT_FIELDS]                        # drfe_pose_opt_out
+
+
+SIM3_OPT_IN_FIELDS = ("S12", "K1", "K2", "R1w", "t1w", "R2w", "t2w", "th2", "fix_scale", "match_offsets", "index", "P3D1w", "P3D2w",
+                      "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2")
+SIM3_OPT_OUT_FIELDS = ("S12", "T12", "Scw", "returns", "n_bad", "iterations", "trials", "diag", "outlier")
+SIM3_OPT_DIAG = ("rejected", "last_rejected", "nbad_stops", "small_theta", "big_theta", "early_return", "stale_decided")
+SIM3_OPT_MAX_PROBLEMS, SIM3_OPT_MAX_MATCHES = 1024, 8192
+SIM3OPT_DEVICE_FROM = 8                              # DRFE_SIM3OPT_DEVICE_FROM
+SIM3_OPT_STATS = ("calls", "problems", "matches", "free_scale", "iterations", "trials", "handed_back", "early_returns")
+
+
+class Sim3OptProblems(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_void_p) for k in SIM3_OPT_IN_FIELDS]   # drfe_sim3_opt_problems
+
+
+class Sim3OptOut(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in SIM3_OPT_OUT_FIELDS]                        # drfe_sim3_opt_out
 
 
 class InitProblems(C.Structure):
@@ -433,6 +452,12 @@ def load() -> C.CDLL:
     L.drfe_trans_opt_stats.argtypes = [vp, vp]
     L.drfe_debug_trans_opt_hand_back.argtypes = [vp, i32]
     L.drfe_debug_trans_opt_plane_error.argtypes = [i32, vp, vp, vp, vp]
+    L.drfe_sim3_opt_host.argtypes = [vp, vp]
+    L.drfe_sim3_opt_batch.argtypes = [vp, vp, vp, vp]
+    L.drfe_sim3_opt_stats.argtypes = [vp, vp]
+    L.drfe_debug_sim3_opt_ldlt.argtypes = [vp, vp, vp, vp]
+    L.drfe_debug_sim3_opt_step.argtypes = [vp, vp, i32, i32, vp, vp]
+    L.drfe_debug_sim3_opt_hand_back.argtypes = [vp, i32]
     L.drfe_pnp_stats.argtypes = [vp, vp]
     L.drfe_lines_is_good_batch.argtypes = [vp, vp, vp, vp]
     L.drfe_line3d_chunk_frames.argtypes = [i32]
@@ -1012,6 +1037,65 @@ def trans_opt_plane_error(kind, meas, world, Tcw):
     if load().drfe_debug_trans_opt_plane_error(int(kind), _p(meas), _p(world), _p(Tcw), _p(e)) != 0:
         raise DrfeError("drfe_debug_trans_opt_plane_error failed")
     return e
+
+
+def _sim3_opt_pack(problems):
+    """Packs a set of OptimizeSim3 problems (dict: S12 [n, 8] (quaternion x y z w, t, s), K1 / K2 [n, 4] (fx, fy, cx, cy), R1w / R2w
+    [n, 9], t1w / t2w [n, 3], th2 [n], fix_scale [n], match_offsets [n + 1]; per kept match index [M], P3D1w / P3D2w [M, 3], obs1 /
+    obs2 [M, 2], inv_sigma2_1 / inv_sigma2_2 [M]) into drfe_sim3_opt_problems and allocates the outputs: (problems record, out
+    record, the outputs as a dict, the arrays to keep alive).  The outputs: per problem S12 [8], T12 [16], Scw [16], returns, n_bad,
+    iterations [2], trials [2], diag [8] (SIM3_OPT_DIAG names the first seven); per match the outlier byte."""
+    keep = {}
+    kinds = dict(S12=(np.float64, (-1, 8)), K1=(np.float32, (-1, 4)), K2=(np.float32, (-1, 4)), R1w=(np.float32, (-1, 9)),
+                 t1w=(np.float32, (-1, 3)), R2w=(np.float32, (-1, 9)), t2w=(np.float32, (-1, 3)), th2=(np.float32, (-1,)),
+                 fix_scale=(np.uint8, (-1,)), match_offsets=(np.int32, (-1,)), index=(np.int32, (-1,)),
+                 P3D1w=(np.float32, (-1, 3)), P3D2w=(np.float32, (-1, 3)), obs1=(np.float32, (-1, 2)), obs2=(np.float32, (-1, 2)),
+                 inv_sigma2_1=(np.float32, (-1,)), inv_sigma2_2=(np.float32, (-1,)))
+    for k in SIM3_OPT_IN_FIELDS:
+        dt, shape = kinds[k]
+        v = np.asarray(problems.get(k, np.zeros(0)), dt)
+        keep[k] = np.ascontiguousarray(v.reshape(shape) if v.size else np.zeros((0,) + shape[1:], dt))
+    off = keep["match_offsets"]
+    n = len(off) - 1
+    nM = max(int(off[-1]), 0) if len(off) else 0
+    P = Sim3OptProblems(n, 0, *[_p(keep[k]) for k in SIM3_OPT_IN_FIELDS])
+    r = dict(S12=np.zeros((n, 8), np.float64), T12=np.zeros((n, 16), np.float32), Scw=np.zeros((n, 16), np.float32),
+             returns=np.zeros(n, np.int32), n_bad=np.zeros(n, np.int32), iterations=np.zeros((n, 2), np.int32),
+             trials=np.zeros((n, 2), np.int32), diag=np.zeros((n, 8), np.int32), outlier=np.zeros(nM, np.uint8))
+    out = Sim3OptOut(*[_p(r[k]) for k in SIM3_OPT_OUT_FIELDS])
+    return P, out, r, keep
+
+
+def sim3_opt_host(problems):
+    """Optimizer::OptimizeSim3 of every problem on the host (drfe_sim3_opt_host, DESIGN.md section 22); problems and result as
+    _sim3_opt_pack"""
+    P, out, r, _keep = _sim3_opt_pack(problems)
+    rc = load().drfe_sim3_opt_host(C.byref(P), C.byref(out))
+    if rc != 0:
+        raise DrfeError(f"drfe_sim3_opt_host failed ({rc})")
+    return r
+
+
+def sim3_opt_ldlt(A, b):
+    """the 7x7 form of pose_opt_core.h's Eigen::LDLT of the symmetric A (its lower triangle) and solve of A x = b: (isPositive, x)"""
+    A = np.ascontiguousarray(np.asarray(A, np.float64).reshape(7, 7))
+    b = np.ascontiguousarray(np.asarray(b, np.float64).reshape(7))
+    x, pos = np.zeros(7, np.float64), np.zeros(1, np.int32)
+    if load().drfe_debug_sim3_opt_ldlt(_p(A), _p(b), _p(x), _p(pos)) != 0:
+        raise DrfeError("drfe_debug_sim3_opt_ldlt failed")
+    return bool(pos[0]), x
+
+
+def sim3_opt_step(S12, x, b, lam, fix_scale, read_before=False):
+    """sim3_opt_core.h's VertexSim3Expmap::oplusImpl of x [7] on S12 [8] and Levenberg's computeScale over (x, b, lambda), read after
+    the update as g2o does or, with read_before, before oplusImpl wrote x[6] = 0 for a fixed scale: (S12 after the step, scale)"""
+    S12 = np.ascontiguousarray(np.asarray(S12, np.float64).reshape(8))
+    xbl = np.ascontiguousarray(np.concatenate([np.asarray(x, np.float64).reshape(7), np.asarray(b, np.float64).reshape(7),
+                                               np.asarray([lam], np.float64)]))
+    out, scale = np.zeros(8, np.float64), np.zeros(1, np.float64)
+    if load().drfe_debug_sim3_opt_step(_p(S12), _p(xbl), int(bool(fix_scale)), int(bool(read_before)), _p(out), _p(scale)) != 0:
+        raise DrfeError("drfe_debug_sim3_opt_step failed")
+    return out, float(scale[0])
 
 
 def cr_cube(x):
@@ -2407,6 +2491,22 @@ class Context:
     def trans_opt_hand_back(self, every):
         """test hook: the host runs every `every`-th frame of a trans_opt_batch call again as if the device had handed it back"""
         self._chk(self.L.drfe_debug_trans_opt_hand_back(self.h, int(every)), "drfe_debug_trans_opt_hand_back")
+
+    def sim3_opt_batch(self, problems):
+        """sim3_opt_host on the device (drfe_sim3_opt_batch): same outputs, same bits"""
+        P, out, r, _keep = _sim3_opt_pack(problems)
+        self._chk(self.L.drfe_sim3_opt_batch(self.h, C.byref(P), C.byref(out), None), "drfe_sim3_opt_batch")
+        return r
+
+    def sim3_opt_stats(self):
+        """drfe_sim3_opt_stats as a dict over SIM3_OPT_STATS"""
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_sim3_opt_stats(self.h, _p(st)), "drfe_sim3_opt_stats")
+        return dict(zip(SIM3_OPT_STATS, st.tolist()))
+
+    def sim3_opt_hand_back(self, every):
+        """test hook: the host runs every `every`-th problem of a sim3_opt_batch call again as if the device had not certified it"""
+        self._chk(self.L.drfe_debug_sim3_opt_hand_back(self.h, int(every)), "drfe_debug_sim3_opt_hand_back")
 
     def init_ransac_batch(self, problems):
         """init_ransac_host on the device (drfe_init_ransac_batch): same outputs, same bits"""

@@ -1426,6 +1426,70 @@ int drfe_trans_opt_batch(drfe_ctx* ctx, const drfe_pose_opt_problems* problems, 
  * returned before the loop (fewer than 3 points). */
 int drfe_trans_opt_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
 
+/* Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (src/Optimizer.cc:3982-4177), the fourth of the five
+ * steps LoopClosing::ComputeSim3 runs per loop candidate, between SearchBySim3 and SearchByProjection(KF, Scw): every problem of a
+ * call at once.  DESIGN.md section 22.
+ *
+ * A problem is the Sim3 estimate, the two key frames' intrinsics and poses, th2, bFixScale and its kept matches in index order:
+ * the caller leaves out a match whose vpMatches1[i] is NULL, whose map point of either side is NULL or bad, or whose i2 is below 0,
+ * as the reference's `continue`s do.  The two optimize() calls, the two classifications, the numeric Jacobians and what g2o and
+ * Eigen run under them are restated; parity with a g2o / Eigen 3.3.7 build is not pinned yet.
+ * Caps: DRFE_SIM3_OPT_MAX_PROBLEMS problems per call, DRFE_SIM3_OPT_MAX_MATCHES kept matches per problem; above them the call is
+ * refused (DRFE_ERR_INVALID), as are decreasing offsets. */
+enum { DRFE_SIM3_OPT_MAX_PROBLEMS = 1024, DRFE_SIM3_OPT_MAX_MATCHES = 8192 };
+/* problems in a call from which drfe::Sim3OptBatch uses the device entry (the measured crossover) */
+enum { DRFE_SIM3OPT_DEVICE_FROM = 8 };
+typedef struct drfe_sim3_opt_problems {
+    int32_t n;                   /* problems */
+    int32_t pad;
+    const double* S12;           /* n x 8: g2oS12 as rotation().coeffs() (x y z w), translation(), scale() */
+    const float* K1;             /* n x 4: fx, fy, cx, cy of pKF1->mK */
+    const float* K2;             /* n x 4: of pKF2->mK */
+    const float* R1w;            /* n x 9: pKF1->GetRotation(), row-major */
+    const float* t1w;            /* n x 3: pKF1->GetTranslation() */
+    const float* R2w;            /* n x 9 */
+    const float* t2w;            /* n x 3 */
+    const float* th2;            /* n */
+    const uint8_t* fix_scale;    /* n: bFixScale */
+    const int32_t* match_offsets; /* n + 1: problem p's matches are [match_offsets[p], match_offsets[p + 1]); [0] == 0 */
+    const int32_t* index;        /* per match: i, increasing within a problem; the entry only checks it.  May be NULL */
+    const float* P3D1w;          /* 3 per match: vpMapPoints1[i]->GetWorldPos() */
+    const float* P3D2w;          /* 3 per match: vpMatches1[i]->GetWorldPos() */
+    const float* obs1;           /* 2 per match: pKF1->mvKeysUn[i].pt */
+    const float* obs2;           /* 2 per match: pKF2->mvKeysUn[i2].pt */
+    const float* inv_sigma2_1;   /* per match: pKF1->mvInvLevelSigma2[kpUn1.octave] */
+    const float* inv_sigma2_2;   /* per match: pKF2->mvInvLevelSigma2[kpUn2.octave] */
+} drfe_sim3_opt_problems;
+/* The per-match arrays may be NULL when no problem has a match.  diag may be NULL. */
+typedef struct drfe_sim3_opt_out {
+    double* S12;                 /* n x 8: g2oS12 after the call; the input's bits when the call returns before the second optimize() */
+    float* T12;                  /* n x 16: Converter::toCvMat(g2oS12) of that estimate */
+    float* Scw;                  /* n x 16: Converter::toCvMat(g2oS12 * g2o::Sim3(toMatrix3d(R2w), toVector3d(t2w), 1.0)), mScw of
+                                    src/LoopClosing.cc:379-381 */
+    int32_t* returns;            /* n: nIn, or 0 when fewer than 10 matches are left after the first classification */
+    int32_t* n_bad;              /* n: nBad of the first classification */
+    int32_t* iterations;         /* n x 2: Levenberg iterations of the first and the second optimize() */
+    int32_t* trials;             /* n x 2: trial steps (linear solves) of each */
+    int32_t* diag;               /* n x 8: [0] rejected trials, [1] optimize() calls whose last trial was rejected (the classification
+                                    after them reads the errors at the rejected estimate), [2] calls stopped by _nBad >= 3, [3] updates
+                                    with theta < 1e-5, [4] with theta >= 1e-5, [5] 1 for the return before the second optimize(),
+                                    [6] matches that the errors at the rejected estimate classified differently from the errors at the
+                                    kept one, [7] 0 */
+    uint8_t* outlier;            /* per match: vpMatches1[i] was set to NULL by either classification */
+} drfe_sim3_opt_out;
+/* On the host, no context. */
+int drfe_sim3_opt_host(const drfe_sim3_opt_problems* problems, drfe_sim3_opt_out* out);
+/* The same on the device: the inputs staged with one copy, one launch (a workgroup per problem runs both optimize() calls and both
+ * classifications), the results back with one copy; returns with the outputs written (`stream` NULL = the context's).  A problem
+ * with a free scale needs exp, which has no certified form on the device: the host core runs it inside the same call while the
+ * launch is in flight.  Same bits as the host entry.  For a free scale both entries use the host libm's exp: their bits agree with
+ * each other, and depend on that libm in the last place where its exp is not the correctly rounded one. */
+int drfe_sim3_opt_batch(drfe_ctx* ctx, const drfe_sim3_opt_problems* problems, drfe_sim3_opt_out* out, void* stream);
+/* Counters since the context was created: stats[0] batch calls, [1] problems, [2] kept matches, [3] problems with a free scale, run
+ * by the host core, [4] Levenberg iterations, [5] trial steps, [6] fixed-scale problems the device could not certify (sin / cos,
+ * x^3) and the host finished, [7] problems that returned before the second optimize(). */
+int drfe_sim3_opt_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

@@ -2928,6 +2928,133 @@ private:
 
 template <class FrameT> using TransOptBatch = PoseOptBatch<FrameT, true>;
 
+/* Optimizer::OptimizeSim3 (src/Optimizer.cc:3982-4177) for one loop candidate or for the live candidates of one round of
+ * LoopClosing::ComputeSim3's loop (src/LoopClosing.cc:333-388): Add() flattens what the reference reads of a candidate, leaving out
+ * a match as its `continue`s do (vpMatches1[i] NULL, either map point NULL or bad, i2 < 0); Run() optimises every added candidate
+ * by one drfe_sim3_opt_batch call (or, below `deviceFrom` candidates, by the host entry: same bits) and writes back what the
+ * reference writes: vpMatches1[i] = NULL for the matches either classification rejects, and g2oS12.  Result(i) is the i-th added
+ * candidate's return value, Scw(i) its mScw = toCvMat(g2oS12 * Sim3(R2w, t2w, 1)), T12(i) toCvMat(g2oS12).  An object belongs to
+ * one thread.  DESIGN.md section 22.  No g2o here:
+ * Sim3T: rotation() with x() y() z() w(), translation() with operator[], scale(), each also as a reference to write through
+ * (g2o::Sim3 is one).  KeyFrameT: mK (3x3 float), GetRotation(), GetTranslation(), GetMapPointMatches(), mvKeysUn,
+ * mvInvLevelSigma2.  MapPointT: isBad(), GetWorldPos(), GetIndexInKeyFrame(KeyFrameT*). */
+template <class KeyFrameT, class MapPointT, class Sim3T>
+class Sim3OptBatch {
+public:
+    explicit Sim3OptBatch(int device = 0, int deviceFrom = (int)DRFE_SIM3OPT_DEVICE_FROM) : mDevice(device), mDeviceFrom(deviceFrom) { Clear(); }
+    /* true / false: the device / the host entry whatever the number of candidates */
+    void UseDevice(bool on) { mDeviceFrom = on ? 0 : 2147483647; }
+    void Clear()
+    {
+        mMatches.clear(); mSims.clear(); mS12.clear(); mK1.clear(); mK2.clear(); mR1w.clear(); mt1w.clear(); mR2w.clear(); mt2w.clear();
+        mTh2.clear(); mFix.clear(); mOff.assign(1, 0); mIdx.clear(); mP1.clear(); mP2.clear(); mObs1.clear(); mObs2.clear();
+        mInv1.clear(); mInv2.clear();
+    }
+    size_t size() const { return mSims.size(); }
+    void Add(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches1, Sim3T& g2oS12, const float th2, const bool bFixScale)
+    {
+        using Planar_SLAM::drfe_detail::mat_f;
+        mMatches.push_back(&vpMatches1);
+        mSims.push_back(&g2oS12);
+        const auto& r = g2oS12.rotation();
+        mS12.push_back(r.x()); mS12.push_back(r.y()); mS12.push_back(r.z()); mS12.push_back(r.w());
+        for (int k = 0; k < 3; k++) mS12.push_back(g2oS12.translation()[k]);
+        mS12.push_back(g2oS12.scale());
+        KeyFrameT* kf[2] = {pKF1, pKF2};
+        std::vector<float>* K[2] = {&mK1, &mK2};
+        std::vector<float>* R[2] = {&mR1w, &mR2w};
+        std::vector<float>* t[2] = {&mt1w, &mt2w};
+        for (int q = 0; q < 2; q++) {
+            K[q]->push_back(mat_f(kf[q]->mK, 0, 0)); K[q]->push_back(mat_f(kf[q]->mK, 1, 1));
+            K[q]->push_back(mat_f(kf[q]->mK, 0, 2)); K[q]->push_back(mat_f(kf[q]->mK, 1, 2));
+            const auto Rm = kf[q]->GetRotation();
+            const auto tm = kf[q]->GetTranslation();
+            for (int i = 0; i < 3; i++)
+                for (int j = 0; j < 3; j++) R[q]->push_back(mat_f(Rm, i, j));
+            for (int i = 0; i < 3; i++) t[q]->push_back(mat_f(tm, i));
+        }
+        mTh2.push_back(th2);
+        mFix.push_back(bFixScale ? 1 : 0);
+        const int N = (int)vpMatches1.size();
+        const auto vpMapPoints1 = pKF1->GetMapPointMatches();
+        for (int i = 0; i < N; i++) {
+            if (!vpMatches1[(size_t)i]) continue;
+            MapPointT* pMP1 = vpMapPoints1[(size_t)i];
+            MapPointT* pMP2 = vpMatches1[(size_t)i];
+            const int i2 = pMP2->GetIndexInKeyFrame(pKF2);
+            if (!pMP1 || !pMP2 || pMP1->isBad() || pMP2->isBad() || i2 < 0) continue;
+            const auto P3D1w = pMP1->GetWorldPos();
+            const auto P3D2w = pMP2->GetWorldPos();
+            for (int k = 0; k < 3; k++) { mP1.push_back(mat_f(P3D1w, k)); mP2.push_back(mat_f(P3D2w, k)); }
+            const auto& kpUn1 = pKF1->mvKeysUn[(size_t)i];
+            const auto& kpUn2 = pKF2->mvKeysUn[(size_t)i2];
+            mObs1.push_back(kpUn1.pt.x); mObs1.push_back(kpUn1.pt.y);
+            mObs2.push_back(kpUn2.pt.x); mObs2.push_back(kpUn2.pt.y);
+            mInv1.push_back(pKF1->mvInvLevelSigma2[(size_t)kpUn1.octave]);
+            mInv2.push_back(pKF2->mvInvLevelSigma2[(size_t)kpUn2.octave]);
+            mIdx.push_back(i);
+        }
+        mOff.push_back((int32_t)mIdx.size());
+    }
+    /* optimises every added candidate and writes the matches and estimates back; the batch is empty afterwards but for Result(),
+     * T12() and Scw() */
+    void Run()
+    {
+        const size_t n = mSims.size();
+        std::vector<double> S12(8 * n + 1);
+        std::vector<int32_t> nBad(n + 1), its(2 * n + 1), trials(2 * n + 1);
+        std::vector<uint8_t> outlier(mIdx.size() + 1);
+        mReturns.assign(n, 0); mT12.assign(16 * n, 0.f); mScw.assign(16 * n, 0.f);
+        drfe_sim3_opt_problems in = {};
+        in.n = (int32_t)n;
+        in.S12 = mS12.data(); in.K1 = mK1.data(); in.K2 = mK2.data(); in.R1w = mR1w.data(); in.t1w = mt1w.data();
+        in.R2w = mR2w.data(); in.t2w = mt2w.data(); in.th2 = mTh2.data(); in.fix_scale = mFix.data(); in.match_offsets = mOff.data();
+        in.index = mIdx.data(); in.P3D1w = mP1.data(); in.P3D2w = mP2.data(); in.obs1 = mObs1.data(); in.obs2 = mObs2.data();
+        in.inv_sigma2_1 = mInv1.data(); in.inv_sigma2_2 = mInv2.data();
+        drfe_sim3_opt_out out = {S12.data(), mT12.data(), mScw.data(), mReturns.data(), nBad.data(), its.data(), trials.data(), nullptr,
+                                 outlier.data()};
+        struct ClearOnExit {                           /* also when an entry refuses the call: the batch never keeps stale candidates */
+            Sim3OptBatch* b;
+            ~ClearOnExit() { b->Clear(); }
+        } clearOnExit{this};
+        if (n) {
+            if ((int64_t)n < (int64_t)mDeviceFrom) {
+                if (drfe_sim3_opt_host(&in, &out) != DRFE_OK) {
+                    mReturns.clear();
+                    throw std::runtime_error("drfe_sim3_opt_host: invalid argument");
+                }
+            } else {
+                if (!mCtx) mCtx = Planar_SLAM::drfe_detail::make_ctx(1, 1.2f, 1, 20, 7, 64, 64, 1, mDevice);
+                Planar_SLAM::drfe_detail::check(drfe_sim3_opt_batch(mCtx.get(), &in, &out, nullptr), mCtx.get(), "drfe_sim3_opt_batch");
+            }
+        }
+        for (size_t f = 0; f < n; f++) {
+            for (int32_t k = mOff[f]; k < mOff[f + 1]; k++)
+                if (outlier[(size_t)k]) (*mMatches[f])[(size_t)mIdx[(size_t)k]] = static_cast<MapPointT*>(nullptr);
+            Sim3T& S = *mSims[f];
+            const double* v = &S12[8 * f];
+            auto& r = S.rotation();
+            r.x() = v[0]; r.y() = v[1]; r.z() = v[2]; r.w() = v[3];
+            for (int k = 0; k < 3; k++) S.translation()[k] = v[4 + k];
+            S.scale() = v[7];
+        }
+    }
+    int Result(size_t i) const { return mReturns.at(i); }
+    drfe_cv::Mat T12(size_t i) const { return drfe_detail_sim3::mat32(4, 4, &mT12.at(16 * i)); }
+    drfe_cv::Mat Scw(size_t i) const { return drfe_detail_sim3::mat32(4, 4, &mScw.at(16 * i)); }
+    drfe_ctx* ctx() const { return mCtx.get(); }
+
+private:
+    int mDevice, mDeviceFrom;
+    Planar_SLAM::drfe_detail::CtxPtr mCtx;
+    std::vector<std::vector<MapPointT*>*> mMatches;
+    std::vector<Sim3T*> mSims;
+    std::vector<double> mS12;
+    std::vector<float> mK1, mK2, mR1w, mt1w, mR2w, mt2w, mTh2, mP1, mP2, mObs1, mObs2, mInv1, mInv2, mT12, mScw;
+    std::vector<uint8_t> mFix;
+    std::vector<int32_t> mOff, mIdx, mReturns;
+};
+
 }  // namespace drfe
 
 namespace Planar_SLAM {
@@ -2941,7 +3068,7 @@ public:
     static drfe::PlaneSettings& Settings() { static drfe::PlaneSettings s; return s; }
     static void SetPlaneSettings(const drfe::PlaneSettings& s) { Settings() = s; }
     static bool& DeviceFlag() { static bool on = 1 >= DRFE_POSEOPT_DEVICE_FROM; return on; }
-    static void UseDevice(bool on) { DeviceFlag() = on; TransDeviceFlag() = on; }
+    static void UseDevice(bool on) { DeviceFlag() = on; TransDeviceFlag() = on; Sim3DeviceFlag() = on; }
     template <class FrameT> static int PoseOptimization(FrameT* pFrame, bool bStruct)
     {
         static thread_local drfe::PoseOptBatch<FrameT> batch;       /* keeps its context between calls */
@@ -2964,8 +3091,24 @@ public:
         return batch.Result(0);
     }
 
+    /* LoopClosing::ComputeSim3's call; LastScw() is mScw of the last call on this thread (src/LoopClosing.cc:379-381) */
+    template <class KeyFrameT, class MapPointT, class Sim3T>
+    static int OptimizeSim3(KeyFrameT* pKF1, KeyFrameT* pKF2, std::vector<MapPointT*>& vpMatches1, Sim3T& g2oS12, const float th2,
+                            const bool bFixScale)
+    {
+        static thread_local drfe::Sim3OptBatch<KeyFrameT, MapPointT, Sim3T> batch;   /* keeps its context between calls */
+        batch.UseDevice(Sim3DeviceFlag());
+        batch.Clear();
+        batch.Add(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale);
+        batch.Run();
+        LastScw() = batch.Scw(0);
+        return batch.Result(0);
+    }
+    static drfe_cv::Mat& LastScw() { static thread_local drfe_cv::Mat m; return m; }
+
 private:
     static bool& TransDeviceFlag() { static bool on = 1 >= DRFE_TRANSOPT_DEVICE_FROM; return on; }
+    static bool& Sim3DeviceFlag() { static bool on = 1 >= DRFE_SIM3OPT_DEVICE_FROM; return on; }
 };
 
 }  // namespace Planar_SLAM
