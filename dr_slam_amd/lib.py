@@ -62,6 +62,10 @@ SYMBOLS = (
     "drfe_debug_trans_opt_plane_error",
     "drfe_sim3_opt_host", "drfe_sim3_opt_batch", "drfe_sim3_opt_stats", "drfe_debug_sim3_opt_ldlt", "drfe_debug_sim3_opt_step",
     "drfe_debug_sim3_opt_hand_back",
+    "drfe_kfdb_create", "drfe_kfdb_destroy", "drfe_kfdb_last_error", "drfe_kfdb_put", "drfe_kfdb_add", "drfe_kfdb_erase",
+    "drfe_kfdb_clear", "drfe_kfdb_remove", "drfe_kfdb_set_neighbours", "drfe_kfdb_size", "drfe_kfdb_loop_queries_host",
+    "drfe_kfdb_loop_queries_device", "drfe_kfdb_loop_queries_batch", "drfe_kfdb_reloc_queries_host",
+    "drfe_kfdb_reloc_queries_device", "drfe_kfdb_reloc_queries_batch", "drfe_kfdb_score", "drfe_kfdb_stats",
 )
 
 FRUSTUM_POINT_DTYPE = np.dtype([("world", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"),
@@ -226,6 +230,30 @@ class Sim3OptProblems(C.Structure):
 
 class Sim3OptOut(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in SIM3_OPT_OUT_FIELDS]                        # drfe_sim3_opt_out
+
+
+KFDB_L1_NORM, KFDB_L2_NORM, KFDB_CHI_SQUARE, KFDB_KL, KFDB_BHATTACHARYYA, KFDB_DOT_PRODUCT = range(6)   # DBoW2::ScoringType
+KFDB_NEIGHBOURS = 10
+KFDB_DEVICE_FROM = 16                                                                # DRFE_KFDB_DEVICE_FROM
+KFDB_STATS = ("loop_calls", "loop_queries", "reloc_calls", "reloc_queries", "device_calls", "uploads", "candidates",
+              "uninit_reads")
+ERR_INVALID, ERR_HIP, ERR_CAPACITY, ERR_STATE = -1, -2, -3, -4
+
+
+class KfdbLoopQueries(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "handle", "id", "connected_offsets", "connected", "min_score", "covisible_offsets", "covisible",
+        "add_after")]                                                                # drfe_kfdb_loop_queries
+
+
+class KfdbRelocQueries(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "id", "word_offsets", "word_ids", "values")]                                 # drfe_kfdb_reloc_queries
+
+
+class KfdbOut(C.Structure):
+    _fields_ = [("cand_capacity", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "cand_offsets", "candidates", "record", "min_score", "uninit_reads")]        # drfe_kfdb_out
 
 
 class InitProblems(C.Structure):
@@ -458,6 +486,23 @@ def load() -> C.CDLL:
     L.drfe_debug_sim3_opt_ldlt.argtypes = [vp, vp, vp, vp]
     L.drfe_debug_sim3_opt_step.argtypes = [vp, vp, i32, i32, vp, vp]
     L.drfe_debug_sim3_opt_hand_back.argtypes = [vp, i32]
+    L.drfe_kfdb_create.argtypes = [vp, i32, C.POINTER(vp)]
+    L.drfe_kfdb_destroy.argtypes = [vp]
+    L.drfe_kfdb_destroy.restype = None
+    L.drfe_kfdb_last_error.argtypes = [vp]
+    L.drfe_kfdb_last_error.restype = C.c_char_p
+    L.drfe_kfdb_put.argtypes = [vp, i32, i32, vp, vp]
+    for name in ("add", "erase", "remove"):
+        getattr(L, "drfe_kfdb_" + name).argtypes = [vp, i32]
+    L.drfe_kfdb_clear.argtypes = [vp]
+    L.drfe_kfdb_set_neighbours.argtypes = [vp, i32, vp, vp]
+    L.drfe_kfdb_size.argtypes = [vp, vp]
+    for kind in ("loop", "reloc"):
+        getattr(L, f"drfe_kfdb_{kind}_queries_host").argtypes = [vp, vp, vp]
+        getattr(L, f"drfe_kfdb_{kind}_queries_device").argtypes = [vp, vp, vp, vp]
+        getattr(L, f"drfe_kfdb_{kind}_queries_batch").argtypes = [vp, vp, vp, vp]
+    L.drfe_kfdb_score.argtypes = [i32, vp, vp, i32, vp, vp, vp]
+    L.drfe_kfdb_stats.argtypes = [vp, vp]
     L.drfe_pnp_stats.argtypes = [vp, vp]
     L.drfe_lines_is_good_batch.argtypes = [vp, vp, vp, vp]
     L.drfe_line3d_chunk_frames.argtypes = [i32]
@@ -1360,6 +1405,134 @@ def line3d_frames(lines, n_lines, depth, K9, cx, cy, invfx, invfy, k_as_f64=True
     r = (np.full((F, cap), -1, np.float32), np.zeros((F, cap, 6), np.float64), np.zeros((F, cap), np.int32), np.zeros(F, np.int32))
     out = Line3dOut(*[_p(a) for a in r])
     return fr, out, r, (kl, nl, d, sd)
+
+
+def _csr_i32(lists):
+    off = np.zeros(len(lists) + 1, np.int32)
+    off[1:] = np.cumsum([len(x) for x in lists])
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(x, np.int32).reshape(-1) for x in lists]) if len(lists) else [], np.int32)
+    return off, flat
+
+
+def kfdb_score(ids_a, vals_a, ids_b, vals_b):
+    """TemplatedVocabulary::score of two BowVectors (L1), as float32 (drfe_kfdb_score)"""
+    ia, ib = np.ascontiguousarray(ids_a, np.int32), np.ascontiguousarray(ids_b, np.int32)
+    va, vb = np.ascontiguousarray(vals_a, np.float64), np.ascontiguousarray(vals_b, np.float64)
+    out = np.zeros(1, np.float32)
+    rc = load().drfe_kfdb_score(len(ia), _p(ia), _p(va), len(ib), _p(ib), _p(vb), _p(out))
+    if rc != 0:
+        raise DrfeError(f"drfe_kfdb_score failed ({rc})")
+    return out[0]
+
+
+class KeyFrameDatabase:
+    """drfe_kfdb: KeyFrameDatabase with its loop and relocalisation queries.  ctx None = host-only; with a
+    Context, mode "device" runs a call on its GPU and "batch" by the crossover.  A failing call raises DrfeError with .rc."""
+
+    def __init__(self, ctx=None, scoring=KFDB_L1_NORM):
+        self.L = load()
+        self.ctx = ctx                                  # keeps the context alive
+        h = C.c_void_p()
+        rc = self.L.drfe_kfdb_create(ctx.h if ctx is not None else None, int(scoring), C.byref(h))
+        if rc != 0:
+            e = DrfeError(f"drfe_kfdb_create failed ({rc})")
+            e.rc = rc
+            raise e
+        self.h = h
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            e = DrfeError(f"{what} failed ({rc}): {self.L.drfe_kfdb_last_error(self.h).decode()}")
+            e.rc = rc
+            raise e
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.drfe_kfdb_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def put(self, handle, word_ids, values):
+        ids = np.ascontiguousarray(word_ids, np.int32)
+        vals = np.ascontiguousarray(values, np.float64)
+        assert ids.shape == vals.shape and ids.ndim == 1
+        self._chk(self.L.drfe_kfdb_put(self.h, int(handle), len(ids), _p(ids), _p(vals)), "drfe_kfdb_put")
+
+    def add(self, handle):
+        self._chk(self.L.drfe_kfdb_add(self.h, int(handle)), "drfe_kfdb_add")
+
+    def erase(self, handle):
+        self._chk(self.L.drfe_kfdb_erase(self.h, int(handle)), "drfe_kfdb_erase")
+
+    def remove(self, handle):
+        self._chk(self.L.drfe_kfdb_remove(self.h, int(handle)), "drfe_kfdb_remove")
+
+    def clear(self):
+        self._chk(self.L.drfe_kfdb_clear(self.h), "drfe_kfdb_clear")
+
+    def set_neighbours(self, handles, nbr):
+        """nbr: one list of at most 10 handles per key frame (GetBestCovisibilityKeyFrames(10)); padded with -1 here"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        tab = np.full((len(hs), KFDB_NEIGHBOURS), -1, np.int32)
+        for i, row in enumerate(nbr):
+            row = np.asarray(row, np.int32).reshape(-1)[:KFDB_NEIGHBOURS]
+            tab[i, :len(row)] = row
+        self._chk(self.L.drfe_kfdb_set_neighbours(self.h, len(hs), _p(hs), _p(tab)), "drfe_kfdb_set_neighbours")
+
+    def size(self):
+        out = np.zeros(2, np.int32)
+        self._chk(self.L.drfe_kfdb_size(self.h, _p(out)), "drfe_kfdb_size")
+        return int(out[0]), int(out[1])
+
+    def stats(self):
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_kfdb_stats(self.h, _p(st)), "drfe_kfdb_stats")
+        return dict(zip(KFDB_STATS, (int(v) for v in st)))
+
+    def _run(self, kind, Q, n, mode, capacity):
+        if capacity is None:
+            capacity = n * (self.size()[1] + n)
+        r = {"cand_offsets": np.zeros(n + 1, np.int32), "candidates": np.zeros(max(1, capacity), np.int32),
+             "record": np.zeros((n, 4), np.int32), "min_score": np.zeros(n, np.float32), "uninit_reads": np.zeros(n, np.int32)}
+        out = KfdbOut(int(capacity), 0, *[_p(r[k]) for k in ("cand_offsets", "candidates", "record", "min_score", "uninit_reads")])
+        fn = getattr(self.L, f"drfe_kfdb_{kind}_queries_{mode}")
+        args = (self.h, C.byref(Q), C.byref(out)) + (() if mode == "host" else (None,))
+        self._chk(fn(*args), f"drfe_kfdb_{kind}_queries_{mode}")
+        off = r["cand_offsets"]
+        r["candidates"] = [r["candidates"][off[k]:off[k + 1]].copy() for k in range(n)]
+        return r
+
+    def loop_queries(self, queries, mode="host", capacity=None):
+        """DetectLoopCandidates of every query: dicts with handle, id, connected (handles) and either min_score or covisible
+        (handles, GetVectorCovisibleKeyFrames order), and add_after (default False).  Returns candidates (one array of handles per
+        query), min_score [n], record [n, 4] (listed, scored, kept, maxCommonWords)."""
+        n = len(queries)
+        explicit = [("min_score" in q) for q in queries]
+        assert all(explicit) or not any(explicit), "either every query gives min_score or none does"
+        handle = np.array([q["handle"] for q in queries], np.int32)
+        ident = np.array([q["id"] for q in queries], np.int64)
+        coff, conn = _csr_i32([q.get("connected", ()) for q in queries])
+        voff, cov = _csr_i32([q.get("covisible", ()) for q in queries])
+        ms = np.array([q["min_score"] for q in queries], np.float32) if n and explicit[0] else None
+        after = np.array([1 if q.get("add_after") else 0 for q in queries], np.uint8)
+        Q = KfdbLoopQueries(n, 0, _p(handle), _p(ident), _p(coff), _p(conn), _p(ms), _p(voff), _p(cov), _p(after))
+        return self._run("loop", Q, n, mode, capacity)
+
+    def reloc_queries(self, queries, mode="host", capacity=None):
+        """DetectRelocalizationCandidates of every query (id, word_ids, values), as if run one after another.  Returns candidates,
+        record [n, 4] and uninit_reads [n]."""
+        n = len(queries)
+        ident = np.array([q[0] for q in queries], np.int64)
+        off, ids = _csr_i32([q[1] for q in queries])
+        vals = np.ascontiguousarray(np.concatenate([np.asarray(q[2], np.float64).reshape(-1) for q in queries]) if n else [],
+                                    np.float64)
+        Q = KfdbRelocQueries(n, 0, _p(ident), _p(off), _p(ids), _p(vals))
+        return self._run("reloc", Q, n, mode, capacity)
 
 
 class Shard:

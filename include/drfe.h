@@ -1490,6 +1490,104 @@ int drfe_sim3_opt_batch(drfe_ctx* ctx, const drfe_sim3_opt_problems* problems, d
  * x^3) and the host finished, [7] problems that returned before the second optimize(). */
 int drfe_sim3_opt_stats(drfe_ctx* ctx, int64_t* stats /* 8 */);
 
+/* KeyFrameDatabase (src/KeyFrameDatabase.cc:40-309) with DBoW2's L1Scoring::score (Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68)
+ * and the minScore loop of LoopClosing::DetectLoop (src/LoopClosing.cc:137-151): the candidate lists that ComputeSim3 and
+ * Relocalization start from, every query of a call at once.  DESIGN.md section 23.
+ *
+ * A drfe_kfdb is an object of its own.  Created with a context it runs calls of DRFE_KFDB_DEVICE_FROM queries or more on that
+ * context's device (the context must outlive it); created with NULL it is host-only.  It owns a mutex that every entry takes, as
+ * the reference's mMutex: Tracking and LoopClosing may both call in.  A key frame is known by the caller's handle (>= 0; the
+ * adaptor uses mnId).  Its life: put (the BowVector is stored; queries do not see it yet, but a loop query can name it as the
+ * query, as connected or as covisible) -> add (in the inverted file, visible) -> erase (stored, not visible) -> remove (forgotten;
+ * implies erase).  put of a stored handle, add of a visible one, erase of one that is not visible and any unknown handle are
+ * refused (DRFE_ERR_INVALID), and the refused call changes nothing.
+ *
+ * Kept from the reference: the order of the listed key frames (ascending word of the query, each word's list in order of the
+ * latest add); a connected key frame is never listed and never counts as a neighbour; minCommonWords = (int)(maxCommonWords * 0.8f);
+ * mLoopScore is stored below minScore too; the float accumulation over GetBestCovisibilityKeyFrames(10) in neighbour order; strict
+ * > for the best key frame, for bestAccScore and for the retain threshold; duplicates dropped at their first occurrence; the
+ * relocalisation query's neighbour test (shares a word) and with it its state: a neighbour that was not scored by this query adds
+ * the mRelocScore an earlier query left in it.  The reference never initialises that member: here a never-written one reads as
+ * 0.0f and the read is counted (uninit_reads).  Only L1 scoring exists; another scoring type is refused (DRFE_ERR_INVALID).
+ * Query ids: per kind (loop, relocalisation) nonzero and strictly greater than the last id used on this database, else
+ * DRFE_ERR_INVALID.  Parity with a DBoW2 build is not pinned. */
+typedef struct drfe_kfdb drfe_kfdb;
+/* DBoW2::ScoringType, in its order */
+enum { DRFE_KFDB_L1_NORM = 0, DRFE_KFDB_L2_NORM, DRFE_KFDB_CHI_SQUARE, DRFE_KFDB_KL, DRFE_KFDB_BHATTACHARYYA, DRFE_KFDB_DOT_PRODUCT };
+/* Caps: DRFE_KFDB_MAX_QUERIES queries per call (DRFE_ERR_INVALID above); a device call of more than 2^26 (query, stored key frame)
+ * pairs is refused with DRFE_ERR_CAPACITY by the _device forms and run on the host by the _batch forms. */
+enum { DRFE_KFDB_NEIGHBOURS = 10, DRFE_KFDB_MAX_QUERIES = 4096 };
+/* queries in a call from which the _batch entries of a database with a context use the device (the measured crossover, DESIGN.md
+ * section 23, profiles/kfdb_timing.jsonl) */
+enum { DRFE_KFDB_DEVICE_FROM = 16 };
+int drfe_kfdb_create(drfe_ctx* ctx /* or NULL */, int scoring, drfe_kfdb** out);
+void drfe_kfdb_destroy(drfe_kfdb* db);
+/* the reason of the last failed call on this database (valid until its next call) */
+const char* drfe_kfdb_last_error(const drfe_kfdb* db);
+/* mBowVec of a key frame: n ascending word ids and their values, as drfe_bow_download and the host fold leave them */
+int drfe_kfdb_put(drfe_kfdb* db, int32_t handle, int32_t n, const int32_t* word_ids, const double* values);
+/* KeyFrameDatabase::add / erase / clear (clear empties the inverted file: every key frame stays stored, none is visible) */
+int drfe_kfdb_add(drfe_kfdb* db, int32_t handle);
+int drfe_kfdb_erase(drfe_kfdb* db, int32_t handle);
+int drfe_kfdb_clear(drfe_kfdb* db);
+/* a culled key frame: its vector, neighbours and mRelocScore are dropped, the handle is free again */
+int drfe_kfdb_remove(drfe_kfdb* db, int32_t handle);
+/* GetBestCovisibilityKeyFrames(10) of `count` key frames: nbr is count x 10 handles in the reference's order, padded with -1.  A row
+ * replaces that key frame's earlier one.  A handle that has been removed by the time of a query is skipped there. */
+int drfe_kfdb_set_neighbours(drfe_kfdb* db, int32_t count, const int32_t* handles, const int32_t* nbr);
+/* out2[0] stored key frames, out2[1] visible ones.  n x (visible + n) candidates always suffice for a call of n queries. */
+int drfe_kfdb_size(drfe_kfdb* db, int32_t* out2);
+
+typedef struct drfe_kfdb_loop_queries {
+    int32_t n;                        /* queries; query k + 1 behaves as if run after query k */
+    int32_t pad;
+    const int32_t* handle;            /* n: the query key frame (stored; usually not visible yet) */
+    const int64_t* id;                /* n: pKF->mnId */
+    const int32_t* connected_offsets; /* n + 1, [0] == 0 */
+    const int32_t* connected;         /* handles of GetConnectedKeyFrames() */
+    const float* min_score;           /* n, or NULL: computed from `covisible` as src/LoopClosing.cc:139-151, from 1.0f */
+    const int32_t* covisible_offsets; /* n + 1 (read when min_score is NULL) */
+    const int32_t* covisible;         /* handles of GetVectorCovisibleKeyFrames() in its order, bad ones left out */
+    const uint8_t* add_after;         /* n, or NULL: nonzero = KeyFrameDatabase::add(query key frame) after its query, before the next */
+} drfe_kfdb_loop_queries;
+typedef struct drfe_kfdb_reloc_queries {
+    int32_t n;                        /* queries, as if run one after another in array order */
+    int32_t pad;
+    const int64_t* id;                /* n: F->mnId */
+    const int32_t* word_offsets;      /* n + 1, [0] == 0: F->mBowVec of query k is [word_offsets[k], word_offsets[k + 1]) */
+    const int32_t* word_ids;          /* ascending within a query */
+    const double* values;
+} drfe_kfdb_reloc_queries;
+typedef struct drfe_kfdb_out {
+    int32_t cand_capacity;            /* of candidates; DRFE_ERR_CAPACITY when the call needs more (the call then changes nothing) */
+    int32_t pad;
+    int32_t* cand_offsets;            /* n + 1 */
+    int32_t* candidates;              /* handles, per query in the reference's order */
+    int32_t* record;                  /* n x 4: key frames listed (lKFsSharingWords), scored (nscores), kept (lScoreAndMatch), and
+                                         maxCommonWords */
+    float* min_score;                 /* n: the minScore used (loop queries; may be NULL) */
+    int32_t* uninit_reads;            /* n: reads of an mRelocScore no query has written (relocalisation queries; may be NULL) */
+} drfe_kfdb_out;
+/* KeyFrameDatabase::DetectLoopCandidates / DetectRelocalizationCandidates of every query.  A database with a context runs a call
+ * of DRFE_KFDB_DEVICE_FROM queries or more on the device: what put / add / erase / remove / set_neighbours changed since the last
+ * device call is sent first, then the call's queries go up in one copy, all of them run in one launch sequence with no host
+ * round trip between the stages, and the results return in two copies (the records and offsets, then exactly the candidates).
+ * The _host forms always run on the host, the _device forms always on the device (DRFE_ERR_STATE without a context).  All three
+ * return the same bytes and leave the same state.  `stream` NULL = the context's. */
+int drfe_kfdb_loop_queries_host(drfe_kfdb* db, const drfe_kfdb_loop_queries* q, drfe_kfdb_out* out);
+int drfe_kfdb_loop_queries_device(drfe_kfdb* db, const drfe_kfdb_loop_queries* q, drfe_kfdb_out* out, void* stream);
+int drfe_kfdb_loop_queries_batch(drfe_kfdb* db, const drfe_kfdb_loop_queries* q, drfe_kfdb_out* out, void* stream);
+int drfe_kfdb_reloc_queries_host(drfe_kfdb* db, const drfe_kfdb_reloc_queries* q, drfe_kfdb_out* out);
+int drfe_kfdb_reloc_queries_device(drfe_kfdb* db, const drfe_kfdb_reloc_queries* q, drfe_kfdb_out* out, void* stream);
+int drfe_kfdb_reloc_queries_batch(drfe_kfdb* db, const drfe_kfdb_reloc_queries* q, drfe_kfdb_out* out, void* stream);
+/* TemplatedVocabulary::score(a, b) of two vectors (L1): (float)L1Scoring::score.  Host code, no database. */
+int drfe_kfdb_score(int32_t na, const int32_t* ids_a, const double* values_a, int32_t nb, const int32_t* ids_b, const double* values_b,
+                    float* score);
+/* Counters since the database was created: stats[0] loop calls, [1] loop queries, [2] relocalisation calls, [3] relocalisation
+ * queries, [4] calls run on the device, [5] uploads of the database image, [6] candidates returned, [7] uninitialised mRelocScore
+ * reads. */
+int drfe_kfdb_stats(drfe_kfdb* db, int64_t* stats /* 8 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

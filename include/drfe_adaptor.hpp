@@ -3113,4 +3113,214 @@ private:
 
 }  // namespace Planar_SLAM
 
+namespace Planar_SLAM {
+
+/* include/KeyFrameDatabase.h over drfe_kfdb: the reference's five signatures, so that LoopClosing.cc and
+ * Tracking.cc compile unchanged against KeyFrameDatabase<KeyFrame, Frame>, and the two batch forms.  A key frame's handle is its
+ * mnId, a query's id the mnId of its key frame / frame (the reference compares mnLoopQuery / mnRelocQuery with it): ids must grow
+ * from query to query, as the reference's do.  A key frame's mBowVec is stored when the database first meets it (add, a query, a
+ * connected or covisible key frame of a query) and is not read again.  Before every query call the GetBestCovisibilityKeyFrames(10)
+ * row of every key frame the database knows and that is not bad is sent again: one pass over the key frames per call, not per
+ * query, which is the price of not being told when the covisibility graph changes.  Forget(pKF) drops a culled key frame.
+ * `device` < 0 (the default) is a host-only database; with a device, a call of DRFE_KFDB_DEVICE_FROM queries or more runs there.
+ * KeyFrameT: mnId, mBowVec (iterable pairs of word id and value), isBad(), GetConnectedKeyFrames(), GetVectorCovisibleKeyFrames(),
+ * GetBestCovisibilityKeyFrames(int).  FrameT: mnId, mBowVec. */
+template <class KeyFrameT, class FrameT>
+class KeyFrameDatabase {
+public:
+    explicit KeyFrameDatabase(int device = -1) { Open(device); }
+    /* the reference's constructor: the vocabulary only sizes its inverted file */
+    template <class Voc> explicit KeyFrameDatabase(const Voc&, int device = -1) { Open(device); }
+    ~KeyFrameDatabase() { drfe_kfdb_destroy(mDb); }
+    KeyFrameDatabase(const KeyFrameDatabase&) = delete;
+    KeyFrameDatabase& operator=(const KeyFrameDatabase&) = delete;
+    /* true / false: the device / the host entries whatever the number of queries (the device needs `device` >= 0) */
+    void UseDevice(bool on) { mForce = on ? 1 : -1; }
+
+    void add(KeyFrameT* pKF)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        Know(pKF);
+        Check(drfe_kfdb_add(mDb, Handle(pKF)), "drfe_kfdb_add");
+        mVisible.insert(Handle(pKF));
+    }
+    /* as the reference's, a key frame that is not in the inverted file is left alone */
+    void erase(KeyFrameT* pKF)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        if (!mVisible.erase(Handle(pKF))) return;
+        Check(drfe_kfdb_erase(mDb, Handle(pKF)), "drfe_kfdb_erase");
+    }
+    void clear()
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        Check(drfe_kfdb_clear(mDb), "drfe_kfdb_clear");
+        mVisible.clear();
+    }
+    /* a culled key frame: out of the inverted file and out of the database's tables */
+    void Forget(KeyFrameT* pKF)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        if (!mKFs.erase(Handle(pKF))) return;
+        mVisible.erase(Handle(pKF));
+        Check(drfe_kfdb_remove(mDb, Handle(pKF)), "drfe_kfdb_remove");
+    }
+
+    std::vector<KeyFrameT*> DetectLoopCandidates(KeyFrameT* pKF, float minScore)
+    {
+        std::vector<KeyFrameT*> queue(1, pKF);
+        std::vector<float> ms(1, minScore);
+        return Loop(queue, &ms, false)[0];
+    }
+    /* LoopClosing::DetectLoop's :137-167 for a queue of key frames in one call: minScore of each from its
+     * GetVectorCovisibleKeyFrames() (bad ones left out), and with addAfter the add() that follows each query, so that a later key
+     * frame of the queue meets the earlier ones.  MinScores() holds the minScore each query used. */
+    std::vector<std::vector<KeyFrameT*>> DetectLoopCandidates(const std::vector<KeyFrameT*>& queue, bool addAfter)
+    {
+        return Loop(queue, nullptr, addAfter);
+    }
+    std::vector<KeyFrameT*> DetectRelocalizationCandidates(FrameT* F)
+    {
+        return DetectRelocalizationCandidates(std::vector<FrameT*>(1, F))[0];
+    }
+    /* every lost frame of a batched tracker in one call, as if asked one after another */
+    std::vector<std::vector<KeyFrameT*>> DetectRelocalizationCandidates(const std::vector<FrameT*>& frames)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const size_t n = frames.size();
+        std::vector<int64_t> id(n);
+        std::vector<int32_t> off(1, 0), words;
+        std::vector<double> values;
+        for (size_t k = 0; k < n; k++) {
+            id[k] = (int64_t)frames[k]->mnId;
+            Flatten(frames[k]->mBowVec, words, values);
+            off.push_back((int32_t)words.size());
+        }
+        drfe_kfdb_reloc_queries q = {};
+        q.n = (int32_t)n;
+        q.id = id.data(); q.word_offsets = off.data(); q.word_ids = words.data(); q.values = values.data();
+        return Run(n, [&](drfe_kfdb_out* o) {
+            return mForce < 0 ? drfe_kfdb_reloc_queries_host(mDb, &q, o)
+                 : mForce > 0 ? drfe_kfdb_reloc_queries_device(mDb, &q, o, nullptr) : drfe_kfdb_reloc_queries_batch(mDb, &q, o, nullptr);
+        }, "drfe_kfdb_reloc_queries");
+    }
+    /* of the last query call: the minScore of each loop query, the reads of a never-written mRelocScore of each relocalisation
+     * query (where the reference itself reads an uninitialised float), and listed / scored / kept / maxCommonWords of each */
+    const std::vector<float>& MinScores() const { return mMinScore; }
+    const std::vector<int32_t>& UninitReads() const { return mUninit; }
+    const std::vector<int32_t>& Records() const { return mRecord; }
+    drfe_kfdb* db() const { return mDb; }
+
+private:
+    static int32_t Handle(const KeyFrameT* pKF) { return (int32_t)pKF->mnId; }
+    void Open(int device)
+    {
+        if (device >= 0) mCtx = drfe_detail::make_ctx(1, 1.2f, 1, 20, 7, 64, 64, 1, device);
+        if (drfe_kfdb_create(mCtx.get(), DRFE_KFDB_L1_NORM, &mDb) != DRFE_OK) throw std::runtime_error("drfe_kfdb_create failed");
+    }
+    void Check(int rc, const char* what) const
+    {
+        if (rc != DRFE_OK) throw std::runtime_error(std::string(what) + ": " + drfe_kfdb_last_error(mDb));
+    }
+    template <class Bow> static void Flatten(const Bow& bow, std::vector<int32_t>& words, std::vector<double>& values)
+    {
+        for (auto it = bow.begin(); it != bow.end(); ++it) {
+            words.push_back((int32_t)it->first);
+            values.push_back((double)it->second);
+        }
+    }
+    void Know(KeyFrameT* pKF)
+    {
+        if (mKFs.count(Handle(pKF))) return;
+        std::vector<int32_t> words;
+        std::vector<double> values;
+        Flatten(pKF->mBowVec, words, values);
+        Check(drfe_kfdb_put(mDb, Handle(pKF), (int32_t)words.size(), words.data(), values.data()), "drfe_kfdb_put");
+        mKFs[Handle(pKF)] = pKF;
+    }
+    /* a neighbour the database has not met is in no inverted file: it cannot pass either query's neighbour test */
+    void RefreshNeighbours()
+    {
+        std::vector<int32_t> handles, rows;
+        for (auto& kv : mKFs) {
+            if (kv.second->isBad()) continue;
+            handles.push_back(kv.first);
+            const auto vpNeighs = kv.second->GetBestCovisibilityKeyFrames(DRFE_KFDB_NEIGHBOURS);
+            size_t k = 0;
+            for (; k < vpNeighs.size() && k < (size_t)DRFE_KFDB_NEIGHBOURS; k++)
+                rows.push_back(mKFs.count(Handle(vpNeighs[k])) ? Handle(vpNeighs[k]) : -1);
+            for (; k < (size_t)DRFE_KFDB_NEIGHBOURS; k++) rows.push_back(-1);
+        }
+        Check(drfe_kfdb_set_neighbours(mDb, (int32_t)handles.size(), handles.data(), rows.data()), "drfe_kfdb_set_neighbours");
+    }
+    template <class Fn> std::vector<std::vector<KeyFrameT*>> Run(size_t n, Fn call, const char* what)
+    {
+        RefreshNeighbours();
+        int32_t size[2] = {0, 0};
+        Check(drfe_kfdb_size(mDb, size), "drfe_kfdb_size");
+        std::vector<int32_t> off(n + 1, 0), cand(n * ((size_t)size[1] + n) + 1);
+        mRecord.assign(4 * n, 0);
+        mMinScore.assign(n, 0.f);
+        mUninit.assign(n, 0);
+        drfe_kfdb_out o = {};
+        o.cand_capacity = (int32_t)cand.size();
+        o.cand_offsets = off.data(); o.candidates = cand.data(); o.record = mRecord.data();
+        o.min_score = mMinScore.data(); o.uninit_reads = mUninit.data();
+        Check(call(&o), what);
+        std::vector<std::vector<KeyFrameT*>> out(n);
+        for (size_t k = 0; k < n; k++)
+            for (int32_t i = off[k]; i < off[k + 1]; i++) out[k].push_back(mKFs.at(cand[(size_t)i]));
+        return out;
+    }
+    std::vector<std::vector<KeyFrameT*>> Loop(const std::vector<KeyFrameT*>& queue, const std::vector<float>* minScore, bool addAfter)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const size_t n = queue.size();
+        std::vector<int32_t> handle(n), connOff(1, 0), conn, covOff(1, 0), cov;
+        std::vector<int64_t> id(n);
+        std::vector<uint8_t> after(n, addAfter ? 1 : 0);
+        for (size_t k = 0; k < n; k++) {
+            KeyFrameT* pKF = queue[k];
+            Know(pKF);
+            handle[k] = Handle(pKF);
+            id[k] = (int64_t)pKF->mnId;
+            for (KeyFrameT* c : pKF->GetConnectedKeyFrames()) {
+                Know(c);
+                conn.push_back(Handle(c));
+            }
+            connOff.push_back((int32_t)conn.size());
+            if (!minScore)
+                for (KeyFrameT* c : pKF->GetVectorCovisibleKeyFrames()) {
+                    if (c->isBad()) continue;
+                    Know(c);
+                    cov.push_back(Handle(c));
+                }
+            covOff.push_back((int32_t)cov.size());
+        }
+        drfe_kfdb_loop_queries q = {};
+        q.n = (int32_t)n;
+        q.handle = handle.data(); q.id = id.data(); q.connected_offsets = connOff.data(); q.connected = conn.data();
+        q.min_score = minScore ? minScore->data() : nullptr;
+        q.covisible_offsets = covOff.data(); q.covisible = cov.data(); q.add_after = after.data();
+        auto out = Run(n, [&](drfe_kfdb_out* o) {
+            return mForce < 0 ? drfe_kfdb_loop_queries_host(mDb, &q, o)
+                 : mForce > 0 ? drfe_kfdb_loop_queries_device(mDb, &q, o, nullptr) : drfe_kfdb_loop_queries_batch(mDb, &q, o, nullptr);
+        }, "drfe_kfdb_loop_queries");
+        if (addAfter)
+            for (size_t k = 0; k < n; k++) mVisible.insert(handle[k]);
+        return out;
+    }
+
+    drfe_detail::CtxPtr mCtx;
+    drfe_kfdb* mDb = nullptr;
+    int mForce = 0;
+    std::mutex mMutex;
+    std::map<int32_t, KeyFrameT*> mKFs;
+    std::set<int32_t> mVisible;
+    std::vector<float> mMinScore;
+    std::vector<int32_t> mUninit, mRecord;
+};
+
+}  // namespace Planar_SLAM
+
 #endif /* DRFE_ADAPTOR_HPP */
