@@ -770,7 +770,11 @@ static int ensure_arena(drfe_ctx* c, int w, int h, int frames, const float* K4, 
         /* capacities scale with the frame: 2^19 neighbour-pool words and 2^20 flood-fill queue entries for the 3072 blocks /
          * 307 200 pixels of a 640 x 480 frame (3.4 entries per pixel) */
         P.maxNodes = 2 * NB + 256; P.planeCap = AHC_DEV_PLANE_CAP;
-        P.poolCap = 1 << 19; P.rfCap = 1 << 20;
+        /* every merge appends the merged node's list: 130 words per block on a 640 x 480 wall, 188 on a three-plane 1000 x 600
+         * frame, whose 1 126 000 words missed the 2^20 that 170 per block round up to at 6 000 blocks.  So the frames of the big
+         * kernels (more than 3 200 blocks) start at 2^21 words, which is what 170 per block already gave 1280 x 960
+         * (170 * 12 288 = 2 088 960): 2^21 from 3 201 to 12 336 blocks, 2^22 above; the small kernels' frames keep their sizes */
+        P.poolCap = NB > 3200 ? 1 << 21 : 1 << 19; P.rfCap = 1 << 20;
         while (P.poolCap < 170 * NB) P.poolCap <<= 1;
         while ((size_t)P.rfCap < npx * 7 / 2) P.rfCap <<= 1;
         if (P.maxNodes > 65535) { c->ahcArena = nullptr; delete a; c->err = "planes: the device extractor keeps node ids in 16 bits (frame too large)"; return DRFE_ERR_INVALID; }
