@@ -435,6 +435,32 @@ int drfe_orb_fast_partition(drfe_ctx* c, int w, int h, int32_t* ncells, int64_t*
     return DRFE_OK;
 }
 
+int drfe_orb_fast_cells(drfe_ctx* c, int w, int h, int32_t* rows, int cap, int* n_out)
+{
+    if (!c || !n_out || cap < 0 || (cap > 0 && !rows)) return DRFE_ERR_INVALID;
+    DevGeom g;
+    std::memset(&g, 0, sizeof(g));
+    std::vector<FastCell> cells;
+    const int rc = drfe_build_geometry(c, w, h, &g, &cells, nullptr, nullptr);
+    if (rc != DRFE_OK) return rc;
+    *n_out = (int)cells.size();
+    if (cap == 0) return DRFE_OK;
+    if ((int)cells.size() > cap) { c->err = "drfe_orb_fast_cells: buffer too small"; return DRFE_ERR_CAPACITY; }
+    const bool cols = g.fastCols && !c->fastGeneric;
+    int caps[2];
+    drfe_fastc_list_caps(g, caps);
+    for (size_t i = 0; i < cells.size(); i++) {
+        const FastCell& f = cells[i];
+        const int big = (int)i >= g.fastColsSmall ? 1 : 0;
+        int32_t* r = rows + i * DRFE_FAST_CELL_FIELDS;
+        r[0] = f.level; r[1] = f.x0; r[2] = f.y0; r[3] = f.ww; r[4] = f.wh; r[5] = f.offX; r[6] = f.offY; r[7] = (int32_t)f.cellIdx;
+        r[8] = f.ncp; r[9] = f.rpl; r[10] = f.nrb;
+        r[11] = cols ? (big ? DRFE_FASTC_MAX_RPL : 8) : 0;
+        r[12] = cols ? caps[big] : 0;
+    }
+    return DRFE_OK;
+}
+
 int drfe_batch_download_async(drfe_ctx* c, int nframes, drfe_keypoint* kps, uint8_t* desc, int32_t* kp_counts, int32_t* matches,
                               int32_t* match_counts, void* stream)
 {

@@ -338,6 +338,8 @@ int drfe_build_geometry(drfe_ctx* c, int w, int h, DevGeom* g, std::vector<FastC
 /* orb_kernels.hip */
 hipError_t drfe_launch_orb(drfe_ctx* c, const uint8_t* d_gray, size_t frameStride, size_t rowStride, int nframes,
                            hipStream_t s);
+/* survivor-list capacity (16-bit entries) of the k_fast_cells_cols<8> and <DRFE_FASTC_MAX_RPL> launches of a geometry */
+void drfe_fastc_list_caps(const DevGeom& g, int caps[2]);
 /* match_kernels.hip */
 hipError_t drfe_launch_glue(drfe_ctx* c, const uint16_t* d_depth, size_t frameStride, size_t rowStride,
                             const drfe_camera& cam, int nframes, hipStream_t s);

@@ -1645,3 +1645,10 @@ hipError_t drfe_launch_orb(drfe_ctx* c, const uint8_t* d_gray, size_t frameStrid
 }
 
 size_t drfe_quadtree_lds_bytes() { return sizeof(QtShared<512, DRFE_QT_MAX_NODES>); }
+
+/* the listCap arguments of the two k_fast_cells_cols launches above */
+void drfe_fastc_list_caps(const DevGeom& g, int caps[2])
+{
+    caps[0] = fastc_list_cap(g.fastColsRows, 8 * 64);
+    caps[1] = fastc_list_cap(g.fastColsRows, DRFE_FASTC_MAX_RPL * 64);
+}

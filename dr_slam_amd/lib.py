@@ -36,7 +36,7 @@ SYMBOLS = (
     "drfe_match_orb_points", "drfe_planes_cape", "drfe_voc_upload", "drfe_bow_transform_batch", "drfe_bow_download",
     "drfe_search_by_bow", "drfe_search_by_bow_kf", "drfe_search_for_triangulation", "drfe_lsd_extract", "drfe_lsd_extract_batch", "drfe_lsd_stages", "drfe_lines_is_good", "drfe_lsd_search_by_descriptor", "drfe_lsd_search_for_triangulation", "drfe_lsd_search_by_projection_last",
     "drfe_lsd_search_by_projection_map", "drfe_plane_voxel_grid", "drfe_plane_refit", "drfe_planes_ahc_postprocess",
-    "drfe_planes_cape_postprocess", "drfe_surface_normals", "drfe_surface_normals_batch", "drfe_surface_normals_download", "drfe_batch_download_async", "drfe_orb_fast_partition", "drfe_lsd_segments_host", "drfe_orb_keypoint_pixels_async", "drfe_gather_keypoint_depth",
+    "drfe_planes_cape_postprocess", "drfe_surface_normals", "drfe_surface_normals_batch", "drfe_surface_normals_download", "drfe_batch_download_async", "drfe_orb_fast_partition", "drfe_orb_fast_cells", "drfe_lsd_segments_host", "drfe_orb_keypoint_pixels_async", "drfe_gather_keypoint_depth",
     "drfe_frame_stereo_grid_batch_kpdepth", "drfe_planes_ahc_post_batch", "drfe_planes_ahc_from_blocks", "drfe_debug_ahc_trials", "drfe_debug_order_sort", "drfe_debug_order_sort_heap_max", "drfe_debug_device_voxel_grid", "drfe_debug_plane_refit", "drfe_search_for_initialization", "drfe_lsd_fuse_search_sim3", "drfe_lsd_search_by_projection_kf",
     "drfe_lsd_search_by_sim3", "drfe_frame_submit", "drfe_frame_collect", "drfe_pipeline_create", "drfe_pipeline_destroy",
     "drfe_pipeline_depth", "drfe_pipeline_context", "drfe_pipeline_last_error", "drfe_pipeline_submit", "drfe_pipeline_sync",
@@ -68,6 +68,8 @@ SYMBOLS = (
     "drfe_kfdb_reloc_queries_device", "drfe_kfdb_reloc_queries_batch", "drfe_kfdb_score", "drfe_kfdb_stats",
 )
 
+FAST_CELL_DTYPE = np.dtype([(n, "<i4") for n in ("level", "x0", "y0", "ww", "wh", "offX", "offY", "cellIdx", "ncp", "rpl", "nrb",
+                                                  "kernel", "list_cap")])   # drfe_orb_fast_cells, DRFE_FAST_CELL_FIELDS int32
 FRUSTUM_POINT_DTYPE = np.dtype([("world", "<f4", (3,)), ("normal", "<f4", (3,)), ("min_distance", "<f4"),
                                 ("max_distance", "<f4")])                            # drfe_frustum_point, 32 B
 FRUSTUM_LINE_DTYPE = np.dtype([("world", "<f8", (6,)), ("normal", "<f8", (3,)), ("min_distance", "<f4"),
@@ -353,6 +355,7 @@ def load() -> C.CDLL:
     L.drfe_orb_download.argtypes = [vp, i32, vp, vp, i32, C.POINTER(i32)]
     L.drfe_orb_counts.argtypes = [vp, i32, vp]
     L.drfe_orb_fast_partition.argtypes = [vp, i32, i32, vp, vp]
+    L.drfe_orb_fast_cells.argtypes = [vp, i32, i32, vp, i32, vp]
     L.drfe_orb_keypoint_pixels_async.argtypes = [vp, i32, vp, vp, vp]
     L.drfe_gather_keypoint_depth.argtypes = [vp, sz, sz, i32, vp, vp, i32, vp, i32]
     L.drfe_frame_stereo_grid_batch_kpdepth.argtypes = [vp, vp, i32, C.POINTER(Camera), i32, vp]
@@ -1779,6 +1782,16 @@ class Context:
         px = np.zeros(2, np.int64)
         self._chk(self.L.drfe_orb_fast_partition(self.h, w, h, _p(cells), _p(px)), "drfe_orb_fast_partition")
         return cells, px
+
+    def fast_cells(self, w: int, h: int):
+        """-> the FAST cell table of a w x h frame in launch order (FAST_CELL_DTYPE): level, window, offsets, emission index, the
+        lane layout of k_fast_cells_cols, the kernel each cell runs (8 / 12, 0 = the generic k_fast_cells) and the survivor-list
+        capacity of that launch.  Host code."""
+        n = C.c_int(0)
+        self._chk(self.L.drfe_orb_fast_cells(self.h, w, h, None, 0, C.byref(n)), "drfe_orb_fast_cells")
+        rows = np.zeros(max(n.value, 1), FAST_CELL_DTYPE)
+        self._chk(self.L.drfe_orb_fast_cells(self.h, w, h, _p(rows), len(rows), C.byref(n)), "drfe_orb_fast_cells")
+        return rows[:n.value]
 
     def orb_counts(self, nframes: int):
         c = np.zeros(nframes, np.int32)

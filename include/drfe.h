@@ -1597,6 +1597,13 @@ enum { DRFE_STAGE_PYRAMID = 0, DRFE_STAGE_FAST, DRFE_STAGE_QUADTREE, DRFE_STAGE_
 /* How the FAST cells of a w x h frame split over the two launches: cells[2] and evaluated pixels[2] (sum of the cells'
  * (window - 6)^2 areas: every pixel of the detection region belongs to exactly one cell).  Host code. */
 int drfe_orb_fast_partition(drfe_ctx* ctx, int w, int h, int32_t* cells, int64_t* pixels);
+/* The FAST cell table of a w x h frame in launch order, DRFE_FAST_CELL_FIELDS int32 per cell: level, window x0, y0 (level
+ * coordinates), window width, height, offX, offY (what is added to a candidate's window coordinates less 3), cellIdx (emission order
+ * inside the level), then the lane layout of k_fast_cells_cols - ncp column pairs, rpl rows per lane, nrb row blocks -, the kernel the
+ * cell runs (8 / 12: k_fast_cells_cols<8> / <12>, 0: the generic k_fast_cells) and the survivor-list capacity of that launch (0 for
+ * the generic kernel).  cap = 0: only *n is set.  Host code: no kernel, no device memory. */
+#define DRFE_FAST_CELL_FIELDS 13
+int drfe_orb_fast_cells(drfe_ctx* ctx, int w, int h, int32_t* rows, int cap, int* n);
 /* When enabled, batched calls bracket every stage with HIP events on the launch stream. */
 int drfe_profile_enable(drfe_ctx* ctx, int on);
 /* Milliseconds per stage of the most recent batched calls (synchronises). */
