@@ -8,13 +8,9 @@
 
 #include <algorithm>
 
-struct InitBuffers : RansacBuffers {};
+struct InitBuffers : BatchBuffers {};
 
-void drfe_init_free(drfe_ctx* c)
-{
-    delete c->init;
-    c->init = nullptr;
-}
+void drfe_init_free(drfe_ctx* c) { batch_free(c->init); }
 
 namespace {
 
@@ -340,8 +336,7 @@ int drfe_init_ransac_batch(drfe_ctx* c, const drfe_init_problems* p, drfe_init_o
     Plan P;
     const int rc = make_plan(p, o, P, c->err);
     if (rc) return rc;
-    InitBuffers* b = c->init;
-    if (!b) { b = new InitBuffers(); c->init = b; }
+    InitBuffers* b = batch_buffers(c->init);
     P.count_call(b->stats, P.matchOff.data());
     if (p->n == 0) return DRFE_OK;
     const int n = p->n, H = P.nHyp;
@@ -366,10 +361,8 @@ int drfe_init_ransac_batch(drfe_ctx* c, const drfe_init_problems* p, drfe_init_o
     const auto sMP3D = out.add<float>(nK1 * 24);
     const auto sH12 = scr.add<float>(nH * 9);
     const auto sLastH = scr.add<int32_t>(nS), sLastF = scr.add<int32_t>(nS);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, b->io.grow(in.bytes(), out.bytes()));
-    HIPCHK(c, b->scratch.grow(scr.bytes()));
+    hipStream_t st;
+    if (const int e = batch_begin(c, b, stream, in.bytes(), out.bytes(), scr.bytes(), &st)) return e;
     char* h = b->io.hin;
     sSolver.put(h, P.rec.data());
     sMatch.put(h, P.match.data());
@@ -380,8 +373,7 @@ int drfe_init_ransac_batch(drfe_ctx* c, const drfe_init_problems* p, drfe_init_o
     const char* d = b->io.din;
     char* dO = b->io.dout;
     char* dS = b->scratch;
-    HIPCHK(c, hipMemcpyAsync(b->io.din, h, in.bytes(), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(dO, 0, out.bytes(), st));
+    if (const int e = batch_upload(c, b, in.bytes(), out.bytes(), st)) return e;
     InitLaunch L{};
     L.solver = sSolver.at(d);
     L.nSolvers = n; L.nHyp = H; L.maxHyp = P.maxHyp;
@@ -394,7 +386,7 @@ int drfe_init_ransac_batch(drfe_ctx* c, const drfe_init_problems* p, drfe_init_o
     L.branch = sBranch.at(dO); L.motions = sMotions.at(dO); L.flags = sFlags.at(dO);
     L.mR = sMR.at(dO); L.mt = sMt.at(dO); L.mCos = sMCos.at(dO); L.mGood = sMGood.at(dO); L.mStatus = sMStatus.at(dO);
     L.mVbGood = sMVb.at(dO); L.mP3D = sMP3D.at(dO);
-    if (const int e = ransac_finish(c, "init", drfe_launch_init(L, st), b->io, out.bytes(), st)) return e;
+    if (const int e = batch_finish(c, "init", drfe_launch_init(L, st), b, out.bytes(), st)) return e;
     const char* ho = b->io.hout;
     sMR.get(ho, o->motion_R);
     sMt.get(ho, o->motion_t);
@@ -487,8 +479,7 @@ int drfe_debug_init_check_rt(drfe_ctx* c, const float* K, const float* R, const 
         *parallax = parallax_of(*good, *cosSel);
         return DRFE_OK;
     }
-    InitBuffers* b = c->init;
-    if (!b) { b = new InitBuffers(); c->init = b; }
+    InitBuffers* b = batch_buffers(c->init);
     StageLayout<16> in, out;
     const auto sSolver = in.add<InitSolverRec>(1);
     const auto sMatch = in.add<InitMatch>(N);
@@ -525,7 +516,7 @@ int drfe_debug_init_check_rt(drfe_ctx* c, const float* K, const float* R, const 
     L.maskH = sMask.at(d); L.lastH = sLast.at(d); L.branch = sBranch.at(d); L.motions = sMotions.at(d);
     L.mR = sMR.at(d); L.mt = sMt.at(d);
     L.mCos = sMCos.at(dO); L.mGood = sMGood.at(dO); L.mStatus = sMStatus.at(dO); L.mVbGood = sMVb.at(dO); L.mP3D = sMP3D.at(dO);
-    if (const int e = ransac_finish(c, "init check", drfe_launch_init_check(L, st), b->io, out.bytes(), st)) return e;
+    if (const int e = batch_finish(c, "init check", drfe_launch_init_check(L, st), b, out.bytes(), st)) return e;
     const char* ho = b->io.hout;
     *good = sMGood.at(ho)[0];
     *cosSel = sMCos.at(ho)[0];
@@ -536,11 +527,6 @@ int drfe_debug_init_check_rt(drfe_ctx* c, const float* K, const float* R, const 
     return DRFE_OK;
 }
 
-int drfe_init_stats(drfe_ctx* c, int64_t* stats)
-{
-    if (!c || !stats) return DRFE_ERR_INVALID;
-    ransac_stats(c->init, stats);
-    return DRFE_OK;
-}
+int drfe_init_stats(drfe_ctx* c, int64_t* stats) { return batch_stats(c, &drfe_ctx::init, stats); }
 
 }  // extern "C"

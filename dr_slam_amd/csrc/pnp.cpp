@@ -7,13 +7,9 @@
 #include "stage_layout.h"
 #include "../../include/drfe_debug.h"
 
-struct PnpBuffers : RansacBuffers {};  /* scratch: the refine jobs of every solver */
+struct PnpBuffers : BatchBuffers {};   /* scratch: the refine jobs of every solver */
 
-void drfe_pnp_free(drfe_ctx* c)
-{
-    delete c->pnp;
-    c->pnp = nullptr;
-}
+void drfe_pnp_free(drfe_ctx* c) { batch_free(c->pnp); }
 
 namespace {
 
@@ -185,8 +181,7 @@ int drfe_pnp_ransac_batch(drfe_ctx* c, const drfe_pnp_problems* p, drfe_pnp_out*
     Plan P;
     const int rc = make_plan(p, o, P, c->err);
     if (rc) return rc;
-    PnpBuffers* b = c->pnp;
-    if (!b) { b = new PnpBuffers(); c->pnp = b; }
+    PnpBuffers* b = batch_buffers(c->pnp);
     P.count_call(b->stats, p->offsets);
     if (p->n == 0) return DRFE_OK;
     const int n = p->n, M = p->offsets[n], H = P.nHyp;
@@ -205,10 +200,8 @@ int drfe_pnp_ransac_batch(drfe_ctx* c, const drfe_pnp_problems* p, drfe_pnp_out*
     const auto sRet = out.add<uint8_t>(nH);
     const auto sMask = out.add<uint64_t>(nW), sRefMask = out.add<uint64_t>(nW);
     const auto sJobs = scr.add<int32_t>(nH), sJobSolver = scr.add<int32_t>(nH), sJobRow = scr.add<int32_t>(nH), sTotal = scr.add<int32_t>(1);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, b->io.grow(in.bytes(), out.bytes()));
-    HIPCHK(c, b->scratch.grow(scr.bytes()));
+    hipStream_t st;
+    if (const int e = batch_begin(c, b, stream, in.bytes(), out.bytes(), scr.bytes(), &st)) return e;
     char* h = b->io.hin;
     PnpSolverRec* sol = sSolver.at(h);
     for (int s = 0; s < n; s++) {
@@ -221,8 +214,7 @@ int drfe_pnp_ransac_batch(drfe_ctx* c, const drfe_pnp_problems* p, drfe_pnp_out*
     const char* d = b->io.din;
     char* dO = b->io.dout;
     char* dS = b->scratch;
-    HIPCHK(c, hipMemcpyAsync(b->io.din, h, in.bytes(), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(dO, 0, out.bytes(), st));
+    if (const int e = batch_upload(c, b, in.bytes(), out.bytes(), st)) return e;
     PnpLaunch L{};
     L.solver = sSolver.at(d);
     L.nSolvers = n; L.nCorr = M; L.nHyp = H; L.maxHyp = P.maxHyp;
@@ -234,7 +226,7 @@ int drfe_pnp_ransac_batch(drfe_ctx* c, const drfe_pnp_problems* p, drfe_pnp_out*
     L.inliers = sInl.at(dO); L.best = sBest.at(dO); L.refInliers = sRefInl.at(dO); L.nJobs = sJobsN.at(dO);
     L.returns = sRet.at(dO);
     L.mask = sMask.at(dO); L.refMask = sRefMask.at(dO);
-    if (const int e = ransac_finish(c, "pnp", drfe_launch_pnp(L, st), b->io, out.bytes(), st)) return e;
+    if (const int e = batch_finish(c, "pnp", drfe_launch_pnp(L, st), b, out.bytes(), st)) return e;
     const char* ho = b->io.hout;
     for (int s = 0; s < n; s++) {
         const size_t hy = (size_t)P.hyp[(size_t)s], r0 = (size_t)P.row0[(size_t)s];
@@ -261,12 +253,7 @@ int drfe_pnp_ransac_batch(drfe_ctx* c, const drfe_pnp_problems* p, drfe_pnp_out*
     return DRFE_OK;
 }
 
-int drfe_pnp_stats(drfe_ctx* c, int64_t* stats)
-{
-    if (!c || !stats) return DRFE_ERR_INVALID;
-    ransac_stats(c->pnp, stats);
-    return DRFE_OK;
-}
+int drfe_pnp_stats(drfe_ctx* c, int64_t* stats) { return batch_stats(c, &drfe_ctx::pnp, stats); }
 
 int drfe_debug_pnp_svd(const double* A, int m, int n, double* w, double* ut, double* vt)
 {

@@ -3,24 +3,16 @@
  * argument checks and caps, the edge list of a call, the frame's rounds on the host, and the hand-back of a frame whose sin / cos
  * or cube the device could not certify.  DESIGN.md section 20. */
 #include "pose_opt_internal.h"
+#include "batch_entry.h"
 #include "stage_layout.h"
 #include "../../include/drfe_debug.h"
 
 #include <cstring>
 #include <vector>
 
-struct PoseOptBuffers {
-    StagePair io;                      /* staging: one copy each way */
-    DevBuf<char> scratch;              /* _error of every edge */
-    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int handBackEvery = 0;             /* drfe_debug_pose_opt_hand_back: treat every k-th frame of a call as not certified */
-};
+struct PoseOptBuffers : BatchBuffers {};   /* scratch: _error of every edge; the hand-back counts frames */
 
-void drfe_pose_opt_free(drfe_ctx* c)
-{
-    delete c->pose_opt;
-    c->pose_opt = nullptr;
-}
+void drfe_pose_opt_free(drfe_ctx* c) { batch_free(c->pose_opt); }
 
 namespace {
 
@@ -28,16 +20,6 @@ struct Plan {
     std::vector<PoFrameRec> frame;
     std::vector<PoEdge> edge;
 };
-
-bool offsets_ok(const int32_t* off, int n, int cap, const char* what, const char* capName, std::string& err)
-{
-    if (off[0] != 0) { err = std::string("pose_opt: ") + what + "_offsets[0] is not 0"; return false; }
-    for (int f = 0; f < n; f++) {
-        if (off[f + 1] < off[f]) { err = std::string("pose_opt: decreasing ") + what + "_offsets"; return false; }
-        if (off[f + 1] - off[f] > cap) { err = std::string("pose_opt: more than ") + capName + " in a frame"; return false; }
-    }
-    return true;
-}
 
 /* all-or-nothing validation of a call, then its frames and edges */
 int make_plan(const drfe_pose_opt_problems* p, const drfe_pose_opt_out* o, Plan& P, std::string& err)
@@ -49,9 +31,9 @@ int make_plan(const drfe_pose_opt_problems* p, const drfe_pose_opt_out* o, Plan&
     if (n == 0) return DRFE_OK;
     if (!p->Tcw || !p->K || !p->bf || !p->b_struct || !p->point_offsets || !p->line_offsets || !p->plane_offsets) return DRFE_ERR_INVALID;
     if (!o->Tcw || !o->returns || !o->rounds || !o->iterations || !o->trials) return DRFE_ERR_INVALID;
-    if (!offsets_ok(p->point_offsets, n, DRFE_POSE_OPT_MAX_POINTS, "point", "DRFE_POSE_OPT_MAX_POINTS points", err) ||
-        !offsets_ok(p->line_offsets, n, DRFE_POSE_OPT_MAX_LINES, "line", "DRFE_POSE_OPT_MAX_LINES lines", err) ||
-        !offsets_ok(p->plane_offsets, n, DRFE_POSE_OPT_MAX_PLANES, "plane", "DRFE_POSE_OPT_MAX_PLANES plane slots", err))
+    if (!batch_offsets_ok("pose_opt", p->point_offsets, n, DRFE_POSE_OPT_MAX_POINTS, "point", "DRFE_POSE_OPT_MAX_POINTS points", err) ||
+        !batch_offsets_ok("pose_opt", p->line_offsets, n, DRFE_POSE_OPT_MAX_LINES, "line", "DRFE_POSE_OPT_MAX_LINES lines", err) ||
+        !batch_offsets_ok("pose_opt", p->plane_offsets, n, DRFE_POSE_OPT_MAX_PLANES, "plane", "DRFE_POSE_OPT_MAX_PLANES plane slots", err))
         return DRFE_ERR_INVALID;
     const int nP = p->point_offsets[n], nL = p->line_offsets[n], nS = p->plane_offsets[n];
     if (nS > 0 && (!p->plane_meas || !p->plane_world || !p->plane_mask || !o->plane_outlier || !o->par_plane_outlier ||
@@ -137,7 +119,7 @@ double host_errors(const PoFrameRec& F, const PoEdge* E, const uint8_t* flag, Po
     double chi = 0.0;
     for (int k = 0; k < F.nEdges; k++) {
         if (flag[k]) continue;
-        po_edge_error(S.ctx, E[k], F.cam, S.q, S.t, err + 3 * (size_t)k);
+        po_edge_error(S.lm.ctx, E[k], F.cam, S.q, S.t, err + 3 * (size_t)k);
         chi += po_chi_term(E[k], err + 3 * (size_t)k, robust);
     }
     return chi;
@@ -153,49 +135,49 @@ void host_frame(const PoFrameRec& F, const PoEdge* E, uint8_t* flag, PoFrameOut&
     if (nInitial < 3) return;
     std::vector<double> err(3 * (size_t)F.nEdges, 0.0);
     PoLM S;
-    po_lm_init(S, 1);
+    lm_init(S.lm, 1);
     int robust = 1, nBad = 0;
     for (int it = 0; it < 4; it++) {
         mp_to_se3quat(F.Tcw, S.q, S.t);
-        S.lastRejected = 0;
+        S.lm.lastRejected = 0;
         int nActive = 0;
         for (int k = 0; k < F.nEdges; k++) nActive += flag[k] ? 0 : 1;
         if (nActive == 0) O.diag[PO_DIAG_EMPTY_ROUNDS]++;       /* optimize() returns before its first iteration: no active vertex */
         for (int i = 0; i < 10 && nActive > 0; i++) {
             const double chi = host_errors(F, E, flag, S, robust, err.data());
-            for (int r = 0; r < PO_H_TERMS; r++) S.H[r] = 0.0;
-            for (int r = 0; r < 6; r++) S.b[r] = 0.0;
+            for (int r = 0; r < PO_H_TERMS; r++) S.lm.H[r] = 0.0;
+            for (int r = 0; r < 6; r++) S.lm.b[r] = 0.0;
             for (int k = 0; k < F.nEdges; k++) {
                 if (flag[k]) continue;
                 double J[3][6], term[PO_TERMS];
-                if (po_is_plane(E[k].kind)) po_plane_jacobian(S.ctx, E[k], S.q, S.t, J);
+                if (po_is_plane(E[k].kind)) po_plane_jacobian(S.lm.ctx, E[k], S.q, S.t, J);
                 else po_edge_jacobian(E[k], F.cam, S.q, S.t, J);
                 po_edge_terms(E[k], J, err.data() + 3 * (size_t)k, robust, term);
-                for (int r = 0; r < PO_H_TERMS; r++) S.H[r] += term[r];
-                for (int r = 0; r < 6; r++) S.b[r] -= term[PO_H_TERMS + r];
+                for (int r = 0; r < PO_H_TERMS; r++) S.lm.H[r] += term[r];
+                for (int r = 0; r < 6; r++) S.lm.b[r] -= term[PO_H_TERMS + r];
             }
-            po_lm_begin(S, i, chi);
+            lm_begin(S.lm, i, chi);
             int more;
             do {
-                po_lm_step(S);
-                more = po_lm_judge(S, host_errors(F, E, flag, S, robust, err.data()));
+                lm_step(S);
+                more = lm_judge(S, host_errors(F, E, flag, S, robust, err.data()));
             } while (more);
-            if (!po_lm_end(S)) break;
+            if (!lm_end(S.lm)) break;
         }
         O.rounds++;
-        if (S.lastRejected) O.diag[PO_DIAG_LAST_REJECTED]++;
+        if (S.lm.lastRejected) O.diag[PO_DIAG_LAST_REJECTED]++;
         nBad = 0;
         const int line0 = F.nPoints, plane0 = F.nPoints + 2 * F.nLines;
         for (int k = 0; k < F.nEdges; k++) {
             if (k >= line0 && k < plane0) continue;
-            if (flag[k]) po_edge_error(S.ctx, E[k], F.cam, S.q, S.t, err.data() + 3 * (size_t)k);
+            if (flag[k]) po_edge_error(S.lm.ctx, E[k], F.cam, S.q, S.t, err.data() + 3 * (size_t)k);
             flag[k] = (uint8_t)po_outlier(E[k], err.data() + 3 * (size_t)k);
             nBad += flag[k];
         }
         for (int l = 0; l < F.nLines; l++) {
             const int k = line0 + 2 * l;
-            po_edge_error(S.ctx, E[k], F.cam, S.q, S.t, err.data() + 3 * (size_t)k);
-            po_edge_error(S.ctx, E[k + 1], F.cam, S.q, S.t, err.data() + 3 * (size_t)(k + 1));
+            po_edge_error(S.lm.ctx, E[k], F.cam, S.q, S.t, err.data() + 3 * (size_t)k);
+            po_edge_error(S.lm.ctx, E[k + 1], F.cam, S.q, S.t, err.data() + 3 * (size_t)(k + 1));
             const int out = po_outlier(E[k], err.data() + 3 * (size_t)k) || po_outlier(E[k + 1], err.data() + 3 * (size_t)(k + 1));
             flag[k] = flag[k + 1] = (uint8_t)out;
             nBad += out;
@@ -205,12 +187,12 @@ void host_frame(const PoFrameRec& F, const PoEdge* E, uint8_t* flag, PoFrameOut&
     }
     po_pose_out(S.q, S.t, O.Tcw);
     O.ret = nInitial - nBad;
-    O.iterations = S.iterations;
-    O.trials = S.trials;
-    O.diag[PO_DIAG_REJECTED] = S.rejected;
-    O.diag[PO_DIAG_NBAD_STOPS] = S.nBadStops;
-    O.diag[PO_DIAG_SMALL_THETA] = S.smallTheta;
-    O.diag[PO_DIAG_BIG_THETA] = S.bigTheta;
+    O.iterations = S.lm.iterations;
+    O.trials = S.lm.trials;
+    O.diag[PO_DIAG_REJECTED] = S.lm.rejected;
+    O.diag[PO_DIAG_NBAD_STOPS] = S.lm.nBadStops;
+    O.diag[PO_DIAG_SMALL_THETA] = S.lm.smallTheta;
+    O.diag[PO_DIAG_BIG_THETA] = S.lm.bigTheta;
 }
 
 /* a frame's record and per-edge flags into the caller's arrays */
@@ -261,8 +243,7 @@ int drfe_pose_opt_batch(drfe_ctx* c, const drfe_pose_opt_problems* p, drfe_pose_
     Plan P;
     const int rc = make_plan(p, o, P, c->err);
     if (rc) return rc;
-    PoseOptBuffers* b = c->pose_opt;
-    if (!b) { b = new PoseOptBuffers(); c->pose_opt = b; }
+    PoseOptBuffers* b = batch_buffers(c->pose_opt);
     b->stats[0]++;
     if (p->n == 0) return DRFE_OK;
     const int n = p->n;
@@ -273,18 +254,15 @@ int drfe_pose_opt_batch(drfe_ctx* c, const drfe_pose_opt_problems* p, drfe_pose_
     const auto sOut = out.add<PoFrameOut>((size_t)n);
     const auto sFlag = out.add<uint8_t>(nE);
     const auto sErr = scr.add<double>(3 * nE);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, b->io.grow(in.bytes(), out.bytes()));
-    HIPCHK(c, b->scratch.grow(scr.bytes()));
+    hipStream_t st;
+    if (const int e = batch_begin(c, b, stream, in.bytes(), out.bytes(), scr.bytes(), &st)) return e;
     char* h = b->io.hin;
     sFrame.put(h, P.frame.data());
     sEdge.put(h, P.edge.data());
     const char* d = b->io.din;
     char* dO = b->io.dout;
     char* dS = b->scratch;
-    HIPCHK(c, hipMemcpyAsync(b->io.din, h, in.bytes(), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(dO, 0, out.bytes(), st));
+    if (const int e = batch_upload(c, b, in.bytes(), out.bytes(), st)) return e;
     PoLaunch L{};
     L.nFrames = n;
     L.frame = sFrame.at(d);
@@ -292,10 +270,7 @@ int drfe_pose_opt_batch(drfe_ctx* c, const drfe_pose_opt_problems* p, drfe_pose_
     L.err = sErr.at(dS);
     L.flag = sFlag.at(dO);
     L.out = sOut.at(dO);
-    hipError_t e = drfe_launch_pose_opt(L, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(b->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) { c->err = std::string("pose_opt batch: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
-    HIPCHK(c, hipStreamSynchronize(st));
+    if (const int e = batch_finish(c, "pose_opt", drfe_launch_pose_opt(L, st), b, out.bytes(), st)) return e;
     const char* ho = b->io.hout;
     std::vector<uint8_t> flag;
     for (int f = 0; f < n; f++) {
@@ -322,21 +297,9 @@ int drfe_pose_opt_batch(drfe_ctx* c, const drfe_pose_opt_problems* p, drfe_pose_
     return DRFE_OK;
 }
 
-int drfe_pose_opt_stats(drfe_ctx* c, int64_t* stats)
-{
-    if (!c || !stats) return DRFE_ERR_INVALID;
-    if (c->pose_opt) std::memcpy(stats, c->pose_opt->stats, sizeof(c->pose_opt->stats));
-    else std::memset(stats, 0, 8 * sizeof(int64_t));
-    return DRFE_OK;
-}
+int drfe_pose_opt_stats(drfe_ctx* c, int64_t* stats) { return batch_stats(c, &drfe_ctx::pose_opt, stats); }
 
-int drfe_debug_pose_opt_hand_back(drfe_ctx* c, int every)
-{
-    if (!c || every < 0) return DRFE_ERR_INVALID;
-    if (!c->pose_opt) c->pose_opt = new PoseOptBuffers();
-    c->pose_opt->handBackEvery = every;
-    return DRFE_OK;
-}
+int drfe_debug_pose_opt_hand_back(drfe_ctx* c, int every) { return batch_hand_back(c, &drfe_ctx::pose_opt, every); }
 
 int drfe_debug_cr_cube(const double* x, int n, double* out, uint8_t* ok)
 {
@@ -357,7 +320,7 @@ int drfe_debug_pose_opt_plane_error(int kind, const float* meas, const float* wo
     po_to_plane3d(world, E.X);
     double q[4], t[3];
     mp_to_se3quat(Tcw, q, t);
-    PoCtx ctx = {0, 1};
+    LmCtx ctx = {0, 1};
     po_plane_error(ctx, E, q, t, e);
     return DRFE_OK;
 }
@@ -368,7 +331,7 @@ int drfe_debug_pose_opt_ldlt(const double* A, const double* b, double* x, int32_
     double M[6][6];
     for (int i = 0; i < 6; i++)
         for (int j = 0; j < 6; j++) M[i][j] = A[6 * i + j];
-    *positive = po_ldlt_solve(M, b, x);
+    *positive = lm_ldlt_solve<6>(M, b, x);
     return DRFE_OK;
 }
 

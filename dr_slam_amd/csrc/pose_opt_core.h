@@ -1,6 +1,6 @@
 /* pose_opt_core.h — the arithmetic of Optimizer::PoseOptimization (reference src/Optimizer.cc:601-1338) and of what g2o runs
- * under it, restated statement by statement: the unary edges, Huber's kernel, the 6x6 normal equations, Eigen's LDLT, the
- * Levenberg step control and VertexSE3Expmap::oplusImpl.  Shared by the host entry (pose_opt.cpp) and the device kernel
+ * under it, restated statement by statement: the unary edges, Huber's kernel, the 6x6 normal equations and
+ * VertexSE3Expmap::oplusImpl; Eigen's LDLT and the Levenberg step control are lm_core.h's.  Shared by the host entry (pose_opt.cpp) and the device kernel
  * (pose_opt_kernels.hip) so that both produce the same bits: plain IEEE add / mul / div / sqrt in double, compiled with
  * -ffp-contract=off on both sides; sin, cos and the two cubes through cr_sincos.h / cr_cube.h.  DESIGN.md section 20 states the
  * evaluation order of every expression; where Eigen leaves an association open it is read left to right.
@@ -14,7 +14,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "map_plane_core.h"
-#include "cr_cube.h"
+#include "lm_core.h"
 #include "cr_atan2.h"
 
 enum { PO_MONO = 0, PO_STEREO = 1, PO_LINE = 2, PO_PLANE = 3, PO_PAR_PLANE = 4, PO_VER_PLANE = 5 };
@@ -38,10 +38,6 @@ struct PoEdge {
 /* a frame's camera: fx fy cx cy bf, floats widened as the reference's `e->fx = pFrame->fx` does */
 struct PoCam { double fx, fy, cx, cy, bf; };
 
-/* what a lane carries through the transcendentals: fail = one could not be certified and no libm stood in (device: the frame goes
- * back to the host); libm = the host's libm stands in */
-struct PoCtx { int32_t fail, libm; };
-
 DRFE_HD int po_dim(int kind) { return (kind == PO_MONO || kind == PO_PAR_PLANE || kind == PO_VER_PLANE) ? 2 : 3; }
 DRFE_HD int po_is_plane(int kind) { return kind >= PO_PLANE; }
 
@@ -52,21 +48,9 @@ DRFE_HD double po_th_mono() { return (double)5.991f; }
 DRFE_HD double po_th_stereo() { return (double)7.815f; }
 DRFE_HD double po_th_line() { return (double)(2 * 5.991f); }
 
-/* the transcendentals: correctly rounded, or the host's libm where the certificate fails, or ctx.fail */
-DRFE_HD double po_cube(PoCtx& ctx, double v)
-{
-    double r;
-    if (!(fabs(v) <= DBL_MAX)) return v * v * v;          /* NaN and the infinities, as pow(v, 3) */
-    if (drfe_cr_cube(v, &r)) return r;
-#if !defined(__HIP_DEVICE_COMPILE__)
-    if (ctx.libm) return pow(v, 3);
-#endif
-    ctx.fail = 1;
-    return r;
-}
-
-/* sin and cos of any |x| < 64: sin is odd, cos even, exactly */
-DRFE_HD void po_sincos(PoCtx& ctx, double x, double* sn, double* cs)
+/* the transcendentals (the cube is lm_core.h's): correctly rounded, or the host's libm where the certificate fails, or ctx.fail.
+ * sin and cos of any |x| < 64: sin is odd, cos even, exactly */
+DRFE_HD void po_sincos(LmCtx& ctx, double x, double* sn, double* cs)
 {
     const double ax = fabs(x);
     double s = 0.0, c = 1.0;
@@ -83,7 +67,7 @@ DRFE_HD void po_sincos(PoCtx& ctx, double x, double* sn, double* cs)
 }
 
 /* atan2 of any y: odd in y, exactly (atan2(-0, x) = -atan2(+0, x)) */
-DRFE_HD double po_atan2(PoCtx& ctx, double y, double x)
+DRFE_HD double po_atan2(LmCtx& ctx, double y, double x)
 {
     const int neg = y == y && signbit(y);
     double r;
@@ -130,7 +114,7 @@ DRFE_HD void po_to_plane3d(const float coe[4], double c[4])
 /* Plane3D::rotation(v): (AngleAxisd(azimuth, Z) * AngleAxisd(-elevation, Y)).toRotationMatrix().  AngleAxis * AngleAxis is the
  * product of their quaternions (w = cos(angle / 2), vec = sin(angle / 2) * axis, the zeros of the axes multiplied through),
  * Eigen's generic quat_product, not normalised */
-DRFE_HD void po_plane_rotation(PoCtx& ctx, const double v[3], double R[3][3])
+DRFE_HD void po_plane_rotation(LmCtx& ctx, const double v[3], double R[3][3])
 {
     const double az = po_atan2(ctx, v[1], v[0]);
     const double el = po_atan2(ctx, v[2], sqrt(v[0] * v[0] + v[1] * v[1]));
@@ -148,7 +132,7 @@ DRFE_HD void po_plane_rotation(PoCtx& ctx, const double v[3], double R[3][3])
 }
 
 /* R^T m, then (azimuth, elevation) of it: the tail of ominus, ominus_par and ominus_ver */
-DRFE_HD void po_plane_angles(PoCtx& ctx, const double nor[3], const double m[3], double e[2])
+DRFE_HD void po_plane_angles(LmCtx& ctx, const double nor[3], const double m[3], double e[2])
 {
     double R[3][3], n[3];
     po_plane_rotation(ctx, nor, R);
@@ -160,8 +144,8 @@ DRFE_HD void po_plane_angles(PoCtx& ctx, const double nor[3], const double m[3],
 /* computeError of EdgePlaneOnlyPose / EdgeParallelPlaneOnlyPose / EdgeVerticalPlaneOnlyPose: localPlane = Isometry3D(estimate) *
  * Xw (operator*, Plane3D.h:189-202; rotation() of an isometry is its linear part), then ominus / ominus_par / ominus_ver of the
  * measurement */
-DRFE_HD void po_plane_ominus(PoCtx& ctx, const PoEdge& E, double l[4], const double t[3], double e[3]);
-DRFE_HD void po_plane_error(PoCtx& ctx, const PoEdge& E, const double q[4], const double t[3], double e[3])
+DRFE_HD void po_plane_ominus(LmCtx& ctx, const PoEdge& E, double l[4], const double t[3], double e[3]);
+DRFE_HD void po_plane_error(LmCtx& ctx, const PoEdge& E, const double q[4], const double t[3], double e[3])
 {
     double R[3][3], l[4];
     mp_quat_to_matrix(q, R);
@@ -171,7 +155,7 @@ DRFE_HD void po_plane_error(PoCtx& ctx, const PoEdge& E, const double q[4], cons
 
 /* what follows the normal l[0..2] of the local plane, shared with the translation-only plane edges (trans_opt_core.h, whose
  * operator+ leaves the normal as it is): d - t . n, the four negated below zero, the Plane3D constructor, then the edge's ominus */
-DRFE_HD void po_plane_ominus(PoCtx& ctx, const PoEdge& E, double l[4], const double t[3], double e[3])
+DRFE_HD void po_plane_ominus(LmCtx& ctx, const PoEdge& E, double l[4], const double t[3], double e[3])
 {
     l[3] = E.X[3] - ((t[0] * l[0] + t[1] * l[1]) + t[2] * l[2]);
     if (l[3] < 0.0)
@@ -209,7 +193,7 @@ DRFE_HD void po_plane_ominus(PoCtx& ctx, const PoEdge& E, double l[4], const dou
 
 /* computeError of the edge under the estimate (q, t); e[2] of a mono edge is not read and set to 0 */
 DRFE_HD void po_project_error(const PoEdge& E, const PoCam& C, const double p[3], double e[3]);
-DRFE_HD void po_edge_error(PoCtx& ctx, const PoEdge& E, const PoCam& C, const double q[4], const double t[3], double e[3])
+DRFE_HD void po_edge_error(LmCtx& ctx, const PoEdge& E, const PoCam& C, const double q[4], const double t[3], double e[3])
 {
     if (po_is_plane(E.kind)) { po_plane_error(ctx, E, q, t, e); return; }
     double p[3];
@@ -371,111 +355,8 @@ DRFE_HD void po_edge_terms(const PoEdge& E, const double J[3][6], const double e
     }
 }
 
-/* ---- the vertex and the step control: one lane ---- */
-
-struct PoLM {
-    double q[4], t[3];             /* the estimate: quaternion x y z w, translation */
-    double qs[4], ts[3];           /* what push() saved */
-    double H[PO_H_TERMS], b[6];    /* the system of the current iteration */
-    double x[6];                   /* the solver's x: kept over a failed solve and over rounds, zero at the start of a call */
-    double lambda, ni, currentChi, iniChi, rho;
-    int32_t nBad, qmax;
-    int32_t solved;                /* the last trial's LDLT was isPositive() and wrote x (Levenberg's ok2) */
-    PoCtx ctx;
-    int32_t iterations, trials, rejected, lastRejected, nBadStops, smallTheta, bigTheta;   /* diagnostics of the call */
-};
-
-DRFE_HD void po_lm_init(PoLM& S, int libm)
-{
-    for (int k = 0; k < 6; k++) S.x[k] = 0.0;
-    S.ctx.fail = 0; S.ctx.libm = libm;
-    S.iterations = 0; S.trials = 0; S.rejected = 0; S.lastRejected = 0; S.nBadStops = 0; S.smallTheta = 0; S.bigTheta = 0;
-    S.lambda = -1.0; S.ni = 2.0; S.nBad = 0; S.qmax = 0; S.solved = 0; S.rho = 0.0; S.currentChi = 0.0; S.iniChi = 0.0;
-}
-
-/* Eigen::LDLT<MatrixXd>::compute of the 6x6 whose lower triangle is A (full storage, row-major; the upper triangle is not
- * read), in place (ldlt_inplace<Lower>::unblocked, Eigen 3.3.7), then solve(b) into x when isPositive().  Returns isPositive().
- * Dot products and the rank update's products are summed over the inner index from 0 up.  The size is a template argument: the
- * 7x7 of the Sim3 vertex (sim3_opt_core.h) runs the same statements. */
-template <int N>
-DRFE_HD int po_ldlt_solve_n(double A[N][N], const double b[N], double x[N])
-{
-    const int n = N;
-    int tr[N];
-    double temp[N];
-    int sign = 0;                                  /* 0 ZeroSign, 1 PositiveSemiDef, -1 NegativeSemiDef, 2 Indefinite */
-    bool early = false;                            /* (found_zero_pivot only decides info(), which g2o does not read) */
-    for (int k = 0; k < n && !early; k++) {
-        int big = k;
-        double best = fabs(A[k][k]);
-        for (int i = k + 1; i < n; i++) {
-            const double v = fabs(A[i][i]);
-            if (v > best) { best = v; big = i; }
-        }
-        tr[k] = big;
-        if (k != big) {
-            for (int j = 0; j < k; j++) { const double s = A[k][j]; A[k][j] = A[big][j]; A[big][j] = s; }
-            for (int i = big + 1; i < n; i++) { const double s = A[i][k]; A[i][k] = A[i][big]; A[i][big] = s; }
-            { const double s = A[k][k]; A[k][k] = A[big][big]; A[big][big] = s; }
-            for (int i = k + 1; i < big; i++) { const double s = A[i][k]; A[i][k] = A[big][i]; A[big][i] = s; }
-        }
-        const int rs = n - k - 1;
-        if (k > 0) {
-            for (int j = 0; j < k; j++) temp[j] = A[j][j] * A[k][j];
-            double s = 0.0;
-            for (int j = 0; j < k; j++) { const double a = A[k][j] * temp[j]; s = j == 0 ? a : s + a; }
-            A[k][k] -= s;
-            for (int i = k + 1; i < n; i++) {
-                double u = 0.0;
-                for (int j = 0; j < k; j++) { const double a = A[i][j] * temp[j]; u = j == 0 ? a : u + a; }
-                A[i][k] -= u;
-            }
-        }
-        const double realAkk = A[k][k];
-        const bool pivot_is_valid = fabs(realAkk) > 0.0;
-        if (k == 0 && !pivot_is_valid) {
-            sign = 0;
-            for (int j = 0; j < n; j++) tr[j] = j;
-            early = true;
-            break;
-        }
-        if (rs > 0 && pivot_is_valid)
-            for (int i = k + 1; i < n; i++) A[i][k] /= realAkk;
-        if (sign == 1) {
-            if (realAkk < 0.0) sign = 2;
-        } else if (sign == -1) {
-            if (realAkk > 0.0) sign = 2;
-        } else if (sign == 0) {
-            if (realAkk > 0.0) sign = 1;
-            else if (realAkk < 0.0) sign = -1;
-        }
-    }
-    if (!(sign == 1 || sign == 0)) return 0;
-    /* LDLT::_solve_impl: P b; L^-1 (column by column); D^-1 with the tolerance 1 / highest(); L^-T (row by row); P^T */
-    double d[N];
-    for (int i = 0; i < n; i++) d[i] = b[i];
-    for (int k = 0; k < n; k++) { const double s = d[k]; d[k] = d[tr[k]]; d[tr[k]] = s; }
-    for (int i = 0; i < n; i++)
-        if (d[i] != 0.0)                           /* triangular_solve_vector skips a zero right-hand side element */
-            for (int j = i + 1; j < n; j++) d[j] -= d[i] * A[j][i];
-    const double tolerance = 1.0 / DBL_MAX;
-    for (int i = 0; i < n; i++) {
-        if (fabs(A[i][i]) > tolerance) d[i] /= A[i][i];
-        else d[i] = 0.0;
-    }
-    for (int i = n - 1; i >= 0; i--) {
-        double s = 0.0;
-        for (int j = i + 1; j < n; j++) { const double a = A[j][i] * d[j]; s = j == i + 1 ? a : s + a; }
-        if (i + 1 < n) d[i] -= s;
-    }
-    for (int k = n - 1; k >= 0; k--) { const double s = d[k]; d[k] = d[tr[k]]; d[tr[k]] = s; }
-    for (int i = 0; i < n; i++) x[i] = d[i];
-    return 1;
-}
-DRFE_HD int po_ldlt_solve(double A[6][6], const double b[6], double x[6]) { return po_ldlt_solve_n<6>(A, b, x); }
-
 /* VertexSE3Expmap::oplusImpl: estimate = SE3Quat::exp(u) * estimate (types/se3quat.h:227-261, :104-110) */
-DRFE_HD int po_oplus(PoCtx& ctx, double q[4], double t[3], const double u[6])
+DRFE_HD int po_oplus(LmCtx& ctx, double q[4], double t[3], const double u[6])
 {
     const double o0 = u[0], o1 = u[1], o2 = u[2];
     const double theta = sqrt((o0 * o0 + o1 * o1) + o2 * o2);
@@ -495,7 +376,7 @@ DRFE_HD int po_oplus(PoCtx& ctx, double q[4], double t[3], const double u[6])
         po_sincos(ctx, theta, &sn, &cs);
         const double a = sn / theta;
         const double bq = (1.0 - cs) / (theta * theta);
-        const double cq = (theta - sn) / po_cube(ctx, theta);
+        const double cq = (theta - sn) / lm_cube(ctx, theta);
         for (int r = 0; r < 3; r++)
             for (int c = 0; c < 3; c++) {
                 const double id = r == c ? 1.0 : 0.0;
@@ -534,7 +415,7 @@ DRFE_HD int po_oplus(PoCtx& ctx, double q[4], double t[3], const double u[6])
 /* BaseUnaryEdge::linearizeOplus, the numeric Jacobian of the plane edges (core/base_unary_edge.hpp:82-123): perturbation
  * (d, side) is computeError at exp(+-1e-9 e_d) * estimate, side 0 the plus step; column d = (1 / 2e-9) * (plus - minus).  The
  * estimate is pushed and popped around every step and _error restored afterwards, so nothing but J leaves. */
-DRFE_HD void po_plane_perturbed(PoCtx& ctx, const PoEdge& E, const double q[4], const double t[3], int d, int side, double e[3])
+DRFE_HD void po_plane_perturbed(LmCtx& ctx, const PoEdge& E, const double q[4], const double t[3], int d, int side, double e[3])
 {
     double u[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, pq[4], pt[3];
     u[d] = side ? -1e-9 : 1e-9;
@@ -543,10 +424,9 @@ DRFE_HD void po_plane_perturbed(PoCtx& ctx, const PoEdge& E, const double q[4], 
     (void)po_oplus(ctx, pq, pt, u);
     po_plane_error(ctx, E, pq, pt, e);
 }
-DRFE_HD double po_numeric_scalar() { return 1.0 / (2 * 1e-9); }
-DRFE_HD void po_plane_jacobian(PoCtx& ctx, const PoEdge& E, const double q[4], const double t[3], double J[3][6])
+DRFE_HD void po_plane_jacobian(LmCtx& ctx, const PoEdge& E, const double q[4], const double t[3], double J[3][6])
 {
-    const double scalar = po_numeric_scalar();
+    const double scalar = lm_numeric_scalar();
     for (int d = 0; d < 6; d++) {
         double e1[3], e2[3];
         po_plane_perturbed(ctx, E, q, t, d, 0, e1);
@@ -555,85 +435,33 @@ DRFE_HD void po_plane_jacobian(PoCtx& ctx, const PoEdge& E, const double q[4], c
     }
 }
 
-/* OptimizationAlgorithmLevenberg::solve (core/optimization_algorithm_levenberg.cpp:61-164) cut at its calls into the graph:
- *   po_lm_begin(S, iteration, chi)   after computeActiveErrors / activeRobustChi2 / buildSystem (S.H, S.b filled)
- *   po_lm_step(S)                    push, setLambda, solve, update, restoreDiagonal; then the caller recomputes the errors
- *   po_lm_judge(S, tempChi)          the rho test; returns 1 when the do-while goes on
- *   po_lm_end(S)                     returns 1 for OK, 0 for Terminate */
-DRFE_HD void po_lm_begin(PoLM& S, int iteration, double chi)
-{
-    S.currentChi = chi;
-    S.iniChi = chi;
-    if (iteration == 0) {
-        /* computeLambdaInit: std::max(fabs(h), maxDiagonal) is (fabs(h) < maxDiagonal) ? maxDiagonal : fabs(h) */
-        double maxDiagonal = 0.0;
-        for (int j = 0; j < 6; j++) {
-            const double a = fabs(S.H[j * (j + 1) / 2 + j]);
-            maxDiagonal = a < maxDiagonal ? maxDiagonal : a;
-        }
-        S.lambda = 1e-5 * maxDiagonal;
-        S.ni = 2.0;
-        S.nBad = 0;
-    }
-    S.rho = 0.0;
-    S.qmax = 0;
-    S.iterations++;
-}
+/* ---- the vertex under lm_core.h's step control: one lane ---- */
 
-DRFE_HD void po_lm_step(PoLM& S)
+struct PoLM {
+    double q[4], t[3];             /* the estimate: quaternion x y z w, translation */
+    double qs[4], ts[3];           /* what push() saved */
+    LmControl<6> lm;               /* x is kept over rounds */
+};
+
+/* push, solve, update */
+DRFE_HD void lm_step(PoLM& S)
 {
     for (int k = 0; k < 4; k++) S.qs[k] = S.q[k];
     for (int k = 0; k < 3; k++) S.ts[k] = S.t[k];
-    double A[6][6];
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j <= i; j++) {
-            const double h = S.H[i * (i + 1) / 2 + j];
-            A[i][j] = i == j ? h + S.lambda : h;
-            A[j][i] = A[i][j];
-        }
-    S.solved = po_ldlt_solve(A, S.b, S.x);
-    if (po_oplus(S.ctx, S.q, S.t, S.x)) S.smallTheta++;
-    else S.bigTheta++;
-    S.trials++;
+    lm_solve(S.lm);
+    lm_count_theta(S.lm, po_oplus(S.lm.ctx, S.q, S.t, S.lm.x));
 }
 
-DRFE_HD int po_lm_judge(PoLM& S, double tempChi)
+/* the rho test, pop after a rejected trial */
+DRFE_HD int lm_judge(PoLM& S, double tempChi)
 {
-    if (!S.solved) tempChi = DBL_MAX;
-    double rho = S.currentChi - tempChi;
-    double scale = 0.0;
-    for (int j = 0; j < 6; j++) scale += S.x[j] * (S.lambda * S.x[j] + S.b[j]);
-    scale += 1e-3;
-    rho /= scale;
-    if (rho > 0.0 && isfinite(tempChi)) {
-        double alpha = 1.0 - po_cube(S.ctx, 2.0 * rho - 1.0);
-        const double up = 2.0 / 3.0, lo = 1.0 / 3.0;
-        alpha = up < alpha ? up : alpha;                       /* std::min(alpha, up) */
-        const double scaleFactor = lo < alpha ? alpha : lo;    /* std::max(lo, alpha) */
-        S.lambda *= scaleFactor;
-        S.ni = 2.0;
-        S.currentChi = tempChi;
-        S.lastRejected = 0;
-    } else {
-        S.lambda *= S.ni;
-        S.ni *= 2.0;
+    int accepted;
+    const int more = lm_judge(S.lm, tempChi, accepted);
+    if (!accepted) {
         for (int k = 0; k < 4; k++) S.q[k] = S.qs[k];
         for (int k = 0; k < 3; k++) S.t[k] = S.ts[k];
-        S.rejected++;
-        S.lastRejected = 1;
     }
-    S.rho = rho;
-    S.qmax++;
-    return rho < 0.0 && S.qmax < 10;
-}
-
-DRFE_HD int po_lm_end(PoLM& S)
-{
-    if (S.qmax == 10 || S.rho == 0.0) return 0;
-    if ((S.iniChi - S.currentChi) * 1e3 < S.iniChi) S.nBad++;
-    else S.nBad = 0;
-    if (S.nBad >= 3) { S.nBadStops++; return 0; }
-    return 1;
+    return more;
 }
 
 /* the classification of one edge after a round (src/Optimizer.cc:1067-1326): 1 for an outlier.  `const float chi2 = e->chi2()`

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "pose_opt_internal.h"
+#include "lm_device.h"
 
 namespace {
 
@@ -28,30 +29,15 @@ struct PoShared {
 };
 
 /* what lanes 0..26 and lane 0 add after a chunk's terms are in LDS */
-struct PoSums {
-    double acc, chi;
-    __device__ void add(const PoShared& sh, int cnt, bool build)
-    {
-        const int tid = threadIdx.x;
-        if (tid == 0)
-            for (int j = 0; j < cnt; j++) chi += sh.chi[j];
-        if (build && tid < PO_TERMS) {
-            const double* row = sh.term + tid * PO_TERM_STRIDE;
-            if (tid < PO_H_TERMS)
-                for (int j = 0; j < cnt; j++) acc += row[j];
-            else
-                for (int j = 0; j < cnt; j++) acc -= row[j];
-        }
-    }
-};
+using PoSums = LmSums<PO_TERMS, PO_H_TERMS, PO_TERM_STRIDE>;
 
-/* computeActiveErrors and activeRobustChi2; with `build` also linearizeOplus and constructQuadraticForm into S.H / S.b.
+/* computeActiveErrors and activeRobustChi2; with `build` also linearizeOplus and constructQuadraticForm into S.lm.H / S.lm.b.
  * Returns the robust chi2 in lane 0.  Every lane of the workgroup calls it. */
 __device__ double po_pass(PoShared& sh, const PoFrameRec& F, const PoEdge* edge, double* err, const uint8_t* flag, int robust,
                           bool build)
 {
     const int tid = threadIdx.x;
-    PoCtx ctx = {0, 0};
+    LmCtx ctx = {0, 0};
     double q[4], t[3];
     for (int k = 0; k < 4; k++) q[k] = sh.S.q[k];
     for (int k = 0; k < 3; k++) t[k] = sh.S.t[k];
@@ -78,7 +64,7 @@ __device__ double po_pass(PoShared& sh, const PoFrameRec& F, const PoEdge* edge,
         }
         sh.chi[tid] = c;
         __syncthreads();
-        sums.add(sh, plane0 - base < PO_THREADS ? plane0 - base : PO_THREADS, build);
+        sums.add(sh.term, sh.chi, plane0 - base < PO_THREADS ? plane0 - base : PO_THREADS, build);
         __syncthreads();
     }
     for (int base = plane0; base < F.nEdges; base += PO_PLANE_GROUP) {
@@ -109,7 +95,7 @@ __device__ double po_pass(PoShared& sh, const PoFrameRec& F, const PoEdge* edge,
             double term[PO_TERMS];
             if (act) {
                 double J[3][6];
-                const double scalar = po_numeric_scalar();
+                const double scalar = lm_numeric_scalar();
                 for (int d = 0; d < 6; d++)
                     for (int r = 0; r < 3; r++)
                         J[r][d] = scalar * (sh.pert[((own * 12 + 2 * d) * 3) + r] - sh.pert[((own * 12 + 2 * d + 1) * 3) + r]);
@@ -120,13 +106,13 @@ __device__ double po_pass(PoShared& sh, const PoFrameRec& F, const PoEdge* edge,
             for (int r = 0; r < PO_TERMS; r++) sh.term[r * PO_TERM_STRIDE + own] = term[r];
         }
         __syncthreads();
-        sums.add(sh, cnt, build);
+        sums.add(sh.term, sh.chi, cnt, build);
         __syncthreads();
     }
     if (ctx.fail) sh.fail = 1;
     if (build) {
-        if (tid < PO_H_TERMS) sh.S.H[tid] = sums.acc;
-        else if (tid < PO_TERMS) sh.S.b[tid - PO_H_TERMS] = sums.acc;
+        if (tid < PO_H_TERMS) sh.S.lm.H[tid] = sums.acc;
+        else if (tid < PO_TERMS) sh.S.lm.b[tid - PO_H_TERMS] = sums.acc;
         __syncthreads();
     }
     return sums.chi;
@@ -143,20 +129,20 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoLaunch L)
     const PoEdge* edge = L.edge + F.edge0;
     double* err = L.err + 3 * (size_t)F.edge0;
     uint8_t* flag = L.flag + F.edge0;
-    const int nInitial = F.nPoints + F.nLines + F.nPlaneEdges;
+    const int nInitial = lm_uniform(F.nPoints + F.nLines + F.nPlaneEdges), nEdges = lm_uniform(F.nEdges);
     if (nInitial < 3) {                                 /* uniform: the pose untouched, the flags false (zero before the launch) */
         if (tid < 16) O.Tcw[tid] = F.Tcw[tid];
         return;
     }
     int robust = 1, rounds = 0, lastRejectedRounds = 0, emptyRounds = 0, nBad = 0;
     if (tid == 0) {
-        po_lm_init(sh.S, 0);
+        lm_init(sh.S.lm, 0);
         sh.fail = 0;
     }
     for (int it = 0; it < 4; it++) {
         if (tid == 0) {
             mp_to_se3quat(F.Tcw, sh.S.q, sh.S.t);
-            sh.S.lastRejected = 0;
+            sh.S.lm.lastRejected = 0;
             sh.count = 0;
         }
         __syncthreads();
@@ -166,38 +152,20 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoLaunch L)
             if (mine) atomicAdd(&sh.count, mine);
         }
         __syncthreads();
-        const int nActive = sh.count;
+        const int nActive = lm_uniform(sh.count);
         __syncthreads();
         if (nActive == 0) emptyRounds++;
-        for (int i = 0; i < 10 && nActive > 0; i++) {
-            const double chi = po_pass(sh, F, edge, err, flag, robust, true);
-            if (tid == 0) po_lm_begin(sh.S, i, chi);
-            int more;
-            do {
-                if (tid == 0) po_lm_step(sh.S);
-                __syncthreads();
-                const double tempChi = po_pass(sh, F, edge, err, flag, robust, false);
-                if (tid == 0) sh.ctl = po_lm_judge(sh.S, tempChi);
-                __syncthreads();
-                more = sh.ctl;
-                __syncthreads();
-            } while (more);
-            if (tid == 0) sh.ctl = po_lm_end(sh.S);
-            __syncthreads();
-            const int ok = sh.ctl;
-            __syncthreads();
-            if (!ok) break;
-        }
+        else lm_iterations(sh.S, sh.ctl, 10, [&](bool build) { return po_pass(sh, F, edge, err, flag, robust, build); });
         rounds++;
         if (tid == 0) {
-            if (sh.S.lastRejected) lastRejectedRounds++;
+            if (sh.S.lm.lastRejected) lastRejectedRounds++;
             sh.count = 0;
         }
         __syncthreads();
         /* the classification: a point or a plane by one lane (a point by the lane that owns its edge in po_pass), a line's two
          * ends by one lane */
         {
-            PoCtx ctx = {0, 0};
+            LmCtx ctx = {0, 0};
             double q[4], t[3];
             for (int k = 0; k < 4; k++) q[k] = sh.S.q[k];
             for (int k = 0; k < 3; k++) t[k] = sh.S.t[k];
@@ -232,10 +200,10 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoLaunch L)
             if (ctx.fail) sh.fail = 1;
         }
         __syncthreads();
-        nBad = sh.count;
+        nBad = lm_uniform(sh.count);
         __syncthreads();
         if (it == 2) robust = 0;
-        if (F.nEdges < 10) break;
+        if (nEdges < 10) break;
     }
     if (tid == 0) {
         float T[16];
@@ -243,15 +211,15 @@ __global__ __launch_bounds__(PO_THREADS) void k_pose_opt(const PoLaunch L)
         for (int k = 0; k < 16; k++) O.Tcw[k] = T[k];
         O.ret = nInitial - nBad;
         O.rounds = rounds;
-        O.iterations = sh.S.iterations;
-        O.trials = sh.S.trials;
-        O.diag[PO_DIAG_REJECTED] = sh.S.rejected;
+        O.iterations = sh.S.lm.iterations;
+        O.trials = sh.S.lm.trials;
+        O.diag[PO_DIAG_REJECTED] = sh.S.lm.rejected;
         O.diag[PO_DIAG_LAST_REJECTED] = lastRejectedRounds;
-        O.diag[PO_DIAG_NBAD_STOPS] = sh.S.nBadStops;
-        O.diag[PO_DIAG_SMALL_THETA] = sh.S.smallTheta;
-        O.diag[PO_DIAG_BIG_THETA] = sh.S.bigTheta;
+        O.diag[PO_DIAG_NBAD_STOPS] = sh.S.lm.nBadStops;
+        O.diag[PO_DIAG_SMALL_THETA] = sh.S.lm.smallTheta;
+        O.diag[PO_DIAG_BIG_THETA] = sh.S.lm.bigTheta;
         O.diag[PO_DIAG_EMPTY_ROUNDS] = emptyRounds;
-        O.handBack = (sh.S.ctx.fail || sh.fail) ? 1 : 0;
+        O.handBack = (sh.S.lm.ctx.fail || sh.fail) ? 1 : 0;
     }
 }
 

@@ -1,12 +1,12 @@
 /* ransac_table.h — what the RANSAC solvers (sim3.cpp, pnp.cpp) share on the host: a call is a table of rows, one per hypothesis,
  * a solver's rows contiguous; the caller's table has a solver's cap of rows, the compact one of a call only those that run.  Here:
- * the iteration count, the sampling, the plan of where a solver's rows lie in both tables, the head of a solver's device record
- * and the two ends of a batch entry that do not depend on the mathematics.  A solver keeps its argument checks, its records and
- * its rows.  Host only; DESIGN.md section 16. */
+ * the iteration count, the sampling, the plan of where a solver's rows lie in both tables and the head of a solver's device record;
+ * the buffers and the ends of a batch entry are batch_entry.h's.  A solver keeps its argument checks, its records and its rows.
+ * Host only; DESIGN.md section 16. */
 #ifndef DRFE_RANSAC_TABLE_H
 #define DRFE_RANSAC_TABLE_H
 
-#include "drfe_internal.h"
+#include "batch_entry.h"
 #include "glibc_rand.h"
 
 #include <climits>
@@ -139,27 +139,5 @@ struct RansacPlan {
             if (!h) stats[7]++;
     }
 };
-
-/* a solver's buffers in the context */
-struct RansacBuffers {
-    StagePair io;                      /* staging: one copy each way */
-    DevBuf<char> scratch;
-    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-};
-
-inline void ransac_stats(const RansacBuffers* b, int64_t* stats)
-{
-    if (b) std::memcpy(stats, b->stats, sizeof(b->stats));
-    else std::memset(stats, 0, 8 * sizeof(int64_t));
-}
-
-/* the end of a batch entry: the launches' error, the out block back to the host, the stream drained */
-inline int ransac_finish(drfe_ctx* c, const char* name, hipError_t e, StagePair& io, size_t outBytes, hipStream_t st)
-{
-    if (e == hipSuccess) e = hipMemcpyAsync(io.hout, io.dout, outBytes, hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) { c->err = std::string(name) + " batch: " + hipGetErrorString(e); return DRFE_ERR_HIP; }
-    HIPCHK(c, hipStreamSynchronize(st));
-    return DRFE_OK;
-}
 
 #endif

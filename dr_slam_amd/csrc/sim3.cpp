@@ -7,15 +7,9 @@
 #include "stage_layout.h"
 #include "../../include/drfe_debug.h"
 
-struct Sim3Buffers : RansacBuffers {   /* scratch: Sim3Corr per correspondence, T21 per hypothesis */
-    int handBackEvery = 0;             /* drfe_debug_sim3_hand_back: treat every k-th hypothesis of a call as not certified */
-};
+struct Sim3Buffers : BatchBuffers {};  /* scratch: Sim3Corr per correspondence, T21 per hypothesis; the hand-back counts hypotheses */
 
-void drfe_sim3_free(drfe_ctx* c)
-{
-    delete c->sim3;
-    c->sim3 = nullptr;
-}
+void drfe_sim3_free(drfe_ctx* c) { batch_free(c->sim3); }
 
 namespace {
 
@@ -153,8 +147,7 @@ int drfe_sim3_ransac_batch(drfe_ctx* c, const drfe_sim3_problems* p, drfe_sim3_o
     Plan P;
     const int rc = make_plan(p, o, P, c->err);
     if (rc) return rc;
-    Sim3Buffers* b = c->sim3;
-    if (!b) { b = new Sim3Buffers(); c->sim3 = b; }
+    Sim3Buffers* b = batch_buffers(c->sim3);
     P.count_call(b->stats, p->offsets);
     if (p->n == 0) return DRFE_OK;
     const int n = p->n, M = p->offsets[n], H = P.nHyp;
@@ -174,10 +167,8 @@ int drfe_sim3_ransac_batch(drfe_ctx* c, const drfe_sim3_problems* p, drfe_sim3_o
     const auto sMask = out.add<uint64_t>((size_t)P.maskWords);
     const auto sCorr = scr.add<Sim3Corr>(nM);
     const auto sT21 = scr.add<float>(nH * 12);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, b->io.grow(in.bytes(), out.bytes()));
-    HIPCHK(c, b->scratch.grow(scr.bytes()));
+    hipStream_t st;
+    if (const int e = batch_begin(c, b, stream, in.bytes(), out.bytes(), scr.bytes(), &st)) return e;
     char* h = b->io.hin;
     Sim3Solver* sol = sSolver.at(h);
     int32_t* corrSolver = sCorrSolver.at(h);
@@ -201,7 +192,7 @@ int drfe_sim3_ransac_batch(drfe_ctx* c, const drfe_sim3_problems* p, drfe_sim3_o
     const char* d = b->io.din;
     char* dO = b->io.dout;
     char* dS = b->scratch;
-    HIPCHK(c, hipMemcpyAsync(b->io.din, h, in.bytes(), hipMemcpyHostToDevice, st));
+    if (const int e = batch_upload(c, b, in.bytes(), 0, st)) return e;    /* this entry does not clear its out block */
     Sim3Launch L{};
     L.solver = sSolver.at(d);
     L.nSolvers = n; L.nCorr = M; L.nHyp = H; L.maxHyp = P.maxHyp;
@@ -214,7 +205,7 @@ int drfe_sim3_ransac_batch(drfe_ctx* c, const drfe_sim3_problems* p, drfe_sim3_o
     L.R12 = sR.at(dO); L.t12 = sT.at(dO); L.s12 = sS.at(dO); L.T12 = sT12.at(dO);
     L.inliers = sInl.at(dO); L.best = sBest.at(dO); L.returns = sRet.at(dO); L.uncertified = sUnc.at(dO);
     L.mask = sMask.at(dO);
-    if (const int e = ransac_finish(c, "sim3", drfe_launch_sim3(L, st), b->io, out.bytes(), st)) return e;
+    if (const int e = batch_finish(c, "sim3", drfe_launch_sim3(L, st), b, out.bytes(), st)) return e;
     const char* ho = b->io.hout;
     const uint8_t* unc = sUnc.at(ho);
     std::vector<Sim3Corr> corr;
@@ -244,12 +235,7 @@ int drfe_sim3_ransac_batch(drfe_ctx* c, const drfe_sim3_problems* p, drfe_sim3_o
     return DRFE_OK;
 }
 
-int drfe_sim3_stats(drfe_ctx* c, int64_t* stats)
-{
-    if (!c || !stats) return DRFE_ERR_INVALID;
-    ransac_stats(c->sim3, stats);
-    return DRFE_OK;
-}
+int drfe_sim3_stats(drfe_ctx* c, int64_t* stats) { return batch_stats(c, &drfe_ctx::sim3, stats); }
 
 int drfe_debug_sim3_atan2(const double* y, const double* x, int n, double* out, int32_t* ok)
 {
@@ -258,13 +244,7 @@ int drfe_debug_sim3_atan2(const double* y, const double* x, int n, double* out, 
     return DRFE_OK;
 }
 
-int drfe_debug_sim3_hand_back(drfe_ctx* c, int every)
-{
-    if (!c || every < 0) return DRFE_ERR_INVALID;
-    if (!c->sim3) c->sim3 = new Sim3Buffers();
-    c->sim3->handBackEvery = every;
-    return DRFE_OK;
-}
+int drfe_debug_sim3_hand_back(drfe_ctx* c, int every) { return batch_hand_back(c, &drfe_ctx::sim3, every); }
 
 int drfe_debug_sim3_horn(const float* P1, const float* P2, int n, int fix_scale, int libm, float* out, int32_t* ok)
 {

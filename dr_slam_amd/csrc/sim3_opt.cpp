@@ -4,24 +4,16 @@
  * batch entry keeps on the host, and the hand-back of a problem whose sin / cos or cube the device could not certify.  DESIGN.md
  * section 22. */
 #include "sim3_opt_internal.h"
+#include "batch_entry.h"
 #include "stage_layout.h"
 #include "../../include/drfe_debug.h"
 
 #include <cstring>
 #include <vector>
 
-struct Sim3OptBuffers {
-    StagePair io;                      /* staging: one copy each way */
-    DevBuf<char> scratch;              /* _error of every edge */
-    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int handBackEvery = 0;             /* drfe_debug_sim3_opt_hand_back: treat every k-th problem of a call as not certified */
-};
+struct Sim3OptBuffers : BatchBuffers {};   /* scratch: _error of every edge; the hand-back counts problems */
 
-void drfe_sim3_opt_free(drfe_ctx* c)
-{
-    delete c->sim3_opt;
-    c->sim3_opt = nullptr;
-}
+void drfe_sim3_opt_free(drfe_ctx* c) { batch_free(c->sim3_opt); }
 
 namespace {
 
@@ -122,17 +114,17 @@ void host_problem(const SoProbRec& P, const SoMatch* M, uint8_t* flag, SoProbOut
     int nBad = 0, early = 0;
     for (int phase = 0; phase < 2; phase++) {
         const int iters = phase == 0 ? 5 : (nBad > 0 ? 10 : 5);
-        const int it0 = L.iterations, tr0 = L.trials;
-        L.lastRejected = 0;
+        const int it0 = L.lm.iterations, tr0 = L.lm.trials;
+        L.lm.lastRejected = 0;
         int nActive = 0;
         for (int m = 0; m < P.nMatches; m++) nActive += flag[m] ? 0 : 1;
         for (int i = 0; i < iters && nActive > 0; i++) {
             const double chi = host_errors(P, M, flag, L.S, err.data());
             SoSim3 pert[14], pinv[14];
-            for (int j = 0; j < 14; j++) so_perturbed(L.ctx, L.S, P.fixScale, j, pert[j], pinv[j]);
-            for (int r = 0; r < SO_H_TERMS; r++) L.H[r] = 0.0;
-            for (int r = 0; r < 7; r++) L.b[r] = 0.0;
-            const double scalar = po_numeric_scalar();
+            for (int j = 0; j < 14; j++) so_perturbed(L.lm.ctx, L.S, P.fixScale, j, pert[j], pinv[j]);
+            for (int r = 0; r < SO_H_TERMS; r++) L.lm.H[r] = 0.0;
+            for (int r = 0; r < 7; r++) L.lm.b[r] = 0.0;
+            const double scalar = lm_numeric_scalar();
             for (int m = 0; m < P.nMatches; m++) {
                 if (flag[m]) continue;
                 for (int kind = 0; kind < 2; kind++) {
@@ -144,22 +136,22 @@ void host_problem(const SoProbRec& P, const SoMatch* M, uint8_t* flag, SoProbOut
                         for (int r = 0; r < 2; r++) J[r][d] = scalar * (e1[r] - e2[r]);
                     }
                     so_edge_terms(kind ? M[m].info2 : M[m].info1, P.cam.delta, J, err.data() + 4 * (size_t)m + 2 * kind, term);
-                    for (int r = 0; r < SO_H_TERMS; r++) L.H[r] += term[r];
-                    for (int r = 0; r < 7; r++) L.b[r] += term[SO_H_TERMS + r];
+                    for (int r = 0; r < SO_H_TERMS; r++) L.lm.H[r] += term[r];
+                    for (int r = 0; r < 7; r++) L.lm.b[r] += term[SO_H_TERMS + r];
                 }
             }
-            so_lm_begin(L, i, chi);
+            lm_begin(L.lm, i, chi);
             int more;
             do {
-                so_lm_step(L);
+                lm_step(L);
                 const double tempChi = host_errors(P, M, flag, L.S, err.data());
-                more = so_lm_judge(L, tempChi);
+                more = lm_judge(L, tempChi);
             } while (more);
-            if (!so_lm_end(L)) break;
+            if (!lm_end(L.lm)) break;
         }
-        O.iterations[phase] = L.iterations - it0;
-        O.trials[phase] = L.trials - tr0;
-        if (L.lastRejected) O.diag[SO_DIAG_LAST_REJECTED]++;
+        O.iterations[phase] = L.lm.iterations - it0;
+        O.trials[phase] = L.lm.trials - tr0;
+        if (L.lm.lastRejected) O.diag[SO_DIAG_LAST_REJECTED]++;
         /* no computeError() precedes the classification: _error is what the last trial left, also a rejected one */
         SoSim3 Sinv;
         so_inverse(L.S, Sinv);
@@ -167,7 +159,7 @@ void host_problem(const SoProbRec& P, const SoMatch* M, uint8_t* flag, SoProbOut
         for (int m = 0; m < P.nMatches; m++) {
             if (flag[m]) continue;
             const int out = so_outlier(M[m], P.cam.th2, err.data() + 4 * (size_t)m);
-            if (L.lastRejected) {
+            if (L.lm.lastRejected) {
                 double e[4];
                 so_edge_error(M[m], P.cam, 0, L.S, Sinv, e);
                 so_edge_error(M[m], P.cam, 1, L.S, Sinv, e + 2);
@@ -184,10 +176,10 @@ void host_problem(const SoProbRec& P, const SoMatch* M, uint8_t* flag, SoProbOut
         }
     }
     O.nBad = nBad;
-    O.diag[SO_DIAG_REJECTED] = L.rejected;
-    O.diag[SO_DIAG_NBAD_STOPS] = L.nBadStops;
-    O.diag[SO_DIAG_SMALL_THETA] = L.smallTheta;
-    O.diag[SO_DIAG_BIG_THETA] = L.bigTheta;
+    O.diag[SO_DIAG_REJECTED] = L.lm.rejected;
+    O.diag[SO_DIAG_NBAD_STOPS] = L.lm.nBadStops;
+    O.diag[SO_DIAG_SMALL_THETA] = L.lm.smallTheta;
+    O.diag[SO_DIAG_BIG_THETA] = L.lm.bigTheta;
     O.diag[SO_DIAG_EARLY_RETURN] = early;
     so_finish(P, early ? S0 : L.S, O);
 }
@@ -235,8 +227,7 @@ int drfe_sim3_opt_batch(drfe_ctx* c, const drfe_sim3_opt_problems* p, drfe_sim3_
     Plan P;
     const int rc = make_plan(p, o, P, c->err);
     if (rc) return rc;
-    Sim3OptBuffers* b = c->sim3_opt;
-    if (!b) { b = new Sim3OptBuffers(); c->sim3_opt = b; }
+    Sim3OptBuffers* b = batch_buffers(c->sim3_opt);
     b->stats[0]++;
     if (p->n == 0) return DRFE_OK;
     const int n = p->n;
@@ -247,18 +238,15 @@ int drfe_sim3_opt_batch(drfe_ctx* c, const drfe_sim3_opt_problems* p, drfe_sim3_
     const auto sOut = out.add<SoProbOut>((size_t)n);
     const auto sFlag = out.add<uint8_t>(nM);
     const auto sErr = scr.add<double>(4 * nM);
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, b->io.grow(in.bytes(), out.bytes()));
-    HIPCHK(c, b->scratch.grow(scr.bytes()));
+    hipStream_t st;
+    if (const int e = batch_begin(c, b, stream, in.bytes(), out.bytes(), scr.bytes(), &st)) return e;
     char* h = b->io.hin;
     sProb.put(h, P.prob.data());
     sMatch.put(h, P.match.data());
     const char* d = b->io.din;
     char* dO = b->io.dout;
     char* dS = b->scratch;
-    HIPCHK(c, hipMemcpyAsync(b->io.din, h, in.bytes(), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(dO, 0, out.bytes(), st));
+    if (const int e = batch_upload(c, b, in.bytes(), out.bytes(), st)) return e;
     SoLaunch L{};
     L.nProblems = n;
     L.prob = sProb.at(d);
@@ -266,9 +254,7 @@ int drfe_sim3_opt_batch(drfe_ctx* c, const drfe_sim3_opt_problems* p, drfe_sim3_
     L.err = sErr.at(dS);
     L.flag = sFlag.at(dO);
     L.out = sOut.at(dO);
-    hipError_t e = drfe_launch_sim3_opt(L, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(b->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) { c->err = std::string("sim3_opt batch: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
+    if (const int e = batch_copy_back(c, "sim3_opt", drfe_launch_sim3_opt(L, st), b, out.bytes(), st)) return e;
     /* the free-scale problems need exp: the host core runs them while the launch is in flight (their workgroups return at once) */
     std::vector<uint8_t> flag;
     for (int f = 0; f < n; f++) {
@@ -309,21 +295,9 @@ int drfe_sim3_opt_batch(drfe_ctx* c, const drfe_sim3_opt_problems* p, drfe_sim3_
     return DRFE_OK;
 }
 
-int drfe_sim3_opt_stats(drfe_ctx* c, int64_t* stats)
-{
-    if (!c || !stats) return DRFE_ERR_INVALID;
-    if (c->sim3_opt) std::memcpy(stats, c->sim3_opt->stats, sizeof(c->sim3_opt->stats));
-    else std::memset(stats, 0, 8 * sizeof(int64_t));
-    return DRFE_OK;
-}
+int drfe_sim3_opt_stats(drfe_ctx* c, int64_t* stats) { return batch_stats(c, &drfe_ctx::sim3_opt, stats); }
 
-int drfe_debug_sim3_opt_hand_back(drfe_ctx* c, int every)
-{
-    if (!c || every < 0) return DRFE_ERR_INVALID;
-    if (!c->sim3_opt) c->sim3_opt = new Sim3OptBuffers();
-    c->sim3_opt->handBackEvery = every;
-    return DRFE_OK;
-}
+int drfe_debug_sim3_opt_hand_back(drfe_ctx* c, int every) { return batch_hand_back(c, &drfe_ctx::sim3_opt, every); }
 
 int drfe_debug_sim3_opt_ldlt(const double* A, const double* b, double* x, int32_t* positive)
 {
@@ -331,7 +305,7 @@ int drfe_debug_sim3_opt_ldlt(const double* A, const double* b, double* x, int32_
     double M[7][7];
     for (int i = 0; i < 7; i++)
         for (int j = 0; j < 7; j++) M[i][j] = A[7 * i + j];
-    *positive = po_ldlt_solve_n<7>(M, b, x);
+    *positive = lm_ldlt_solve<7>(M, b, x);
     return DRFE_OK;
 }
 
@@ -340,12 +314,12 @@ int drfe_debug_sim3_opt_step(const double* S12, const double* x, int fix_scale, 
     if (!S12 || !x || !S12_out || !scale) return DRFE_ERR_INVALID;
     SoLM L;
     so_lm_init(L, S12, fix_scale, 1);
-    for (int k = 0; k < 7; k++) { L.x[k] = x[k]; L.b[k] = x[7 + k]; }
-    L.lambda = x[14];
-    /* the core's own update and computeScale, in the order so_lm_step and so_lm_judge run them, or the other way round */
-    const double before = so_lm_scale(L);
+    for (int k = 0; k < 7; k++) { L.lm.x[k] = x[k]; L.lm.b[k] = x[7 + k]; }
+    L.lm.lambda = x[14];
+    /* the core's own update and computeScale, in the order lm_step and lm_judge run them, or the other way round */
+    const double before = lm_scale(L.lm);
     so_lm_update(L);
-    *scale = read_before ? before : so_lm_scale(L);
+    *scale = read_before ? before : lm_scale(L.lm);
     for (int k = 0; k < 4; k++) S12_out[k] = L.S.q[k];
     for (int k = 0; k < 3; k++) S12_out[4 + k] = L.S.t[k];
     S12_out[7] = L.S.s;

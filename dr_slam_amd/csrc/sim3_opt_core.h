@@ -1,12 +1,12 @@
 /* sim3_opt_core.h — the arithmetic of Optimizer::OptimizeSim3 (reference src/Optimizer.cc:3982-4177) and of what g2o runs under
  * it, restated statement by statement: g2o::Sim3 (types/sim3.h: the exponential with its four branches, map, inverse, operator*),
  * the two projection edges of types_seven_dof_expmap.h, BaseBinaryEdge's numeric Jacobian and quadratic form for the one free
- * vertex, Huber's kernel, the 7x7 normal equations, Eigen's LDLT, the Levenberg step control and VertexSim3Expmap::oplusImpl.
+ * vertex, Huber's kernel, the 7x7 normal equations and VertexSim3Expmap::oplusImpl; the LDLT and the step control are lm_core.h's.
  * Shared by the host entry (sim3_opt.cpp) and the device kernel (sim3_opt_kernels.hip) so that both produce the same bits: plain
  * IEEE add / mul / div / sqrt in double, compiled with -ffp-contract=off on both sides; sin and cos through cr_sincos.h.  exp has
  * no certified form here: a problem with a free scale runs on the host with the host's libm, also inside the device entry.
  * DESIGN.md section 22 states the evaluation order of every expression; where Eigen leaves an association open it is read left
- * to right, as in section 20, whose solver, kernel and quaternion pieces (pose_opt_core.h) this header reuses.
+ * to right, as in section 20, whose kernel and quaternion pieces (pose_opt_core.h) this header reuses.
  *
  * Parity with a g2o / Eigen 3.3.7 build is not pinned: Eigen is not available to the tests.
  *
@@ -85,7 +85,7 @@ DRFE_HD void so_mul(const SoSim3& A, const SoSim3& B, SoSim3& R)
 
 /* std::exp(sigma): exp(0) is 1; anything else is the host's libm (no certified exp exists here yet, so a last-place difference
  * from a correctly rounded exp is possible), or ctx.fail on the device */
-DRFE_HD double so_exp(PoCtx& ctx, double sigma)
+DRFE_HD double so_exp(LmCtx& ctx, double sigma)
 {
     if (sigma == 0.0) return 1.0;
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -97,7 +97,7 @@ DRFE_HD double so_exp(PoCtx& ctx, double sigma)
 
 /* Sim3(const Vector7d& update) (types/sim3.h:70-142): omega, upsilon, sigma.  Returns theta < eps.  R is ((I + a Omega) + b
  * Omega2) element by element, W = ((A Omega) + (B Omega2)) + C I; Quaterniond(R) is not normalised. */
-DRFE_HD int so_exp_map(PoCtx& ctx, const double u[7], SoSim3& S)
+DRFE_HD int so_exp_map(LmCtx& ctx, const double u[7], SoSim3& S)
 {
     const double o0 = u[0], o1 = u[1], o2 = u[2];
     const double sigma = u[6];
@@ -159,7 +159,7 @@ DRFE_HD int so_exp_map(PoCtx& ctx, const double u[7], SoSim3& S)
 
 /* VertexSim3Expmap::oplusImpl: `update[6] = 0` through the caller's array when the scale is fixed, then estimate = Sim3(update)
  * * estimate.  Returns theta < eps. */
-DRFE_HD int so_oplus(PoCtx& ctx, SoSim3& S, double u[7], int fixScale)
+DRFE_HD int so_oplus(LmCtx& ctx, SoSim3& S, double u[7], int fixScale)
 {
     if (fixScale) u[6] = 0.0;
     SoSim3 E;
@@ -171,7 +171,7 @@ DRFE_HD int so_oplus(PoCtx& ctx, SoSim3& S, double u[7], int fixScale)
 /* the perturbed estimates of BaseBinaryEdge::linearizeOplus for vertex 1 (core/base_binary_edge.hpp:176-198): perturbation
  * j = 2 d + side is oplus(+-1e-9 e_d) of the estimate (side 0 the plus step), P[j] what EdgeSim3ProjectXYZ maps with and Pinv[j]
  * its inverse(), which EdgeInverseSim3ProjectXYZ maps with.  The estimate is pushed and popped around every step. */
-DRFE_HD void so_perturbed(PoCtx& ctx, const SoSim3& S, int fixScale, int j, SoSim3& P, SoSim3& Pinv)
+DRFE_HD void so_perturbed(LmCtx& ctx, const SoSim3& S, int fixScale, int j, SoSim3& P, SoSim3& Pinv)
 {
     double u[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     u[j >> 1] = (j & 1) ? -1e-9 : 1e-9;
@@ -240,18 +240,12 @@ DRFE_HD void so_edge_terms(double info, double delta, const double J[2][7], cons
     }
 }
 
-/* ---- the vertex and the step control: one lane ---- */
+/* ---- the vertex under lm_core.h's step control: one lane ---- */
 
 struct SoLM {
     SoSim3 S, saved;               /* the estimate and what push() saved */
-    double H[SO_H_TERMS], b[7];    /* the system of the current iteration */
-    double x[7];                   /* the solver's x: kept over a failed solve and over the two phases, zero at the start of a call */
-    double lambda, ni, currentChi, iniChi, rho;
-    int32_t nBad, qmax;
-    int32_t solved;                /* the last trial's LDLT was isPositive() and wrote x (Levenberg's ok2) */
     int32_t fixScale;
-    PoCtx ctx;
-    int32_t iterations, trials, rejected, lastRejected, nBadStops, smallTheta, bigTheta;   /* diagnostics of the call */
+    LmControl<7> lm;               /* x is kept over the two phases */
 };
 
 DRFE_HD void so_lm_init(SoLM& L, const double S12[8], int fixScale, int libm)
@@ -260,101 +254,28 @@ DRFE_HD void so_lm_init(SoLM& L, const double S12[8], int fixScale, int libm)
     for (int k = 0; k < 3; k++) L.S.t[k] = S12[4 + k];
     L.S.s = S12[7];
     L.saved = L.S;
-    for (int k = 0; k < 7; k++) L.x[k] = 0.0;
-    L.ctx.fail = 0; L.ctx.libm = libm;
     L.fixScale = fixScale;
-    L.iterations = 0; L.trials = 0; L.rejected = 0; L.lastRejected = 0; L.nBadStops = 0; L.smallTheta = 0; L.bigTheta = 0;
-    L.lambda = -1.0; L.ni = 2.0; L.nBad = 0; L.qmax = 0; L.solved = 0; L.rho = 0.0; L.currentChi = 0.0; L.iniChi = 0.0;
-}
-
-/* OptimizationAlgorithmLevenberg::solve cut at its calls into the graph, as po_lm_* (pose_opt_core.h) for seven dimensions:
- *   so_lm_begin(L, iteration, chi)   after computeActiveErrors / activeRobustChi2 / buildSystem (L.H, L.b filled)
- *   so_lm_step(L)                    push, setLambda, solve, update, restoreDiagonal; then the caller recomputes the errors
- *   so_lm_judge(L, tempChi)          the rho test; returns 1 when the do-while goes on
- *   so_lm_end(L)                     returns 1 for OK, 0 for Terminate */
-DRFE_HD void so_lm_begin(SoLM& L, int iteration, double chi)
-{
-    L.currentChi = chi;
-    L.iniChi = chi;
-    if (iteration == 0) {
-        double maxDiagonal = 0.0;
-        for (int j = 0; j < 7; j++) {
-            const double a = fabs(L.H[j * (j + 1) / 2 + j]);
-            maxDiagonal = a < maxDiagonal ? maxDiagonal : a;
-        }
-        L.lambda = 1e-5 * maxDiagonal;
-        L.ni = 2.0;
-        L.nBad = 0;
-    }
-    L.rho = 0.0;
-    L.qmax = 0;
-    L.iterations++;
+    lm_init(L.lm, libm);
 }
 
 /* update(): oplusImpl zeroes x[6] in the solver's own array when the scale is fixed */
-DRFE_HD void so_lm_update(SoLM& L)
-{
-    if (so_oplus(L.ctx, L.S, L.x, L.fixScale)) L.smallTheta++;
-    else L.bigTheta++;
-}
+DRFE_HD void so_lm_update(SoLM& L) { lm_count_theta(L.lm, so_oplus(L.lm.ctx, L.S, L.lm.x, L.fixScale)); }
 
-/* computeScale: reads the solver's x, after update() has run */
-DRFE_HD double so_lm_scale(const SoLM& L)
-{
-    double scale = 0.0;
-    for (int j = 0; j < 7; j++) scale += L.x[j] * (L.lambda * L.x[j] + L.b[j]);
-    scale += 1e-3;
-    return scale;
-}
-
-DRFE_HD void so_lm_step(SoLM& L)
+/* push, solve, update: the update before lm_judge's computeScale reads x */
+DRFE_HD void lm_step(SoLM& L)
 {
     L.saved = L.S;
-    double A[7][7];
-    for (int i = 0; i < 7; i++)
-        for (int j = 0; j <= i; j++) {
-            const double h = L.H[i * (i + 1) / 2 + j];
-            A[i][j] = i == j ? h + L.lambda : h;
-            A[j][i] = A[i][j];
-        }
-    L.solved = po_ldlt_solve_n<7>(A, L.b, L.x);
-    so_lm_update(L);                               /* before so_lm_judge's computeScale reads x */
-    L.trials++;
+    lm_solve(L.lm);
+    so_lm_update(L);
 }
 
-DRFE_HD int so_lm_judge(SoLM& L, double tempChi)
+/* the rho test, pop after a rejected trial */
+DRFE_HD int lm_judge(SoLM& L, double tempChi)
 {
-    if (!L.solved) tempChi = DBL_MAX;
-    double rho = L.currentChi - tempChi;
-    rho /= so_lm_scale(L);
-    if (rho > 0.0 && isfinite(tempChi)) {
-        double alpha = 1.0 - po_cube(L.ctx, 2.0 * rho - 1.0);
-        const double up = 2.0 / 3.0, lo = 1.0 / 3.0;
-        alpha = up < alpha ? up : alpha;
-        const double scaleFactor = lo < alpha ? alpha : lo;
-        L.lambda *= scaleFactor;
-        L.ni = 2.0;
-        L.currentChi = tempChi;
-        L.lastRejected = 0;
-    } else {
-        L.lambda *= L.ni;
-        L.ni *= 2.0;
-        L.S = L.saved;
-        L.rejected++;
-        L.lastRejected = 1;
-    }
-    L.rho = rho;
-    L.qmax++;
-    return rho < 0.0 && L.qmax < 10;
-}
-
-DRFE_HD int so_lm_end(SoLM& L)
-{
-    if (L.qmax == 10 || L.rho == 0.0) return 0;
-    if ((L.iniChi - L.currentChi) * 1e3 < L.iniChi) L.nBad++;
-    else L.nBad = 0;
-    if (L.nBad >= 3) { L.nBadStops++; return 0; }
-    return 1;
+    int accepted;
+    const int more = lm_judge(L.lm, tempChi, accepted);
+    if (!accepted) L.S = L.saved;
+    return more;
 }
 
 /* `e12->chi2() > th2 || e21->chi2() > th2`: doubles against the widened float; a NaN is no outlier.  e = e12's error, then e21's */

@@ -15,12 +15,9 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "sim3_opt_internal.h"
+#include "lm_device.h"
 
 namespace {
-
-/* a value every lane of the workgroup holds alike, as a scalar: the branches on it are scalar branches, so that no wavefront
- * walks a barrier of a loop it has left with its lanes masked off */
-__device__ inline int so_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
 struct SoShared {
     double term[SO_ROWS * SO_TERM_STRIDE];   /* rows 0..34 the terms of H and b, row 35 the chi2 terms */
@@ -33,17 +30,18 @@ struct SoShared {
     int32_t fail;                  /* a lane could not certify a transcendental */
 };
 
-/* computeActiveErrors and activeRobustChi2; with `build` also linearizeOplus and constructQuadraticForm into L.H / L.b.
- * Returns the robust chi2 in every lane.  Every lane of the workgroup calls it. */
-__device__ double so_pass(SoShared& sh, const SoProbRec& P, const SoMatch* match, double* err, const uint8_t* flag, bool build)
+/* computeActiveErrors and activeRobustChi2; with `build` also linearizeOplus and constructQuadraticForm into L.lm.H / L.lm.b.
+ * Returns the robust chi2 in every lane.  Every lane of the workgroup calls it.  Kept out of line, as the compiler had it while the
+ * trial loop called it from two places: inlined, the kernel takes 107 AGPRs instead of the 32 of DESIGN.md section 22. */
+__device__ __noinline__ double so_pass(SoShared& sh, const SoProbRec& P, const SoMatch* match, double* err, const uint8_t* flag, bool build)
 {
     const int tid = threadIdx.x;
-    PoCtx ctx = {0, 0};
+    LmCtx ctx = {0, 0};
     if (tid == 0) so_inverse(sh.L.S, sh.Sinv);
     if (build && tid < 14) so_perturbed(ctx, sh.L.S, P.fixScale, tid, sh.pert[tid], sh.pinv[tid]);
     __syncthreads();
     const SoSim3 S = sh.L.S, Sinv = sh.Sinv;
-    const int nEdges = 2 * so_uniform(P.nMatches);
+    const int nEdges = 2 * lm_uniform(P.nMatches);
     double acc = 0.0;
     for (int base = 0; base < nEdges; base += SO_THREADS) {
         const int k = base + tid;
@@ -60,7 +58,7 @@ __device__ double so_pass(SoShared& sh, const SoProbRec& P, const SoMatch* match
             c = so_chi_term(info, P.cam.delta, e);
             if (build) {
                 double J[2][7], term[SO_TERMS];
-                const double scalar = po_numeric_scalar();
+                const double scalar = lm_numeric_scalar();
                 for (int d = 0; d < 7; d++) {
                     double e1[2], e2[2];
                     so_edge_error(M, P.cam, kind, sh.pert[2 * d], sh.pinv[2 * d], e1);
@@ -84,8 +82,8 @@ __device__ double so_pass(SoShared& sh, const SoProbRec& P, const SoMatch* match
     }
     if (ctx.fail) sh.fail = 1;
     if (build) {
-        if (tid < SO_H_TERMS) sh.L.H[tid] = acc;
-        else if (tid < SO_TERMS) sh.L.b[tid - SO_H_TERMS] = acc;
+        if (tid < SO_H_TERMS) sh.L.lm.H[tid] = acc;
+        else if (tid < SO_TERMS) sh.L.lm.b[tid - SO_H_TERMS] = acc;
     }
     if (tid == SO_TERMS) sh.chi = acc;
     __syncthreads();
@@ -99,59 +97,36 @@ __global__ __launch_bounds__(SO_THREADS) void k_sim3_opt(const SoLaunch L)
     __shared__ SoShared sh;
     const int tid = threadIdx.x;
     const SoProbRec& P = L.prob[blockIdx.x];
-    if (!so_uniform(P.fixScale)) return;                            /* uniform: the host core runs the problem */
+    if (!lm_uniform(P.fixScale)) return;                            /* uniform: the host core runs the problem */
     SoProbOut& O = L.out[blockIdx.x];
     const SoMatch* match = L.match + P.match0;
     double* err = L.err + 4 * (size_t)P.match0;
     uint8_t* flag = L.flag + P.match0;
-    const int nM = so_uniform(P.nMatches);
+    const int nM = lm_uniform(P.nMatches);
     int nBad = 0, early = 0, ret = 0, lastRejectedPhases = 0, stale = 0;
     int iterations[2] = {0, 0}, trials[2] = {0, 0};
     if (tid == 0) {
         so_lm_init(sh.L, P.S12, 1, 0);
         sh.fail = 0;
-        sh.ctl = 0;
     }
     for (int phase = 0; phase < 2; phase++) {
         const int iters = phase == 0 ? 5 : (nBad > 0 ? 10 : 5);
         if (tid == 0) {
-            sh.L.lastRejected = 0;
+            sh.L.lm.lastRejected = 0;
             sh.count = 0;
             sh.count2 = 0;
         }
         __syncthreads();
-        const int it0 = so_uniform(sh.L.iterations), tr0 = so_uniform(sh.L.trials);
+        const int it0 = lm_uniform(sh.L.lm.iterations), tr0 = lm_uniform(sh.L.lm.trials);
         {
             int mine = 0;
             for (int m = tid; m < nM; m += SO_THREADS) mine += flag[m] ? 0 : 1;
             if (mine) atomicAdd(&sh.count, mine);
         }
         __syncthreads();
-        const int nActive = so_uniform(sh.count);
+        const int nActive = lm_uniform(sh.count);
         __syncthreads();
-        for (int i = 0; i < iters && nActive > 0; i++) {
-            const double chi = so_pass(sh, P, match, err, flag, true);
-            if (tid == 0) so_lm_begin(sh.L, i, chi);
-            /* this barrier keeps lane 0's block above apart from the trial loop: without it the compiler threads the block into
-             * the loop's first trip, the other lanes walk a whole pass and the loop's barriers with lane 0 masked off, read the
-             * control word of the iteration before and may leave the loop a trip early */
-            __syncthreads();
-            int more;
-            do {
-                if (tid == 0) so_lm_step(sh.L);
-                __syncthreads();
-                const double tempChi = so_pass(sh, P, match, err, flag, false);
-                if (tid == 0) sh.ctl = so_lm_judge(sh.L, tempChi);
-                __syncthreads();
-                more = so_uniform(sh.ctl);
-                __syncthreads();
-            } while (more);
-            if (tid == 0) sh.ctl = so_lm_end(sh.L);
-            __syncthreads();
-            const int ok = so_uniform(sh.ctl);
-            __syncthreads();
-            if (!ok) break;
-        }
+        if (nActive > 0) lm_iterations(sh.L, sh.ctl, iters, [&](bool build) { return so_pass(sh, P, match, err, flag, build); });
         /* the classification on _error as the last trial left it; after a rejected one also on the errors at the kept estimate,
          * to count what the stale ones decided differently */
         if (tid == 0) {
@@ -159,9 +134,9 @@ __global__ __launch_bounds__(SO_THREADS) void k_sim3_opt(const SoLaunch L)
             sh.count = 0;
         }
         __syncthreads();
-        const int rejected = so_uniform(sh.L.lastRejected);
-        iterations[phase] = so_uniform(sh.L.iterations) - it0;
-        trials[phase] = so_uniform(sh.L.trials) - tr0;
+        const int rejected = lm_uniform(sh.L.lm.lastRejected);
+        iterations[phase] = lm_uniform(sh.L.lm.iterations) - it0;
+        trials[phase] = lm_uniform(sh.L.lm.trials) - tr0;
         lastRejectedPhases += rejected ? 1 : 0;
         {
             int mine = 0, mine2 = 0;
@@ -183,8 +158,8 @@ __global__ __launch_bounds__(SO_THREADS) void k_sim3_opt(const SoLaunch L)
             if (mine2) atomicAdd(&sh.count2, mine2);
         }
         __syncthreads();
-        const int count = so_uniform(sh.count);
-        stale += so_uniform(sh.count2);
+        const int count = lm_uniform(sh.count);
+        stale += lm_uniform(sh.count2);
         __syncthreads();
         if (phase == 0) {
             nBad = count;
@@ -199,14 +174,14 @@ __global__ __launch_bounds__(SO_THREADS) void k_sim3_opt(const SoLaunch L)
         R.nBad = nBad;
         for (int k = 0; k < 2; k++) { R.iterations[k] = iterations[k]; R.trials[k] = trials[k]; }
         for (int k = 0; k < SO_DIAG_N; k++) R.diag[k] = 0;
-        R.diag[SO_DIAG_REJECTED] = sh.L.rejected;
+        R.diag[SO_DIAG_REJECTED] = sh.L.lm.rejected;
         R.diag[SO_DIAG_LAST_REJECTED] = lastRejectedPhases;
-        R.diag[SO_DIAG_NBAD_STOPS] = sh.L.nBadStops;
-        R.diag[SO_DIAG_SMALL_THETA] = sh.L.smallTheta;
-        R.diag[SO_DIAG_BIG_THETA] = sh.L.bigTheta;
+        R.diag[SO_DIAG_NBAD_STOPS] = sh.L.lm.nBadStops;
+        R.diag[SO_DIAG_SMALL_THETA] = sh.L.lm.smallTheta;
+        R.diag[SO_DIAG_BIG_THETA] = sh.L.lm.bigTheta;
         R.diag[SO_DIAG_EARLY_RETURN] = early;
         R.diag[SO_DIAG_STALE_DECIDED] = stale;
-        R.handBack = (sh.L.ctx.fail || sh.fail) ? 1 : 0;
+        R.handBack = (sh.L.lm.ctx.fail || sh.fail) ? 1 : 0;
         R.pad = 0;
         SoSim3 S = sh.L.S;
         if (early) {

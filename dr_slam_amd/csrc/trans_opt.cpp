@@ -3,36 +3,18 @@
  * over the caller's arrays as they are; here are the argument checks and caps, the frame's rounds on the host in the full 6x6
  * form, and the hand-back of a frame the device could not certify or that met a term that is not finite.  DESIGN.md section 21. */
 #include "trans_opt_internal.h"
+#include "batch_entry.h"
 #include "stage_layout.h"
 #include "../../include/drfe_debug.h"
 
 #include <cstring>
 #include <vector>
 
-struct TransOptBuffers {
-    StagePair io;                      /* staging: one copy each way */
-    DevBuf<char> scratch;              /* _error of every edge */
-    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int handBackEvery = 0;             /* drfe_debug_trans_opt_hand_back: treat every k-th frame of a call as handed back */
-};
+struct TransOptBuffers : BatchBuffers {};  /* scratch: _error of every edge; the hand-back counts frames */
 
-void drfe_trans_opt_free(drfe_ctx* c)
-{
-    delete c->trans_opt;
-    c->trans_opt = nullptr;
-}
+void drfe_trans_opt_free(drfe_ctx* c) { batch_free(c->trans_opt); }
 
 namespace {
-
-bool offsets_ok(const int32_t* off, int n, int cap, const char* what, const char* capName, std::string& err)
-{
-    if (off[0] != 0) { err = std::string("trans_opt: ") + what + "_offsets[0] is not 0"; return false; }
-    for (int f = 0; f < n; f++) {
-        if (off[f + 1] < off[f]) { err = std::string("trans_opt: decreasing ") + what + "_offsets"; return false; }
-        if (off[f + 1] - off[f] > cap) { err = std::string("trans_opt: more than ") + capName + " in a frame"; return false; }
-    }
-    return true;
-}
 
 /* all-or-nothing validation of a call, then its view over the caller's arrays */
 int check_call(const drfe_pose_opt_problems* p, const drfe_pose_opt_out* o, ToView& V, std::string& err)
@@ -44,9 +26,9 @@ int check_call(const drfe_pose_opt_problems* p, const drfe_pose_opt_out* o, ToVi
     if (n == 0) return DRFE_OK;
     if (!p->Tcw || !p->K || !p->bf || !p->b_struct || !p->point_offsets || !p->line_offsets || !p->plane_offsets) return DRFE_ERR_INVALID;
     if (!o->Tcw || !o->returns || !o->rounds || !o->iterations || !o->trials) return DRFE_ERR_INVALID;
-    if (!offsets_ok(p->point_offsets, n, DRFE_POSE_OPT_MAX_POINTS, "point", "DRFE_POSE_OPT_MAX_POINTS points", err) ||
-        !offsets_ok(p->line_offsets, n, DRFE_POSE_OPT_MAX_LINES, "line", "DRFE_POSE_OPT_MAX_LINES lines", err) ||
-        !offsets_ok(p->plane_offsets, n, DRFE_POSE_OPT_MAX_PLANES, "plane", "DRFE_POSE_OPT_MAX_PLANES plane slots", err))
+    if (!batch_offsets_ok("trans_opt", p->point_offsets, n, DRFE_POSE_OPT_MAX_POINTS, "point", "DRFE_POSE_OPT_MAX_POINTS points", err) ||
+        !batch_offsets_ok("trans_opt", p->line_offsets, n, DRFE_POSE_OPT_MAX_LINES, "line", "DRFE_POSE_OPT_MAX_LINES lines", err) ||
+        !batch_offsets_ok("trans_opt", p->plane_offsets, n, DRFE_POSE_OPT_MAX_PLANES, "plane", "DRFE_POSE_OPT_MAX_PLANES plane slots", err))
         return DRFE_ERR_INVALID;
     const int nP = p->point_offsets[n], nL = p->line_offsets[n], nS = p->plane_offsets[n];
     if (nS > 0 && (!p->plane_meas || !p->plane_world || !p->plane_mask || !o->plane_outlier || !o->par_plane_outlier ||
@@ -86,7 +68,7 @@ struct HostFrame {
         double chi = 0.0;
         for (int k = 0; k < F.nEdges; k++) {
             if (flag(k)) continue;
-            to_edge_error(S.ctx, E[(size_t)k], F.cam, S.t, &err[3 * (size_t)k]);
+            to_edge_error(S.lm.ctx, E[(size_t)k], F.cam, S.t, &err[3 * (size_t)k]);
             chi += po_chi_term(E[(size_t)k], &err[3 * (size_t)k], robust);
         }
         return chi;
@@ -104,52 +86,52 @@ struct HostFrame {
         for (int k = 0; k < F.nEdges; k++) to_make_edge(V, F, planeAt, k, E[(size_t)k]);
         err.assign(3 * (size_t)F.nEdges, 0.0);
         PoLM S;
-        po_lm_init(S, 1);
+        lm_init(S.lm, 1);
         int robust = 1, nBad = 0;
         for (int it = 0; it < 4; it++) {
             mp_to_se3quat(Tcw, S.q, S.t);
-            S.lastRejected = 0;
+            S.lm.lastRejected = 0;
             int nActive = 0;
             for (int k = 0; k < F.nEdges; k++) nActive += flag(k) ? 0 : 1;
             if (nActive == 0) O.diag[PO_DIAG_EMPTY_ROUNDS]++;
             for (int i = 0; i < 10 && nActive > 0; i++) {
                 const double chi = errors(S, robust);
-                for (int r = 0; r < PO_H_TERMS; r++) S.H[r] = 0.0;
-                for (int r = 0; r < 6; r++) S.b[r] = 0.0;
+                for (int r = 0; r < PO_H_TERMS; r++) S.lm.H[r] = 0.0;
+                for (int r = 0; r < 6; r++) S.lm.b[r] = 0.0;
                 for (int k = 0; k < F.nEdges; k++) {
                     if (flag(k)) continue;
                     const PoEdge& Ek = E[(size_t)k];
                     double J3[3][3], J[3][6], term[PO_TERMS];
-                    if (po_is_plane(Ek.kind)) to_plane_jacobian(S.ctx, Ek, S.q, S.t, J3);
+                    if (po_is_plane(Ek.kind)) to_plane_jacobian(S.lm.ctx, Ek, S.q, S.t, J3);
                     else to_edge_jacobian(Ek, F.cam, S.t, J3);
                     to_full_jacobian(J3, J);
                     po_edge_terms(Ek, J, &err[3 * (size_t)k], robust, term);
-                    for (int r = 0; r < PO_H_TERMS; r++) S.H[r] += term[r];
-                    for (int r = 0; r < 6; r++) S.b[r] -= term[PO_H_TERMS + r];
+                    for (int r = 0; r < PO_H_TERMS; r++) S.lm.H[r] += term[r];
+                    for (int r = 0; r < 6; r++) S.lm.b[r] -= term[PO_H_TERMS + r];
                 }
-                po_lm_begin(S, i, chi);
+                lm_begin(S.lm, i, chi);
                 int more;
                 do {
-                    po_lm_step(S);
-                    more = po_lm_judge(S, errors(S, robust));
+                    lm_step(S);
+                    more = lm_judge(S, errors(S, robust));
                 } while (more);
-                if (!po_lm_end(S)) break;
+                if (!lm_end(S.lm)) break;
             }
             O.rounds++;
-            if (S.lastRejected) O.diag[PO_DIAG_LAST_REJECTED]++;
+            if (S.lm.lastRejected) O.diag[PO_DIAG_LAST_REJECTED]++;
             nBad = 0;                                            /* nLineBad is counted by the reference and not returned */
             const int line0 = F.nPoints, plane0 = F.nPoints + 2 * F.nLines;
             for (int k = 0; k < F.nEdges; k++) {
                 if (k >= line0 && k < plane0) continue;
-                if (flag(k)) to_edge_error(S.ctx, E[(size_t)k], F.cam, S.t, &err[3 * (size_t)k]);
+                if (flag(k)) to_edge_error(S.lm.ctx, E[(size_t)k], F.cam, S.t, &err[3 * (size_t)k]);
                 flag(k) = (uint8_t)po_outlier(E[(size_t)k], &err[3 * (size_t)k]);
                 nBad += flag(k);
             }
             for (int l = 0; l < F.nLines; l++) {
                 const int k = line0 + 2 * l;
                 if (flag(k)) {
-                    to_edge_error(S.ctx, E[(size_t)k], F.cam, S.t, &err[3 * (size_t)k]);
-                    to_edge_error(S.ctx, E[(size_t)k + 1], F.cam, S.t, &err[3 * (size_t)(k + 1)]);
+                    to_edge_error(S.lm.ctx, E[(size_t)k], F.cam, S.t, &err[3 * (size_t)k]);
+                    to_edge_error(S.lm.ctx, E[(size_t)k + 1], F.cam, S.t, &err[3 * (size_t)(k + 1)]);
                 }
                 flag(k) = (uint8_t)(po_outlier(E[(size_t)k], &err[3 * (size_t)k]) || po_outlier(E[(size_t)k + 1], &err[3 * (size_t)(k + 1)]));
             }
@@ -158,12 +140,12 @@ struct HostFrame {
         }
         po_pose_out(S.q, S.t, O.Tcw);
         O.ret = nInitial - nBad;
-        O.iterations = S.iterations;
-        O.trials = S.trials;
-        O.diag[PO_DIAG_REJECTED] = S.rejected;
-        O.diag[PO_DIAG_NBAD_STOPS] = S.nBadStops;
-        O.diag[PO_DIAG_SMALL_THETA] = S.smallTheta;
-        O.diag[PO_DIAG_BIG_THETA] = S.bigTheta;
+        O.iterations = S.lm.iterations;
+        O.trials = S.lm.trials;
+        O.diag[PO_DIAG_REJECTED] = S.lm.rejected;
+        O.diag[PO_DIAG_NBAD_STOPS] = S.lm.nBadStops;
+        O.diag[PO_DIAG_SMALL_THETA] = S.lm.smallTheta;
+        O.diag[PO_DIAG_BIG_THETA] = S.lm.bigTheta;
     }
 };
 
@@ -217,8 +199,7 @@ int drfe_trans_opt_batch(drfe_ctx* c, const drfe_pose_opt_problems* p, drfe_pose
     ToView V;
     const int rc = check_call(p, o, V, c->err);
     if (rc) return rc;
-    TransOptBuffers* b = c->trans_opt;
-    if (!b) { b = new TransOptBuffers(); c->trans_opt = b; }
+    TransOptBuffers* b = batch_buffers(c->trans_opt);
     b->stats[0]++;
     if (p->n == 0) return DRFE_OK;
     const size_t n = (size_t)p->n;
@@ -246,10 +227,8 @@ int drfe_trans_opt_batch(drfe_ctx* c, const drfe_pose_opt_problems* p, drfe_pose
     const auto sLineFlag = out.add<uint8_t>(nL);
     const auto sPlaneFlag = out.add<uint8_t>(3 * nS);
     const auto sErr = scr.add<double>(3 * (nP + 2 * nL + 3 * nS));
-    HIPCHK(c, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, b->io.grow(in.bytes(), out.bytes()));
-    HIPCHK(c, b->scratch.grow(scr.bytes()));
+    hipStream_t st;
+    if (const int e = batch_begin(c, b, stream, in.bytes(), out.bytes(), scr.bytes(), &st)) return e;
     char* h = b->io.hin;
     sTcw.put(h, p->Tcw); sK.put(h, p->K); sBf.put(h, p->bf); sStruct.put(h, p->b_struct);
     sPointOff.put(h, p->point_offsets); sLineOff.put(h, p->line_offsets); sPlaneOff.put(h, p->plane_offsets);
@@ -258,8 +237,7 @@ int drfe_trans_opt_batch(drfe_ctx* c, const drfe_pose_opt_problems* p, drfe_pose
     sMeas.put(h, p->plane_meas); sWorld.put(h, p->plane_world); sMask.put(h, p->plane_mask);
     const char* d = b->io.din;
     char* dO = b->io.dout;
-    HIPCHK(c, hipMemcpyAsync(b->io.din, h, in.bytes(), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(dO, 0, out.bytes(), st));
+    if (const int e = batch_upload(c, b, in.bytes(), out.bytes(), st)) return e;
     ToLaunch L{};
     L.nFrames = p->n;
     L.view = V;                                    /* the settings; every pointer is replaced */
@@ -275,10 +253,7 @@ int drfe_trans_opt_batch(drfe_ctx* c, const drfe_pose_opt_problems* p, drfe_pose
     L.lineErr0 = (int64_t)nP;
     L.planeErr0 = (int64_t)(nP + 2 * nL);
     L.out = sOut.at(dO);
-    hipError_t e = drfe_launch_trans_opt(L, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(b->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, st);
-    if (e != hipSuccess) { c->err = std::string("trans_opt batch: ") + hipGetErrorString(e); return DRFE_ERR_HIP; }
-    HIPCHK(c, hipStreamSynchronize(st));
+    if (const int e = batch_finish(c, "trans_opt", drfe_launch_trans_opt(L, st), b, out.bytes(), st)) return e;
     const char* ho = b->io.hout;
     /* the flags are in the caller's layout already */
     sPointFlag.get(ho, o->point_outlier);
@@ -313,21 +288,9 @@ int drfe_trans_opt_batch(drfe_ctx* c, const drfe_pose_opt_problems* p, drfe_pose
     return DRFE_OK;
 }
 
-int drfe_trans_opt_stats(drfe_ctx* c, int64_t* stats)
-{
-    if (!c || !stats) return DRFE_ERR_INVALID;
-    if (c->trans_opt) std::memcpy(stats, c->trans_opt->stats, sizeof(c->trans_opt->stats));
-    else std::memset(stats, 0, 8 * sizeof(int64_t));
-    return DRFE_OK;
-}
+int drfe_trans_opt_stats(drfe_ctx* c, int64_t* stats) { return batch_stats(c, &drfe_ctx::trans_opt, stats); }
 
-int drfe_debug_trans_opt_hand_back(drfe_ctx* c, int every)
-{
-    if (!c || every < 0) return DRFE_ERR_INVALID;
-    if (!c->trans_opt) c->trans_opt = new TransOptBuffers();
-    c->trans_opt->handBackEvery = every;
-    return DRFE_OK;
-}
+int drfe_debug_trans_opt_hand_back(drfe_ctx* c, int every) { return batch_hand_back(c, &drfe_ctx::trans_opt, every); }
 
 int drfe_debug_trans_opt_plane_error(int kind, const float* meas, const float* world, const float* Tcw, double* e)
 {
@@ -351,7 +314,7 @@ int drfe_debug_trans_opt_plane_error(int kind, const float* meas, const float* w
     to_make_edge(V, F, planeAt, 0, E);
     double q[4], t[3];
     mp_to_se3quat(Tcw, q, t);
-    PoCtx ctx = {0, 1};
+    LmCtx ctx = {0, 1};
     to_edge_error(ctx, E, F.cam, t, e);
     return DRFE_OK;
 }

@@ -139,7 +139,7 @@ DRFE_HD uint8_t* to_flag(const ToView& V, const ToFrame& F, const uint8_t* plane
 }
 
 /* computeError of the *OnlyTranslation edges: estimate().mapTrans(Xc) = Xc + t, or localPlane = w2n + Xc (Plane3D.h:204-212) */
-DRFE_HD void to_edge_error(PoCtx& ctx, const PoEdge& E, const PoCam& C, const double t[3], double e[3])
+DRFE_HD void to_edge_error(LmCtx& ctx, const PoEdge& E, const PoCam& C, const double t[3], double e[3])
 {
     if (po_is_plane(E.kind)) {
         double l[4] = {E.X[0], E.X[1], E.X[2], 0.0};
@@ -179,7 +179,7 @@ DRFE_HD void to_edge_jacobian(const PoEdge& E, const PoCam& C, const double t[3]
 
 /* one perturbed error of a plane edge's numeric Jacobian, dimension 3 + d: computeError at exp(+-1e-9 e_(3 + d)) * estimate,
  * through the whole of oplusImpl as BaseUnaryEdge::linearizeOplus does (a translation that is not finite spreads there) */
-DRFE_HD void to_plane_perturbed(PoCtx& ctx, const PoEdge& E, const double q[4], const double t[3], int d, int side, double e[3])
+DRFE_HD void to_plane_perturbed(LmCtx& ctx, const PoEdge& E, const double q[4], const double t[3], int d, int side, double e[3])
 {
     double u[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, pq[4], pt[3];
     u[3 + d] = side ? -1e-9 : 1e-9;
@@ -190,9 +190,9 @@ DRFE_HD void to_plane_perturbed(PoCtx& ctx, const PoEdge& E, const double q[4], 
     po_plane_ominus(ctx, E, l, pt, e);
 }
 /* the plane Jacobian: columns 3..5 of BaseUnaryEdge::linearizeOplus(); what it computes for 0..2 is overwritten with 0 */
-DRFE_HD void to_plane_jacobian(PoCtx& ctx, const PoEdge& E, const double q[4], const double t[3], double J[3][3])
+DRFE_HD void to_plane_jacobian(LmCtx& ctx, const PoEdge& E, const double q[4], const double t[3], double J[3][3])
 {
-    const double scalar = po_numeric_scalar();
+    const double scalar = lm_numeric_scalar();
     for (int d = 0; d < 3; d++) {
         double e1[3], e2[3];
         to_plane_perturbed(ctx, E, q, t, d, 0, e1);

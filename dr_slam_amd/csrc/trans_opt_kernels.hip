@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "trans_opt_internal.h"
+#include "lm_device.h"
 
 namespace {
 
@@ -32,31 +33,16 @@ struct ToShared {
 };
 
 /* what lanes 0..8 and lane 0 add after a chunk's terms are in LDS */
-struct ToSums {
-    double acc, chi;
-    __device__ void add(const ToShared& sh, int cnt, bool build)
-    {
-        const int tid = threadIdx.x;
-        if (tid == 0)
-            for (int j = 0; j < cnt; j++) chi += sh.chi[j];
-        if (build && tid < TO_TERMS) {
-            const double* row = sh.term + tid * TO_TERM_STRIDE;
-            if (tid < TO_H_TERMS)
-                for (int j = 0; j < cnt; j++) acc += row[j];
-            else
-                for (int j = 0; j < cnt; j++) acc -= row[j];
-        }
-    }
-};
+using ToSums = LmSums<TO_TERMS, TO_H_TERMS, TO_TERM_STRIDE>;
 
-/* computeActiveErrors and activeRobustChi2; with `build` also linearizeOplus and constructQuadraticForm into S.H / S.b.
+/* computeActiveErrors and activeRobustChi2; with `build` also linearizeOplus and constructQuadraticForm into S.lm.H / S.lm.b.
  * Returns the robust chi2 in lane 0.  Every lane of the workgroup calls it. */
 __device__ double to_pass(ToShared& sh, const ToLaunch& L, int robust, bool build)
 {
     const int tid = threadIdx.x;
     const ToView& V = L.view;
     const ToFrame& F = sh.F;
-    PoCtx ctx = {0, 0};
+    LmCtx ctx = {0, 0};
     int fin = 1;
     double q[4], t[3];
     for (int k = 0; k < 4; k++) q[k] = sh.S.q[k];
@@ -86,7 +72,7 @@ __device__ double to_pass(ToShared& sh, const ToLaunch& L, int robust, bool buil
         }
         sh.chi[tid] = c;
         __syncthreads();
-        sums.add(sh, plane0 - base < TO_THREADS ? plane0 - base : TO_THREADS, build);
+        sums.add(sh.term, sh.chi, plane0 - base < TO_THREADS ? plane0 - base : TO_THREADS, build);
         __syncthreads();
     }
     for (int base = plane0; base < F.nEdges; base += TO_PLANE_GROUP) {
@@ -121,7 +107,7 @@ __device__ double to_pass(ToShared& sh, const ToLaunch& L, int robust, bool buil
             double term[TO_TERMS];
             if (act) {
                 double J[3][3];
-                const double scalar = po_numeric_scalar();
+                const double scalar = lm_numeric_scalar();
                 for (int d = 0; d < 3; d++)
                     for (int r = 0; r < 3; r++)
                         J[r][d] = scalar * (sh.pert[((own * 6 + 2 * d) * 3) + r] - sh.pert[((own * 6 + 2 * d + 1) * 3) + r]);
@@ -132,16 +118,16 @@ __device__ double to_pass(ToShared& sh, const ToLaunch& L, int robust, bool buil
             for (int r = 0; r < TO_TERMS; r++) sh.term[r * TO_TERM_STRIDE + own] = term[r];
         }
         __syncthreads();
-        sums.add(sh, cnt, build);
+        sums.add(sh.term, sh.chi, cnt, build);
         __syncthreads();
     }
     if (ctx.fail || !fin) sh.fail = 1;
     if (build) {
-        if (tid < PO_H_TERMS) sh.S.H[tid] = 0.0;
-        if (tid < 6) sh.S.b[tid] = 0.0;
+        if (tid < PO_H_TERMS) sh.S.lm.H[tid] = 0.0;
+        if (tid < 6) sh.S.lm.b[tid] = 0.0;
         __syncthreads();
-        if (tid < TO_H_TERMS) sh.S.H[to_h_index(tid)] = sums.acc;
-        else if (tid < TO_TERMS) sh.S.b[3 + tid - TO_H_TERMS] = sums.acc;
+        if (tid < TO_H_TERMS) sh.S.lm.H[to_h_index(tid)] = sums.acc;
+        else if (tid < TO_TERMS) sh.S.lm.b[3 + tid - TO_H_TERMS] = sums.acc;
         __syncthreads();
     }
     return sums.chi;
@@ -159,12 +145,12 @@ __global__ __launch_bounds__(TO_THREADS) void k_trans_opt(const ToLaunch L)
     const float* Tcw = V.Tcw + 16 * (size_t)f;
     if (tid == 0) {
         to_frame(V, f, sh.F);
-        po_lm_init(sh.S, 0);
+        lm_init(sh.S.lm, 0);
         sh.fail = 0;
     }
     __syncthreads();
     const ToFrame& F = sh.F;
-    const int nInitial = F.nPoints;
+    const int nInitial = lm_uniform(F.nPoints);
     if (nInitial < 3) {                                 /* uniform: the pose untouched, the flags false (zero before the launch) */
         if (tid < 16) O.Tcw[tid] = Tcw[tid];
         return;
@@ -174,11 +160,12 @@ __global__ __launch_bounds__(TO_THREADS) void k_trans_opt(const ToLaunch L)
         sh.F.nEdges = sh.F.nPoints + 2 * sh.F.nLines + sh.F.nPlaneEdges;
     }
     __syncthreads();
+    const int nEdges = lm_uniform(F.nEdges);
     int robust = 1, rounds = 0, lastRejectedRounds = 0, emptyRounds = 0, nBad = 0;
     for (int it = 0; it < 4; it++) {
         if (tid == 0) {
             mp_to_se3quat(Tcw, sh.S.q, sh.S.t);
-            sh.S.lastRejected = 0;
+            sh.S.lm.lastRejected = 0;
             sh.count = 0;
         }
         __syncthreads();
@@ -188,38 +175,20 @@ __global__ __launch_bounds__(TO_THREADS) void k_trans_opt(const ToLaunch L)
             if (mine) atomicAdd(&sh.count, mine);
         }
         __syncthreads();
-        const int nActive = sh.count;
+        const int nActive = lm_uniform(sh.count);
         __syncthreads();
         if (nActive == 0) emptyRounds++;
-        for (int i = 0; i < 10 && nActive > 0; i++) {
-            const double chi = to_pass(sh, L, robust, true);
-            if (tid == 0) po_lm_begin(sh.S, i, chi);
-            int more;
-            do {
-                if (tid == 0) po_lm_step(sh.S);
-                __syncthreads();
-                const double tempChi = to_pass(sh, L, robust, false);
-                if (tid == 0) sh.ctl = po_lm_judge(sh.S, tempChi);
-                __syncthreads();
-                more = sh.ctl;
-                __syncthreads();
-            } while (more);
-            if (tid == 0) sh.ctl = po_lm_end(sh.S);
-            __syncthreads();
-            const int ok = sh.ctl;
-            __syncthreads();
-            if (!ok) break;
-        }
+        else lm_iterations(sh.S, sh.ctl, 10, [&](bool build) { return to_pass(sh, L, robust, build); });
         rounds++;
         if (tid == 0) {
-            if (sh.S.lastRejected) lastRejectedRounds++;
+            if (sh.S.lm.lastRejected) lastRejectedRounds++;
             sh.count = 0;
         }
         __syncthreads();
         /* the classification: a point or a plane edge by one lane, a line's two ends by one lane; an outlier's error is
          * computed again, an inlier's is what the last computeActiveErrors left.  nLineBad is not returned */
         {
-            PoCtx ctx = {0, 0};
+            LmCtx ctx = {0, 0};
             double t[3];
             for (int k = 0; k < 3; k++) t[k] = sh.S.t[k];
             const int line0 = F.nPoints, plane0 = F.nPoints + 2 * F.nLines;
@@ -262,10 +231,10 @@ __global__ __launch_bounds__(TO_THREADS) void k_trans_opt(const ToLaunch L)
             if (ctx.fail) sh.fail = 1;
         }
         __syncthreads();
-        nBad = sh.count;
+        nBad = lm_uniform(sh.count);
         __syncthreads();
         if (it == 2) robust = 0;
-        if (F.nEdges < 10) break;
+        if (nEdges < 10) break;
     }
     if (tid == 0) {
         float T[16];
@@ -273,15 +242,15 @@ __global__ __launch_bounds__(TO_THREADS) void k_trans_opt(const ToLaunch L)
         for (int k = 0; k < 16; k++) O.Tcw[k] = T[k];
         O.ret = nInitial - nBad;
         O.rounds = rounds;
-        O.iterations = sh.S.iterations;
-        O.trials = sh.S.trials;
-        O.diag[PO_DIAG_REJECTED] = sh.S.rejected;
+        O.iterations = sh.S.lm.iterations;
+        O.trials = sh.S.lm.trials;
+        O.diag[PO_DIAG_REJECTED] = sh.S.lm.rejected;
         O.diag[PO_DIAG_LAST_REJECTED] = lastRejectedRounds;
-        O.diag[PO_DIAG_NBAD_STOPS] = sh.S.nBadStops;
-        O.diag[PO_DIAG_SMALL_THETA] = sh.S.smallTheta;
-        O.diag[PO_DIAG_BIG_THETA] = sh.S.bigTheta;
+        O.diag[PO_DIAG_NBAD_STOPS] = sh.S.lm.nBadStops;
+        O.diag[PO_DIAG_SMALL_THETA] = sh.S.lm.smallTheta;
+        O.diag[PO_DIAG_BIG_THETA] = sh.S.lm.bigTheta;
         O.diag[PO_DIAG_EMPTY_ROUNDS] = emptyRounds;
-        O.handBack = (sh.S.ctx.fail || sh.fail) ? 1 : 0;
+        O.handBack = (sh.S.lm.ctx.fail || sh.fail) ? 1 : 0;
     }
 }
 

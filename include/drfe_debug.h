@@ -127,11 +127,11 @@ int drfe_debug_pose_opt_hand_back(drfe_ctx* ctx, int every);
 int drfe_debug_trans_opt_plane_error(int kind, const float* meas, const float* world, const float* Tcw, double* e);
 int drfe_debug_trans_opt_hand_back(drfe_ctx* ctx, int every);
 /* Test hooks of OptimizeSim3 (dr_slam_amd/csrc/sim3_opt_core.h).  Host code.
- * _sim3_opt_ldlt: the 7x7 form of pose_opt_core.h's Eigen::LDLT (A row-major, the lower triangle is read) and its solve of A x = b;
+ * _sim3_opt_ldlt: the 7x7 form of lm_core.h's Eigen::LDLT (A row-major, the lower triangle is read) and its solve of A x = b;
  *   *positive = isPositive(), x is written only then.
  * _sim3_opt_step: the core's update (so_lm_update: VertexSim3Expmap::oplusImpl of xbl[0..6] on S12, eight doubles) into S12_out, and
- *   the core's computeScale (so_lm_scale, what so_lm_judge divides by) over x = xbl[0..6], b = xbl[7..13], lambda = xbl[14], read
- *   after the update as so_lm_step / so_lm_judge and g2o do, or with read_before before oplusImpl wrote x[6] = 0 for a fixed scale.
+ *   the core's computeScale (lm_scale, what lm_judge divides by) over x = xbl[0..6], b = xbl[7..13], lambda = xbl[14], read
+ *   after the update as lm_step / lm_judge and g2o do, or with read_before before oplusImpl wrote x[6] = 0 for a fixed scale.
  * _hand_back: every > 0 makes drfe_sim3_opt_batch treat every `every`-th problem of a call as not certified by the device, so that
  *   the host core finishes it; 0 switches the hook off. */
 int drfe_debug_sim3_opt_ldlt(const double* A, const double* b, double* x, int32_t* positive);
