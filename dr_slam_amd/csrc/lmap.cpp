@@ -1,0 +1,875 @@
+/* lmap.cpp — Tracking::UpdateLocalMap (reference src/Tracking.cc:3383-3541) behind the C-ABI of include/drfe.h: the store of the
+ * graph the three functions read, its flat image, the argument checks, the host walk, the device entry (lmap_kernels.hip) and the
+ * counters.  Both sides read the same image and evaluate lmap_core.h.  A call is checked as a whole and committed only when its
+ * results fit the caller's arrays.  DESIGN.md section 25. */
+#include "lmap_internal.h"
+#include "stage_layout.h"
+
+#include <algorithm>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+namespace {
+
+struct KfRow {
+    uint64_t rank = 0;
+    uint8_t bad = 0;
+    int32_t parent = -1;
+    int32_t nbr[LMAP_NEIGHBOURS];
+    std::vector<int32_t> children, mps, mls;   /* handles */
+};
+
+struct MpRow {
+    uint8_t bad = 0;
+    std::vector<int32_t> obs;                  /* key-frame handles */
+};
+
+/* the graph with every handle resolved to a slot: what the host walk and the kernels read */
+struct Image {
+    std::vector<int32_t> kfHandle, mpHandle, mlHandle;   /* by slot */
+    std::unordered_map<int32_t, int32_t> kfSlot, mpSlot, mlSlot;
+    std::vector<uint8_t> kfBad, mpBad, mlBad;
+    std::vector<int32_t> kfParent, kfNbr, childOff, child, kfMpOff, kfMp, kfMlOff, kfMl, obsOff, obs;
+    int32_t maxRow[2] = {0, 0};
+    LmapImage view() const
+    {
+        LmapImage I;
+        I.nK = (int32_t)kfHandle.size();
+        I.nP = (int32_t)mpHandle.size();
+        I.nL = (int32_t)mlHandle.size();
+        I.kfBad = kfBad.data();
+        I.kfParent = kfParent.data();
+        I.kfNbr = kfNbr.data();
+        I.childOff = childOff.data();
+        I.child = child.data();
+        I.kfMpOff = kfMpOff.data();
+        I.kfMp = kfMp.data();
+        I.kfMlOff = kfMlOff.data();
+        I.kfMl = kfMl.data();
+        I.mpBad = mpBad.data();
+        I.obsOff = obsOff.data();
+        I.obs = obs.data();
+        I.mlBad = mlBad.data();
+        return I;
+    }
+};
+
+/* a checked call, in slots */
+struct Call {
+    int n = 0;
+    std::vector<int32_t> ptOff, pts, lnOff, lns, prevOff, prev;
+    int64_t lastId = 0;
+    int32_t maxPrev = 0, maxPts = 0;
+};
+
+struct Result {
+    std::vector<int32_t> kfOff, kfs, ref, mpOff, mps, mlOff, mls, nuOff, nulled, record;
+    std::vector<uint8_t> mpIn, mlIn;
+    void start()
+    {
+        kfOff.assign(1, 0);
+        mpOff.assign(1, 0);
+        mlOff.assign(1, 0);
+        nuOff.assign(1, 0);
+    }
+};
+
+}  // namespace
+
+struct drfe_lmap {
+    drfe_ctx* ctx = nullptr;
+    int device = 0;
+    std::mutex mu;
+    std::string err;
+    std::unordered_map<int32_t, KfRow> kf;
+    std::unordered_map<int32_t, MpRow> mp;
+    std::unordered_map<int32_t, uint8_t> ml;
+    std::unordered_map<uint64_t, int32_t> rankOwner;
+    Image img;
+    bool imgDirty = true;              /* the image lacks an edit of the rows */
+    bool devDirty = true, devBadDirty = true;   /* the device copy lacks the image / its bad flags */
+    int64_t lastId = 0;
+    int64_t scratchBytes = (int64_t)1 << 30;
+    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    /* the host walk's stamps, kept between calls: an item is stamped for the query whose serial it holds */
+    std::vector<int32_t> stampP, stampL, inP, inL;
+    int32_t serial = 0;
+    DevBuf<char> dImg;
+    LmapImage dView;
+    StagePair io;
+    DevBuf<char> scratch;
+    PinnedBuf<char> hup, hlist;
+};
+
+namespace {
+
+int fail(drfe_lmap* db, int rc, const std::string& why)
+{
+    db->err = why;
+    return rc;
+}
+
+bool offsets_ok(const int32_t* off, int n)
+{
+    if (!off || off[0] != 0) return false;
+    for (int k = 0; k < n; k++)
+        if (off[k + 1] < off[k]) return false;
+    return true;
+}
+
+bool handles_ok(const int32_t* h, int n)
+{
+    for (int i = 0; i < n; i++)
+        if (h[i] < -1) return false;
+    return true;
+}
+
+/* the flat image of the rows; DRFE_ERR_STATE and the name of the reference when one dangles */
+int build_image(drfe_lmap* db)
+{
+    if (!db->imgDirty) return DRFE_OK;
+    Image G;
+    std::vector<std::pair<uint64_t, int32_t>> order;
+    order.reserve(db->kf.size());
+    for (const auto& e : db->kf) order.emplace_back(e.second.rank, e.first);
+    std::sort(order.begin(), order.end());
+    for (const auto& e : order) {
+        G.kfSlot[e.second] = (int32_t)G.kfHandle.size();
+        G.kfHandle.push_back(e.second);
+    }
+    for (const auto& e : db->mp) G.mpHandle.push_back(e.first);
+    std::sort(G.mpHandle.begin(), G.mpHandle.end());
+    for (size_t s = 0; s < G.mpHandle.size(); s++) G.mpSlot[G.mpHandle[s]] = (int32_t)s;
+    for (const auto& e : db->ml) G.mlHandle.push_back(e.first);
+    std::sort(G.mlHandle.begin(), G.mlHandle.end());
+    for (size_t s = 0; s < G.mlHandle.size(); s++) G.mlSlot[G.mlHandle[s]] = (int32_t)s;
+    const size_t nK = G.kfHandle.size(), nP = G.mpHandle.size(), nL = G.mlHandle.size();
+    auto dangling = [&](const char* what, int32_t of, const char* kind, int32_t h) {
+        return fail(db, DRFE_ERR_STATE, std::string("lmap: ") + what + " of " + kind + " " + std::to_string(of) + " names unknown handle " + std::to_string(h));
+    };
+    G.kfBad.resize(nK);
+    G.kfParent.assign(nK, -1);
+    G.kfNbr.assign(nK * LMAP_NEIGHBOURS, -1);
+    G.childOff.assign(1, 0);
+    G.kfMpOff.assign(1, 0);
+    G.kfMlOff.assign(1, 0);
+    std::vector<int32_t> ch;
+    for (size_t s = 0; s < nK; s++) {
+        const int32_t h = G.kfHandle[s];
+        const KfRow& K = db->kf.at(h);
+        G.kfBad[s] = K.bad;
+        if (K.parent >= 0) {
+            const auto it = G.kfSlot.find(K.parent);
+            if (it == G.kfSlot.end()) return dangling("the parent", h, "key frame", K.parent);
+            G.kfParent[s] = it->second;
+        }
+        for (int k = 0; k < LMAP_NEIGHBOURS; k++)
+            if (K.nbr[k] >= 0) {
+                const auto it = G.kfSlot.find(K.nbr[k]);
+                if (it == G.kfSlot.end()) return dangling("a neighbour", h, "key frame", K.nbr[k]);
+                G.kfNbr[s * LMAP_NEIGHBOURS + k] = it->second;
+            }
+        ch.clear();
+        for (const int32_t c : K.children) {
+            const auto it = G.kfSlot.find(c);
+            if (it == G.kfSlot.end()) return dangling("a child", h, "key frame", c);
+            ch.push_back(it->second);
+        }
+        std::sort(ch.begin(), ch.end());   /* ascending slot = rank order: set<KeyFrame*> */
+        G.child.insert(G.child.end(), ch.begin(), ch.end());
+        G.childOff.push_back((int32_t)G.child.size());
+        for (const int32_t p : K.mps) {
+            int32_t sl = -1;
+            if (p >= 0) {
+                const auto it = G.mpSlot.find(p);
+                if (it == G.mpSlot.end()) return dangling("a map-point match", h, "key frame", p);
+                sl = it->second;
+            }
+            G.kfMp.push_back(sl);
+        }
+        G.kfMpOff.push_back((int32_t)G.kfMp.size());
+        for (const int32_t l : K.mls) {
+            int32_t sl = -1;
+            if (l >= 0) {
+                const auto it = G.mlSlot.find(l);
+                if (it == G.mlSlot.end()) return dangling("a map-line match", h, "key frame", l);
+                sl = it->second;
+            }
+            G.kfMl.push_back(sl);
+        }
+        G.kfMlOff.push_back((int32_t)G.kfMl.size());
+        G.maxRow[0] = std::max(G.maxRow[0], (int32_t)K.mps.size());
+        G.maxRow[1] = std::max(G.maxRow[1], (int32_t)K.mls.size());
+    }
+    G.mpBad.resize(nP);
+    G.obsOff.assign(1, 0);
+    for (size_t s = 0; s < nP; s++) {
+        const MpRow& P = db->mp.at(G.mpHandle[s]);
+        G.mpBad[s] = P.bad;
+        for (const int32_t o : P.obs) {
+            const auto it = G.kfSlot.find(o);
+            if (it == G.kfSlot.end()) return dangling("an observation", G.mpHandle[s], "map point", o);
+            G.obs.push_back(it->second);
+        }
+        G.obsOff.push_back((int32_t)G.obs.size());
+    }
+    G.mlBad.resize(nL);
+    for (size_t s = 0; s < nL; s++) G.mlBad[s] = db->ml.at(G.mlHandle[s]);
+    db->img = std::move(G);
+    db->imgDirty = false;
+    db->devDirty = true;
+    return DRFE_OK;
+}
+
+int slots_of(drfe_lmap* db, const std::unordered_map<int32_t, int32_t>& map, const int32_t* h, int n, bool allowNull, const char* what,
+             std::vector<int32_t>& out)
+{
+    out.resize((size_t)n);
+    for (int i = 0; i < n; i++) {
+        if (h[i] == -1 && allowNull) {
+            out[(size_t)i] = -1;
+            continue;
+        }
+        const auto it = map.find(h[i]);
+        if (it == map.end()) return fail(db, DRFE_ERR_INVALID, std::string("lmap: a query names an unknown ") + what + " handle");
+        out[(size_t)i] = it->second;
+    }
+    return DRFE_OK;
+}
+
+int plan(drfe_lmap* db, const drfe_lmap_queries* q, const drfe_lmap_out* o, Call& C)
+{
+    if (!q || q->n < 0 || !o) return fail(db, DRFE_ERR_INVALID, "lmap: invalid argument");
+    if (q->n > DRFE_LMAP_MAX_QUERIES) return fail(db, DRFE_ERR_INVALID, "lmap: more than DRFE_LMAP_MAX_QUERIES queries in a call");
+    if (o->kf_capacity < 0 || o->mp_capacity < 0 || o->ml_capacity < 0 || o->nulled_capacity < 0 || !o->kf_offsets || !o->ref_kf ||
+        !o->mp_offsets || !o->ml_offsets || !o->nulled_offsets || !o->record || (o->kf_capacity > 0 && !o->kfs) ||
+        (o->mp_capacity > 0 && (!o->mps || !o->mp_in_frame)) || (o->ml_capacity > 0 && (!o->mls || !o->ml_in_frame)) ||
+        (o->nulled_capacity > 0 && !o->nulled))
+        return fail(db, DRFE_ERR_INVALID, "lmap: invalid output arrays");
+    const int n = q->n;
+    C.n = n;
+    if (n == 0) return DRFE_OK;
+    if (!q->frame_id) return fail(db, DRFE_ERR_INVALID, "lmap: invalid argument");
+    int64_t last = db->lastId;
+    for (int k = 0; k < n; k++) {
+        if (q->frame_id[k] == 0 || q->frame_id[k] <= last)
+            return fail(db, DRFE_ERR_INVALID, "lmap: a frame id is 0 or does not exceed the last id used on this store");
+        last = q->frame_id[k];
+    }
+    C.lastId = last;
+    if (!offsets_ok(q->point_offsets, n) || (q->point_offsets[n] > 0 && !q->points))
+        return fail(db, DRFE_ERR_INVALID, "lmap: point_offsets do not start at 0 or decrease");
+    if (q->line_offsets && (!offsets_ok(q->line_offsets, n) || (q->line_offsets[n] > 0 && !q->lines)))
+        return fail(db, DRFE_ERR_INVALID, "lmap: line_offsets do not start at 0 or decrease");
+    if (q->prev_kf_offsets && (!offsets_ok(q->prev_kf_offsets, n) || (q->prev_kf_offsets[n] > 0 && !q->prev_kfs)))
+        return fail(db, DRFE_ERR_INVALID, "lmap: prev_kf_offsets do not start at 0 or decrease");
+    int rc = build_image(db);
+    if (rc) return rc;
+    const Image& G = db->img;
+    C.ptOff.assign(q->point_offsets, q->point_offsets + n + 1);
+    rc = slots_of(db, G.mpSlot, q->points, C.ptOff[(size_t)n], true, "map-point", C.pts);
+    if (rc) return rc;
+    if (q->line_offsets) {
+        C.lnOff.assign(q->line_offsets, q->line_offsets + n + 1);
+        rc = slots_of(db, G.mlSlot, q->lines, C.lnOff[(size_t)n], true, "map-line", C.lns);
+        if (rc) return rc;
+    } else {
+        C.lnOff.assign((size_t)n + 1, 0);
+    }
+    if (q->prev_kf_offsets) {
+        C.prevOff.assign(q->prev_kf_offsets, q->prev_kf_offsets + n + 1);
+        rc = slots_of(db, G.kfSlot, q->prev_kfs, C.prevOff[(size_t)n], false, "key-frame", C.prev);
+        if (rc) return rc;
+    } else {
+        C.prevOff.assign((size_t)n + 1, 0);
+    }
+    for (int k = 0; k < n; k++) {
+        C.maxPrev = std::max(C.maxPrev, C.prevOff[(size_t)k + 1] - C.prevOff[(size_t)k]);
+        C.maxPts = std::max(C.maxPts, C.ptOff[(size_t)k + 1] - C.ptOff[(size_t)k]);
+    }
+    return DRFE_OK;
+}
+
+/* the reference's loops, query after query, with stamps for mnTrackReferenceForFrame */
+void run_host(drfe_lmap* db, const Call& C, Result& R)
+{
+    const LmapImage I = db->img.view();
+    const int n = C.n;
+    R.start();
+    R.ref.assign((size_t)n, -1);
+    R.record.assign((size_t)n * 4, 0);
+    std::vector<int32_t> votes((size_t)I.nK), list;
+    std::vector<uint32_t> mark(((size_t)I.nK + 31) / 32);
+    std::vector<int32_t>&stampP = db->stampP, &stampL = db->stampL, &inP = db->inP, &inL = db->inL;
+    if (stampP.size() != (size_t)I.nP || stampL.size() != (size_t)I.nL || db->serial > 0x7fffffff - n) {
+        stampP.assign((size_t)I.nP, 0);
+        inP.assign((size_t)I.nP, 0);
+        stampL.assign((size_t)I.nL, 0);
+        inL.assign((size_t)I.nL, 0);
+        db->serial = 0;
+    }
+    for (int q = 0; q < n; q++) {
+        const int32_t k = ++db->serial;
+        std::fill(votes.begin(), votes.end(), 0);
+        for (int i = C.ptOff[(size_t)q]; i < C.ptOff[(size_t)q + 1]; i++) {
+            const int32_t p = C.pts[(size_t)i];
+            const int what = lmap_frame_point(p, I.mpBad);
+            if (what == 2) R.nulled.push_back(i - C.ptOff[(size_t)q]);
+            if (what != 1) continue;
+            inP[(size_t)p] = k;
+            for (int o = I.obsOff[p]; o < I.obsOff[p + 1]; o++) votes[(size_t)I.obs[o]]++;
+        }
+        R.nuOff.push_back((int32_t)R.nulled.size());
+        for (int i = C.lnOff[(size_t)q]; i < C.lnOff[(size_t)q + 1]; i++)
+            if (C.lns[(size_t)i] >= 0) inL[(size_t)C.lns[(size_t)i]] = k;
+        int32_t counter = 0, bv = 0, bs = 0x7fffffff;
+        list.clear();
+        std::fill(mark.begin(), mark.end(), 0u);
+        for (int32_t s = 0; s < I.nK; s++) {
+            const int32_t v = votes[(size_t)s];
+            if (v > 0) counter++;
+            if (!lmap_listed(v, I.kfBad[s])) continue;
+            if (lmap_better(v, s, bv, bs)) {
+                bv = v;
+                bs = s;
+            }
+            list.push_back(s);
+            lmap_mark(mark.data(), s);
+        }
+        if (counter == 0) {
+            list.assign(C.prev.begin() + C.prevOff[(size_t)q], C.prev.begin() + C.prevOff[(size_t)q + 1]);
+        } else {
+            const int32_t nListed = (int32_t)list.size();
+            list.resize((size_t)I.nK);
+            const int32_t added = lmap_expand(I, list.data(), nListed, mark.data());
+            list.resize((size_t)(nListed + added));
+            R.ref[(size_t)q] = bv > 0 ? bs : -1;
+            R.record[4 * (size_t)q + 0] = counter;
+            R.record[4 * (size_t)q + 1] = nListed;
+            R.record[4 * (size_t)q + 2] = added;
+            R.record[4 * (size_t)q + 3] = bv;
+        }
+        R.kfs.insert(R.kfs.end(), list.begin(), list.end());
+        R.kfOff.push_back((int32_t)R.kfs.size());
+        for (const int32_t kf : list) {
+            for (int i = I.kfMpOff[kf]; i < I.kfMpOff[kf + 1]; i++) {
+                const int32_t p = I.kfMp[i];
+                if (p < 0 || stampP[(size_t)p] == k || I.mpBad[p]) continue;
+                stampP[(size_t)p] = k;
+                R.mps.push_back(p);
+                R.mpIn.push_back(inP[(size_t)p] == k ? 1 : 0);
+            }
+            for (int i = I.kfMlOff[kf]; i < I.kfMlOff[kf + 1]; i++) {
+                const int32_t l = I.kfMl[i];
+                if (l < 0 || stampL[(size_t)l] == k || I.mlBad[l]) continue;
+                stampL[(size_t)l] = k;
+                R.mls.push_back(l);
+                R.mlIn.push_back(inL[(size_t)l] == k ? 1 : 0);
+            }
+        }
+        R.mpOff.push_back((int32_t)R.mps.size());
+        R.mlOff.push_back((int32_t)R.mls.size());
+    }
+}
+
+/* bytes of device scratch one query takes, its packed results included */
+int64_t query_scratch(const drfe_lmap* db, const Call& C, int32_t rowK)
+{
+    const Image& G = db->img;
+    const int64_t nK = (int64_t)G.kfHandle.size(), nP = (int64_t)G.mpHandle.size(), nL = (int64_t)G.mlHandle.size();
+    return (nK > LMAP_LDS_KFS ? 4 * nK : 0) + 4 * ((nK + 31) / 32) + 16 * (int64_t)rowK + 10 * (nP + nL) + 8 * (int64_t)C.maxPts + 256;
+}
+
+int32_t row_k(const drfe_lmap* db, const Call& C) { return std::max((int32_t)db->img.kfHandle.size(), C.maxPrev); }
+
+/* the device can run the call: a query fits the scratch budget and the walk ranks fit an int32 */
+bool device_fits(const drfe_lmap* db, const Call& C)
+{
+    const int32_t rowK = row_k(db, C);
+    const int64_t stride = (int64_t)std::max(db->img.maxRow[0], db->img.maxRow[1]) + 1;
+    return query_scratch(db, C, rowK) <= db->scratchBytes && (int64_t)rowK * stride < (int64_t)LMAP_NO_CLAIM;
+}
+
+int upload_image(drfe_lmap* db, hipStream_t st)
+{
+    const Image& G = db->img;
+    if (!db->devDirty && !db->devBadDirty) return DRFE_OK;
+    StageLayout<16> up;
+    const auto uKfBad = up.add<uint8_t>(G.kfBad.size());
+    const auto uMpBad = up.add<uint8_t>(G.mpBad.size());
+    const auto uMlBad = up.add<uint8_t>(G.mlBad.size());
+    const size_t badBytes = up.bytes();
+    const auto uParent = up.add<int32_t>(G.kfParent.size());
+    const auto uNbr = up.add<int32_t>(G.kfNbr.size());
+    const auto uChildOff = up.add<int32_t>(G.childOff.size());
+    const auto uChild = up.add<int32_t>(G.child.size());
+    const auto uKfMpOff = up.add<int32_t>(G.kfMpOff.size());
+    const auto uKfMp = up.add<int32_t>(G.kfMp.size());
+    const auto uKfMlOff = up.add<int32_t>(G.kfMlOff.size());
+    const auto uKfMl = up.add<int32_t>(G.kfMl.size());
+    const auto uObsOff = up.add<int32_t>(G.obsOff.size());
+    const auto uObs = up.add<int32_t>(G.obs.size());
+    const bool all = db->devDirty;
+    const size_t bytes = all ? up.bytes() : badBytes;
+    HIPCHK_TO(db->err, db->hup.grow(db->hup.capacity() >= bytes ? bytes : 2 * bytes));
+    char* h = db->hup;
+    uKfBad.put(h, G.kfBad.data());
+    uMpBad.put(h, G.mpBad.data());
+    uMlBad.put(h, G.mlBad.data());
+    if (all) {
+        uParent.put(h, G.kfParent.data());
+        uNbr.put(h, G.kfNbr.data());
+        uChildOff.put(h, G.childOff.data());
+        uChild.put(h, G.child.data());
+        uKfMpOff.put(h, G.kfMpOff.data());
+        uKfMp.put(h, G.kfMp.data());
+        uKfMlOff.put(h, G.kfMlOff.data());
+        uKfMl.put(h, G.kfMl.data());
+        uObsOff.put(h, G.obsOff.data());
+        uObs.put(h, G.obs.data());
+        /* an image that no longer fits is allocated at twice the size */
+        HIPCHK_TO(db->err, db->dImg.grow(db->dImg.capacity() >= bytes ? bytes : 2 * bytes));
+        const char* d = db->dImg;
+        LmapImage& V = db->dView;
+        V = G.view();
+        V.kfBad = uKfBad.at(d);
+        V.mpBad = uMpBad.at(d);
+        V.mlBad = uMlBad.at(d);
+        V.kfParent = uParent.at(d);
+        V.kfNbr = uNbr.at(d);
+        V.childOff = uChildOff.at(d);
+        V.child = uChild.at(d);
+        V.kfMpOff = uKfMpOff.at(d);
+        V.kfMp = uKfMp.at(d);
+        V.kfMlOff = uKfMlOff.at(d);
+        V.kfMl = uKfMl.at(d);
+        V.obsOff = uObsOff.at(d);
+        V.obs = uObs.at(d);
+    }
+    if (bytes) HIPCHK_TO(db->err, hipMemcpyAsync(db->dImg, h, bytes, hipMemcpyHostToDevice, st));
+    /* the staging block is written again by the next upload */
+    HIPCHK_TO(db->err, hipStreamSynchronize(st));
+    db->devDirty = db->devBadDirty = false;
+    db->stats[3]++;
+    return DRFE_OK;
+}
+
+/* queries [k0, k1) of the call: one staging block up, the launches, the offsets and records back, then exactly the lists */
+int run_chunk(drfe_lmap* db, const Call& C, int k0, int k1, int32_t rowK, Result& R, hipStream_t st)
+{
+    const Image& G = db->img;
+    const size_t nQ = (size_t)(k1 - k0), nK = G.kfHandle.size(), nP = G.mpHandle.size(), nL = G.mlHandle.size();
+    const size_t markWords = (nK + 31) / 32;
+    const int32_t pt0 = C.ptOff[(size_t)k0], ln0 = C.lnOff[(size_t)k0], pv0 = C.prevOff[(size_t)k0];
+    const size_t nPts = (size_t)(C.ptOff[(size_t)k1] - pt0), nLns = (size_t)(C.lnOff[(size_t)k1] - ln0), nPrev = (size_t)(C.prevOff[(size_t)k1] - pv0);
+    StageLayout<16> in, out, scr;
+    const auto sPtOff = in.add<int32_t>(nQ + 1);
+    const auto sPts = in.add<int32_t>(nPts);
+    const auto sLnOff = in.add<int32_t>(nQ + 1);
+    const auto sLns = in.add<int32_t>(nLns);
+    const auto sPrevOff = in.add<int32_t>(nQ + 1);
+    const auto sPrev = in.add<int32_t>(nPrev);
+    const auto oRec = out.add<LmapQueryRec>(nQ);
+    const auto oOff = out.add<int32_t>(4 * (nQ + 1));
+    /* zeroed: the global histogram (when the LDS one is too small) and the in-frame rows */
+    const auto xHist = scr.add<int32_t>(nK > LMAP_LDS_KFS ? nQ * nK : 0);
+    const auto xInP = scr.add<uint8_t>(nQ * nP);
+    const auto xInL = scr.add<uint8_t>(nQ * nL);
+    const size_t zeroEnd = scr.bytes();
+    /* LMAP_NO_CLAIM bytes */
+    const auto xClaimP = scr.add<int32_t>(nQ * nP);
+    const auto xClaimL = scr.add<int32_t>(nQ * nL);
+    const size_t claimEnd = scr.bytes();
+    const auto xMark = scr.add<uint32_t>(nQ * markWords);
+    const auto xList = scr.add<int32_t>(nQ * (size_t)rowK);
+    const auto xCntP = scr.add<int32_t>(nQ * (size_t)rowK);
+    const auto xCntL = scr.add<int32_t>(nQ * (size_t)rowK);
+    const auto xNulledTmp = scr.add<int32_t>(nPts);
+    const auto xKf = scr.add<int32_t>(nQ * (size_t)rowK);
+    const auto xMp = scr.add<int32_t>(nQ * nP);
+    const auto xMl = scr.add<int32_t>(nQ * nL);
+    const auto xNulled = scr.add<int32_t>(nPts);
+    const auto xMpIn = scr.add<uint8_t>(nQ * nP);
+    const auto xMlIn = scr.add<uint8_t>(nQ * nL);
+    HIPCHK_TO(db->err, db->io.grow(in.bytes(), out.bytes()));
+    HIPCHK_TO(db->err, db->scratch.grow(scr.bytes()));
+    char* h = db->io.hin;
+    for (size_t k = 0; k <= nQ; k++) {
+        sPtOff.at(h)[k] = C.ptOff[(size_t)k0 + k] - pt0;
+        sLnOff.at(h)[k] = C.lnOff[(size_t)k0 + k] - ln0;
+        sPrevOff.at(h)[k] = C.prevOff[(size_t)k0 + k] - pv0;
+    }
+    sPts.put(h, C.pts.data() + pt0);
+    sLns.put(h, C.lns.data() + ln0);
+    sPrev.put(h, C.prev.data() + pv0);
+    const char* d = db->io.din;
+    char* dO = db->io.dout;
+    char* dS = db->scratch;
+    HIPCHK_TO(db->err, hipMemcpyAsync(db->io.din, h, in.bytes(), hipMemcpyHostToDevice, st));
+    if (zeroEnd) HIPCHK_TO(db->err, hipMemsetAsync(dS, 0, zeroEnd, st));
+    if (claimEnd > zeroEnd) HIPCHK_TO(db->err, hipMemsetAsync(dS + zeroEnd, LMAP_NO_CLAIM & 0xff, claimEnd - zeroEnd, st));
+    LmapLaunch L{};
+    L.I = db->dView;
+    L.nQ = (int32_t)nQ;
+    L.rowK = rowK;
+    L.rowStride[0] = G.maxRow[0] + 1;
+    L.rowStride[1] = G.maxRow[1] + 1;
+    L.markWords = (int32_t)markWords;
+    L.ptOff = sPtOff.at(d);
+    L.pts = sPts.at(d);
+    L.lnOff = sLnOff.at(d);
+    L.lns = sLns.at(d);
+    L.prevOff = sPrevOff.at(d);
+    L.prev = sPrev.at(d);
+    L.hist = xHist.at(dS);
+    L.mark = xMark.at(dS);
+    L.list = xList.at(dS);
+    L.cnt[0] = xCntP.at(dS);
+    L.cnt[1] = xCntL.at(dS);
+    L.claim[0] = xClaimP.at(dS);
+    L.claim[1] = xClaimL.at(dS);
+    L.inFrame[0] = xInP.at(dS);
+    L.inFrame[1] = xInL.at(dS);
+    L.nulledTmp = xNulledTmp.at(dS);
+    L.rec = oRec.at(dO);
+    for (int f = 0; f < 4; f++) L.off[f] = oOff.at(dO) + (size_t)f * (nQ + 1);
+    L.packedKf = xKf.at(dS);
+    L.packedItem[0] = xMp.at(dS);
+    L.packedItem[1] = xMl.at(dS);
+    L.packedIn[0] = xMpIn.at(dS);
+    L.packedIn[1] = xMlIn.at(dS);
+    L.packedNulled = xNulled.at(dS);
+    hipError_t e = drfe_launch_lmap(L, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(db->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(db, DRFE_ERR_HIP, std::string("lmap device call: ") + hipGetErrorString(e));
+    const char* ho = db->io.hout;
+    const LmapQueryRec* rec = oRec.at(ho);
+    const int32_t* off = oOff.at(ho);
+    const size_t tKf = (size_t)off[nQ], tMp = (size_t)off[2 * nQ + 1], tMl = (size_t)off[3 * nQ + 2], tNu = (size_t)off[4 * nQ + 3];
+    StageLayout<16> li;
+    const auto lKf = li.add<int32_t>(tKf);
+    const auto lMp = li.add<int32_t>(tMp);
+    const auto lMl = li.add<int32_t>(tMl);
+    const auto lNu = li.add<int32_t>(tNu);
+    const auto lMpIn = li.add<uint8_t>(tMp);
+    const auto lMlIn = li.add<uint8_t>(tMl);
+    HIPCHK_TO(db->err, db->hlist.grow(li.bytes()));
+    char* hl = db->hlist;
+    if (tKf) HIPCHK_TO(db->err, hipMemcpyAsync(lKf.at(hl), xKf.at(dS), lKf.bytes(), hipMemcpyDeviceToHost, st));
+    if (tMp) HIPCHK_TO(db->err, hipMemcpyAsync(lMp.at(hl), xMp.at(dS), lMp.bytes(), hipMemcpyDeviceToHost, st));
+    if (tMl) HIPCHK_TO(db->err, hipMemcpyAsync(lMl.at(hl), xMl.at(dS), lMl.bytes(), hipMemcpyDeviceToHost, st));
+    if (tNu) HIPCHK_TO(db->err, hipMemcpyAsync(lNu.at(hl), xNulled.at(dS), lNu.bytes(), hipMemcpyDeviceToHost, st));
+    if (tMp) HIPCHK_TO(db->err, hipMemcpyAsync(lMpIn.at(hl), xMpIn.at(dS), lMpIn.bytes(), hipMemcpyDeviceToHost, st));
+    if (tMl) HIPCHK_TO(db->err, hipMemcpyAsync(lMlIn.at(hl), xMlIn.at(dS), lMlIn.bytes(), hipMemcpyDeviceToHost, st));
+    HIPCHK_TO(db->err, hipStreamSynchronize(st));
+    const int32_t bKf = R.kfOff.back(), bMp = R.mpOff.back(), bMl = R.mlOff.back(), bNu = R.nuOff.back();
+    for (size_t k = 0; k < nQ; k++) {
+        R.kfOff.push_back(bKf + off[k + 1]);
+        R.mpOff.push_back(bMp + off[(nQ + 1) + k + 1]);
+        R.mlOff.push_back(bMl + off[2 * (nQ + 1) + k + 1]);
+        R.nuOff.push_back(bNu + off[3 * (nQ + 1) + k + 1]);
+        R.ref.push_back(rec[k].refKf);
+        for (int f = 0; f < 4; f++) R.record.push_back(rec[k].rec[f]);
+    }
+    R.kfs.insert(R.kfs.end(), lKf.at(hl), lKf.at(hl) + tKf);
+    R.mps.insert(R.mps.end(), lMp.at(hl), lMp.at(hl) + tMp);
+    R.mls.insert(R.mls.end(), lMl.at(hl), lMl.at(hl) + tMl);
+    R.nulled.insert(R.nulled.end(), lNu.at(hl), lNu.at(hl) + tNu);
+    R.mpIn.insert(R.mpIn.end(), lMpIn.at(hl), lMpIn.at(hl) + tMp);
+    R.mlIn.insert(R.mlIn.end(), lMlIn.at(hl), lMlIn.at(hl) + tMl);
+    return DRFE_OK;
+}
+
+int run_device(drfe_lmap* db, const Call& C, Result& R, void* stream)
+{
+    drfe_ctx* c = db->ctx;
+    HIPCHK_TO(db->err, hipSetDevice(c->device));
+    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
+    int rc = upload_image(db, st);
+    if (rc) return rc;
+    const int32_t rowK = row_k(db, C);
+    const int64_t perQuery = query_scratch(db, C, rowK);
+    const int chunk = (int)std::min<int64_t>(C.n, std::max<int64_t>(1, db->scratchBytes / perQuery));
+    R.start();
+    for (int k0 = 0; k0 < C.n; k0 += chunk) {
+        rc = run_chunk(db, C, k0, std::min(C.n, k0 + chunk), rowK, R, st);
+        if (rc) return rc;
+    }
+    return DRFE_OK;
+}
+
+/* results into the caller's arrays and the call into the store's id and counters, or neither */
+int finish(drfe_lmap* db, const Call& C, const Result& R, drfe_lmap_out* o, bool onDevice)
+{
+    const int n = C.n;
+    const Image& G = db->img;
+    o->kf_offsets[0] = o->mp_offsets[0] = o->ml_offsets[0] = o->nulled_offsets[0] = 0;
+    if (n == 0) return DRFE_OK;
+    const int32_t tKf = R.kfOff[(size_t)n], tMp = R.mpOff[(size_t)n], tMl = R.mlOff[(size_t)n], tNu = R.nuOff[(size_t)n];
+    if (tKf > o->kf_capacity) return fail(db, DRFE_ERR_CAPACITY, "lmap: more local key frames than kf_capacity");
+    if (tMp > o->mp_capacity) return fail(db, DRFE_ERR_CAPACITY, "lmap: more local points than mp_capacity");
+    if (tMl > o->ml_capacity) return fail(db, DRFE_ERR_CAPACITY, "lmap: more local lines than ml_capacity");
+    if (tNu > o->nulled_capacity) return fail(db, DRFE_ERR_CAPACITY, "lmap: more nulled points than nulled_capacity");
+    for (int k = 0; k < n; k++) {
+        o->kf_offsets[k + 1] = R.kfOff[(size_t)k + 1];
+        o->mp_offsets[k + 1] = R.mpOff[(size_t)k + 1];
+        o->ml_offsets[k + 1] = R.mlOff[(size_t)k + 1];
+        o->nulled_offsets[k + 1] = R.nuOff[(size_t)k + 1];
+        o->ref_kf[k] = R.ref[(size_t)k] >= 0 ? G.kfHandle[(size_t)R.ref[(size_t)k]] : -1;
+    }
+    std::memcpy(o->record, R.record.data(), sizeof(int32_t) * 4 * (size_t)n);
+    for (int32_t i = 0; i < tKf; i++) o->kfs[i] = G.kfHandle[(size_t)R.kfs[(size_t)i]];
+    for (int32_t i = 0; i < tMp; i++) o->mps[i] = G.mpHandle[(size_t)R.mps[(size_t)i]];
+    for (int32_t i = 0; i < tMl; i++) o->mls[i] = G.mlHandle[(size_t)R.mls[(size_t)i]];
+    if (tMp) std::memcpy(o->mp_in_frame, R.mpIn.data(), (size_t)tMp);
+    if (tMl) std::memcpy(o->ml_in_frame, R.mlIn.data(), (size_t)tMl);
+    if (tNu) std::memcpy(o->nulled, R.nulled.data(), sizeof(int32_t) * (size_t)tNu);
+    db->lastId = C.lastId;
+    db->stats[0]++;
+    db->stats[1] += n;
+    if (onDevice) db->stats[2]++;
+    db->stats[4] += tKf;
+    db->stats[5] += tMp;
+    db->stats[6] += tMl;
+    db->stats[7] += tNu;
+    return DRFE_OK;
+}
+
+/* mode: 0 host, 1 device, 2 by the crossover */
+int entry(drfe_lmap* db, const drfe_lmap_queries* q, drfe_lmap_out* o, int mode, void* stream)
+{
+    if (!db) return DRFE_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(db->mu);
+    if (mode == 1 && !db->ctx) return fail(db, DRFE_ERR_STATE, "lmap: a device call on a store without a context");
+    Call C;
+    int rc = plan(db, q, o, C);
+    if (rc) return rc;
+    bool dev = mode == 1;
+    if (mode == 2) dev = db->ctx && C.n >= DRFE_LMAP_DEVICE_FROM && device_fits(db, C);
+    if (C.n == 0) dev = false;
+    if (dev && !device_fits(db, C))
+        return fail(db, DRFE_ERR_CAPACITY, "lmap: one query does not fit the configured device scratch (or its walk ranks an int32)");
+    Result R;
+    if (dev) {
+        rc = run_device(db, C, R, stream);
+        if (rc) return rc;
+    } else if (C.n > 0) {
+        run_host(db, C, R);
+    }
+    return finish(db, C, R, o, dev);
+}
+
+template <class Map>
+int set_bad(drfe_lmap* db, Map& rows, const std::unordered_map<int32_t, int32_t>& slot, std::vector<uint8_t>& bad, int32_t count,
+            const int32_t* handles, const uint8_t* flags, uint8_t& (*field)(typename Map::mapped_type&))
+{
+    for (int i = 0; i < count; i++)
+        if (rows.find(handles[i]) == rows.end()) return fail(db, DRFE_ERR_INVALID, "lmap_set_bad: unknown handle");
+    for (int i = 0; i < count; i++) {
+        field(rows.at(handles[i])) = flags[i] ? 1 : 0;
+        if (!db->imgDirty) bad[(size_t)slot.at(handles[i])] = flags[i] ? 1 : 0;
+    }
+    if (count) db->devBadDirty = true;
+    return DRFE_OK;
+}
+
+uint8_t& kf_bad(KfRow& r) { return r.bad; }
+uint8_t& mp_bad(MpRow& r) { return r.bad; }
+uint8_t& ml_bad(uint8_t& r) { return r; }
+
+}  // namespace
+
+extern "C" {
+
+int drfe_lmap_create(drfe_ctx* ctx, drfe_lmap** out)
+{
+    if (!out) return DRFE_ERR_INVALID;
+    drfe_lmap* db = new drfe_lmap();
+    db->ctx = ctx;
+    if (ctx) db->device = ctx->device;
+    db->dView = LmapImage{};
+    *out = db;
+    return DRFE_OK;
+}
+
+void drfe_lmap_destroy(drfe_lmap* db)
+{
+    if (!db) return;
+    if (db->ctx) (void)hipSetDevice(db->device);
+    delete db;
+}
+
+const char* drfe_lmap_last_error(const drfe_lmap* db) { return db ? db->err.c_str() : "lmap: no store"; }
+
+int drfe_lmap_configure(drfe_lmap* db, int64_t scratch_bytes)
+{
+    if (!db) return DRFE_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(db->mu);
+    if (scratch_bytes <= 0) return fail(db, DRFE_ERR_INVALID, "lmap_configure: scratch_bytes must be positive");
+    db->scratchBytes = scratch_bytes;
+    return DRFE_OK;
+}
+
+int drfe_lmap_limits(int32_t* out4)
+{
+    if (!out4) return DRFE_ERR_INVALID;
+    out4[0] = LMAP_LDS_KFS;
+    out4[1] = LMAP_THREADS;
+    out4[2] = LMAP_GATHER_ENTRIES;
+    out4[3] = DRFE_LMAP_DEVICE_FROM;
+    return DRFE_OK;
+}
+
+int drfe_lmap_set_keyframes(drfe_lmap* db, const drfe_lmap_keyframes* r)
+{
+    if (!db) return DRFE_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(db->mu);
+    if (!r || r->count < 0) return fail(db, DRFE_ERR_INVALID, "lmap_set_keyframes: invalid argument");
+    const int n = r->count;
+    if (n == 0) return DRFE_OK;
+    if (!r->handle || !r->rank || !r->bad || !r->parent || !r->neighbours || !offsets_ok(r->child_offsets, n) ||
+        !offsets_ok(r->point_offsets, n) || !offsets_ok(r->line_offsets, n) || (r->child_offsets[n] > 0 && !r->children) ||
+        (r->point_offsets[n] > 0 && !r->points) || (r->line_offsets[n] > 0 && !r->lines))
+        return fail(db, DRFE_ERR_INVALID, "lmap_set_keyframes: invalid argument");
+    if (!handles_ok(r->parent, n) || !handles_ok(r->neighbours, n * LMAP_NEIGHBOURS) || !handles_ok(r->points, r->point_offsets[n]) ||
+        !handles_ok(r->lines, r->line_offsets[n]))
+        return fail(db, DRFE_ERR_INVALID, "lmap_set_keyframes: a handle below -1");
+    /* the last row of a handle wins; ranks stay distinct within the store */
+    std::unordered_map<int32_t, int> lastRow;
+    for (int i = 0; i < n; i++) {
+        if (r->handle[i] < 0) return fail(db, DRFE_ERR_INVALID, "lmap_set_keyframes: a negative handle");
+        lastRow[r->handle[i]] = i;
+    }
+    std::unordered_map<uint64_t, int32_t> ranks;
+    std::vector<int32_t> ch;
+    for (const auto& e : lastRow) {
+        const int i = e.second;
+        const auto own = db->rankOwner.find(r->rank[i]);
+        if ((own != db->rankOwner.end() && lastRow.find(own->second) == lastRow.end()) || !ranks.emplace(r->rank[i], e.first).second)
+            return fail(db, DRFE_ERR_INVALID, "lmap_set_keyframes: two key frames of the store would have the same rank");
+        ch.assign(r->children + r->child_offsets[i], r->children + r->child_offsets[i + 1]);
+        std::sort(ch.begin(), ch.end());
+        if ((!ch.empty() && ch[0] < 0) || std::adjacent_find(ch.begin(), ch.end()) != ch.end())
+            return fail(db, DRFE_ERR_INVALID, "lmap_set_keyframes: a child is negative or named twice");
+    }
+    for (const auto& e : lastRow) {
+        const auto old = db->kf.find(e.first);
+        if (old != db->kf.end()) db->rankOwner.erase(old->second.rank);
+    }
+    for (const auto& e : lastRow) {
+        const int i = e.second;
+        KfRow& K = db->kf[e.first];
+        K.rank = r->rank[i];
+        K.bad = r->bad[i] ? 1 : 0;
+        K.parent = r->parent[i];
+        std::memcpy(K.nbr, r->neighbours + (size_t)i * LMAP_NEIGHBOURS, sizeof(K.nbr));
+        K.children.assign(r->children + r->child_offsets[i], r->children + r->child_offsets[i + 1]);
+        K.mps.assign(r->points + r->point_offsets[i], r->points + r->point_offsets[i + 1]);
+        K.mls.assign(r->lines + r->line_offsets[i], r->lines + r->line_offsets[i + 1]);
+        db->rankOwner[K.rank] = e.first;
+    }
+    db->imgDirty = true;
+    return DRFE_OK;
+}
+
+int drfe_lmap_set_points(drfe_lmap* db, int32_t count, const int32_t* handles, const uint8_t* bad, const int32_t* obs_offsets, const int32_t* obs)
+{
+    if (!db) return DRFE_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(db->mu);
+    if (count < 0) return fail(db, DRFE_ERR_INVALID, "lmap_set_points: invalid argument");
+    if (count == 0) return DRFE_OK;
+    if (!handles || !bad || !offsets_ok(obs_offsets, count) || (obs_offsets[count] > 0 && !obs))
+        return fail(db, DRFE_ERR_INVALID, "lmap_set_points: invalid argument");
+    std::vector<int32_t> row;
+    for (int i = 0; i < count; i++) {
+        if (handles[i] < 0) return fail(db, DRFE_ERR_INVALID, "lmap_set_points: a negative handle");
+        row.assign(obs + obs_offsets[i], obs + obs_offsets[i + 1]);
+        std::sort(row.begin(), row.end());
+        if (!row.empty() && row[0] < 0) return fail(db, DRFE_ERR_INVALID, "lmap_set_points: a negative observation");
+        if (std::adjacent_find(row.begin(), row.end()) != row.end())
+            return fail(db, DRFE_ERR_INVALID, "lmap_set_points: a key frame observes a point twice");
+    }
+    for (int i = 0; i < count; i++) {
+        MpRow& P = db->mp[handles[i]];
+        P.bad = bad[i] ? 1 : 0;
+        P.obs.assign(obs + obs_offsets[i], obs + obs_offsets[i + 1]);
+    }
+    db->imgDirty = true;
+    return DRFE_OK;
+}
+
+int drfe_lmap_set_lines(drfe_lmap* db, int32_t count, const int32_t* handles, const uint8_t* bad)
+{
+    if (!db) return DRFE_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(db->mu);
+    if (count < 0 || (count > 0 && (!handles || !bad))) return fail(db, DRFE_ERR_INVALID, "lmap_set_lines: invalid argument");
+    for (int i = 0; i < count; i++)
+        if (handles[i] < 0) return fail(db, DRFE_ERR_INVALID, "lmap_set_lines: a negative handle");
+    for (int i = 0; i < count; i++) db->ml[handles[i]] = bad[i] ? 1 : 0;
+    if (count) db->imgDirty = true;
+    return DRFE_OK;
+}
+
+int drfe_lmap_set_bad(drfe_lmap* db, int kind, int32_t count, const int32_t* handles, const uint8_t* flags)
+{
+    if (!db) return DRFE_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(db->mu);
+    if (count < 0 || (count > 0 && (!handles || !flags))) return fail(db, DRFE_ERR_INVALID, "lmap_set_bad: invalid argument");
+    Image& G = db->img;
+    if (kind == DRFE_LMAP_KEYFRAME) return set_bad(db, db->kf, G.kfSlot, G.kfBad, count, handles, flags, kf_bad);
+    if (kind == DRFE_LMAP_POINT) return set_bad(db, db->mp, G.mpSlot, G.mpBad, count, handles, flags, mp_bad);
+    if (kind == DRFE_LMAP_LINE) return set_bad(db, db->ml, G.mlSlot, G.mlBad, count, handles, flags, ml_bad);
+    return fail(db, DRFE_ERR_INVALID, "lmap_set_bad: unknown kind");
+}
+
+int drfe_lmap_remove(drfe_lmap* db, int kind, int32_t handle)
+{
+    if (!db) return DRFE_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(db->mu);
+    size_t gone = 0;
+    if (kind == DRFE_LMAP_KEYFRAME) {
+        const auto it = db->kf.find(handle);
+        if (it != db->kf.end()) {
+            db->rankOwner.erase(it->second.rank);
+            db->kf.erase(it);
+            gone = 1;
+        }
+    } else if (kind == DRFE_LMAP_POINT) {
+        gone = db->mp.erase(handle);
+    } else if (kind == DRFE_LMAP_LINE) {
+        gone = db->ml.erase(handle);
+    } else {
+        return fail(db, DRFE_ERR_INVALID, "lmap_remove: unknown kind");
+    }
+    if (!gone) return fail(db, DRFE_ERR_INVALID, "lmap_remove: unknown handle");
+    db->imgDirty = true;
+    return DRFE_OK;
+}
+
+int drfe_lmap_size(drfe_lmap* db, int32_t* out3)
+{
+    if (!db || !out3) return DRFE_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(db->mu);
+    out3[0] = (int32_t)db->kf.size();
+    out3[1] = (int32_t)db->mp.size();
+    out3[2] = (int32_t)db->ml.size();
+    return DRFE_OK;
+}
+
+int drfe_lmap_update_host(drfe_lmap* db, const drfe_lmap_queries* q, drfe_lmap_out* o) { return entry(db, q, o, 0, nullptr); }
+int drfe_lmap_update_device(drfe_lmap* db, const drfe_lmap_queries* q, drfe_lmap_out* o, void* stream) { return entry(db, q, o, 1, stream); }
+int drfe_lmap_update_batch(drfe_lmap* db, const drfe_lmap_queries* q, drfe_lmap_out* o, void* stream) { return entry(db, q, o, 2, stream); }
+
+int drfe_lmap_stats(drfe_lmap* db, int64_t* stats)
+{
+    if (!db || !stats) return DRFE_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(db->mu);
+    std::memcpy(stats, db->stats, sizeof(db->stats));
+    return DRFE_OK;
+}
+
+}  // extern "C"

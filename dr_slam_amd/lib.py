@@ -66,6 +66,9 @@ SYMBOLS = (
     "drfe_kfdb_clear", "drfe_kfdb_remove", "drfe_kfdb_set_neighbours", "drfe_kfdb_size", "drfe_kfdb_loop_queries_host",
     "drfe_kfdb_loop_queries_device", "drfe_kfdb_loop_queries_batch", "drfe_kfdb_reloc_queries_host",
     "drfe_kfdb_reloc_queries_device", "drfe_kfdb_reloc_queries_batch", "drfe_kfdb_score", "drfe_kfdb_stats",
+    "drfe_lmap_create", "drfe_lmap_destroy", "drfe_lmap_last_error", "drfe_lmap_configure", "drfe_lmap_limits",
+    "drfe_lmap_set_keyframes", "drfe_lmap_set_points", "drfe_lmap_set_lines", "drfe_lmap_set_bad", "drfe_lmap_remove",
+    "drfe_lmap_size", "drfe_lmap_update_host", "drfe_lmap_update_device", "drfe_lmap_update_batch", "drfe_lmap_stats",
 )
 
 FAST_CELL_DTYPE = np.dtype([(n, "<i4") for n in ("level", "x0", "y0", "ww", "wh", "offX", "offY", "cellIdx", "ncp", "rpl", "nrb",
@@ -256,6 +259,32 @@ class KfdbRelocQueries(C.Structure):
 class KfdbOut(C.Structure):
     _fields_ = [("cand_capacity", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_void_p) for k in (
         "cand_offsets", "candidates", "record", "min_score", "uninit_reads")]        # drfe_kfdb_out
+
+
+LMAP_NEIGHBOURS = 10
+LMAP_KEYFRAME, LMAP_POINT, LMAP_LINE = range(3)                                      # the kinds of drfe_lmap_set_bad / _remove
+LMAP_STATS = ("calls", "queries", "device_calls", "uploads", "local_kfs", "local_points", "local_lines", "nulled")
+LMAP_LIMITS = ("lds_keyframes", "vote_threads", "gather_entries", "device_from")
+
+
+class LmapKeyframes(C.Structure):
+    _fields_ = [("count", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "handle", "rank", "bad", "parent", "neighbours", "child_offsets", "children", "point_offsets", "points",
+        "line_offsets", "lines")]                                                    # drfe_lmap_keyframes
+
+
+class LmapQueries(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "frame_id", "point_offsets", "points", "line_offsets", "lines", "prev_kf_offsets", "prev_kfs")]   # drfe_lmap_queries
+
+
+LMAP_OUT_FIELDS = ("kf_offsets", "kfs", "ref_kf", "mp_offsets", "mps", "mp_in_frame", "ml_offsets", "mls", "ml_in_frame",
+                   "nulled_offsets", "nulled", "record")
+
+
+class LmapOut(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("kf_capacity", "mp_capacity", "ml_capacity", "nulled_capacity")] + [
+        (k, C.c_void_p) for k in LMAP_OUT_FIELDS]                                    # drfe_lmap_out
 
 
 class InitProblems(C.Structure):
@@ -506,6 +535,23 @@ def load() -> C.CDLL:
         getattr(L, f"drfe_kfdb_{kind}_queries_batch").argtypes = [vp, vp, vp, vp]
     L.drfe_kfdb_score.argtypes = [i32, vp, vp, i32, vp, vp, vp]
     L.drfe_kfdb_stats.argtypes = [vp, vp]
+    L.drfe_lmap_create.argtypes = [vp, C.POINTER(vp)]
+    L.drfe_lmap_destroy.argtypes = [vp]
+    L.drfe_lmap_destroy.restype = None
+    L.drfe_lmap_last_error.argtypes = [vp]
+    L.drfe_lmap_last_error.restype = C.c_char_p
+    L.drfe_lmap_configure.argtypes = [vp, C.c_int64]
+    L.drfe_lmap_limits.argtypes = [vp]
+    L.drfe_lmap_set_keyframes.argtypes = [vp, vp]
+    L.drfe_lmap_set_points.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.drfe_lmap_set_lines.argtypes = [vp, i32, vp, vp]
+    L.drfe_lmap_set_bad.argtypes = [vp, i32, i32, vp, vp]
+    L.drfe_lmap_remove.argtypes = [vp, i32, i32]
+    L.drfe_lmap_size.argtypes = [vp, vp]
+    L.drfe_lmap_update_host.argtypes = [vp, vp, vp]
+    L.drfe_lmap_update_device.argtypes = [vp, vp, vp, vp]
+    L.drfe_lmap_update_batch.argtypes = [vp, vp, vp, vp]
+    L.drfe_lmap_stats.argtypes = [vp, vp]
     L.drfe_pnp_stats.argtypes = [vp, vp]
     L.drfe_lines_is_good_batch.argtypes = [vp, vp, vp, vp]
     L.drfe_line3d_chunk_frames.argtypes = [i32]
@@ -1536,6 +1582,134 @@ class KeyFrameDatabase:
                                     np.float64)
         Q = KfdbRelocQueries(n, 0, _p(ident), _p(off), _p(ids), _p(vals))
         return self._run("reloc", Q, n, mode, capacity)
+
+
+class LocalMap:
+    """drfe_lmap (DESIGN.md section 25): the part of the map graph Tracking::UpdateLocalMap reads, and that function for every frame
+    of a call.  ctx None = host-only; with a Context, mode "device" runs a call on its GPU and "batch" by the crossover.  A failing
+    call raises DrfeError with .rc."""
+
+    def __init__(self, ctx=None):
+        self.L = load()
+        self.ctx = ctx                                  # keeps the context alive
+        h = C.c_void_p()
+        rc = self.L.drfe_lmap_create(ctx.h if ctx is not None else None, C.byref(h))
+        if rc != 0:
+            e = DrfeError(f"drfe_lmap_create failed ({rc})")
+            e.rc = rc
+            raise e
+        self.h = h
+
+    def _chk(self, rc, what):
+        if rc != 0:
+            e = DrfeError(f"{what} failed ({rc}): {self.L.drfe_lmap_last_error(self.h).decode()}")
+            e.rc = rc
+            raise e
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.drfe_lmap_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    @staticmethod
+    def limits():
+        out = np.zeros(4, np.int32)
+        rc = load().drfe_lmap_limits(_p(out))
+        if rc != 0:
+            raise DrfeError(f"drfe_lmap_limits failed ({rc})")
+        return dict(zip(LMAP_LIMITS, (int(v) for v in out)))
+
+    def configure(self, scratch_bytes):
+        self._chk(self.L.drfe_lmap_configure(self.h, int(scratch_bytes)), "drfe_lmap_configure")
+
+    def set_keyframes(self, rows):
+        """rows: dicts with handle, rank, and optionally bad, parent (-1), neighbours (at most 10 handles, padded with -1 here),
+        children, points, lines (handles by keypoint index, -1 = null)"""
+        n = len(rows)
+        handle = np.array([r["handle"] for r in rows], np.int32)
+        rank = np.array([r["rank"] for r in rows], np.uint64)
+        bad = np.array([1 if r.get("bad") else 0 for r in rows], np.uint8)
+        parent = np.array([r.get("parent", -1) for r in rows], np.int32)
+        nbr = np.full((n, LMAP_NEIGHBOURS), -1, np.int32)
+        for i, r in enumerate(rows):
+            row = np.asarray(r.get("neighbours", ()), np.int32).reshape(-1)[:LMAP_NEIGHBOURS]
+            nbr[i, :len(row)] = row
+        coff, ch = _csr_i32([r.get("children", ()) for r in rows])
+        poff, pts = _csr_i32([r.get("points", ()) for r in rows])
+        loff, lns = _csr_i32([r.get("lines", ()) for r in rows])
+        K = LmapKeyframes(n, 0, _p(handle), _p(rank), _p(bad), _p(parent), _p(nbr), _p(coff), _p(ch), _p(poff), _p(pts), _p(loff),
+                          _p(lns))
+        self._chk(self.L.drfe_lmap_set_keyframes(self.h, C.byref(K)), "drfe_lmap_set_keyframes")
+
+    def set_points(self, rows):
+        """rows: dicts with handle, and optionally bad and obs (the key-frame handles of GetObservations())"""
+        handle = np.array([r["handle"] for r in rows], np.int32)
+        bad = np.array([1 if r.get("bad") else 0 for r in rows], np.uint8)
+        off, obs = _csr_i32([r.get("obs", ()) for r in rows])
+        self._chk(self.L.drfe_lmap_set_points(self.h, len(rows), _p(handle), _p(bad), _p(off), _p(obs)), "drfe_lmap_set_points")
+
+    def set_lines(self, handles, bad=None):
+        hs = np.ascontiguousarray(handles, np.int32)
+        b = np.zeros(len(hs), np.uint8) if bad is None else np.ascontiguousarray(bad, np.uint8)
+        self._chk(self.L.drfe_lmap_set_lines(self.h, len(hs), _p(hs), _p(b)), "drfe_lmap_set_lines")
+
+    def set_bad(self, kind, handles, flags):
+        hs = np.ascontiguousarray(handles, np.int32)
+        b = np.ascontiguousarray(flags, np.uint8)
+        assert hs.shape == b.shape
+        self._chk(self.L.drfe_lmap_set_bad(self.h, int(kind), len(hs), _p(hs), _p(b)), "drfe_lmap_set_bad")
+
+    def remove(self, kind, handle):
+        self._chk(self.L.drfe_lmap_remove(self.h, int(kind), int(handle)), "drfe_lmap_remove")
+
+    def size(self):
+        out = np.zeros(3, np.int32)
+        self._chk(self.L.drfe_lmap_size(self.h, _p(out)), "drfe_lmap_size")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def stats(self):
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_lmap_stats(self.h, _p(st)), "drfe_lmap_stats")
+        return dict(zip(LMAP_STATS, (int(v) for v in st)))
+
+    def update(self, queries, mode="batch", capacity=None):
+        """UpdateLocalMap of every frame: dicts with frame_id, points (handles by keypoint index, -1 = null) and optionally lines
+        and prev_kfs.  Returns a dict: kfs, mps, mp_in_frame, mls, ml_in_frame, nulled (one array per query), ref_kf [n] and
+        record [n, 4].  capacity: (kf, mp, ml, nulled), default the bounds of drfe_lmap_size."""
+        n = len(queries)
+        ident = np.array([q["frame_id"] for q in queries], np.int64)
+        poff, pts = _csr_i32([q.get("points", ()) for q in queries])
+        has_l = any("lines" in q for q in queries)
+        has_v = any("prev_kfs" in q for q in queries)
+        loff, lns = _csr_i32([q.get("lines", ()) for q in queries]) if has_l else (None, None)
+        voff, prev = _csr_i32([q.get("prev_kfs", ()) for q in queries]) if has_v else (None, None)
+        if capacity is None:
+            nk, npt, nl = self.size()
+            capacity = (n * nk + (len(prev) if has_v else 0), n * npt, n * nl, len(pts))
+        ckf, cmp_, cml, cnu = (int(c) for c in capacity)
+        r = {"kf_offsets": np.zeros(n + 1, np.int32), "kfs": np.zeros(max(1, ckf), np.int32), "ref_kf": np.zeros(n, np.int32),
+             "mp_offsets": np.zeros(n + 1, np.int32), "mps": np.zeros(max(1, cmp_), np.int32),
+             "mp_in_frame": np.zeros(max(1, cmp_), np.uint8), "ml_offsets": np.zeros(n + 1, np.int32),
+             "mls": np.zeros(max(1, cml), np.int32), "ml_in_frame": np.zeros(max(1, cml), np.uint8),
+             "nulled_offsets": np.zeros(n + 1, np.int32), "nulled": np.zeros(max(1, cnu), np.int32),
+             "record": np.zeros((n, 4), np.int32)}
+        Q = LmapQueries(n, 0, _p(ident), _p(poff), _p(pts), _p(loff), _p(lns), _p(voff), _p(prev))
+        out = LmapOut(ckf, cmp_, cml, cnu, *[_p(r[k]) for k in LMAP_OUT_FIELDS])
+        fn = getattr(self.L, f"drfe_lmap_update_{mode}")
+        args = (self.h, C.byref(Q), C.byref(out)) + (() if mode == "host" else (None,))
+        self._chk(fn(*args), f"drfe_lmap_update_{mode}")
+        res = {"ref_kf": r["ref_kf"], "record": r["record"]}
+        for name, off in (("kfs", "kf_offsets"), ("mps", "mp_offsets"), ("mp_in_frame", "mp_offsets"), ("mls", "ml_offsets"),
+                          ("ml_in_frame", "ml_offsets"), ("nulled", "nulled_offsets")):
+            o = r[off]
+            res[name] = [r[name][o[k]:o[k + 1]].copy() for k in range(n)]
+        return res
 
 
 class Shard:

@@ -1588,6 +1588,108 @@ int drfe_kfdb_score(int32_t na, const int32_t* ids_a, const double* values_a, in
  * reads. */
 int drfe_kfdb_stats(drfe_kfdb* db, int64_t* stats /* 8 */);
 
+/* Tracking::UpdateLocalMap (src/Tracking.cc:3383-3541): UpdateLocalKeyFrames, UpdateLocalPoints and UpdateLocalLines of every frame
+ * of a call at once, the step of TrackLocalMap in front of drfe_frame_is_in_frustum, the map projection searches and
+ * drfe_pose_opt_batch.  DESIGN.md section 25.
+ *
+ * A drfe_lmap is an object of its own, like a drfe_kfdb: created with a context (which must outlive it) it can run calls on that
+ * context's device, created with NULL it is host-only; it owns a mutex that every entry takes.  It stores the part of the map
+ * graph that the three functions read.  Per key frame: rank (the reference walks map<KeyFrame*, int> and set<KeyFrame*> in pointer
+ * order; rank is that order, distinct within a store; the adaptor passes the pointer value), bad, parent, the 10 handles of
+ * GetBestCovisibilityKeyFrames(10), the children (ordered by rank by the store), mvpMapPoints and mvpMapLines as handles by
+ * keypoint index.  Per map point: bad and the key frames of GetObservations().  Per map line: bad.  Handles are the caller's
+ * (>= 0, one space per kind; the adaptor uses mnId), -1 is null.  A set_* may name handles that are not stored yet; a query on a
+ * store in which an observation, neighbour, child, parent or match names an unknown handle fails with DRFE_ERR_STATE, its message
+ * names the reference, and it changes nothing.
+ *
+ * Kept from the reference: a bad frame point does not vote and is reported as nulled; a point that is in the frame twice votes
+ * twice; bad key frames count in keyframeCounter but are never listed and never pKFmax; pKFmax by strict > in rank order from
+ * max = 0; an empty counter returns early (the list stays prev_kfs, ref_kf -1, the gathers still run on it); the expansion walks
+ * only the key frames the vote listed, tests size() > 80 at the top of each iteration, takes per key frame the first neighbour
+ * that is neither bad nor listed, the first such child in rank order, then the parent (no bad test), and the parent's break ends
+ * the whole expansion; the gathers walk the list in order, bad key frames included, matches in index order, skip null, listed and
+ * bad items, and list an item where it is first met.  Parity with a build of the reference's Tracking.cc is not pinned. */
+typedef struct drfe_lmap drfe_lmap;
+enum { DRFE_LMAP_NEIGHBOURS = 10, DRFE_LMAP_MAX_QUERIES = 4096 };
+enum { DRFE_LMAP_KEYFRAME = 0, DRFE_LMAP_POINT = 1, DRFE_LMAP_LINE = 2 };
+/* queries in a call from which drfe_lmap_update_batch of a store with a context uses the device (the measured crossover, DESIGN.md
+ * section 25, profiles/lmap_timing.jsonl: a call of one query loses to the host on a store of 100 key frames) */
+enum { DRFE_LMAP_DEVICE_FROM = 4 };
+int drfe_lmap_create(drfe_ctx* ctx /* or NULL */, drfe_lmap** out);
+void drfe_lmap_destroy(drfe_lmap* db);
+const char* drfe_lmap_last_error(const drfe_lmap* db);
+/* bytes of device scratch a call may use (> 0; the default is 1 GiB).  A call that needs more runs in chunks of queries; when
+ * one query does not fit, _device refuses with DRFE_ERR_CAPACITY and _batch runs the call on the host. */
+int drfe_lmap_configure(drfe_lmap* db, int64_t scratch_bytes);
+/* out[0] stored key frames up to which the vote's histogram is in LDS, [1] workgroup size of the vote, [2] entries of a key frame's
+ * match row that one pass of a gather workgroup takes, [3] DRFE_LMAP_DEVICE_FROM */
+int drfe_lmap_limits(int32_t* out4);
+typedef struct drfe_lmap_keyframes {
+    int32_t count;                    /* rows; a row replaces the stored one of its handle (the last row of a handle wins) */
+    int32_t pad;
+    const int32_t* handle;            /* count */
+    const uint64_t* rank;             /* count */
+    const uint8_t* bad;               /* count */
+    const int32_t* parent;            /* count: handle or -1 */
+    const int32_t* neighbours;        /* count x 10 handles in the reference's order, padded with -1 */
+    const int32_t* child_offsets;     /* count + 1, [0] == 0 */
+    const int32_t* children;          /* handles, in any order */
+    const int32_t* point_offsets;     /* count + 1: mvpMapPoints by keypoint index, -1 = null */
+    const int32_t* points;
+    const int32_t* line_offsets;      /* count + 1: mvpMapLines */
+    const int32_t* lines;
+} drfe_lmap_keyframes;
+int drfe_lmap_set_keyframes(drfe_lmap* db, const drfe_lmap_keyframes* rows);
+/* map points: bad and the key-frame handles of GetObservations() (a duplicate within a row is refused) */
+int drfe_lmap_set_points(drfe_lmap* db, int32_t count, const int32_t* handles, const uint8_t* bad, const int32_t* obs_offsets,
+                         const int32_t* obs);
+int drfe_lmap_set_lines(drfe_lmap* db, int32_t count, const int32_t* handles, const uint8_t* bad);
+/* the cheap edit: the bad flags of stored items of one kind (an unknown handle: DRFE_ERR_INVALID, nothing changed) */
+int drfe_lmap_set_bad(drfe_lmap* db, int kind, int32_t count, const int32_t* handles, const uint8_t* flags);
+int drfe_lmap_remove(drfe_lmap* db, int kind, int32_t handle);
+/* out3: stored key frames, map points, map lines.  For a call of n queries, n x key frames + all prev_kfs entries, n x map
+ * points, n x map lines and all frame points always suffice as kf / mp / ml / nulled capacities. */
+int drfe_lmap_size(drfe_lmap* db, int32_t* out3);
+
+typedef struct drfe_lmap_queries {
+    int32_t n;                        /* frames; each behaves as the reference's UpdateLocalMap of that frame on this graph */
+    int32_t pad;
+    const int64_t* frame_id;          /* n: mCurrentFrame.mnId; nonzero and strictly greater than the last id used on this store */
+    const int32_t* point_offsets;     /* n + 1, [0] == 0 */
+    const int32_t* points;            /* mCurrentFrame.mvpMapPoints by keypoint index, -1 = null */
+    const int32_t* line_offsets;      /* n + 1 or NULL: mCurrentFrame.mvpMapLines, read only for ml_in_frame */
+    const int32_t* lines;
+    const int32_t* prev_kf_offsets;   /* n + 1 or NULL: mvpLocalKeyFrames as the previous frame left it */
+    const int32_t* prev_kfs;
+} drfe_lmap_queries;
+typedef struct drfe_lmap_out {
+    int32_t kf_capacity, mp_capacity, ml_capacity, nulled_capacity;   /* DRFE_ERR_CAPACITY when one is too small; nothing changes */
+    int32_t* kf_offsets;              /* n + 1 */
+    int32_t* kfs;                     /* mvpLocalKeyFrames, in the reference's order */
+    int32_t* ref_kf;                  /* n: pKFmax, or -1 = mpReferenceKF unchanged */
+    int32_t* mp_offsets;              /* n + 1 */
+    int32_t* mps;                     /* mvpLocalMapPoints */
+    uint8_t* mp_in_frame;             /* per local point: 1 = one of the frame's remaining map points (the ones the first loop of
+                                         SearchLocalPoints, src/Tracking.cc:3278-3290, stamps with mnLastFrameSeen) */
+    int32_t* ml_offsets;              /* n + 1 */
+    int32_t* mls;                     /* mvpLocalMapLines */
+    uint8_t* ml_in_frame;
+    int32_t* nulled_offsets;          /* n + 1 */
+    int32_t* nulled;                  /* keypoint indices whose map point was bad (set to NULL at src/Tracking.cc:3459), ascending */
+    int32_t* record;                  /* n x 4: size of keyframeCounter, local key frames after the vote loop, key frames added by
+                                         the expansion loop, votes of pKFmax */
+} drfe_lmap_out;
+/* _host always runs on the host, _device always on the device (DRFE_ERR_STATE without a context), _batch on the device from
+ * DRFE_LMAP_DEVICE_FROM queries.  All three return the same bytes.  What the setters changed since the last device call is sent
+ * before the next one (counted in stats[3]); then one staging block goes up, the offsets and records come back, then exactly
+ * the lists.  `stream` NULL = the context's. */
+int drfe_lmap_update_host(drfe_lmap* db, const drfe_lmap_queries* q, drfe_lmap_out* out);
+int drfe_lmap_update_device(drfe_lmap* db, const drfe_lmap_queries* q, drfe_lmap_out* out, void* stream);
+int drfe_lmap_update_batch(drfe_lmap* db, const drfe_lmap_queries* q, drfe_lmap_out* out, void* stream);
+/* Counters since the store was created: stats[0] calls, [1] queries, [2] calls run on the device, [3] uploads of the image,
+ * [4] local key frames returned, [5] local points returned, [6] local lines returned, [7] frame points nulled. */
+int drfe_lmap_stats(drfe_lmap* db, int64_t* stats /* 8 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

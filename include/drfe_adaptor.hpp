@@ -3321,6 +3321,191 @@ private:
     std::vector<int32_t> mUninit, mRecord;
 };
 
+/* Tracking::UpdateLocalMap (src/Tracking.cc:3383-3541) over drfe_lmap: what UpdateLocalKeyFrames,
+ * UpdateLocalPoints and UpdateLocalLines leave, for one frame or for every frame of a batched tracker in one call.  The store holds
+ * a copy of the graph: Sync(pKF) / Sync(pMP) / Sync(pML) read an object's accessors again (after KeyFrame::UpdateConnections,
+ * AddMapPoint, AddObservation, SetBadFlag, ...), Forget drops a culled one.  Handles are the objects' mnId (one space per class),
+ * a key frame's rank is its address: the order in which the reference walks map<KeyFrame*, int> and set<KeyFrame*>.  A query on a
+ * store in which some reference names an object that was never synced throws with the store's message.
+ * `device` < 0 (the default) is a host-only store; with a device, a call of DRFE_LMAP_DEVICE_FROM frames or more runs there.
+ * KeyFrameT: mnId, mnTrackReferenceForFrame, isBad(), GetParent(), GetChilds(), GetBestCovisibilityKeyFrames(int),
+ * GetMapPointMatches(), GetMapLineMatches().  MapPointT: mnId, mnTrackReferenceForFrame, isBad(), GetObservations() (iterable
+ * pairs whose first is a KeyFrameT*).  MapLineT: mnId, mnTrackReferenceForFrame, isBad().  FrameT: mnId, mvpMapPoints,
+ * mvpMapLines, mpReferenceKF. */
+template <class KeyFrameT, class MapPointT, class MapLineT, class FrameT>
+class LocalMapTracker {
+public:
+    /* what UpdateLocalMap leaves for one frame.  kfs goes in as mvpLocalKeyFrames of the previous frame (kept when no point of the
+     * frame votes).  mpInFrame / mlInFrame: 1 for a local point / line that the frame itself holds, which SearchLocalPoints /
+     * SearchLocalLines stamp with mnLastFrameSeen instead of projecting. */
+    struct Local {
+        std::vector<KeyFrameT*> kfs;
+        std::vector<MapPointT*> mps;
+        std::vector<MapLineT*> mls;
+        std::vector<uint8_t> mpInFrame, mlInFrame;
+        KeyFrameT* ref = nullptr;          /* pKFmax, or nullptr: mpReferenceKF stays */
+        int32_t record[4] = {0, 0, 0, 0};
+    };
+
+    explicit LocalMapTracker(int device = -1)
+    {
+        if (device >= 0) mCtx = drfe_detail::make_ctx(1, 1.2f, 1, 20, 7, 64, 64, 1, device);
+        if (drfe_lmap_create(mCtx.get(), &mDb) != DRFE_OK) throw std::runtime_error("drfe_lmap_create failed");
+    }
+    ~LocalMapTracker() { drfe_lmap_destroy(mDb); }
+    LocalMapTracker(const LocalMapTracker&) = delete;
+    LocalMapTracker& operator=(const LocalMapTracker&) = delete;
+    /* true / false: the device / the host entry whatever the number of frames (the device needs `device` >= 0) */
+    void UseDevice(bool on) { mForce = on ? 1 : -1; }
+
+    void Sync(KeyFrameT* pKF)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const int32_t handle = (int32_t)pKF->mnId;
+        const uint64_t rank = (uint64_t)reinterpret_cast<uintptr_t>(pKF);
+        const uint8_t bad = pKF->isBad() ? 1 : 0;
+        KeyFrameT* pParent = pKF->GetParent();
+        const int32_t parent = pParent ? (int32_t)pParent->mnId : -1;
+        int32_t nbr[DRFE_LMAP_NEIGHBOURS];
+        const auto vNeighs = pKF->GetBestCovisibilityKeyFrames(DRFE_LMAP_NEIGHBOURS);
+        for (size_t k = 0; k < (size_t)DRFE_LMAP_NEIGHBOURS; k++) nbr[k] = k < vNeighs.size() ? (int32_t)vNeighs[k]->mnId : -1;
+        std::vector<int32_t> children, points, lines;
+        for (KeyFrameT* c : pKF->GetChilds()) children.push_back((int32_t)c->mnId);
+        for (MapPointT* p : pKF->GetMapPointMatches()) points.push_back(p ? (int32_t)p->mnId : -1);
+        for (MapLineT* l : pKF->GetMapLineMatches()) lines.push_back(l ? (int32_t)l->mnId : -1);
+        const int32_t cOff[2] = {0, (int32_t)children.size()}, pOff[2] = {0, (int32_t)points.size()}, lOff[2] = {0, (int32_t)lines.size()};
+        drfe_lmap_keyframes r = {};
+        r.count = 1;
+        r.handle = &handle; r.rank = &rank; r.bad = &bad; r.parent = &parent; r.neighbours = nbr;
+        r.child_offsets = cOff; r.children = children.data(); r.point_offsets = pOff; r.points = points.data();
+        r.line_offsets = lOff; r.lines = lines.data();
+        Check(drfe_lmap_set_keyframes(mDb, &r), "drfe_lmap_set_keyframes");
+        mKFs[handle] = pKF;
+    }
+    void Sync(MapPointT* pMP)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const int32_t handle = (int32_t)pMP->mnId;
+        const uint8_t bad = pMP->isBad() ? 1 : 0;
+        std::vector<int32_t> obs;
+        for (const auto& o : pMP->GetObservations()) obs.push_back((int32_t)o.first->mnId);
+        const int32_t off[2] = {0, (int32_t)obs.size()};
+        Check(drfe_lmap_set_points(mDb, 1, &handle, &bad, off, obs.data()), "drfe_lmap_set_points");
+        mMPs[handle] = pMP;
+    }
+    void Sync(MapLineT* pML)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const int32_t handle = (int32_t)pML->mnId;
+        const uint8_t bad = pML->isBad() ? 1 : 0;
+        Check(drfe_lmap_set_lines(mDb, 1, &handle, &bad), "drfe_lmap_set_lines");
+        mMLs[handle] = pML;
+    }
+    /* a culled object; one the store never met is left alone */
+    void Forget(KeyFrameT* pKF) { Drop(mKFs, DRFE_LMAP_KEYFRAME, (int32_t)pKF->mnId); }
+    void Forget(MapPointT* pMP) { Drop(mMPs, DRFE_LMAP_POINT, (int32_t)pMP->mnId); }
+    void Forget(MapLineT* pML) { Drop(mMLs, DRFE_LMAP_LINE, (int32_t)pML->mnId); }
+
+    /* Tracking::UpdateLocalMap for mCurrentFrame: the three vectors are Tracking's mvpLocalKeyFrames, mvpLocalMapPoints and
+     * mvpLocalMapLines, refKF its mpReferenceKF */
+    void UpdateLocalMap(FrameT& F, std::vector<KeyFrameT*>& localKFs, std::vector<MapPointT*>& localMPs, std::vector<MapLineT*>& localMLs,
+                        KeyFrameT*& refKF)
+    {
+        std::vector<Local> one(1);
+        one[0].kfs.swap(localKFs);
+        UpdateLocalMap(std::vector<FrameT*>(1, &F), one);
+        localKFs.swap(one[0].kfs);
+        localMPs.swap(one[0].mps);
+        localMLs.swap(one[0].mls);
+        if (one[0].ref) refKF = one[0].ref;
+    }
+    /* every frame of a batched tracker in one call (mnId ascending), each with its own tracker's lists */
+    void UpdateLocalMap(const std::vector<FrameT*>& frames, std::vector<Local>& locals)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const size_t n = frames.size();
+        if (locals.size() != n) throw std::runtime_error("LocalMapTracker: one Local per frame");
+        std::vector<int64_t> id(n);
+        std::vector<int32_t> pOff(1, 0), pts, lOff(1, 0), lns, vOff(1, 0), prev;
+        for (size_t k = 0; k < n; k++) {
+            id[k] = (int64_t)frames[k]->mnId;
+            for (MapPointT* p : frames[k]->mvpMapPoints) pts.push_back(p ? (int32_t)p->mnId : -1);
+            for (MapLineT* l : frames[k]->mvpMapLines) lns.push_back(l ? (int32_t)l->mnId : -1);
+            for (KeyFrameT* kf : locals[k].kfs) prev.push_back((int32_t)kf->mnId);
+            pOff.push_back((int32_t)pts.size());
+            lOff.push_back((int32_t)lns.size());
+            vOff.push_back((int32_t)prev.size());
+        }
+        int32_t size[3] = {0, 0, 0};
+        Check(drfe_lmap_size(mDb, size), "drfe_lmap_size");
+        std::vector<int32_t> kfOff(n + 1), mpOff(n + 1), mlOff(n + 1), nuOff(n + 1), ref(n), rec(4 * n);
+        std::vector<int32_t> kfs(n * (size_t)size[0] + prev.size() + 1), mps(n * (size_t)size[1] + 1), mls(n * (size_t)size[2] + 1), nulled(pts.size() + 1);
+        std::vector<uint8_t> mpIn(mps.size()), mlIn(mls.size());
+        drfe_lmap_queries q = {};
+        q.n = (int32_t)n;
+        q.frame_id = id.data(); q.point_offsets = pOff.data(); q.points = pts.data(); q.line_offsets = lOff.data(); q.lines = lns.data();
+        q.prev_kf_offsets = vOff.data(); q.prev_kfs = prev.data();
+        drfe_lmap_out o = {};
+        o.kf_capacity = (int32_t)kfs.size(); o.mp_capacity = (int32_t)mps.size(); o.ml_capacity = (int32_t)mls.size();
+        o.nulled_capacity = (int32_t)nulled.size();
+        o.kf_offsets = kfOff.data(); o.kfs = kfs.data(); o.ref_kf = ref.data(); o.mp_offsets = mpOff.data(); o.mps = mps.data();
+        o.mp_in_frame = mpIn.data(); o.ml_offsets = mlOff.data(); o.mls = mls.data(); o.ml_in_frame = mlIn.data();
+        o.nulled_offsets = nuOff.data(); o.nulled = nulled.data(); o.record = rec.data();
+        Check(mForce < 0 ? drfe_lmap_update_host(mDb, &q, &o)
+            : mForce > 0 ? drfe_lmap_update_device(mDb, &q, &o, nullptr) : drfe_lmap_update_batch(mDb, &q, &o, nullptr), "drfe_lmap_update");
+        for (size_t k = 0; k < n; k++) {
+            FrameT& F = *frames[k];
+            Local& L = locals[k];
+            const auto fid = F.mnId;
+            for (int32_t i = nuOff[k]; i < nuOff[k + 1]; i++) F.mvpMapPoints[(size_t)nulled[(size_t)i]] = nullptr;
+            L.kfs.clear(); L.mps.clear(); L.mls.clear();
+            for (int f = 0; f < 4; f++) L.record[f] = rec[4 * k + (size_t)f];
+            /* the early return stamps no key frame: the list is the previous frame's */
+            const bool voted = L.record[0] > 0;
+            for (int32_t i = kfOff[k]; i < kfOff[k + 1]; i++) {
+                KeyFrameT* pKF = mKFs.at(kfs[(size_t)i]);
+                L.kfs.push_back(pKF);
+                if (voted) pKF->mnTrackReferenceForFrame = fid;
+            }
+            for (int32_t i = mpOff[k]; i < mpOff[k + 1]; i++) {
+                MapPointT* pMP = mMPs.at(mps[(size_t)i]);
+                L.mps.push_back(pMP);
+                pMP->mnTrackReferenceForFrame = fid;
+            }
+            for (int32_t i = mlOff[k]; i < mlOff[k + 1]; i++) {
+                MapLineT* pML = mMLs.at(mls[(size_t)i]);
+                L.mls.push_back(pML);
+                pML->mnTrackReferenceForFrame = fid;
+            }
+            L.mpInFrame.assign(mpIn.begin() + mpOff[k], mpIn.begin() + mpOff[k + 1]);
+            L.mlInFrame.assign(mlIn.begin() + mlOff[k], mlIn.begin() + mlOff[k + 1]);
+            L.ref = ref[k] >= 0 ? mKFs.at(ref[k]) : nullptr;
+            if (L.ref) F.mpReferenceKF = L.ref;
+        }
+    }
+    drfe_lmap* db() const { return mDb; }
+
+private:
+    void Check(int rc, const char* what) const
+    {
+        if (rc != DRFE_OK) throw std::runtime_error(std::string(what) + ": " + drfe_lmap_last_error(mDb));
+    }
+    template <class M> void Drop(M& known, int kind, int32_t handle)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        if (!known.erase(handle)) return;
+        Check(drfe_lmap_remove(mDb, kind, handle), "drfe_lmap_remove");
+    }
+
+    drfe_detail::CtxPtr mCtx;
+    drfe_lmap* mDb = nullptr;
+    int mForce = 0;
+    std::mutex mMutex;
+    std::map<int32_t, KeyFrameT*> mKFs;
+    std::map<int32_t, MapPointT*> mMPs;
+    std::map<int32_t, MapLineT*> mMLs;
+};
+
 }  // namespace Planar_SLAM
 
 #endif /* DRFE_ADAPTOR_HPP */
