@@ -4,6 +4,7 @@
 
 #include "drfe_internal.h"
 #include "lmap_core.h"
+#include "conn_core.h"
 
 /* threads of a workgroup: frame points and key-frame slots go across them in the vote, the entries of a match row in the gather */
 #define LMAP_THREADS 256
@@ -53,5 +54,70 @@ struct LmapLaunch {
     int32_t* packedNulled;         /* ptOff[nQ] */
 };
 hipError_t drfe_launch_lmap(const LmapLaunch& L, hipStream_t s);
+
+/* ---- KeyFrame::UpdateConnections (conn_kernels.hip) ---- */
+/* keys of one tile of the list sort: a workgroup ranks LMAP_THREADS keys against one tile in LDS at a time */
+#define CONN_SORT_TILE LMAP_THREADS
+/* workgroups of the touched-row launches: workgroup b takes the touched key frames b, b + CONN_ROW_GROUPS, ... */
+#define CONN_ROW_GROUPS 256
+
+/* the connection rows of the image, resident next to LmapImage */
+struct ConnImage {
+    const uint8_t* first;          /* nK: first_connection */
+    const int32_t* wOff;           /* nK + 1: the weights rows, ascending slot */
+    const int32_t* wKf;
+    const int32_t* wW;
+    const int32_t* oOff;           /* nK + 1: the ordered rows */
+    const int32_t* oKf;
+    const int32_t* oW;
+};
+
+/* per called key frame: counter size, listed after the fallback, nmax, pKFmax's slot or -1 */
+struct ConnRec {
+    int32_t nC, nL, nmax, best;
+};
+
+/* head words of a call */
+enum { CONN_HEAD_TOUCHED = 0, CONN_HEAD_WEIGHTS, CONN_HEAD_ORDERED, CONN_HEAD_COUNTER, CONN_HEAD_WORDS };
+
+/* One call.  The counter, list and edge-flag regions of called key frame p start at capOff[p]; the host sizes them from the match
+ * rows (a counter has at most one entry per observation of a voting point, and at most nK - 1). */
+struct ConnLaunch {
+    LmapImage I;                   /* resident */
+    ConnImage G;
+    int32_t n;                     /* called key frames */
+    int32_t chunk;                 /* called key frames per vote launch */
+    /* staged */
+    const int32_t* called;         /* n slots, in call order */
+    const int32_t* pos;            /* nK: position in the call or -1 */
+    const int32_t* capOff;         /* n + 1 */
+    /* scratch */
+    int32_t* hist;                 /* chunk x nK, zero before each vote launch; unused while nK <= LMAP_LDS_KFS */
+    int32_t* dense;                /* CONN_ROW_GROUPS x nK; unused while nK <= LMAP_LDS_KFS */
+    int32_t* cntKf;                /* capOff[n]: the counters, ascending slot */
+    int32_t* cntW;
+    uint64_t* lst;                 /* capOff[n]: the listed keys, descending */
+    uint8_t* chg;                  /* capOff[n]: per counter entry 0 not listed, 1 AddConnection without a change, 2 with one */
+    uint8_t* mark;                 /* nK, zero before the launch: touched */
+    int32_t* tMode;                /* nK: per touched key frame, which list it ends with */
+    /* out */
+    ConnRec* rec;                  /* n */
+    int32_t* newParent;            /* n: slot or -1 */
+    int32_t* cntOff;               /* n + 1: offsets of the packed counters */
+    int32_t* head;                 /* CONN_HEAD_WORDS */
+    int32_t* touched;              /* nK: slots, ascending */
+    int32_t* wOff;                 /* nK + 1: offsets of the packed final weights rows */
+    int32_t* oOff;                 /* nK + 1 */
+    int32_t* tParent;              /* nK: per touched key frame */
+    uint8_t* tFirst;               /* nK */
+    int32_t* pkCntKf;              /* capOff[n] */
+    int32_t* pkCntW;
+    int32_t* pkWKf;                /* the host's bound on all final weights rows */
+    int32_t* pkWW;
+    int32_t* pkOKf;                /* the same bound */
+    int32_t* pkOW;
+};
+/* memsets of mark and hist, then every launch, in stream order */
+hipError_t drfe_launch_conn(const ConnLaunch& L, hipStream_t s);
 
 #endif

@@ -69,6 +69,8 @@ SYMBOLS = (
     "drfe_lmap_create", "drfe_lmap_destroy", "drfe_lmap_last_error", "drfe_lmap_configure", "drfe_lmap_limits",
     "drfe_lmap_set_keyframes", "drfe_lmap_set_points", "drfe_lmap_set_lines", "drfe_lmap_set_bad", "drfe_lmap_remove",
     "drfe_lmap_size", "drfe_lmap_update_host", "drfe_lmap_update_device", "drfe_lmap_update_batch", "drfe_lmap_stats",
+    "drfe_lmap_set_connections", "drfe_lmap_get_connections", "drfe_lmap_connect_host", "drfe_lmap_connect_device",
+    "drfe_lmap_connect_batch", "drfe_lmap_connect_limits", "drfe_lmap_connect_stats",
 )
 
 FAST_CELL_DTYPE = np.dtype([(n, "<i4") for n in ("level", "x0", "y0", "ww", "wh", "offX", "offY", "cellIdx", "ncp", "rpl", "nrb",
@@ -285,6 +287,34 @@ LMAP_OUT_FIELDS = ("kf_offsets", "kfs", "ref_kf", "mp_offsets", "mps", "mp_in_fr
 class LmapOut(C.Structure):
     _fields_ = [(k, C.c_int32) for k in ("kf_capacity", "mp_capacity", "ml_capacity", "nulled_capacity")] + [
         (k, C.c_void_p) for k in LMAP_OUT_FIELDS]                                    # drfe_lmap_out
+
+
+LMAP_CONNECT_TH = 15
+LMAP_CONNECT_STATS = ("calls", "keyframes", "device_calls", "counter_entries", "listed", "touched", "first_connections",
+                      "empty_counters")
+LMAP_CONNECT_LIMITS = ("threshold", "device_from", "sort_tile", "row_groups")
+CONN_WEIGHTS, CONN_ORDERED, CONN_PARENT = 1, 2, 4                                    # the bits of drfe_lmap_connect_out.flags
+
+
+class LmapConnections(C.Structure):
+    _fields_ = [("count", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "handle", "first_connection", "weight_offsets", "weight_kfs", "weight_w", "ordered_offsets", "ordered_kfs",
+        "ordered_w")]                                                                # drfe_lmap_connections
+
+
+LMAP_CONN_ROWS_FIELDS = ("weight_offsets", "weight_kfs", "weight_w", "ordered_offsets", "ordered_kfs", "ordered_w", "parent",
+                         "first_connection")
+
+
+class LmapConnRows(C.Structure):
+    _fields_ = [("weights_capacity", C.c_int32), ("ordered_capacity", C.c_int32)] + [
+        (k, C.c_void_p) for k in LMAP_CONN_ROWS_FIELDS]                              # drfe_lmap_conn_rows
+
+
+class LmapConnectOut(C.Structure):
+    _fields_ = [("counter_capacity", C.c_int32), ("touched_capacity", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "counter_offsets", "counter_kfs", "counter_votes", "record", "new_parent", "n_touched", "touched")] + [
+        ("rows", LmapConnRows), ("flags", C.c_void_p)]                               # drfe_lmap_connect_out
 
 
 class InitProblems(C.Structure):
@@ -552,6 +582,13 @@ def load() -> C.CDLL:
     L.drfe_lmap_update_device.argtypes = [vp, vp, vp, vp]
     L.drfe_lmap_update_batch.argtypes = [vp, vp, vp, vp]
     L.drfe_lmap_stats.argtypes = [vp, vp]
+    L.drfe_lmap_set_connections.argtypes = [vp, vp]
+    L.drfe_lmap_get_connections.argtypes = [vp, i32, vp, vp, i32, vp, vp]
+    L.drfe_lmap_connect_host.argtypes = [vp, i32, vp, vp]
+    L.drfe_lmap_connect_device.argtypes = [vp, i32, vp, vp, vp]
+    L.drfe_lmap_connect_batch.argtypes = [vp, i32, vp, vp, vp]
+    L.drfe_lmap_connect_limits.argtypes = [vp]
+    L.drfe_lmap_connect_stats.argtypes = [vp, vp]
     L.drfe_pnp_stats.argtypes = [vp, vp]
     L.drfe_lines_is_good_batch.argtypes = [vp, vp, vp, vp]
     L.drfe_line3d_chunk_frames.argtypes = [i32]
@@ -1709,6 +1746,103 @@ class LocalMap:
                           ("ml_in_frame", "ml_offsets"), ("nulled", "nulled_offsets")):
             o = r[off]
             res[name] = [r[name][o[k]:o[k + 1]].copy() for k in range(n)]
+        return res
+
+    # ---- KeyFrame::UpdateConnections on the store ----
+
+    @staticmethod
+    def connect_limits():
+        out = np.zeros(4, np.int32)
+        rc = load().drfe_lmap_connect_limits(_p(out))
+        if rc != 0:
+            raise DrfeError(f"drfe_lmap_connect_limits failed ({rc})")
+        return dict(zip(LMAP_CONNECT_LIMITS, (int(v) for v in out)))
+
+    def connect_stats(self):
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_lmap_connect_stats(self.h, _p(st)), "drfe_lmap_connect_stats")
+        return dict(zip(LMAP_CONNECT_STATS, (int(v) for v in st)))
+
+    def set_connections(self, rows):
+        """rows: dicts with handle, and optionally first (mbFirstConnection && mnId != 0), weights and ordered: lists of
+        (key-frame handle, weight) pairs - mConnectedKeyFrameWeights in any order, the ordered list in the reference's order"""
+        handle = np.array([r["handle"] for r in rows], np.int32)
+        first = np.array([1 if r.get("first") else 0 for r in rows], np.uint8)
+        woff, wkf = _csr_i32([[p[0] for p in r.get("weights", ())] for r in rows])
+        _, ww = _csr_i32([[p[1] for p in r.get("weights", ())] for r in rows])
+        ooff, okf = _csr_i32([[p[0] for p in r.get("ordered", ())] for r in rows])
+        _, ow = _csr_i32([[p[1] for p in r.get("ordered", ())] for r in rows])
+        K = LmapConnections(len(rows), 0, _p(handle), _p(first), _p(woff), _p(wkf), _p(ww), _p(ooff), _p(okf), _p(ow))
+        self._chk(self.L.drfe_lmap_set_connections(self.h, C.byref(K)), "drfe_lmap_set_connections")
+
+    @staticmethod
+    def _conn_rows(n_rows, cw, co):
+        r = {"weight_offsets": np.zeros(n_rows + 1, np.int32), "weight_kfs": np.zeros(max(1, cw), np.int32),
+             "weight_w": np.zeros(max(1, cw), np.int32), "ordered_offsets": np.zeros(n_rows + 1, np.int32),
+             "ordered_kfs": np.zeros(max(1, co), np.int32), "ordered_w": np.zeros(max(1, co), np.int32),
+             "parent": np.zeros(max(1, n_rows), np.int32), "first_connection": np.zeros(max(1, n_rows), np.uint8)}
+        return r, LmapConnRows(cw, co, *[_p(r[k]) for k in LMAP_CONN_ROWS_FIELDS])
+
+    @staticmethod
+    def _conn_unpack(r, n):
+        out = {"parent": r["parent"][:n].copy(), "first": r["first_connection"][:n].copy()}
+        for name, off, kf, w in (("weights", "weight_offsets", "weight_kfs", "weight_w"),
+                                 ("ordered", "ordered_offsets", "ordered_kfs", "ordered_w")):
+            o = r[off]
+            out[name] = [np.stack([r[kf][o[k]:o[k + 1]], r[w][o[k]:o[k + 1]]], axis=1) for k in range(n)]
+        return out
+
+    def get_connections(self, handles):
+        """the stored state of the named key frames: dict of parent [n], first [n], weights and ordered (one [m, 2] array of
+        (handle, weight) per key frame; weights in ascending rank) and children (one array per key frame, ascending rank)"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        n = len(hs)
+        cap = 1 << 12
+        while True:
+            r, rows = self._conn_rows(n, cap, cap)
+            coff, ch = np.zeros(n + 1, np.int32), np.zeros(cap, np.int32)
+            rc = self.L.drfe_lmap_get_connections(self.h, n, _p(hs), C.byref(rows), cap, _p(coff), _p(ch))
+            if rc != ERR_CAPACITY:
+                break
+            cap *= 4
+        self._chk(rc, "drfe_lmap_get_connections")
+        out = self._conn_unpack(r, n)
+        out["children"] = [ch[coff[k]:coff[k + 1]].copy() for k in range(n)]
+        return out
+
+    def connect(self, handles, mode="batch", capacity=None):
+        """UpdateConnections of the named key frames, one after another in that order.  Returns a dict: counter (one [m, 2] array of
+        (handle, votes) per called key frame), record [n, 4], new_parent [n]; touched [t] and, per touched key frame, weights,
+        ordered, parent, first, flags.  capacity: (counter, touched, weights, ordered); default: the documented bounds for the
+        first two and arrays grown until the call fits for the others (a call that does not fit changes nothing)."""
+        hs = np.ascontiguousarray(handles, np.int32)
+        n = len(hs)
+        fn = getattr(self.L, f"drfe_lmap_connect_{mode}")
+        grow = capacity is None
+        if grow:
+            nk = self.size()[0]
+            capacity = (n * max(nk - 1, 0), nk, 1 << 14, 1 << 14)
+        cc, ct, cw, co = (int(c) for c in capacity)
+        while True:
+            r, rows = self._conn_rows(ct, cw, co)
+            c = {"counter_offsets": np.zeros(n + 1, np.int32), "counter_kfs": np.zeros(max(1, cc), np.int32),
+                 "counter_votes": np.zeros(max(1, cc), np.int32), "record": np.zeros((n, 4), np.int32),
+                 "new_parent": np.zeros(max(1, n), np.int32), "n_touched": np.zeros(1, np.int32),
+                 "touched": np.zeros(max(1, ct), np.int32), "flags": np.zeros(max(1, ct), np.uint8)}
+            out = LmapConnectOut(cc, ct, _p(c["counter_offsets"]), _p(c["counter_kfs"]), _p(c["counter_votes"]), _p(c["record"]),
+                                 _p(c["new_parent"]), _p(c["n_touched"]), _p(c["touched"]), rows, _p(c["flags"]))
+            args = (self.h, n, _p(hs), C.byref(out)) + (() if mode == "host" else (None,))
+            rc = fn(*args)
+            if not (grow and rc == ERR_CAPACITY and cw < nk * nk):       # nk x nk always suffices: what remains is the scratch budget
+                break
+            cw, co = cw * 8, co * 8
+        self._chk(rc, f"drfe_lmap_connect_{mode}")
+        nt = int(c["n_touched"][0])
+        res = self._conn_unpack(r, nt)
+        o = c["counter_offsets"]
+        res.update(counter=[np.stack([c["counter_kfs"][o[k]:o[k + 1]], c["counter_votes"][o[k]:o[k + 1]]], axis=1) for k in range(n)],
+                   record=c["record"], new_parent=c["new_parent"][:n].copy(), touched=c["touched"][:nt].copy(),
+                   flags=c["flags"][:nt].copy())
         return res
 
 

@@ -1690,6 +1690,92 @@ int drfe_lmap_update_batch(drfe_lmap* db, const drfe_lmap_queries* q, drfe_lmap_
  * [4] local key frames returned, [5] local points returned, [6] local lines returned, [7] frame points nulled. */
 int drfe_lmap_stats(drfe_lmap* db, int64_t* stats /* 8 */);
 
+/* KeyFrame::UpdateConnections (src/KeyFrame.cc:366-500, with AddConnection :200-213 and UpdateBestCovisibles :215-234) of every
+ * key frame of a call, on the same store.  DESIGN.md section 26.
+ *
+ * Per key frame the store holds, besides the rows above, its connection state: first_connection (the caller passes
+ * mbFirstConnection && mnId != 0), the weights row (mConnectedKeyFrameWeights as (handle, weight) pairs, in any order, a handle
+ * once, weight > 0) and the ordered row (mvpOrderedConnectedKeyFrames with mvOrderedWeights, in the reference's order; the store
+ * keeps it as given, because the reference's list cannot be derived from the weights).  A key frame without it has empty rows and
+ * first_connection 0.  drfe_lmap_set_keyframes on a stored handle leaves it alone; drfe_lmap_remove drops it.  An entry that names
+ * an unknown key frame fails the next query with DRFE_ERR_STATE, like every other reference.
+ *
+ * A call names key frames s_0 .. s_{n-1} (at most DRFE_LMAP_MAX_QUERIES), each once (a handle named twice: DRFE_ERR_INVALID), and
+ * gives what the reference's calls made one after another in that order give.  Kept from the reference: an entry of mvpMapPoints that is neither null nor bad adds
+ * a vote to every key frame of its observations but the one whose handle is the called one's; a point that is in the row twice
+ * votes twice; bad key frames are counted, connected and become parents like any other; lines and planes do not vote; an empty
+ * counter changes nothing of the called key frame; pKFmax by strict > in rank order from nmax = 0; every counter entry of at least
+ * DRFE_LMAP_CONNECT_TH votes is listed, or pKFmax alone when none is; each listed key frame gets AddConnection, which sets its
+ * entry and re-sorts ALL of its weights when the entry was absent or different and does nothing otherwise; the called key frame's
+ * weights become the whole counter, its ordered list the listed pairs only, by descending weight and among equal weights by
+ * descending rank; with first_connection set its parent becomes the front of that list (no bad test), the parent gains it as a
+ * child, the flag clears; nothing is ever erased from another key frame's rows. */
+enum { DRFE_LMAP_CONNECT_TH = 15 };
+/* key frames in a call from which drfe_lmap_connect_batch of a store with a context uses the device (the measured crossover,
+ * DESIGN.md section 26, profiles/conn_timing.jsonl: calls of 1 and 4 key frames lose to the host at every measured store size) */
+enum { DRFE_LMAP_CONNECT_DEVICE_FROM = 16 };
+typedef struct drfe_lmap_connections {
+    int32_t count;                    /* rows; a row replaces the stored connection state of its handle (the last row wins) */
+    int32_t pad;
+    const int32_t* handle;            /* count: stored or not yet stored key frames */
+    const uint8_t* first_connection;  /* count */
+    const int32_t* weight_offsets;    /* count + 1, [0] == 0 */
+    const int32_t* weight_kfs;        /* key-frame handles, one mention per row */
+    const int32_t* weight_w;          /* > 0 */
+    const int32_t* ordered_offsets;   /* count + 1 */
+    const int32_t* ordered_kfs;
+    const int32_t* ordered_w;         /* > 0 */
+} drfe_lmap_connections;
+int drfe_lmap_set_connections(drfe_lmap* db, const drfe_lmap_connections* rows);
+/* What drfe_lmap_get_connections and the connect entries fill per key frame.  Weights rows are in ascending rank. */
+typedef struct drfe_lmap_conn_rows {
+    int32_t weights_capacity, ordered_capacity;   /* entries; DRFE_ERR_CAPACITY when one is too small */
+    int32_t* weight_offsets;          /* rows + 1 */
+    int32_t* weight_kfs;
+    int32_t* weight_w;
+    int32_t* ordered_offsets;         /* rows + 1 */
+    int32_t* ordered_kfs;
+    int32_t* ordered_w;
+    int32_t* parent;                  /* rows: handle or -1 */
+    uint8_t* first_connection;        /* rows */
+} drfe_lmap_conn_rows;
+/* the stored state of `count` key frames (an unknown handle: DRFE_ERR_INVALID); `children_*` may be NULL, else the child lists in
+ * ascending rank with their own capacity */
+int drfe_lmap_get_connections(drfe_lmap* db, int32_t count, const int32_t* handles, drfe_lmap_conn_rows* out,
+                              int32_t children_capacity, int32_t* children_offsets, int32_t* children);
+typedef struct drfe_lmap_connect_out {
+    int32_t counter_capacity, touched_capacity;   /* counter entries of the call; touched key frames */
+    /* per called key frame */
+    int32_t* counter_offsets;         /* n + 1 */
+    int32_t* counter_kfs;             /* KFcounter in rank order: GetConnectedKeyFrames() right after its own call */
+    int32_t* counter_votes;
+    int32_t* record;                  /* n x 4: size of the counter, listed key frames after the fallback, nmax, pKFmax or -1 */
+    int32_t* new_parent;              /* n: the parent the first connection set, or -1 */
+    /* per touched key frame (called, or listed by a called one), in ascending rank */
+    int32_t* n_touched;               /* 1 */
+    int32_t* touched;                 /* touched_capacity handles */
+    drfe_lmap_conn_rows rows;         /* the final state; its arrays hold touched_capacity (+ 1) rows */
+    uint8_t* flags;                   /* touched_capacity: bit 0 the weights row, bit 1 the ordered row, bit 2 the parent differs
+                                         from what was stored */
+} drfe_lmap_connect_out;
+/* _host always runs on the host, _device always on the device (DRFE_ERR_STATE without a context; DRFE_ERR_CAPACITY when the call's
+ * counters do not fit the configured scratch), _batch on the device from DRFE_LMAP_CONNECT_DEVICE_FROM key frames when the call
+ * fits.  All three return the same bytes and leave the same store.  When a capacity is too small the call returns
+ * DRFE_ERR_CAPACITY and nothing changes.  On success the call commits: the rows, parent and first_connection of every touched key
+ * frame, its neighbours (the first 10 of its ordered row, padded with -1) when the ordered row changed, and the new parents' child
+ * lists; the next drfe_lmap_update_* reads the new graph.  For a call of n key frames, n x (key frames - 1) counter entries and
+ * min(key frames, n x key frames) touched rows always suffice; a touched row has at most key frames - 1 entries. */
+int drfe_lmap_connect_host(drfe_lmap* db, int32_t n, const int32_t* handles, drfe_lmap_connect_out* out);
+int drfe_lmap_connect_device(drfe_lmap* db, int32_t n, const int32_t* handles, drfe_lmap_connect_out* out, void* stream);
+int drfe_lmap_connect_batch(drfe_lmap* db, int32_t n, const int32_t* handles, drfe_lmap_connect_out* out, void* stream);
+/* out[0] DRFE_LMAP_CONNECT_TH, [1] DRFE_LMAP_CONNECT_DEVICE_FROM, [2] keys of one tile of the device's list sort, [3] workgroups of
+ * the touched-row launch */
+int drfe_lmap_connect_limits(int32_t* out4);
+/* Counters since the store was created: stats[0] connect calls, [1] called key frames, [2] calls run on the device, [3] counter
+ * entries returned, [4] listed key frames (AddConnection calls), [5] touched key frames returned, [6] first connections made,
+ * [7] called key frames with an empty counter. */
+int drfe_lmap_connect_stats(drfe_lmap* db, int64_t* stats /* 8 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

@@ -3483,6 +3483,95 @@ public:
             if (L.ref) F.mpReferenceKF = L.ref;
         }
     }
+    /* KeyFrame::UpdateConnections (src/KeyFrame.cc:366-500) of pKF on the store.  Further accessors of
+     * KeyFrameT: GetConnectedKeyFrames(), GetVectorCovisibleKeyFrames(), GetWeight(KeyFrameT*), AddChild(KeyFrameT*) and one setter
+     * that the integrator adds: SetConnections(const std::map<KeyFrameT*, int>& weights,
+     * const std::vector<KeyFrameT*>& ordered, const std::vector<int>& orderedWeights, KeyFrameT* parent, bool firstConnection).
+     * mbFirstConnection has no accessor: it is read as mnId != 0 && GetParent() == nullptr, which is what it is while the key
+     * frame's parent is only ever set by UpdateConnections and ChangeParent. */
+    /* the connection state of pKF into the store: its weights, its ordered list and mbFirstConnection && mnId != 0.  Call it with
+     * Sync(pKF) when a key frame enters the store, and after anything but UpdateConnections below wrote its connections. */
+    void SyncConnections(KeyFrameT* pKF)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const int32_t handle = (int32_t)pKF->mnId;
+        const uint8_t first = pKF->mnId != 0 && pKF->GetParent() == nullptr ? 1 : 0;
+        std::vector<int32_t> wKf, wW, oKf, oW;
+        for (KeyFrameT* c : pKF->GetConnectedKeyFrames()) {
+            wKf.push_back((int32_t)c->mnId);
+            wW.push_back((int32_t)pKF->GetWeight(c));
+        }
+        for (KeyFrameT* c : pKF->GetVectorCovisibleKeyFrames()) {
+            oKf.push_back((int32_t)c->mnId);
+            oW.push_back((int32_t)pKF->GetWeight(c));
+        }
+        const int32_t wOff[2] = {0, (int32_t)wKf.size()}, oOff[2] = {0, (int32_t)oKf.size()};
+        drfe_lmap_connections c = {};
+        c.count = 1;
+        c.handle = &handle; c.first_connection = &first; c.weight_offsets = wOff; c.weight_kfs = wKf.data(); c.weight_w = wW.data();
+        c.ordered_offsets = oOff; c.ordered_kfs = oKf.data(); c.ordered_w = oW.data();
+        Check(drfe_lmap_set_connections(mDb, &c), "drfe_lmap_set_connections");
+    }
+    void UpdateConnections(KeyFrameT* pKF) { UpdateConnections(std::vector<KeyFrameT*>(1, pKF)); }
+    /* the calls of the reference one after another in this order, in one call of the store: the two loops of
+     * LoopClosing::CorrectLoop.  Each key frame once.  The named key frames' rows and connection state are synced first; every key
+     * frame an edge lands on must be in the store with its current state (SyncConnections; it is current when its connections
+     * were last written by this function).  Returns per named key frame what GetConnectedKeyFrames() gives right after its own call. */
+    std::vector<std::set<KeyFrameT*>> UpdateConnections(const std::vector<KeyFrameT*>& vpKFs)
+    {
+        const size_t n = vpKFs.size();
+        std::vector<int32_t> handles(n);
+        for (size_t k = 0; k < n; k++) {
+            Sync(vpKFs[k]);
+            SyncConnections(vpKFs[k]);
+            handles[k] = (int32_t)vpKFs[k]->mnId;
+        }
+        std::unique_lock<std::mutex> lock(mMutex);
+        int32_t size[3] = {0, 0, 0};
+        Check(drfe_lmap_size(mDb, size), "drfe_lmap_size");
+        const size_t nK = (size_t)size[0];
+        std::vector<int32_t> cOff(n + 1), cKf(n * nK + 1), cVotes(n * nK + 1), rec(4 * n + 1), newParent(n + 1), touched(nK + 1), parent(nK + 1);
+        std::vector<int32_t> rwOff(nK + 2), roOff(nK + 2), rwKf, rwW, roKf, roW;
+        std::vector<uint8_t> rFirst(nK + 1), flags(nK + 1);
+        int32_t nTouched = 0;
+        /* a touched row has at most nK - 1 entries, but nK rows of them are rarely needed: grow until the call fits (a call that
+         * does not fit changes nothing) */
+        for (size_t cap = 64 * (n + 16) + 1024;; cap *= 4) {
+            rwKf.resize(cap); rwW.resize(cap); roKf.resize(cap); roW.resize(cap);
+            drfe_lmap_connect_out o = {};
+            o.counter_capacity = (int32_t)(n * nK); o.touched_capacity = (int32_t)nK;
+            o.counter_offsets = cOff.data(); o.counter_kfs = cKf.data(); o.counter_votes = cVotes.data(); o.record = rec.data();
+            o.new_parent = newParent.data(); o.n_touched = &nTouched; o.touched = touched.data(); o.flags = flags.data();
+            o.rows.weights_capacity = o.rows.ordered_capacity = (int32_t)cap;
+            o.rows.weight_offsets = rwOff.data(); o.rows.weight_kfs = rwKf.data(); o.rows.weight_w = rwW.data();
+            o.rows.ordered_offsets = roOff.data(); o.rows.ordered_kfs = roKf.data(); o.rows.ordered_w = roW.data();
+            o.rows.parent = parent.data(); o.rows.first_connection = rFirst.data();
+            const int rc = mForce < 0 ? drfe_lmap_connect_host(mDb, (int32_t)n, handles.data(), &o)
+                         : mForce > 0 ? drfe_lmap_connect_device(mDb, (int32_t)n, handles.data(), &o, nullptr)
+                                      : drfe_lmap_connect_batch(mDb, (int32_t)n, handles.data(), &o, nullptr);
+            if (rc == DRFE_ERR_CAPACITY && cap < nK * nK) continue;      /* nK x nK always suffices: what remains is the scratch budget */
+            Check(rc, "drfe_lmap_connect");
+            break;
+        }
+        for (int32_t t = 0; t < nTouched; t++) {
+            KeyFrameT* pKF = mKFs.at(touched[(size_t)t]);
+            std::map<KeyFrameT*, int> weights;
+            std::vector<KeyFrameT*> ordered;
+            std::vector<int> orderedWeights;
+            for (int32_t i = rwOff[(size_t)t]; i < rwOff[(size_t)t + 1]; i++) weights[mKFs.at(rwKf[(size_t)i])] = rwW[(size_t)i];
+            for (int32_t i = roOff[(size_t)t]; i < roOff[(size_t)t + 1]; i++) {
+                ordered.push_back(mKFs.at(roKf[(size_t)i]));
+                orderedWeights.push_back(roW[(size_t)i]);
+            }
+            pKF->SetConnections(weights, ordered, orderedWeights, parent[(size_t)t] >= 0 ? mKFs.at(parent[(size_t)t]) : nullptr, rFirst[(size_t)t] != 0);
+        }
+        std::vector<std::set<KeyFrameT*>> connected(n);
+        for (size_t k = 0; k < n; k++) {
+            if (newParent[k] >= 0) mKFs.at(newParent[k])->AddChild(vpKFs[k]);
+            for (int32_t i = cOff[k]; i < cOff[k + 1]; i++) connected[k].insert(mKFs.at(cKf[(size_t)i]));
+        }
+        return connected;
+    }
     drfe_lmap* db() const { return mDb; }
 
 private:
