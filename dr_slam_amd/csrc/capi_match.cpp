@@ -2,6 +2,7 @@
 #include "drfe_internal.h"
 #include "match_internal.h"
 #include "stage_layout.h"
+#include "kf_pose_core.h"
 #include "../../include/drfe_math.h"
 
 #include <algorithm>
@@ -116,16 +117,6 @@ static hipError_t call_scratch(drfe_ctx* c, size_t bytes, uint8_t** out)
     }
     *out = c->d_callScratch;
     return hipSuccess;
-}
-
-/* KeyFrame::GetCameraCenter(): Ow = -Rwc*tcw with Rwc = Rcw.t() stored first (KeyFrame::SetPose, src/KeyFrame.cc:153-154), so
- * the product has no transpose flag and cv::gemm takes its small-matrix float path: float dot, then * alpha = -1 */
-static void camera_centre_kf(const float* Tcw, float Ow[3])
-{
-    for (int i = 0; i < 3; i++) {
-        const float d = Tcw[0 * 4 + i] * Tcw[3] + Tcw[1 * 4 + i] * Tcw[7] + Tcw[2 * 4 + i] * Tcw[11];
-        Ow[i] = (float)((double)d * -1.0);
-    }
 }
 
 template <class In, class Out, class Launch>

@@ -1,8 +1,10 @@
 /* lmap.cpp — Tracking::UpdateLocalMap (reference src/Tracking.cc:3383-3541) behind the C-ABI of include/drfe.h: the store of the
  * graph the three functions read, its flat image, the argument checks, the host walk, the device entry (lmap_kernels.hip) and the
  * counters.  Both sides read the same image and evaluate lmap_core.h.  A call is checked as a whole and committed only when its
- * results fit the caller's arrays.  DESIGN.md section 25. */
-#include "lmap_internal.h"
+ * results fit the caller's arrays.  DESIGN.md section 25.  On the same store: KeyFrame::UpdateConnections (section 26) here, and
+ * the Sim3 propagation of LoopClosing::CorrectLoop with the geometry it reads in lmap_correct.cpp (section 27); lmap_store.h is
+ * the store they share. */
+#include "lmap_store.h"
 #include "stage_layout.h"
 
 static_assert(CONN_TH == DRFE_LMAP_CONNECT_TH, "the vote threshold of conn_core.h is the header's");
@@ -10,64 +12,10 @@ static_assert(CONN_TH == DRFE_LMAP_CONNECT_TH, "the vote threshold of conn_core.
 #include <algorithm>
 #include <cstring>
 #include <map>
-#include <mutex>
-#include <string>
-#include <unordered_map>
-#include <vector>
+
+using namespace lmap_store;
 
 namespace {
-
-struct KfRow {
-    uint64_t rank = 0;
-    uint8_t bad = 0;
-    int32_t parent = -1;
-    int32_t nbr[LMAP_NEIGHBOURS];
-    std::vector<int32_t> children, mps, mls;   /* handles */
-};
-
-/* mbFirstConnection && mnId != 0, mConnectedKeyFrameWeights and the ordered list of one key frame, by handle */
-struct ConnRow {
-    uint8_t first = 0;
-    std::vector<int32_t> wKf, wW, oKf, oW;
-};
-
-struct MpRow {
-    uint8_t bad = 0;
-    std::vector<int32_t> obs;                  /* key-frame handles */
-};
-
-/* the graph with every handle resolved to a slot: what the host walk and the kernels read */
-struct Image {
-    std::vector<int32_t> kfHandle, mpHandle, mlHandle;   /* by slot */
-    std::unordered_map<int32_t, int32_t> kfSlot, mpSlot, mlSlot;
-    std::vector<uint8_t> kfBad, mpBad, mlBad;
-    std::vector<int32_t> kfParent, kfNbr, childOff, child, kfMpOff, kfMp, kfMlOff, kfMl, obsOff, obs;
-    int32_t maxRow[2] = {0, 0};
-    /* the connection rows: weights in ascending slot, the ordered list as stored */
-    std::vector<uint8_t> kfFirst;
-    std::vector<int32_t> cwOff, cwKf, cwW, coOff, coKf, coW;
-    LmapImage view() const
-    {
-        LmapImage I;
-        I.nK = (int32_t)kfHandle.size();
-        I.nP = (int32_t)mpHandle.size();
-        I.nL = (int32_t)mlHandle.size();
-        I.kfBad = kfBad.data();
-        I.kfParent = kfParent.data();
-        I.kfNbr = kfNbr.data();
-        I.childOff = childOff.data();
-        I.child = child.data();
-        I.kfMpOff = kfMpOff.data();
-        I.kfMp = kfMp.data();
-        I.kfMlOff = kfMlOff.data();
-        I.kfMl = kfMl.data();
-        I.mpBad = mpBad.data();
-        I.obsOff = obsOff.data();
-        I.obs = obs.data();
-        I.mlBad = mlBad.data();
-        return I;
-    }
-};
 
 /* a checked call, in slots */
 struct Call {
@@ -88,39 +36,6 @@ struct Result {
         nuOff.assign(1, 0);
     }
 };
-
-}  // namespace
-
-struct drfe_lmap {
-    drfe_ctx* ctx = nullptr;
-    int device = 0;
-    std::mutex mu;
-    std::string err;
-    std::unordered_map<int32_t, KfRow> kf;
-    std::unordered_map<int32_t, MpRow> mp;
-    std::unordered_map<int32_t, uint8_t> ml;
-    std::unordered_map<int32_t, ConnRow> conn;   /* by key-frame handle; a key frame without an entry has empty rows */
-    std::unordered_map<uint64_t, int32_t> rankOwner;
-    Image img;
-    bool imgDirty = true;              /* the image lacks an edit of the rows */
-    bool devDirty = true, devBadDirty = true;   /* the device copy lacks the image / its bad flags */
-    bool devGraphDirty = true;         /* the device copy lacks what a connect call committed */
-    int64_t lastId = 0;
-    int64_t scratchBytes = (int64_t)1 << 30;
-    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int64_t connStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    /* the host walk's stamps, kept between calls: an item is stamped for the query whose serial it holds */
-    std::vector<int32_t> stampP, stampL, inP, inL;
-    int32_t serial = 0;
-    DevBuf<char> dImg, dGraph;
-    LmapImage dView;
-    ConnImage dConn;
-    StagePair io;
-    DevBuf<char> scratch;
-    PinnedBuf<char> hup, hgraph, hlist;
-};
-
-namespace {
 
 int fail(drfe_lmap* db, int rc, const std::string& why)
 {
@@ -268,6 +183,7 @@ int build_image(drfe_lmap* db)
     db->img = std::move(G);
     db->imgDirty = false;
     db->devDirty = true;
+    db->geoDirty = true;               /* the slots may have moved */
     return DRFE_OK;
 }
 
@@ -1264,6 +1180,11 @@ int conn_entry(drfe_lmap* db, int32_t n, const int32_t* handles, drfe_lmap_conne
 
 }  // namespace
 
+/* what lmap_correct.cpp shares (lmap_store.h) */
+int lmap_fail(drfe_lmap* db, int rc, const std::string& why) { return fail(db, rc, why); }
+int lmap_build_image(drfe_lmap* db) { return build_image(db); }
+int lmap_upload_image(drfe_lmap* db, hipStream_t st) { return upload_image(db, st); }
+
 extern "C" {
 
 int drfe_lmap_create(drfe_ctx* ctx, drfe_lmap** out)
@@ -1274,6 +1195,7 @@ int drfe_lmap_create(drfe_ctx* ctx, drfe_lmap** out)
     if (ctx) db->device = ctx->device;
     db->dView = LmapImage{};
     db->dConn = ConnImage{};
+    db->dCorr = CorrImage{};
     *out = db;
     return DRFE_OK;
 }
@@ -1419,10 +1341,12 @@ int drfe_lmap_remove(drfe_lmap* db, int kind, int32_t handle)
             db->rankOwner.erase(it->second.rank);
             db->kf.erase(it);
             db->conn.erase(handle);
+            db->kfPose.erase(handle);
             gone = 1;
         }
     } else if (kind == DRFE_LMAP_POINT) {
         gone = db->mp.erase(handle);
+        if (gone) db->mpGeo.erase(handle);
     } else if (kind == DRFE_LMAP_LINE) {
         gone = db->ml.erase(handle);
     } else {
@@ -1571,5 +1495,4 @@ int drfe_lmap_connect_stats(drfe_lmap* db, int64_t* stats)
     std::memcpy(stats, db->connStats, sizeof(db->connStats));
     return DRFE_OK;
 }
-
 }  // extern "C"

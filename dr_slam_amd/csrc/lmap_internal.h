@@ -1,10 +1,11 @@
-/* lmap_internal.h — what lmap.cpp hands to lmap_kernels.hip. */
+/* lmap_internal.h — what lmap.cpp and lmap_correct.cpp hand to the store's kernels (DESIGN.md sections 25 to 27). */
 #ifndef DRFE_LMAP_INTERNAL_H
 #define DRFE_LMAP_INTERNAL_H
 
 #include "drfe_internal.h"
 #include "lmap_core.h"
 #include "conn_core.h"
+#include "correct_core.h"
 
 /* threads of a workgroup: frame points and key-frame slots go across them in the vote, the entries of a match row in the gather */
 #define LMAP_THREADS 256
@@ -119,5 +120,49 @@ struct ConnLaunch {
 };
 /* memsets of mark and hist, then every launch, in stream order */
 hipError_t drfe_launch_conn(const ConnLaunch& L, hipStream_t s);
+
+/* ---- LoopClosing::CorrectLoop's Sim3 propagation (correct_kernels.hip) ---- */
+/* entries of a called key frame's match row that one claim workgroup takes, and one pass of a move workgroup */
+#define CORRECT_TILE LMAP_THREADS
+/* bytes of scratch per entry of a chunk's match rows: the packed record of a moved point (41 bytes), rounded up */
+#define CORRECT_ENTRY_BYTES 48
+
+/* One call.  Positions 0 .. n are the called key frames in rank order.  The plan launches fill kf, cnt and off for the whole call;
+ * a chunk is the positions [j0, j1), whose moved points go to the packed arrays from 0 and into the image. */
+struct CorrLaunch {
+    LmapImage I;                   /* resident */
+    CorrImage G;                   /* resident */
+    int32_t n;
+    int32_t cur;                   /* handle of the current key frame: the stamp */
+    int32_t curPos;                /* its position */
+    int32_t rowStride;             /* lmap_walk_rank's stride: above every called row length */
+    int32_t maxRow;                /* the longest called row */
+    int32_t j0, j1;
+    double Scw[8];
+    /* staged */
+    const int32_t* called;         /* n slots by position */
+    const int32_t* calledHandle;   /* n */
+    const int32_t* pos;            /* nK: position or -1 */
+    /* scratch */
+    int32_t* claim;                /* nP: LMAP_NO_CLAIM bytes before the plan */
+    int32_t* cnt;                  /* n: moved points of each position */
+    /* out */
+    CorrKf* kf;                    /* n by position */
+    int32_t* off;                  /* n + 1: exclusive prefix of cnt */
+    /* a chunk's packed records, in walk order */
+    int32_t* pkItem;               /* point slot */
+    int32_t* pkBy;                 /* claiming position */
+    float* pkWorld;                /* 3 each */
+    float* pkNormal;               /* 3 each */
+    float* pkMax;
+    float* pkMin;
+    uint8_t* pkStatus;
+};
+/* poses of every position, the claims, the counts and their prefix */
+hipError_t drfe_launch_correct_plan(const CorrLaunch& L, hipStream_t s);
+/* the moved points of positions [j0, j1): packed, then scattered into the image */
+hipError_t drfe_launch_correct_chunk(const CorrLaunch& L, hipStream_t s);
+/* the new poses and centres into the image: after the last chunk, which still reads the stored ones */
+hipError_t drfe_launch_correct_poses(const CorrLaunch& L, hipStream_t s);
 
 #endif

@@ -1,0 +1,130 @@
+/* lmap_store.h — the local-map store itself: its rows by handle, the flat image of them, the optional geometry and the device
+ * copies, for the two files that implement its entries: lmap.cpp (Tracking::UpdateLocalMap and KeyFrame::UpdateConnections,
+ * DESIGN.md sections 25 and 26) and lmap_correct.cpp (the Sim3 propagation of LoopClosing::CorrectLoop, section 27). */
+#ifndef DRFE_LMAP_STORE_H
+#define DRFE_LMAP_STORE_H
+
+#include "lmap_internal.h"
+
+#include <array>
+#include <mutex>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+namespace lmap_store {
+
+struct KfRow {
+    uint64_t rank = 0;
+    uint8_t bad = 0;
+    int32_t parent = -1;
+    int32_t nbr[LMAP_NEIGHBOURS];
+    std::vector<int32_t> children, mps, mls;   /* handles */
+};
+
+/* mbFirstConnection && mnId != 0, mConnectedKeyFrameWeights and the ordered list of one key frame, by handle */
+struct ConnRow {
+    uint8_t first = 0;
+    std::vector<int32_t> wKf, wW, oKf, oW;
+};
+
+struct MpRow {
+    uint8_t bad = 0;
+    std::vector<int32_t> obs;                  /* key-frame handles */
+};
+
+/* what CorrectLoop reads of a map point: GetWorldPos(), the reference key frame, its octave there and the two stamps */
+struct MpGeo {
+    float X[3] = {0.0f, 0.0f, 0.0f};
+    int32_t ref = -1, level = 0, by = 0, byRef = 0;
+};
+
+/* the geometry by slot, next to the image; has = the item has geometry, complete = no call needs to look for a missing piece */
+struct GeoImage {
+    std::vector<uint8_t> kfHas, mpHas;
+    std::vector<float> kfTcw, kfOw, mpWorld;
+    std::vector<int32_t> mpRef, mpLevel, mpBy, mpByRef;
+    bool complete = false;
+};
+
+/* the graph with every handle resolved to a slot: what the host walk and the kernels read */
+struct Image {
+    std::vector<int32_t> kfHandle, mpHandle, mlHandle;   /* by slot */
+    std::unordered_map<int32_t, int32_t> kfSlot, mpSlot, mlSlot;
+    std::vector<uint8_t> kfBad, mpBad, mlBad;
+    std::vector<int32_t> kfParent, kfNbr, childOff, child, kfMpOff, kfMp, kfMlOff, kfMl, obsOff, obs;
+    int32_t maxRow[2] = {0, 0};
+    /* the connection rows: weights in ascending slot, the ordered list as stored */
+    std::vector<uint8_t> kfFirst;
+    std::vector<int32_t> cwOff, cwKf, cwW, coOff, coKf, coW;
+    LmapImage view() const
+    {
+        LmapImage I;
+        I.nK = (int32_t)kfHandle.size();
+        I.nP = (int32_t)mpHandle.size();
+        I.nL = (int32_t)mlHandle.size();
+        I.kfBad = kfBad.data();
+        I.kfParent = kfParent.data();
+        I.kfNbr = kfNbr.data();
+        I.childOff = childOff.data();
+        I.child = child.data();
+        I.kfMpOff = kfMpOff.data();
+        I.kfMp = kfMp.data();
+        I.kfMlOff = kfMlOff.data();
+        I.kfMl = kfMl.data();
+        I.mpBad = mpBad.data();
+        I.obsOff = obsOff.data();
+        I.obs = obs.data();
+        I.mlBad = mlBad.data();
+        return I;
+    }
+};
+
+}  // namespace lmap_store
+
+struct drfe_lmap {
+    drfe_ctx* ctx = nullptr;
+    int device = 0;
+    std::mutex mu;
+    std::string err;
+    std::unordered_map<int32_t, lmap_store::KfRow> kf;
+    std::unordered_map<int32_t, lmap_store::MpRow> mp;
+    std::unordered_map<int32_t, uint8_t> ml;
+    std::unordered_map<int32_t, lmap_store::ConnRow> conn;   /* by key-frame handle; a key frame without an entry has empty rows */
+    std::unordered_map<uint64_t, int32_t> rankOwner;
+    lmap_store::Image img;
+    bool imgDirty = true;              /* the image lacks an edit of the rows */
+    bool devDirty = true, devBadDirty = true;   /* the device copy lacks the image / its bad flags */
+    bool devGraphDirty = true;         /* the device copy lacks what a connect call committed */
+    int64_t lastId = 0;
+    int64_t scratchBytes = (int64_t)1 << 30;
+    int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t connStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    /* the optional geometry, by handle, and its image by slot */
+    std::unordered_map<int32_t, std::array<float, 16>> kfPose;
+    std::unordered_map<int32_t, lmap_store::MpGeo> mpGeo;
+    std::vector<float> scales;
+    lmap_store::GeoImage geo;
+    bool geoDirty = true;              /* the geometry image lacks an edit of the rows or of the geometry */
+    bool devGeoDirty = true;           /* the device copy lacks the geometry image */
+    int64_t corrStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    DevBuf<char> dGeo;
+    CorrImage dCorr;
+    /* the host walk's stamps, kept between calls: an item is stamped for the query whose serial it holds */
+    std::vector<int32_t> stampP, stampL, inP, inL;
+    int32_t serial = 0;
+    DevBuf<char> dImg, dGraph;
+    LmapImage dView;
+    ConnImage dConn;
+    StagePair io;
+    DevBuf<char> scratch;
+    PinnedBuf<char> hup, hgraph, hlist;
+};
+
+/* lmap.cpp's, for lmap_correct.cpp: the error of a refused call; the image of the rows, rebuilt when an edit made it stale
+ * (DRFE_ERR_STATE and the name of the reference when one dangles); the image on the device, sent when it is stale */
+int lmap_fail(drfe_lmap* db, int rc, const std::string& why);
+int lmap_build_image(drfe_lmap* db);
+int lmap_upload_image(drfe_lmap* db, hipStream_t st);
+
+#endif

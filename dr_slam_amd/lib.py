@@ -71,6 +71,9 @@ SYMBOLS = (
     "drfe_lmap_size", "drfe_lmap_update_host", "drfe_lmap_update_device", "drfe_lmap_update_batch", "drfe_lmap_stats",
     "drfe_lmap_set_connections", "drfe_lmap_get_connections", "drfe_lmap_connect_host", "drfe_lmap_connect_device",
     "drfe_lmap_connect_batch", "drfe_lmap_connect_limits", "drfe_lmap_connect_stats",
+    "drfe_lmap_set_scales", "drfe_lmap_get_scales", "drfe_lmap_set_poses", "drfe_lmap_get_poses",
+    "drfe_lmap_set_point_geometry", "drfe_lmap_get_point_geometry", "drfe_lmap_correct_host", "drfe_lmap_correct_device",
+    "drfe_lmap_correct_batch", "drfe_lmap_correct_limits", "drfe_lmap_correct_scratch", "drfe_lmap_correct_stats",
 )
 
 FAST_CELL_DTYPE = np.dtype([(n, "<i4") for n in ("level", "x0", "y0", "ww", "wh", "offX", "offY", "cellIdx", "ncp", "rpl", "nrb",
@@ -315,6 +318,25 @@ class LmapConnectOut(C.Structure):
     _fields_ = [("counter_capacity", C.c_int32), ("touched_capacity", C.c_int32)] + [(k, C.c_void_p) for k in (
         "counter_offsets", "counter_kfs", "counter_votes", "record", "new_parent", "n_touched", "touched")] + [
         ("rows", LmapConnRows), ("flags", C.c_void_p)]                               # drfe_lmap_connect_out
+
+
+LMAP_CORRECT_STATS = ("calls", "keyframes", "device_calls", "moved", "moved_without_obs", "entries_walked", "device_chunks",
+                      "geometry_uploads")
+LMAP_CORRECT_LIMITS = ("claim_tile", "device_from", "entry_bytes", "threads")
+
+
+class LmapPointGeometry(C.Structure):
+    _fields_ = [("count", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "handle", "world", "ref_kf", "ref_level", "corrected_by", "corrected_ref")]  # drfe_lmap_point_geometry
+
+
+LMAP_CORRECT_OUT_FIELDS = ("walk_pos", "corrected", "non_corrected", "Tiw", "n_points", "points", "claimed_by", "world", "normal",
+                           "max_distance", "min_distance", "status")
+
+
+class LmapCorrectOut(C.Structure):
+    _fields_ = [("points_capacity", C.c_int32), ("pad", C.c_int32)] + [
+        (k, C.c_void_p) for k in LMAP_CORRECT_OUT_FIELDS]                            # drfe_lmap_correct_out
 
 
 class InitProblems(C.Structure):
@@ -589,6 +611,18 @@ def load() -> C.CDLL:
     L.drfe_lmap_connect_batch.argtypes = [vp, i32, vp, vp, vp]
     L.drfe_lmap_connect_limits.argtypes = [vp]
     L.drfe_lmap_connect_stats.argtypes = [vp, vp]
+    L.drfe_lmap_set_scales.argtypes = [vp, i32, vp]
+    L.drfe_lmap_get_scales.argtypes = [vp, i32, vp, vp]
+    L.drfe_lmap_set_poses.argtypes = [vp, i32, vp, vp]
+    L.drfe_lmap_get_poses.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.drfe_lmap_set_point_geometry.argtypes = [vp, vp]
+    L.drfe_lmap_get_point_geometry.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.drfe_lmap_correct_host.argtypes = [vp, i32, vp, i32, vp, vp]
+    L.drfe_lmap_correct_device.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    L.drfe_lmap_correct_batch.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    L.drfe_lmap_correct_limits.argtypes = [vp]
+    L.drfe_lmap_correct_scratch.argtypes = [vp, i32, vp, vp]
+    L.drfe_lmap_correct_stats.argtypes = [vp, vp]
     L.drfe_pnp_stats.argtypes = [vp, vp]
     L.drfe_lines_is_good_batch.argtypes = [vp, vp, vp, vp]
     L.drfe_line3d_chunk_frames.argtypes = [i32]
@@ -1843,6 +1877,109 @@ class LocalMap:
         res.update(counter=[np.stack([c["counter_kfs"][o[k]:o[k + 1]], c["counter_votes"][o[k]:o[k + 1]]], axis=1) for k in range(n)],
                    record=c["record"], new_parent=c["new_parent"][:n].copy(), touched=c["touched"][:nt].copy(),
                    flags=c["flags"][:nt].copy())
+        return res
+
+    # ---- LoopClosing::CorrectLoop's Sim3 propagation on the store ----
+
+    @staticmethod
+    def correct_limits():
+        out = np.zeros(4, np.int32)
+        rc = load().drfe_lmap_correct_limits(_p(out))
+        if rc != 0:
+            raise DrfeError(f"drfe_lmap_correct_limits failed ({rc})")
+        return dict(zip(LMAP_CORRECT_LIMITS, (int(v) for v in out)))
+
+    def correct_stats(self):
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_lmap_correct_stats(self.h, _p(st)), "drfe_lmap_correct_stats")
+        return dict(zip(LMAP_CORRECT_STATS, (int(v) for v in st)))
+
+    def correct_scratch(self, handles):
+        """bytes of device scratch a correct call of these key frames takes: (as one chunk, at least, shared by every chunk)"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        out = np.zeros(3, np.int64)
+        self._chk(self.L.drfe_lmap_correct_scratch(self.h, len(hs), _p(hs), _p(out)), "drfe_lmap_correct_scratch")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def set_scales(self, scale_factors):
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        self._chk(self.L.drfe_lmap_set_scales(self.h, len(sf), _p(sf)), "drfe_lmap_set_scales")
+
+    def get_scales(self):
+        n = np.zeros(1, np.int32)
+        sf = np.zeros(64, np.float32)
+        rc = self.L.drfe_lmap_get_scales(self.h, len(sf), _p(n), _p(sf))
+        if rc == ERR_CAPACITY:
+            sf = np.zeros(int(n[0]), np.float32)
+            rc = self.L.drfe_lmap_get_scales(self.h, len(sf), _p(n), _p(sf))
+        self._chk(rc, "drfe_lmap_get_scales")
+        return sf[:int(n[0])].copy()
+
+    def set_poses(self, handles, Tcw):
+        """Tcw [n, 4, 4] float32, what SetPose received"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        T = np.ascontiguousarray(Tcw, np.float32).reshape(len(hs), 16)
+        self._chk(self.L.drfe_lmap_set_poses(self.h, len(hs), _p(hs), _p(T)), "drfe_lmap_set_poses")
+
+    def get_poses(self, handles):
+        """dict of Tcw [n, 4, 4], Ow [n, 3] and Twc [n, 4, 4] as SetPose derives them"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        n = len(hs)
+        T, O, W = np.zeros((n, 4, 4), np.float32), np.zeros((n, 3), np.float32), np.zeros((n, 4, 4), np.float32)
+        self._chk(self.L.drfe_lmap_get_poses(self.h, n, _p(hs), _p(T), _p(O), _p(W)), "drfe_lmap_get_poses")
+        return {"Tcw": T, "Ow": O, "Twc": W}
+
+    def set_point_geometry(self, rows):
+        """rows: dicts with handle, world (3 floats), ref_kf, and optionally ref_level (0), corrected_by (0), corrected_ref (0)"""
+        n = len(rows)
+        handle = np.array([r["handle"] for r in rows], np.int32)
+        world = np.array([r["world"] for r in rows], np.float32).reshape(n, 3)
+        ref = np.array([r["ref_kf"] for r in rows], np.int32)
+        level = np.array([r.get("ref_level", 0) for r in rows], np.int32)
+        by = np.array([r.get("corrected_by", 0) for r in rows], np.int32)
+        byref = np.array([r.get("corrected_ref", 0) for r in rows], np.int32)
+        G = LmapPointGeometry(n, 0, _p(handle), _p(world), _p(ref), _p(level), _p(by), _p(byref))
+        self._chk(self.L.drfe_lmap_set_point_geometry(self.h, C.byref(G)), "drfe_lmap_set_point_geometry")
+
+    def get_point_geometry(self, handles):
+        """dict of world [n, 3], ref_kf, ref_level, corrected_by, corrected_ref [n]"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        n = len(hs)
+        r = {"world": np.zeros((n, 3), np.float32), "ref_kf": np.zeros(n, np.int32), "ref_level": np.zeros(n, np.int32),
+             "corrected_by": np.zeros(n, np.int32), "corrected_ref": np.zeros(n, np.int32)}
+        self._chk(self.L.drfe_lmap_get_point_geometry(self.h, n, _p(hs), *[_p(v) for v in r.values()]),
+                  "drfe_lmap_get_point_geometry")
+        return r
+
+    def correct(self, cur, Scw, handles, mode="batch", capacity=None):
+        """CorrectLoop's propagation (src/LoopClosing.cc:480-562) for the current key frame `cur`, Scw = (qx, qy, qz, qw, tx, ty, tz,
+        s) and the connected key frames `handles` (cur among them, any order).  Returns a dict: per called key frame, in the
+        caller's order, walk_pos [n], corrected [n, 8], non_corrected [n, 8], Tiw [n, 4, 4]; per moved point, in walk order, points,
+        claimed_by, world [m, 3], normal [m, 3], max_distance, min_distance, status.  capacity: moved points, default the total
+        length of the called match rows (a call that does not fit changes nothing)."""
+        hs = np.ascontiguousarray(handles, np.int32)
+        S = np.ascontiguousarray(Scw, np.float64).reshape(8)
+        n = len(hs)
+        cap = 1 << 12 if capacity is None else int(capacity)
+        fn = getattr(self.L, f"drfe_lmap_correct_{mode}")
+        while True:
+            m = max(1, cap)
+            r = {"walk_pos": np.zeros(max(1, n), np.int32), "corrected": np.zeros((max(1, n), 8), np.float64),
+                 "non_corrected": np.zeros((max(1, n), 8), np.float64), "Tiw": np.zeros((max(1, n), 4, 4), np.float32),
+                 "n_points": np.zeros(1, np.int32), "points": np.zeros(m, np.int32), "claimed_by": np.zeros(m, np.int32),
+                 "world": np.zeros((m, 3), np.float32), "normal": np.zeros((m, 3), np.float32),
+                 "max_distance": np.zeros(m, np.float32), "min_distance": np.zeros(m, np.float32), "status": np.zeros(m, np.uint8)}
+            out = LmapCorrectOut(cap, 0, *[_p(r[k]) for k in LMAP_CORRECT_OUT_FIELDS])
+            args = (self.h, int(cur), _p(S), n, _p(hs), C.byref(out)) + (() if mode == "host" else (None,))
+            rc = fn(*args)
+            if not (capacity is None and rc == ERR_CAPACITY and cap < (1 << 28)
+                    and b"points_capacity" in self.L.drfe_lmap_last_error(self.h)):
+                break
+            cap *= 8
+        self._chk(rc, f"drfe_lmap_correct_{mode}")
+        m = int(r["n_points"][0])
+        res = {k: r[k][:n].copy() for k in ("walk_pos", "corrected", "non_corrected", "Tiw")}
+        res.update({k: r[k][:m].copy() for k in LMAP_CORRECT_OUT_FIELDS[5:]})
         return res
 
 

@@ -1776,6 +1776,98 @@ int drfe_lmap_connect_limits(int32_t* out4);
  * [7] called key frames with an empty counter. */
 int drfe_lmap_connect_stats(drfe_lmap* db, int64_t* stats /* 8 */);
 
+/* LoopClosing::CorrectLoop's Sim3 propagation (src/LoopClosing.cc:480-562) on the same store: the corrected Sim3 of every key frame
+ * connected to the current one, the correction of every map point they see, and the new key-frame poses.  DESIGN.md section 27.
+ *
+ * The geometry it reads is optional; a store without it behaves as before.  Per store: mnScaleLevels and mvScaleFactors.  Per key
+ * frame: Tcw as SetPose last received it; Ow and Twc are derived as SetPose derives them.  Per map point: GetWorldPos(), the
+ * reference key frame, ref_level (the octave of the reference key frame's key point, 0 when the reference key frame is not among
+ * the observations, as in drfe_upkeep_items) and the stamps mnCorrectedByKF / mnCorrectedReference as handles (0 when not given,
+ * as the reference's constructors leave them).  A setter row replaces the stored one, may name a handle that is not stored yet,
+ * and is uploaded before the next device call; drfe_lmap_remove drops the geometry with the item. */
+int drfe_lmap_set_scales(drfe_lmap* db, int32_t n_levels, const float* scale_factors);
+/* *n_levels is set; the factors are written when capacity holds them (DRFE_ERR_CAPACITY otherwise) */
+int drfe_lmap_get_scales(drfe_lmap* db, int32_t capacity, int32_t* n_levels, float* scale_factors);
+int drfe_lmap_set_poses(drfe_lmap* db, int32_t count, const int32_t* handles, const float* Tcw /* 16 each, row-major */);
+/* Tcw, Ow (3 each) and Twc (16 each) of key frames with a pose; each array may be NULL.  A handle without one: DRFE_ERR_INVALID */
+int drfe_lmap_get_poses(drfe_lmap* db, int32_t count, const int32_t* handles, float* Tcw, float* Ow, float* Twc);
+typedef struct drfe_lmap_point_geometry {
+    int32_t count;                    /* rows; the last row of a handle wins */
+    int32_t pad;
+    const int32_t* handle;            /* count */
+    const float* world;               /* 3 each */
+    const int32_t* ref_kf;            /* count: key-frame handle */
+    const int32_t* ref_level;         /* count */
+    const int32_t* corrected_by;      /* count, or NULL = 0 */
+    const int32_t* corrected_ref;     /* count, or NULL = 0 */
+} drfe_lmap_point_geometry;
+int drfe_lmap_set_point_geometry(drfe_lmap* db, const drfe_lmap_point_geometry* rows);
+/* the stored rows; each array may be NULL.  A handle without geometry: DRFE_ERR_INVALID */
+int drfe_lmap_get_point_geometry(drfe_lmap* db, int32_t count, const int32_t* handles, float* world, int32_t* ref_kf,
+                                 int32_t* ref_level, int32_t* corrected_by, int32_t* corrected_ref);
+
+/* A call names cur, the handle of mpCurrentKF; Scw = mg2oScw as double[8] (the quaternion's coeffs x y z w, t, s: the layout of
+ * drfe_sim3_opt_problems::S12); and n handles, GetVectorCovisibleKeyFrames() plus the current key frame, in any order, each once
+ * and cur among them (DRFE_ERR_INVALID otherwise; at most DRFE_LMAP_MAX_QUERIES).
+ *
+ * Kept from the reference.  The called key frames are processed in rank order, the iteration order of KeyFrameAndPose, whatever
+ * order the caller passed.  Per key frame i: NonCorrected = Sim3(Quaterniond(Riw), tiw, 1); for i != cur Tic = Tiw * Twc_cur as a
+ * float 4x4 product, Sic from it and Corrected = Sic * Scw; for cur Corrected = Scw as given; Swi = Corrected.inverse(); the new
+ * pose is toCvSE3(r.toRotationMatrix(), t * (1. / s)).  Each key frame's match row is walked in index order: a null or bad entry
+ * or one with corrected_by == cur is skipped (so with cur == 0 and untouched stamps no point moves), otherwise the point moves to
+ * (float)Swi.map(Siw.map((double)X)) and its stamps become cur and i: a point is moved once, by the first (key frame, index) that
+ * meets it.  UpdateNormalAndDepth of a moved point runs on the new position over its observations in stored order; an observing
+ * or reference key frame counts with its corrected centre exactly when it is a called key frame strictly before the claimant in
+ * rank order, with its stored centre otherwise - the claimant itself included, whose SetPose comes after its points.  A point
+ * without observations still moves; its normal and distances are not computed (status 0, zeros).  Bad key frames are not tested
+ * anywhere; map lines and planes are untouched.
+ *
+ * The integer graph is unchanged, so drfe_lmap_connect_* of the same handles afterwards gives what the reference's interleaved
+ * UpdateConnections calls give, when the handles are passed to it in rank order (ascending walk_pos). */
+typedef struct drfe_lmap_correct_out {
+    int32_t points_capacity;          /* moved points; the total length of the called match rows always suffices */
+    int32_t pad;
+    /* per called key frame, in the caller's order */
+    int32_t* walk_pos;                /* n: its position in rank order among the called */
+    double* corrected;                /* n x 8: CorrectedSim3 */
+    double* non_corrected;            /* n x 8: NonCorrectedSim3 */
+    float* Tiw;                       /* n x 16: the pose SetPose receives */
+    /* per moved point, in walk order */
+    int32_t* n_points;                /* 1 */
+    int32_t* points;                  /* handles */
+    int32_t* claimed_by;              /* the key frame that moved it: mnCorrectedReference */
+    float* world;                     /* 3 each: the new position */
+    float* normal;                    /* 3 each */
+    float* max_distance;
+    float* min_distance;
+    uint8_t* status;                  /* DRFE_UPKEEP_NORMAL when normal and distances were computed, else 0 */
+} drfe_lmap_correct_out;
+/* key frames in a call from which drfe_lmap_correct_batch of a store with a context uses the device (the measured crossover,
+ * DESIGN.md section 27, profiles/loop_correct_timing.jsonl) */
+enum { DRFE_LMAP_CORRECT_DEVICE_FROM = 16 };
+/* _host always runs on the host, _device always on the device (DRFE_ERR_STATE without a context; DRFE_ERR_CAPACITY when the
+ * longest called row does not fit the configured scratch), _batch on the device from DRFE_LMAP_CORRECT_DEVICE_FROM key frames when
+ * the call fits.  All three return the same bytes and leave the same store.  A refused call changes nothing: DRFE_ERR_STATE, with
+ * a message that names the item, when a called key frame, a point the walk would move, one of its observers or its reference key
+ * frame lacks geometry or is unknown, when the scales are missing, or when the ref_level of such a point with observations is
+ * out of range; DRFE_ERR_CAPACITY when points_capacity is too small.  On success the call commits poses, positions and stamps
+ * into the store, and on the device into the resident image in place. */
+int drfe_lmap_correct_host(drfe_lmap* db, int32_t cur, const double* Scw, int32_t n, const int32_t* handles, drfe_lmap_correct_out* out);
+int drfe_lmap_correct_device(drfe_lmap* db, int32_t cur, const double* Scw, int32_t n, const int32_t* handles,
+                             drfe_lmap_correct_out* out, void* stream);
+int drfe_lmap_correct_batch(drfe_lmap* db, int32_t cur, const double* Scw, int32_t n, const int32_t* handles,
+                            drfe_lmap_correct_out* out, void* stream);
+/* out[0] entries of a match row that one claim workgroup takes, [1] DRFE_LMAP_CORRECT_DEVICE_FROM, [2] bytes of scratch per
+ * match-row entry of a chunk, [3] workgroup size */
+int drfe_lmap_correct_limits(int32_t* out4);
+/* the scratch a device call of these handles takes: out[0] bytes with which it runs as one chunk, [1] the least bytes with which
+ * it runs at all (one key frame a chunk), [2] the part every chunk shares */
+int drfe_lmap_correct_scratch(drfe_lmap* db, int32_t n, const int32_t* handles, int64_t* out3);
+/* Counters since the store was created: stats[0] correct calls, [1] called key frames, [2] calls run on the device, [3] points
+ * moved, [4] moved points without observations, [5] match-row entries walked, [6] chunks run on the device, [7] uploads of the
+ * geometry. */
+int drfe_lmap_correct_stats(drfe_lmap* db, int64_t* stats /* 8 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

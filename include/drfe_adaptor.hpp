@@ -3572,6 +3572,101 @@ public:
         }
         return connected;
     }
+
+    /* The Sim3 propagation of LoopClosing::CorrectLoop (src/LoopClosing.cc:480-562) on the store.  Further
+     * accessors of KeyFrameT: GetPose() (4x4 float), SetPose(Mat), mvKeysUn (.octave), mvScaleFactors, mnScaleLevels; of MapPointT:
+     * GetWorldPos() (3x1 float), SetWorldPos(Mat), GetReferenceKeyFrame(), the public mnCorrectedByKF / mnCorrectedReference, and
+     * one setter that the integrator adds because mNormalVector, mfMaxDistance and mfMinDistance are protected (INTEGRATION.md
+     * section 4p): SetNormalAndDepth(const float normal[3], float maxDistance, float minDistance).  Sim3T as for Sim3OptBatch:
+     * default-constructible, rotation() with x() y() z() w(), translation() with operator[], scale(), each writable. */
+    /* the pose SetPose last received, and the store's mvScaleFactors from this key frame */
+    void SyncGeometry(KeyFrameT* pKF)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const int32_t handle = (int32_t)pKF->mnId;
+        float T[16];
+        const auto Tcw = pKF->GetPose();
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++) T[r * 4 + c] = Tcw.template ptr<float>(r)[c];
+        Check(drfe_lmap_set_poses(mDb, 1, &handle, T), "drfe_lmap_set_poses");
+        const std::vector<float> sf(pKF->mvScaleFactors.begin(), pKF->mvScaleFactors.begin() + pKF->mnScaleLevels);
+        Check(drfe_lmap_set_scales(mDb, (int32_t)sf.size(), sf.data()), "drfe_lmap_set_scales");
+    }
+    /* position, reference key frame with the octave of its key point (key point 0 when it does not observe the point) and stamps */
+    void SyncGeometry(MapPointT* pMP)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const int32_t handle = (int32_t)pMP->mnId;
+        float X[3];
+        const auto P = pMP->GetWorldPos();
+        for (int k = 0; k < 3; k++) X[k] = P.template ptr<float>(k)[0];
+        KeyFrameT* pRef = pMP->GetReferenceKeyFrame();
+        const auto observations = pMP->GetObservations();
+        const auto f = observations.find(pRef);
+        const int32_t ref = (int32_t)pRef->mnId;
+        const int32_t level = pRef->mvKeysUn.empty() ? 0 : (int32_t)pRef->mvKeysUn[f == observations.end() ? (size_t)0 : (size_t)f->second].octave;
+        const int32_t by = (int32_t)pMP->mnCorrectedByKF, byRef = (int32_t)pMP->mnCorrectedReference;
+        drfe_lmap_point_geometry g = {};
+        g.count = 1;
+        g.handle = &handle; g.world = X; g.ref_kf = &ref; g.ref_level = &level; g.corrected_by = &by; g.corrected_ref = &byRef;
+        Check(drfe_lmap_set_point_geometry(mDb, &g), "drfe_lmap_set_point_geometry");
+    }
+    /* Lines :480-562 for mpCurrentKF = pCurKF, mg2oScw = g2oScw and mvpCurrentConnectedKFs = vpConnected (pCurKF among them),
+     * without the UpdateConnections calls of its loop: call UpdateConnections(inRankOrder) afterwards, where inRankOrder is the
+     * returned maps' iteration order.  The store must hold the current rows and geometry of the connected key frames, of the
+     * points in their match rows and of those points' observers (Sync, SyncGeometry).  Writes poses, positions, stamps, normals
+     * and distances into the caller's objects and returns CorrectedSim3 and NonCorrectedSim3. */
+    template <class Sim3T>
+    std::pair<std::map<KeyFrameT*, Sim3T>, std::map<KeyFrameT*, Sim3T>> CorrectLoop(KeyFrameT* pCurKF, const Sim3T& g2oScw,
+                                                                                     const std::vector<KeyFrameT*>& vpConnected)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const size_t n = vpConnected.size();
+        std::vector<int32_t> handles(n);
+        size_t cap = 1;
+        for (size_t k = 0; k < n; k++) {
+            handles[k] = (int32_t)vpConnected[k]->mnId;
+            cap += vpConnected[k]->GetMapPointMatches().size();
+        }
+        const auto& q = g2oScw.rotation();
+        const double Scw[8] = {q.x(), q.y(), q.z(), q.w(), g2oScw.translation()[0], g2oScw.translation()[1], g2oScw.translation()[2],
+                               g2oScw.scale()};
+        std::vector<int32_t> walk(n + 1), points(cap), by(cap);
+        std::vector<double> corrected(8 * n + 8), nonCorrected(8 * n + 8);
+        std::vector<float> Tiw(16 * n + 16), world(3 * cap), normal(3 * cap), maxD(cap), minD(cap);
+        std::vector<uint8_t> status(cap);
+        int32_t nPoints = 0;
+        drfe_lmap_correct_out o = {};
+        o.points_capacity = (int32_t)cap;
+        o.walk_pos = walk.data(); o.corrected = corrected.data(); o.non_corrected = nonCorrected.data(); o.Tiw = Tiw.data();
+        o.n_points = &nPoints; o.points = points.data(); o.claimed_by = by.data(); o.world = world.data(); o.normal = normal.data();
+        o.max_distance = maxD.data(); o.min_distance = minD.data(); o.status = status.data();
+        const int32_t cur = (int32_t)pCurKF->mnId;
+        Check(mForce < 0 ? drfe_lmap_correct_host(mDb, cur, Scw, (int32_t)n, handles.data(), &o)
+            : mForce > 0 ? drfe_lmap_correct_device(mDb, cur, Scw, (int32_t)n, handles.data(), &o, nullptr)
+                         : drfe_lmap_correct_batch(mDb, cur, Scw, (int32_t)n, handles.data(), &o, nullptr), "drfe_lmap_correct");
+        using ::drfe::drfe_detail_sim3::mat32;
+        for (int32_t t = 0; t < nPoints; t++) {
+            MapPointT* pMP = mMPs.at(points[(size_t)t]);
+            pMP->SetWorldPos(mat32(3, 1, &world[3 * (size_t)t]));
+            pMP->mnCorrectedByKF = pCurKF->mnId;
+            pMP->mnCorrectedReference = mKFs.at(by[(size_t)t])->mnId;
+            if (status[(size_t)t] & DRFE_UPKEEP_NORMAL) pMP->SetNormalAndDepth(&normal[3 * (size_t)t], maxD[(size_t)t], minD[(size_t)t]);
+        }
+        std::pair<std::map<KeyFrameT*, Sim3T>, std::map<KeyFrameT*, Sim3T>> sims;
+        auto fill = [](Sim3T& S, const double* v) {
+            auto& r = S.rotation();
+            r.x() = v[0]; r.y() = v[1]; r.z() = v[2]; r.w() = v[3];
+            for (int k = 0; k < 3; k++) S.translation()[k] = v[4 + k];
+            S.scale() = v[7];
+        };
+        for (size_t k = 0; k < n; k++) {
+            fill(sims.first[vpConnected[k]], &corrected[8 * k]);
+            fill(sims.second[vpConnected[k]], &nonCorrected[8 * k]);
+            vpConnected[k]->SetPose(mat32(4, 4, &Tiw[16 * k]));
+        }
+        return sims;
+    }
     drfe_lmap* db() const { return mDb; }
 
 private:

@@ -1,0 +1,19 @@
+# loop_correct_asan: loop_correct_caller.cpp with the local-map store's host code compiled into it under AddressSanitizer and
+# UndefinedBehaviorSanitizer, as a program of its own (never loaded into python, never run on a GPU: run it in host mode, where the
+# store has no context).  Not part of build(); run by hand:
+#   make -C tests/native -f loop_correct_asan.mk && tests/native/loop_correct_asan host
+# lmap.cpp and lmap_correct.cpp are compiled into the program with the sanitizers on its host side; the kernel files only satisfy their launch symbols, and
+# libdrfe.so the adaptor's references to the context entries, which host mode never calls.
+ROOT := $(abspath ../..)
+SRC := $(ROOT)/dr_slam_amd/csrc
+HIPCC ?= /opt/rocm/bin/hipcc
+FLAGS := -O1 -g -std=c++17 -ffp-contract=off --offload-arch=gfx950 -Wall -I$(ROOT)/include -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer
+LDFLAGS := -L$(SRC) -ldrfe -Wl,-rpath,'$$ORIGIN/../../dr_slam_amd/csrc' -Wl,-rpath,/opt/rocm/lib
+
+all: loop_correct_asan
+
+loop_correct_asan: loop_correct_caller.cpp $(SRC)/lmap.cpp $(SRC)/lmap_correct.cpp $(SRC)/lmap_store.h $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/correct_kernels.hip $(SRC)/correct_core.h $(SRC)/lmap_internal.h $(ROOT)/include/drfe_adaptor.hpp
+	$(HIPCC) $(FLAGS) -x hip loop_correct_caller.cpp $(SRC)/lmap.cpp $(SRC)/lmap_correct.cpp $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/correct_kernels.hip -o $@ $(LDFLAGS)
+
+clean:
+	rm -f loop_correct_asan
