@@ -73,6 +73,8 @@ static int upload_geometry(drfe_ctx* c, int w, int h)
      * (lastBatch only remembers the highest one) finds zero keypoints instead of another geometry's leftovers */
     HIPCHK(c, hipMemset(c->d_kpCount, 0, sizeof(int) * (size_t)c->cfg.max_batch));
     drfe_bow_slots_invalidate(c, 0, c->cfg.max_batch);
+    drfe_level0_mark_copy(c, 0, c->cfg.max_batch);
+    c->lastInPlace = 0;
     return DRFE_OK;
 }
 
@@ -264,6 +266,10 @@ int drfe_create(const drfe_config* cfg, drfe_ctx** out)
         c->fastGeneric = (e && e[0] == '1') ? 1 : 0;
         const char* es = std::getenv("DRFE_FAST_SCREEN");
         c->fastScreen = (es && es[0] >= '0' && es[0] <= '2') ? es[0] - '0' : 2;     /* 0 never, 1 at minThFAST only (rounds 3-4), 2 at iniThFAST first */
+        const char* el = std::getenv("DRFE_LEVEL0_COPY");
+        c->level0Copy = (el && el[0] == '1') ? 1 : 0;                                /* drfe_orb_configure_level0 */
+        c->lastInPlace = 0;
+        c->level0.assign((size_t)std::max(cfg->max_batch, 1), Level0Record{false, nullptr, 0});
     }
 
     /* size the arenas with the geometry of the largest frame */
@@ -281,7 +287,8 @@ int drfe_create(const drfe_config* cfg, drfe_ctx** out)
     c->maxKp = gmax.kpSlotElems;
     c->cellsCap = (int)cells.size() + 64;
     c->tilesCap = (int)tiles.size() + 64;
-    c->tapsCap = (int)taps.size() + 64;
+    /* + level 1's window origins for an unbordered level 0 (one per block): a smaller frame may have them where the largest has not */
+    c->tapsCap = (int)taps.size() + 64 + (cfg->nlevels >= 2 ? gmax.lv[1].rzBlocks + 64 : 0);
     const int nl = cfg->nlevels;
 
     CHIP(dalloc(&c->d_geom, 1));
@@ -369,12 +376,23 @@ int drfe_orb_extract_batch(drfe_ctx* c, const uint8_t* d_gray, size_t frame_stri
     int rc = upload_geometry(c, w, h);
     if (rc != DRFE_OK) return rc;
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    HIPCHK(c, drfe_launch_orb(c, d_gray, frame_stride, row_stride, nframes, s));
+    HIPCHK(c, drfe_launch_orb(c, d_gray, frame_stride, row_stride, nframes, s, !c->level0Staged));
+    for (int f = 0; f < nframes; f++)
+        c->level0[(size_t)f] = Level0Record{c->lastInPlace != 0, d_gray + (size_t)f * frame_stride, row_stride};
     c->lastBatch = nframes;
     c->glueValid = false;
     drfe_bow_slots_invalidate(c, 0, nframes);         /* new descriptors: the slots' words are stale until transformed again */
     return DRFE_OK;
 }
+
+int drfe_orb_configure_level0(drfe_ctx* c, int in_place)
+{
+    if (!c || (in_place != 0 && in_place != 1)) { if (c) c->err = "drfe_orb_configure_level0: in_place is 0 or 1"; return DRFE_ERR_INVALID; }
+    c->level0Copy = in_place ? 0 : 1;
+    return DRFE_OK;
+}
+
+int drfe_orb_level0_in_place(const drfe_ctx* c) { return c ? c->lastInPlace : DRFE_ERR_INVALID; }
 
 int drfe_stream_sync(drfe_ctx* c)
 {
@@ -615,6 +633,8 @@ int drfe_orb_extract(drfe_ctx* c, const uint8_t* gray, int w, int h, size_t stri
     if (o && o->exec && !o->disabled && !c->profile && o->w == w && o->h == h) {
         for (int y = 0; y < h; y++) std::memcpy(o->h_in + (size_t)y * w, gray + (size_t)y * stride, (size_t)w);
         drfe_bow_slot_invalidate(c, 0);
+        drfe_level0_mark_copy(c, 0, 1);
+        c->lastInPlace = 0;
         HIPCHK(c, hipGraphLaunch(o->exec, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         c->lastBatch = 1;
@@ -632,7 +652,9 @@ int drfe_orb_extract(drfe_ctx* c, const uint8_t* gray, int w, int h, size_t stri
     }
     HIPCHK(c, hipMemcpy2DAsync(c->d_stage, (size_t)w, gray, stride, (size_t)w, (size_t)h, hipMemcpyHostToDevice,
                                c->stream));
+    c->level0Staged = true;                  /* the staging buffer is overwritten by the next upload: level 0 is copied */
     int rc = drfe_orb_extract_batch(c, c->d_stage, (size_t)w * h, (size_t)w, w, h, 1, c->stream);
+    c->level0Staged = false;
     if (rc != DRFE_OK) return rc;
     return drfe_orb_download(c, 0, kps, desc, cap, n_out);
 }
@@ -647,6 +669,13 @@ int drfe_orb_pyramid_level(drfe_ctx* c, int slot, int level, uint8_t* out, int* 
     if (!out) return DRFE_OK;
     int rc = drfe_stream_sync(c);
     if (rc != DRFE_OK) return rc;
+    const Level0Record rec = c->level0[(size_t)slot];
+    if (level == 0 && rec.inPlace) {
+        /* the slot's extraction read level 0 from the caller's image: border it into the arena now, as the copy path would have */
+        SlotShift shift(c, slot);
+        HIPCHK(c, drfe_launch_level0(c, rec.frame, 0, rec.rowStride, 1, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
     HIPCHK(c, hipMemcpy2D(out, (size_t)W, c->d_pyr + (size_t)slot * c->geom.pyrSlotBytes + L.pyrOff, (size_t)L.pyrPitch,
                           (size_t)W, (size_t)H, hipMemcpyDeviceToHost));
     return DRFE_OK;
@@ -924,6 +953,7 @@ static int frame_submit_impl(drfe_ctx* c, int slot, const uint8_t* gray, int w, 
         } else { L.graphOff = true; (void)hipGetLastError(); }
     }
     drfe_bow_slot_invalidate(c, slot);                /* the submission rewrites the slot's descriptors */
+    drfe_level0_mark_copy(c, slot, 1);                /* ... and copies its staged frame into the arena's level 0 */
     if (L.exec && !c->profile) HIPCHK(c, hipGraphLaunch(L.exec, s));
     else HIPCHK(c, frame_enqueue(c, L, slot, w, h, s));
     HIPCHK(c, hipEventRecord(L.done, s));

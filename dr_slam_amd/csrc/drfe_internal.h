@@ -2,7 +2,8 @@
  *
  * One context owns, for `max_batch` frame slots, frame-major arenas:
  *   pyr    bordered pyramid, all levels of a slot contiguous (level l at lv[l].pyrOff, row pitch
- *          lv[l].pyrPitch = align64(w_l + 38))
+ *          lv[l].pyrPitch = align64(w_l + 38)); level 0 of a batch that reads it in place stays in the caller's frames
+ *          and is bordered into its place here only when drfe_orb_pyramid_level asks (level0_view.h)
  *   blur   blurred interior levels (pitch align64(w_l))
  *   cand   FAST candidates per (slot, level): key0 = x | y<<12 | response<<24, key1 = emission-order key
  *   node   quadtree scratch: node id per candidate (u16)
@@ -81,6 +82,13 @@ struct DevGeom {
     int fastCols;                   /* 1: every cell fits k_fast_cells_cols (ew <= 38, rows per lane <= 12) */
     int fastColsSmall;              /* cells [0, fastColsSmall) of the table have rpl <= 8 */
     int fastColsRows;               /* LDS tile rows k_fast_cells_cols touches: max over cells of nrb * rpl + 6 */
+    /* level 0 read in place (level0_view.h).  l0InPlace = the geometry's part of the eligibility: w a multiple of 16, every cell
+     * in k_fast_cells_cols with its in-place alignment, level 1 on the tiled resize with the window plan below - the plan of
+     * plan_resize_tile for an UNBORDERED source: origins in interior coordinates, 16-byte aligned in the caller's rows, never
+     * before column 0 or past w.  The origins sit behind every other table in the tap array. */
+    int l0InPlace;
+    int rz0Rows, rz0Wq, rz0Fill, rz0WinOff;
+    uint32_t rz0WqMagic;
     DevLevel lv[DRFE_MAX_LEVELS];
 };
 
@@ -114,6 +122,11 @@ struct BlurTile { uint16_t tx, ty; uint16_t level, pad; };
 struct ResizeTap { uint16_t s0, s1; int16_t w0, w1; };
 
 #include "undistort_math.h"
+#include "level0_view.h"
+
+/* where a slot's level 0 is: in the arena (inPlace == false), or in the caller's image, which drfe_orb_pyramid_level borders on
+ * demand */
+struct Level0Record { bool inPlace; const uint8_t* frame; size_t rowStride; };
 
 struct drfe_ctx {
     drfe_config cfg;
@@ -153,6 +166,10 @@ struct drfe_ctx {
     int fastScreen;           /* k_fast_cells_cols' screened paths; 2 (default): at iniThFAST first (textured cells), then at minThFAST (low-texture cells); 1: at
                                * minThFAST only; 0: never.  DRFE_FAST_SCREEN in the environment sets it (A/B, tests) */
     int fastGeneric;          /* DRFE_FAST_GENERIC=1 in the environment: run k_fast_cells even where k_fast_cells_cols fits (A/B, tests) */
+    int level0Copy;           /* drfe_orb_configure_level0 / DRFE_LEVEL0_COPY=1: 1 = the batch entry always copies level 0 into the arena */
+    int lastInPlace;          /* 1: the most recent drfe_launch_orb read level 0 in place */
+    bool level0Staged = false; /* drfe_orb_extract's plain path is inside drfe_orb_extract_batch with the context's staging buffer */
+    std::vector<Level0Record> level0;   /* per slot */
 
     /* frame glue + match */
     float* d_uRight; float* d_depth;      /* [slot][maxKp] */
@@ -336,8 +353,12 @@ int drfe_build_geometry(drfe_ctx* c, int w, int h, DevGeom* g, std::vector<FastC
                         std::vector<BlurTile>* tiles, std::vector<ResizeTap>* taps);
 
 /* orb_kernels.hip */
+/* allowInPlace: the frames outlive the call's kernels (drfe_orb_extract_batch), so level 0 may be read from them in place;
+ * sets c->lastInPlace */
 hipError_t drfe_launch_orb(drfe_ctx* c, const uint8_t* d_gray, size_t frameStride, size_t rowStride, int nframes,
-                           hipStream_t s);
+                           hipStream_t s, bool allowInPlace = false);
+/* the two level-0 kernels alone: copyMakeBorder(REFLECT_101) of nframes frames into the arena's level 0 */
+hipError_t drfe_launch_level0(drfe_ctx* c, const uint8_t* d_gray, size_t frameStride, size_t rowStride, int nframes, hipStream_t s);
 /* survivor-list capacity (16-bit entries) of the k_fast_cells_cols<8> and <DRFE_FASTC_MAX_RPL> launches of a geometry */
 void drfe_fastc_list_caps(const DevGeom& g, int caps[2]);
 /* match_kernels.hip */
@@ -347,6 +368,21 @@ hipError_t drfe_launch_grid(drfe_ctx* c, const drfe_camera& cam, int nframes, hi
 hipError_t drfe_launch_kp_pixels(drfe_ctx* c, int nframes, uint32_t* d_uv, hipStream_t s);
 hipError_t drfe_launch_match_consecutive(drfe_ctx* c, const drfe_camera& cam, float th, int mono, int checkOri,
                                          int nframes, hipStream_t s);
+
+/* Whether a batch reads level 0 in place: a pure function of geometry, pointer and strides.  The pointer and both strides are
+ * multiples of 16 (the resize fills 16-byte quads, the blur and the descriptor aligned dwords); the strides keep every offset
+ * inside a frame within the kernels' 24-bit multiplies and 32-bit offsets. */
+static inline bool drfe_level0_in_place_ok(const DevGeom& g, const void* d_gray, size_t frameStride, size_t rowStride)
+{
+    if (!g.l0InPlace || !d_gray) return false;
+    if ((((uintptr_t)d_gray | frameStride | rowStride) & 15) != 0) return false;
+    if (rowStride < (size_t)g.imgW || rowStride > ((size_t)1 << 20) || (size_t)g.imgH * rowStride >= ((size_t)1 << 31)) return false;
+    return true;
+}
+static inline void drfe_level0_mark_copy(drfe_ctx* c, int first, int count)
+{
+    for (int s = first; s < first + count && s < (int)c->level0.size(); s++) c->level0[(size_t)s] = Level0Record{false, nullptr, 0};
+}
 
 #define DRFE_RESIZE_BLOCK 256          /* items (4 x 4 output pixels) per k_pyr_resize_tile block */
 #define DRFE_RESIZE_MAX_FILL 8         /* most 16-byte tile loads per thread (template instances) */

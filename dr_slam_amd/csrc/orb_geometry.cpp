@@ -155,6 +155,54 @@ static void plan_resize_tile(DevLevel& L, const DevLevel& P, std::vector<ResizeT
     }
 }
 
+/* The same tile plan for level 1 when level 0 is the caller's image (level0_view.h): the items and their taps are those of
+ * plan_resize_tile, the source has no border.  Window rows and columns are interior coordinates, the column origin is 16-byte
+ * aligned in the caller's rows (w is a multiple of 16, so pulling a window back from the row's end keeps it aligned), and a
+ * window never starts before column 0 or ends past w: only bytes a tap with a non-zero weight reads are counted (the last
+ * column's second tap has weight 0 and may fall on the tile's spare bytes).  Appended behind every other table: the offsets
+ * of the bordered plan do not move.  false: level 1 cannot run the tile kernel on an unbordered source. */
+static bool plan_resize_tile_raw(DevGeom* g, std::vector<ResizeTap>* taps)
+{
+    const DevLevel& L = g->lv[1];
+    const DevLevel& P = g->lv[0];
+    g->rz0Rows = g->rz0Wq = g->rz0Fill = g->rz0WinOff = 0;
+    g->rz0WqMagic = 0;
+    if (!L.resizeLds || (P.w & 15)) return false;
+    const int B = DRFE_RESIZE_BLOCK, cols = L.rzCols, groups = L.rzGroups, blocks = L.rzBlocks;
+    const ResizeTap* xt = taps->data() + L.xtabOff;
+    const ResizeTap* yt = taps->data() + L.ytabOff;
+    std::vector<int> r0v(blocks), c0v(blocks);
+    int rows = 0, quads = 0;
+    for (int b = 0; b < blocks; b++) {
+        const int i0 = b * B, i1 = std::min(groups * cols, i0 + B);
+        int r0 = 1 << 30, r1 = -1, c0 = 1 << 30, c1 = -1;
+        for (int gi = i0 / cols; gi <= (i1 - 1) / cols; gi++) {
+            for (int y = L.rzRow0 + 4 * gi; y < L.rzRow0 + 4 * gi + 4; y++) {
+                r0 = std::min(r0, (int)yt[y].s0); r1 = std::max(r1, (int)yt[y].s1);
+            }
+            const int ca = std::max(i0 - gi * cols, 0), cb = std::min(i1 - gi * cols, cols);
+            for (int x = 4 * ca; x < 4 * cb; x++) {
+                c0 = std::min(c0, (int)xt[x].s0); c1 = std::max(c1, (int)xt[x].s1);
+            }
+        }
+        r0v[b] = r0; c0v[b] = c0 & ~15;
+        rows = std::max(rows, r1 - r0 + 1);
+        quads = std::max(quads, (c1 - c0v[b]) / 16 + 1);
+    }
+    quads = std::max(quads, 2);
+    if (rows > P.h || 16 * quads > P.w) return false;
+    const int fill = (rows * quads + B - 1) / B;
+    if (fill > DRFE_RESIZE_MAX_FILL || rows * quads * 16 + 16 > DRFE_RESIZE_TILE_BYTES) return false;
+    g->rz0Rows = rows; g->rz0Wq = quads; g->rz0Fill = fill;
+    g->rz0WqMagic = drfe_div_magic((uint32_t)quads);
+    g->rz0WinOff = (int)taps->size();
+    for (int b = 0; b < blocks; b++) {
+        const int r0 = std::max(0, std::min(r0v[b], P.h - rows)), c0 = std::max(0, std::min(c0v[b], P.w - 16 * quads));
+        taps->push_back(ResizeTap{(uint16_t)r0, (uint16_t)c0, 0, 0});
+    }
+    return true;
+}
+
 int drfe_build_geometry(drfe_ctx* c, int w, int h, DevGeom* g, std::vector<FastCell>* cells,
                         std::vector<BlurTile>* tiles, std::vector<ResizeTap>* taps)
 {
@@ -306,6 +354,17 @@ int drfe_build_geometry(drfe_ctx* c, int w, int h, DevGeom* g, std::vector<FastC
     if (cells) {
         std::stable_partition(cells->begin(), cells->end(), [](const FastCell& f) { return f.rpl <= 8; });
         for (const FastCell& f : *cells) g->fastColsSmall += f.rpl <= 8 ? 1 : 0;
+    }
+    /* level 0 in place (level0_view.h): the geometry's part of the eligibility */
+    g->l0InPlace = 0;
+    g->rz0Rows = g->rz0Wq = g->rz0Fill = g->rz0WinOff = 0;
+    g->rz0WqMagic = 0;
+    if (cells && taps && nl >= 2 && (w & 15) == 0) {
+        bool fit = g->fastCols != 0;
+        /* k_fast_cells_cols' tile row holds three 16-byte chunks: window width + its start inside the first aligned dword */
+        for (const FastCell& f : *cells)
+            if (f.level == 0 && f.ww + drfe_l0_fast_off(f.x0) > 48) fit = false;
+        if (plan_resize_tile_raw(g, taps) && fit) g->l0InPlace = 1;
     }
     g->pyrSlotBytes = pyrOff;
     g->blurSlotBytes = blurOff;

@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize(const DevLevel L, const DevL
 template <int FILL>
 __global__ __launch_bounds__(256) void k_pyr_resize_tile(const DevLevel L, const DevLevel P, int pyrSlotBytes,
                                                          const ResizeTap* __restrict__ taps, uint8_t* __restrict__ pyr,
-                                                         uint32_t magicBlocks)
+                                                         uint32_t magicBlocks, const Level0Src src0)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t tile[];
     int bx, slot;
@@ -176,7 +176,12 @@ __global__ __launch_bounds__(256) void k_pyr_resize_tile(const DevLevel L, const
     uint8_t* const base = pyr + (size_t)slot * pyrSlotBytes;
     /* the block's window origin through the constant address space: a scalar load */
     const uint32_t winp = ((const __attribute__((address_space(4))) uint32_t*)taps)[2 * (L.rzWinOff + bx)];
-    const struct { uint32_t s0, s1; } win = {winp & 0xFFFFu, winp >> 16};   /* bordered source row, column of tile byte 0 */
+    const struct { uint32_t s0, s1; } win = {winp & 0xFFFFu, winp >> 16};   /* source row, column of tile byte 0 (bordered coordinates in the arena) */
+    /* the source level: P in the arena, or (level 1 only) the caller's image itself - no border, its own pitch; kernel-uniform */
+    const bool raw = src0.base != nullptr;
+    const int srcEdge = raw ? 0 : DRFE_EDGE;
+    const uint32_t srcPitch = raw ? src0.rowStride : (uint32_t)P.pyrPitch;
+    const uint8_t* const srcLevel = raw ? src0.base + (size_t)slot * src0.frameStride : base + P.pyrOff;
     const uint32_t nItems = (uint32_t)(L.rzGroups * L.rzCols);
     uint32_t item = (uint32_t)(bx * DRFE_RESIZE_BLOCK + tid);
     const bool active = item < nItems;
@@ -194,7 +199,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize_tile(const DevLevel L, const
     const uint4 ta = *reinterpret_cast<const uint4*>(tb8 + txo);            /* taps of x4, x4+1 */
     const uint4 tb = *reinterpret_cast<const uint4*>(tb8 + (txo + 16u));    /* x4+2, x4+3 */
     {
-        const uint8_t* const srcw = base + P.pyrOff + (uint32_t)((int)win.s0 * P.pyrPitch + (int)win.s1);
+        const uint8_t* const srcw = srcLevel + drfe_rz_window_origin(win.s0, win.s1, srcPitch);
         const uint32_t nq = (uint32_t)(L.rzRows * L.rzWq), tpitch = (uint32_t)L.rzWq * 16u;
         uint4 v[FILL];
         uint32_t dst[FILL];
@@ -203,8 +208,9 @@ __global__ __launch_bounds__(256) void k_pyr_resize_tile(const DevLevel L, const
 #pragma unroll
         for (int k = 0; k < FILL; k++) {
             const uint32_t j = (uint32_t)tid + (uint32_t)(k * DRFE_RESIZE_BLOCK), jc = j < nq ? j : 0u;
-            const uint32_t r = divm(jc, (uint32_t)L.rzWq, L.rzWqMagic), q = jc - r * (uint32_t)L.rzWq;
-            v[k] = *reinterpret_cast<const uint4*>(srcw + (__umul24(r, (uint32_t)P.pyrPitch) + q * 16u));
+            uint32_t r, q;
+            const uint32_t so = drfe_rz_fill_offset(jc, (uint32_t)L.rzWq, L.rzWqMagic, srcPitch, &r, &q);
+            v[k] = *reinterpret_cast<const uint4*>(srcw + so);
             dst[k] = j < nq ? __umul24(r, tpitch) + q * 16u : nq * 16u;
         }
 #pragma unroll
@@ -219,7 +225,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize_tile(const DevLevel L, const
      * by zero) */
     int o[4];
 #pragma unroll
-    for (int k = 0; k < 4; k++) o[k] = (int)(sp[k] & 0xFFFFu) + DRFE_EDGE - (int)win.s1;
+    for (int k = 0; k < 4; k++) o[k] = (int)(sp[k] & 0xFFFFu) + srcEdge - (int)win.s1;
     const uint32_t p01 = (uint32_t)min(o[0], o[1]) & ~3u, p23 = (uint32_t)min(o[2], o[3]) & ~3u;
     uint32_t sel[4];
 #pragma unroll
@@ -246,7 +252,7 @@ __global__ __launch_bounds__(256) void k_pyr_resize_tile(const DevLevel L, const
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const uint32_t sy = typ[r].x, wy2 = typ[r].y;
-        const int a = (int)(sy & 0xFFFFu) + DRFE_EDGE - (int)win.s0, b = (int)(sy >> 16) + DRFE_EDGE - (int)win.s0;
+        const int a = (int)(sy & 0xFFFFu) + srcEdge - (int)win.s0, b = (int)(sy >> 16) + srcEdge - (int)win.s0;
         uint32_t Ha[4], Hb[4];
         if (a == prevB) {
 #pragma unroll
@@ -600,7 +606,8 @@ __global__ __launch_bounds__(64) void k_fast_cells_cols(const FastCell* __restri
                                                         int candSlotElems, int iniTh, int minTh,
                                                         const uint8_t* __restrict__ pyr, uint32_t* __restrict__ cand0,
                                                         uint32_t* __restrict__ cand1, int* __restrict__ candCount,
-                                                        int* __restrict__ status, uint32_t gxMagic, int cellFirst, int screen, int listOff, int listCap)
+                                                        int* __restrict__ status, uint32_t gxMagic, int cellFirst, int screen, int listOff, int listCap,
+                                                        const Level0Src src0)
 {
     int bx, by;
     drfe_xcd_swizzle_2d(gxMagic, bx, by);
@@ -610,8 +617,14 @@ __global__ __launch_bounds__(64) void k_fast_cells_cols(const FastCell* __restri
     const int lane = threadIdx.x;
     const int ww = fc.ww, wh = fc.wh;
     const int ew = ww - 6, eh = wh - 6;
-    const int off = fc.off;
+    int off = fc.off;
+    uint32_t pitch = fc.pitch;
     const uint8_t* src = pyr + (size_t)__builtin_amdgcn_readfirstlane(slot) * pyrSlotBytes + fc.srcOff;    /* block-uniform: a scalar base */
+    if (src0.base != nullptr && fc.level == 0) {          /* block-uniform: the cell's window in the caller's image (level0_view.h) */
+        off = drfe_l0_fast_off(fc.x0);
+        pitch = src0.rowStride;
+        src = src0.base + (size_t)__builtin_amdgcn_readfirstlane(slot) * src0.frameStride + drfe_l0_fast_origin(fc.x0, fc.y0, pitch);
+    }
     {   /* window rows as 16-byte chunks, widened to one pixel per 16-bit lane.  Tile index k of a row holds byte k + sh of
            the aligned source row, sh = off & 1: pixel (wx, wy) of the window sits at index (off & 2) + wx, so every pixel
            pair a lane reads starts at an even index.  A chunk is loaded only if the window needs its first byte (and the
@@ -623,9 +636,8 @@ __global__ __launch_bounds__(64) void k_fast_cells_cols(const FastCell* __restri
         const int sh = off & 1;
         const uint32_t selE = sh ? 0x0C020C01u : 0x0C010C00u, selO = sh ? 0x0C040C03u : 0x0C030C02u;
         for (int i = lane; i < nitems; i += 64) {
-            const int r = nch == 1 ? i : nch == 2 ? (i >> 1) : (int)(((uint32_t)i * 21846u) >> 16);
-            const int c = i - r * nch;
-            const uint8_t* p = src + (uint32_t)(__umul24((uint32_t)r, fc.pitch) + (uint32_t)c * 16u);      /* 32-bit offset: a window is a few KB */
+            int r, c;
+            const uint8_t* p = src + drfe_fastc_fill_offset(i, nch, pitch, &r, &c);      /* 32-bit offset: a window is a few KB */
             const u32x4_a4 g = *reinterpret_cast<const u32x4_a4*>(p);
             uint32_t g4 = 0;
             if (sh && c * 16 + 16 < need) g4 = *reinterpret_cast<const uint32_t*>(p + 16);
@@ -1178,9 +1190,11 @@ __global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : 6) void k_quadt
  * BORDERED pyramid level: its 19-px frame already holds the REFLECT_101 image of the interior, which is
  * exactly what GaussianBlur(BORDER_REFLECT_101) of the cloned interior ROI reads (3 px needed), so no
  * reflection logic runs here.  Horizontal pass straight from three aligned dword loads into 8.8 sums
- * in LDS (v_dot4_u32_u8); vertical pass from LDS (v_mad_u32_u16). */
+ * in LDS (v_dot4_u32_u8); vertical pass from LDS (v_mad_u32_u16).  Level-0 tiles of a batch that reads level 0 in place
+ * (src0.base != nullptr) take their rows from the caller's image and reflect them there: see the branch below. */
 __global__ __launch_bounds__(256) void k_blur(const DevGeom* __restrict__ G, const BlurTile* __restrict__ tiles,
-                                              const uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur, uint32_t gxMagic)
+                                              const uint8_t* __restrict__ pyr, uint8_t* __restrict__ blur, uint32_t gxMagic,
+                                              const Level0Src src0)
 {
     /* XCD-aware numbering (whole frames per XCD): neighbouring tiles share the 128-byte lines their 136-byte rows straddle and
      * the halo rows; dealt round-robin over eight private L2s every such line was fetched twice (2 x FETCH_SIZE = 2.4 x the
@@ -1227,12 +1241,39 @@ __global__ __launch_bounds__(256) void k_blur(const DevGeom* __restrict__ G, con
         h[3] = __builtin_amdgcn_udot4(w0, TAP4(0, 0, 0, 18), __builtin_amdgcn_udot4(w1, TAP4(34, 49, 55, 49),
                                       __builtin_amdgcn_udot4(w2, TAP4(34, 18, 0, 0), 0u, false), false), false);
     };
-#undef TAP4
     /* low halves of two registers as one dword (the sums fit 16 bits): one v_perm_b32 */
     auto pack16 = [](uint32_t lo, uint32_t hi) { return __builtin_amdgcn_perm(hi, lo, 0x05040100u); };
     /* source rows y0-3 .. min(y0 + TH, h) + 2 are all the stored output rows read: a tile that overhangs the level's last row
      * (a third of the tile area on the small levels) stops there - whole wavefronts drop out, a wave is two tile rows */
     const int pEnd = __builtin_amdgcn_readfirstlane(min(BLUR_ROWS / 2, (min(DRFE_BLUR_TH, L.h - y0) + 7) >> 1));
+    if (src0.base != nullptr && t.level == 0) {
+        /* Level 0 in the caller's image (level0_view.h; block-uniform): no border, so the rows are reflected here and interior
+         * column x - 3 is not dword-aligned - the thread reads the aligned dwords [x-4..x-1] [x..x+3] [x+4..x+7], byte k = column
+         * x - 4 + k, pixel x + j under taps at bytes j+1..j+7: again 2 + 3 + 3 + 2 v_dot4_u32_u8.  At the image's first / last
+         * dword column the dword outside the row is not loaded but permuted out of the middle one (the selectors are the identity
+         * elsewhere), and a thread past the row repeats the last in-row thread's loads. */
+        const uint8_t* img0 = src0.base + (size_t)__builtin_amdgcn_readfirstlane(slot) * src0.frameStride;
+        const L0BlurCols bc = drfe_l0_blur_cols(x0 + cg * 4, L.w);
+        const int h0 = L.h;
+        auto hsum4raw = [&](uint32_t rowOff, uint32_t (&h)[4]) {
+            const uint32_t m = *reinterpret_cast<const uint32_t*>(img0 + (rowOff + bc.m));
+            const uint32_t l = __builtin_amdgcn_perm(m, *reinterpret_cast<const uint32_t*>(img0 + (rowOff + bc.l)), bc.selL);
+            const uint32_t r = __builtin_amdgcn_perm(*reinterpret_cast<const uint32_t*>(img0 + (rowOff + bc.r)), m, bc.selR);
+            h[0] = __builtin_amdgcn_udot4(l, TAP4(0, 18, 34, 49), __builtin_amdgcn_udot4(m, TAP4(55, 49, 34, 18), 0u, false), false);
+            h[1] = __builtin_amdgcn_udot4(l, TAP4(0, 0, 18, 34), __builtin_amdgcn_udot4(m, TAP4(49, 55, 49, 34),
+                                          __builtin_amdgcn_udot4(r, TAP4(18, 0, 0, 0), 0u, false), false), false);
+            h[2] = __builtin_amdgcn_udot4(l, TAP4(0, 0, 0, 18), __builtin_amdgcn_udot4(m, TAP4(34, 49, 55, 49),
+                                          __builtin_amdgcn_udot4(r, TAP4(34, 18, 0, 0), 0u, false), false), false);
+            h[3] = __builtin_amdgcn_udot4(m, TAP4(18, 34, 49, 55), __builtin_amdgcn_udot4(r, TAP4(49, 34, 18, 0), 0u, false), false);
+        };
+        for (int p = rr; p < pEnd; p += BLUR_ROWL) {
+            uint32_t ha[4], hc[4];
+            hsum4raw(drfe_l0_blur_row(y0, 2 * p, h0, src0.rowStride), ha);
+            hsum4raw(drfe_l0_blur_row(y0, 2 * p + 1, h0, src0.rowStride), hc);
+            *reinterpret_cast<uint4*>(&hb2[p * DRFE_BLUR_TW + cg * 4]) =
+                make_uint4(pack16(ha[0], hc[0]), pack16(ha[1], hc[1]), pack16(ha[2], hc[2]), pack16(ha[3], hc[3]));
+        }
+    } else
     for (int p = rr; p < pEnd; p += BLUR_ROWL) {
         uint32_t ha[4], hc[4];
         const uint32_t ra = (uint32_t)min(y0 + 2 * p - 3 + DRFE_EDGE, lastRow), rc = (uint32_t)min(y0 + 2 * p - 2 + DRFE_EDGE, lastRow);
@@ -1241,6 +1282,7 @@ __global__ __launch_bounds__(256) void k_blur(const DevGeom* __restrict__ G, con
         *reinterpret_cast<uint4*>(&hb2[p * DRFE_BLUR_TW + cg * 4]) =
             make_uint4(pack16(ha[0], hc[0]), pack16(ha[1], hc[1]), pack16(ha[2], hc[2]), pack16(ha[3], hc[3]));
     }
+#undef TAP4
     __syncthreads();
     /* vertical pass, two output rows (2q, 2q+1) per thread from the four row pairs q..q+3:
      *   row 2q   = (18,34).P[q] + (49,55).P[q+1] + (49,34).P[q+2] + 18 * lo(P[q+3])
@@ -1315,7 +1357,7 @@ __global__ __launch_bounds__(DESC_THREADS) void k_orient_desc(const DevGeom* __r
                                                      const int8_t* __restrict__ pattern,
                                                      const int16_t* __restrict__ disc, int discCount,
                                                      drfe_keypoint* __restrict__ kps, uint8_t* __restrict__ desc,
-                                                     int* __restrict__ kpCount, int maxKp, uint32_t gxMagic)
+                                                     int* __restrict__ kpCount, int maxKp, uint32_t gxMagic, const Level0Src src0)
 {
     __shared__ uint32_t sPatch[DESC_WAVES][DESC_KPW][DESC_LDS_DW];
     int bx, by;
@@ -1371,6 +1413,12 @@ __global__ __launch_bounds__(DESC_THREADS) void k_orient_desc(const DevGeom* __r
         /* blurred level: tiled (drfe_blur_offset); cB = the level, (bx0, by0) = the patch corner moved left to a dword */
         shP[j] = (int)(oP & 3); shB[j] = (xi[j] - DESC_REACH) & 3;
         cP[j] = pyr + (oP & ~(size_t)3);
+        if (src0.base != nullptr && level[j] == 0) {       /* wave-uniform: the raw patch from the caller's image (level0_view.h) */
+            const uint32_t o0 = drfe_l0_patch_origin(xi[j], yi[j], src0.rowStride);
+            pitchP[j] = (int)src0.rowStride;
+            shP[j] = (int)(o0 & 3u);
+            cP[j] = src0.base + (size_t)slot * src0.frameStride + (o0 & ~3u);
+        }
         cB[j] = blur + (size_t)slot * G->blurSlotBytes + L.blurOff;
         bx0[j] = (xi[j] - DESC_REACH) & ~3; by0[j] = yi[j] - DESC_REACH;
     }
@@ -1382,7 +1430,7 @@ __global__ __launch_bounds__(DESC_THREADS) void k_orient_desc(const DevGeom* __r
 #pragma unroll
         for (int k = 0; k < DESC_RAW_LD; k++) {
             const int t = min(lane + k * WAVE, DESC_RAW_N - 1);               /* the tail repeats the last dword */
-            rRow[k] = (int)(__umul24(t, 7282) >> 16); rCol[k] = (t - __mul24(rRow[k], DESC_RAW_DW)) * 4;
+            drfe_desc_raw_dword(t, &rRow[k], &rCol[k]);
         }
 #pragma unroll
         for (int k = 0; k < DESC_BLUR_LD; k++) {
@@ -1535,12 +1583,37 @@ __global__ void k_clear_counts(int* __restrict__ candCount, int n, int* __restri
     if (i == 0) status[0] = 0;
 }
 
+hipError_t drfe_launch_level0(drfe_ctx* c, const uint8_t* d_gray, size_t frameStride, size_t rowStride, int nframes, hipStream_t s)
+{
+    const DevGeom& g = c->geom;
+    const DevLevel& L = g.lv[0];
+    const int bh = L.h + 2 * DRFE_EDGE;
+    const bool aligned16 = (((uintptr_t)d_gray | frameStride | rowStride) & 15) == 0;
+    /* wide kernel: 16-px groups whose two aligned source words lie inside the row: x16 - 19 >= 13, x16 <= w */
+    int x16First = 32, x16Last = (L.w / 16) * 16, leftEnd = 0, rightBegin = 0;
+    if (aligned16 && x16Last >= x16First) {
+        const int nWide = (x16Last - x16First) / 16 + 1;
+        hipLaunchKernelGGL(k_pyr_level0_wide, dim3((nWide + 63) / 64, (bh + 4 * PYR0_ROWS - 1) / (4 * PYR0_ROWS), nframes),
+                           dim3(64, 4), 0, s, L, g.pyrSlotBytes, d_gray, frameStride, rowStride, x16First, x16Last, c->d_pyr);
+        leftEnd = x16First; rightBegin = x16Last + 16;
+    }
+    const int nEdge = leftEnd / 4 + (L.pyrPitch - rightBegin) / 4;      /* leftEnd == rightBegin == 0: every dword */
+    hipLaunchKernelGGL(k_pyr_level0_edge, dim3((nEdge * bh + 255) / 256, nframes), dim3(256), 0, s, L,
+                       g.pyrSlotBytes, d_gray, frameStride, rowStride, leftEnd, rightBegin, c->d_pyr);
+    return hipGetLastError();
+}
+
 hipError_t drfe_launch_orb(drfe_ctx* c, const uint8_t* d_gray, size_t frameStride, size_t rowStride, int nframes,
-                           hipStream_t s)
+                           hipStream_t s, bool allowInPlace)
 {
     const DevGeom& g = c->geom;
     const int nl = g.nlevels;
     hipError_t e;
+    /* level 0 in place (level0_view.h): the two level-0 launches disappear and level 0's four readers take the caller's frames */
+    const bool inPlace = allowInPlace && !c->level0Copy && !c->fastGeneric && drfe_level0_in_place_ok(g, d_gray, frameStride, rowStride);
+    const Level0Src src0 = inPlace ? Level0Src{d_gray, frameStride, (uint32_t)rowStride} : Level0Src{nullptr, 0, 0};
+    const Level0Src noSrc0 = {nullptr, 0, 0};
+    c->lastInPlace = inPlace ? 1 : 0;
     /* a kernel, not two hipMemsetAsync: memset nodes of a captured graph (the single-frame entry replays one) did not run
      * on this ROCm, and one launch is cheaper than two anyway */
     hipLaunchKernelGGL(k_clear_counts, dim3((nframes * DRFE_CC_SLOT / DRFE_CC_LINE + 255) / 256), dim3(256), 0, s, c->d_candCount, nframes * DRFE_CC_SLOT / DRFE_CC_LINE, c->d_status);
@@ -1548,31 +1621,23 @@ hipError_t drfe_launch_orb(drfe_ctx* c, const uint8_t* d_gray, size_t frameStrid
     if (e != hipSuccess) return e;
 
     prof_begin(c, DRFE_STAGE_PYRAMID, s);
-    {
-        const DevLevel& L = g.lv[0];
-        const int bh = L.h + 2 * DRFE_EDGE;
-        const bool aligned16 = (((uintptr_t)d_gray | frameStride | rowStride) & 15) == 0;
-        /* wide kernel: 16-px groups whose two aligned source words lie inside the row: x16 - 19 >= 13, x16 <= w */
-        int x16First = 32, x16Last = (L.w / 16) * 16, leftEnd = 0, rightBegin = 0;
-        if (aligned16 && x16Last >= x16First) {
-            const int nWide = (x16Last - x16First) / 16 + 1;
-            hipLaunchKernelGGL(k_pyr_level0_wide, dim3((nWide + 63) / 64, (bh + 4 * PYR0_ROWS - 1) / (4 * PYR0_ROWS), nframes),
-                               dim3(64, 4), 0, s, L, g.pyrSlotBytes, d_gray, frameStride, rowStride, x16First, x16Last, c->d_pyr);
-            leftEnd = x16First; rightBegin = x16Last + 16;
-        }
-        const int nEdge = leftEnd / 4 + (L.pyrPitch - rightBegin) / 4;      /* leftEnd == rightBegin == 0: every dword */
-        hipLaunchKernelGGL(k_pyr_level0_edge, dim3((nEdge * bh + 255) / 256, nframes), dim3(256), 0, s, L,
-                           g.pyrSlotBytes, d_gray, frameStride, rowStride, leftEnd, rightBegin, c->d_pyr);
+    if (!inPlace) {
+        e = drfe_launch_level0(c, d_gray, frameStride, rowStride, nframes, s);
+        if (e != hipSuccess) return e;
     }
     for (int l = 1; l < nl; l++) {
-        const DevLevel& L = g.lv[l];
+        DevLevel L = g.lv[l];
+        const bool raw = inPlace && l == 1;
+        if (raw) {                 /* the window plan for the unbordered source */
+            L.rzRows = g.rz0Rows; L.rzWq = g.rz0Wq; L.rzFill = g.rz0Fill; L.rzWinOff = g.rz0WinOff; L.rzWqMagic = g.rz0WqMagic;
+        }
         if (L.resizeLds) {
-            typedef void (*ResizeTileFn)(const DevLevel, const DevLevel, int, const ResizeTap*, uint8_t*, uint32_t);
+            typedef void (*ResizeTileFn)(const DevLevel, const DevLevel, int, const ResizeTap*, uint8_t*, uint32_t, const Level0Src);
             static const ResizeTileFn fns[DRFE_RESIZE_MAX_FILL] = {k_pyr_resize_tile<1>, k_pyr_resize_tile<2>, k_pyr_resize_tile<3>,
                 k_pyr_resize_tile<4>, k_pyr_resize_tile<5>, k_pyr_resize_tile<6>, k_pyr_resize_tile<7>, k_pyr_resize_tile<8>};
             const dim3 grid(L.rzBlocks, nframes);
             hipLaunchKernelGGL(fns[L.rzFill - 1], grid, dim3(DRFE_RESIZE_BLOCK), (size_t)(L.rzRows * L.rzWq * 16 + 16), s, L,
-                               g.lv[l - 1], g.pyrSlotBytes, c->d_taps, c->d_pyr, drfe_div_magic(grid.x));
+                               g.lv[l - 1], g.pyrSlotBytes, c->d_taps, c->d_pyr, drfe_div_magic(grid.x), raw ? src0 : noSrc0);
         } else {
             const dim3 grid((L.pyrPitch / 4 + 63) / 64, (L.h + 2 * DRFE_EDGE + 4 * PYR_ROWS - 1) / (4 * PYR_ROWS), nframes);
             hipLaunchKernelGGL(k_pyr_resize, grid, dim3(64, 4), 0, s, L, g.lv[l - 1], g.pyrSlotBytes, c->d_taps, c->d_pyr);
@@ -1586,7 +1651,7 @@ hipError_t drfe_launch_orb(drfe_ctx* c, const uint8_t* d_gray, size_t frameStrid
         if (nSmall > 0)
             hipLaunchKernelGGL((k_fast_cells_cols<8>), dim3(nSmall, nframes), dim3(64), (size_t)fastc_lds_bytes(g.fastColsRows, 8 * 64), s,
                                c->d_cells, g.nlevels, g.pyrSlotBytes, g.candSlotElems, g.iniTh, g.minTh, c->d_pyr, c->d_cand0,
-                               c->d_cand1, c->d_candCount, c->d_status, drfe_div_magic((uint32_t)nSmall), 0, c->fastScreen, fastc_list_off(g.fastColsRows), fastc_list_cap(g.fastColsRows, 8 * 64));
+                               c->d_cand1, c->d_candCount, c->d_status, drfe_div_magic((uint32_t)nSmall), 0, c->fastScreen, fastc_list_off(g.fastColsRows), fastc_list_cap(g.fastColsRows, 8 * 64), src0);
         if (nBig > 0) {
             prof_end(c, DRFE_STAGE_FAST, s);
             prof_begin(c, DRFE_STAGE_FAST_B, s);
@@ -1595,7 +1660,7 @@ hipError_t drfe_launch_orb(drfe_ctx* c, const uint8_t* d_gray, size_t frameStrid
             hipLaunchKernelGGL((k_fast_cells_cols<DRFE_FASTC_MAX_RPL>), dim3(nBig, nframes), dim3(64),
                                (size_t)fastc_lds_bytes(g.fastColsRows, DRFE_FASTC_MAX_RPL * 64), s, c->d_cells, g.nlevels, g.pyrSlotBytes, g.candSlotElems,
                                g.iniTh, g.minTh, c->d_pyr, c->d_cand0, c->d_cand1, c->d_candCount, c->d_status,
-                               drfe_div_magic((uint32_t)nBig), nSmall, c->fastScreen, fastc_list_off(g.fastColsRows), fastc_list_cap(g.fastColsRows, DRFE_FASTC_MAX_RPL * 64));
+                               drfe_div_magic((uint32_t)nBig), nSmall, c->fastScreen, fastc_list_off(g.fastColsRows), fastc_list_cap(g.fastColsRows, DRFE_FASTC_MAX_RPL * 64), src0);
         if (nBig > 0) prof_end(c, DRFE_STAGE_FAST_B, s);
         else prof_end(c, DRFE_STAGE_FAST, s);
     } else {
@@ -1633,13 +1698,13 @@ hipError_t drfe_launch_orb(drfe_ctx* c, const uint8_t* d_gray, size_t frameStrid
 
     prof_begin(c, DRFE_STAGE_BLUR, s);
     hipLaunchKernelGGL(k_blur, dim3(g.totalTiles, nframes), dim3(256), 0, s, c->d_geom, c->d_tiles, c->d_pyr,
-                       c->d_blur, drfe_div_magic((uint32_t)g.totalTiles));
+                       c->d_blur, drfe_div_magic((uint32_t)g.totalTiles), src0);
     prof_end(c, DRFE_STAGE_BLUR, s);
 
     prof_begin(c, DRFE_STAGE_DESC, s);
     hipLaunchKernelGGL(k_orient_desc, dim3((c->maxKp + DESC_WAVES * DESC_KPW - 1) / (DESC_WAVES * DESC_KPW), nframes), dim3(DESC_THREADS), 0, s, c->d_geom, c->d_pyr,
                        c->d_blur, c->d_sel, c->d_selCount, c->d_pattern, c->d_disc, c->discCount, c->d_kps,
-                       c->d_desc, c->d_kpCount, c->maxKp, drfe_div_magic((uint32_t)((c->maxKp + DESC_WAVES * DESC_KPW - 1) / (DESC_WAVES * DESC_KPW))));
+                       c->d_desc, c->d_kpCount, c->maxKp, drfe_div_magic((uint32_t)((c->maxKp + DESC_WAVES * DESC_KPW - 1) / (DESC_WAVES * DESC_KPW))), src0);
     prof_end(c, DRFE_STAGE_DESC, s);
     return hipGetLastError();
 }

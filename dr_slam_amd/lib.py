@@ -29,6 +29,7 @@ SYMBOLS = (
     "drfe_create", "drfe_destroy", "drfe_last_error", "drfe_version", "drfe_orb_scale_tables",
     "drfe_orb_max_keypoints", "drfe_orb_extract", "drfe_orb_extract_batch", "drfe_orb_download", "drfe_orb_counts",
     "drfe_orb_pyramid_level", "drfe_orb_blurred_level", "drfe_orb_candidates", "drfe_frame_stereo_grid_batch",
+    "drfe_orb_configure_level0", "drfe_orb_level0_in_place",
     "drfe_fuse_search", "drfe_fuse_search_sim3", "drfe_search_by_sim3", "drfe_search_by_projection_kf", "drfe_search_by_projection_reloc", "drfe_lsd_fuse_search", "drfe_frame_is_in_frustum", "drfe_frame_is_in_frustum_lines", "drfe_frame_set_distortion", "drfe_frame_image_bounds", "drfe_frame_download_keys_un",
     "drfe_frame_download_stereo", "drfe_frame_download_grid", "drfe_match_consecutive_batch", "drfe_match_download",
     "drfe_search_by_projection_last", "drfe_search_by_projection_map", "drfe_match_bf_knn", "drfe_profile_enable",
@@ -442,6 +443,8 @@ def load() -> C.CDLL:
     L.drfe_frame_stereo_grid_batch_kpdepth.argtypes = [vp, vp, i32, C.POINTER(Camera), i32, vp]
     L.drfe_batch_download_async.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
     L.drfe_orb_pyramid_level.argtypes = [vp, i32, i32, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.drfe_orb_configure_level0.argtypes = [vp, i32]
+    L.drfe_orb_level0_in_place.argtypes = [vp]
     L.drfe_orb_blurred_level.argtypes = [vp, i32, i32, vp, C.POINTER(i32), C.POINTER(i32)]
     L.drfe_orb_candidates.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32)]
     L.drfe_frame_stereo_grid_batch.argtypes = [vp, vp, sz, sz, C.POINTER(Camera), i32, vp]
@@ -2242,6 +2245,16 @@ class Context:
         c = np.zeros(nframes, np.int32)
         self._chk(self.L.drfe_orb_counts(self.h, nframes, _p(c)), "drfe_orb_counts")
         return c
+
+    def orb_configure_level0(self, in_place=True):
+        """Whether orb_extract_batch_ptr may read pyramid level 0 from the caller's frames (default) or always copies it."""
+        self._chk(self.L.drfe_orb_configure_level0(self.h, 1 if in_place else 0), "drfe_orb_configure_level0")
+
+    def orb_level0_in_place(self) -> bool:
+        """True if the most recent batch read pyramid level 0 in place."""
+        rc = self.L.drfe_orb_level0_in_place(self.h)
+        self._chk(min(rc, 0), "drfe_orb_level0_in_place")
+        return rc == 1
 
     def pyramid_level(self, slot, level):
         w, h = C.c_int(), C.c_int()

@@ -91,9 +91,19 @@ int drfe_orb_extract(drfe_ctx* ctx, const uint8_t* gray, int w, int h, size_t st
  * NULL = the context's own stream).  Results stay in the context's frame slots 0..nframes-1.
  * Several contexts working at once (batches in flight): pass NULL - the stream every drfe_create makes sits on its own
  * hardware queue, so the contexts' kernels really overlap (+10 % device rate at three batches in flight); streams from a
- * framework's pool may share a queue, and the batches then run one behind the other. */
+ * framework's pool may share a queue, and the batches then run one behind the other.
+ * The frames are read until the call's last extraction kernel (orientation + descriptors) has finished, not only at its start:
+ * where d_gray, frame_stride and row_stride are multiples of 16 and the frame size allows it (w a multiple of 16; 640x480 and
+ * 1280x960 do), pyramid level 0 is not copied into the context but read from the frames in place.  Do not overwrite or free them
+ * before the stream has passed the call. */
 int drfe_orb_extract_batch(drfe_ctx* ctx, const uint8_t* d_gray, size_t frame_stride, size_t row_stride, int w,
                            int h, int nframes, void* stream);
+/* 0: drfe_orb_extract_batch always copies level 0 into the context (the frames are then read at the start of the call only);
+ * 1 (default): it reads level 0 in place where it can.  Results are identical.  DRFE_LEVEL0_COPY=1 in the environment sets 0 at
+ * drfe_create. */
+int drfe_orb_configure_level0(drfe_ctx* ctx, int in_place);
+/* 1 if the most recent drfe_orb_extract_batch on ctx read level 0 in place, 0 if it copied it. */
+int drfe_orb_level0_in_place(const drfe_ctx* ctx);
 /* Copy slot results to host (synchronises the batch stream). */
 int drfe_orb_download(drfe_ctx* ctx, int slot, drfe_keypoint* kps, uint8_t* desc, int cap, int* n_out);
 /* The whole batch to host memory in five copies, asynchronous on `stream` (hipStream_t; NULL = the context stream): for a
@@ -115,7 +125,9 @@ int drfe_batch_check(drfe_ctx* ctx);
 int drfe_orb_counts(drfe_ctx* ctx, int nframes, int* counts);
 
 /* mvImagePyramid parity (public member, include/ORBextractor.h:85): copy the bordered level
- * ((w_l+38) x (h_l+38), tightly packed) of a slot to host.  out may be NULL to query sizes. */
+ * ((w_l+38) x (h_l+38), tightly packed) of a slot to host.  out may be NULL to query sizes.
+ * Level 0 of a slot whose batch read it in place (drfe_orb_level0_in_place) is bordered by this call, from the frame that was
+ * passed to drfe_orb_extract_batch: that frame must still be alive and unchanged. */
 int drfe_orb_pyramid_level(drfe_ctx* ctx, int slot, int level, uint8_t* out, int* bordered_w, int* bordered_h);
 /* Debug/parity taps (tests): blurred interior level, FAST candidates (x,y,response relative to the
  * 16-px detection border, unordered). */
