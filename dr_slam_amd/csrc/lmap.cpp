@@ -184,6 +184,7 @@ int build_image(drfe_lmap* db)
     db->imgDirty = false;
     db->devDirty = true;
     db->geoDirty = true;               /* the slots may have moved */
+    db->cullDirty = true;
     return DRFE_OK;
 }
 
@@ -362,7 +363,7 @@ bool device_fits(const drfe_lmap* db, const Call& C)
 int upload_image(drfe_lmap* db, hipStream_t st)
 {
     const Image& G = db->img;
-    if (!db->devDirty && !db->devBadDirty && !db->devGraphDirty) return DRFE_OK;
+    if (!db->devDirty && !db->devBadDirty && !db->devGraphDirty && !db->devObsDirty && db->devNulls.empty()) return DRFE_OK;
     const bool all = db->devDirty, graph = all || db->devGraphDirty;
     StageLayout<16> up, gr;
     const auto uKfBad = up.add<uint8_t>(G.kfBad.size());
@@ -404,7 +405,28 @@ int upload_image(drfe_lmap* db, hipStream_t st)
             HIPCHK_TO(db->err, db->dImg.grow(db->dImg.capacity() >= bytes ? bytes : 2 * bytes));
         }
         HIPCHK_TO(db->err, hipMemcpyAsync(db->dImg, h, bytes, hipMemcpyHostToDevice, st));
+        db->sentBytes[0] += (int64_t)bytes;
     }
+    if (!all) {
+        /* what a cull call committed, piece by piece: the nulled match-row entries, and the observations with their offsets,
+         * which are the end of the block (a shortened row moves the rows behind it, never the sections in front) */
+        static const int32_t kNull = -1;
+        char* d = db->dImg;
+        for (const int32_t e : db->devNulls)
+            HIPCHK_TO(db->err, hipMemcpyAsync(uKfMp.at(d) + e, &kNull, sizeof(kNull), hipMemcpyHostToDevice, st));
+        db->sentBytes[0] += (int64_t)(sizeof(kNull) * db->devNulls.size());
+        if (db->devObsDirty) {
+            const size_t total = up.bytes(), tail = total - uObsOff.off;
+            HIPCHK_TO(db->err, db->hup.grow(db->hup.capacity() >= total ? total : 2 * total));
+            char* h = db->hup;
+            uObsOff.put(h, G.obsOff.data());
+            uObs.put(h, G.obs.data());
+            HIPCHK_TO(db->err, hipMemcpyAsync(d + uObsOff.off, h + uObsOff.off, tail, hipMemcpyHostToDevice, st));
+            db->sentBytes[0] += (int64_t)tail;
+        }
+    }
+    db->devNulls.clear();
+    db->devObsDirty = false;
     if (graph) {
         const size_t gb = gr.bytes();
         HIPCHK_TO(db->err, db->hgraph.grow(db->hgraph.capacity() >= gb ? gb : 2 * gb));
@@ -422,6 +444,7 @@ int upload_image(drfe_lmap* db, hipStream_t st)
         uCoW.put(h, G.coW.data());
         HIPCHK_TO(db->err, db->dGraph.grow(db->dGraph.capacity() >= gb ? gb : 2 * gb));
         if (gb) HIPCHK_TO(db->err, hipMemcpyAsync(db->dGraph, h, gb, hipMemcpyHostToDevice, st));
+        db->sentBytes[1] += (int64_t)gb;
     }
     if (graph) {
         /* either block may have moved or changed its layout */
@@ -1196,6 +1219,7 @@ int drfe_lmap_create(drfe_ctx* ctx, drfe_lmap** out)
     db->dView = LmapImage{};
     db->dConn = ConnImage{};
     db->dCorr = CorrImage{};
+    db->dCull = CullImage{};
     *out = db;
     return DRFE_OK;
 }
@@ -1342,11 +1366,15 @@ int drfe_lmap_remove(drfe_lmap* db, int kind, int32_t handle)
             db->kf.erase(it);
             db->conn.erase(handle);
             db->kfPose.erase(handle);
+            db->kfCull.erase(handle);
             gone = 1;
         }
     } else if (kind == DRFE_LMAP_POINT) {
         gone = db->mp.erase(handle);
-        if (gone) db->mpGeo.erase(handle);
+        if (gone) {
+            db->mpGeo.erase(handle);
+            db->mpCull.erase(handle);
+        }
     } else if (kind == DRFE_LMAP_LINE) {
         gone = db->ml.erase(handle);
     } else {
@@ -1476,6 +1504,14 @@ int drfe_lmap_connect_device(drfe_lmap* db, int32_t n, const int32_t* handles, d
 int drfe_lmap_connect_batch(drfe_lmap* db, int32_t n, const int32_t* handles, drfe_lmap_connect_out* o, void* stream)
 {
     return conn_entry(db, n, handles, o, 2, stream);
+}
+
+int drfe_lmap_upload_bytes(drfe_lmap* db, int64_t* out4)
+{
+    if (!db || !out4) return DRFE_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(db->mu);
+    std::memcpy(out4, db->sentBytes, sizeof(db->sentBytes));
+    return DRFE_OK;
 }
 
 int drfe_lmap_connect_limits(int32_t* out4)

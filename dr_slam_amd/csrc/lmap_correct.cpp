@@ -261,6 +261,7 @@ int upload_geo(drfe_lmap* db, hipStream_t st)
     uBy.put(h, E.mpBy.data());
     uByRef.put(h, E.mpByRef.data());
     if (bytes) HIPCHK_TO(db->err, hipMemcpyAsync(db->dGeo, h, bytes, hipMemcpyHostToDevice, st));
+    db->sentBytes[2] += (int64_t)bytes;
     char* d = db->dGeo;
     CorrImage& V = db->dCorr;
     V.nLevels = (int32_t)db->scales.size();

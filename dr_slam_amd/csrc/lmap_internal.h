@@ -1,4 +1,4 @@
-/* lmap_internal.h — what lmap.cpp and lmap_correct.cpp hand to the store's kernels (DESIGN.md sections 25 to 27). */
+/* lmap_internal.h — what lmap.cpp, lmap_correct.cpp and lmap_cull.cpp hand to the store's kernels (DESIGN.md sections 25 to 28). */
 #ifndef DRFE_LMAP_INTERNAL_H
 #define DRFE_LMAP_INTERNAL_H
 
@@ -6,6 +6,7 @@
 #include "lmap_core.h"
 #include "conn_core.h"
 #include "correct_core.h"
+#include "cull_core.h"
 
 /* threads of a workgroup: frame points and key-frame slots go across them in the vote, the entries of a match row in the gather */
 #define LMAP_THREADS 256
@@ -164,5 +165,54 @@ hipError_t drfe_launch_correct_plan(const CorrLaunch& L, hipStream_t s);
 hipError_t drfe_launch_correct_chunk(const CorrLaunch& L, hipStream_t s);
 /* the new poses and centres into the image: after the last chunk, which still reads the stored ones */
 hipError_t drfe_launch_correct_poses(const CorrLaunch& L, hipStream_t s);
+
+/* ---- LocalMapping::KeyFrameCulling (cull_kernels.hip) ---- */
+/* entries of a called key frame's match row that one record workgroup takes */
+#define CULL_TILE LMAP_THREADS
+/* threads of the one workgroup that walks the called key frames in order: lanes go over the entries of the key frame it is at */
+#define CULL_WALK_THREADS 1024
+/* bytes of scratch per entry of a chunk's match rows: its CullRecord */
+#define CULL_ENTRY_BYTES 8
+/* words the walk writes per called key frame: nMPs, nRedundant, action, points gone bad, observers walked (low, high) */
+#define CULL_OUT_WORDS 6
+
+/* the attributes of the image, resident in a block of their own; nObs is what the stored counters are, never written */
+struct CullImage {
+    const float* thDepth;          /* nK */
+    const uint8_t* kfFlags;        /* nK */
+    const int32_t* octave;         /* parallel to kfMp */
+    const float* depth;
+    const uint8_t* stereo;
+    const int32_t* nObs;           /* nP */
+    const int32_t* obsIdx;         /* parallel to obs */
+};
+
+/* the counts of a called key frame as the record launch found them */
+struct CullSpec {
+    int32_t nMPs, nRedundant;
+    unsigned long long walked;
+};
+
+/* One call.  The working state is scratch: the resident image is only read.  A chunk is the positions [j0, j1) of the call, whose
+ * records lie from 0 in rec, key frame after key frame (recOff). */
+struct CullLaunch {
+    CullState S;                   /* the working arrays in scratch, the image and the attributes resident */
+    int32_t monocular;
+    int32_t j0, j1;
+    int32_t maxRow;                /* the longest row of the chunk */
+    /* staged */
+    const int32_t* called;         /* the call's slots, in call order */
+    const int32_t* pos;            /* nK: position in the call or -1 */
+    const int32_t* recOff;         /* one more than positions: entries of the called rows before each */
+    /* scratch */
+    CullRecord* rec;               /* the chunk's */
+    int32_t* claim;                /* nP: 0xff bytes before the first chunk; the position whose erasure took the point last */
+    uint8_t* touched;              /* nP: zero before each chunk; the point lost an observation since the chunk's records */
+    CullSpec* spec;                /* per position: zero before the first chunk */
+    /* out */
+    int32_t* out;                  /* CULL_OUT_WORDS per position of the call */
+};
+/* the records of the chunk, then its walk */
+hipError_t drfe_launch_cull_chunk(const CullLaunch& L, hipStream_t s);
 
 #endif

@@ -1,6 +1,7 @@
-/* lmap_store.h — the local-map store itself: its rows by handle, the flat image of them, the optional geometry and the device
- * copies, for the two files that implement its entries: lmap.cpp (Tracking::UpdateLocalMap and KeyFrame::UpdateConnections,
- * DESIGN.md sections 25 and 26) and lmap_correct.cpp (the Sim3 propagation of LoopClosing::CorrectLoop, section 27). */
+/* lmap_store.h — the local-map store itself: its rows by handle, the flat image of them, the optional geometry and culling
+ * attributes and the device copies, for the three files that implement its entries: lmap.cpp (Tracking::UpdateLocalMap and
+ * KeyFrame::UpdateConnections, DESIGN.md sections 25 and 26), lmap_correct.cpp (the Sim3 propagation of LoopClosing::CorrectLoop,
+ * section 27) and lmap_cull.cpp (LocalMapping::KeyFrameCulling with KeyFrame::SetBadFlag, section 28). */
 #ifndef DRFE_LMAP_STORE_H
 #define DRFE_LMAP_STORE_H
 
@@ -45,6 +46,30 @@ struct GeoImage {
     std::vector<float> kfTcw, kfOw, mpWorld;
     std::vector<int32_t> mpRef, mpLevel, mpBy, mpByRef;
     bool complete = false;
+};
+
+/* what KeyFrameCulling reads of a key frame (mThDepth, the flags byte of cull_core.h, and octave, depth and stereo parallel to
+ * its match row) and of a map point (nObs as the reference holds it, mit->second parallel to its observations) */
+struct KfCull {
+    float thDepth = 0.0f;
+    uint8_t flags = 0;
+    std::vector<int32_t> octave;
+    std::vector<float> depth;
+    std::vector<uint8_t> stereo;
+};
+
+struct MpCull {
+    int32_t nObs = 0;
+    std::vector<int32_t> obsIdx;
+};
+
+/* the attributes by slot, next to the image; has = the item has attributes that fit its row.  live is one flag per stored
+ * observation, all set between calls: the walk clears what it erases and the commit compacts. */
+struct CullAttr {
+    std::vector<uint8_t> kfHas, mpHas, kfFlags, stereo, live;
+    std::vector<float> thDepth, depth;
+    std::vector<int32_t> octave, nObs, obsIdx;
+    bool complete = false;             /* every stored item has attributes that fit and every index is inside its row */
 };
 
 /* the graph with every handle resolved to a slot: what the host walk and the kernels read */
@@ -110,6 +135,20 @@ struct drfe_lmap {
     int64_t corrStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     DevBuf<char> dGeo;
     CorrImage dCorr;
+    /* the optional attributes of KeyFrameCulling, by handle, and their image by slot */
+    std::unordered_map<int32_t, lmap_store::KfCull> kfCull;
+    std::unordered_map<int32_t, lmap_store::MpCull> mpCull;
+    lmap_store::CullAttr cull;
+    bool cullDirty = true;             /* the attribute image lacks an edit of the rows or of the attributes */
+    bool devCullDirty = true;          /* the device copy lacks the attribute image */
+    bool devCullTailDirty = false;     /* or only its counters and observation indices, the end of the block */
+    /* what a cull call committed into the image and the device copy of the rows block still lacks */
+    bool devObsDirty = false;          /* the observations and their offsets, the end of the block */
+    std::vector<int32_t> devNulls;     /* match-row entries set to -1 */
+    int64_t sentBytes[4] = {0, 0, 0, 0};   /* host-to-device bytes of the rows, graph, geometry and attribute blocks */
+    int64_t cullStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    DevBuf<char> dCullBlock;
+    CullImage dCull;
     /* the host walk's stamps, kept between calls: an item is stamped for the query whose serial it holds */
     std::vector<int32_t> stampP, stampL, inP, inL;
     int32_t serial = 0;
@@ -121,7 +160,7 @@ struct drfe_lmap {
     PinnedBuf<char> hup, hgraph, hlist;
 };
 
-/* lmap.cpp's, for lmap_correct.cpp: the error of a refused call; the image of the rows, rebuilt when an edit made it stale
+/* lmap.cpp's, for lmap_correct.cpp and lmap_cull.cpp: the error of a refused call; the image of the rows, rebuilt when an edit made it stale
  * (DRFE_ERR_STATE and the name of the reference when one dangles); the image on the device, sent when it is stale */
 int lmap_fail(drfe_lmap* db, int rc, const std::string& why);
 int lmap_build_image(drfe_lmap* db);

@@ -75,6 +75,8 @@ SYMBOLS = (
     "drfe_lmap_set_scales", "drfe_lmap_get_scales", "drfe_lmap_set_poses", "drfe_lmap_get_poses",
     "drfe_lmap_set_point_geometry", "drfe_lmap_get_point_geometry", "drfe_lmap_correct_host", "drfe_lmap_correct_device",
     "drfe_lmap_correct_batch", "drfe_lmap_correct_limits", "drfe_lmap_correct_scratch", "drfe_lmap_correct_stats",
+    "drfe_lmap_set_cull_attributes", "drfe_lmap_get_cull_attributes", "drfe_lmap_cull_host", "drfe_lmap_cull_device",
+    "drfe_lmap_cull_batch", "drfe_lmap_cull_limits", "drfe_lmap_cull_scratch", "drfe_lmap_cull_stats", "drfe_lmap_upload_bytes",
 )
 
 FAST_CELL_DTYPE = np.dtype([(n, "<i4") for n in ("level", "x0", "y0", "ww", "wh", "offX", "offY", "cellIdx", "ncp", "rpl", "nrb",
@@ -338,6 +340,34 @@ LMAP_CORRECT_OUT_FIELDS = ("walk_pos", "corrected", "non_corrected", "Tiw", "n_p
 class LmapCorrectOut(C.Structure):
     _fields_ = [("points_capacity", C.c_int32), ("pad", C.c_int32)] + [
         (k, C.c_void_p) for k in LMAP_CORRECT_OUT_FIELDS]                            # drfe_lmap_correct_out
+
+
+LMAP_CULL_STATS = ("calls", "keyframes", "device_calls", "culled", "deferred", "points_bad", "observers_walked", "empty_begin")
+LMAP_CULL_LIMITS = ("record_tile", "device_from", "entry_bytes", "walk_threads")
+CULL_NOT_ERASE, CULL_ORIGIN, CULL_TO_BE_ERASED = 1, 2, 4                             # the bits of a key frame's flags byte
+CULL_KEPT, CULL_CULLED, CULL_DEFERRED, CULL_SKIPPED_ORIGIN = 0, 1, 2, 3              # record[:, 3]
+# the bits of drfe_lmap_cull_out.flags after CONN_WEIGHTS, CONN_ORDERED, CONN_PARENT
+CULL_CHILDREN, CULL_NULLED, CULL_WENT_BAD = 8, 16, 32
+LMAP_CULL_ATTR_FIELDS = ("kf_handle", "th_depth", "kf_flags", "row_offsets", "octave", "depth", "stereo", "point_handle", "n_obs",
+                         "obs_offsets", "obs_index")
+
+
+class LmapCullAttributes(C.Structure):
+    _fields_ = [("n_kfs", C.c_int32), ("n_points", C.c_int32)] + [
+        (k, C.c_void_p) for k in LMAP_CULL_ATTR_FIELDS]                              # drfe_lmap_cull_attributes
+
+
+class LmapCullAttributesOut(C.Structure):
+    _fields_ = [("n_kfs", C.c_int32), ("n_points", C.c_int32), ("row_capacity", C.c_int32), ("obs_capacity", C.c_int32)] + [
+        (k, C.c_void_p) for k in LMAP_CULL_ATTR_FIELDS]                              # drfe_lmap_cull_attributes_out
+
+
+class LmapCullOut(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("touched_capacity", "children_capacity", "nulled_capacity", "points_capacity",
+                                         "obs_capacity", "pad")] + [(k, C.c_void_p) for k in (
+        "record", "Tcp", "has_Tcp", "n_culled", "culled", "n_touched", "touched")] + [("rows", LmapConnRows)] + [
+        (k, C.c_void_p) for k in ("flags", "children_offsets", "children", "nulled_offsets", "nulled", "n_points", "points",
+                                  "point_n_obs", "point_ref", "point_bad", "obs_offsets", "obs", "obs_index")]   # drfe_lmap_cull_out
 
 
 class InitProblems(C.Structure):
@@ -626,6 +656,15 @@ def load() -> C.CDLL:
     L.drfe_lmap_correct_limits.argtypes = [vp]
     L.drfe_lmap_correct_scratch.argtypes = [vp, i32, vp, vp]
     L.drfe_lmap_correct_stats.argtypes = [vp, vp]
+    L.drfe_lmap_set_cull_attributes.argtypes = [vp, vp]
+    L.drfe_lmap_get_cull_attributes.argtypes = [vp, vp]
+    L.drfe_lmap_cull_host.argtypes = [vp, i32, vp, i32, vp]
+    L.drfe_lmap_cull_device.argtypes = [vp, i32, vp, i32, vp, vp]
+    L.drfe_lmap_cull_batch.argtypes = [vp, i32, vp, i32, vp, vp]
+    L.drfe_lmap_cull_limits.argtypes = [vp]
+    L.drfe_lmap_cull_scratch.argtypes = [vp, i32, vp, vp]
+    L.drfe_lmap_cull_stats.argtypes = [vp, vp]
+    L.drfe_lmap_upload_bytes.argtypes = [vp, vp]
     L.drfe_pnp_stats.argtypes = [vp, vp]
     L.drfe_lines_is_good_batch.argtypes = [vp, vp, vp, vp]
     L.drfe_line3d_chunk_frames.argtypes = [i32]
@@ -1983,6 +2022,130 @@ class LocalMap:
         m = int(r["n_points"][0])
         res = {k: r[k][:n].copy() for k in ("walk_pos", "corrected", "non_corrected", "Tiw")}
         res.update({k: r[k][:m].copy() for k in LMAP_CORRECT_OUT_FIELDS[5:]})
+        return res
+
+    # ---- LocalMapping::KeyFrameCulling with KeyFrame::SetBadFlag on the store ----
+
+    @staticmethod
+    def cull_limits():
+        out = np.zeros(4, np.int32)
+        rc = load().drfe_lmap_cull_limits(_p(out))
+        if rc != 0:
+            raise DrfeError(f"drfe_lmap_cull_limits failed ({rc})")
+        return dict(zip(LMAP_CULL_LIMITS, (int(v) for v in out)))
+
+    def cull_stats(self):
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_lmap_cull_stats(self.h, _p(st)), "drfe_lmap_cull_stats")
+        return dict(zip(LMAP_CULL_STATS, (int(v) for v in st)))
+
+    def upload_bytes(self):
+        """host-to-device bytes since the store was made: dict of rows, graph, geometry, attributes"""
+        out = np.zeros(4, np.int64)
+        self._chk(self.L.drfe_lmap_upload_bytes(self.h, _p(out)), "drfe_lmap_upload_bytes")
+        return dict(zip(("rows", "graph", "geometry", "attributes"), (int(v) for v in out)))
+
+    def cull_scratch(self, handles):
+        """bytes of device scratch a cull call of these key frames takes: (as one chunk, at least, shared by every chunk)"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        out = np.zeros(3, np.int64)
+        self._chk(self.L.drfe_lmap_cull_scratch(self.h, len(hs), _p(hs), _p(out)), "drfe_lmap_cull_scratch")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def set_cull_attributes(self, kfs=(), points=()):
+        """kfs: dicts with handle, th_depth, and optionally flags (CULL_NOT_ERASE | CULL_ORIGIN | CULL_TO_BE_ERASED) and octave,
+        depth, stereo parallel to the match row.  points: dicts with handle, n_obs and obs_index parallel to the observations."""
+        kh = np.array([r["handle"] for r in kfs], np.int32)
+        th = np.array([r["th_depth"] for r in kfs], np.float32)
+        fl = np.array([r.get("flags", 0) for r in kfs], np.uint8)
+        roff, octv = _csr_i32([r.get("octave", ()) for r in kfs])
+        dep = np.ascontiguousarray(np.concatenate([np.asarray(r.get("depth", ()), np.float32).reshape(-1) for r in kfs])
+                                   if len(kfs) else [], np.float32)
+        ste = np.ascontiguousarray(np.concatenate([np.asarray(r.get("stereo", ()), np.uint8).reshape(-1) for r in kfs])
+                                   if len(kfs) else [], np.uint8)
+        if len(dep) != len(octv) or len(ste) != len(octv):
+            raise ValueError("octave, depth and stereo of a key frame must have one length")
+        ph = np.array([r["handle"] for r in points], np.int32)
+        nobs = np.array([r["n_obs"] for r in points], np.int32)
+        ooff, oidx = _csr_i32([r.get("obs_index", ()) for r in points])
+        A = LmapCullAttributes(len(kh), len(ph), _p(kh), _p(th), _p(fl), _p(roff), _p(octv), _p(dep), _p(ste), _p(ph), _p(nobs),
+                               _p(ooff), _p(oidx))
+        self._chk(self.L.drfe_lmap_set_cull_attributes(self.h, C.byref(A)), "drfe_lmap_set_cull_attributes")
+
+    def get_cull_attributes(self, kf_handles=(), point_handles=()):
+        """the stored attributes: dict of kfs (dicts with handle, th_depth, flags, octave, depth, stereo) and points (dicts with
+        handle, n_obs, obs_index)"""
+        kh = np.ascontiguousarray(kf_handles, np.int32)
+        ph = np.ascontiguousarray(point_handles, np.int32)
+        nk, npt = len(kh), len(ph)
+        cap = 1 << 12
+        while True:
+            r = {"th_depth": np.zeros(max(1, nk), np.float32), "kf_flags": np.zeros(max(1, nk), np.uint8),
+                 "row_offsets": np.zeros(nk + 1, np.int32), "octave": np.zeros(cap, np.int32), "depth": np.zeros(cap, np.float32),
+                 "stereo": np.zeros(cap, np.uint8), "n_obs": np.zeros(max(1, npt), np.int32),
+                 "obs_offsets": np.zeros(npt + 1, np.int32), "obs_index": np.zeros(cap, np.int32)}
+            O = LmapCullAttributesOut(nk, npt, cap, cap, _p(kh), _p(r["th_depth"]), _p(r["kf_flags"]), _p(r["row_offsets"]),
+                                      _p(r["octave"]), _p(r["depth"]), _p(r["stereo"]), _p(ph), _p(r["n_obs"]), _p(r["obs_offsets"]),
+                                      _p(r["obs_index"]))
+            rc = self.L.drfe_lmap_get_cull_attributes(self.h, C.byref(O))
+            if rc != ERR_CAPACITY or cap >= (1 << 28):
+                break
+            cap *= 8
+        self._chk(rc, "drfe_lmap_get_cull_attributes")
+        ro, oo = r["row_offsets"], r["obs_offsets"]
+        return {"kfs": [{"handle": int(kh[i]), "th_depth": r["th_depth"][i], "flags": int(r["kf_flags"][i]),
+                         "octave": r["octave"][ro[i]:ro[i + 1]].copy(), "depth": r["depth"][ro[i]:ro[i + 1]].copy(),
+                         "stereo": r["stereo"][ro[i]:ro[i + 1]].copy()} for i in range(nk)],
+                "points": [{"handle": int(ph[i]), "n_obs": int(r["n_obs"][i]), "obs_index": r["obs_index"][oo[i]:oo[i + 1]].copy()}
+                           for i in range(npt)]}
+
+    def cull(self, handles, monocular=False, mode="batch", capacity=None):
+        """KeyFrameCulling over `handles` (GetVectorCovisibleKeyFrames() of the current key frame, in that order).  Returns a dict:
+        per called key frame record [n, 4] (nMPs, nRedundant, verdict, action), Tcp [n, 4, 4], has_Tcp [n]; culled (handles in
+        order); per touched key frame (ascending rank) touched, flags, parent, first, weights, ordered, children, nulled; per
+        touched point (ascending handle) points, point_n_obs, point_ref, point_bad, obs and obs_index (one array per point).
+        capacity: (touched, weights, ordered, children, nulled, points, obs); default: arrays grown until the call fits (a call
+        that does not fit changes nothing)."""
+        hs = np.ascontiguousarray(handles, np.int32)
+        n = len(hs)
+        fn = getattr(self.L, f"drfe_lmap_cull_{mode}")
+        grow = capacity is None
+        caps = [1 << 10, 1 << 14, 1 << 14, 1 << 12, 1 << 12, 1 << 12, 1 << 14] if grow else [int(c) for c in capacity]
+        while True:
+            ct, cw, co, cch, cnu, cp, cob = caps
+            r, rows = self._conn_rows(ct, cw, co)
+            c = {"record": np.zeros((max(1, n), 4), np.int32), "Tcp": np.zeros((max(1, n), 4, 4), np.float32),
+                 "has_Tcp": np.zeros(max(1, n), np.uint8), "n_culled": np.zeros(1, np.int32), "culled": np.zeros(max(1, n), np.int32),
+                 "n_touched": np.zeros(1, np.int32), "touched": np.zeros(max(1, ct), np.int32), "flags": np.zeros(max(1, ct), np.uint8),
+                 "children_offsets": np.zeros(ct + 1, np.int32), "children": np.zeros(max(1, cch), np.int32),
+                 "nulled_offsets": np.zeros(ct + 1, np.int32), "nulled": np.zeros(max(1, cnu), np.int32),
+                 "n_points": np.zeros(1, np.int32), "points": np.zeros(max(1, cp), np.int32),
+                 "point_n_obs": np.zeros(max(1, cp), np.int32), "point_ref": np.zeros(max(1, cp), np.int32),
+                 "point_bad": np.zeros(max(1, cp), np.uint8), "obs_offsets": np.zeros(cp + 1, np.int32),
+                 "obs": np.zeros(max(1, cob), np.int32), "obs_index": np.zeros(max(1, cob), np.int32)}
+            out = LmapCullOut(ct, cch, cnu, cp, cob, 0, _p(c["record"]), _p(c["Tcp"]), _p(c["has_Tcp"]), _p(c["n_culled"]),
+                              _p(c["culled"]), _p(c["n_touched"]), _p(c["touched"]), rows, _p(c["flags"]), _p(c["children_offsets"]),
+                              _p(c["children"]), _p(c["nulled_offsets"]), _p(c["nulled"]), _p(c["n_points"]), _p(c["points"]),
+                              _p(c["point_n_obs"]), _p(c["point_ref"]), _p(c["point_bad"]), _p(c["obs_offsets"]), _p(c["obs"]),
+                              _p(c["obs_index"]))
+            args = (self.h, n, _p(hs), 1 if monocular else 0, C.byref(out)) + (() if mode == "host" else (None,))
+            rc = fn(*args)
+            if not (grow and rc == ERR_CAPACITY and caps[0] < (1 << 26)
+                    and b"the call returns more than" in self.L.drfe_lmap_last_error(self.h)):
+                break
+            caps = [v * 8 for v in caps]
+        self._chk(rc, f"drfe_lmap_cull_{mode}")
+        nt, npt, nc = int(c["n_touched"][0]), int(c["n_points"][0]), int(c["n_culled"][0])
+        res = self._conn_unpack(r, nt)
+        co_, no_, oo = c["children_offsets"], c["nulled_offsets"], c["obs_offsets"]
+        res.update(record=c["record"][:n].copy(), Tcp=c["Tcp"][:n].copy(), has_Tcp=c["has_Tcp"][:n].copy(),
+                   culled=c["culled"][:nc].copy(), touched=c["touched"][:nt].copy(), flags=c["flags"][:nt].copy(),
+                   children=[c["children"][co_[k]:co_[k + 1]].copy() for k in range(nt)],
+                   nulled=[c["nulled"][no_[k]:no_[k + 1]].copy() for k in range(nt)],
+                   points=c["points"][:npt].copy(), point_n_obs=c["point_n_obs"][:npt].copy(),
+                   point_ref=c["point_ref"][:npt].copy(), point_bad=c["point_bad"][:npt].copy(),
+                   obs=[c["obs"][oo[k]:oo[k + 1]].copy() for k in range(npt)],
+                   obs_index=[c["obs_index"][oo[k]:oo[k + 1]].copy() for k in range(npt)])
         return res
 
 

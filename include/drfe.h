@@ -1880,6 +1880,140 @@ int drfe_lmap_correct_scratch(drfe_lmap* db, int32_t n, const int32_t* handles, 
  * geometry. */
 int drfe_lmap_correct_stats(drfe_lmap* db, int64_t* stats /* 8 */);
 
+/* LocalMapping::KeyFrameCulling (src/LocalMapping.cc:1226-1285) with KeyFrame::SetBadFlag (src/KeyFrame.cc:574-683) underneath it,
+ * on the same store: the one entry that takes something away.  DESIGN.md section 28.  Parity with a build of the reference's
+ * LocalMapping.cc and KeyFrame.cc is not pinned.
+ *
+ * The attributes it reads are optional; a store without them behaves as before.  Per key frame: mThDepth, a flags byte (bit 0
+ * mbNotErase, bit 1 mnId == 0, bit 2 mbToBeErased) and three arrays parallel to its match row: mvKeysUn[i].octave, mvDepth[i] and
+ * mvuRight[i] >= 0.  Per map point: the nObs counter as the reference holds it (it is not derived from the observations) and
+ * mit->second of every stored observation, parallel to them.  A setter row replaces the stored one, may name a handle that is not
+ * stored yet, and is uploaded before the next device call in a block of its own: an edit of the attributes does not send the
+ * graph again.  Attributes whose arrays do not have the length of the stored row count as missing.  drfe_lmap_remove drops them
+ * with the item. */
+typedef struct drfe_lmap_cull_attributes {
+    int32_t n_kfs, n_points;
+    const int32_t* kf_handle;         /* n_kfs */
+    const float* th_depth;            /* n_kfs */
+    const uint8_t* kf_flags;          /* n_kfs */
+    const int32_t* row_offsets;       /* n_kfs + 1 */
+    const int32_t* octave;            /* by row_offsets */
+    const float* depth;
+    const uint8_t* stereo;
+    const int32_t* point_handle;      /* n_points */
+    const int32_t* n_obs;             /* n_points */
+    const int32_t* obs_offsets;       /* n_points + 1 */
+    const int32_t* obs_index;         /* by obs_offsets */
+} drfe_lmap_cull_attributes;
+int drfe_lmap_set_cull_attributes(drfe_lmap* db, const drfe_lmap_cull_attributes* rows);
+/* The stored attributes of the named items (one without: DRFE_ERR_INVALID); the handle arrays are read, the others written when
+ * row_capacity / obs_capacity hold them (DRFE_ERR_CAPACITY otherwise).  n_kfs or n_points may be 0. */
+typedef struct drfe_lmap_cull_attributes_out {
+    int32_t n_kfs, n_points, row_capacity, obs_capacity;
+    const int32_t* kf_handle;
+    float* th_depth;
+    uint8_t* kf_flags;
+    int32_t* row_offsets;
+    int32_t* octave;
+    float* depth;
+    uint8_t* stereo;
+    const int32_t* point_handle;
+    int32_t* n_obs;
+    int32_t* obs_offsets;
+    int32_t* obs_index;
+} drfe_lmap_cull_attributes_out;
+int drfe_lmap_get_cull_attributes(drfe_lmap* db, drfe_lmap_cull_attributes_out* out);
+
+/* A call names n handles: GetVectorCovisibleKeyFrames() of the current key frame, in that order (at most DRFE_LMAP_MAX_QUERIES).
+ * The walk order is the caller's, not rank order.  A handle named twice, an unknown one or a key frame that is already bad is
+ * refused with DRFE_ERR_INVALID.  The mbNewPlane early return, map lines and planes, Map::EraseKeyFrame and
+ * KeyFrameDatabase::erase stay with the caller, which gets the culled list; the decision reads none of them.
+ *
+ * Kept from the reference, per called key frame in order.  One with flag bit 1 is skipped (action 3).  Its match row is walked in
+ * index order; null and bad entries are skipped; with monocular == 0 an entry with depth > th_depth || depth < 0 is skipped (as
+ * written: a NaN depth counts); every other entry adds to nMPs.  Only when the point's n_obs > 3 is its observer list looked at:
+ * the key frame itself is skipped, an observer counts when octave(observer, obs_index) <= octave + 1, and three of them make the
+ * entry redundant.  The verdict is nRedundant > 0.9 * nMPs with the product in double.
+ *
+ * A verdict on a key frame with flag bit 0 only sets its bit 2 (action 2).  Otherwise (action 1) every key frame of its weights
+ * row that holds it loses the entry and gets its ordered row sorted again from all its weights (descending weight, descending
+ * rank among equals: AddConnection's rule), and its neighbours refreshed from the first ten.  Every non-null entry of its match
+ * row, bad or not, in index order, gets EraseObservation: when the point's observations hold the key frame, n_obs drops by 2
+ * where stereo[obs_index] is set and by 1 otherwise, the observation goes, the point's reference key frame - when the store has
+ * its geometry and it was this key frame - becomes the lowest-ranked remaining observer (with none left the stored value stays
+ * and the read is counted: the reference reads begin() of an empty map), and with n_obs <= 2 the point goes bad: its observations
+ * are cleared and every remaining observer's match-row entry at its obs_index is set to null, whatever stands there.  The key
+ * frame's own weights and ordered rows are cleared.  The spanning tree follows as written: parent candidates start as the key
+ * frame's parent; per round every child that is not bad, in rank order, has its ordered row compared with the candidates and
+ * the pair with the greatest weight wins (strict >, from -1; the weight is the child's own for that key frame, 0 when it has
+ * none), the winning child takes that parent, becomes a candidate and leaves the children; a round without a winner sends every
+ * remaining child, bad ones included, to the key frame's parent and leaves them in its child set.  The parent loses the key frame
+ * as a child, Tcp = Tcw * Twc(parent) is the float 4x4 product of section 27 when both have poses, and the key frame is bad.
+ * Later key frames of the call see all of it.
+ *
+ * A call is refused with DRFE_ERR_STATE and a message that names the item, and changes nothing, when a called key frame that is
+ * not the origin, a point in its row or an observer of such a point lacks attributes, when an obs_index of such a point lies
+ * outside its observer's row, or when a key frame the walk culls has no parent (the reference would dereference null). */
+typedef struct drfe_lmap_cull_out {
+    int32_t touched_capacity, children_capacity, nulled_capacity, points_capacity, obs_capacity;
+    int32_t pad;
+    /* per called key frame, in the caller's order */
+    int32_t* record;                  /* n x 4: nMPs, nRedundant, verdict, action (0 kept, 1 culled, 2 deferred by mbNotErase,
+                                         3 skipped origin) */
+    float* Tcp;                       /* n x 16: mTcp of a culled key frame, zeros otherwise */
+    uint8_t* has_Tcp;                 /* n: 1 when Tcp was computed */
+    int32_t* n_culled;                /* 1 */
+    int32_t* culled;                  /* n: the culled key frames in order */
+    /* per key frame whose rows, parent, children, match row or bad flag changed, in ascending rank: the final state */
+    int32_t* n_touched;               /* 1 */
+    int32_t* touched;                 /* touched_capacity handles */
+    drfe_lmap_conn_rows rows;         /* its arrays hold touched_capacity (+ 1) rows */
+    uint8_t* flags;                   /* touched_capacity: bit 0 the weights row, bit 1 the ordered row, bit 2 the parent, bit 3 the
+                                         children differ from what was stored, bit 4 match-row entries were nulled, bit 5 it went bad */
+    int32_t* children_offsets;        /* touched_capacity + 1 */
+    int32_t* children;                /* children_capacity, ascending rank */
+    int32_t* nulled_offsets;          /* touched_capacity + 1 */
+    int32_t* nulled;                  /* nulled_capacity: the match-row indices set to null, ascending */
+    /* per map point that lost an observation, in ascending handle: the final state */
+    int32_t* n_points;                /* 1 */
+    int32_t* points;                  /* points_capacity handles */
+    int32_t* point_n_obs;
+    int32_t* point_ref;               /* the reference key frame, or -1 when the store has no geometry of the point */
+    uint8_t* point_bad;
+    int32_t* obs_offsets;             /* points_capacity + 1 */
+    int32_t* obs;                     /* obs_capacity: the remaining observations in stored order */
+    int32_t* obs_index;               /* obs_capacity */
+} drfe_lmap_cull_out;
+/* key frames in a call from which drfe_lmap_cull_batch of a store with a context uses the device.  Measured (DESIGN.md section 28,
+ * profiles/cull_timing.jsonl) the device entry wins from 4 key frames a call when nothing is culled and does not win at every
+ * store size when a tenth of the call is culled, so there is no such size: the constant stands above DRFE_LMAP_MAX_QUERIES and
+ * _batch runs on the host; _device is there to be called. */
+enum { DRFE_LMAP_CULL_DEVICE_FROM = 4097 };
+/* _host always runs on the host, _device always on the device (DRFE_ERR_STATE without a context; DRFE_ERR_CAPACITY when the working
+ * state and the longest called row do not fit the configured scratch), _batch on the device from DRFE_LMAP_CULL_DEVICE_FROM key
+ * frames when the call fits.  All three return the same bytes and leave the same store.  When a capacity is too small the call
+ * returns DRFE_ERR_CAPACITY and nothing changes.  On success the call commits into the rows and the image in place; a call that
+ * culled nothing leaves the device image as it is, one that culled has the changed pieces sent before the next device call
+ * (drfe_lmap_upload_bytes). */
+int drfe_lmap_cull_host(drfe_lmap* db, int32_t n, const int32_t* handles, int32_t monocular, drfe_lmap_cull_out* out);
+int drfe_lmap_cull_device(drfe_lmap* db, int32_t n, const int32_t* handles, int32_t monocular, drfe_lmap_cull_out* out, void* stream);
+int drfe_lmap_cull_batch(drfe_lmap* db, int32_t n, const int32_t* handles, int32_t monocular, drfe_lmap_cull_out* out, void* stream);
+/* out[0] entries of a match row that one record workgroup takes, [1] DRFE_LMAP_CULL_DEVICE_FROM, [2] bytes of scratch per
+ * match-row entry of a chunk, [3] threads of the walking workgroup */
+int drfe_lmap_cull_limits(int32_t* out4);
+/* the scratch a device call of these handles takes: out[0] bytes with which it runs as one chunk, [1] the least bytes with which
+ * it runs at all (one key frame a chunk), [2] the part every chunk shares (the working state) */
+int drfe_lmap_cull_scratch(drfe_lmap* db, int32_t n, const int32_t* handles, int64_t* out3);
+/* Counters since the store was created: stats[0] cull calls, [1] called key frames, [2] calls run on the device, [3] key frames
+ * culled, [4] deferred by mbNotErase, [5] points gone bad, [6] observers walked (the lists the decision looked at), [7] reads of
+ * begin() of an empty observation map. */
+int drfe_lmap_cull_stats(drfe_lmap* db, int64_t* stats /* 8 */);
+/* Host-to-device bytes since the store was created, per block of the device image: out[0] the rows block (bad flags, match rows,
+ * observations), [1] the graph block, [2] the geometry, [3] the culling attributes.  After a cull call the next device call sends
+ * the bad flags, 4 bytes per nulled match-row entry, the observations with their offsets when a row got shorter, the graph
+ * block, and the counters and observation indices of the attributes; the match rows stay where they are. */
+int drfe_lmap_upload_bytes(drfe_lmap* db, int64_t* out4);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

@@ -3667,6 +3667,111 @@ public:
         }
         return sims;
     }
+
+    /* LocalMapping::KeyFrameCulling (src/LocalMapping.cc:1226-1285) with KeyFrame::SetBadFlag on the store.
+     * Further accessors of KeyFrameT: the public mThDepth, mvKeysUn (.octave), mvDepth, mvuRight and mbNewPlane, SetBadFlag(), and
+     * two getters that the integrator adds because mbNotErase and mbToBeErased are protected:
+     * GetNotErase() and GetToBeErased(); of MapPointT: Observations() and GetObservations(). */
+    /* what the walk reads of pKF: mThDepth, the flags, and octave, depth and stereo of every entry of its match row.  Call it
+     * with Sync(pKF): the arrays have to fit the row the store holds. */
+    void SyncCulling(KeyFrameT* pKF)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const int32_t handle = (int32_t)pKF->mnId;
+        const float th = (float)pKF->mThDepth;
+        const uint8_t flags = (uint8_t)((pKF->GetNotErase() ? 1 : 0) | (pKF->mnId == 0 ? 2 : 0) | (pKF->GetToBeErased() ? 4 : 0));
+        const size_t n = pKF->GetMapPointMatches().size();
+        std::vector<int32_t> octave(n);
+        std::vector<float> depth(n);
+        std::vector<uint8_t> stereo(n);
+        for (size_t i = 0; i < n; i++) {
+            octave[i] = (int32_t)pKF->mvKeysUn[i].octave;
+            depth[i] = (float)pKF->mvDepth[i];
+            stereo[i] = pKF->mvuRight[i] >= 0 ? 1 : 0;
+        }
+        const int32_t off[2] = {0, (int32_t)n};
+        drfe_lmap_cull_attributes a = {};
+        a.n_kfs = 1;
+        a.kf_handle = &handle; a.th_depth = &th; a.kf_flags = &flags; a.row_offsets = off;
+        a.octave = octave.data(); a.depth = depth.data(); a.stereo = stereo.data();
+        Check(drfe_lmap_set_cull_attributes(mDb, &a), "drfe_lmap_set_cull_attributes");
+    }
+    /* nObs and mit->second of every observation of pMP, in the order Sync(pMP) sends the observations */
+    void SyncCulling(MapPointT* pMP)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const int32_t handle = (int32_t)pMP->mnId;
+        const int32_t nObs = (int32_t)pMP->Observations();
+        std::vector<int32_t> idx;
+        for (const auto& o : pMP->GetObservations()) idx.push_back((int32_t)o.second);
+        const int32_t off[2] = {0, (int32_t)idx.size()};
+        drfe_lmap_cull_attributes a = {};
+        a.n_points = 1;
+        a.point_handle = &handle; a.n_obs = &nObs; a.obs_offsets = off; a.obs_index = idx.data();
+        Check(drfe_lmap_set_cull_attributes(mDb, &a), "drfe_lmap_set_cull_attributes");
+    }
+    /* KeyFrameCulling() for mpCurrentKeyFrame = pCurrentKF and mbMonocular = bMonocular.  The store must hold the current rows,
+     * connections and culling attributes of the covisible key frames, of the points in their match rows and of those points'
+     * observers (Sync, SyncConnections, SyncCulling).  The store decides and takes the culled key frames out of its own graph;
+     * then every key frame with a verdict gets its own SetBadFlag() in that order, which does the same to the objects and sees to
+     * map lines, planes, the map and the key-frame database (and only sets mbToBeErased where mbNotErase holds).  Returns the
+     * culled key frames in order. */
+    std::vector<KeyFrameT*> KeyFrameCulling(KeyFrameT* pCurrentKF, bool bMonocular)
+    {
+        std::vector<KeyFrameT*> culled;
+        if (pCurrentKF->mbNewPlane) return culled;
+        const std::vector<KeyFrameT*> vpLocalKeyFrames = pCurrentKF->GetVectorCovisibleKeyFrames();
+        const size_t n = vpLocalKeyFrames.size();
+        if (n == 0) return culled;
+        std::unique_lock<std::mutex> lock(mMutex);
+        std::vector<int32_t> handles(n);
+        size_t rows = 1;
+        for (size_t k = 0; k < n; k++) {
+            handles[k] = (int32_t)vpLocalKeyFrames[k]->mnId;
+            rows += vpLocalKeyFrames[k]->GetMapPointMatches().size();
+        }
+        int32_t size[3] = {0, 0, 0};
+        Check(drfe_lmap_size(mDb, size), "drfe_lmap_size");
+        const size_t nK = (size_t)size[0] + 1;
+        std::vector<int32_t> rec(4 * n), culledH(n), touched(nK), parent(nK), rwOff(nK + 1), roOff(nK + 1), chOff(nK + 1), nuOff(nK + 1);
+        std::vector<int32_t> rwKf, rwW, roKf, roW, ch, nulled, points, pNObs, pRef, obsOff, obs, obsIdx;
+        std::vector<float> Tcp(16 * n);
+        std::vector<uint8_t> hasTcp(n), flags(nK), rFirst(nK), pBad;
+        int32_t nCulled = 0, nTouched = 0, nPoints = 0;
+        /* a call touches at most the points of the called rows; the rows of connections and children grow until the call fits (a
+         * call that does not fit changes nothing) */
+        for (size_t cap = 64 * (n + 16) + 1024;; cap *= 4) {
+            rwKf.resize(cap); rwW.resize(cap); roKf.resize(cap); roW.resize(cap); ch.resize(cap); nulled.resize(cap * 4);
+            points.resize(rows); pNObs.resize(rows); pRef.resize(rows); pBad.resize(rows); obsOff.resize(rows + 1);
+            obs.resize(cap * 16); obsIdx.resize(cap * 16);
+            drfe_lmap_cull_out o = {};
+            o.touched_capacity = (int32_t)nK; o.children_capacity = (int32_t)cap; o.nulled_capacity = (int32_t)(cap * 4);
+            o.points_capacity = (int32_t)rows; o.obs_capacity = (int32_t)(cap * 16);
+            o.record = rec.data(); o.Tcp = Tcp.data(); o.has_Tcp = hasTcp.data(); o.n_culled = &nCulled; o.culled = culledH.data();
+            o.n_touched = &nTouched; o.touched = touched.data(); o.flags = flags.data();
+            o.rows.weights_capacity = o.rows.ordered_capacity = (int32_t)cap;
+            o.rows.weight_offsets = rwOff.data(); o.rows.weight_kfs = rwKf.data(); o.rows.weight_w = rwW.data();
+            o.rows.ordered_offsets = roOff.data(); o.rows.ordered_kfs = roKf.data(); o.rows.ordered_w = roW.data();
+            o.rows.parent = parent.data(); o.rows.first_connection = rFirst.data();
+            o.children_offsets = chOff.data(); o.children = ch.data(); o.nulled_offsets = nuOff.data(); o.nulled = nulled.data();
+            o.n_points = &nPoints; o.points = points.data(); o.point_n_obs = pNObs.data(); o.point_ref = pRef.data();
+            o.point_bad = pBad.data(); o.obs_offsets = obsOff.data(); o.obs = obs.data(); o.obs_index = obsIdx.data();
+            const int32_t mono = bMonocular ? 1 : 0;
+            const int rc = mForce < 0 ? drfe_lmap_cull_host(mDb, (int32_t)n, handles.data(), mono, &o)
+                         : mForce > 0 ? drfe_lmap_cull_device(mDb, (int32_t)n, handles.data(), mono, &o, nullptr)
+                                      : drfe_lmap_cull_batch(mDb, (int32_t)n, handles.data(), mono, &o, nullptr);
+            if (rc == DRFE_ERR_CAPACITY && cap < ((size_t)1 << 26) &&
+                std::string(drfe_lmap_last_error(mDb)).find("the call returns more than") != std::string::npos)
+                continue;
+            Check(rc, "drfe_lmap_cull");
+            break;
+        }
+        lock.unlock();
+        for (size_t k = 0; k < n; k++)
+            if (rec[4 * k + 2]) vpLocalKeyFrames[k]->SetBadFlag();       /* culled, or deferred by mbNotErase */
+        for (int32_t i = 0; i < nCulled; i++) culled.push_back(mKFs.at(culledH[(size_t)i]));
+        return culled;
+    }
     drfe_lmap* db() const { return mDb; }
 
 private:
