@@ -1,5 +1,5 @@
 /* kf_pose_core.h — what KeyFrame::SetPose (reference src/KeyFrame.cc:147-167) derives from Tcw, once, for the matchers' host
- * side (capi_match.cpp), the map store (lmap_correct.cpp) and the correction kernels (correct_kernels.hip).  Plain IEEE float
+ * side (capi_match.cpp), the map store (lmap_correct.cpp, lmap_gba.cpp) and its kernels (correct_kernels.hip, gba_kernels.hip).  Plain IEEE float
  * mul / add, compiled with -ffp-contract=off on both sides. */
 #ifndef DRFE_KF_POSE_CORE_H
 #define DRFE_KF_POSE_CORE_H

@@ -185,6 +185,7 @@ int build_image(drfe_lmap* db)
     db->devDirty = true;
     db->geoDirty = true;               /* the slots may have moved */
     db->cullDirty = true;
+    db->gbaDirty = true;
     return DRFE_OK;
 }
 
@@ -1367,6 +1368,7 @@ int drfe_lmap_remove(drfe_lmap* db, int kind, int32_t handle)
             db->conn.erase(handle);
             db->kfPose.erase(handle);
             db->kfCull.erase(handle);
+            db->kfGba.erase(handle);
             gone = 1;
         }
     } else if (kind == DRFE_LMAP_POINT) {
@@ -1374,6 +1376,7 @@ int drfe_lmap_remove(drfe_lmap* db, int kind, int32_t handle)
         if (gone) {
             db->mpGeo.erase(handle);
             db->mpCull.erase(handle);
+            db->mpGba.erase(handle);
         }
     } else if (kind == DRFE_LMAP_LINE) {
         gone = db->ml.erase(handle);
@@ -1506,11 +1509,11 @@ int drfe_lmap_connect_batch(drfe_lmap* db, int32_t n, const int32_t* handles, dr
     return conn_entry(db, n, handles, o, 2, stream);
 }
 
-int drfe_lmap_upload_bytes(drfe_lmap* db, int64_t* out4)
+int drfe_lmap_upload_bytes(drfe_lmap* db, int64_t* out5)
 {
-    if (!db || !out4) return DRFE_ERR_INVALID;
+    if (!db || !out5) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    std::memcpy(out4, db->sentBytes, sizeof(db->sentBytes));
+    std::memcpy(out5, db->sentBytes, sizeof(db->sentBytes));
     return DRFE_OK;
 }
 

@@ -513,6 +513,10 @@ int corr_entry(drfe_lmap* db, int32_t cur, const double* Scw, int32_t n, const i
 
 }  // namespace
 
+int lmap_build_geo(drfe_lmap* db) { return build_geo(db); }
+CorrImage lmap_geo_view(drfe_lmap* db) { return geo_view(db); }
+int lmap_upload_geo(drfe_lmap* db, hipStream_t st) { return upload_geo(db, st); }
+
 extern "C" {
 
 int drfe_lmap_set_scales(drfe_lmap* db, int32_t n_levels, const float* scale_factors)

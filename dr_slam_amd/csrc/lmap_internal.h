@@ -1,4 +1,5 @@
-/* lmap_internal.h — what lmap.cpp, lmap_correct.cpp and lmap_cull.cpp hand to the store's kernels (DESIGN.md sections 25 to 28). */
+/* lmap_internal.h — what lmap.cpp, lmap_correct.cpp, lmap_cull.cpp and lmap_gba.cpp hand to the store's kernels (DESIGN.md sections
+ * 25 to 29). */
 #ifndef DRFE_LMAP_INTERNAL_H
 #define DRFE_LMAP_INTERNAL_H
 
@@ -7,6 +8,7 @@
 #include "conn_core.h"
 #include "correct_core.h"
 #include "cull_core.h"
+#include "gba_core.h"
 
 /* threads of a workgroup: frame points and key-frame slots go across them in the vote, the entries of a match row in the gather */
 #define LMAP_THREADS 256
@@ -214,5 +216,45 @@ struct CullLaunch {
 };
 /* the records of the chunk, then its walk */
 hipError_t drfe_launch_cull_chunk(const CullLaunch& L, hipStream_t s);
+
+/* ---- the map update of LoopClosing::RunGlobalBundleAdjustment (gba_kernels.hip) ---- */
+/* point slots of one workgroup of the point launches, a lane each */
+#define GBA_TILE LMAP_THREADS
+/* bytes of scratch per point slot of a chunk: its kind byte, its packed record (slot, position, kind: 17 bytes) and its share of
+ * the workgroup counters, rounded up */
+#define GBA_POINT_BYTES 24
+/* bytes of scratch every chunk shares: alignment of the sections */
+#define GBA_FIXED_BYTES 1024
+
+/* One call.  The host has walked the integer graph: list is the visited key frames in the reference's FIFO order, and the composed
+ * ones among them lie round after round by their unstamped depth.  A chunk is the point slots [p0, p1). */
+struct GbaLaunch {
+    LmapImage I;                   /* resident */
+    CorrImage G;                   /* resident */
+    GbaImage B;                    /* resident */
+    int32_t loop;                  /* nLoopKF as a handle: the stamp */
+    int32_t nV;                    /* visited key frames */
+    int32_t nRounds;               /* the deepest unstamped chain */
+    int32_t p0, p1;
+    int32_t pkCap;                 /* records the packed arrays hold: the host's count of the fullest chunk */
+    /* staged */
+    const int32_t* list;           /* nV slots */
+    const int32_t* roundOff;       /* nRounds + 1 */
+    const int32_t* roundKf;        /* roundOff[nRounds] slots: the composed key frames, depth 1 first */
+    const int32_t* roundParent;    /* parallel: the slot of the key frame whose children row holds it */
+    /* scratch, per chunk */
+    uint8_t* kind;                 /* p1 - p0 */
+    int32_t* groupCnt;             /* workgroups of the chunk + 1: moved points of each, then their exclusive prefix */
+    int32_t* pkItem;               /* point slot */
+    float* pkWorld;                /* 3 each */
+    uint8_t* pkKind;
+    /* out */
+    float* outPose;                /* nV x 16, in list order: what SetPose received */
+    float* outBef;                 /* nV x 16: mTcwBefGBA */
+};
+/* the composed poses round after round, then every visited key frame's commit into the two resident blocks and its record */
+hipError_t drfe_launch_gba_keyframes(const GbaLaunch& L, hipStream_t s);
+/* the points of the chunk: moved in place, then packed in slot order; groupCnt[workgroups] is their number */
+hipError_t drfe_launch_gba_points(const GbaLaunch& L, hipStream_t s);
 
 #endif

@@ -1,7 +1,8 @@
 /* lmap_store.h — the local-map store itself: its rows by handle, the flat image of them, the optional geometry and culling
  * attributes and the device copies, for the three files that implement its entries: lmap.cpp (Tracking::UpdateLocalMap and
  * KeyFrame::UpdateConnections, DESIGN.md sections 25 and 26), lmap_correct.cpp (the Sim3 propagation of LoopClosing::CorrectLoop,
- * section 27) and lmap_cull.cpp (LocalMapping::KeyFrameCulling with KeyFrame::SetBadFlag, section 28). */
+ * section 27), lmap_cull.cpp (LocalMapping::KeyFrameCulling with KeyFrame::SetBadFlag, section 28) and lmap_gba.cpp (the map update
+ * of LoopClosing::RunGlobalBundleAdjustment, section 29). */
 #ifndef DRFE_LMAP_STORE_H
 #define DRFE_LMAP_STORE_H
 
@@ -70,6 +71,27 @@ struct CullAttr {
     std::vector<float> thDepth, depth;
     std::vector<int32_t> octave, nObs, obsIdx;
     bool complete = false;             /* every stored item has attributes that fit and every index is inside its row */
+};
+
+/* what RunGlobalBundleAdjustment's map update reads of a key frame (mTcwGBA, mTcwBefGBA, mnBAGlobalForKF) and of a map point
+ * (mPosGBA, mnBAGlobalForKF); a piece that was never given or left by a call is not there */
+struct KfGba {
+    float T[16] = {0}, bef[16] = {0};
+    int32_t stamp = 0;
+    uint8_t hasT = 0, hasBef = 0;
+};
+
+struct MpGba {
+    float X[3] = {0.0f, 0.0f, 0.0f};
+    int32_t stamp = 0;
+    uint8_t hasX = 0;
+};
+
+/* that state by slot, next to the image; an item without state has stamp 0 and no piece */
+struct GbaAttr {
+    std::vector<float> kfTcwGBA, kfBef, mpPosGBA;
+    std::vector<int32_t> kfStamp, mpStamp;
+    std::vector<uint8_t> kfHasT, kfHasBef, mpHasPos;
 };
 
 /* the graph with every handle resolved to a slot: what the host walk and the kernels read */
@@ -145,10 +167,19 @@ struct drfe_lmap {
     /* what a cull call committed into the image and the device copy of the rows block still lacks */
     bool devObsDirty = false;          /* the observations and their offsets, the end of the block */
     std::vector<int32_t> devNulls;     /* match-row entries set to -1 */
-    int64_t sentBytes[4] = {0, 0, 0, 0};   /* host-to-device bytes of the rows, graph, geometry and attribute blocks */
+    int64_t sentBytes[5] = {0, 0, 0, 0, 0};   /* host-to-device bytes of the rows, graph, geometry, attribute and adjustment blocks */
     int64_t cullStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     DevBuf<char> dCullBlock;
     CullImage dCull;
+    /* the optional state of the map update after a global bundle adjustment, by handle, and by slot */
+    std::unordered_map<int32_t, lmap_store::KfGba> kfGba;
+    std::unordered_map<int32_t, lmap_store::MpGba> mpGba;
+    lmap_store::GbaAttr gba;
+    bool gbaDirty = true;              /* the state by slot lacks an edit of the rows or of the state */
+    bool devGbaDirty = true;           /* the device copy lacks the state by slot */
+    int64_t gbaStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    DevBuf<char> dGbaBlock;
+    GbaImage dGba;
     /* the host walk's stamps, kept between calls: an item is stamped for the query whose serial it holds */
     std::vector<int32_t> stampP, stampL, inP, inL;
     int32_t serial = 0;
@@ -165,5 +196,10 @@ struct drfe_lmap {
 int lmap_fail(drfe_lmap* db, int rc, const std::string& why);
 int lmap_build_image(drfe_lmap* db);
 int lmap_upload_image(drfe_lmap* db, hipStream_t st);
+/* lmap_correct.cpp's, for lmap_gba.cpp: the geometry by slot, rebuilt when stale; its view; the geometry block on the device, sent
+ * when it is stale (after the image) */
+int lmap_build_geo(drfe_lmap* db);
+CorrImage lmap_geo_view(drfe_lmap* db);
+int lmap_upload_geo(drfe_lmap* db, hipStream_t st);
 
 #endif

@@ -77,6 +77,9 @@ SYMBOLS = (
     "drfe_lmap_correct_batch", "drfe_lmap_correct_limits", "drfe_lmap_correct_scratch", "drfe_lmap_correct_stats",
     "drfe_lmap_set_cull_attributes", "drfe_lmap_get_cull_attributes", "drfe_lmap_cull_host", "drfe_lmap_cull_device",
     "drfe_lmap_cull_batch", "drfe_lmap_cull_limits", "drfe_lmap_cull_scratch", "drfe_lmap_cull_stats", "drfe_lmap_upload_bytes",
+    "drfe_lmap_set_gba_keyframes", "drfe_lmap_set_gba_points", "drfe_lmap_get_gba_keyframes", "drfe_lmap_get_gba_points",
+    "drfe_lmap_gba_host", "drfe_lmap_gba_device", "drfe_lmap_gba_batch", "drfe_lmap_gba_limits", "drfe_lmap_gba_scratch",
+    "drfe_lmap_gba_stats",
 )
 
 FAST_CELL_DTYPE = np.dtype([(n, "<i4") for n in ("level", "x0", "y0", "ww", "wh", "offX", "offY", "cellIdx", "ncp", "rpl", "nrb",
@@ -340,6 +343,17 @@ LMAP_CORRECT_OUT_FIELDS = ("walk_pos", "corrected", "non_corrected", "Tiw", "n_p
 class LmapCorrectOut(C.Structure):
     _fields_ = [("points_capacity", C.c_int32), ("pad", C.c_int32)] + [
         (k, C.c_void_p) for k in LMAP_CORRECT_OUT_FIELDS]                            # drfe_lmap_correct_out
+
+
+LMAP_GBA_STATS = ("calls", "device_calls", "visited", "composed", "deepest_chain", "kind_pos", "kind_ref", "skipped_ref")
+LMAP_GBA_LIMITS = ("threads", "device_from", "depth_limit", "point_bytes", "fixed_bytes", "wavefront")
+GBA_POINT_POS, GBA_POINT_REF = 1, 2                                                  # drfe_lmap_gba_out.kind
+LMAP_GBA_OUT_FIELDS = ("n_keyframes", "keyframes", "Tcw", "TcwBef", "composed", "n_points", "points", "world", "kind")
+
+
+class LmapGbaOut(C.Structure):
+    _fields_ = [("keyframes_capacity", C.c_int32), ("points_capacity", C.c_int32)] + [
+        (k, C.c_void_p) for k in LMAP_GBA_OUT_FIELDS]                                # drfe_lmap_gba_out
 
 
 LMAP_CULL_STATS = ("calls", "keyframes", "device_calls", "culled", "deferred", "points_bad", "observers_walked", "empty_begin")
@@ -665,6 +679,16 @@ def load() -> C.CDLL:
     L.drfe_lmap_cull_scratch.argtypes = [vp, i32, vp, vp]
     L.drfe_lmap_cull_stats.argtypes = [vp, vp]
     L.drfe_lmap_upload_bytes.argtypes = [vp, vp]
+    L.drfe_lmap_set_gba_keyframes.argtypes = [vp, i32, vp, vp, vp]
+    L.drfe_lmap_set_gba_points.argtypes = [vp, i32, vp, vp, vp]
+    L.drfe_lmap_get_gba_keyframes.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.drfe_lmap_get_gba_points.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.drfe_lmap_gba_host.argtypes = [vp, i32, i32, vp, vp]
+    L.drfe_lmap_gba_device.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.drfe_lmap_gba_batch.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.drfe_lmap_gba_limits.argtypes = [vp]
+    L.drfe_lmap_gba_scratch.argtypes = [vp, vp]
+    L.drfe_lmap_gba_stats.argtypes = [vp, vp]
     L.drfe_pnp_stats.argtypes = [vp, vp]
     L.drfe_lines_is_good_batch.argtypes = [vp, vp, vp, vp]
     L.drfe_line3d_chunk_frames.argtypes = [i32]
@@ -2040,10 +2064,85 @@ class LocalMap:
         return dict(zip(LMAP_CULL_STATS, (int(v) for v in st)))
 
     def upload_bytes(self):
-        """host-to-device bytes since the store was made: dict of rows, graph, geometry, attributes"""
-        out = np.zeros(4, np.int64)
+        """host-to-device bytes since the store was made: dict of rows, graph, geometry, attributes, gba"""
+        out = np.zeros(5, np.int64)
         self._chk(self.L.drfe_lmap_upload_bytes(self.h, _p(out)), "drfe_lmap_upload_bytes")
-        return dict(zip(("rows", "graph", "geometry", "attributes"), (int(v) for v in out)))
+        return dict(zip(("rows", "graph", "geometry", "attributes", "gba"), (int(v) for v in out)))
+
+    # ---- the map update of LoopClosing::RunGlobalBundleAdjustment on the store (DESIGN.md section 29) ----
+
+    @staticmethod
+    def gba_limits():
+        out = np.zeros(6, np.int32)
+        rc = load().drfe_lmap_gba_limits(_p(out))
+        if rc != 0:
+            raise DrfeError(f"drfe_lmap_gba_limits failed ({rc})")
+        return dict(zip(LMAP_GBA_LIMITS, (int(v) for v in out)))
+
+    def gba_stats(self):
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_lmap_gba_stats(self.h, _p(st)), "drfe_lmap_gba_stats")
+        return dict(zip(LMAP_GBA_STATS, (int(v) for v in st)))
+
+    def gba_scratch(self):
+        """bytes of device scratch a gba call takes: (as one chunk, at least, shared by every chunk)"""
+        out = np.zeros(3, np.int64)
+        self._chk(self.L.drfe_lmap_gba_scratch(self.h, _p(out)), "drfe_lmap_gba_scratch")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def set_gba_keyframes(self, handles, TcwGBA, stamps):
+        """mTcwGBA [n, 4, 4] float32 and mnBAGlobalForKF (handles) as the adjustment's write-back left them"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        T = np.ascontiguousarray(TcwGBA, np.float32).reshape(len(hs), 16)
+        st = np.ascontiguousarray(stamps, np.int32).reshape(len(hs))
+        self._chk(self.L.drfe_lmap_set_gba_keyframes(self.h, len(hs), _p(hs), _p(T), _p(st)), "drfe_lmap_set_gba_keyframes")
+
+    def set_gba_points(self, handles, PosGBA, stamps):
+        """mPosGBA [n, 3] float32 and mnBAGlobalForKF (handles)"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        X = np.ascontiguousarray(PosGBA, np.float32).reshape(len(hs), 3)
+        st = np.ascontiguousarray(stamps, np.int32).reshape(len(hs))
+        self._chk(self.L.drfe_lmap_set_gba_points(self.h, len(hs), _p(hs), _p(X), _p(st)), "drfe_lmap_set_gba_points")
+
+    def get_gba_keyframes(self, handles):
+        """dict of TcwGBA [n, 4, 4], stamp [n], TcwBefGBA [n, 4, 4], has_TcwGBA [n], has_TcwBefGBA [n]"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        n = len(hs)
+        r = {"TcwGBA": np.zeros((n, 4, 4), np.float32), "stamp": np.zeros(n, np.int32), "TcwBefGBA": np.zeros((n, 4, 4), np.float32),
+             "has_TcwGBA": np.zeros(n, np.uint8), "has_TcwBefGBA": np.zeros(n, np.uint8)}
+        self._chk(self.L.drfe_lmap_get_gba_keyframes(self.h, n, _p(hs), *[_p(v) for v in r.values()]), "drfe_lmap_get_gba_keyframes")
+        return r
+
+    def get_gba_points(self, handles):
+        """dict of PosGBA [n, 3], stamp [n], has_PosGBA [n]"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        n = len(hs)
+        r = {"PosGBA": np.zeros((n, 3), np.float32), "stamp": np.zeros(n, np.int32), "has_PosGBA": np.zeros(n, np.uint8)}
+        self._chk(self.L.drfe_lmap_get_gba_points(self.h, n, _p(hs), *[_p(v) for v in r.values()]), "drfe_lmap_get_gba_points")
+        return r
+
+    def gba(self, loop, origins, mode="batch", capacity=None):
+        """The map update after a global bundle adjustment (src/LoopClosing.cc:722-783) for nLoopKF = `loop` from the origin key
+        frames.  Returns a dict: per visited key frame in the reference's FIFO order keyframes, Tcw [v, 4, 4], TcwBef [v, 4, 4],
+        composed; per moved point in ascending handle points, world [m, 3], kind.  capacity: (key frames, points), default the
+        sizes of the store (a call that does not fit changes nothing)."""
+        og = np.ascontiguousarray(origins, np.int32)
+        if capacity is None:
+            nk, npt, _ = self.size()
+            capacity = (nk, npt)
+        ck, cp = (int(c) for c in capacity)
+        k, m = max(1, ck), max(1, cp)
+        r = {"n_keyframes": np.zeros(1, np.int32), "keyframes": np.zeros(k, np.int32), "Tcw": np.zeros((k, 4, 4), np.float32),
+             "TcwBef": np.zeros((k, 4, 4), np.float32), "composed": np.zeros(k, np.uint8), "n_points": np.zeros(1, np.int32),
+             "points": np.zeros(m, np.int32), "world": np.zeros((m, 3), np.float32), "kind": np.zeros(m, np.uint8)}
+        out = LmapGbaOut(ck, cp, *[_p(r[f]) for f in LMAP_GBA_OUT_FIELDS])
+        fn = getattr(self.L, f"drfe_lmap_gba_{mode}")
+        args = (self.h, int(loop), len(og), _p(og), C.byref(out)) + (() if mode == "host" else (None,))
+        self._chk(fn(*args), f"drfe_lmap_gba_{mode}")
+        nv, nm = int(r["n_keyframes"][0]), int(r["n_points"][0])
+        res = {f: r[f][:nv].copy() for f in ("keyframes", "Tcw", "TcwBef", "composed")}
+        res.update({f: r[f][:nm].copy() for f in ("points", "world", "kind")})
+        return res
 
     def cull_scratch(self, handles):
         """bytes of device scratch a cull call of these key frames takes: (as one chunk, at least, shared by every chunk)"""

@@ -2009,10 +2009,88 @@ int drfe_lmap_cull_scratch(drfe_lmap* db, int32_t n, const int32_t* handles, int
  * begin() of an empty observation map. */
 int drfe_lmap_cull_stats(drfe_lmap* db, int64_t* stats /* 8 */);
 /* Host-to-device bytes since the store was created, per block of the device image: out[0] the rows block (bad flags, match rows,
- * observations), [1] the graph block, [2] the geometry, [3] the culling attributes.  After a cull call the next device call sends
+ * observations), [1] the graph block, [2] the geometry, [3] the culling attributes, [4] the state of the map update after a global
+ * bundle adjustment (below).  After a cull call the next device call sends
  * the bad flags, 4 bytes per nulled match-row entry, the observations with their offsets when a row got shorter, the graph
  * block, and the counters and observation indices of the attributes; the match rows stay where they are. */
-int drfe_lmap_upload_bytes(drfe_lmap* db, int64_t* out4);
+int drfe_lmap_upload_bytes(drfe_lmap* db, int64_t* out5);
+
+/* The map update that ends LoopClosing::RunGlobalBundleAdjustment (src/LoopClosing.cc:722-783) on the same store: the walk over the
+ * spanning tree that gives every key frame its new pose, then the move of every map point of the map.  The adjustment itself stays
+ * with the caller.  DESIGN.md section 29.  Parity with a build of the reference's LoopClosing.cc is not pinned.
+ *
+ * The state it reads is optional; a store that is never given it behaves as before.  Per key frame: mTcwGBA, mnBAGlobalForKF as a
+ * handle (0 when never given, as the constructors leave it) and mTcwBefGBA, which only a call leaves.  Per map point: mPosGBA and
+ * mnBAGlobalForKF.  The setters are what the integrator calls after Optimizer::BundleAdjustment's write-back (src/Optimizer.cc:
+ * 505-546): the last row of a handle wins, a row may name a handle that is not stored yet, drfe_lmap_remove drops the state with
+ * the item.  The state lies in a device block of its own: an edit of it sends neither the rows, the graph nor the geometry again. */
+int drfe_lmap_set_gba_keyframes(drfe_lmap* db, int32_t count, const int32_t* handles, const float* TcwGBA /* 16 each */,
+                                const int32_t* stamp);
+int drfe_lmap_set_gba_points(drfe_lmap* db, int32_t count, const int32_t* handles, const float* PosGBA /* 3 each */, const int32_t* stamp);
+/* each array may be NULL; has_TcwGBA and has_TcwBefGBA tell whether the matrix was ever stored (zeros otherwise).  A handle without
+ * state: DRFE_ERR_INVALID */
+int drfe_lmap_get_gba_keyframes(drfe_lmap* db, int32_t count, const int32_t* handles, float* TcwGBA, int32_t* stamp, float* TcwBefGBA,
+                                uint8_t* has_TcwGBA, uint8_t* has_TcwBefGBA);
+int drfe_lmap_get_gba_points(drfe_lmap* db, int32_t count, const int32_t* handles, float* PosGBA, int32_t* stamp, uint8_t* has_PosGBA);
+
+/* A call names loop, nLoopKF as a handle, and the origins, mpMap->mvpKeyFrameOrigins, each once (n_origins <= 0 or a duplicate:
+ * DRFE_ERR_INVALID).
+ *
+ * Kept from the reference.  A FIFO starts with the origins.  For the front key frame, Twc is the inverse of its pose before its
+ * own SetPose; its children are walked in rank order; a child whose stamp differs from loop gets mTcwGBA = (Tcw_child * Twc) *
+ * mTcwGBA_parent, two float 4x4 products, with the parent's mTcwGBA the adjustment's or itself composed a moment before, and takes
+ * the stamp; every child is pushed, stamped or not; then mTcwBefGBA = the pose and SetPose(mTcwGBA).  An origin is never composed
+ * and never stamped: it takes whatever mTcwGBA it holds.  isBad() is tested nowhere in the walk.  Then every map point of the
+ * store, in slot order: a bad point is skipped; a point whose stamp equals loop goes to mPosGBA (kind 1); otherwise, when its
+ * reference key frame's stamp after the walk differs from loop the point is skipped, else it goes through mTcwBefGBA of that key
+ * frame and the inverse of its new pose (kind 2): Xc = Rcw * X + tcw, then Rwc * Xc + twc, each a float dot with the C term added in
+ * double.  An unreached reference key frame that holds the stamp is used with the mTcwBefGBA an earlier call left, stale as it is.
+ * The reference key frame's badness is not tested.  With loop == 0 and untouched stamps everything counts as stamped.
+ * UpdateNormalAndDepth is not called, and map lines and planes are not touched although the adjustment stamps them too. */
+typedef struct drfe_lmap_gba_out {
+    int32_t keyframes_capacity;       /* visited key frames; the number of stored key frames always suffices */
+    int32_t points_capacity;          /* moved points; the number of stored points always suffices */
+    /* per visited key frame, in the reference's FIFO order */
+    int32_t* n_keyframes;             /* 1 */
+    int32_t* keyframes;               /* handles */
+    float* Tcw;                       /* 16 each: the pose SetPose receives */
+    float* TcwBef;                    /* 16 each: mTcwBefGBA */
+    uint8_t* composed;                /* 1 = composed through the parent (and stamped), 0 = the mTcwGBA it held */
+    /* per moved point, in ascending slot (ascending handle) */
+    int32_t* n_points;                /* 1 */
+    int32_t* points;                  /* handles */
+    float* world;                     /* 3 each: the new position */
+    uint8_t* kind;                    /* 1 = mPosGBA, 2 = through the reference key frame */
+} drfe_lmap_gba_out;
+/* stored points from which drfe_lmap_gba_batch of a store with a context uses the device (the measured crossover, DESIGN.md
+ * section 29, profiles/gba_propagate_timing.jsonl: the smallest measured store from which the device entry wins at every stamp
+ * mix, the setters that precede a call included) */
+enum { DRFE_LMAP_GBA_DEVICE_FROM = 125000 };
+/* _host always runs on the host, _device always on the device (DRFE_ERR_STATE without a context; DRFE_ERR_CAPACITY when the
+ * configured scratch does not hold one point slot), _batch on the device from DRFE_LMAP_GBA_DEVICE_FROM stored points when the call
+ * fits.  All three return the same bytes and leave the same store.  A refused call changes nothing: DRFE_ERR_STATE, with a message
+ * that names the item, when an origin is unknown; when a visited key frame has no pose; when an origin, or a visited key frame
+ * that holds the stamp, has no mTcwGBA; when a key frame would be visited twice (in two children rows, an origin in a children
+ * row, a cycle); when a point that is not bad has no geometry (it either moves, and its position is part of its geometry, or is
+ * asked for its reference key frame); when a point of kind 1 has no mPosGBA; when a point that is not bad and does not hold the
+ * stamp has an unknown reference key frame, or would move with kind 2 through a key frame without a pose, or through an unreached
+ * one without a stored mTcwBefGBA; DRFE_ERR_CAPACITY when a capacity is too small.  On success the call commits poses (with Ow and
+ * Twc), mTcwBefGBA, the composed mTcwGBA, the key-frame stamps and the positions into the store, and on the device into the
+ * resident geometry and state blocks in place, with no upload of what it wrote. */
+int drfe_lmap_gba_host(drfe_lmap* db, int32_t loop, int32_t n_origins, const int32_t* origins, drfe_lmap_gba_out* out);
+int drfe_lmap_gba_device(drfe_lmap* db, int32_t loop, int32_t n_origins, const int32_t* origins, drfe_lmap_gba_out* out, void* stream);
+int drfe_lmap_gba_batch(drfe_lmap* db, int32_t loop, int32_t n_origins, const int32_t* origins, drfe_lmap_gba_out* out, void* stream);
+/* out[0] threads of a workgroup = point slots of one, [1] DRFE_LMAP_GBA_DEVICE_FROM, [2] the depth of unstamped chain the in-launch
+ * loop handles (0 = any: one workgroup loops over the rounds), [3] bytes of scratch per point slot of a chunk, [4] bytes of scratch
+ * every chunk shares, [5] lanes of a wavefront */
+int drfe_lmap_gba_limits(int32_t* out6);
+/* the scratch a device call takes: out[0] bytes with which it runs as one chunk, [1] the least bytes with which it runs at all
+ * (one point slot a chunk), [2] the part every chunk shares */
+int drfe_lmap_gba_scratch(drfe_lmap* db, int64_t* out3);
+/* Counters since the store was created: stats[0] calls, [1] calls run on the device, [2] key frames visited, [3] key frames
+ * composed, [4] the deepest unstamped chain seen, [5] points of kind 1, [6] points of kind 2, [7] points skipped for a reference
+ * key frame without the stamp. */
+int drfe_lmap_gba_stats(drfe_lmap* db, int64_t* stats /* 8 */);
 
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */

@@ -3668,6 +3668,69 @@ public:
         return sims;
     }
 
+    /* The map update that ends LoopClosing::RunGlobalBundleAdjustment (src/LoopClosing.cc:722-783) on the store (DESIGN.md section
+     * 29).  Further accessors: the public mTcwGBA, mTcwBefGBA and mnBAGlobalForKF of KeyFrameT, mPosGBA and mnBAGlobalForKF of
+     * MapPointT.  Call SyncGlobalBA for what Optimizer::BundleAdjustment's write-back touched (an empty mTcwGBA / mPosGBA is not
+     * sent: the item then has no state, as a key frame or point made while the adjustment ran). */
+    void SyncGlobalBA(KeyFrameT* pKF)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        if (pKF->mTcwGBA.empty()) return;
+        const int32_t handle = (int32_t)pKF->mnId, stamp = (int32_t)pKF->mnBAGlobalForKF;
+        float T[16];
+        for (int r = 0; r < 4; r++)
+            for (int c = 0; c < 4; c++) T[r * 4 + c] = pKF->mTcwGBA.template ptr<float>(r)[c];
+        Check(drfe_lmap_set_gba_keyframes(mDb, 1, &handle, T, &stamp), "drfe_lmap_set_gba_keyframes");
+    }
+    void SyncGlobalBA(MapPointT* pMP)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        if (pMP->mPosGBA.empty()) return;
+        const int32_t handle = (int32_t)pMP->mnId, stamp = (int32_t)pMP->mnBAGlobalForKF;
+        float X[3];
+        for (int k = 0; k < 3; k++) X[k] = pMP->mPosGBA.template ptr<float>(k)[0];
+        Check(drfe_lmap_set_gba_points(mDb, 1, &handle, X, &stamp), "drfe_lmap_set_gba_points");
+    }
+    /* Lines :722-783 for nLoopKF and mpMap->mvpKeyFrameOrigins = vpOrigins.  The store must hold the current rows and geometry of
+     * every key frame and map point of the map (Sync, SyncGeometry) and the adjustment's results (SyncGlobalBA).  Writes mTcwGBA,
+     * mTcwBefGBA, mnBAGlobalForKF and SetPose into the visited key frames in the order of the reference's FIFO and SetWorldPos
+     * into the moved points; returns the visited key frames in that order. */
+    std::vector<KeyFrameT*> PropagateGlobalBA(unsigned long nLoopKF, const std::vector<KeyFrameT*>& vpOrigins)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        std::vector<int32_t> origins;
+        for (KeyFrameT* pKF : vpOrigins) origins.push_back((int32_t)pKF->mnId);
+        int32_t size[3] = {0, 0, 0};
+        Check(drfe_lmap_size(mDb, size), "drfe_lmap_size");
+        const size_t capK = (size_t)size[0] + 1, capP = (size_t)size[1] + 1;
+        std::vector<int32_t> kfs(capK), points(capP);
+        std::vector<float> Tcw(16 * capK), bef(16 * capK), world(3 * capP);
+        std::vector<uint8_t> composed(capK), kind(capP);
+        int32_t nKfs = 0, nPoints = 0;
+        drfe_lmap_gba_out o = {};
+        o.keyframes_capacity = (int32_t)capK; o.points_capacity = (int32_t)capP;
+        o.n_keyframes = &nKfs; o.keyframes = kfs.data(); o.Tcw = Tcw.data(); o.TcwBef = bef.data(); o.composed = composed.data();
+        o.n_points = &nPoints; o.points = points.data(); o.world = world.data(); o.kind = kind.data();
+        const int32_t loop = (int32_t)nLoopKF;
+        Check(mForce < 0 ? drfe_lmap_gba_host(mDb, loop, (int32_t)origins.size(), origins.data(), &o)
+            : mForce > 0 ? drfe_lmap_gba_device(mDb, loop, (int32_t)origins.size(), origins.data(), &o, nullptr)
+                         : drfe_lmap_gba_batch(mDb, loop, (int32_t)origins.size(), origins.data(), &o, nullptr), "drfe_lmap_gba");
+        using ::drfe::drfe_detail_sim3::mat32;
+        std::vector<KeyFrameT*> visited;
+        for (int32_t v = 0; v < nKfs; v++) {
+            KeyFrameT* pKF = mKFs.at(kfs[(size_t)v]);
+            if (composed[(size_t)v]) {
+                pKF->mTcwGBA = mat32(4, 4, &Tcw[16 * (size_t)v]);
+                pKF->mnBAGlobalForKF = nLoopKF;
+            }
+            pKF->mTcwBefGBA = mat32(4, 4, &bef[16 * (size_t)v]);
+            pKF->SetPose(mat32(4, 4, &Tcw[16 * (size_t)v]));
+            visited.push_back(pKF);
+        }
+        for (int32_t t = 0; t < nPoints; t++) mMPs.at(points[(size_t)t])->SetWorldPos(mat32(3, 1, &world[3 * (size_t)t]));
+        return visited;
+    }
+
     /* LocalMapping::KeyFrameCulling (src/LocalMapping.cc:1226-1285) with KeyFrame::SetBadFlag on the store.
      * Further accessors of KeyFrameT: the public mThDepth, mvKeysUn (.octave), mvDepth, mvuRight and mbNewPlane, SetBadFlag(), and
      * two getters that the integrator adds because mbNotErase and mbToBeErased are protected:
