@@ -266,6 +266,7 @@ int drfe_create(const drfe_config* cfg, drfe_ctx** out)
         c->fastGeneric = (e && e[0] == '1') ? 1 : 0;
         const char* es = std::getenv("DRFE_FAST_SCREEN");
         c->fastScreen = (es && es[0] >= '0' && es[0] <= '2') ? es[0] - '0' : 2;     /* 0 never, 1 at minThFAST only (rounds 3-4), 2 at iniThFAST first */
+        c->qtForceN = drfe_quadtree_parse_force(std::getenv("DRFE_QT_FORCE"), c->qtForce);
         const char* el = std::getenv("DRFE_LEVEL0_COPY");
         c->level0Copy = (el && el[0] == '1') ? 1 : 0;                                /* drfe_orb_configure_level0 */
         c->lastInPlace = 0;

@@ -92,6 +92,27 @@ struct DevGeom {
     DevLevel lv[DRFE_MAX_LEVELS];
 };
 
+/* k_quadtree<threads, keys per thread, node-list capacity>: every instantiation the library holds, X(threads, kpt, maxn).
+ * threads * kpt candidate keys of a level live in registers (the rest take the global arrays), 2 * threads >= maxn >= kpCap.
+ * Order: the two node capacities of the 512-thread kernel, then by falling register capacity. */
+#define DRFE_QT_INSTANCES(X) X(512, 16, DRFE_QT_MAX_NODES) X(512, 16, 256) X(256, 12, 256) X(64, 20, 128)
+struct QtInstance { int threads, kpt, maxn; };
+extern const QtInstance drfe_qt_instances[];
+extern const int drfe_qt_ninstances;
+struct QtLaunch { int level0, nlevels, inst; };          /* levels [level0, level0 + nlevels) run drfe_qt_instances[inst] */
+struct QtPlan {
+    int inst[DRFE_MAX_LEVELS];                           /* per level */
+    int nlaunch;
+    QtLaunch launch[DRFE_MAX_LEVELS];                    /* runs of equal inst[], in level order */
+};
+/* Candidates the plan provides registers for on a level of `pixels` pixels (orb_geometry.cpp). */
+int drfe_quadtree_design_load(int pixels);
+/* The instantiation of every level and the launches of a batch of nframes frames, from the geometry alone.  force: nforce
+ * (threads, kpt) pairs of DRFE_QT_FORCE - one pair for every level, or one pair per level (the last one repeated); a level a
+ * pair is not legal for (no such instantiation with maxn >= kpCap) keeps its own choice. */
+void drfe_quadtree_plan(const DevGeom& g, int nframes, const int* force, int nforce, QtPlan* plan);
+int drfe_quadtree_parse_force(const char* text, int* pairs);   /* -> number of pairs (at most DRFE_MAX_LEVELS); malformed text: 0 */
+
 /* FAST's per-(slot, level) candidate counters are bumped by one returning atomic per cell, and every wavefront waits for its
  * answer: packed as [slot][level] ints, four slots share a 128-byte line and the kernel's time depended on where the 16 KB array
  * happened to lie (0.59 / 0.66 / 0.69 / 0.71 ms from context to context, tools/fast_mode_probe2.py).  One counter per line. */
@@ -166,6 +187,8 @@ struct drfe_ctx {
     int fastScreen;           /* k_fast_cells_cols' screened paths; 2 (default): at iniThFAST first (textured cells), then at minThFAST (low-texture cells); 1: at
                                * minThFAST only; 0: never.  DRFE_FAST_SCREEN in the environment sets it (A/B, tests) */
     int fastGeneric;          /* DRFE_FAST_GENERIC=1 in the environment: run k_fast_cells even where k_fast_cells_cols fits (A/B, tests) */
+    int qtForce[2 * DRFE_MAX_LEVELS]; /* DRFE_QT_FORCE=<threads>,<kpt>[;<threads>,<kpt>...] in the environment: (threads, kpt) pairs for */
+    int qtForceN = 0;         /* drfe_quadtree_plan (A/B, tests); 0 pairs: the plan's own choice */
     int level0Copy;           /* drfe_orb_configure_level0 / DRFE_LEVEL0_COPY=1: 1 = the batch entry always copies level 0 into the arena */
     int lastInPlace;          /* 1: the most recent drfe_launch_orb read level 0 in place */
     bool level0Staged = false; /* drfe_orb_extract's plain path is inside drfe_orb_extract_batch with the context's staging buffer */

@@ -374,3 +374,100 @@ int drfe_build_geometry(drfe_ctx* c, int w, int h, DevGeom* g, std::vector<FastC
     g->totalTiles = tiles ? (int)tiles->size() : 0;
     return DRFE_OK;
 }
+
+/* ------------------------------------------------------------------------------------------------ */
+/* k_quadtree: which instantiation a level runs                                                      */
+
+#define X(T, K, M) {T, K, M},
+const QtInstance drfe_qt_instances[] = {DRFE_QT_INSTANCES(X)};
+#undef X
+const int drfe_qt_ninstances = (int)(sizeof(drfe_qt_instances) / sizeof(drfe_qt_instances[0]));
+
+/* FAST candidates per pixel fall with the level's size: on rendered indoor frames at 640x480 / 1.2 / 8 levels from 2.4 % of
+ * 307 k pixels on level 0 to 0.8 % of 24 k on level 7 (7286 / 4070 / 2454 / 1489 / 947 / 587 / 363 / 202 candidates at most).
+ * load = 2.66 % * pixels * (pixels / 307200)^0.36 lies 12 - 25 % above every one of them; a level that has more keeps the
+ * rest in the global arrays. */
+int drfe_quadtree_design_load(int pixels)
+{
+    return (int)std::ceil(0.0266 * (double)pixels * std::pow((double)pixels / 307200.0, 0.36));
+}
+
+/* DRFE_QT_FORCE: "<threads>,<kpt>" pairs separated by ';' -> out[2 * pairs]; anything malformed gives no pairs */
+int drfe_quadtree_parse_force(const char* s, int* out)
+{
+    int n = 0;
+    while (s && *s && n < DRFE_MAX_LEVELS) {
+        char* e = nullptr;
+        const long t = std::strtol(s, &e, 10);
+        if (e == s || *e != ',') return 0;
+        s = e + 1;
+        const long k = std::strtol(s, &e, 10);
+        if (e == s || (*e && *e != ';') || t <= 0 || k <= 0) return 0;
+        out[2 * n] = (int)t; out[2 * n + 1] = (int)k;
+        n++;
+        s = *e ? e + 1 : e;
+    }
+    return n;
+}
+
+int drfe_orb_quadtree_plan(const drfe_config* cfg, int width, int height, int nframes, const char* force, int32_t* out)
+{
+    if (!cfg || !out || cfg->nlevels < 1 || cfg->nlevels > DRFE_MAX_LEVELS || width <= 0 || height <= 0 || nframes < 1) return DRFE_ERR_INVALID;
+    drfe_ctx* c = new drfe_ctx();
+    c->cfg = *cfg;
+    drfe_build_tables(c);
+    DevGeom g;
+    int rc = drfe_build_geometry(c, width, height, &g, nullptr, nullptr, nullptr);
+    if (rc == DRFE_OK) {
+        int pairs[2 * DRFE_MAX_LEVELS];
+        QtPlan plan;
+        drfe_quadtree_plan(g, nframes, pairs, drfe_quadtree_parse_force(force, pairs), &plan);
+        for (int i = 0; i < plan.nlaunch; i++)
+            for (int l = plan.launch[i].level0; l < plan.launch[i].level0 + plan.launch[i].nlevels; l++) {
+                const QtInstance& q = drfe_qt_instances[plan.inst[l]];
+                int32_t* o = out + 5 * l;
+                o[0] = q.threads; o[1] = q.kpt; o[2] = q.maxn; o[3] = g.lv[l].kpCap; o[4] = i;
+            }
+        rc = plan.nlaunch;
+    }
+    delete c;
+    return rc;
+}
+
+void drfe_quadtree_plan(const DevGeom& g, int nframes, const int* force, int nforce, QtPlan* plan)
+{
+    const int nl = g.nlevels;
+    /* a batch whose workgroups are all resident at once (2 x 512 threads per CU) finishes soonest as ONE launch of the
+     * 512-thread kernel: it is latency-bound and a second launch would only queue behind the first */
+    const bool small = nl * nframes <= 2 * 256;
+    int capMax = 0;
+    for (int l = 0; l < nl; l++) capMax = std::max(capMax, g.lv[l].kpCap);
+    for (int l = 0; l < nl; l++) {
+        const DevLevel& L = g.lv[l];
+        int pick = -1;
+        if (nforce > 0) {
+            const int* f = force + 2 * std::min(l, nforce - 1);
+            for (int i = 0; i < drfe_qt_ninstances && pick < 0; i++) {
+                const QtInstance& q = drfe_qt_instances[i];
+                /* of the 512-thread kernel's two node capacities the small one where it holds the level */
+                if (q.threads == f[0] && q.kpt == f[1] && q.maxn >= L.kpCap && !(q.maxn > 256 && L.kpCap <= 256)) pick = i;
+            }
+        }
+        if (pick < 0 && small) pick = capMax > 256 ? 0 : 1;
+        if (pick < 0) {
+            /* the smallest instantiation whose registers hold the design load; none does: the largest */
+            const int load = drfe_quadtree_design_load(L.w * L.h);
+            pick = L.kpCap > 256 ? 0 : 1;
+            for (int i = drfe_qt_ninstances - 1; i >= 1; i--) {
+                const QtInstance& q = drfe_qt_instances[i];
+                if (q.maxn >= L.kpCap && q.threads * q.kpt >= load) { pick = i; break; }
+            }
+        }
+        plan->inst[l] = pick;
+    }
+    plan->nlaunch = 0;
+    for (int l = 0; l < nl; l++) {
+        if (l > 0 && plan->inst[l] == plan->inst[l - 1]) { plan->launch[plan->nlaunch - 1].nlevels++; continue; }
+        plan->launch[plan->nlaunch++] = QtLaunch{l, 1, plan->inst[l]};
+    }
+}

@@ -839,8 +839,30 @@ __global__ __launch_bounds__(64) void k_fast_cells_cols(const FastCell* __restri
 /* quadtree                                                                                          */
 
 /* k_quadtree<QT_THREADS, QT_KPT, QT_MAXN>: workgroup size, candidate keys a thread keeps in registers,
- * node-list capacity.  The host picks <512,16,*> for the large levels and <256,8,256> for the small ones
- * (less LDS and fewer registers -> more workgroups per CU). */
+ * node-list capacity.  drfe_quadtree_plan (orb_geometry.cpp) gives every level the instantiation of
+ * DRFE_QT_INSTANCES whose register capacity QT_THREADS * QT_KPT covers the level's expected candidates:
+ * fewer threads and registers -> more workgroups per CU.  QT_THREADS == 64 is one wavefront: no barrier
+ * and no wave totals, LDS operations of one wave execute in order. */
+
+/* the second __launch_bounds__ argument (waves per SIMD) of every instantiation:
+ * <512,16,*> 6 (80 VGPRs, three workgroups per CU); <256,12,256> 7 (72 VGPRs, seven workgroups per CU; 8 would leave
+ * three registers in scratch); <64,20,128> 4 (121 VGPRs, sixteen wavefronts per CU, twice what 2048 of them need) */
+#ifndef QT_WAVES_256
+#define QT_WAVES_256 7
+#endif
+template <int QT_THREADS> struct QtWaves { static constexpr int value = QT_THREADS == 512 ? 6 : QT_THREADS == 256 ? QT_WAVES_256 : 4; };
+
+/* workgroup barrier of the kernel; for a single wavefront only the point no LDS access is moved across */
+template <int QT_THREADS> __device__ __forceinline__ void qt_sync()
+{
+    if (QT_THREADS > 64) {
+        __syncthreads();
+    } else {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}
 
 template <int QT_THREADS, int QT_MAXN> struct QtShared {
     short x0[2][QT_MAXN], x1[2][QT_MAXN], y0[2][QT_MAXN], y1[2][QT_MAXN]; /* UL.x, UR.x, UL.y, BR.y */
@@ -863,6 +885,11 @@ template <int QT_THREADS> __device__ __forceinline__ int qt_scan2(int a, int b, 
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int s = a + b;
     const int incl = drfe_wave_incl_scan(s, lane);
+    if (QT_THREADS == 64) {                        /* one wavefront: its own scan is the block scan */
+        exA = incl - s;
+        exB = exA + a;
+        return __builtin_amdgcn_readlane(incl, 63);
+    }
     if (lane == 63) wtot[w] = incl;
     __syncthreads();
     int before = 0, total = 0;
@@ -914,7 +941,7 @@ template <class SH> __device__ __forceinline__ int qt_child_slot(const SH& S, in
  * rule of SURVEY.md §9.1) and stop as soon as the list holds N nodes (:730).  Keys never move: each
  * carries the list position of its node. */
 template <int QT_THREADS, int QT_KPT, int QT_MAXN>
-__global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : 6) void k_quadtree(const DevGeom* __restrict__ G, int levelBase,
+__global__ __launch_bounds__(QT_THREADS, QtWaves<QT_THREADS>::value) void k_quadtree(const DevGeom* __restrict__ G, int levelBase,
                                                          const uint32_t* __restrict__ cand0,
                                                          const uint32_t* __restrict__ cand1,
                                                          uint16_t* __restrict__ node,
@@ -922,8 +949,12 @@ __global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : 6) void k_quadt
                                                          uint32_t* __restrict__ sel, int* __restrict__ selCount,
                                                          int* __restrict__ status)
 {
+    static_assert(2 * QT_THREADS >= QT_MAXN, "step C gives every thread two list positions");
+    static_assert(QT_THREADS % 64 == 0 && QT_KPT % 2 == 0, "whole wavefronts; node positions are packed in pairs");
     __shared__ QtShared<QT_THREADS, QT_MAXN> S;
-    const int level = levelBase + blockIdx.x, slot = blockIdx.y, tid = threadIdx.x;
+    /* level-major grid: workgroups are handed out largest level first, so the places the small levels free early are
+     * refilled with small levels, not with another frame's level 0 */
+    const int level = levelBase + blockIdx.y, slot = blockIdx.x, tid = threadIdx.x;
     const DevLevel& L = G->lv[level];
     const int n = min(candCount[DRFE_CC_IDX(slot, level)], L.candCap);
     const size_t coff = (size_t)slot * G->candSlotElems + L.candOff;
@@ -945,7 +976,7 @@ __global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : 6) void k_quadt
         S.isNew[0][i] = 0;
     }
     if (tid == 0) { S.err = 0; S.finish = 0; S.phase = 1; S.nExp = 0; S.take = 0x7FFFFFFF; }
-    __syncthreads();
+    qt_sync<QT_THREADS>();
     /* keys (x | y << 12 | score << 24) and their node positions live in registers: QT_KPT per thread;
      * only a level with more than QT_KPT * QT_THREADS candidates spills the rest to the global arrays */
     uint32_t rk[QT_KPT], rn2[QT_KPT / 2];     /* node positions: two 16-bit fields per register */
@@ -972,7 +1003,7 @@ __global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : 6) void k_quadt
         if (kb + tid < n) { r = min((int)((float)(int)(k0[kb + tid] & 0xFFF) / L.hX), nIni - 1); nd[kb + tid] = (uint16_t)r; }
         qt_wave_add(S.cnt[0], r);
     }
-    __syncthreads();
+    qt_sync<QT_THREADS>();
     /* erase empty roots, :577-590 */
     if (tid == 0) {
         int m = 0;
@@ -986,10 +1017,10 @@ __global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : 6) void k_quadt
         }
         S.len = m;
     }
-    __syncthreads();
+    qt_sync<QT_THREADS>();
     if (S.len != nIni)
         QT_FOR_KEYS({ NODE = (uint32_t)S.newPos[NODE]; })
-    __syncthreads();
+    qt_sync<QT_THREADS>();
 
     int cur = 0;
     while (true) {
@@ -1008,7 +1039,7 @@ __global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : 6) void k_quadt
             S.newPos[i] = c ? (int)(((uint32_t)ci << 10) | (uint32_t)(QT_MAXN - 1 - i)) : 0;
             S.ccnt[4 * i] = 0; S.ccnt[4 * i + 1] = 0; S.ccnt[4 * i + 2] = 0; S.ccnt[4 * i + 3] = 0;
         }
-        __syncthreads();
+        qt_sync<QT_THREADS>();
         /* B. DivideNode key association (:512-526) for every candidate node */
         {
             /* while the list is short thousands of keys fall on a handful of counters: same-address LDS
@@ -1027,7 +1058,7 @@ __global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : 6) void k_quadt
                 if (agg) qt_wave_add(S.ccnt, tgt); else if (tgt >= 0) atomicAdd(&S.ccnt[tgt], 1);
             }
         }
-        __syncthreads();
+        qt_sync<QT_THREADS>();
         /* C. which candidates are divided, in which order.  Thread t owns list positions (sweep rounds) or
          * ranks (largest-first rounds) 2t, 2t+1.  Outputs: for each of its two elements whether that node
          * is divided (dv), which node it is (i), how many children earlier-processed nodes create (c);
@@ -1062,7 +1093,7 @@ __global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : 6) void k_quadt
                 for (int j = 0; j < len; j++) rank += ((uint32_t)S.newPos[j] > ki) ? 1 : 0;
                 S.order[rank] = (unsigned short)i;
             }
-            __syncthreads();
+            qt_sync<QT_THREADS>();
             /* children per candidate in processing order; the division stops with the node that brings the
              * list to N (:730) */
             int nch0 = 0, nch1 = 0;
@@ -1072,13 +1103,13 @@ __global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : 6) void k_quadt
             qt_scan2<QT_THREADS>(nch0, nch1, S.wtot[1], c0, c1);
             if (e0 < m && len + (c0 + nch0) - (e0 + 1) >= N) atomicMin(&S.take, e0 + 1);
             if (e1 < m && len + (c1 + nch1) - (e1 + 1) >= N) atomicMin(&S.take, e1 + 1);
-            __syncthreads();
+            qt_sync<QT_THREADS>();
             const int take = min(S.take, m);
             if (e0 >= take && e0 < m) S.proc[i0] = 0;
             if (e1 >= take && e1 < m) S.proc[i1] = 0;
             if (e0 == take - 1) S.total = c0 + nch0;
             if (e1 == take - 1) S.total = c1 + nch1;
-            __syncthreads();
+            qt_sync<QT_THREADS>();
             total = take > 0 ? S.total : 0;
             dv0 = e0 < take; dv1 = e1 < take;
             s0 = e0 < len && !S.proc[e0]; s1 = e1 < len && !S.proc[e1];
@@ -1127,7 +1158,7 @@ __global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : 6) void k_quadt
                 S.newPos[i] = p2;
             }
         }
-        __syncthreads();
+        qt_sync<QT_THREADS>();
         if (tid == 0 && !S.err) {
             /* termination, :662-666 / :733-734, and the switch to largest-first rounds, :668 */
             if (newLen >= N || newLen == len) S.finish = 1;
@@ -1135,7 +1166,7 @@ __global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : 6) void k_quadt
             S.len = newLen;
             S.nExp = 0; S.take = 0x7FFFFFFF;
         }
-        __syncthreads();
+        qt_sync<QT_THREADS>();
         if (__builtin_amdgcn_readfirstlane(S.err)) break;          /* LDS flags as wave-uniform scalars: scalar branches around the barriers */
         /* F. keys follow their node */
         QT_FOR_KEYS({
@@ -1145,7 +1176,7 @@ __global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : 6) void k_quadt
             NODE = (uint32_t)(slot4 >= 0 ? S.ccnt[slot4] : S.newPos[i]);
         })
         cur = nxt;
-        __syncthreads();
+        qt_sync<QT_THREADS>();
         if (__builtin_amdgcn_readfirstlane(S.finish)) break;
     }
     if (S.err) {
@@ -1156,7 +1187,7 @@ __global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : 6) void k_quadt
     const int len = S.len;
     unsigned long long* best = reinterpret_cast<unsigned long long*>(S.ccnt);
     for (int i = tid; i < len; i += QT_THREADS) best[i] = 0ull;
-    __syncthreads();
+    qt_sync<QT_THREADS>();
     uint32_t ord[QT_KPT];                                   /* ~emission order: larger = earlier */
 #pragma unroll
     for (int t = 0; t < QT_KPT; t++) { const int k = tid + t * QT_THREADS; ord[t] = k < n ? ~k1[k] : 0u; }
@@ -1165,7 +1196,7 @@ __global__ __launch_bounds__(QT_THREADS, QT_THREADS == 256 ? 8 : 6) void k_quadt
         if (tid + t * QT_THREADS < n) atomicMax(&best[RN_GET(t)], ((unsigned long long)(rk[t] >> 24) << 32) | ord[t]);
     for (int k = tid + QT_KPT * QT_THREADS; k < n; k += QT_THREADS)
         atomicMax(&best[nd[k]], ((unsigned long long)(k0[k] >> 24) << 32) | (unsigned long long)(~k1[k]));
-    __syncthreads();
+    qt_sync<QT_THREADS>();
     uint32_t* out = sel + (size_t)slot * G->kpSlotElems + L.kpOff;
 #pragma unroll
     for (int t = 0; t < QT_KPT; t++)
@@ -1673,26 +1704,18 @@ hipError_t drfe_launch_orb(drfe_ctx* c, const uint8_t* d_gray, size_t frameStrid
 
     prof_begin(c, DRFE_STAGE_QUADTREE, s);
     {
-        /* levels are ordered large -> small: [0, nBig) take the 512-thread variant, the rest the 256-thread one */
-        int nBig = 0, capMax = 0;
-        for (int l = 0; l < nl; l++) {
-            if (g.lv[l].w * g.lv[l].h > 160000 || g.lv[l].kpCap > 256) nBig = l + 1;
-            capMax = std::max(capMax, g.lv[l].kpCap);
+        /* levels are ordered large -> small; one launch per run of levels that share an instantiation, the heaviest first */
+        typedef void (*QtFn)(const DevGeom*, int, const uint32_t*, const uint32_t*, uint16_t*, const int*, uint32_t*, int*, int*);
+#define X(T, K, M) k_quadtree<T, K, M>,
+        static const QtFn fns[] = {DRFE_QT_INSTANCES(X)};
+#undef X
+        QtPlan plan;
+        drfe_quadtree_plan(g, nframes, c->qtForce, c->qtForceN, &plan);
+        for (int i = 0; i < plan.nlaunch; i++) {
+            const QtLaunch& q = plan.launch[i];
+            hipLaunchKernelGGL(fns[q.inst], dim3(nframes, q.nlevels), dim3(drfe_qt_instances[q.inst].threads), 0, s, c->d_geom, q.level0,
+                               c->d_cand0, c->d_cand1, c->d_node, c->d_candCount, c->d_sel, c->d_selCount, c->d_status);
         }
-        /* a batch whose workgroups are all resident at once (2 x 512 threads per CU) finishes soonest as ONE
-         * launch: the kernel is latency-bound and a second launch would only queue behind the first */
-        if (nl * nframes <= 2 * 256) nBig = nl;
-        if (nBig > 0) {
-            if (capMax > 256)
-                hipLaunchKernelGGL((k_quadtree<512, 16, DRFE_QT_MAX_NODES>), dim3(nBig, nframes), dim3(512), 0, s, c->d_geom, 0,
-                                   c->d_cand0, c->d_cand1, c->d_node, c->d_candCount, c->d_sel, c->d_selCount, c->d_status);
-            else
-                hipLaunchKernelGGL((k_quadtree<512, 16, 256>), dim3(nBig, nframes), dim3(512), 0, s, c->d_geom, 0, c->d_cand0,
-                                   c->d_cand1, c->d_node, c->d_candCount, c->d_sel, c->d_selCount, c->d_status);
-        }
-        if (nBig < nl)
-            hipLaunchKernelGGL((k_quadtree<256, 8, 256>), dim3(nl - nBig, nframes), dim3(256), 0, s, c->d_geom, nBig, c->d_cand0,
-                               c->d_cand1, c->d_node, c->d_candCount, c->d_sel, c->d_selCount, c->d_status);
     }
     prof_end(c, DRFE_STAGE_QUADTREE, s);
 

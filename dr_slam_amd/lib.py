@@ -29,7 +29,7 @@ SYMBOLS = (
     "drfe_create", "drfe_destroy", "drfe_last_error", "drfe_version", "drfe_orb_scale_tables",
     "drfe_orb_max_keypoints", "drfe_orb_extract", "drfe_orb_extract_batch", "drfe_orb_download", "drfe_orb_counts",
     "drfe_orb_pyramid_level", "drfe_orb_blurred_level", "drfe_orb_candidates", "drfe_frame_stereo_grid_batch",
-    "drfe_orb_configure_level0", "drfe_orb_level0_in_place",
+    "drfe_orb_configure_level0", "drfe_orb_level0_in_place", "drfe_orb_quadtree_plan",
     "drfe_fuse_search", "drfe_fuse_search_sim3", "drfe_search_by_sim3", "drfe_search_by_projection_kf", "drfe_search_by_projection_reloc", "drfe_lsd_fuse_search", "drfe_frame_is_in_frustum", "drfe_frame_is_in_frustum_lines", "drfe_frame_set_distortion", "drfe_frame_image_bounds", "drfe_frame_download_keys_un",
     "drfe_frame_download_stereo", "drfe_frame_download_grid", "drfe_match_consecutive_batch", "drfe_match_download",
     "drfe_search_by_projection_last", "drfe_search_by_projection_map", "drfe_match_bf_knn", "drfe_profile_enable",
@@ -737,6 +737,23 @@ def load() -> C.CDLL:
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def quadtree_plan(width, height, nfeatures=1000, scale_factor=1.2, nlevels=8, nframes=512, force=None):
+    """How a batch of nframes frames runs k_quadtree (host code, no device): one dict per level with the instantiation's
+    threads, kpt (candidate keys a thread keeps in registers) and maxn (node-list capacity), the level's kp_cap and the
+    index of its launch.  force: the text of DRFE_QT_FORCE ("<threads>,<kpt>", or one pair per level separated by ';')."""
+    L = load()
+    # the arguments are set here, not in load(): a variant build from before this entry still loads (tools/bench_variant.py)
+    L.drfe_orb_quadtree_plan.argtypes = [C.POINTER(Config), C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_void_p]
+    cfg = Config(0, int(width), int(height), int(nframes), int(nfeatures), float(scale_factor), int(nlevels), 20, 7)
+    out = np.zeros((int(nlevels), 5), np.int32)
+    rc = L.drfe_orb_quadtree_plan(C.byref(cfg), int(width), int(height), int(nframes),
+                                  None if force is None else str(force).encode(), _p(out))
+    if rc < 0:
+        raise DrfeError(f"drfe_orb_quadtree_plan failed ({rc})")
+    return [dict(level=l, threads=int(r[0]), kpt=int(r[1]), maxn=int(r[2]), kp_cap=int(r[3]), launch=int(r[4]))
+            for l, r in enumerate(out)]
 
 
 def lsd_segments_host(modgrad, angles, cs, max_grad, rect_mode=0):

@@ -104,6 +104,13 @@ int drfe_orb_extract_batch(drfe_ctx* ctx, const uint8_t* d_gray, size_t frame_st
 int drfe_orb_configure_level0(drfe_ctx* ctx, int in_place);
 /* 1 if the most recent drfe_orb_extract_batch on ctx read level 0 in place, 0 if it copied it. */
 int drfe_orb_level0_in_place(const drfe_ctx* ctx);
+/* How drfe_orb_extract_batch runs DistributeOctTree for frames of width x height in a batch of nframes: per level the
+ * workgroup size, the candidate keys a thread keeps in registers, the node-list capacity, the level's node capacity
+ * (quota + 4) and the index of its launch, as out[nlevels][5].  A pure function of its arguments: needs no device, reads only
+ * cfg's nfeatures, scale_factor and nlevels.  force: NULL, or the text DRFE_QT_FORCE would hold in the environment at
+ * drfe_create ("<threads>,<kpt>" for every level it is legal for, or one pair per level separated by ';').  Returns the number
+ * of launches, or a DRFE_ERR_* code. */
+int drfe_orb_quadtree_plan(const drfe_config* cfg, int width, int height, int nframes, const char* force, int32_t* out);
 /* Copy slot results to host (synchronises the batch stream). */
 int drfe_orb_download(drfe_ctx* ctx, int slot, drfe_keypoint* kps, uint8_t* desc, int cap, int* n_out);
 /* The whole batch to host memory in five copies, asynchronous on `stream` (hipStream_t; NULL = the context stream): for a
