@@ -42,8 +42,7 @@ int finish_host(const std::vector<float>& in, float* out_xyz, int cap, int* n_ou
     return DRFE_OK;
 }
 
-/* one voxel job of an update or rebuild call: segments [seg0, seg1) of the call's list, then (resident) the plane's cloud */
-struct Job { int plane, seg0, seg1; bool resident; };
+typedef MpJob Job;
 
 /* new slots for every plane whose cloud may outgrow its slot (need[j] > cap[j]): a fresh arena, every cloud moved in */
 int repack(drfe_ctx* c, PmBuffers* b, const std::vector<int64_t>& need, hipStream_t s)
@@ -212,6 +211,27 @@ PmBuffers* maps_of(drfe_ctx* c, const char* who)
 }
 
 }  // namespace
+
+int drfe_pm_run_jobs(drfe_ctx* c, PmBuffers* b, const std::vector<MpJob>& jobs, const std::vector<MpSeg>& segs, const float* poses,
+                     int nposes, const float* src, size_t nsrc, hipStream_t s)
+{
+    return run_jobs(c, b, jobs, segs, poses, nposes, src, nsrc, s);
+}
+
+int drfe_pm_set_cloud(drfe_ctx* c, PmBuffers* b, int g, const float* xyz, int n, hipStream_t s)
+{
+    if (n > b->capH[g]) {
+        std::vector<int64_t> need(b->cntH.size(), 0);
+        need[g] = n;
+        if (int rc = repack(c, b, need, s)) return rc;
+    }
+    if (n) HIPCHK(c, hipMemcpy(b->cloud + 3 * (size_t)b->begH[g], xyz, (size_t)n * 12, hipMemcpyHostToDevice));
+    const int32_t end = b->begH[g] + n;
+    HIPCHK(c, hipMemcpy(b->cloudEnd + g, &end, 4, hipMemcpyHostToDevice));
+    b->cntH[g] = n;
+    drfe_pm_chunks(b);
+    return DRFE_OK;
+}
 
 int drfe_pm_push_planes(drfe_ctx* c, PmBuffers* b)
 {

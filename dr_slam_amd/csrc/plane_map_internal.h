@@ -52,6 +52,11 @@ struct PmBuffers {
     DevBuf<int> upList, upCounts;
     DevBuf<int4> upMove;
     int64_t upStats[4] = {0, 0, 0, 0};   /* voxel jobs on the device, jobs redone on the host, rounds, arena repacks */
+    /* plane culling (plane_cull.cpp): pair angles and keys (column-major triangle), the gated rows of every column */
+    DevBuf<float> pcAngle;
+    DevBuf<uint32_t> pcKey;
+    DevBuf<int32_t> pcRowList, pcRowCount;
+    int64_t cullStats[4] = {0, 0, 0, 0}; /* calls, device calls, distance launches, rebuild calls */
 };
 
 /* Map upkeep launches (map_plane_kernels.hip).  A segment is one piece of a voxel job's input: `n` points written to
@@ -67,6 +72,34 @@ hipError_t drfe_launch_map_plane_commit(const MpCommit* jobs, int njobs, int max
                                         int32_t* cloudEnd, hipStream_t s);
 /* moves[k] = (old begin, new begin, points) of plane k */
 hipError_t drfe_launch_map_plane_move(const int4* moves, int nplanes, int maxN, const float* from, float* to, hipStream_t s);
+
+/* one voxel job of an update or rebuild call: segments [seg0, seg1) of the call's list, then (resident) the plane's cloud */
+struct MpJob { int plane, seg0, seg1; bool resident; };
+/* the rounds of map_plane.cpp over a call's jobs (global plane indices): gather, voxel grid, commit, hand-back, repack */
+int drfe_pm_run_jobs(drfe_ctx* c, PmBuffers* b, const std::vector<MpJob>& jobs, const std::vector<MpSeg>& segs, const float* poses,
+                     int nposes, const float* src, size_t nsrc, hipStream_t s);
+/* replaces the cloud of global plane g with n host points (a repack when the slot is too small) */
+int drfe_pm_set_cloud(drfe_ctx* c, PmBuffers* b, int g, const float* xyz, int n, hipStream_t s);
+
+/* Plane culling launches (plane_cull_kernels.hip) over the P planes of one map, global planes [pb, pb + P) */
+#define PC_THREADS 256
+#define PC_POINTS_PER_LANE 4
+#define PC_CHUNK (PC_THREADS * PC_POINTS_PER_LANE)   /* cloud points of one work item of the distance pass */
+#define PC_ROW_TILE 16                               /* gated rows one work item scans its points against */
+struct PcLaunch {
+    const float *mapCoefs, *cloud;
+    const uint8_t* mapBad;
+    const int32_t *cloudBeg, *cloudEnd;
+    float* angle;
+    uint32_t* key;
+    int32_t *rowList, *rowCount;
+    int pb, P, tile;
+    double aTh;
+};
+/* angle, key reset and the gated rows of every column; rowCount must be zero */
+hipError_t drfe_launch_plane_cull_pairs(const PcLaunch& L, hipStream_t s);
+/* the distance pass over columns [col0, col0 + ncols): maxChunks / maxRows bound the chunks of a cloud and the rows of a column */
+hipError_t drfe_launch_plane_cull_dist(const PcLaunch& L, int col0, int ncols, int maxChunks, int maxRows, hipStream_t s);
 
 /* per-plane arrays and work-list sizes from the host mirrors (after an upload, an edit or an update) */
 int drfe_pm_push_planes(drfe_ctx* c, PmBuffers* b);

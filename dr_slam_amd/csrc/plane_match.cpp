@@ -151,6 +151,7 @@ int drfe_plane_map_upload(drfe_ctx* c, int n_maps, const int32_t* plane_offsets,
     for (int j = 0; j < nPlanes; j++) b->cntH[j] = cloud_offsets[j + 1] - cloud_offsets[j];
     b->capH = b->cntH;
     std::fill(b->upStats, b->upStats + 4, 0);
+    std::fill(b->cullStats, b->cullStats + 4, 0);
     if (int rc = drfe_pm_push_planes(c, b)) return rc;
     b->frames = 0;                    /* results of an earlier batch referred to the previous maps */
     return DRFE_OK;

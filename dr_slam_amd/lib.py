@@ -47,6 +47,7 @@ SYMBOLS = (
     "drfe_plane_match_batch", "drfe_plane_match_download", "drfe_plane_flags_download",
     "drfe_map_plane_update_host", "drfe_map_plane_rebuild_host", "drfe_plane_map_update_batch", "drfe_plane_map_rebuild_batch",
     "drfe_plane_map_edit", "drfe_plane_map_cloud_download", "drfe_plane_map_update_stats",
+    "drfe_plane_map_cull_host", "drfe_plane_map_cull_batch", "drfe_plane_map_cull_limits", "drfe_plane_map_cull_stats",
     "drfe_map_point_upkeep_host", "drfe_map_line_upkeep_host", "drfe_map_point_upkeep_batch", "drfe_map_line_upkeep_batch",
     "drfe_map_upkeep_stats",
     "drfe_triangulate_points_host", "drfe_triangulate_lines_host", "drfe_triangulate_points_batch", "drfe_triangulate_lines_batch",
@@ -573,6 +574,10 @@ def load() -> C.CDLL:
     L.drfe_plane_map_edit.argtypes = [vp, i32, i32, vp, vp, vp]
     L.drfe_plane_map_cloud_download.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32)]
     L.drfe_plane_map_update_stats.argtypes = [vp, vp]
+    L.drfe_plane_map_cull_host.argtypes = [C.POINTER(PlaneCullIn), vp, vp, vp, vp, C.POINTER(PlaneCullOut)]
+    L.drfe_plane_map_cull_batch.argtypes = [vp, i32, C.POINTER(PlaneCullIn), i32, C.POINTER(PlaneCullOut), vp]
+    L.drfe_plane_map_cull_limits.argtypes = [vp]
+    L.drfe_plane_map_cull_stats.argtypes = [vp, vp]
     L.drfe_map_point_upkeep_host.argtypes = [i32, vp, vp, vp]
     L.drfe_map_line_upkeep_host.argtypes = [i32, vp, vp, vp]
     L.drfe_map_point_upkeep_batch.argtypes = [vp, i32, vp, vp, vp, vp]
@@ -969,6 +974,108 @@ def map_plane_rebuild_host(Twc, clouds):
     if rc != 0:
         raise DrfeError(f"drfe_map_plane_rebuild_host failed ({rc})")
     return out[:n.value].copy()
+
+
+class PlaneCullIn(C.Structure):
+    _fields_ = [("n_planes", C.c_int32), ("n_kfs", C.c_int32), ("n_recent", C.c_int32), ("current_kf_id", C.c_int32),
+                ("dTh", C.c_double), ("aTh", C.c_double)] + [(k, C.c_void_p) for k in (
+        "found", "visible", "n_obs", "first_kf_id", "obs_offsets", "obs_kf", "obs_idx", "obs_cloud", "obs_cloud_n")] + [
+        ("obs_cloud_stride", C.c_int32), ("Twc", C.c_void_p), ("recent", C.c_void_p)]      # drfe_plane_cull_in
+
+
+class PlaneCullOut(C.Structure):
+    _fields_ = [("n_events", C.c_int32), ("n_rebuilt", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "events", "bad", "n_obs", "found", "visible", "rebuilt", "rebuilt_offsets", "rebuilt_xyz")] + [
+        ("rebuilt_capacity", C.c_int32), ("verdicts", C.c_void_p), ("counters", C.c_int64 * 4)]   # drfe_plane_cull_out
+
+
+# DRFE_PLANE_CULL_*: the verdict of one entry of mlpRecentAddedMapPlanes
+PLANE_CULL_KEPT, PLANE_CULL_ERASED_BAD, PLANE_CULL_BAD_BY_RATIO, PLANE_CULL_BAD_BY_OBSERVATIONS, PLANE_CULL_ERASED_BY_AGE = range(5)
+PLANE_CULL_COUNTERS = ("gated_pairs", "pair_points", "rebuilds", "stale_columns")
+PLANE_CULL_STATS = ("calls", "device_calls", "dist_launches", "rebuild_calls")
+PLANE_CULL_DISPATCH, PLANE_CULL_DEVICE, PLANE_CULL_HOST_WALK, PLANE_CULL_DEVICE_PER_PAIR = range(4)   # drfe_plane_map_cull_batch's mode
+PLANE_CULL_DEVICE_FROM = 16385                                                       # DRFE_PLANE_CULL_DEVICE_FROM
+PLANE_CULL_CLOUD_STRIDE = 16         # the bytes between the points of an observation cloud as the wrappers pack them (PointXYZ)
+
+
+def _plane_cull_pack(scene, rebuilt_capacity=None):
+    """A culling scene (dict: found / visible / n_obs / first_kf_id [P], obs = per plane a list of (key frame, plane in it) in
+    key-frame order, kf_clouds = per key frame a list of [n, 3] clouds, Twc [K, 4, 4], dTh, aTh, current_kf_id, recent) ->
+    (drfe_plane_cull_in, drfe_plane_cull_out, the arrays they point to, the output arrays)"""
+    P = len(scene["found"])
+    K = len(scene["kf_clouds"])
+    keep = {}
+    for k in ("found", "visible", "n_obs", "first_kf_id"):
+        keep[k] = np.ascontiguousarray(scene[k], np.int32).reshape(P)
+    off = np.zeros(P + 1, np.int32)
+    off[1:] = np.cumsum([len(o) for o in scene["obs"]]) if P else []
+    flat = [o for obs in scene["obs"] for o in obs]
+    keep["obs_offsets"] = off
+    keep["obs_kf"] = np.ascontiguousarray([o[0] for o in flat], np.int32)
+    keep["obs_idx"] = np.ascontiguousarray([o[1] for o in flat], np.int32)
+    # every key-frame cloud padded to PointXYZ's 16 bytes, the pad poisoned: only x y z may be read
+    padded = {}
+    for kf, idx in flat:
+        if (kf, idx) not in padded:
+            c = np.asarray(scene["kf_clouds"][kf][idx], np.float32).reshape(-1, 3)
+            q = np.full((max(len(c), 1), 4), np.nan, np.float32)
+            q[:len(c), :3] = c
+            padded[(kf, idx)] = (q, len(c))
+    keep["padded"] = padded
+    keep["obs_cloud"] = np.ascontiguousarray([padded[o][0].ctypes.data for o in flat], np.uint64)
+    keep["obs_cloud_n"] = np.ascontiguousarray([padded[o][1] for o in flat], np.int32)
+    keep["Twc"] = np.ascontiguousarray(np.asarray(scene["Twc"], np.float32).reshape(-1, 16), np.float32)
+    assert len(keep["Twc"]) == K
+    keep["recent"] = np.ascontiguousarray(scene["recent"], np.int32).reshape(-1)
+    cin = PlaneCullIn(P, K, len(keep["recent"]), int(scene["current_kf_id"]), float(scene["dTh"]), float(scene["aTh"]))
+    for k in ("found", "visible", "n_obs", "first_kf_id", "obs_offsets", "obs_kf", "obs_idx", "obs_cloud", "obs_cloud_n", "Twc", "recent"):
+        setattr(cin, k, _p(keep[k]) if keep[k].size else None)
+    cin.obs_offsets = _p(off)
+    cin.obs_cloud_stride = PLANE_CULL_CLOUD_STRIDE
+    cap = int(keep["obs_cloud_n"].sum()) if rebuilt_capacity is None else int(rebuilt_capacity)
+    o = dict(events=np.zeros((max(P, 1), 2), np.int32), bad=np.zeros(max(P, 1), np.uint8), n_obs=np.zeros(max(P, 1), np.int32),
+             found=np.zeros(max(P, 1), np.int32), visible=np.zeros(max(P, 1), np.int32), rebuilt=np.zeros(max(P, 1), np.int32),
+             rebuilt_offsets=np.zeros(P + 1, np.int32), rebuilt_xyz=np.zeros((max(cap, 1), 3), np.float32),
+             verdicts=np.zeros(max(len(keep["recent"]), 1), np.uint8))
+    cout = PlaneCullOut()
+    for k, a in o.items():
+        setattr(cout, k, _p(a))
+    cout.rebuilt_capacity = cap
+    return cin, cout, keep, o
+
+
+def _plane_cull_result(cin, cout, o):
+    P, E, R = cin.n_planes, cout.n_events, cout.n_rebuilt
+    off = o["rebuilt_offsets"]
+    return dict(events=o["events"][:E].copy(), bad=o["bad"][:P].copy(), n_obs=o["n_obs"][:P].copy(), found=o["found"][:P].copy(),
+                visible=o["visible"][:P].copy(), rebuilt=o["rebuilt"][:R].tolist(),
+                clouds={int(o["rebuilt"][k]): o["rebuilt_xyz"][off[k]:off[k + 1]].copy() for k in range(R)},
+                verdicts=o["verdicts"][:cin.n_recent].copy(), counters=dict(zip(PLANE_CULL_COUNTERS, list(cout.counters))))
+
+
+def plane_map_cull_host(scene, rebuilt_capacity=None):
+    """LocalMapping::MapPlaneCulling on the host (drfe_plane_map_cull_host): scene as _plane_cull_pack takes it plus coefs [P, 4],
+    bad [P] and clouds (list of P [n, 3]).  Returns dict(events [E, 2] (replaced, survivor), bad, n_obs, found, visible, rebuilt,
+    clouds {plane: [n, 3]}, verdicts, counters)."""
+    L = load()
+    cin, cout, keep, o = _plane_cull_pack(scene, rebuilt_capacity)
+    coefs = np.ascontiguousarray(scene["coefs"], np.float32).reshape(-1, 4)
+    bad = np.ascontiguousarray(scene["bad"], np.uint8).reshape(-1)
+    coff, xyz = _clouds_csr(list(scene["clouds"]))
+    assert len(coefs) == len(bad) == len(scene["clouds"]) == cin.n_planes
+    rc = L.drfe_plane_map_cull_host(C.byref(cin), _p(coefs), _p(bad), _p(coff), _p(xyz), C.byref(cout))
+    if rc != 0:
+        raise DrfeError(f"drfe_plane_map_cull_host failed ({rc})")
+    return _plane_cull_result(cin, cout, o)
+
+
+def plane_map_cull_limits():
+    """dict(chunk, row_tile, device_from, max_planes) of the device culling pass"""
+    out = np.zeros(4, np.int32)
+    rc = load().drfe_plane_map_cull_limits(_p(out))
+    if rc != 0:
+        raise DrfeError(f"drfe_plane_map_cull_limits failed ({rc})")
+    return dict(zip(("chunk", "row_tile", "device_from", "max_planes"), out.tolist()))
 
 
 def _upkeep_call(fn, head, line, scene, what, frustum):
@@ -3334,6 +3441,24 @@ class Context:
         st = np.zeros(4, np.int64)
         self._chk(self.L.drfe_plane_map_update_stats(self.h, _p(st)), "drfe_plane_map_update_stats")
         return dict(zip(("device_jobs", "host_jobs", "rounds", "repacks"), st.tolist()))
+
+    def plane_map_cull_batch(self, map_id: int, scene, mode: int = PLANE_CULL_DISPATCH, rebuilt_capacity=None, stream: int = 0):
+        """LocalMapping::MapPlaneCulling on resident map map_id (drfe_plane_map_cull_batch): scene as plane_map_cull_host takes it,
+        its coefs / bad / clouds unread (they are resident).  Same result dict; the bad flags and the rebuilt clouds are
+        committed into the resident map."""
+        cin, cout, keep, o = _plane_cull_pack(scene, rebuilt_capacity)
+        self._chk(self.L.drfe_plane_map_cull_batch(self.h, map_id, C.byref(cin), int(mode), C.byref(cout), C.c_void_p(stream)),
+                  "drfe_plane_map_cull_batch")
+        return _plane_cull_result(cin, cout, o)
+
+    def plane_map_cull_limits(self):
+        return plane_map_cull_limits()
+
+    def plane_map_cull_stats(self):
+        """dict(calls, device_calls, dist_launches, rebuild_calls) since plane_map_upload"""
+        st = np.zeros(4, np.int64)
+        self._chk(self.L.drfe_plane_map_cull_stats(self.h, _p(st)), "drfe_plane_map_cull_stats")
+        return dict(zip(PLANE_CULL_STATS, st.tolist()))
 
     def map_point_upkeep_batch(self, scene, what=3, frustum=True):
         """map_point_upkeep_host on the device (drfe_map_point_upkeep_batch): same outputs, same bits"""

@@ -987,6 +987,68 @@ int drfe_plane_map_cloud_download(drfe_ctx* ctx, int map, int plane, float* xyz,
  * the sort's heap-sort branch), [2] rounds, [3] arena repacks (clouds that outgrew their slots). */
 int drfe_plane_map_update_stats(drfe_ctx* ctx, int64_t* stats /* 4 */);
 
+/* LocalMapping::MapPlaneCulling (src/LocalMapping.cc:233-307) with Map::PointDistanceFromPlane (src/Map.cc:433-448) and
+ * MapPlane::Replace (src/MapPlane.cc:197-271) over all planes of one map in vpMapPlanes order (GetAllMapPlanes(); null entries
+ * are not supported).  Row i scans the merged cloud of every later plane j that passes the angle gate against plane i's
+ * coefficients; the nearest below dTh is merged with i (the one with fewer observations is replaced, plane i on a tie), and the
+ * survivor's cloud becomes the voxel grid of its merged observations (the observation form above).  Then the recent-plane
+ * list is walked.  DESIGN.md section 30.
+ *
+ * Per plane: found / visible (mnFound, mnVisible), n_obs (nObs), first_kf_id ((int)mnFirstKFid) and mObservations in CSR form in
+ * std::map<KeyFrame*> order: observation o of plane p, o in [obs_offsets[p], obs_offsets[p + 1]), is plane obs_idx[o] of key
+ * frame obs_kf[o].  obs_kf indexes the call's key-frame table, which is in pointer order too, so inside one plane obs_kf
+ * increases strictly.  Twc + 16 k is key frame k's GetPoseInverse().  The cloud of observation o (KF->mvPlanePoints[idx]) is
+ * obs_cloud_n[o] points, point q's x y z being the three floats at (const char*)obs_cloud[o] + q * obs_cloud_stride; it is
+ * read only when a survivor that holds the observation is rebuilt.
+ * recent: mlpRecentAddedMapPlanes as plane indices, -1 for a plane that has left the map (bad by construction, erased). */
+enum { DRFE_PLANE_CULL_KEPT = 0, DRFE_PLANE_CULL_ERASED_BAD = 1, DRFE_PLANE_CULL_BAD_BY_RATIO = 2,
+       DRFE_PLANE_CULL_BAD_BY_OBSERVATIONS = 3, DRFE_PLANE_CULL_ERASED_BY_AGE = 4 };
+typedef struct drfe_plane_cull_in {
+    int32_t n_planes, n_kfs, n_recent, current_kf_id;    /* current_kf_id: (int)mpCurrentKeyFrame->mnId */
+    double dTh, aTh;                                     /* Plane.AssociationDisRef / AngRef, doubles in the reference */
+    const int32_t *found, *visible, *n_obs, *first_kf_id;            /* n_planes each */
+    const int32_t *obs_offsets, *obs_kf, *obs_idx;       /* n_planes + 1; one per observation */
+    const float* const* obs_cloud;                       /* one per observation; may be NULL where obs_cloud_n is 0 */
+    const int32_t* obs_cloud_n;
+    int32_t obs_cloud_stride;                            /* bytes between points, >= 12 (sizeof(PointT) for a PCL cloud) */
+    const float* Twc;                                    /* n_kfs x 16 */
+    const int32_t* recent;                               /* n_recent */
+} drfe_plane_cull_in;
+typedef struct drfe_plane_cull_out {
+    int32_t n_events, n_rebuilt;
+    int32_t* events;            /* n_planes x 2: (replaced, survivor) in the order they happen, at most one per row */
+    uint8_t* bad;               /* n_planes each: isBad(), nObs, mnFound, mnVisible after the call */
+    int32_t *n_obs, *found, *visible;
+    int32_t* rebuilt;           /* n_planes: the planes whose cloud was rebuilt, ascending, each once */
+    int32_t* rebuilt_offsets;   /* n_planes + 1: plane rebuilt[k]'s cloud = points [rebuilt_offsets[k], rebuilt_offsets[k + 1]) */
+    float* rebuilt_xyz;
+    int32_t rebuilt_capacity;   /* points; DRFE_ERR_CAPACITY when too small (the sum of obs_cloud_n always suffices) */
+    uint8_t* verdicts;          /* n_recent: DRFE_PLANE_CULL_*; every verdict but KEPT erases the list entry, BAD_BY_* after SetBadFlag */
+    int64_t counters[4];        /* pairs scanned, cloud points scanned, clouds rebuilt, rebuilt clouds read again as a column */
+} drfe_plane_cull_out;
+/* On the host, no context: map_coefs (4 per plane, GetWorldPos), map_bad and the clouds in CSR form as drfe_plane_match_host
+ * takes them.  DRFE_ERR_INVALID on an argument out of range (offsets, key-frame or recent indices, observation order, stride);
+ * nothing is written then. */
+int drfe_plane_map_cull_host(const drfe_plane_cull_in* in, const float* map_coefs, const uint8_t* map_bad,
+                             const int32_t* cloud_offsets, const float* cloud_xyz, drfe_plane_cull_out* out);
+/* The same on resident map `map` of drfe_plane_map_upload, whose coefficients, bad flags and clouds are read in place:
+ * DRFE_ERR_STATE when in->n_planes is not the map's plane count.  Same outputs, byte for byte.  On success the call commits into
+ * the resident map with nothing re-uploaded: the bad flags, and the rebuilt clouds through the rounds of
+ * drfe_plane_map_rebuild_batch (drfe_plane_map_update_stats counts them); with DRFE_ERR_CAPACITY for rebuilt_capacity the map is
+ * committed all the same and drfe_plane_map_cloud_download still returns the clouds.  mode 0 runs on the device from
+ * DRFE_PLANE_CULL_DEVICE_FROM planes and below it runs the host walk on the downloaded clouds; 1 forces the device, 2 the host
+ * walk, 3 the device with one row per tile (a per-pair work list, kept for measurement).  More than
+ * DRFE_PLANE_CULL_MAX_PLANES planes always take the host walk.  Synchronises. */
+enum { DRFE_PLANE_CULL_MAX_PLANES = 16384, DRFE_PLANE_CULL_DEVICE_FROM = 16385 };
+int drfe_plane_map_cull_batch(drfe_ctx* ctx, int map, const drfe_plane_cull_in* in, int mode, drfe_plane_cull_out* out, void* stream);
+/* out[0] cloud points of one chunk of the distance pass, [1] gated rows of one tile, [2] DRFE_PLANE_CULL_DEVICE_FROM,
+ * [3] DRFE_PLANE_CULL_MAX_PLANES */
+int drfe_plane_map_cull_limits(int32_t* out4);
+/* Counters since drfe_plane_map_upload: stats[0] calls, [1] calls that took the device pass, [2] distance launches (the first
+ * pass and one per recomputed column), [3] rebuild calls into the rounds (one per stale column or replaced survivor, one for
+ * the end-of-call batch). */
+int drfe_plane_map_cull_stats(drfe_ctx* ctx, int64_t* stats /* 4 */);
+
 /* Map-point and map-line upkeep: MapPoint::ComputeDistinctiveDescriptors + UpdateNormalAndDepth (src/MapPoint.cc:288-350,
  * 376-411) and MapLine::ComputeDistinctiveDescriptors + UpdateAverageDir (src/MapLine.cpp:241-318, 320-362) for n independent
  * items.  Each item lists its observations in the caller's order (the reference iterates a std::map<KeyFrame*, size_t>, so

@@ -1763,6 +1763,99 @@ inline void UpdateCoefficientsAndPoints(MapPlaneT& pMP)
         throw std::runtime_error("drfe_map_plane_rebuild_host failed");
     drfe_detail_mp::replace_cloud(pMP, out, n);
 }
+
+/* LocalMapping::MapPlaneCulling (src/LocalMapping.cc:233-307) over drfe_plane_map_cull_batch on resident map `map` of ctx, or, with
+ * ctx == nullptr, over drfe_plane_map_cull_host (no context, no device).  vpMapPlanes is mpMap->GetAllMapPlanes() (no null
+ * entries), in the order the map was uploaded in; mlpRecentAddedMapPlanes is the thread's list, edited in place.  The entry decides;
+ * this function applies: each event (replaced, survivor) through MapPlane::ReplaceWithoutRebuild(survivor) - the reference's
+ * Replace (src/MapPlane.cc:197-271) without its closing pMP->UpdateCoefficientsAndPoints(), a member the integration adds because
+ * mObservations and mbBad are protected -, then every rebuilt cloud from the entry, then SetBadFlag() and the
+ * erasures of the list walk.  Reads
+ *   MapPlane: isBad(), GetWorldPos() (4x1 float), mvPlanePoints, GetObservations() (std::map<KeyFrame*, size_t>), Observations(),
+ *             mnFound, mnVisible, mnFirstKFid
+ *   KeyFrame: GetPoseInverse() (4x4 float), mvPlanePoints[idx].points (x y z at the head of a point), mnId
+ * Observation clouds are passed in place (pointer, count, sizeof(point)): nothing is copied unless a survivor is rebuilt.
+ * Returns the number of merges.  DESIGN.md section 30. */
+template <class MapPlaneT, class KeyFrameT, class ListT>
+inline int MapPlaneCulling(drfe_ctx* ctx, int map, const std::vector<MapPlaneT*>& vpMapPlanes, ListT& mlpRecentAddedMapPlanes,
+                           KeyFrameT* pCurrentKF, double dTh, double aTh)
+{
+    const int P = (int)vpMapPlanes.size();
+    std::map<KeyFrameT*, int32_t> rank;                      /* pointer order, as the observation maps iterate */
+    for (MapPlaneT* pl : vpMapPlanes)
+        for (const auto& ob : pl->GetObservations()) rank[ob.first] = 0;
+    std::vector<float> Twc(16 * rank.size() + 16);
+    {
+        int32_t k = 0;
+        for (auto& e : rank) {
+            drfe_detail_mp::pose16(e.first->GetPoseInverse(), &Twc[16 * (size_t)k]);
+            e.second = k++;
+        }
+    }
+    std::vector<int32_t> found(P), visible(P), nobs(P), first(P), obsOff(P + 1, 0), obsKf, obsIdx, obsN, cloudOff(P + 1, 0);
+    std::vector<const float*> obsCloud;
+    std::vector<float> coefs(4 * (size_t)P + 4, 0.f), xyz;
+    std::vector<uint8_t> bad(P + 1, 0);
+    typedef typename std::decay<decltype(vpMapPlanes[0]->mvPlanePoints->points[0])>::type PointT;
+    static_assert(sizeof(PointT) % sizeof(float) == 0, "a cloud point is a whole number of floats");
+    std::map<MapPlaneT*, int32_t> index;
+    for (int p = 0; p < P; p++) {
+        MapPlaneT* pl = vpMapPlanes[p];
+        index[pl] = p;
+        found[p] = pl->mnFound; visible[p] = pl->mnVisible; nobs[p] = pl->Observations(); first[p] = (int)pl->mnFirstKFid;
+        bad[p] = pl->isBad() ? 1 : 0;
+        for (const auto& ob : pl->GetObservations()) {
+            const auto& cl = ob.first->mvPlanePoints[ob.second];
+            obsKf.push_back(rank[ob.first]);
+            obsIdx.push_back((int32_t)ob.second);
+            obsN.push_back((int32_t)cl.points.size());
+            obsCloud.push_back(cl.points.empty() ? nullptr : &cl.points[0].x);
+        }
+        obsOff[p + 1] = (int32_t)obsKf.size();
+        if (!ctx && !bad[p]) {                /* a bad plane's position and cloud are never read */
+            const auto pW = pl->GetWorldPos();
+            for (int k = 0; k < 4; k++) coefs[4 * (size_t)p + k] = pW.template ptr<float>(k)[0];
+            drfe_detail_mp::append_xyz(*pl->mvPlanePoints, xyz);
+        }
+        cloudOff[p + 1] = (int32_t)(xyz.size() / 3);
+    }
+    std::vector<int32_t> recent;
+    for (MapPlaneT* pl : mlpRecentAddedMapPlanes) recent.push_back(index.count(pl) ? index[pl] : -1);
+    int64_t cap = 0;
+    for (int32_t n : obsN) cap += n;
+    if (cap > INT32_MAX) throw std::runtime_error("MapPlaneCulling: the observation clouds outgrow 2^31 points");
+    drfe_plane_cull_in in = {};
+    in.n_planes = P; in.n_kfs = (int32_t)rank.size(); in.n_recent = (int32_t)recent.size(); in.current_kf_id = (int)pCurrentKF->mnId;
+    in.dTh = dTh; in.aTh = aTh;
+    in.found = found.data(); in.visible = visible.data(); in.n_obs = nobs.data(); in.first_kf_id = first.data();
+    in.obs_offsets = obsOff.data(); in.obs_kf = obsKf.data(); in.obs_idx = obsIdx.data();
+    in.obs_cloud = obsCloud.data(); in.obs_cloud_n = obsN.data(); in.obs_cloud_stride = (int32_t)sizeof(PointT);
+    in.Twc = Twc.data(); in.recent = recent.data();
+    std::vector<int32_t> events(2 * (size_t)P + 2), oN(P + 1), oF(P + 1), oV(P + 1), rebuilt(P + 1), rOff(P + 2);
+    std::vector<uint8_t> oBad(P + 1), verdicts(recent.size() + 1);
+    std::vector<float> rXyz(3 * (size_t)cap + 3);
+    drfe_plane_cull_out out = {};
+    out.events = events.data(); out.bad = oBad.data(); out.n_obs = oN.data(); out.found = oF.data(); out.visible = oV.data();
+    out.rebuilt = rebuilt.data(); out.rebuilt_offsets = rOff.data(); out.rebuilt_xyz = rXyz.data(); out.rebuilt_capacity = (int32_t)cap;
+    out.verdicts = verdicts.data();
+    const int rc = ctx ? drfe_plane_map_cull_batch(ctx, map, &in, 0, &out, nullptr)
+                       : drfe_plane_map_cull_host(&in, coefs.data(), bad.data(), cloudOff.data(), xyz.data(), &out);
+    if (rc != DRFE_OK) throw std::runtime_error(ctx ? "drfe_plane_map_cull_batch failed" : "drfe_plane_map_cull_host failed");
+    for (int e = 0; e < out.n_events; e++) vpMapPlanes[events[2 * e]]->ReplaceWithoutRebuild(vpMapPlanes[events[2 * e + 1]]);
+    std::vector<float> one;
+    for (int k = 0; k < out.n_rebuilt; k++) {
+        one.assign(rXyz.begin() + 3 * (size_t)rOff[k], rXyz.begin() + 3 * (size_t)rOff[k + 1]);
+        drfe_detail_mp::replace_cloud(*vpMapPlanes[rebuilt[k]], one, rOff[k + 1] - rOff[k]);
+    }
+    size_t k = 0;
+    for (auto lit = mlpRecentAddedMapPlanes.begin(); lit != mlpRecentAddedMapPlanes.end(); k++) {
+        const int v = verdicts[k];
+        if (v == DRFE_PLANE_CULL_BAD_BY_RATIO || v == DRFE_PLANE_CULL_BAD_BY_OBSERVATIONS) (*lit)->SetBadFlag();
+        if (v == DRFE_PLANE_CULL_KEPT) ++lit;
+        else lit = mlpRecentAddedMapPlanes.erase(lit);
+    }
+    return out.n_events;
+}
 /* MapPoint::ComputeDistinctiveDescriptors / UpdateNormalAndDepth (src/MapPoint.cc:288-411) and MapLine::ComputeDistinctiveDescriptors
  * / UpdateAverageDir (src/MapLine.cpp:241-362) over drfe_map_point_upkeep_host / drfe_map_line_upkeep_host and the batch entries.
  * Reads only public accessors:
