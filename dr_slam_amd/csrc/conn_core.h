@@ -1,5 +1,5 @@
 /* conn_core.h — the rules of KeyFrame::UpdateConnections, AddConnection and UpdateBestCovisibles (reference src/KeyFrame.cc:200-234,
- * 366-500), once, for lmap.cpp's host walk and conn_kernels.hip.  DESIGN.md section 26.  Integer-only.
+ * 366-500), once, for lmap_conn.cpp's host walk and conn_kernels.hip.  DESIGN.md section 26.  Integer-only.
  *
  * Both sides read the image of lmap_core.h (key frames are slots in rank order) and two rows per key frame: the weights
  * (mConnectedKeyFrameWeights) as (slot, weight) pairs in ascending slot, and the ordered list (mvpOrderedConnectedKeyFrames with

@@ -10,16 +10,10 @@
 
 using namespace lmap_store;
 
-namespace {
-
-int fail(drfe_lmap* db, int rc, const std::string& why) { return lmap_fail(db, rc, why); }
-int build_image(drfe_lmap* db) { return lmap_build_image(db); }
-int upload_image(drfe_lmap* db, hipStream_t st) { return lmap_upload_image(db, st); }
-
 /* the geometry by slot, after the image */
-int build_geo(drfe_lmap* db)
+int lmap_build_geo(drfe_lmap* db)
 {
-    const int rc = build_image(db);
+    const int rc = lmap_build_image(db);
     if (rc) return rc;
     if (!db->geoDirty) return DRFE_OK;
     const Image& G = db->img;
@@ -64,25 +58,11 @@ int build_geo(drfe_lmap* db)
     }
     E.complete = complete;
     db->geoDirty = false;
-    db->devGeoDirty = true;
+    db->blk[drfe_lmap::GEO].stale_all();
     return DRFE_OK;
 }
 
-CorrImage geo_view(drfe_lmap* db)
-{
-    GeoImage& E = db->geo;
-    CorrImage V;
-    V.nLevels = (int32_t)db->scales.size();
-    V.scale = db->scales.data();
-    V.kfTcw = E.kfTcw.data();
-    V.kfOw = E.kfOw.data();
-    V.mpWorld = E.mpWorld.data();
-    V.mpRef = E.mpRef.data();
-    V.mpLevel = E.mpLevel.data();
-    V.mpBy = E.mpBy.data();
-    V.mpByRef = E.mpByRef.data();
-    return V;
-}
+namespace {
 
 /* a checked call: the called key frames by position (rank order) */
 struct CorrPlan {
@@ -111,9 +91,9 @@ bool corr_out_ok(const drfe_lmap_correct_out* o)
 /* the handles of a call into positions; refuses a duplicate, an unknown handle and, when cur is given, a list without it */
 int corr_positions(drfe_lmap* db, int32_t n, const int32_t* handles, const int32_t* cur, CorrPlan& C)
 {
-    if (n <= 0 || !handles) return fail(db, DRFE_ERR_INVALID, "lmap_correct: invalid argument");
-    if (n > DRFE_LMAP_MAX_QUERIES) return fail(db, DRFE_ERR_INVALID, "lmap_correct: more than DRFE_LMAP_MAX_QUERIES key frames in a call");
-    const int rc = build_geo(db);
+    if (n <= 0 || !handles) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_correct: invalid argument");
+    if (n > DRFE_LMAP_MAX_QUERIES) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_correct: more than DRFE_LMAP_MAX_QUERIES key frames in a call");
+    const int rc = lmap_build_geo(db);
     if (rc) return rc;
     const Image& G = db->img;
     C.n = n;
@@ -121,8 +101,8 @@ int corr_positions(drfe_lmap* db, int32_t n, const int32_t* handles, const int32
     C.pos.assign(G.kfHandle.size(), -1);
     for (int a = 0; a < n; a++) {
         const auto it = G.kfSlot.find(handles[a]);
-        if (it == G.kfSlot.end()) return fail(db, DRFE_ERR_INVALID, "lmap_correct: the call names an unknown key-frame handle");
-        if (C.pos[(size_t)it->second] >= 0) return fail(db, DRFE_ERR_INVALID, "lmap_correct: the call names a key frame twice");
+        if (it == G.kfSlot.end()) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_correct: the call names an unknown key-frame handle");
+        if (C.pos[(size_t)it->second] >= 0) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_correct: the call names a key frame twice");
         C.pos[(size_t)it->second] = 0;
         order.emplace_back(it->second, a);
     }
@@ -141,7 +121,7 @@ int corr_positions(drfe_lmap* db, int32_t n, const int32_t* handles, const int32
         C.sumRows += len;
         if (cur && G.kfHandle[(size_t)s] == *cur) C.curPos = j;
     }
-    if (cur && C.curPos < 0) return fail(db, DRFE_ERR_INVALID, "lmap_correct: the current key frame is not among the called");
+    if (cur && C.curPos < 0) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_correct: the current key frame is not among the called");
     return DRFE_OK;
 }
 
@@ -152,9 +132,9 @@ int corr_check(drfe_lmap* db, const CorrPlan& C)
     const GeoImage& E = db->geo;
     if (E.complete) return DRFE_OK;
     const int32_t nLevels = (int32_t)db->scales.size();
-    if (nLevels <= 0) return fail(db, DRFE_ERR_STATE, "lmap_correct: the store has no scale factors");
+    if (nLevels <= 0) return lmap_fail(db, DRFE_ERR_STATE, "lmap_correct: the store has no scale factors");
     auto lacks = [&](const char* kind, int32_t h, const std::string& of) {
-        return fail(db, DRFE_ERR_STATE, std::string("lmap_correct: ") + kind + " " + std::to_string(h) + of + " has no geometry");
+        return lmap_fail(db, DRFE_ERR_STATE, std::string("lmap_correct: ") + kind + " " + std::to_string(h) + of + " has no geometry");
     };
     for (int j = 0; j < C.n; j++) {
         const int32_t k = C.called[(size_t)j];
@@ -173,11 +153,11 @@ int corr_check(drfe_lmap* db, const CorrPlan& C)
                 if (!E.kfHas[(size_t)G.obs[(size_t)o]]) return lacks("observing key frame", G.kfHandle[(size_t)G.obs[(size_t)o]], of);
             const int32_t r = E.mpRef[(size_t)p];
             if (r < 0)
-                return fail(db, DRFE_ERR_STATE, "lmap_correct: the reference key frame " + std::to_string(db->mpGeo.at(h).ref) +
+                return lmap_fail(db, DRFE_ERR_STATE, "lmap_correct: the reference key frame " + std::to_string(db->mpGeo.at(h).ref) +
                                                     " of map point " + std::to_string(h) + " is unknown");
             if (!E.kfHas[(size_t)r]) return lacks("reference key frame", G.kfHandle[(size_t)r], of);
             if (E.mpLevel[(size_t)p] < 0 || E.mpLevel[(size_t)p] >= nLevels)
-                return fail(db, DRFE_ERR_STATE, "lmap_correct: ref_level of map point " + std::to_string(h) + " is not a level of the store");
+                return lmap_fail(db, DRFE_ERR_STATE, "lmap_correct: ref_level of map point " + std::to_string(h) + " is not a level of the store");
         }
     }
     return DRFE_OK;
@@ -186,9 +166,9 @@ int corr_check(drfe_lmap* db, const CorrPlan& C)
 /* the reference's loops: every key frame's Sim3 pair first, then key frame after key frame its points and its pose */
 void corr_host(drfe_lmap* db, const CorrPlan& C, CorrResult& R)
 {
-    const Image& G = db->img;
-    const LmapImage I = G.view();
-    const CorrImage V = geo_view(db);
+    lmap_host_views(db);
+    const LmapImage I = db->hView;
+    const CorrImage V = db->hCorr;
     float TwcCur[16];
     pose_inverse_kf(V.kfTcw + 16 * (size_t)C.called[(size_t)C.curPos], TwcCur);
     R.kf.resize((size_t)C.n);
@@ -231,54 +211,6 @@ CorrFit corr_fit(const drfe_lmap* db, const CorrPlan& C)
     return F;
 }
 
-/* the geometry block of the device image: whole after an edit, otherwise kept current by the calls themselves */
-int upload_geo(drfe_lmap* db, hipStream_t st)
-{
-    const bool moved = db->devDirty;           /* the slots changed: upload_image is about to send the rows again */
-    int rc = upload_image(db, st);
-    if (rc) return rc;
-    if (!moved && !db->devGeoDirty) return DRFE_OK;
-    const GeoImage& E = db->geo;
-    StageLayout<16> up;
-    const auto uScale = up.add<float>(db->scales.size());
-    const auto uTcw = up.add<float>(E.kfTcw.size());
-    const auto uOw = up.add<float>(E.kfOw.size());
-    const auto uWorld = up.add<float>(E.mpWorld.size());
-    const auto uRef = up.add<int32_t>(E.mpRef.size());
-    const auto uLevel = up.add<int32_t>(E.mpLevel.size());
-    const auto uBy = up.add<int32_t>(E.mpBy.size());
-    const auto uByRef = up.add<int32_t>(E.mpByRef.size());
-    const size_t bytes = up.bytes();
-    HIPCHK_TO(db->err, db->hup.grow(db->hup.capacity() >= bytes ? bytes : 2 * bytes));
-    HIPCHK_TO(db->err, db->dGeo.grow(db->dGeo.capacity() >= bytes ? bytes : 2 * bytes));
-    char* h = db->hup;
-    uScale.put(h, db->scales.data());
-    uTcw.put(h, E.kfTcw.data());
-    uOw.put(h, E.kfOw.data());
-    uWorld.put(h, E.mpWorld.data());
-    uRef.put(h, E.mpRef.data());
-    uLevel.put(h, E.mpLevel.data());
-    uBy.put(h, E.mpBy.data());
-    uByRef.put(h, E.mpByRef.data());
-    if (bytes) HIPCHK_TO(db->err, hipMemcpyAsync(db->dGeo, h, bytes, hipMemcpyHostToDevice, st));
-    db->sentBytes[2] += (int64_t)bytes;
-    char* d = db->dGeo;
-    CorrImage& V = db->dCorr;
-    V.nLevels = (int32_t)db->scales.size();
-    V.scale = uScale.at(d);
-    V.kfTcw = uTcw.at(d);
-    V.kfOw = uOw.at(d);
-    V.mpWorld = uWorld.at(d);
-    V.mpRef = uRef.at(d);
-    V.mpLevel = uLevel.at(d);
-    V.mpBy = uBy.at(d);
-    V.mpByRef = uByRef.at(d);
-    HIPCHK_TO(db->err, hipStreamSynchronize(st));
-    db->devGeoDirty = false;
-    db->corrStats[7]++;
-    return DRFE_OK;
-}
-
 /* The plan launches and the totals back, the capacity test, then chunk after chunk its records back; the image on the device is
  * written only after the capacity test.  A HIP failure in between leaves the device copy to be sent again. */
 int corr_device(drfe_lmap* db, const CorrPlan& C, const CorrFit& F, int32_t capacity, CorrResult& R, void* stream)
@@ -286,7 +218,7 @@ int corr_device(drfe_lmap* db, const CorrPlan& C, const CorrFit& F, int32_t capa
     drfe_ctx* c = db->ctx;
     HIPCHK_TO(db->err, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int rc = upload_geo(db, st);
+    int rc = lmap_upload(db, LMAP_NEED_GEO, st);
     if (rc) return rc;
     const Image& G = db->img;
     const size_t n = (size_t)C.n, nK = G.kfHandle.size(), nP = G.mpHandle.size();
@@ -351,13 +283,13 @@ int corr_device(drfe_lmap* db, const CorrPlan& C, const CorrFit& F, int32_t capa
     hipError_t e = drfe_launch_correct_plan(L, st);
     if (e == hipSuccess) e = hipMemcpyAsync(db->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(db, DRFE_ERR_HIP, std::string("lmap correct device call: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return lmap_fail(db, DRFE_ERR_HIP, std::string("lmap correct device call: ") + hipGetErrorString(e));
     const char* ho = db->io.hout;
     R.kf.assign(oKf.at(ho), oKf.at(ho) + n);
     const std::vector<int32_t> off(oOff.at(ho), oOff.at(ho) + n + 1);
     const int64_t total = off[n];
-    if (total < 0 || total > C.sumRows) return fail(db, DRFE_ERR_STATE, "lmap correct device call: totals past their bounds");
-    if (total > capacity) return fail(db, DRFE_ERR_CAPACITY, "lmap_correct: more moved points than points_capacity");
+    if (total < 0 || total > C.sumRows) return lmap_fail(db, DRFE_ERR_STATE, "lmap correct device call: totals past their bounds");
+    if (total > capacity) return lmap_fail(db, DRFE_ERR_CAPACITY, "lmap_correct: more moved points than points_capacity");
     R.item.resize((size_t)total);
     R.by.resize((size_t)total);
     R.world.resize(3 * (size_t)total);
@@ -365,7 +297,7 @@ int corr_device(drfe_lmap* db, const CorrPlan& C, const CorrFit& F, int32_t capa
     R.maxD.resize((size_t)total);
     R.minD.resize((size_t)total);
     R.status.resize((size_t)total);
-    db->devGeoDirty = true;                    /* until the last launch has run */
+    db->blk[drfe_lmap::GEO].stale_all();       /* until the last launch has run */
     StageLayout<16> li;
     const auto lItem = li.add<int32_t>((size_t)chunkRows);
     const auto lBy = li.add<int32_t>((size_t)chunkRows);
@@ -389,7 +321,7 @@ int corr_device(drfe_lmap* db, const CorrPlan& C, const CorrFit& F, int32_t capa
         L.j1 = (int32_t)j1;
         const size_t b = (size_t)off[j0], cnt = (size_t)(off[j1] - off[j0]);
         e = drfe_launch_correct_chunk(L, st);
-        if (e != hipSuccess) return fail(db, DRFE_ERR_HIP, std::string("lmap correct device call: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return lmap_fail(db, DRFE_ERR_HIP, std::string("lmap correct device call: ") + hipGetErrorString(e));
         if (cnt) {
             HIPCHK_TO(db->err, hipMemcpyAsync(lItem.at(hl), xItem.at(dS), 4 * cnt, hipMemcpyDeviceToHost, st));
             HIPCHK_TO(db->err, hipMemcpyAsync(lBy.at(hl), xBy.at(dS), 4 * cnt, hipMemcpyDeviceToHost, st));
@@ -414,8 +346,8 @@ int corr_device(drfe_lmap* db, const CorrPlan& C, const CorrFit& F, int32_t capa
     }
     e = drfe_launch_correct_poses(L, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(db, DRFE_ERR_HIP, std::string("lmap correct device call: ") + hipGetErrorString(e));
-    db->devGeoDirty = false;
+    if (e != hipSuccess) return lmap_fail(db, DRFE_ERR_HIP, std::string("lmap correct device call: ") + hipGetErrorString(e));
+    db->blk[drfe_lmap::GEO].assume_current();
     return DRFE_OK;
 }
 
@@ -425,7 +357,7 @@ int corr_finish(drfe_lmap* db, const CorrPlan& C, const CorrResult& R, drfe_lmap
     const Image& G = db->img;
     GeoImage& E = db->geo;
     const size_t total = R.item.size();
-    if ((int64_t)total > o->points_capacity) return fail(db, DRFE_ERR_CAPACITY, "lmap_correct: more moved points than points_capacity");
+    if ((int64_t)total > o->points_capacity) return lmap_fail(db, DRFE_ERR_CAPACITY, "lmap_correct: more moved points than points_capacity");
     for (int a = 0; a < C.n; a++) {
         const int32_t j = C.posOfArg[(size_t)a];
         const CorrKf& K = R.kf[(size_t)j];
@@ -466,7 +398,7 @@ int corr_finish(drfe_lmap* db, const CorrPlan& C, const CorrResult& R, drfe_lmap
         std::memcpy(&E.kfTcw[16 * s], K.Tiw, sizeof(K.Tiw));
         std::memcpy(&E.kfOw[3 * s], K.Ow, sizeof(K.Ow));
     }
-    if (!onDevice) db->devGeoDirty = true;
+    if (!onDevice) db->blk[drfe_lmap::GEO].stale_all();
     int64_t* st = db->corrStats;
     st[0]++;
     st[1] += C.n;
@@ -484,8 +416,8 @@ int corr_entry(drfe_lmap* db, int32_t cur, const double* Scw, int32_t n, const i
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (mode == 1 && !db->ctx) return fail(db, DRFE_ERR_STATE, "lmap_correct: a device call on a store without a context");
-    if (!Scw || !corr_out_ok(o)) return fail(db, DRFE_ERR_INVALID, "lmap_correct: invalid argument");
+    if (mode == 1 && !db->ctx) return lmap_fail(db, DRFE_ERR_STATE, "lmap_correct: a device call on a store without a context");
+    if (!Scw || !corr_out_ok(o)) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_correct: invalid argument");
     CorrPlan C;
     C.cur = cur;
     corr_sim3_from8(Scw, C.Scw);
@@ -498,7 +430,7 @@ int corr_entry(drfe_lmap* db, int32_t cur, const double* Scw, int32_t n, const i
     if (dev) {
         F = corr_fit(db, C);
         if (!F.fits && mode == 1)
-            return fail(db, DRFE_ERR_CAPACITY, "lmap_correct: the longest called row does not fit the configured device scratch (or the walk ranks an int32)");
+            return lmap_fail(db, DRFE_ERR_CAPACITY, "lmap_correct: the longest called row does not fit the configured device scratch (or the walk ranks an int32)");
         dev = F.fits;
     }
     CorrResult R;
@@ -513,17 +445,13 @@ int corr_entry(drfe_lmap* db, int32_t cur, const double* Scw, int32_t n, const i
 
 }  // namespace
 
-int lmap_build_geo(drfe_lmap* db) { return build_geo(db); }
-CorrImage lmap_geo_view(drfe_lmap* db) { return geo_view(db); }
-int lmap_upload_geo(drfe_lmap* db, hipStream_t st) { return upload_geo(db, st); }
-
 extern "C" {
 
 int drfe_lmap_set_scales(drfe_lmap* db, int32_t n_levels, const float* scale_factors)
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (n_levels <= 0 || !scale_factors) return fail(db, DRFE_ERR_INVALID, "lmap_set_scales: invalid argument");
+    if (n_levels <= 0 || !scale_factors) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_scales: invalid argument");
     db->scales.assign(scale_factors, scale_factors + n_levels);
     db->geoDirty = true;
     return DRFE_OK;
@@ -533,9 +461,9 @@ int drfe_lmap_get_scales(drfe_lmap* db, int32_t capacity, int32_t* n_levels, flo
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (!n_levels || capacity < 0 || (capacity > 0 && !scale_factors)) return fail(db, DRFE_ERR_INVALID, "lmap_get_scales: invalid argument");
+    if (!n_levels || capacity < 0 || (capacity > 0 && !scale_factors)) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_get_scales: invalid argument");
     *n_levels = (int32_t)db->scales.size();
-    if (*n_levels > capacity) return fail(db, DRFE_ERR_CAPACITY, "lmap_get_scales: more levels than capacity");
+    if (*n_levels > capacity) return lmap_fail(db, DRFE_ERR_CAPACITY, "lmap_get_scales: more levels than capacity");
     if (*n_levels) std::memcpy(scale_factors, db->scales.data(), sizeof(float) * db->scales.size());
     return DRFE_OK;
 }
@@ -544,9 +472,9 @@ int drfe_lmap_set_poses(drfe_lmap* db, int32_t count, const int32_t* handles, co
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (count < 0 || (count > 0 && (!handles || !Tcw))) return fail(db, DRFE_ERR_INVALID, "lmap_set_poses: invalid argument");
+    if (count < 0 || (count > 0 && (!handles || !Tcw))) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_poses: invalid argument");
     for (int i = 0; i < count; i++)
-        if (handles[i] < 0) return fail(db, DRFE_ERR_INVALID, "lmap_set_poses: a negative handle");
+        if (handles[i] < 0) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_poses: a negative handle");
     for (int i = 0; i < count; i++) std::memcpy(db->kfPose[handles[i]].data(), Tcw + 16 * (size_t)i, sizeof(float) * 16);
     if (count) db->geoDirty = true;
     return DRFE_OK;
@@ -556,9 +484,9 @@ int drfe_lmap_get_poses(drfe_lmap* db, int32_t count, const int32_t* handles, fl
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (count < 0 || (count > 0 && !handles)) return fail(db, DRFE_ERR_INVALID, "lmap_get_poses: invalid argument");
+    if (count < 0 || (count > 0 && !handles)) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_get_poses: invalid argument");
     for (int i = 0; i < count; i++)
-        if (db->kfPose.find(handles[i]) == db->kfPose.end()) return fail(db, DRFE_ERR_INVALID, "lmap_get_poses: a handle without a pose");
+        if (db->kfPose.find(handles[i]) == db->kfPose.end()) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_get_poses: a handle without a pose");
     for (int i = 0; i < count; i++) {
         const float* T = db->kfPose.at(handles[i]).data();
         if (Tcw) std::memcpy(Tcw + 16 * (size_t)i, T, sizeof(float) * 16);
@@ -573,9 +501,9 @@ int drfe_lmap_set_point_geometry(drfe_lmap* db, const drfe_lmap_point_geometry* 
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
     if (!r || r->count < 0 || (r->count > 0 && (!r->handle || !r->world || !r->ref_kf || !r->ref_level)))
-        return fail(db, DRFE_ERR_INVALID, "lmap_set_point_geometry: invalid argument");
+        return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_point_geometry: invalid argument");
     for (int i = 0; i < r->count; i++)
-        if (r->handle[i] < 0 || r->ref_kf[i] < 0) return fail(db, DRFE_ERR_INVALID, "lmap_set_point_geometry: a negative handle");
+        if (r->handle[i] < 0 || r->ref_kf[i] < 0) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_point_geometry: a negative handle");
     for (int i = 0; i < r->count; i++) {
         MpGeo& P = db->mpGeo[r->handle[i]];
         std::memcpy(P.X, r->world + 3 * (size_t)i, sizeof(P.X));
@@ -593,10 +521,10 @@ int drfe_lmap_get_point_geometry(drfe_lmap* db, int32_t count, const int32_t* ha
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (count < 0 || (count > 0 && !handles)) return fail(db, DRFE_ERR_INVALID, "lmap_get_point_geometry: invalid argument");
+    if (count < 0 || (count > 0 && !handles)) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_get_point_geometry: invalid argument");
     for (int i = 0; i < count; i++)
         if (db->mpGeo.find(handles[i]) == db->mpGeo.end())
-            return fail(db, DRFE_ERR_INVALID, "lmap_get_point_geometry: a handle without geometry");
+            return lmap_fail(db, DRFE_ERR_INVALID, "lmap_get_point_geometry: a handle without geometry");
     for (int i = 0; i < count; i++) {
         const MpGeo& P = db->mpGeo.at(handles[i]);
         if (world) std::memcpy(world + 3 * (size_t)i, P.X, sizeof(P.X));
@@ -637,7 +565,7 @@ int drfe_lmap_correct_scratch(drfe_lmap* db, int32_t n, const int32_t* handles, 
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (!out3) return fail(db, DRFE_ERR_INVALID, "lmap_correct_scratch: invalid argument");
+    if (!out3) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_correct_scratch: invalid argument");
     CorrPlan C;
     const int rc = corr_positions(db, n, handles, nullptr, C);
     if (rc) return rc;

@@ -18,8 +18,6 @@ using namespace lmap_store;
 
 namespace {
 
-int fail(drfe_lmap* db, int rc, const std::string& why) { return lmap_fail(db, rc, why); }
-
 /* the attributes by slot, after the image */
 int build_cull(drfe_lmap* db)
 {
@@ -77,29 +75,21 @@ int build_cull(drfe_lmap* db)
         }
     A.complete = complete;
     db->cullDirty = false;
-    db->devCullDirty = true;
+    db->blk[drfe_lmap::ATTR].stale_all();
     return DRFE_OK;
 }
 
+/* the walk's state over the image I and the attributes A, host or device; row, mpBad, nObs and live are the caller's working arrays */
+CullState cull_state(const LmapImage& I, const CullImage& A, int32_t* row, uint8_t* mpBad, int32_t* nObs, uint8_t* live)
+{
+    return CullState{I.kfMpOff, I.obsOff, I.obs, row, mpBad, nObs, live, A.thDepth, A.kfFlags, A.octave, A.depth, A.stereo, A.obsIdx};
+}
+
+/* on the host the walk works on the image and the counters themselves, and cull_undo takes it back */
 CullState host_state(drfe_lmap* db)
 {
-    Image& G = db->img;
-    CullAttr& A = db->cull;
-    CullState S;
-    S.kfMpOff = G.kfMpOff.data();
-    S.obsOff = G.obsOff.data();
-    S.obs = G.obs.data();
-    S.row = G.kfMp.data();
-    S.mpBad = G.mpBad.data();
-    S.nObs = A.nObs.data();
-    S.live = A.live.data();
-    S.thDepth = A.thDepth.data();
-    S.kfFlags = A.kfFlags.data();
-    S.octave = A.octave.data();
-    S.depth = A.depth.data();
-    S.stereo = A.stereo.data();
-    S.obsIdx = A.obsIdx.data();
-    return S;
+    lmap_host_views(db);
+    return cull_state(db->hView, db->hCull, db->img.kfMp.data(), db->img.mpBad.data(), db->cull.nObs.data(), db->cull.live.data());
 }
 
 /* a checked call, in slots */
@@ -126,8 +116,8 @@ bool cull_out_ok(const drfe_lmap_cull_out* o)
 /* the handles of a call into slots; refuses an unknown handle, a duplicate and a key frame that is already bad */
 int cull_plan(drfe_lmap* db, int32_t n, const int32_t* handles, int32_t monocular, CullPlan& C)
 {
-    if (n < 0 || (n > 0 && !handles)) return fail(db, DRFE_ERR_INVALID, "lmap_cull: invalid argument");
-    if (n > DRFE_LMAP_MAX_QUERIES) return fail(db, DRFE_ERR_INVALID, "lmap_cull: more than DRFE_LMAP_MAX_QUERIES key frames in a call");
+    if (n < 0 || (n > 0 && !handles)) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_cull: invalid argument");
+    if (n > DRFE_LMAP_MAX_QUERIES) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_cull: more than DRFE_LMAP_MAX_QUERIES key frames in a call");
     const int rc = build_cull(db);
     if (rc) return rc;
     const Image& G = db->img;
@@ -138,10 +128,10 @@ int cull_plan(drfe_lmap* db, int32_t n, const int32_t* handles, int32_t monocula
     C.recOff.assign(1, 0);
     for (int j = 0; j < n; j++) {
         const auto it = G.kfSlot.find(handles[j]);
-        if (it == G.kfSlot.end()) return fail(db, DRFE_ERR_INVALID, "lmap_cull: the call names an unknown key-frame handle");
+        if (it == G.kfSlot.end()) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_cull: the call names an unknown key-frame handle");
         const size_t s = (size_t)it->second;
-        if (C.pos[s] >= 0) return fail(db, DRFE_ERR_INVALID, "lmap_cull: the call names a key frame twice");
-        if (G.kfBad[s]) return fail(db, DRFE_ERR_INVALID, "lmap_cull: the call names a key frame that is already bad");
+        if (C.pos[s] >= 0) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_cull: the call names a key frame twice");
+        if (G.kfBad[s]) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_cull: the call names a key frame that is already bad");
         C.pos[s] = j;
         C.called[(size_t)j] = it->second;
         const int32_t len = G.kfMpOff[s + 1] - G.kfMpOff[s];
@@ -159,7 +149,7 @@ int cull_check(drfe_lmap* db, const CullPlan& C)
     const CullAttr& A = db->cull;
     if (A.complete) return DRFE_OK;
     auto lacks = [&](const char* kind, int32_t h, const std::string& of) {
-        return fail(db, DRFE_ERR_STATE, std::string("lmap_cull: ") + kind + " " + std::to_string(h) + of + " has no culling attributes that fit its row");
+        return lmap_fail(db, DRFE_ERR_STATE, std::string("lmap_cull: ") + kind + " " + std::to_string(h) + of + " has no culling attributes that fit its row");
     };
     for (int j = 0; j < C.n; j++) {
         const size_t k = (size_t)C.called[(size_t)j];
@@ -176,7 +166,7 @@ int cull_check(drfe_lmap* db, const CullPlan& C)
                 if (A.kfHas[ok] != 2) return lacks("observing key frame", G.kfHandle[ok], ", of map point " + std::to_string(h) + ",");
                 const int32_t idx = A.obsIdx[(size_t)o];
                 if (idx < 0 || idx >= G.kfMpOff[ok + 1] - G.kfMpOff[ok])
-                    return fail(db, DRFE_ERR_STATE, "lmap_cull: obs_index " + std::to_string(idx) + " of map point " + std::to_string(h) +
+                    return lmap_fail(db, DRFE_ERR_STATE, "lmap_cull: obs_index " + std::to_string(idx) + " of map point " + std::to_string(h) +
                                                         " lies outside the match row of key frame " + std::to_string(G.kfHandle[ok]));
             }
         }
@@ -255,7 +245,7 @@ int cull_effects(drfe_lmap* db, const CullPlan& C, CullWork& W, int j)
     GraphWork* Kc = &touch(G, W, c);
     const int32_t parent = Kc->parent;
     if (parent < 0)
-        return fail(db, DRFE_ERR_STATE, "lmap_cull: key frame " + std::to_string(G.kfHandle[(size_t)c]) + " would be culled and has no parent");
+        return lmap_fail(db, DRFE_ERR_STATE, "lmap_cull: key frame " + std::to_string(G.kfHandle[(size_t)c]) + " would be culled and has no parent");
     /* EraseConnection on every key frame of its weights row */
     const std::vector<Entry> mine = Kc->w;
     for (const Entry& e : mine) {
@@ -424,52 +414,6 @@ CullFit cull_fit(const drfe_lmap* db, const CullPlan& C)
     return F;
 }
 
-/* the attribute block of the device image: whole after an edit or a commit */
-int upload_cull(drfe_lmap* db, hipStream_t st)
-{
-    const bool moved = db->devDirty;           /* the rows are about to go up again: the arrays parallel to them follow */
-    int rc = lmap_upload_image(db, st);
-    if (rc) return rc;
-    if (!moved && !db->devCullDirty && !db->devCullTailDirty) return DRFE_OK;
-    const bool whole = moved || db->devCullDirty;
-    const CullAttr& A = db->cull;
-    StageLayout<16> up;
-    const auto uTh = up.add<float>(A.thDepth.size());
-    const auto uFlags = up.add<uint8_t>(A.kfFlags.size());
-    const auto uOct = up.add<int32_t>(A.octave.size());
-    const auto uDepth = up.add<float>(A.depth.size());
-    const auto uStereo = up.add<uint8_t>(A.stereo.size());
-    const auto uNObs = up.add<int32_t>(A.nObs.size());
-    const auto uIdx = up.add<int32_t>(A.obsIdx.size());
-    const size_t bytes = up.bytes();
-    HIPCHK_TO(db->err, db->hup.grow(db->hup.capacity() >= bytes ? bytes : 2 * bytes));
-    HIPCHK_TO(db->err, db->dCullBlock.grow(db->dCullBlock.capacity() >= bytes ? bytes : 2 * bytes));
-    char* h = db->hup;
-    uTh.put(h, A.thDepth.data());
-    uFlags.put(h, A.kfFlags.data());
-    uOct.put(h, A.octave.data());
-    uDepth.put(h, A.depth.data());
-    uStereo.put(h, A.stereo.data());
-    uNObs.put(h, A.nObs.data());
-    uIdx.put(h, A.obsIdx.data());
-    /* after a cull call only the counters and the observation indices differ: the end of the block */
-    const size_t from = whole ? 0 : uNObs.off;
-    if (bytes > from) HIPCHK_TO(db->err, hipMemcpyAsync((char*)db->dCullBlock + from, h + from, bytes - from, hipMemcpyHostToDevice, st));
-    db->sentBytes[3] += (int64_t)(bytes - from);
-    const char* d = db->dCullBlock;
-    CullImage& V = db->dCull;
-    V.thDepth = uTh.at(d);
-    V.kfFlags = uFlags.at(d);
-    V.octave = uOct.at(d);
-    V.depth = uDepth.at(d);
-    V.stereo = uStereo.at(d);
-    V.nObs = uNObs.at(d);
-    V.obsIdx = uIdx.at(d);
-    HIPCHK_TO(db->err, hipStreamSynchronize(st));
-    db->devCullDirty = db->devCullTailDirty = false;
-    return DRFE_OK;
-}
-
 /* The working state copied from the resident image, the chunks one after another on the stream, the counts of every position
  * back in one copy; then the effects of the verdicts here, in order, as the host entry applies them.  The resident image is only
  * read. */
@@ -478,7 +422,7 @@ int cull_device(drfe_lmap* db, const CullPlan& C, const CullFit& F, CullWork& W,
     drfe_ctx* c = db->ctx;
     HIPCHK_TO(db->err, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int rc = upload_cull(db, st);
+    int rc = lmap_upload(db, LMAP_NEED_ATTR, st);
     if (rc) return rc;
     const Image& G = db->img;
     const size_t n = (size_t)C.n, nK = G.kfHandle.size(), nP = G.mpHandle.size();
@@ -522,19 +466,7 @@ int cull_device(drfe_lmap* db, const CullPlan& C, const CullFit& F, CullWork& W,
     if (xLive.bytes()) HIPCHK_TO(db->err, hipMemsetAsync(xLive.at(dS), 1, xLive.bytes(), st));
     HIPCHK_TO(db->err, hipMemsetAsync(xSpec.at(dS), 0, xSpec.bytes(), st));
     CullLaunch L{};
-    L.S.kfMpOff = db->dView.kfMpOff;
-    L.S.obsOff = db->dView.obsOff;
-    L.S.obs = db->dView.obs;
-    L.S.row = xRow.at(dS);
-    L.S.mpBad = xBad.at(dS);
-    L.S.nObs = xNObs.at(dS);
-    L.S.live = xLive.at(dS);
-    L.S.thDepth = db->dCull.thDepth;
-    L.S.kfFlags = db->dCull.kfFlags;
-    L.S.octave = db->dCull.octave;
-    L.S.depth = db->dCull.depth;
-    L.S.stereo = db->dCull.stereo;
-    L.S.obsIdx = db->dCull.obsIdx;
+    L.S = cull_state(db->dView, db->dCull, xRow.at(dS), xBad.at(dS), xNObs.at(dS), xLive.at(dS));
     L.monocular = C.monocular;
     L.called = sCalled.at(d);
     L.pos = sPos.at(d);
@@ -565,7 +497,7 @@ int cull_device(drfe_lmap* db, const CullPlan& C, const CullFit& F, CullWork& W,
     }
     if (e == hipSuccess) e = hipMemcpyAsync(db->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(db, DRFE_ERR_HIP, std::string("lmap cull device call: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return lmap_fail(db, DRFE_ERR_HIP, std::string("lmap cull device call: ") + hipGetErrorString(e));
     const int32_t* res = oOut.at((const char*)db->io.hout);
     W.onDevice = true;
     for (size_t j = 0; j < n; j++) {
@@ -573,7 +505,7 @@ int cull_device(drfe_lmap* db, const CullPlan& C, const CullFit& F, CullWork& W,
         rc = cull_decided(db, C, W, (int)j, r[0], r[1]);
         if (rc) return rc;
         if (W.record[4 * j + 3] != r[2] || W.died[j] != r[3])
-            return fail(db, DRFE_ERR_STATE, "lmap cull device call: the device and the host disagree on key frame " +
+            return lmap_fail(db, DRFE_ERR_STATE, "lmap cull device call: the device and the host disagree on key frame " +
                                                 std::to_string(G.kfHandle[(size_t)C.called[j]]));
         W.walked += (int64_t)(uint32_t)r[4] | ((int64_t)r[5] << 32);
     }
@@ -663,7 +595,7 @@ int cull_finish(drfe_lmap* db, const CullPlan& C, CullWork& W, drfe_lmap_cull_ou
     else if (tObs > o->obs_capacity) small = "obs_capacity";
     if (small) {
         cull_undo(db, W);
-        return fail(db, DRFE_ERR_CAPACITY, std::string("lmap_cull: the call returns more than ") + small);
+        return lmap_fail(db, DRFE_ERR_CAPACITY, std::string("lmap_cull: the call returns more than ") + small);
     }
     /* per called key frame */
     const size_t n = (size_t)C.n;
@@ -807,13 +739,20 @@ int cull_finish(drfe_lmap* db, const CullPlan& C, CullWork& W, drfe_lmap_cull_ou
         db->kfCull.at(G.kfHandle[s]).flags |= CULL_KF_TO_BE_ERASED;
         A.kfFlags[s] |= CULL_KF_TO_BE_ERASED;
     }
-    /* what the device copy now lacks, piece by piece (lmap.cpp's upload_image, upload_cull above): the bad flags and the graph
-     * block after a cull, the nulled entries one by one, the observations and their offsets when a row got shorter, with the
-     * counters and indices parallel to them; a deferred key frame's flag is the one change in front of those */
-    if (!W.culled.empty()) db->devBadDirty = db->devGraphDirty = true;
-    for (const Entry& e : W.nulledLog) db->devNulls.push_back(e.first);
-    if (!W.pts.empty()) db->devObsDirty = db->devCullTailDirty = true;
-    if (!W.deferred.empty()) db->devCullDirty = true;
+    /* what the device copy now lacks, piece by piece: the bad flags and the graph block after a cull, the nulled entries one by
+     * one, the observations and their offsets when a row got shorter, with the counters and indices parallel to them; a deferred
+     * key frame's flag is the one change in front of those */
+    ResidentBlock &rows = db->blk[drfe_lmap::ROWS], &attr = db->blk[drfe_lmap::ATTR];
+    if (!W.culled.empty()) {
+        rows.stale(0, db->secMlBad);
+        db->blk[drfe_lmap::GRAPH].stale_all();
+    }
+    for (const Entry& e : W.nulledLog) rows.stale_at(db->secKfMp, (size_t)e.first);
+    if (!W.pts.empty()) {
+        rows.stale(db->secObsOff);
+        attr.stale(db->secNObs);
+    }
+    if (!W.deferred.empty()) attr.stale_all();
     if (refMoved) db->geoDirty = true;
     int64_t died = 0;
     for (const int32_t d : W.died) died += d;
@@ -834,8 +773,8 @@ int cull_entry_point(drfe_lmap* db, int32_t n, const int32_t* handles, int32_t m
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (mode == 1 && !db->ctx) return fail(db, DRFE_ERR_STATE, "lmap_cull: a device call on a store without a context");
-    if (!cull_out_ok(o)) return fail(db, DRFE_ERR_INVALID, "lmap_cull: invalid output arrays");
+    if (mode == 1 && !db->ctx) return lmap_fail(db, DRFE_ERR_STATE, "lmap_cull: a device call on a store without a context");
+    if (!cull_out_ok(o)) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_cull: invalid output arrays");
     CullPlan C;
     int rc = cull_plan(db, n, handles, monocular, C);
     if (rc) return rc;
@@ -846,7 +785,7 @@ int cull_entry_point(drfe_lmap* db, int32_t n, const int32_t* handles, int32_t m
     if (dev) {
         F = cull_fit(db, C);
         if (!F.fits && mode == 1)
-            return fail(db, DRFE_ERR_CAPACITY, "lmap_cull: the working state and the longest called row do not fit the configured device scratch");
+            return lmap_fail(db, DRFE_ERR_CAPACITY, "lmap_cull: the working state and the longest called row do not fit the configured device scratch");
         dev = F.fits;
     }
     CullWork W;
@@ -867,23 +806,17 @@ int drfe_lmap_set_cull_attributes(drfe_lmap* db, const drfe_lmap_cull_attributes
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (!r || r->n_kfs < 0 || r->n_points < 0) return fail(db, DRFE_ERR_INVALID, "lmap_set_cull_attributes: invalid argument");
+    if (!r || r->n_kfs < 0 || r->n_points < 0) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_cull_attributes: invalid argument");
     const int nk = r->n_kfs, np = r->n_points;
-    auto offsets_ok = [](const int32_t* off, int n) {
-        if (!off || off[0] != 0) return false;
-        for (int i = 0; i < n; i++)
-            if (off[i + 1] < off[i]) return false;
-        return true;
-    };
-    if (nk > 0 && (!r->kf_handle || !r->th_depth || !r->kf_flags || !offsets_ok(r->row_offsets, nk) ||
+    if (nk > 0 && (!r->kf_handle || !r->th_depth || !r->kf_flags || !lmap_offsets_ok(r->row_offsets, nk) ||
                    (r->row_offsets[nk] > 0 && (!r->octave || !r->depth || !r->stereo))))
-        return fail(db, DRFE_ERR_INVALID, "lmap_set_cull_attributes: invalid key-frame arrays");
-    if (np > 0 && (!r->point_handle || !r->n_obs || !offsets_ok(r->obs_offsets, np) || (r->obs_offsets[np] > 0 && !r->obs_index)))
-        return fail(db, DRFE_ERR_INVALID, "lmap_set_cull_attributes: invalid map-point arrays");
+        return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_cull_attributes: invalid key-frame arrays");
+    if (np > 0 && (!r->point_handle || !r->n_obs || !lmap_offsets_ok(r->obs_offsets, np) || (r->obs_offsets[np] > 0 && !r->obs_index)))
+        return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_cull_attributes: invalid map-point arrays");
     for (int i = 0; i < nk; i++)
-        if (r->kf_handle[i] < 0) return fail(db, DRFE_ERR_INVALID, "lmap_set_cull_attributes: a negative handle");
+        if (r->kf_handle[i] < 0) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_cull_attributes: a negative handle");
     for (int i = 0; i < np; i++)
-        if (r->point_handle[i] < 0) return fail(db, DRFE_ERR_INVALID, "lmap_set_cull_attributes: a negative handle");
+        if (r->point_handle[i] < 0) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_cull_attributes: a negative handle");
     for (int i = 0; i < nk; i++) {
         KfCull& K = db->kfCull[r->kf_handle[i]];
         const int32_t a = r->row_offsets[i], b = r->row_offsets[i + 1];
@@ -911,19 +844,19 @@ int drfe_lmap_get_cull_attributes(drfe_lmap* db, drfe_lmap_cull_attributes_out* 
         (o->n_kfs > 0 && (!o->kf_handle || !o->th_depth || !o->kf_flags || !o->row_offsets)) ||
         (o->row_capacity > 0 && (!o->octave || !o->depth || !o->stereo)) ||
         (o->n_points > 0 && (!o->point_handle || !o->n_obs || !o->obs_offsets)) || (o->obs_capacity > 0 && !o->obs_index))
-        return fail(db, DRFE_ERR_INVALID, "lmap_get_cull_attributes: invalid argument");
+        return lmap_fail(db, DRFE_ERR_INVALID, "lmap_get_cull_attributes: invalid argument");
     int64_t tR = 0, tO = 0;
     for (int i = 0; i < o->n_kfs; i++) {
         const auto it = db->kfCull.find(o->kf_handle[i]);
-        if (it == db->kfCull.end()) return fail(db, DRFE_ERR_INVALID, "lmap_get_cull_attributes: a key frame without attributes");
+        if (it == db->kfCull.end()) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_get_cull_attributes: a key frame without attributes");
         tR += (int64_t)it->second.octave.size();
     }
     for (int i = 0; i < o->n_points; i++) {
         const auto it = db->mpCull.find(o->point_handle[i]);
-        if (it == db->mpCull.end()) return fail(db, DRFE_ERR_INVALID, "lmap_get_cull_attributes: a map point without attributes");
+        if (it == db->mpCull.end()) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_get_cull_attributes: a map point without attributes");
         tO += (int64_t)it->second.obsIdx.size();
     }
-    if (tR > o->row_capacity || tO > o->obs_capacity) return fail(db, DRFE_ERR_CAPACITY, "lmap_get_cull_attributes: an output array is too small");
+    if (tR > o->row_capacity || tO > o->obs_capacity) return lmap_fail(db, DRFE_ERR_CAPACITY, "lmap_get_cull_attributes: an output array is too small");
     int32_t a = 0;
     if (o->n_kfs) o->row_offsets[0] = 0;
     for (int i = 0; i < o->n_kfs; i++) {
@@ -975,7 +908,7 @@ int drfe_lmap_cull_scratch(drfe_lmap* db, int32_t n, const int32_t* handles, int
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (!out3) return fail(db, DRFE_ERR_INVALID, "lmap_cull_scratch: invalid argument");
+    if (!out3) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_cull_scratch: invalid argument");
     CullPlan C;
     const int rc = cull_plan(db, n, handles, 0, C);
     if (rc) return rc;

@@ -12,8 +12,6 @@ using namespace lmap_store;
 
 namespace {
 
-int fail(drfe_lmap* db, int rc, const std::string& why) { return lmap_fail(db, rc, why); }
-
 /* the state by slot, after the geometry */
 int build_gba(drfe_lmap* db)
 {
@@ -52,7 +50,7 @@ int build_gba(drfe_lmap* db)
             A.mpHasPos[s] = P.hasX;
         }
     db->gbaDirty = false;
-    db->devGbaDirty = true;
+    db->blk[drfe_lmap::GBA].stale_all();
     return DRFE_OK;
 }
 
@@ -95,8 +93,8 @@ int gba_walk(drfe_lmap* db, int32_t nOrigins, const int32_t* origins, GbaPlan& W
     for (int a = 0; a < nOrigins; a++) {
         const auto it = G.kfSlot.find(origins[a]);
         if (it == G.kfSlot.end())
-            return fail(db, DRFE_ERR_STATE, "lmap_gba: the origin key frame " + std::to_string(origins[a]) + " is unknown");
-        if (W.at[(size_t)it->second] >= 0) return fail(db, DRFE_ERR_INVALID, "lmap_gba: the call names an origin twice");
+            return lmap_fail(db, DRFE_ERR_STATE, "lmap_gba: the origin key frame " + std::to_string(origins[a]) + " is unknown");
+        if (W.at[(size_t)it->second] >= 0) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_gba: the call names an origin twice");
         W.at[(size_t)it->second] = (int32_t)W.list.size();
         W.list.push_back(it->second);
         W.parentV.push_back(-1);
@@ -105,12 +103,12 @@ int gba_walk(drfe_lmap* db, int32_t nOrigins, const int32_t* origins, GbaPlan& W
     }
     for (size_t v = 0; v < W.list.size(); v++) {
         const int32_t s = W.list[v];
-        if (!E.kfHas[(size_t)s]) return fail(db, DRFE_ERR_STATE, "lmap_gba: the visited " + kfName(s) + " has no pose");
+        if (!E.kfHas[(size_t)s]) return lmap_fail(db, DRFE_ERR_STATE, "lmap_gba: the visited " + kfName(s) + " has no pose");
         if (!W.composed[v] && !A.kfHasT[(size_t)s])
-            return fail(db, DRFE_ERR_STATE, "lmap_gba: the visited " + kfName(s) + " has no TcwGBA");
+            return lmap_fail(db, DRFE_ERR_STATE, "lmap_gba: the visited " + kfName(s) + " has no TcwGBA");
         for (int32_t i = G.childOff[(size_t)s]; i < G.childOff[(size_t)s + 1]; i++) {
             const int32_t c = G.child[(size_t)i];
-            if (W.at[(size_t)c] >= 0) return fail(db, DRFE_ERR_STATE, "lmap_gba: the " + kfName(c) + " would be visited twice");
+            if (W.at[(size_t)c] >= 0) return lmap_fail(db, DRFE_ERR_STATE, "lmap_gba: the " + kfName(c) + " would be visited twice");
             const uint8_t comp = A.kfStamp[(size_t)c] != W.loop;
             const int32_t d = comp ? depth[v] + 1 : 0;
             W.at[(size_t)c] = (int32_t)W.list.size();
@@ -153,11 +151,11 @@ int gba_points(drfe_lmap* db, GbaPlan& W, GbaResult* R)
         const int32_t stamp = A.mpStamp[p];
         int32_t r = -1, v = -1, refStamp = 0;
         /* a point that is not bad either moves, and its position is part of its geometry, or is asked for its reference key frame */
-        if (!bad && !E.mpHas[p]) return fail(db, DRFE_ERR_STATE, "lmap_gba: the " + mpName(p) + " has no geometry");
+        if (!bad && !E.mpHas[p]) return lmap_fail(db, DRFE_ERR_STATE, "lmap_gba: the " + mpName(p) + " has no geometry");
         if (!bad && stamp != W.loop) {
             r = E.mpRef[p];
             if (r < 0)
-                return fail(db, DRFE_ERR_STATE, "lmap_gba: the reference key frame " + std::to_string(db->mpGeo.at(G.mpHandle[p]).ref) +
+                return lmap_fail(db, DRFE_ERR_STATE, "lmap_gba: the reference key frame " + std::to_string(db->mpGeo.at(G.mpHandle[p]).ref) +
                                                     " of " + mpName(p) + " is unknown");
             v = W.at[(size_t)r];
             refStamp = v >= 0 && W.composed[(size_t)v] ? W.loop : A.kfStamp[(size_t)r];
@@ -169,11 +167,11 @@ int gba_points(drfe_lmap* db, GbaPlan& W, GbaResult* R)
         }
         const float *bef = nullptr, *Tcw = nullptr;
         if (kind == GBA_POINT_POS) {
-            if (!A.mpHasPos[p]) return fail(db, DRFE_ERR_STATE, "lmap_gba: the " + mpName(p) + " holds the stamp and has no PosGBA");
+            if (!A.mpHasPos[p]) return lmap_fail(db, DRFE_ERR_STATE, "lmap_gba: the " + mpName(p) + " holds the stamp and has no PosGBA");
         } else {
             const std::string of = "lmap_gba: the reference key frame " + std::to_string(G.kfHandle[(size_t)r]) + " of " + mpName(p);
-            if (!E.kfHas[(size_t)r]) return fail(db, DRFE_ERR_STATE, of + " has no pose");
-            if (v < 0 && !A.kfHasBef[(size_t)r]) return fail(db, DRFE_ERR_STATE, of + " was not reached and has no TcwBefGBA");
+            if (!E.kfHas[(size_t)r]) return lmap_fail(db, DRFE_ERR_STATE, of + " has no pose");
+            if (v < 0 && !A.kfHasBef[(size_t)r]) return lmap_fail(db, DRFE_ERR_STATE, of + " was not reached and has no TcwBefGBA");
             if (R) {
                 bef = v >= 0 ? &R->bef[16 * (size_t)v] : &A.kfBef[16 * (size_t)r];
                 Tcw = v >= 0 ? &R->pose[16 * (size_t)v] : &E.kfTcw[16 * (size_t)r];
@@ -228,45 +226,6 @@ GbaFit gba_fit(const drfe_lmap* db)
     return F;
 }
 
-/* the state block of the device image: whole after an edit, otherwise kept current by the calls themselves */
-int upload_gba(drfe_lmap* db, hipStream_t st)
-{
-    int rc = lmap_upload_geo(db, st);
-    if (rc) return rc;
-    if (!db->devGbaDirty) return DRFE_OK;
-    const GbaAttr& A = db->gba;
-    StageLayout<16> up;
-    const auto uT = up.add<float>(A.kfTcwGBA.size());
-    const auto uBef = up.add<float>(A.kfBef.size());
-    const auto uPos = up.add<float>(A.mpPosGBA.size());
-    const auto uKs = up.add<int32_t>(A.kfStamp.size());
-    const auto uPs = up.add<int32_t>(A.mpStamp.size());
-    const auto uHas = up.add<uint8_t>(A.kfHasBef.size());
-    const size_t bytes = up.bytes();
-    HIPCHK_TO(db->err, db->hup.grow(db->hup.capacity() >= bytes ? bytes : 2 * bytes));
-    HIPCHK_TO(db->err, db->dGbaBlock.grow(db->dGbaBlock.capacity() >= bytes ? bytes : 2 * bytes));
-    char* h = db->hup;
-    uT.put(h, A.kfTcwGBA.data());
-    uBef.put(h, A.kfBef.data());
-    uPos.put(h, A.mpPosGBA.data());
-    uKs.put(h, A.kfStamp.data());
-    uPs.put(h, A.mpStamp.data());
-    uHas.put(h, A.kfHasBef.data());
-    if (bytes) HIPCHK_TO(db->err, hipMemcpyAsync(db->dGbaBlock, h, bytes, hipMemcpyHostToDevice, st));
-    db->sentBytes[4] += (int64_t)bytes;
-    char* d = db->dGbaBlock;
-    GbaImage& V = db->dGba;
-    V.kfTcwGBA = uT.at(d);
-    V.kfBef = uBef.at(d);
-    V.mpPosGBA = uPos.at(d);
-    V.kfStamp = uKs.at(d);
-    V.mpStamp = uPs.at(d);
-    V.kfHasBef = uHas.at(d);
-    HIPCHK_TO(db->err, hipStreamSynchronize(st));
-    db->devGbaDirty = false;
-    return DRFE_OK;
-}
-
 /* The key-frame launches and their records back, then chunk after chunk of point slots its records back.  Everything the call
  * could be refused for has been checked, so the resident blocks are written from the first launch on; a HIP failure in between
  * leaves both to be sent again. */
@@ -275,7 +234,7 @@ int gba_device(drfe_lmap* db, const GbaPlan& W, GbaResult& R, void* stream)
     drfe_ctx* c = db->ctx;
     HIPCHK_TO(db->err, hipSetDevice(c->device));
     hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int rc = upload_gba(db, st);
+    int rc = lmap_upload(db, LMAP_NEED_GBA, st);
     if (rc) return rc;
     const size_t nV = W.list.size(), nP = db->img.mpHandle.size(), chunk = (size_t)W.chunkPts;
     const size_t nGroups = (chunk + GBA_TILE - 1) / GBA_TILE;
@@ -330,12 +289,12 @@ int gba_device(drfe_lmap* db, const GbaPlan& W, GbaResult& R, void* stream)
     L.pkKind = xPk.at(dS);
     L.outPose = oPose.at(dO);
     L.outBef = oBef.at(dO);
-    db->devGeoDirty = true;                    /* until the last launch has run */
-    db->devGbaDirty = true;
+    db->blk[drfe_lmap::GEO].stale_all();       /* until the last launch has run */
+    db->blk[drfe_lmap::GBA].stale_all();
     hipError_t e = drfe_launch_gba_keyframes(L, st);
     if (e == hipSuccess) e = hipMemcpyAsync(db->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(db, DRFE_ERR_HIP, std::string("lmap gba device call: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return lmap_fail(db, DRFE_ERR_HIP, std::string("lmap gba device call: ") + hipGetErrorString(e));
     const char* ho = db->io.hout;
     R.pose.assign(oPose.at(ho), oPose.at(ho) + 16 * nV);
     R.bef.assign(oBef.at(ho), oBef.at(ho) + 16 * nV);
@@ -348,7 +307,7 @@ int gba_device(drfe_lmap* db, const GbaPlan& W, GbaResult& R, void* stream)
         L.p0 = (int32_t)p0;
         L.p1 = (int32_t)p1;
         e = drfe_launch_gba_points(L, st);
-        if (e != hipSuccess) return fail(db, DRFE_ERR_HIP, std::string("lmap gba device call: ") + hipGetErrorString(e));
+        if (e != hipSuccess) return lmap_fail(db, DRFE_ERR_HIP, std::string("lmap gba device call: ") + hipGetErrorString(e));
         const size_t g = (p1 - p0 + GBA_TILE - 1) / GBA_TILE;
         HIPCHK_TO(db->err, hipMemcpyAsync(lTot.at(hl), xCnt.at(dS) + g, 4, hipMemcpyDeviceToHost, st));
         if (cnt) {
@@ -357,7 +316,7 @@ int gba_device(drfe_lmap* db, const GbaPlan& W, GbaResult& R, void* stream)
             HIPCHK_TO(db->err, hipMemcpyAsync(lKind.at(hl), xPk.at(dS), cnt, hipMemcpyDeviceToHost, st));
         }
         HIPCHK_TO(db->err, hipStreamSynchronize(st));
-        if ((size_t)*lTot.at(hl) != cnt) return fail(db, DRFE_ERR_STATE, "lmap gba device call: the moved points of a chunk are not the host's count");
+        if ((size_t)*lTot.at(hl) != cnt) return lmap_fail(db, DRFE_ERR_STATE, "lmap gba device call: the moved points of a chunk are not the host's count");
         if (cnt) {
             std::memcpy(&R.item[b], lItem.at(hl), 4 * cnt);
             std::memcpy(&R.world[3 * b], lWorld.at(hl), 12 * cnt);
@@ -365,8 +324,8 @@ int gba_device(drfe_lmap* db, const GbaPlan& W, GbaResult& R, void* stream)
         }
         b += cnt;
     }
-    db->devGeoDirty = false;
-    db->devGbaDirty = false;
+    db->blk[drfe_lmap::GEO].assume_current();
+    db->blk[drfe_lmap::GBA].assume_current();
     return DRFE_OK;
 }
 
@@ -415,8 +374,8 @@ void gba_finish(drfe_lmap* db, const GbaPlan& W, const GbaResult& R, drfe_lmap_g
         std::memcpy(&E.mpWorld[3 * p], &R.world[3 * t], sizeof(float) * 3);
     }
     if (!onDevice) {
-        db->devGeoDirty = true;
-        db->devGbaDirty = true;
+        db->blk[drfe_lmap::GEO].stale_all();
+        db->blk[drfe_lmap::GBA].stale_all();
     }
     int64_t* st = db->gbaStats;
     st[0]++;
@@ -434,8 +393,8 @@ int gba_entry(drfe_lmap* db, int32_t loop, int32_t nOrigins, const int32_t* orig
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (mode == 1 && !db->ctx) return fail(db, DRFE_ERR_STATE, "lmap_gba: a device call on a store without a context");
-    if (nOrigins <= 0 || !origins || !gba_out_ok(o)) return fail(db, DRFE_ERR_INVALID, "lmap_gba: invalid argument");
+    if (mode == 1 && !db->ctx) return lmap_fail(db, DRFE_ERR_STATE, "lmap_gba: a device call on a store without a context");
+    if (nOrigins <= 0 || !origins || !gba_out_ok(o)) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_gba: invalid argument");
     int rc = build_gba(db);
     if (rc) return rc;
     GbaPlan W;
@@ -445,7 +404,7 @@ int gba_entry(drfe_lmap* db, int32_t loop, int32_t nOrigins, const int32_t* orig
     bool dev = mode == 1 || (mode == 2 && db->ctx && (int64_t)db->img.mpHandle.size() >= (int64_t)DRFE_LMAP_GBA_DEVICE_FROM);
     if (dev) {
         const GbaFit F = gba_fit(db);
-        if (!F.fits && mode == 1) return fail(db, DRFE_ERR_CAPACITY, "lmap_gba: the configured device scratch does not hold one point slot");
+        if (!F.fits && mode == 1) return lmap_fail(db, DRFE_ERR_CAPACITY, "lmap_gba: the configured device scratch does not hold one point slot");
         dev = F.fits;
         W.chunkPts = F.chunkPts;
     }
@@ -457,8 +416,8 @@ int gba_entry(drfe_lmap* db, int32_t loop, int32_t nOrigins, const int32_t* orig
     rc = gba_points(db, W, dev ? nullptr : &R);
     if (rc) return rc;
     if ((int64_t)W.list.size() > o->keyframes_capacity)
-        return fail(db, DRFE_ERR_CAPACITY, "lmap_gba: more visited key frames than keyframes_capacity");
-    if (W.nKind[1] + W.nKind[2] > o->points_capacity) return fail(db, DRFE_ERR_CAPACITY, "lmap_gba: more moved points than points_capacity");
+        return lmap_fail(db, DRFE_ERR_CAPACITY, "lmap_gba: more visited key frames than keyframes_capacity");
+    if (W.nKind[1] + W.nKind[2] > o->points_capacity) return lmap_fail(db, DRFE_ERR_CAPACITY, "lmap_gba: more moved points than points_capacity");
     if (dev) {
         rc = gba_device(db, W, R, stream);
         if (rc) return rc;
@@ -467,7 +426,7 @@ int gba_entry(drfe_lmap* db, int32_t loop, int32_t nOrigins, const int32_t* orig
     return DRFE_OK;
 }
 
-/* a setter's row into the state by slot when that is current, so that an edit costs no rebuild */
+/* a setter's row into the state by slot when that is current, so that an edit costs no rebuild; the setter marks the block, once */
 template <class F>
 void patch_slot(drfe_lmap* db, const std::unordered_map<int32_t, int32_t>& slots, int32_t handle, F&& f)
 {
@@ -477,7 +436,6 @@ void patch_slot(drfe_lmap* db, const std::unordered_map<int32_t, int32_t>& slots
     }
     const auto it = slots.find(handle);
     if (it != slots.end()) f((size_t)it->second);
-    db->devGbaDirty = true;
 }
 
 }  // namespace
@@ -488,9 +446,9 @@ int drfe_lmap_set_gba_keyframes(drfe_lmap* db, int32_t count, const int32_t* han
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (count < 0 || (count > 0 && (!handles || !TcwGBA || !stamp))) return fail(db, DRFE_ERR_INVALID, "lmap_set_gba_keyframes: invalid argument");
+    if (count < 0 || (count > 0 && (!handles || !TcwGBA || !stamp))) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_gba_keyframes: invalid argument");
     for (int i = 0; i < count; i++)
-        if (handles[i] < 0) return fail(db, DRFE_ERR_INVALID, "lmap_set_gba_keyframes: a negative handle");
+        if (handles[i] < 0) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_gba_keyframes: a negative handle");
     GbaAttr& A = db->gba;
     for (int i = 0; i < count; i++) {
         KfGba& K = db->kfGba[handles[i]];
@@ -503,6 +461,7 @@ int drfe_lmap_set_gba_keyframes(drfe_lmap* db, int32_t count, const int32_t* han
             A.kfStamp[s] = K.stamp;
         });
     }
+    if (count) db->blk[drfe_lmap::GBA].stale_all();
     return DRFE_OK;
 }
 
@@ -510,9 +469,9 @@ int drfe_lmap_set_gba_points(drfe_lmap* db, int32_t count, const int32_t* handle
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (count < 0 || (count > 0 && (!handles || !PosGBA || !stamp))) return fail(db, DRFE_ERR_INVALID, "lmap_set_gba_points: invalid argument");
+    if (count < 0 || (count > 0 && (!handles || !PosGBA || !stamp))) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_gba_points: invalid argument");
     for (int i = 0; i < count; i++)
-        if (handles[i] < 0) return fail(db, DRFE_ERR_INVALID, "lmap_set_gba_points: a negative handle");
+        if (handles[i] < 0) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_gba_points: a negative handle");
     GbaAttr& A = db->gba;
     for (int i = 0; i < count; i++) {
         MpGba& P = db->mpGba[handles[i]];
@@ -525,6 +484,7 @@ int drfe_lmap_set_gba_points(drfe_lmap* db, int32_t count, const int32_t* handle
             A.mpStamp[s] = P.stamp;
         });
     }
+    if (count) db->blk[drfe_lmap::GBA].stale_all();
     return DRFE_OK;
 }
 
@@ -533,9 +493,9 @@ int drfe_lmap_get_gba_keyframes(drfe_lmap* db, int32_t count, const int32_t* han
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (count < 0 || (count > 0 && !handles)) return fail(db, DRFE_ERR_INVALID, "lmap_get_gba_keyframes: invalid argument");
+    if (count < 0 || (count > 0 && !handles)) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_get_gba_keyframes: invalid argument");
     for (int i = 0; i < count; i++)
-        if (db->kfGba.find(handles[i]) == db->kfGba.end()) return fail(db, DRFE_ERR_INVALID, "lmap_get_gba_keyframes: a handle without state");
+        if (db->kfGba.find(handles[i]) == db->kfGba.end()) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_get_gba_keyframes: a handle without state");
     for (int i = 0; i < count; i++) {
         const KfGba& K = db->kfGba.at(handles[i]);
         if (TcwGBA) std::memcpy(TcwGBA + 16 * (size_t)i, K.T, sizeof(K.T));
@@ -551,9 +511,9 @@ int drfe_lmap_get_gba_points(drfe_lmap* db, int32_t count, const int32_t* handle
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (count < 0 || (count > 0 && !handles)) return fail(db, DRFE_ERR_INVALID, "lmap_get_gba_points: invalid argument");
+    if (count < 0 || (count > 0 && !handles)) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_get_gba_points: invalid argument");
     for (int i = 0; i < count; i++)
-        if (db->mpGba.find(handles[i]) == db->mpGba.end()) return fail(db, DRFE_ERR_INVALID, "lmap_get_gba_points: a handle without state");
+        if (db->mpGba.find(handles[i]) == db->mpGba.end()) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_get_gba_points: a handle without state");
     for (int i = 0; i < count; i++) {
         const MpGba& P = db->mpGba.at(handles[i]);
         if (PosGBA) std::memcpy(PosGBA + 3 * (size_t)i, P.X, sizeof(P.X));
@@ -592,7 +552,7 @@ int drfe_lmap_gba_scratch(drfe_lmap* db, int64_t* out3)
 {
     if (!db) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    if (!out3) return fail(db, DRFE_ERR_INVALID, "lmap_gba_scratch: invalid argument");
+    if (!out3) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_gba_scratch: invalid argument");
     const int rc = lmap_build_image(db);
     if (rc) return rc;
     const GbaFit F = gba_fit(db);

@@ -1,4 +1,4 @@
-/* lmap_internal.h — what lmap.cpp, lmap_correct.cpp, lmap_cull.cpp and lmap_gba.cpp hand to the store's kernels (DESIGN.md sections
+/* lmap_internal.h — what lmap.cpp, lmap_conn.cpp, lmap_correct.cpp, lmap_cull.cpp and lmap_gba.cpp hand to the store's kernels (DESIGN.md sections
  * 25 to 29). */
 #ifndef DRFE_LMAP_INTERNAL_H
 #define DRFE_LMAP_INTERNAL_H

@@ -1,12 +1,14 @@
-/* lmap_store.h — the local-map store itself: its rows by handle, the flat image of them, the optional geometry and culling
- * attributes and the device copies, for the three files that implement its entries: lmap.cpp (Tracking::UpdateLocalMap and
- * KeyFrame::UpdateConnections, DESIGN.md sections 25 and 26), lmap_correct.cpp (the Sim3 propagation of LoopClosing::CorrectLoop,
+/* lmap_store.h — the local-map store itself: its rows by handle, the flat image of them, the optional geometry, culling attributes
+ * and adjustment state by slot, and the five resident blocks that keep them on the device (resident_block.h).  lmap_store.cpp holds
+ * its lifecycle, setters, image and upload; its entries are in lmap.cpp (Tracking::UpdateLocalMap),
+ * lmap_conn.cpp (KeyFrame::UpdateConnections, section 26), lmap_correct.cpp (the Sim3 propagation of LoopClosing::CorrectLoop,
  * section 27), lmap_cull.cpp (LocalMapping::KeyFrameCulling with KeyFrame::SetBadFlag, section 28) and lmap_gba.cpp (the map update
  * of LoopClosing::RunGlobalBundleAdjustment, section 29). */
 #ifndef DRFE_LMAP_STORE_H
 #define DRFE_LMAP_STORE_H
 
 #include "lmap_internal.h"
+#include "resident_block.h"
 
 #include <array>
 #include <mutex>
@@ -104,27 +106,6 @@ struct Image {
     /* the connection rows: weights in ascending slot, the ordered list as stored */
     std::vector<uint8_t> kfFirst;
     std::vector<int32_t> cwOff, cwKf, cwW, coOff, coKf, coW;
-    LmapImage view() const
-    {
-        LmapImage I;
-        I.nK = (int32_t)kfHandle.size();
-        I.nP = (int32_t)mpHandle.size();
-        I.nL = (int32_t)mlHandle.size();
-        I.kfBad = kfBad.data();
-        I.kfParent = kfParent.data();
-        I.kfNbr = kfNbr.data();
-        I.childOff = childOff.data();
-        I.child = child.data();
-        I.kfMpOff = kfMpOff.data();
-        I.kfMp = kfMp.data();
-        I.kfMlOff = kfMlOff.data();
-        I.kfMl = kfMl.data();
-        I.mpBad = mpBad.data();
-        I.obsOff = obsOff.data();
-        I.obs = obs.data();
-        I.mlBad = mlBad.data();
-        return I;
-    }
 };
 
 }  // namespace lmap_store
@@ -141,8 +122,6 @@ struct drfe_lmap {
     std::unordered_map<uint64_t, int32_t> rankOwner;
     lmap_store::Image img;
     bool imgDirty = true;              /* the image lacks an edit of the rows */
-    bool devDirty = true, devBadDirty = true;   /* the device copy lacks the image / its bad flags */
-    bool devGraphDirty = true;         /* the device copy lacks what a connect call committed */
     int64_t lastId = 0;
     int64_t scratchBytes = (int64_t)1 << 30;
     int64_t stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -153,53 +132,51 @@ struct drfe_lmap {
     std::vector<float> scales;
     lmap_store::GeoImage geo;
     bool geoDirty = true;              /* the geometry image lacks an edit of the rows or of the geometry */
-    bool devGeoDirty = true;           /* the device copy lacks the geometry image */
     int64_t corrStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    DevBuf<char> dGeo;
-    CorrImage dCorr;
     /* the optional attributes of KeyFrameCulling, by handle, and their image by slot */
     std::unordered_map<int32_t, lmap_store::KfCull> kfCull;
     std::unordered_map<int32_t, lmap_store::MpCull> mpCull;
     lmap_store::CullAttr cull;
     bool cullDirty = true;             /* the attribute image lacks an edit of the rows or of the attributes */
-    bool devCullDirty = true;          /* the device copy lacks the attribute image */
-    bool devCullTailDirty = false;     /* or only its counters and observation indices, the end of the block */
-    /* what a cull call committed into the image and the device copy of the rows block still lacks */
-    bool devObsDirty = false;          /* the observations and their offsets, the end of the block */
-    std::vector<int32_t> devNulls;     /* match-row entries set to -1 */
     int64_t sentBytes[5] = {0, 0, 0, 0, 0};   /* host-to-device bytes of the rows, graph, geometry, attribute and adjustment blocks */
     int64_t cullStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    DevBuf<char> dCullBlock;
-    CullImage dCull;
     /* the optional state of the map update after a global bundle adjustment, by handle, and by slot */
     std::unordered_map<int32_t, lmap_store::KfGba> kfGba;
     std::unordered_map<int32_t, lmap_store::MpGba> mpGba;
     lmap_store::GbaAttr gba;
     bool gbaDirty = true;              /* the state by slot lacks an edit of the rows or of the state */
-    bool devGbaDirty = true;           /* the device copy lacks the state by slot */
     int64_t gbaStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    DevBuf<char> dGbaBlock;
-    GbaImage dGba;
     /* the host walk's stamps, kept between calls: an item is stamped for the query whose serial it holds */
     std::vector<int32_t> stampP, stampL, inP, inL;
     int32_t serial = 0;
-    DevBuf<char> dImg, dGraph;
-    LmapImage dView;
-    ConnImage dConn;
+    /* the resident blocks, in upload order, with their device memory; the views of them the kernels take (d...) and the host walks
+     * (h...); the sections that edits mark by name (lmap_store.cpp binds them) */
+    enum { ROWS, GRAPH, GEO, ATTR, GBA, BLOCKS };
+    ResidentBlock blk[BLOCKS];
+    DevBuf<char> dev[BLOCKS];
+    LmapImage dView = {}, hView = {};
+    ConnImage dConn = {};
+    CorrImage dCorr = {}, hCorr = {};
+    CullImage dCull = {}, hCull = {};
+    GbaImage dGba = {};
+    int secMlBad = 0, secKfMp = 0, secObsOff = 0, secNObs = 0;
     StagePair io;
     DevBuf<char> scratch;
-    PinnedBuf<char> hup, hgraph, hlist;
+    PinnedBuf<char> hup, hlist;
 };
 
-/* lmap.cpp's, for lmap_correct.cpp and lmap_cull.cpp: the error of a refused call; the image of the rows, rebuilt when an edit made it stale
- * (DRFE_ERR_STATE and the name of the reference when one dangles); the image on the device, sent when it is stale */
+/* lmap_store.cpp's: the error of a refused call; the image of the rows, rebuilt when an edit made it stale (DRFE_ERR_STATE and the
+ * name of the reference when one dangles), which marks every block wholly stale: the slots may have moved */
 int lmap_fail(drfe_lmap* db, int rc, const std::string& why);
 int lmap_build_image(drfe_lmap* db);
-int lmap_upload_image(drfe_lmap* db, hipStream_t st);
-/* lmap_correct.cpp's, for lmap_gba.cpp: the geometry by slot, rebuilt when stale; its view; the geometry block on the device, sent
- * when it is stale (after the image) */
+/* the counts of the views and the host views' pointers, wherever the arrays are now */
+void lmap_host_views(drfe_lmap* db);
+/* the blocks of `need` (bit b = block b; a later block implies the rows and the graph) brought up to date in block order: the stale
+ * runs staged back to back, one synchronisation.  A call's build_* runs before it. */
+enum { LMAP_NEED_IMAGE = 3, LMAP_NEED_GEO = 3 | 4, LMAP_NEED_ATTR = 3 | 8, LMAP_NEED_GBA = 3 | 4 | 16 };
+int lmap_upload(drfe_lmap* db, unsigned need, hipStream_t st);
+bool lmap_offsets_ok(const int32_t* off, int n);
+/* lmap_correct.cpp's, for lmap_gba.cpp: the geometry by slot, rebuilt when stale */
 int lmap_build_geo(drfe_lmap* db);
-CorrImage lmap_geo_view(drfe_lmap* db);
-int lmap_upload_geo(drfe_lmap* db, hipStream_t st);
 
 #endif

@@ -1,6 +1,6 @@
 /* conn_asan.cpp — a seeded script on the host entries of the local-map store (drfe_lmap_connect_host with conn_core.h,
  * drfe_lmap_get_connections, drfe_lmap_update_host), as a program of its own so that the host code can be built with
- * the address and undefined-behaviour sanitizers on its host side only (conn_asan.mk compiles lmap.cpp into it; no device is
+ * the address and undefined-behaviour sanitizers on its host side only (conn_asan.mk compiles lmap_store.cpp, lmap.cpp and lmap_conn.cpp into it; no device is
  * opened: the store has no context).
  *
  * 60 calls of 1 .. 12 key frames on a clustered graph of 80 key frames, with bad flags set, rows replaced and a key frame removed

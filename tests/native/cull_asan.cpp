@@ -1,6 +1,6 @@
 /* cull_asan.cpp — the host entry of LocalMapping::KeyFrameCulling (drfe_lmap_cull_host, lmap_cull.cpp with cull_core.h) as a
  * program of its own, so that the host code can be built with the address and undefined-behaviour sanitizers on its host side
- * only (cull_asan.mk compiles lmap.cpp and lmap_cull.cpp into it; no device is opened: the stores have no context).
+ * only (cull_asan.mk compiles the store's files and lmap_cull.cpp into it; no device is opened: the stores have no context).
  *
  * It runs what cull_caller.cpp runs in host mode - seven calls through the adaptor on stand-in objects, every store row compared
  * with the objects after each - and then the paths that take work back: every output capacity one too small in turn

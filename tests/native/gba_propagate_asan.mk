@@ -2,7 +2,7 @@
 # UndefinedBehaviorSanitizer, as a program of its own (never loaded into python, never run on a GPU: run it in host mode, where the
 # store has no context).  Not part of build(); run by hand:
 #   make -C tests/native -f gba_propagate_asan.mk && tests/native/gba_propagate_asan host
-# lmap.cpp, lmap_correct.cpp (the geometry the update reads) and lmap_gba.cpp are compiled into the program with the sanitizers on
+# lmap_store.cpp, lmap.cpp, lmap_conn.cpp, lmap_correct.cpp (the geometry the update reads) and lmap_gba.cpp are compiled into the program with the sanitizers on
 # its host side; the kernel files only satisfy their launch symbols, and libdrfe.so the adaptor's references to the other entries,
 # which host mode never calls.
 ROOT := $(abspath ../..)
@@ -10,12 +10,12 @@ SRC := $(ROOT)/dr_slam_amd/csrc
 HIPCC ?= /opt/rocm/bin/hipcc
 FLAGS := -O1 -g -std=c++17 -ffp-contract=off --offload-arch=gfx950 -Wall -I$(ROOT)/include -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-omit-frame-pointer
 LDFLAGS := -L$(SRC) -ldrfe -Wl,-rpath,'$$ORIGIN/../../dr_slam_amd/csrc' -Wl,-rpath,/opt/rocm/lib
-HOST := $(SRC)/lmap.cpp $(SRC)/lmap_correct.cpp $(SRC)/lmap_gba.cpp
+HOST := $(SRC)/lmap_store.cpp $(SRC)/lmap.cpp $(SRC)/lmap_conn.cpp $(SRC)/lmap_correct.cpp $(SRC)/lmap_gba.cpp
 KERNELS := $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/correct_kernels.hip $(SRC)/gba_kernels.hip
 
 all: gba_propagate_asan
 
-gba_propagate_asan: gba_propagate_caller.cpp $(HOST) $(KERNELS) $(SRC)/lmap_store.h $(SRC)/gba_core.h $(SRC)/lmap_internal.h $(ROOT)/include/drfe_adaptor.hpp
+gba_propagate_asan: gba_propagate_caller.cpp $(HOST) $(KERNELS) $(SRC)/lmap_store.h $(SRC)/resident_block.h $(SRC)/gba_core.h $(SRC)/lmap_internal.h $(ROOT)/include/drfe_adaptor.hpp
 	$(HIPCC) $(FLAGS) -x hip gba_propagate_caller.cpp $(HOST) $(KERNELS) -o $@ $(LDFLAGS)
 
 clean:

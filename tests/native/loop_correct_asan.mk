@@ -2,7 +2,7 @@
 # UndefinedBehaviorSanitizer, as a program of its own (never loaded into python, never run on a GPU: run it in host mode, where the
 # store has no context).  Not part of build(); run by hand:
 #   make -C tests/native -f loop_correct_asan.mk && tests/native/loop_correct_asan host
-# lmap.cpp and lmap_correct.cpp are compiled into the program with the sanitizers on its host side; the kernel files only satisfy their launch symbols, and
+# lmap_store.cpp, lmap.cpp, lmap_conn.cpp and lmap_correct.cpp are compiled into the program with the sanitizers on its host side; the kernel files only satisfy their launch symbols, and
 # libdrfe.so the adaptor's references to the context entries, which host mode never calls.
 ROOT := $(abspath ../..)
 SRC := $(ROOT)/dr_slam_amd/csrc
@@ -12,8 +12,8 @@ LDFLAGS := -L$(SRC) -ldrfe -Wl,-rpath,'$$ORIGIN/../../dr_slam_amd/csrc' -Wl,-rpa
 
 all: loop_correct_asan
 
-loop_correct_asan: loop_correct_caller.cpp $(SRC)/lmap.cpp $(SRC)/lmap_correct.cpp $(SRC)/lmap_store.h $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/correct_kernels.hip $(SRC)/correct_core.h $(SRC)/lmap_internal.h $(ROOT)/include/drfe_adaptor.hpp
-	$(HIPCC) $(FLAGS) -x hip loop_correct_caller.cpp $(SRC)/lmap.cpp $(SRC)/lmap_correct.cpp $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/correct_kernels.hip -o $@ $(LDFLAGS)
+loop_correct_asan: loop_correct_caller.cpp $(SRC)/lmap_store.cpp $(SRC)/lmap.cpp $(SRC)/lmap_conn.cpp $(SRC)/lmap_correct.cpp $(SRC)/lmap_store.h $(SRC)/resident_block.h $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/correct_kernels.hip $(SRC)/correct_core.h $(SRC)/lmap_internal.h $(ROOT)/include/drfe_adaptor.hpp
+	$(HIPCC) $(FLAGS) -x hip loop_correct_caller.cpp $(SRC)/lmap_store.cpp $(SRC)/lmap.cpp $(SRC)/lmap_conn.cpp $(SRC)/lmap_correct.cpp $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/correct_kernels.hip -o $@ $(LDFLAGS)
 
 clean:
 	rm -f loop_correct_asan

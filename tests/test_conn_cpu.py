@@ -1,4 +1,4 @@
-"""KeyFrame::UpdateConnections on the host (drfe_lmap_connect_host, dr_slam_amd/csrc/lmap.cpp with conn_core.h) against
+"""KeyFrame::UpdateConnections on the host (drfe_lmap_connect_host, dr_slam_amd/csrc/lmap_conn.cpp with conn_core.h) against
 tests/conn_numpy.py and against rows worked out by hand (tests/conn_scenarios.py).  Equal bytes everywhere; no GPU.
 
 Parity with a build of the reference's KeyFrame.cc is not pinned: it includes OpenCV, Eigen and DBoW2 headers that are not

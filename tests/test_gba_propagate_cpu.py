@@ -178,8 +178,8 @@ def test_counters_and_upload_bytes_on_a_host_store():
 
 def test_native_caller_on_the_host_entry():
     """tests/native/gba_propagate_caller.cpp: the adaptor's SyncGlobalBA / PropagateGlobalBA next to :722-783 on stand-in objects"""
-    exe = os.path.join(lib._HERE, "..", "tests", "native", "gba_propagate_caller")
-    assert os.path.exists(exe), "build() makes it"
+    import native_build
+    exe = native_build.caller("gba_propagate_caller")     # built here if the tests directory holds no build products
     p = subprocess.run([exe, "host"], capture_output=True, text=True, timeout=120)
     assert p.returncode == 0, p.stdout + p.stderr
     assert "ok" in p.stdout

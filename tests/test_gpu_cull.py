@@ -14,6 +14,7 @@ import conn_numpy as cn
 import cull_numpy as un
 import cull_scenarios as us
 import lmap_numpy as ln
+from lmap_scenarios import kf as ls_kf
 from dr_slam_amd import lib
 from test_cull_cpu import same_results, same_store
 
@@ -293,6 +294,95 @@ def test_a_call_that_culled_sends_its_pieces_and_not_the_image(ctx):
     ln.same(dev.update([dict(frame_id=6, points=rows[3]["points"])], mode="device"),
             host.update([dict(frame_id=6, points=rows[3]["points"])], mode="host"))
     assert dev.upload_bytes()["rows"] - first["rows"] == sent["rows"]         # and nothing more after that
+
+
+def block_bytes(*sections):
+    """a resident block of (elements, element bytes) sections, each rounded up to 16 bytes"""
+    return sum((n * e + 15) // 16 * 16 for n, e in sections)
+
+
+def test_every_kind_of_edit_reaches_the_device(ctx):
+    """one store through all five entries with every kind of edit in between, next to a host twin: equal results and equal stores
+    after every call, and of the five resident blocks (rows, graph, geometry, attributes, adjustment state) exactly those go up
+    that an edit touched since the last device call that used them - whole, with sizes restated here from the arrays, where the
+    slots moved or the block is rebuilt, and in pieces after set_bad and after the cull"""
+    import gba_propagate_numpy as gn
+    import loop_correct_numpy as rn
+    ops, expect = us.HAND["stereo_and_mono_cross_the_line"]()[:2]
+    rows = {r["handle"]: r for r in ops[0][1]}
+    kfs, pts = sorted(rows), sorted(r["handle"] for r in ops[1][1])
+    E = sum(len(r["points"]) for r in rows.values())
+    n_obs = sum(len(r["obs"]) for r in ops[1][1])
+    dev, host = lib.LocalMap(ctx), lib.LocalMap()
+    pose = lambda h, d=0.0: np.array([[1, 0, 0, 0.1 * h + d], [0, 1, 0, -0.2 * h], [0, 0, 1, 0.05 * h], [0, 0, 0, 1]], np.float32)
+    for s in (dev, host):
+        us.play(ops[:-1], s)
+        s.set_scales([1.0, 1.2, 1.44])
+        s.set_poses(kfs, [pose(h) for h in kfs])
+        s.set_point_geometry([dict(handle=p, world=(0.01 * i, 0.5, 2.0 + 0.1 * i), ref_kf=2, ref_level=i % 3) for i, p in enumerate(pts)])
+        s.set_gba_keyframes([1, 2], [pose(1, 0.5), pose(2, 0.25)], [7, 7])
+        s.set_gba_points(pts[2:5], [(1, 2, 3), (4, 5, 6), (7, 8, 9)], [7, 7, 7])
+    S = np.array([0, 0, 0, 1, 0.5, 0, 0, 1.0])
+    K, P = len(kfs), len(pts)
+    rows_whole = lambda k, obs: block_bytes((k, 1), (P, 1), (0, 1), (k + 1, 4), (E, 4), (k + 1, 4), (0, 4), (P + 1, 4), (obs, 4))
+    geo_whole = lambda k: block_bytes((3, 4), (16 * k, 4), (3 * k, 4), (3 * P, 4), (P, 4), (P, 4), (P, 4), (P, 4))
+    attr_whole = lambda k, obs: block_bytes((k, 4), (k, 1), (E, 4), (E, 4), (E, 1), (P, 4), (obs, 4))
+    gba_whole = lambda k: block_bytes((16 * k, 4), (16 * k, 4), (3 * P, 4), (k, 4), (P, 4), (k, 1))
+
+    def graph_whole(k):
+        g = host.get_connections(sorted(rows))
+        cw, co, ch = (sum(len(x) for x in g[n]) for n in ("weights", "ordered", "children"))
+        return block_bytes((k, 4), (10 * k, 4), (k + 1, 4), (ch, 4), (k, 1), (k + 1, 4), (cw, 4), (cw, 4), (k + 1, 4), (co, 4), (co, 4))
+
+    def stores_agree():
+        cn.same_state(dev, host, sorted(rows))
+        un.same_attributes(dev, host, kfs, pts)
+        rn.same_geometry(dev, host, sorted(rows), pts)
+        gn.same_store(dev, host, sorted(rows), pts)
+
+    def call(what, same, fn, **sent):
+        """fn on both stores; every block not named in `sent` went up by 0 bytes, a named one by that figure (or passes that test)"""
+        before = dev.upload_bytes()
+        r_dev, r_host = fn(dev, "device"), fn(host, "host")
+        same(r_dev, r_host)
+        stores_agree()
+        delta = {k: v - before[k] for k, v in dev.upload_bytes().items()}
+        print(what, delta)
+        for k, v in delta.items():
+            want = sent.get(k, 0)
+            assert want(v) if callable(want) else v == want, (what, k, v, delta)
+        return r_dev
+
+    def edit(fn):
+        fn(dev)
+        fn(host)
+
+    q = lambda i, h: [dict(frame_id=i, points=rows[h]["points"])]
+    call("update", ln.same, lambda s, m: s.update(q(1, 2), mode=m), rows=rows_whole(K, n_obs), graph=graph_whole(K))
+    edit(lambda s: s.set_bad(us.POINT, [pts[7]], [1]))
+    call("update after set_bad", ln.same, lambda s, m: s.update(q(2, 2), mode=m), rows=lambda v: 0 < v < 4 * E)
+    call("connect", cn.same_connect, lambda s, m: s.connect(kfs, mode=m))
+    r = call("cull", un.same_cull, lambda s, m: s.cull([5], mode=m), graph=graph_whole(K), attributes=attr_whole(K, n_obs))
+    assert list(r["culled"]) == [5]
+    obs_left = sum(len(x) for x in r["obs"])
+    assert len(r["points"]) == P and obs_left < n_obs
+    corr = lambda s, m: s.correct(2, S, [1, 2, 3], mode=m)
+    call("correct", rn.same_correct, corr, rows=lambda v: 0 < v <= rows_whole(K, obs_left) - 4 * E, graph=graph_whole(K), geometry=geo_whole(K))
+    call("gba", gn.same_gba, lambda s, m: s.gba(7, [1], mode=m), gba=gba_whole(K))
+    edit(lambda s: s.set_poses([3], [pose(3, 1.0)]))
+    call("correct after set_poses", rn.same_correct, corr, geometry=geo_whole(K))
+    edit(lambda s: s.set_gba_points([pts[9]], [(3, 2, 1)], [8]))
+    call("gba after set_gba_points", gn.same_gba, lambda s, m: s.gba(8, [1], mode=m), gba=gba_whole(K))
+    new = ls_kf(6, 60, parent=1)
+    rows[6] = new
+    edit(lambda s: (s.set_keyframes([new]), s.set_poses([6], [pose(6)])))
+    call("update after set_keyframes", ln.same, lambda s, m: s.update(q(3, 3), mode=m), rows=rows_whole(K + 1, obs_left), graph=graph_whole(K + 1))
+    # the slots moved for every block: each goes up whole at the first call that uses it, and only then
+    call("correct after set_keyframes", rn.same_correct, corr, geometry=geo_whole(K + 1))
+    r = call("cull after set_keyframes", un.same_cull, lambda s, m: s.cull([2], mode=m), attributes=attr_whole(K + 1, obs_left))
+    assert len(r["culled"]) == 0
+    call("gba after set_keyframes", gn.same_gba, lambda s, m: s.gba(9, [1], mode=m), gba=gba_whole(K + 1))
+    call("update at the end", ln.same, lambda s, m: s.update(q(4, 4), mode=m))
 
 
 def test_native_caller_on_the_device_entry():
