@@ -18,8 +18,10 @@ using namespace lmap_store;
 
 namespace {
 
+}  // namespace
+
 /* the attributes by slot, after the image */
-int build_cull(drfe_lmap* db)
+int lmap_build_cull(drfe_lmap* db)
 {
     const int rc = lmap_build_image(db);
     if (rc) return rc;
@@ -75,9 +77,12 @@ int build_cull(drfe_lmap* db)
         }
     A.complete = complete;
     db->cullDirty = false;
+    db->recDirty = true;               /* which points have attributes that fit is part of that image */
     db->blk[drfe_lmap::ATTR].stale_all();
     return DRFE_OK;
 }
+
+namespace {
 
 /* the walk's state over the image I and the attributes A, host or device; row, mpBad, nObs and live are the caller's working arrays */
 CullState cull_state(const LmapImage& I, const CullImage& A, int32_t* row, uint8_t* mpBad, int32_t* nObs, uint8_t* live)
@@ -118,7 +123,7 @@ int cull_plan(drfe_lmap* db, int32_t n, const int32_t* handles, int32_t monocula
 {
     if (n < 0 || (n > 0 && !handles)) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_cull: invalid argument");
     if (n > DRFE_LMAP_MAX_QUERIES) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_cull: more than DRFE_LMAP_MAX_QUERIES key frames in a call");
-    const int rc = build_cull(db);
+    const int rc = lmap_build_cull(db);
     if (rc) return rc;
     const Image& G = db->img;
     C.n = n;

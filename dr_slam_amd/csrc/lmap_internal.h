@@ -1,5 +1,5 @@
-/* lmap_internal.h — what lmap.cpp, lmap_conn.cpp, lmap_correct.cpp, lmap_cull.cpp and lmap_gba.cpp hand to the store's kernels (DESIGN.md sections
- * 25 to 29). */
+/* lmap_internal.h — what lmap.cpp, lmap_conn.cpp, lmap_correct.cpp, lmap_cull.cpp, lmap_gba.cpp and lmap_recent.cpp hand to the store's
+ * kernels (DESIGN.md sections 25 to 29 and 31). */
 #ifndef DRFE_LMAP_INTERNAL_H
 #define DRFE_LMAP_INTERNAL_H
 
@@ -9,6 +9,7 @@
 #include "correct_core.h"
 #include "cull_core.h"
 #include "gba_core.h"
+#include "recent_core.h"
 
 /* threads of a workgroup: frame points and key-frame slots go across them in the vote, the entries of a match row in the gather */
 #define LMAP_THREADS 256
@@ -216,6 +217,65 @@ struct CullLaunch {
 };
 /* the records of the chunk, then its walk */
 hipError_t drfe_launch_cull_chunk(const CullLaunch& L, hipStream_t s);
+
+/* ---- LocalMapping::MapPointCulling and MapLineCulling (recent_kernels.hip) ---- */
+/* list entries of one workgroup of the entry launches, a lane each */
+#define RECENT_TILE LMAP_THREADS
+/* erased observations of one pass of an erase workgroup, a lane each, and the most workgroups of that launch */
+#define RECENT_ERASE_TILE LMAP_THREADS
+#define RECENT_ERASE_GROUPS 1024
+/* bytes of scratch per list entry of a chunk: its observation count and its share of the workgroup totals */
+#define RECENT_ENTRY_BYTES 8
+/* bytes of scratch every chunk shares besides the claim words: alignment of the sections */
+#define RECENT_FIXED_BYTES 1024
+
+/* the recent-list attributes of the image, resident in a block of their own, and the line observations */
+struct RecentImage {
+    const int32_t* found[2];       /* nP, nL: mnFound */
+    const int32_t* visible[2];     /* mnVisible */
+    const int64_t* first[2];       /* mnFirstKFid */
+    const int32_t* mlNObs;         /* nL: nObs as MapLine holds it */
+    const int32_t* mlObsOff;       /* nL + 1 */
+    const int32_t* mlObs;          /* key-frame slots */
+    const int32_t* mlObsIdx;       /* parallel: mit->second */
+};
+
+/* running totals of a call, on the device across its chunks; the _BASE words are what stood there before the chunk at hand */
+enum { RECENT_HEAD_KEPT_P = 0, RECENT_HEAD_KEPT_L, RECENT_HEAD_CULLED, RECENT_HEAD_ERASED,
+       RECENT_HEAD_BASE, RECENT_HEAD_WORDS = 2 * RECENT_HEAD_BASE };
+/* totals of one workgroup of a chunk, then their exclusive prefix over the chunk's workgroups on top of the bases */
+struct RecentGroup {
+    int32_t v[RECENT_HEAD_BASE];
+};
+
+/* One chunk of a call: entries [e0, e1) of the flat entry space, the nPts entries of the point list first, then the line list. */
+struct RecentLaunch {
+    LmapImage I;                   /* resident; the bad flags and the two kinds of match rows are written */
+    CullImage A;                   /* resident: nObs and obsIdx of the points */
+    RecentImage R;                 /* resident */
+    int64_t current;               /* mpCurrentKeyFrame->mnId */
+    int32_t monocular;
+    int32_t nPts, n;               /* entries of the point list, of both lists */
+    int32_t e0, e1;
+    /* staged */
+    const int32_t* item;           /* n slots */
+    const int32_t* handle;         /* n handles, for the surviving lists */
+    /* scratch */
+    int32_t* claim[2];             /* nP, nL: LMAP_NO_CLAIM bytes before the first chunk */
+    int32_t* cnt;                  /* per entry of the chunk: the observations its verdict erases */
+    RecentGroup* group;            /* per workgroup of the chunk */
+    /* out */
+    uint8_t* action;               /* n */
+    int32_t* kept[2];              /* the surviving lists as handles */
+    int32_t* culledEntry;          /* n: the entries that carry a verdict, in list order */
+    int32_t* erOff;                /* n + 1: exclusive prefix of their observation counts */
+    int32_t* erKf;                 /* erased observations: key-frame slot */
+    int32_t* erIdx;                /* and index */
+    int32_t* head;                 /* RECENT_HEAD_WORDS, zero before the first chunk */
+};
+/* the claims, the verdicts, their prefix, the packed outputs with the bad flags, the erasure: in stream order.  eraseBound is the
+ * host's bound on the observations the chunk erases. */
+hipError_t drfe_launch_recent_chunk(const RecentLaunch& L, int64_t eraseBound, hipStream_t s);
 
 /* ---- the map update of LoopClosing::RunGlobalBundleAdjustment (gba_kernels.hip) ---- */
 /* point slots of one workgroup of the point launches, a lane each */

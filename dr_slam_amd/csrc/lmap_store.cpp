@@ -1,5 +1,5 @@
 /* lmap_store.cpp — the local-map store behind the C-ABI of include/drfe.h (lmap_store.h): its lifecycle, the setters of its rows,
- * the flat image of them, the bindings of the five resident blocks and the one function that brings them up to date on the device.
+ * the flat image of them, the bindings of the six resident blocks and the one function that brings them up to date on the device.
  * DESIGN.md section 25, "The resident blocks". */
 #include "lmap_store.h"
 
@@ -32,6 +32,17 @@ static bool handles_ok(const int32_t* h, int n)
 /* the flat image of the rows; DRFE_ERR_STATE and the name of the reference when one dangles */
 int lmap_build_image(drfe_lmap* db)
 {
+    /* the observations of the stored map lines are looked at like those of the points, after an edit of
+     * either side; they are not part of this image, so an edit of them does not rebuild it */
+    if (db->imgDirty || db->recCheck) {
+        for (const auto& e : db->mlObs) {
+            if (db->ml.find(e.first) == db->ml.end()) continue;
+            for (const int32_t o : e.second.obs)
+                if (db->kf.find(o) == db->kf.end())
+                    return lmap_fail(db, DRFE_ERR_STATE, "lmap: an observation of map line " + std::to_string(e.first) + " names unknown handle " + std::to_string(o));
+        }
+        db->recCheck = false;
+    }
     if (!db->imgDirty) return DRFE_OK;
     Image G;
     std::vector<std::pair<uint64_t, int32_t>> order;
@@ -156,6 +167,7 @@ int lmap_build_image(drfe_lmap* db)
     db->geoDirty = true;               /* the slots may have moved: everything by slot is built and sent again */
     db->cullDirty = true;
     db->gbaDirty = true;
+    db->recDirty = true;
     for (ResidentBlock& B : db->blk) B.stale_all();
     return DRFE_OK;
 }
@@ -174,7 +186,7 @@ static void bind_blocks(drfe_lmap* db)
     R.bind(G.kfMpOff, &D.kfMpOff, &H.kfMpOff);
     db->secKfMp = R.bind(G.kfMp, &D.kfMp, &H.kfMp);
     R.bind(G.kfMlOff, &D.kfMlOff, &H.kfMlOff);
-    R.bind(G.kfMl, &D.kfMl, &H.kfMl);
+    db->secKfMl = R.bind(G.kfMl, &D.kfMl, &H.kfMl);
     db->secObsOff = R.bind(G.obsOff, &D.obsOff, &H.obsOff);
     R.bind(G.obs, &D.obs, &H.obs);
     ResidentBlock& Gr = db->blk[drfe_lmap::GRAPH];
@@ -207,7 +219,7 @@ static void bind_blocks(drfe_lmap* db)
     At.bind(A.depth, &db->dCull.depth, &db->hCull.depth);
     At.bind(A.stereo, &db->dCull.stereo, &db->hCull.stereo);
     db->secNObs = At.bind(A.nObs, &db->dCull.nObs, &db->hCull.nObs);
-    At.bind(A.obsIdx, &db->dCull.obsIdx, &db->hCull.obsIdx);
+    db->secObsIdx = At.bind(A.obsIdx, &db->dCull.obsIdx, &db->hCull.obsIdx);
     GbaAttr& B = db->gba;
     ResidentBlock& Gb = db->blk[drfe_lmap::GBA];
     Gb.bind(B.kfTcwGBA, &db->dGba.kfTcwGBA);
@@ -216,6 +228,19 @@ static void bind_blocks(drfe_lmap* db)
     Gb.bind(B.kfStamp, &db->dGba.kfStamp);
     Gb.bind(B.mpStamp, &db->dGba.mpStamp);
     Gb.bind(B.kfHasBef, &db->dGba.kfHasBef);
+    /* the counters that Tracking raises every frame in front, the line observations at the end */
+    RecentAttr& Q = db->rec;
+    ResidentBlock& Rc = db->blk[drfe_lmap::RECENT];
+    Rc.bind(Q.mpFound, &db->dRec.found[0], &db->hRec.found[0]);
+    Rc.bind(Q.mpVisible, &db->dRec.visible[0], &db->hRec.visible[0]);
+    Rc.bind(Q.mlFound, &db->dRec.found[1], &db->hRec.found[1]);
+    db->secRecCounters = Rc.bind(Q.mlVisible, &db->dRec.visible[1], &db->hRec.visible[1]);
+    Rc.bind(Q.mpFirst, &db->dRec.first[0], &db->hRec.first[0]);
+    Rc.bind(Q.mlFirst, &db->dRec.first[1], &db->hRec.first[1]);
+    Rc.bind(Q.mlNObs, &db->dRec.mlNObs, &db->hRec.mlNObs);
+    db->secRecObsOff = Rc.bind(Q.mlObsOff, &db->dRec.mlObsOff, &db->hRec.mlObsOff);
+    Rc.bind(Q.mlObs, &db->dRec.mlObs, &db->hRec.mlObs);
+    Rc.bind(Q.mlObsIdx, &db->dRec.mlObsIdx, &db->hRec.mlObsIdx);
 }
 
 void lmap_host_views(drfe_lmap* db)
@@ -232,7 +257,7 @@ void lmap_host_views(drfe_lmap* db)
 int lmap_upload(drfe_lmap* db, unsigned need, hipStream_t st)
 {
     lmap_host_views(db);
-    size_t staged = 0, all = 0, sent[drfe_lmap::BLOCKS] = {0, 0, 0, 0, 0};
+    size_t staged = 0, all = 0, sent[drfe_lmap::BLOCKS] = {0, 0, 0, 0, 0, 0};
     for (int b = 0; b < drfe_lmap::BLOCKS; b++) {
         if (!(need >> b & 1)) continue;
         /* a block that no longer fits is allocated at twice the size */
@@ -440,9 +465,14 @@ int drfe_lmap_remove(drfe_lmap* db, int kind, int32_t handle)
             db->mpGeo.erase(handle);
             db->mpCull.erase(handle);
             db->mpGba.erase(handle);
+            db->mpRec.erase(handle);
         }
     } else if (kind == DRFE_LMAP_LINE) {
         gone = db->ml.erase(handle);
+        if (gone) {
+            db->mlRec.erase(handle);
+            db->mlObs.erase(handle);
+        }
     } else {
         return lmap_fail(db, DRFE_ERR_INVALID, "lmap_remove: unknown kind");
     }
@@ -465,7 +495,7 @@ int drfe_lmap_upload_bytes(drfe_lmap* db, int64_t* out5)
 {
     if (!db || !out5) return DRFE_ERR_INVALID;
     std::lock_guard<std::mutex> lock(db->mu);
-    std::memcpy(out5, db->sentBytes, sizeof(db->sentBytes));
+    std::memcpy(out5, db->sentBytes, 5 * sizeof(int64_t));
     return DRFE_OK;
 }
 

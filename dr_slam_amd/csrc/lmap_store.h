@@ -1,9 +1,10 @@
 /* lmap_store.h — the local-map store itself: its rows by handle, the flat image of them, the optional geometry, culling attributes
- * and adjustment state by slot, and the five resident blocks that keep them on the device (resident_block.h).  lmap_store.cpp holds
+ * and adjustment state by slot, and the six resident blocks that keep them on the device (resident_block.h).  lmap_store.cpp holds
  * its lifecycle, setters, image and upload; its entries are in lmap.cpp (Tracking::UpdateLocalMap),
  * lmap_conn.cpp (KeyFrame::UpdateConnections, section 26), lmap_correct.cpp (the Sim3 propagation of LoopClosing::CorrectLoop,
- * section 27), lmap_cull.cpp (LocalMapping::KeyFrameCulling with KeyFrame::SetBadFlag, section 28) and lmap_gba.cpp (the map update
- * of LoopClosing::RunGlobalBundleAdjustment, section 29). */
+ * section 27), lmap_cull.cpp (LocalMapping::KeyFrameCulling with KeyFrame::SetBadFlag, section 28), lmap_gba.cpp (the map update
+ * of LoopClosing::RunGlobalBundleAdjustment, section 29) and lmap_recent.cpp (LocalMapping::MapPointCulling and MapLineCulling,
+ * section 31). */
 #ifndef DRFE_LMAP_STORE_H
 #define DRFE_LMAP_STORE_H
 
@@ -96,6 +97,26 @@ struct GbaAttr {
     std::vector<uint8_t> kfHasT, kfHasBef, mpHasPos;
 };
 
+/* what MapPointCulling and MapLineCulling read of an item (mnFound, mnVisible, mnFirstKFid), and what a map line has to hold
+ * besides: nObs as MapLine holds it, its observing key frames in the caller's order and mit->second parallel to them */
+struct ItemRecent {
+    int32_t found = 0, visible = 0;
+    int64_t first = 0;
+};
+
+struct MlObs {
+    int32_t nObs = 0;
+    std::vector<int32_t> obs, obsIdx;
+};
+
+/* those by slot, next to the image; has = the item has them (a point: with culling attributes that fit its observations) */
+struct RecentAttr {
+    std::vector<uint8_t> mpHas, mlHas;
+    std::vector<int32_t> mpFound, mpVisible, mlFound, mlVisible, mlNObs, mlObsOff, mlObs, mlObsIdx;
+    std::vector<int64_t> mpFirst, mlFirst;
+    bool complete = false;             /* every stored point and line has them and every index is inside its observer's row */
+};
+
 /* the graph with every handle resolved to a slot: what the host walk and the kernels read */
 struct Image {
     std::vector<int32_t> kfHandle, mpHandle, mlHandle;   /* by slot */
@@ -138,7 +159,7 @@ struct drfe_lmap {
     std::unordered_map<int32_t, lmap_store::MpCull> mpCull;
     lmap_store::CullAttr cull;
     bool cullDirty = true;             /* the attribute image lacks an edit of the rows or of the attributes */
-    int64_t sentBytes[5] = {0, 0, 0, 0, 0};   /* host-to-device bytes of the rows, graph, geometry, attribute and adjustment blocks */
+    int64_t sentBytes[6] = {0, 0, 0, 0, 0, 0};   /* host-to-device bytes of the rows, graph, geometry, attribute, adjustment and recent-list blocks */
     int64_t cullStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     /* the optional state of the map update after a global bundle adjustment, by handle, and by slot */
     std::unordered_map<int32_t, lmap_store::KfGba> kfGba;
@@ -146,12 +167,19 @@ struct drfe_lmap {
     lmap_store::GbaAttr gba;
     bool gbaDirty = true;              /* the state by slot lacks an edit of the rows or of the state */
     int64_t gbaStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    /* the optional attributes of MapPointCulling and MapLineCulling, by handle, and their image by slot */
+    std::unordered_map<int32_t, lmap_store::ItemRecent> mpRec, mlRec;
+    std::unordered_map<int32_t, lmap_store::MlObs> mlObs;
+    lmap_store::RecentAttr rec;
+    bool recDirty = true;              /* that image lacks an edit of the rows, of the culling attributes or of these */
+    bool recCheck = false;             /* the line observations changed since the image looked for dangling ones */
+    int64_t recStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     /* the host walk's stamps, kept between calls: an item is stamped for the query whose serial it holds */
     std::vector<int32_t> stampP, stampL, inP, inL;
     int32_t serial = 0;
     /* the resident blocks, in upload order, with their device memory; the views of them the kernels take (d...) and the host walks
      * (h...); the sections that edits mark by name (lmap_store.cpp binds them) */
-    enum { ROWS, GRAPH, GEO, ATTR, GBA, BLOCKS };
+    enum { ROWS, GRAPH, GEO, ATTR, GBA, RECENT, BLOCKS };
     ResidentBlock blk[BLOCKS];
     DevBuf<char> dev[BLOCKS];
     LmapImage dView = {}, hView = {};
@@ -159,7 +187,8 @@ struct drfe_lmap {
     CorrImage dCorr = {}, hCorr = {};
     CullImage dCull = {}, hCull = {};
     GbaImage dGba = {};
-    int secMlBad = 0, secKfMp = 0, secObsOff = 0, secNObs = 0;
+    RecentImage dRec = {}, hRec = {};
+    int secMlBad = 0, secKfMp = 0, secKfMl = 0, secObsOff = 0, secNObs = 0, secObsIdx = 0, secRecCounters = 0, secRecObsOff = 0;
     StagePair io;
     DevBuf<char> scratch;
     PinnedBuf<char> hup, hlist;
@@ -173,10 +202,12 @@ int lmap_build_image(drfe_lmap* db);
 void lmap_host_views(drfe_lmap* db);
 /* the blocks of `need` (bit b = block b; a later block implies the rows and the graph) brought up to date in block order: the stale
  * runs staged back to back, one synchronisation.  A call's build_* runs before it. */
-enum { LMAP_NEED_IMAGE = 3, LMAP_NEED_GEO = 3 | 4, LMAP_NEED_ATTR = 3 | 8, LMAP_NEED_GBA = 3 | 4 | 16 };
+enum { LMAP_NEED_IMAGE = 3, LMAP_NEED_GEO = 3 | 4, LMAP_NEED_ATTR = 3 | 8, LMAP_NEED_GBA = 3 | 4 | 16, LMAP_NEED_RECENT = 3 | 8 | 32 };
 int lmap_upload(drfe_lmap* db, unsigned need, hipStream_t st);
 bool lmap_offsets_ok(const int32_t* off, int n);
 /* lmap_correct.cpp's, for lmap_gba.cpp: the geometry by slot, rebuilt when stale */
 int lmap_build_geo(drfe_lmap* db);
+/* lmap_cull.cpp's, for lmap_recent.cpp: the culling attributes by slot, rebuilt when stale */
+int lmap_build_cull(drfe_lmap* db);
 
 #endif

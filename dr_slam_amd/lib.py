@@ -81,6 +81,9 @@ SYMBOLS = (
     "drfe_lmap_set_gba_keyframes", "drfe_lmap_set_gba_points", "drfe_lmap_get_gba_keyframes", "drfe_lmap_get_gba_points",
     "drfe_lmap_gba_host", "drfe_lmap_gba_device", "drfe_lmap_gba_batch", "drfe_lmap_gba_limits", "drfe_lmap_gba_scratch",
     "drfe_lmap_gba_stats",
+    "drfe_lmap_set_recent_attributes", "drfe_lmap_get_recent_attributes", "drfe_lmap_recent_increase", "drfe_lmap_recent_cull_host",
+    "drfe_lmap_recent_cull_device", "drfe_lmap_recent_cull_batch", "drfe_lmap_recent_cull_limits", "drfe_lmap_recent_cull_scratch",
+    "drfe_lmap_recent_cull_stats", "drfe_lmap_recent_upload_bytes",
 )
 
 FAST_CELL_DTYPE = np.dtype([(n, "<i4") for n in ("level", "x0", "y0", "ww", "wh", "offX", "offY", "cellIdx", "ncp", "rpl", "nrb",
@@ -383,6 +386,28 @@ class LmapCullOut(C.Structure):
         "record", "Tcp", "has_Tcp", "n_culled", "culled", "n_touched", "touched")] + [("rows", LmapConnRows)] + [
         (k, C.c_void_p) for k in ("flags", "children_offsets", "children", "nulled_offsets", "nulled", "n_points", "points",
                                   "point_n_obs", "point_ref", "point_bad", "obs_offsets", "obs", "obs_index")]   # drfe_lmap_cull_out
+
+
+LMAP_RECENT_STATS = ("calls", "entries", "device_calls", "culled_ratio", "culled_observations", "aged_out", "dropped_bad", "nulled")
+LMAP_RECENT_LIMITS = ("entry_tile", "erase_tile", "entry_bytes", "wavefront", "max_entries", "device_from")
+RECENT_KEPT, RECENT_WAS_BAD, RECENT_RATIO, RECENT_OBSERVATIONS, RECENT_AGED = range(5)   # drfe_lmap_recent_list.action
+LMAP_RECENT_ATTR_FIELDS = ("point_handle", "point_found", "point_visible", "point_first_kf", "line_handle", "line_found",
+                           "line_visible", "line_first_kf", "line_n_obs", "line_obs_offsets", "line_obs", "line_obs_index")
+
+
+class LmapRecentAttributes(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("n_lines", C.c_int32)] + [
+        (k, C.c_void_p) for k in LMAP_RECENT_ATTR_FIELDS]                            # drfe_lmap_recent_attributes
+
+
+class LmapRecentAttributesOut(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("n_lines", C.c_int32), ("line_obs_capacity", C.c_int32)] + [
+        (k, C.c_void_p) for k in LMAP_RECENT_ATTR_FIELDS]                            # drfe_lmap_recent_attributes_out
+
+
+class LmapRecentList(C.Structure):
+    _fields_ = [("n", C.c_int32), ("handles", C.c_void_p), ("erased_capacity", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "action", "n_kept", "kept", "n_culled", "culled", "erased_offsets", "erased_kf", "erased_index")]   # drfe_lmap_recent_list
 
 
 class InitProblems(C.Structure):
@@ -694,6 +719,16 @@ def load() -> C.CDLL:
     L.drfe_lmap_gba_limits.argtypes = [vp]
     L.drfe_lmap_gba_scratch.argtypes = [vp, vp]
     L.drfe_lmap_gba_stats.argtypes = [vp, vp]
+    L.drfe_lmap_set_recent_attributes.argtypes = [vp, vp]
+    L.drfe_lmap_get_recent_attributes.argtypes = [vp, vp]
+    L.drfe_lmap_recent_increase.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.drfe_lmap_recent_cull_host.argtypes = [vp, C.c_int64, i32, vp, vp]
+    L.drfe_lmap_recent_cull_device.argtypes = [vp, C.c_int64, i32, vp, vp, vp]
+    L.drfe_lmap_recent_cull_batch.argtypes = [vp, C.c_int64, i32, vp, vp, vp]
+    L.drfe_lmap_recent_cull_limits.argtypes = [vp]
+    L.drfe_lmap_recent_cull_scratch.argtypes = [vp, C.c_int64, vp]
+    L.drfe_lmap_recent_cull_stats.argtypes = [vp, vp]
+    L.drfe_lmap_recent_upload_bytes.argtypes = [vp, vp]
     L.drfe_pnp_stats.argtypes = [vp, vp]
     L.drfe_lines_is_good_batch.argtypes = [vp, vp, vp, vp]
     L.drfe_line3d_chunk_frames.argtypes = [i32]
@@ -2192,6 +2227,125 @@ class LocalMap:
         out = np.zeros(5, np.int64)
         self._chk(self.L.drfe_lmap_upload_bytes(self.h, _p(out)), "drfe_lmap_upload_bytes")
         return dict(zip(("rows", "graph", "geometry", "attributes", "gba"), (int(v) for v in out)))
+
+    # ---- LocalMapping::MapPointCulling and MapLineCulling on the store ----
+
+    @staticmethod
+    def recent_cull_limits():
+        out = np.zeros(6, np.int32)
+        rc = load().drfe_lmap_recent_cull_limits(_p(out))
+        if rc != 0:
+            raise DrfeError(f"drfe_lmap_recent_cull_limits failed ({rc})")
+        return dict(zip(LMAP_RECENT_LIMITS, (int(v) for v in out)))
+
+    def recent_cull_stats(self):
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_lmap_recent_cull_stats(self.h, _p(st)), "drfe_lmap_recent_cull_stats")
+        return dict(zip(LMAP_RECENT_STATS, (int(v) for v in st)))
+
+    def recent_upload_bytes(self):
+        """host-to-device bytes of the recent-list block since the store was made"""
+        out = np.zeros(1, np.int64)
+        self._chk(self.L.drfe_lmap_recent_upload_bytes(self.h, _p(out)), "drfe_lmap_recent_upload_bytes")
+        return int(out[0])
+
+    def recent_cull_scratch(self, n_entries):
+        """bytes of device scratch a recent_cull call of n_entries takes: (as one chunk, at least, shared by every chunk)"""
+        out = np.zeros(3, np.int64)
+        self._chk(self.L.drfe_lmap_recent_cull_scratch(self.h, int(n_entries), _p(out)), "drfe_lmap_recent_cull_scratch")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def set_recent_attributes(self, points=(), lines=()):
+        """points: dicts with handle, found, visible, first_kf.  lines: the same plus n_obs, obs (key-frame handles in the
+        caller's order) and obs_index parallel to them."""
+        ph = np.array([r["handle"] for r in points], np.int32)
+        pf = np.array([r["found"] for r in points], np.int32)
+        pv = np.array([r["visible"] for r in points], np.int32)
+        p1 = np.array([r["first_kf"] for r in points], np.int64)
+        lh = np.array([r["handle"] for r in lines], np.int32)
+        lf = np.array([r["found"] for r in lines], np.int32)
+        lv = np.array([r["visible"] for r in lines], np.int32)
+        l1 = np.array([r["first_kf"] for r in lines], np.int64)
+        ln = np.array([r["n_obs"] for r in lines], np.int32)
+        ooff, obs = _csr_i32([r.get("obs", ()) for r in lines])
+        ioff, idx = _csr_i32([r.get("obs_index", ()) for r in lines])
+        if not np.array_equal(ooff, ioff):
+            raise ValueError("obs and obs_index of a line must have one length")
+        A = LmapRecentAttributes(len(ph), len(lh), _p(ph), _p(pf), _p(pv), _p(p1), _p(lh), _p(lf), _p(lv), _p(l1), _p(ln), _p(ooff),
+                                 _p(obs), _p(idx))
+        self._chk(self.L.drfe_lmap_set_recent_attributes(self.h, C.byref(A)), "drfe_lmap_set_recent_attributes")
+
+    def get_recent_attributes(self, point_handles=(), line_handles=()):
+        """the stored state: dict of points (dicts with handle, found, visible, first_kf) and lines (the same plus n_obs, obs,
+        obs_index)"""
+        ph = np.ascontiguousarray(point_handles, np.int32)
+        lh = np.ascontiguousarray(line_handles, np.int32)
+        npt, nl = len(ph), len(lh)
+        cap = 1 << 12
+        while True:
+            r = {"pf": np.zeros(max(1, npt), np.int32), "pv": np.zeros(max(1, npt), np.int32), "p1": np.zeros(max(1, npt), np.int64),
+                 "lf": np.zeros(max(1, nl), np.int32), "lv": np.zeros(max(1, nl), np.int32), "l1": np.zeros(max(1, nl), np.int64),
+                 "ln": np.zeros(max(1, nl), np.int32), "off": np.zeros(nl + 1, np.int32), "obs": np.zeros(cap, np.int32),
+                 "idx": np.zeros(cap, np.int32)}
+            O = LmapRecentAttributesOut(npt, nl, cap, _p(ph), _p(r["pf"]), _p(r["pv"]), _p(r["p1"]), _p(lh), _p(r["lf"]), _p(r["lv"]),
+                                        _p(r["l1"]), _p(r["ln"]), _p(r["off"]), _p(r["obs"]), _p(r["idx"]))
+            rc = self.L.drfe_lmap_get_recent_attributes(self.h, C.byref(O))
+            if rc != ERR_CAPACITY or cap >= (1 << 28):
+                break
+            cap *= 8
+        self._chk(rc, "drfe_lmap_get_recent_attributes")
+        o = r["off"]
+        return {"points": [{"handle": int(ph[i]), "found": int(r["pf"][i]), "visible": int(r["pv"][i]), "first_kf": int(r["p1"][i])}
+                           for i in range(npt)],
+                "lines": [{"handle": int(lh[i]), "found": int(r["lf"][i]), "visible": int(r["lv"][i]), "first_kf": int(r["l1"][i]),
+                           "n_obs": int(r["ln"][i]), "obs": r["obs"][o[i]:o[i + 1]].copy(),
+                           "obs_index": r["idx"][o[i]:o[i + 1]].copy()} for i in range(nl)]}
+
+    def recent_increase(self, kind, handles, d_found, d_visible):
+        """IncreaseFound / IncreaseVisible of the named points (LMAP_POINT) or lines (LMAP_LINE) by the two deltas each"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        df = np.ascontiguousarray(d_found, np.int32)
+        dv = np.ascontiguousarray(d_visible, np.int32)
+        assert hs.shape == df.shape == dv.shape
+        self._chk(self.L.drfe_lmap_recent_increase(self.h, int(kind), len(hs), _p(hs), _p(df), _p(dv)), "drfe_lmap_recent_increase")
+
+    def recent_cull(self, current_kf_id, points=(), lines=(), monocular=False, mode="batch", capacity=None):
+        """MapPointCulling over `points` and MapLineCulling over `lines` (mlpRecentAddedMapPoints / mlpRecentAddedMapLines as
+        handles, in list order) for mpCurrentKeyFrame->mnId = current_kf_id.  Returns a dict with "points" and "lines", each a
+        dict: action [n], kept (the surviving list), culled (handles in list order), erased (per culled item an [m, 2] array of
+        (key frame, index) in stored order).  capacity: (point observations, line observations) that may be erased; default:
+        grown until the call fits (a call that does not fit changes nothing)."""
+        fn = getattr(self.L, f"drfe_lmap_recent_cull_{mode}")
+        hs = [np.ascontiguousarray(points, np.int32), np.ascontiguousarray(lines, np.int32)]
+        grow = capacity is None
+        caps = [1 << 12, 1 << 12] if grow else [int(c) for c in capacity]
+        while True:
+            arrs, lists = [], []
+            for k in range(2):
+                n = len(hs[k])
+                a = {"action": np.zeros(max(1, n), np.uint8), "n_kept": np.zeros(1, np.int32), "kept": np.zeros(max(1, n), np.int32),
+                     "n_culled": np.zeros(1, np.int32), "culled": np.zeros(max(1, n), np.int32),
+                     "erased_offsets": np.zeros(n + 1, np.int32), "erased_kf": np.zeros(max(1, caps[k]), np.int32),
+                     "erased_index": np.zeros(max(1, caps[k]), np.int32)}
+                arrs.append(a)
+                lists.append(LmapRecentList(n, _p(hs[k]), caps[k], *[_p(a[f]) for f in (
+                    "action", "n_kept", "kept", "n_culled", "culled", "erased_offsets", "erased_kf", "erased_index")]))
+            args = (self.h, int(current_kf_id), 1 if monocular else 0, C.byref(lists[0]), C.byref(lists[1])) + (
+                () if mode == "host" else (None,))
+            rc = fn(*args)
+            if not (grow and rc == ERR_CAPACITY and caps[0] < (1 << 28)
+                    and b"than erased_capacity" in self.L.drfe_lmap_last_error(self.h)):
+                break
+            caps = [v * 8 for v in caps]
+        self._chk(rc, f"drfe_lmap_recent_cull_{mode}")
+        res = {}
+        for k, name in enumerate(("points", "lines")):
+            a, n = arrs[k], len(hs[k])
+            nk, nc, o = int(a["n_kept"][0]), int(a["n_culled"][0]), a["erased_offsets"]
+            res[name] = dict(action=a["action"][:n].copy(), kept=a["kept"][:nk].copy(), culled=a["culled"][:nc].copy(),
+                             erased=[np.stack([a["erased_kf"][o[i]:o[i + 1]], a["erased_index"][o[i]:o[i + 1]]], axis=1)
+                                     for i in range(nc)])
+        return res
 
     # ---- the map update of LoopClosing::RunGlobalBundleAdjustment on the store (DESIGN.md section 29) ----
 

@@ -2161,6 +2161,121 @@ int drfe_lmap_gba_scratch(drfe_lmap* db, int64_t* out3);
  * key frame without the stamp. */
 int drfe_lmap_gba_stats(drfe_lmap* db, int64_t* stats /* 8 */);
 
+/* LocalMapping::MapPointCulling and MapLineCulling (src/LocalMapping.cc:175-231) on the same store: the two walks over
+ * mlpRecentAddedMapPoints and mlpRecentAddedMapLines that run for every new key frame, with MapPoint::SetBadFlag and
+ * MapLine::SetBadFlag.  DESIGN.md section 31.  Parity with a build of the reference's LocalMapping.cc is not pinned.
+ *
+ * The state they read is optional; a store that is never given it behaves as before.  Per map point mnFound, mnVisible and
+ * mnFirstKFid (nObs and mit->second are the culling attributes above).  Per map line the same three, nObs as MapLine holds it
+ * (AddObservation adds 1), the observing key frames in the caller's pointer order and mit->second parallel to them (a key frame
+ * twice in a row, a negative handle: DRFE_ERR_INVALID).  The last row of a handle wins and replaces the stored one, a row may name
+ * a handle that is not stored yet, drfe_lmap_remove drops the state with the item.  An observation of a stored line that names an
+ * unknown key frame refuses every call that reads the image, like one of a point (DRFE_ERR_STATE).  The state lies in a device
+ * block of its own: an edit of it sends neither the rows, the graph nor the culling attributes again. */
+typedef struct drfe_lmap_recent_attributes {
+    int32_t n_points, n_lines;
+    const int32_t* point_handle;
+    const int32_t* point_found;
+    const int32_t* point_visible;
+    const int64_t* point_first_kf;
+    const int32_t* line_handle;
+    const int32_t* line_found;
+    const int32_t* line_visible;
+    const int64_t* line_first_kf;
+    const int32_t* line_n_obs;
+    const int32_t* line_obs_offsets;  /* n_lines + 1 */
+    const int32_t* line_obs;          /* key-frame handles */
+    const int32_t* line_obs_index;    /* parallel */
+} drfe_lmap_recent_attributes;
+int drfe_lmap_set_recent_attributes(drfe_lmap* db, const drfe_lmap_recent_attributes* rows);
+/* the stored state of the named handles (one without it: DRFE_ERR_INVALID; line_obs_capacity too small: DRFE_ERR_CAPACITY) */
+typedef struct drfe_lmap_recent_attributes_out {
+    int32_t n_points, n_lines, line_obs_capacity;
+    const int32_t* point_handle;
+    int32_t* point_found;
+    int32_t* point_visible;
+    int64_t* point_first_kf;
+    const int32_t* line_handle;
+    int32_t* line_found;
+    int32_t* line_visible;
+    int64_t* line_first_kf;
+    int32_t* line_n_obs;
+    int32_t* line_obs_offsets;
+    int32_t* line_obs;
+    int32_t* line_obs_index;
+} drfe_lmap_recent_attributes_out;
+int drfe_lmap_get_recent_attributes(drfe_lmap* db, drfe_lmap_recent_attributes_out* out);
+/* MapPoint::IncreaseFound / IncreaseVisible (kind DRFE_LMAP_POINT) and MapLine's (DRFE_LMAP_LINE): d_found[i] and d_visible[i] are
+ * added to handle i, with wrap-around; a handle may be named more than once.  A handle without the state: DRFE_ERR_INVALID, and
+ * nothing changes.  Only the four counter arrays of the block travel afterwards. */
+int drfe_lmap_recent_increase(drfe_lmap* db, int kind, int32_t count, const int32_t* handles, const int32_t* d_found, const int32_t* d_visible);
+
+/* A call names current_kf_id (mpCurrentKeyFrame->mnId, a value), monocular, and the two recent lists as handles in list order
+ * (each at most DRFE_LMAP_RECENT_MAX_ENTRIES; either may be empty; a handle may stand in a list more than once, as
+ * ProcessNewKeyFrame pushes once per row index).
+ *
+ * Kept from the reference.  Each entry in order: an item that is bad is dropped (action 1).  A point with
+ * static_cast<float>(mnFound) / mnVisible < 0.25f - both converted to float, one correctly rounded division; mnVisible == 0 gives
+ * inf or NaN and NaN is not less - or a line with static_cast<float>(mnFound / mnVisible) < 0.25f - the integer division, so
+ * every line with 0 <= found < visible - gets SetBadFlag and is dropped (action 2).  Otherwise, with d = (int)current_kf_id -
+ * (int)mnFirstKFid (both truncated to int, the difference in 64 bits): d >= 2 && Observations() <= (monocular ? 2 : 3) on the
+ * stored counter gets SetBadFlag and is dropped (action 3); d >= 3 is dropped (action 4); else the entry stays (action 0).  The
+ * first occurrence of a handle carries its verdict; a later occurrence of a culled item is action 1, of any other repeats its
+ * action.  SetBadFlag: the item goes bad, its observations are cleared, and for every former observation in stored order the
+ * observer's mvpMapPoints[idx] (mvpMapLines[idx]) becomes null whatever stands there, also another live item, also in a bad
+ * observer.  nObs, found, visible and the reference key frame stay; an entry of a row that names the item without an observation
+ * behind it stays; Map::EraseMapPoint / EraseMapLine stay with the caller.
+ *
+ * Refused, and nothing changes: an unknown handle (DRFE_ERR_INVALID); with the item's name and DRFE_ERR_STATE a listed item that
+ * is not bad without the state above (a point: or without culling attributes that fit its observations), with an obs_index
+ * outside its observer's row, and a listed line that is not bad with mnVisible == 0 or with INT_MIN / -1, where the reference
+ * divides by zero or overflows; an output array that is too small (DRFE_ERR_CAPACITY). */
+enum { DRFE_LMAP_RECENT_MAX_ENTRIES = 1 << 20 };
+enum { DRFE_LMAP_RECENT_KEPT = 0, DRFE_LMAP_RECENT_WAS_BAD = 1, DRFE_LMAP_RECENT_RATIO = 2, DRFE_LMAP_RECENT_OBSERVATIONS = 3,
+       DRFE_LMAP_RECENT_AGED = 4 };
+/* one kind's share of a call: in the list, out what became of it */
+typedef struct drfe_lmap_recent_list {
+    int32_t n;                        /* list entries */
+    const int32_t* handles;           /* in list order */
+    int32_t erased_capacity;          /* entries of erased_kf / erased_index */
+    uint8_t* action;                  /* n: per list entry */
+    int32_t* n_kept;                  /* 1 */
+    int32_t* kept;                    /* n: the surviving list, in list order */
+    int32_t* n_culled;                /* 1 */
+    int32_t* culled;                  /* n: the handles that got SetBadFlag, in list order */
+    int32_t* erased_offsets;          /* n + 1: per culled item, from 0 */
+    int32_t* erased_kf;               /* the erased observations in stored order: key-frame handle */
+    int32_t* erased_index;            /* and index into its row */
+} drfe_lmap_recent_list;
+/* entries of both lists from which drfe_lmap_recent_cull_batch of a store with a context uses the device.  Measured (DESIGN.md
+ * section 31, profiles/recent_cull_timing.jsonl) the device entry wins at 32 768 entries in five of six shapes and at 4 096 in one,
+ * and at no length at every store size with a tenth culled and with none culled, so there is no such length: the constant stands
+ * above the longest call and _batch runs on the host; _device is there to be called. */
+enum { DRFE_LMAP_RECENT_DEVICE_FROM = 2 * DRFE_LMAP_RECENT_MAX_ENTRIES + 1 };
+/* _host always runs on the host, _device always on the device (DRFE_ERR_STATE without a context; DRFE_ERR_CAPACITY when the
+ * configured scratch does not hold the claim words and one list entry), _batch on the device from DRFE_LMAP_RECENT_DEVICE_FROM
+ * entries of both lists when the call fits.  All three return the same bytes and leave the same store.  On success the call
+ * commits into the rows and the image; the device entry commits the bad flags and the nulled entries into the resident image
+ * itself, so that after it only the observations with their offsets travel (drfe_lmap_upload_bytes: no match rows, no graph). */
+int drfe_lmap_recent_cull_host(drfe_lmap* db, int64_t current_kf_id, int32_t monocular, drfe_lmap_recent_list* points,
+                               drfe_lmap_recent_list* lines);
+int drfe_lmap_recent_cull_device(drfe_lmap* db, int64_t current_kf_id, int32_t monocular, drfe_lmap_recent_list* points,
+                                 drfe_lmap_recent_list* lines, void* stream);
+int drfe_lmap_recent_cull_batch(drfe_lmap* db, int64_t current_kf_id, int32_t monocular, drfe_lmap_recent_list* points,
+                                drfe_lmap_recent_list* lines, void* stream);
+/* out[0] list entries of one workgroup of the device's entry launches, [1] erased observations of one pass of an erase workgroup,
+ * [2] bytes of scratch per list entry of a chunk, [3] lanes of a wavefront, [4] DRFE_LMAP_RECENT_MAX_ENTRIES, [5]
+ * DRFE_LMAP_RECENT_DEVICE_FROM */
+int drfe_lmap_recent_cull_limits(int32_t* out6);
+/* the scratch a device call of n_entries list entries takes: out[0] bytes with which it runs as one chunk, [1] the least bytes
+ * with which it runs at all (one entry a chunk), [2] the part every chunk shares (a claim word per stored point and line) */
+int drfe_lmap_recent_cull_scratch(drfe_lmap* db, int64_t n_entries, int64_t* out3);
+/* Counters since the store was created: stats[0] calls, [1] list entries, [2] calls run on the device, [3] culled by ratio, [4]
+ * culled by observations, [5] aged out, [6] dropped as already bad, [7] match-row entries that went from an item to null. */
+int drfe_lmap_recent_cull_stats(drfe_lmap* db, int64_t* stats /* 8 */);
+/* host-to-device bytes of the recent-list block since the store was created (the sixth block, next to drfe_lmap_upload_bytes) */
+int drfe_lmap_recent_upload_bytes(drfe_lmap* db, int64_t* out1);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

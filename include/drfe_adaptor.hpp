@@ -37,6 +37,7 @@
 #include <cassert>
 #include <cmath>
 #include <cstring>
+#include <list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -3928,12 +3929,107 @@ public:
         for (int32_t i = 0; i < nCulled; i++) culled.push_back(mKFs.at(culledH[(size_t)i]));
         return culled;
     }
+    /* LocalMapping::MapPointCulling and MapLineCulling (src/LocalMapping.cc:175-231) with MapPoint::SetBadFlag and
+     * MapLine::SetBadFlag on the store.  Further accessors of MapPointT and MapLineT: GetFound(), the public
+     * mnFirstKFid, Observations(), GetObservations() (pairs of KeyFrameT* and index), SetBadFlag(), and one getter that the
+     * integrator adds because mnVisible is protected: GetVisible(). */
+    /* mnFound, mnVisible and mnFirstKFid of pMP.  Call it with Sync(pMP) and SyncCulling(pMP), which hold its observations. */
+    void SyncRecent(MapPointT* pMP)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const int32_t handle = (int32_t)pMP->mnId, found = (int32_t)pMP->GetFound(), visible = (int32_t)pMP->GetVisible();
+        const int64_t first = (int64_t)pMP->mnFirstKFid;
+        drfe_lmap_recent_attributes a = {};
+        a.n_points = 1;
+        a.point_handle = &handle; a.point_found = &found; a.point_visible = &visible; a.point_first_kf = &first;
+        Check(drfe_lmap_set_recent_attributes(mDb, &a), "drfe_lmap_set_recent_attributes");
+    }
+    /* the same of pML, with nObs and its observations in the order of GetObservations().  Call it with Sync(pML). */
+    void SyncRecent(MapLineT* pML)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const int32_t handle = (int32_t)pML->mnId, found = (int32_t)pML->GetFound(), visible = (int32_t)pML->GetVisible();
+        const int32_t nObs = (int32_t)pML->Observations();
+        const int64_t first = (int64_t)pML->mnFirstKFid;
+        std::vector<int32_t> obs, idx;
+        for (const auto& o : pML->GetObservations()) {
+            obs.push_back((int32_t)o.first->mnId);
+            idx.push_back((int32_t)o.second);
+        }
+        const int32_t off[2] = {0, (int32_t)obs.size()};
+        drfe_lmap_recent_attributes a = {};
+        a.n_lines = 1;
+        a.line_handle = &handle; a.line_found = &found; a.line_visible = &visible; a.line_first_kf = &first; a.line_n_obs = &nObs;
+        a.line_obs_offsets = off; a.line_obs = obs.data(); a.line_obs_index = idx.data();
+        Check(drfe_lmap_set_recent_attributes(mDb, &a), "drfe_lmap_set_recent_attributes");
+    }
+    /* after pMP->IncreaseFound(dFound) / IncreaseVisible(dVisible), or pML's: the counters alone travel */
+    void Increased(MapPointT* pMP, int dFound, int dVisible) { Increase(DRFE_LMAP_POINT, (int32_t)pMP->mnId, dFound, dVisible); }
+    void Increased(MapLineT* pML, int dFound, int dVisible) { Increase(DRFE_LMAP_LINE, (int32_t)pML->mnId, dFound, dVisible); }
+    /* MapPointCulling() over mlpRecentAddedMapPoints = recent for mpCurrentKeyFrame = pCurrentKF.  The store must hold the current
+     * rows of the listed points that are not bad and of their observers (Sync, SyncCulling, SyncRecent).  The store decides and
+     * nulls its own rows; then the list is walked as the reference walks it: an entry with a verdict gets the object's own
+     * SetBadFlag(), which does the same to the objects and sees to the map, and every entry but a kept one is erased. */
+    void MapPointCulling(std::list<MapPointT*>& recent, KeyFrameT* pCurrentKF, bool bMonocular)
+    {
+        RecentCulling(recent, (int64_t)pCurrentKF->mnId, bMonocular, DRFE_LMAP_POINT);
+    }
+    /* MapLineCulling() over mlpRecentAddedMapLines, likewise (Sync, SyncRecent) */
+    void MapLineCulling(std::list<MapLineT*>& recent, KeyFrameT* pCurrentKF, bool bMonocular)
+    {
+        RecentCulling(recent, (int64_t)pCurrentKF->mnId, bMonocular, DRFE_LMAP_LINE);
+    }
     drfe_lmap* db() const { return mDb; }
 
 private:
     void Check(int rc, const char* what) const
     {
         if (rc != DRFE_OK) throw std::runtime_error(std::string(what) + ": " + drfe_lmap_last_error(mDb));
+    }
+    void Increase(int kind, int32_t handle, int dFound, int dVisible)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const int32_t df = (int32_t)dFound, dv = (int32_t)dVisible;
+        Check(drfe_lmap_recent_increase(mDb, kind, 1, &handle, &df, &dv), "drfe_lmap_recent_increase");
+    }
+    template <class ItemT> void RecentCulling(std::list<ItemT*>& recent, int64_t current, bool bMonocular, int kind)
+    {
+        const size_t n = recent.size();
+        if (n == 0) return;
+        std::unique_lock<std::mutex> lock(mMutex);
+        std::vector<int32_t> handles;
+        for (ItemT* p : recent) handles.push_back((int32_t)p->mnId);
+        std::vector<uint8_t> action(n);
+        std::vector<int32_t> kept(n), culled(n), erOff(n + 1), erKf, erIdx;
+        int32_t nKept = 0, nCulled = 0, none = 0, noneOff = 0;
+        /* the erased observations grow until the call fits (a call that does not fit changes nothing) */
+        for (size_t cap = 8 * n + 1024;; cap *= 8) {
+            erKf.resize(cap);
+            erIdx.resize(cap);
+            drfe_lmap_recent_list mine = {}, other = {};
+            mine.n = (int32_t)n; mine.handles = handles.data(); mine.erased_capacity = (int32_t)cap;
+            mine.action = action.data(); mine.n_kept = &nKept; mine.kept = kept.data(); mine.n_culled = &nCulled; mine.culled = culled.data();
+            mine.erased_offsets = erOff.data(); mine.erased_kf = erKf.data(); mine.erased_index = erIdx.data();
+            other.n_kept = other.n_culled = &none; other.erased_offsets = &noneOff;
+            drfe_lmap_recent_list* points = kind == DRFE_LMAP_POINT ? &mine : &other;
+            drfe_lmap_recent_list* lines = kind == DRFE_LMAP_POINT ? &other : &mine;
+            const int32_t mono = bMonocular ? 1 : 0;
+            const int rc = mForce < 0 ? drfe_lmap_recent_cull_host(mDb, current, mono, points, lines)
+                         : mForce > 0 ? drfe_lmap_recent_cull_device(mDb, current, mono, points, lines, nullptr)
+                                      : drfe_lmap_recent_cull_batch(mDb, current, mono, points, lines, nullptr);
+            if (rc == DRFE_ERR_CAPACITY && cap < ((size_t)1 << 28) &&
+                std::string(drfe_lmap_last_error(mDb)).find("than erased_capacity") != std::string::npos)
+                continue;
+            Check(rc, "drfe_lmap_recent_cull");
+            break;
+        }
+        lock.unlock();
+        size_t i = 0;
+        for (auto lit = recent.begin(); lit != recent.end(); i++) {
+            if (action[i] == DRFE_LMAP_RECENT_RATIO || action[i] == DRFE_LMAP_RECENT_OBSERVATIONS) (*lit)->SetBadFlag();
+            if (action[i] == DRFE_LMAP_RECENT_KEPT) ++lit;
+            else lit = recent.erase(lit);
+        }
     }
     template <class M> void Drop(M& known, int kind, int32_t handle)
     {
