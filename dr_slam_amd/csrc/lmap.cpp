@@ -2,8 +2,7 @@
  * C-ABI of include/drfe.h: the argument checks, the host walk, the device entry (lmap_kernels.hip) and the counters.  Both sides
  * read the same image and evaluate lmap_core.h.  A call is checked as a whole and committed only when its results fit the caller's
  * arrays.  DESIGN.md section 25. */
-#include "lmap_store.h"
-#include "stage_layout.h"
+#include "lmap_call.h"
 
 #include <algorithm>
 #include <cstring>
@@ -204,8 +203,9 @@ bool device_fits(const drfe_lmap* db, const Call& C)
 }
 
 /* queries [k0, k1) of the call: one staging block up, the launches, the offsets and records back, then exactly the lists */
-int run_chunk(drfe_lmap* db, const Call& C, int k0, int k1, int32_t rowK, Result& R, hipStream_t st)
+int run_chunk(LmapCall& call, const Call& C, int k0, int k1, int32_t rowK, Result& R)
 {
+    drfe_lmap* db = call.db;
     const Image& G = db->img;
     const size_t nQ = (size_t)(k1 - k0), nK = G.kfHandle.size(), nP = G.mpHandle.size(), nL = G.mlHandle.size();
     const size_t markWords = (nK + 31) / 32;
@@ -240,9 +240,8 @@ int run_chunk(drfe_lmap* db, const Call& C, int k0, int k1, int32_t rowK, Result
     const auto xNulled = scr.add<int32_t>(nPts);
     const auto xMpIn = scr.add<uint8_t>(nQ * nP);
     const auto xMlIn = scr.add<uint8_t>(nQ * nL);
-    HIPCHK_TO(db->err, db->io.grow(in.bytes(), out.bytes()));
-    HIPCHK_TO(db->err, db->scratch.grow(scr.bytes()));
-    char* h = db->io.hin;
+    if (const int rc = call.stage(in.bytes(), out.bytes(), scr.bytes())) return rc;
+    const auto [h, d, dO, dS, ho] = call.at;
     for (size_t k = 0; k <= nQ; k++) {
         sPtOff.at(h)[k] = C.ptOff[(size_t)k0 + k] - pt0;
         sLnOff.at(h)[k] = C.lnOff[(size_t)k0 + k] - ln0;
@@ -251,12 +250,9 @@ int run_chunk(drfe_lmap* db, const Call& C, int k0, int k1, int32_t rowK, Result
     sPts.put(h, C.pts.data() + pt0);
     sLns.put(h, C.lns.data() + ln0);
     sPrev.put(h, C.prev.data() + pv0);
-    const char* d = db->io.din;
-    char* dO = db->io.dout;
-    char* dS = db->scratch;
-    HIPCHK_TO(db->err, hipMemcpyAsync(db->io.din, h, in.bytes(), hipMemcpyHostToDevice, st));
-    if (zeroEnd) HIPCHK_TO(db->err, hipMemsetAsync(dS, 0, zeroEnd, st));
-    if (claimEnd > zeroEnd) HIPCHK_TO(db->err, hipMemsetAsync(dS + zeroEnd, LMAP_NO_CLAIM & 0xff, claimEnd - zeroEnd, st));
+    if (const int rc = call.send()) return rc;
+    hipError_t e = zeroEnd ? hipMemsetAsync(dS, 0, zeroEnd, call.st) : hipSuccess;
+    if (e == hipSuccess && claimEnd > zeroEnd) e = hipMemsetAsync(dS + zeroEnd, LMAP_NO_CLAIM & 0xff, claimEnd - zeroEnd, call.st);
     LmapLaunch L{};
     L.I = db->dView;
     L.nQ = (int32_t)nQ;
@@ -288,30 +284,19 @@ int run_chunk(drfe_lmap* db, const Call& C, int k0, int k1, int32_t rowK, Result
     L.packedIn[0] = xMpIn.at(dS);
     L.packedIn[1] = xMlIn.at(dS);
     L.packedNulled = xNulled.at(dS);
-    hipError_t e = drfe_launch_lmap(L, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(db->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return lmap_fail(db, DRFE_ERR_HIP, std::string("lmap device call: ") + hipGetErrorString(e));
-    const char* ho = db->io.hout;
+    if (e == hipSuccess) e = drfe_launch_lmap(L, call.st);
+    if (const int rc = call.back(e)) return rc;
     const LmapQueryRec* rec = oRec.at(ho);
     const int32_t* off = oOff.at(ho);
     const size_t tKf = (size_t)off[nQ], tMp = (size_t)off[2 * nQ + 1], tMl = (size_t)off[3 * nQ + 2], tNu = (size_t)off[4 * nQ + 3];
-    StageLayout<16> li;
-    const auto lKf = li.add<int32_t>(tKf);
-    const auto lMp = li.add<int32_t>(tMp);
-    const auto lMl = li.add<int32_t>(tMl);
-    const auto lNu = li.add<int32_t>(tNu);
-    const auto lMpIn = li.add<uint8_t>(tMp);
-    const auto lMlIn = li.add<uint8_t>(tMl);
-    HIPCHK_TO(db->err, db->hlist.grow(li.bytes()));
-    char* hl = db->hlist;
-    if (tKf) HIPCHK_TO(db->err, hipMemcpyAsync(lKf.at(hl), xKf.at(dS), lKf.bytes(), hipMemcpyDeviceToHost, st));
-    if (tMp) HIPCHK_TO(db->err, hipMemcpyAsync(lMp.at(hl), xMp.at(dS), lMp.bytes(), hipMemcpyDeviceToHost, st));
-    if (tMl) HIPCHK_TO(db->err, hipMemcpyAsync(lMl.at(hl), xMl.at(dS), lMl.bytes(), hipMemcpyDeviceToHost, st));
-    if (tNu) HIPCHK_TO(db->err, hipMemcpyAsync(lNu.at(hl), xNulled.at(dS), lNu.bytes(), hipMemcpyDeviceToHost, st));
-    if (tMp) HIPCHK_TO(db->err, hipMemcpyAsync(lMpIn.at(hl), xMpIn.at(dS), lMpIn.bytes(), hipMemcpyDeviceToHost, st));
-    if (tMl) HIPCHK_TO(db->err, hipMemcpyAsync(lMlIn.at(hl), xMlIn.at(dS), lMlIn.bytes(), hipMemcpyDeviceToHost, st));
-    HIPCHK_TO(db->err, hipStreamSynchronize(st));
+    LmapFetch f;
+    const auto lKf = f.add(xKf.at(dS), tKf);
+    const auto lMp = f.add(xMp.at(dS), tMp);
+    const auto lMl = f.add(xMl.at(dS), tMl);
+    const auto lNu = f.add(xNulled.at(dS), tNu);
+    const auto lMpIn = f.add(xMpIn.at(dS), tMp);
+    const auto lMlIn = f.add(xMlIn.at(dS), tMl);
+    if (const int rc = call.fetch(f)) return rc;
     const int32_t bKf = R.kfOff.back(), bMp = R.mpOff.back(), bMl = R.mlOff.back(), bNu = R.nuOff.back();
     for (size_t k = 0; k < nQ; k++) {
         R.kfOff.push_back(bKf + off[k + 1]);
@@ -321,29 +306,25 @@ int run_chunk(drfe_lmap* db, const Call& C, int k0, int k1, int32_t rowK, Result
         R.ref.push_back(rec[k].refKf);
         for (int f = 0; f < 4; f++) R.record.push_back(rec[k].rec[f]);
     }
-    R.kfs.insert(R.kfs.end(), lKf.at(hl), lKf.at(hl) + tKf);
-    R.mps.insert(R.mps.end(), lMp.at(hl), lMp.at(hl) + tMp);
-    R.mls.insert(R.mls.end(), lMl.at(hl), lMl.at(hl) + tMl);
-    R.nulled.insert(R.nulled.end(), lNu.at(hl), lNu.at(hl) + tNu);
-    R.mpIn.insert(R.mpIn.end(), lMpIn.at(hl), lMpIn.at(hl) + tMp);
-    R.mlIn.insert(R.mlIn.end(), lMlIn.at(hl), lMlIn.at(hl) + tMl);
+    R.kfs.insert(R.kfs.end(), f.at(lKf), f.at(lKf) + tKf);
+    R.mps.insert(R.mps.end(), f.at(lMp), f.at(lMp) + tMp);
+    R.mls.insert(R.mls.end(), f.at(lMl), f.at(lMl) + tMl);
+    R.nulled.insert(R.nulled.end(), f.at(lNu), f.at(lNu) + tNu);
+    R.mpIn.insert(R.mpIn.end(), f.at(lMpIn), f.at(lMpIn) + tMp);
+    R.mlIn.insert(R.mlIn.end(), f.at(lMlIn), f.at(lMlIn) + tMl);
     return DRFE_OK;
 }
 
 int run_device(drfe_lmap* db, const Call& C, Result& R, void* stream)
 {
-    drfe_ctx* c = db->ctx;
-    HIPCHK_TO(db->err, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int rc = lmap_upload(db, LMAP_NEED_IMAGE, st);
-    if (rc) return rc;
+    LmapCall call{db, "lmap"};
+    if (const int rc = call.begin(LMAP_NEED_IMAGE, stream)) return rc;
     const int32_t rowK = row_k(db, C);
     const int64_t perQuery = query_scratch(db, C, rowK);
     const int chunk = (int)std::min<int64_t>(C.n, std::max<int64_t>(1, db->scratchBytes / perQuery));
     R.start();
     for (int k0 = 0; k0 < C.n; k0 += chunk) {
-        rc = run_chunk(db, C, k0, std::min(C.n, k0 + chunk), rowK, R, st);
-        if (rc) return rc;
+        if (const int rc = run_chunk(call, C, k0, std::min(C.n, k0 + chunk), rowK, R)) return rc;
     }
     return DRFE_OK;
 }
@@ -427,12 +408,6 @@ int drfe_lmap_update_host(drfe_lmap* db, const drfe_lmap_queries* q, drfe_lmap_o
 int drfe_lmap_update_device(drfe_lmap* db, const drfe_lmap_queries* q, drfe_lmap_out* o, void* stream) { return entry(db, q, o, 1, stream); }
 int drfe_lmap_update_batch(drfe_lmap* db, const drfe_lmap_queries* q, drfe_lmap_out* o, void* stream) { return entry(db, q, o, 2, stream); }
 
-int drfe_lmap_stats(drfe_lmap* db, int64_t* stats)
-{
-    if (!db || !stats) return DRFE_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(db->mu);
-    std::memcpy(stats, db->stats, sizeof(db->stats));
-    return DRFE_OK;
-}
+int drfe_lmap_stats(drfe_lmap* db, int64_t* stats) { return lmap_stats(db, &drfe_lmap::stats, stats); }
 
 }  // extern "C"

@@ -1,8 +1,7 @@
 /* lmap_conn.cpp — KeyFrame::UpdateConnections (reference src/KeyFrame.cc:366-500) on the local-map store (lmap_store.h), behind
  * the C-ABI of include/drfe.h: the setter and getter of the connection rows, the checks, the host walk, the device entry
  * (conn_kernels.hip), the commit into rows and image and the counters.  Both sides evaluate conn_core.h.  DESIGN.md section 26. */
-#include "lmap_store.h"
-#include "stage_layout.h"
+#include "lmap_call.h"
 
 static_assert(CONN_TH == DRFE_LMAP_CONNECT_TH, "the vote threshold of conn_core.h is the header's");
 
@@ -202,11 +201,8 @@ ConnFit conn_fit(const drfe_lmap* db, const std::vector<int32_t>& called)
 int conn_device(drfe_lmap* db, const std::vector<int32_t>& called, const std::vector<int32_t>& pos, const ConnFit& F, ConnResult& R,
                 void* stream)
 {
-    drfe_ctx* c = db->ctx;
-    HIPCHK_TO(db->err, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int rc = lmap_upload(db, LMAP_NEED_IMAGE, st);
-    if (rc) return rc;
+    LmapCall call{db, "lmap connect"};
+    if (const int rc = call.begin(LMAP_NEED_IMAGE, stream)) return rc;
     const Image& G = db->img;
     const size_t n = called.size(), nK = G.kfHandle.size(), cap = (size_t)F.capOff[n], rows = (size_t)F.rowBound;
     const bool global = nK > LMAP_LDS_KFS;
@@ -237,16 +233,12 @@ int conn_device(drfe_lmap* db, const std::vector<int32_t>& called, const std::ve
     const auto xPkWW = scr.add<int32_t>(rows);
     const auto xPkOKf = scr.add<int32_t>(rows);
     const auto xPkOW = scr.add<int32_t>(rows);
-    HIPCHK_TO(db->err, db->io.grow(in.bytes(), out.bytes()));
-    HIPCHK_TO(db->err, db->scratch.grow(scr.bytes()));
-    char* h = db->io.hin;
+    if (const int rc = call.stage(in.bytes(), out.bytes(), scr.bytes())) return rc;
+    const auto [h, d, dO, dS, ho] = call.at;
     sCalled.put(h, called.data());
     sPos.put(h, pos.data());
     sCapOff.put(h, F.capOff.data());
-    const char* d = db->io.din;
-    char* dO = db->io.dout;
-    char* dS = db->scratch;
-    HIPCHK_TO(db->err, hipMemcpyAsync(db->io.din, h, in.bytes(), hipMemcpyHostToDevice, st));
+    if (const int rc = call.send()) return rc;
     ConnLaunch L{};
     L.I = db->dView;
     L.G = db->dConn;
@@ -278,35 +270,23 @@ int conn_device(drfe_lmap* db, const std::vector<int32_t>& called, const std::ve
     L.pkWW = xPkWW.at(dS);
     L.pkOKf = xPkOKf.at(dS);
     L.pkOW = xPkOW.at(dS);
-    hipError_t e = drfe_launch_conn(L, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(db->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return lmap_fail(db, DRFE_ERR_HIP, std::string("lmap connect device call: ") + hipGetErrorString(e));
-    const char* ho = db->io.hout;
+    if (const int rc = call.back(drfe_launch_conn(L, call.st))) return rc;
     const ConnRec* rec = oRec.at(ho);
     const int32_t* head = oHead.at(ho);
     const size_t nT = (size_t)head[CONN_HEAD_TOUCHED], tW = (size_t)head[CONN_HEAD_WEIGHTS], tO = (size_t)head[CONN_HEAD_ORDERED],
                  tC = (size_t)head[CONN_HEAD_COUNTER];
     if (nT > nK || tW > rows || tO > rows || tC > cap) return lmap_fail(db, DRFE_ERR_STATE, "lmap connect device call: totals past their bounds");
-    StageLayout<16> li;
-    const auto lCntKf = li.add<int32_t>(tC);
-    const auto lCntW = li.add<int32_t>(tC);
-    const auto lWKf = li.add<int32_t>(tW);
-    const auto lWW = li.add<int32_t>(tW);
-    const auto lOKf = li.add<int32_t>(tO);
-    const auto lOW = li.add<int32_t>(tO);
-    HIPCHK_TO(db->err, db->hlist.grow(li.bytes()));
-    char* hl = db->hlist;
-    if (tC) HIPCHK_TO(db->err, hipMemcpyAsync(lCntKf.at(hl), xPkCntKf.at(dS), lCntKf.bytes(), hipMemcpyDeviceToHost, st));
-    if (tC) HIPCHK_TO(db->err, hipMemcpyAsync(lCntW.at(hl), xPkCntW.at(dS), lCntW.bytes(), hipMemcpyDeviceToHost, st));
-    if (tW) HIPCHK_TO(db->err, hipMemcpyAsync(lWKf.at(hl), xPkWKf.at(dS), lWKf.bytes(), hipMemcpyDeviceToHost, st));
-    if (tW) HIPCHK_TO(db->err, hipMemcpyAsync(lWW.at(hl), xPkWW.at(dS), lWW.bytes(), hipMemcpyDeviceToHost, st));
-    if (tO) HIPCHK_TO(db->err, hipMemcpyAsync(lOKf.at(hl), xPkOKf.at(dS), lOKf.bytes(), hipMemcpyDeviceToHost, st));
-    if (tO) HIPCHK_TO(db->err, hipMemcpyAsync(lOW.at(hl), xPkOW.at(dS), lOW.bytes(), hipMemcpyDeviceToHost, st));
-    HIPCHK_TO(db->err, hipStreamSynchronize(st));
+    LmapFetch f;
+    const auto lCntKf = f.add(xPkCntKf.at(dS), tC);
+    const auto lCntW = f.add(xPkCntW.at(dS), tC);
+    const auto lWKf = f.add(xPkWKf.at(dS), tW);
+    const auto lWW = f.add(xPkWW.at(dS), tW);
+    const auto lOKf = f.add(xPkOKf.at(dS), tO);
+    const auto lOW = f.add(xPkOW.at(dS), tO);
+    if (const int rc = call.fetch(f)) return rc;
     R.cntOff.assign(oCntOff.at(ho), oCntOff.at(ho) + n + 1);
-    R.cntKf.assign(lCntKf.at(hl), lCntKf.at(hl) + tC);
-    R.cntW.assign(lCntW.at(hl), lCntW.at(hl) + tC);
+    R.cntKf.assign(f.at(lCntKf), f.at(lCntKf) + tC);
+    R.cntW.assign(f.at(lCntW), f.at(lCntW) + tC);
     R.record.resize(4 * n);
     for (size_t p = 0; p < n; p++) {
         R.record[4 * p + 0] = rec[p].nC;
@@ -320,10 +300,10 @@ int conn_device(drfe_lmap* db, const std::vector<int32_t>& called, const std::ve
     R.oOff.assign(oOOff.at(ho), oOOff.at(ho) + nT + 1);
     R.parent.assign(oParent.at(ho), oParent.at(ho) + nT);
     R.first.assign(oFirst.at(ho), oFirst.at(ho) + nT);
-    R.wKf.assign(lWKf.at(hl), lWKf.at(hl) + tW);
-    R.wW.assign(lWW.at(hl), lWW.at(hl) + tW);
-    R.oKf.assign(lOKf.at(hl), lOKf.at(hl) + tO);
-    R.oW.assign(lOW.at(hl), lOW.at(hl) + tO);
+    R.wKf.assign(f.at(lWKf), f.at(lWKf) + tW);
+    R.wW.assign(f.at(lWW), f.at(lWW) + tW);
+    R.oKf.assign(f.at(lOKf), f.at(lOKf) + tO);
+    R.oW.assign(f.at(lOW), f.at(lOW) + tO);
     return DRFE_OK;
 }
 
@@ -622,11 +602,5 @@ int drfe_lmap_connect_limits(int32_t* out4)
     return DRFE_OK;
 }
 
-int drfe_lmap_connect_stats(drfe_lmap* db, int64_t* stats)
-{
-    if (!db || !stats) return DRFE_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(db->mu);
-    std::memcpy(stats, db->connStats, sizeof(db->connStats));
-    return DRFE_OK;
-}
+int drfe_lmap_connect_stats(drfe_lmap* db, int64_t* stats) { return lmap_stats(db, &drfe_lmap::connStats, stats); }
 }  // extern "C"

@@ -2,8 +2,7 @@
  * store, behind the C-ABI of include/drfe.h: the geometry setters and getters, the geometry image, the checks, the host walk, the
  * device entry (correct_kernels.hip), the commit and the counters.  Both sides evaluate correct_core.h.  A call is checked as a
  * whole and committed only when its results fit the caller's arrays.  DESIGN.md section 27. */
-#include "lmap_store.h"
-#include "stage_layout.h"
+#include "lmap_call.h"
 
 #include <algorithm>
 #include <cstring>
@@ -215,11 +214,8 @@ CorrFit corr_fit(const drfe_lmap* db, const CorrPlan& C)
  * written only after the capacity test.  A HIP failure in between leaves the device copy to be sent again. */
 int corr_device(drfe_lmap* db, const CorrPlan& C, const CorrFit& F, int32_t capacity, CorrResult& R, void* stream)
 {
-    drfe_ctx* c = db->ctx;
-    HIPCHK_TO(db->err, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int rc = lmap_upload(db, LMAP_NEED_GEO, st);
-    if (rc) return rc;
+    LmapCall call{db, "lmap correct"};
+    if (const int rc = call.begin(LMAP_NEED_GEO, stream)) return rc;
     const Image& G = db->img;
     const size_t n = (size_t)C.n, nK = G.kfHandle.size(), nP = G.mpHandle.size();
     /* rows of a chunk: as many positions as the budget holds, one at least */
@@ -246,17 +242,13 @@ int corr_device(drfe_lmap* db, const CorrPlan& C, const CorrFit& F, int32_t capa
     const auto xMax = scr.add<float>((size_t)chunkRows);
     const auto xMin = scr.add<float>((size_t)chunkRows);
     const auto xStatus = scr.add<uint8_t>((size_t)chunkRows);
-    HIPCHK_TO(db->err, db->io.grow(in.bytes(), out.bytes()));
-    HIPCHK_TO(db->err, db->scratch.grow(scr.bytes()));
-    char* h = db->io.hin;
+    if (const int rc = call.stage(in.bytes(), out.bytes(), scr.bytes())) return rc;
+    const auto [h, d, dO, dS, ho] = call.at;
     sCalled.put(h, C.called.data());
     sHandle.put(h, C.calledHandle.data());
     sPos.put(h, C.pos.data());
-    const char* d = db->io.din;
-    char* dO = db->io.dout;
-    char* dS = db->scratch;
-    HIPCHK_TO(db->err, hipMemcpyAsync(db->io.din, h, in.bytes(), hipMemcpyHostToDevice, st));
-    if (nP) HIPCHK_TO(db->err, hipMemsetAsync(xClaim.at(dS), LMAP_NO_CLAIM & 0xff, xClaim.bytes(), st));
+    if (const int rc = call.send()) return rc;
+    hipError_t e = nP ? hipMemsetAsync(xClaim.at(dS), LMAP_NO_CLAIM & 0xff, xClaim.bytes(), call.st) : hipSuccess;
     CorrLaunch L{};
     L.I = db->dView;
     L.G = db->dCorr;
@@ -280,11 +272,8 @@ int corr_device(drfe_lmap* db, const CorrPlan& C, const CorrFit& F, int32_t capa
     L.pkMax = xMax.at(dS);
     L.pkMin = xMin.at(dS);
     L.pkStatus = xStatus.at(dS);
-    hipError_t e = drfe_launch_correct_plan(L, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(db->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return lmap_fail(db, DRFE_ERR_HIP, std::string("lmap correct device call: ") + hipGetErrorString(e));
-    const char* ho = db->io.hout;
+    if (e == hipSuccess) e = drfe_launch_correct_plan(L, call.st);
+    if (const int rc = call.back(e)) return rc;
     R.kf.assign(oKf.at(ho), oKf.at(ho) + n);
     const std::vector<int32_t> off(oOff.at(ho), oOff.at(ho) + n + 1);
     const int64_t total = off[n];
@@ -297,17 +286,16 @@ int corr_device(drfe_lmap* db, const CorrPlan& C, const CorrFit& F, int32_t capa
     R.maxD.resize((size_t)total);
     R.minD.resize((size_t)total);
     R.status.resize((size_t)total);
-    db->blk[drfe_lmap::GEO].stale_all();       /* until the last launch has run */
-    StageLayout<16> li;
-    const auto lItem = li.add<int32_t>((size_t)chunkRows);
-    const auto lBy = li.add<int32_t>((size_t)chunkRows);
-    const auto lWorld = li.add<float>(3 * (size_t)chunkRows);
-    const auto lNormal = li.add<float>(3 * (size_t)chunkRows);
-    const auto lMax = li.add<float>((size_t)chunkRows);
-    const auto lMin = li.add<float>((size_t)chunkRows);
-    const auto lStatus = li.add<uint8_t>((size_t)chunkRows);
-    HIPCHK_TO(db->err, db->hlist.grow(li.bytes()));
-    char* hl = db->hlist;
+    LmapWrites writes(db->blk[drfe_lmap::GEO]);
+    LmapFetch f;
+    const auto lItem = f.add(xItem.at(dS), (size_t)chunkRows);
+    const auto lBy = f.add(xBy.at(dS), (size_t)chunkRows);
+    const auto lWorld = f.add(xWorld.at(dS), 3 * (size_t)chunkRows);
+    const auto lNormal = f.add(xNormal.at(dS), 3 * (size_t)chunkRows);
+    const auto lMax = f.add(xMax.at(dS), (size_t)chunkRows);
+    const auto lMin = f.add(xMin.at(dS), (size_t)chunkRows);
+    const auto lStatus = f.add(xStatus.at(dS), (size_t)chunkRows);
+    if (const int rc = call.room(f)) return rc;
     for (size_t j0 = 0; j0 < n;) {
         size_t j1 = j0;
         rows = 0;
@@ -320,34 +308,21 @@ int corr_device(drfe_lmap* db, const CorrPlan& C, const CorrFit& F, int32_t capa
         L.j0 = (int32_t)j0;
         L.j1 = (int32_t)j1;
         const size_t b = (size_t)off[j0], cnt = (size_t)(off[j1] - off[j0]);
-        e = drfe_launch_correct_chunk(L, st);
-        if (e != hipSuccess) return lmap_fail(db, DRFE_ERR_HIP, std::string("lmap correct device call: ") + hipGetErrorString(e));
-        if (cnt) {
-            HIPCHK_TO(db->err, hipMemcpyAsync(lItem.at(hl), xItem.at(dS), 4 * cnt, hipMemcpyDeviceToHost, st));
-            HIPCHK_TO(db->err, hipMemcpyAsync(lBy.at(hl), xBy.at(dS), 4 * cnt, hipMemcpyDeviceToHost, st));
-            HIPCHK_TO(db->err, hipMemcpyAsync(lWorld.at(hl), xWorld.at(dS), 12 * cnt, hipMemcpyDeviceToHost, st));
-            HIPCHK_TO(db->err, hipMemcpyAsync(lNormal.at(hl), xNormal.at(dS), 12 * cnt, hipMemcpyDeviceToHost, st));
-            HIPCHK_TO(db->err, hipMemcpyAsync(lMax.at(hl), xMax.at(dS), 4 * cnt, hipMemcpyDeviceToHost, st));
-            HIPCHK_TO(db->err, hipMemcpyAsync(lMin.at(hl), xMin.at(dS), 4 * cnt, hipMemcpyDeviceToHost, st));
-            HIPCHK_TO(db->err, hipMemcpyAsync(lStatus.at(hl), xStatus.at(dS), cnt, hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK_TO(db->err, hipStreamSynchronize(st));
-        if (cnt) {
-            std::memcpy(&R.item[b], lItem.at(hl), 4 * cnt);
-            std::memcpy(&R.by[b], lBy.at(hl), 4 * cnt);
-            std::memcpy(&R.world[3 * b], lWorld.at(hl), 12 * cnt);
-            std::memcpy(&R.normal[3 * b], lNormal.at(hl), 12 * cnt);
-            std::memcpy(&R.maxD[b], lMax.at(hl), 4 * cnt);
-            std::memcpy(&R.minD[b], lMin.at(hl), 4 * cnt);
-            std::memcpy(&R.status[b], lStatus.at(hl), cnt);
-        }
+        f.set(cnt, lItem, lBy, lMax, lMin, lStatus);
+        f.set(3 * cnt, lWorld, lNormal);
+        if (const int rc = call.fetch(f, drfe_launch_correct_chunk(L, call.st))) return rc;
+        f.get(lItem, R.item.data() + b);
+        f.get(lBy, R.by.data() + b);
+        f.get(lWorld, R.world.data() + 3 * b);
+        f.get(lNormal, R.normal.data() + 3 * b);
+        f.get(lMax, R.maxD.data() + b);
+        f.get(lMin, R.minD.data() + b);
+        f.get(lStatus, R.status.data() + b);
         R.chunks++;
         j0 = j1;
     }
-    e = drfe_launch_correct_poses(L, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return lmap_fail(db, DRFE_ERR_HIP, std::string("lmap correct device call: ") + hipGetErrorString(e));
-    db->blk[drfe_lmap::GEO].assume_current();
+    if (const int rc = call.drain(drfe_launch_correct_poses(L, call.st))) return rc;
+    writes.done();
     return DRFE_OK;
 }
 
@@ -576,12 +551,6 @@ int drfe_lmap_correct_scratch(drfe_lmap* db, int32_t n, const int32_t* handles, 
     return DRFE_OK;
 }
 
-int drfe_lmap_correct_stats(drfe_lmap* db, int64_t* stats)
-{
-    if (!db || !stats) return DRFE_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(db->mu);
-    std::memcpy(stats, db->corrStats, sizeof(db->corrStats));
-    return DRFE_OK;
-}
+int drfe_lmap_correct_stats(drfe_lmap* db, int64_t* stats) { return lmap_stats(db, &drfe_lmap::corrStats, stats); }
 
 }  // extern "C"

@@ -6,8 +6,7 @@
  * part works on the image in place and keeps a log, so that a call that is refused late is undone; the graph part works on copies
  * of the touched rows.  DESIGN.md section 28.  Parity with a build of the reference's LocalMapping.cc and KeyFrame.cc is not
  * pinned: neither can be built here. */
-#include "lmap_store.h"
-#include "stage_layout.h"
+#include "lmap_call.h"
 
 #include <algorithm>
 #include <cstring>
@@ -424,11 +423,8 @@ CullFit cull_fit(const drfe_lmap* db, const CullPlan& C)
  * read. */
 int cull_device(drfe_lmap* db, const CullPlan& C, const CullFit& F, CullWork& W, void* stream)
 {
-    drfe_ctx* c = db->ctx;
-    HIPCHK_TO(db->err, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int rc = lmap_upload(db, LMAP_NEED_ATTR, st);
-    if (rc) return rc;
+    LmapCall call{db, "lmap cull"};
+    if (const int rc = call.begin(LMAP_NEED_ATTR, stream)) return rc;
     const Image& G = db->img;
     const size_t n = (size_t)C.n, nK = G.kfHandle.size(), nP = G.mpHandle.size();
     const int64_t room = (std::min<int64_t>(db->scratchBytes, F.whole) - F.fixed) / CULL_ENTRY_BYTES;
@@ -452,24 +448,19 @@ int cull_device(drfe_lmap* db, const CullPlan& C, const CullFit& F, CullWork& W,
     const auto xTouched = scr.add<uint8_t>(nP);
     const auto xSpec = scr.add<CullSpec>(n);
     const auto xRec = scr.add<CullRecord>((size_t)chunkRows);
-    HIPCHK_TO(db->err, db->io.grow(in.bytes(), out.bytes()));
-    HIPCHK_TO(db->err, db->scratch.grow(scr.bytes()));
-    char* h = db->io.hin;
+    if (const int rc = call.stage(in.bytes(), out.bytes(), scr.bytes())) return rc;
+    const auto [h, d, dO, dS, ho] = call.at;
     sCalled.put(h, C.called.data());
     sPos.put(h, C.pos.data());
     sRecOff.put(h, C.recOff.data());
-    const char* d = db->io.din;
-    char* dO = db->io.dout;
-    char* dS = db->scratch;
-    HIPCHK_TO(db->err, hipMemcpyAsync(db->io.din, h, in.bytes(), hipMemcpyHostToDevice, st));
-    if (xRow.bytes()) HIPCHK_TO(db->err, hipMemcpyAsync(xRow.at(dS), db->dView.kfMp, xRow.bytes(), hipMemcpyDeviceToDevice, st));
-    if (nP) {
-        HIPCHK_TO(db->err, hipMemcpyAsync(xNObs.at(dS), db->dCull.nObs, xNObs.bytes(), hipMemcpyDeviceToDevice, st));
-        HIPCHK_TO(db->err, hipMemcpyAsync(xBad.at(dS), db->dView.mpBad, xBad.bytes(), hipMemcpyDeviceToDevice, st));
-        HIPCHK_TO(db->err, hipMemsetAsync(xClaim.at(dS), 0xff, xClaim.bytes(), st));
-    }
-    if (xLive.bytes()) HIPCHK_TO(db->err, hipMemsetAsync(xLive.at(dS), 1, xLive.bytes(), st));
-    HIPCHK_TO(db->err, hipMemsetAsync(xSpec.at(dS), 0, xSpec.bytes(), st));
+    if (const int rc = call.send()) return rc;
+    hipError_t e = hipSuccess;
+    if (xRow.bytes()) e = hipMemcpyAsync(xRow.at(dS), db->dView.kfMp, xRow.bytes(), hipMemcpyDeviceToDevice, call.st);
+    if (e == hipSuccess && nP) e = hipMemcpyAsync(xNObs.at(dS), db->dCull.nObs, xNObs.bytes(), hipMemcpyDeviceToDevice, call.st);
+    if (e == hipSuccess && nP) e = hipMemcpyAsync(xBad.at(dS), db->dView.mpBad, xBad.bytes(), hipMemcpyDeviceToDevice, call.st);
+    if (e == hipSuccess && nP) e = hipMemsetAsync(xClaim.at(dS), 0xff, xClaim.bytes(), call.st);
+    if (e == hipSuccess && xLive.bytes()) e = hipMemsetAsync(xLive.at(dS), 1, xLive.bytes(), call.st);
+    if (e == hipSuccess) e = hipMemsetAsync(xSpec.at(dS), 0, xSpec.bytes(), call.st);
     CullLaunch L{};
     L.S = cull_state(db->dView, db->dCull, xRow.at(dS), xBad.at(dS), xNObs.at(dS), xLive.at(dS));
     L.monocular = C.monocular;
@@ -481,7 +472,6 @@ int cull_device(drfe_lmap* db, const CullPlan& C, const CullFit& F, CullWork& W,
     L.touched = xTouched.at(dS);
     L.spec = xSpec.at(dS);
     L.out = oOut.at(dO);
-    hipError_t e = hipSuccess;
     for (size_t j0 = 0; j0 < n && e == hipSuccess;) {
         size_t j1 = j0;
         rows = 0;
@@ -496,19 +486,16 @@ int cull_device(drfe_lmap* db, const CullPlan& C, const CullFit& F, CullWork& W,
         L.j0 = (int32_t)j0;
         L.j1 = (int32_t)j1;
         L.maxRow = maxRow;
-        if (nP) e = hipMemsetAsync(xTouched.at(dS), 0, xTouched.bytes(), st);
-        if (e == hipSuccess) e = drfe_launch_cull_chunk(L, st);
+        if (nP) e = hipMemsetAsync(xTouched.at(dS), 0, xTouched.bytes(), call.st);
+        if (e == hipSuccess) e = drfe_launch_cull_chunk(L, call.st);
         j0 = j1;
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(db->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return lmap_fail(db, DRFE_ERR_HIP, std::string("lmap cull device call: ") + hipGetErrorString(e));
-    const int32_t* res = oOut.at((const char*)db->io.hout);
+    if (const int rc = call.back(e)) return rc;
+    const int32_t* res = oOut.at(ho);
     W.onDevice = true;
     for (size_t j = 0; j < n; j++) {
         const int32_t* r = res + CULL_OUT_WORDS * j;
-        rc = cull_decided(db, C, W, (int)j, r[0], r[1]);
-        if (rc) return rc;
+        if (const int rc = cull_decided(db, C, W, (int)j, r[0], r[1])) return rc;
         if (W.record[4 * j + 3] != r[2] || W.died[j] != r[3])
             return lmap_fail(db, DRFE_ERR_STATE, "lmap cull device call: the device and the host disagree on key frame " +
                                                 std::to_string(G.kfHandle[(size_t)C.called[j]]));
@@ -924,12 +911,6 @@ int drfe_lmap_cull_scratch(drfe_lmap* db, int32_t n, const int32_t* handles, int
     return DRFE_OK;
 }
 
-int drfe_lmap_cull_stats(drfe_lmap* db, int64_t* stats)
-{
-    if (!db || !stats) return DRFE_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(db->mu);
-    std::memcpy(stats, db->cullStats, sizeof(db->cullStats));
-    return DRFE_OK;
-}
+int drfe_lmap_cull_stats(drfe_lmap* db, int64_t* stats) { return lmap_stats(db, &drfe_lmap::cullStats, stats); }
 
 }  // extern "C"

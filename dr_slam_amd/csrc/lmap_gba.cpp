@@ -2,8 +2,7 @@
  * local-map store, behind the C-ABI of include/drfe.h: the setters and getters of mTcwGBA, mTcwBefGBA, mPosGBA and the stamps,
  * that state by slot, the integer walk with its checks, the host entry, the device entry (gba_kernels.hip), the commit and the
  * counters.  Both sides evaluate gba_core.h.  A call is checked as a whole before anything is written.  DESIGN.md section 29. */
-#include "lmap_store.h"
-#include "stage_layout.h"
+#include "lmap_call.h"
 
 #include <algorithm>
 #include <cstring>
@@ -231,17 +230,14 @@ GbaFit gba_fit(const drfe_lmap* db)
  * leaves both to be sent again. */
 int gba_device(drfe_lmap* db, const GbaPlan& W, GbaResult& R, void* stream)
 {
-    drfe_ctx* c = db->ctx;
-    HIPCHK_TO(db->err, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    int rc = lmap_upload(db, LMAP_NEED_GBA, st);
-    if (rc) return rc;
+    LmapCall call{db, "lmap gba"};
+    if (const int rc = call.begin(LMAP_NEED_GBA, stream)) return rc;
     const size_t nV = W.list.size(), nP = db->img.mpHandle.size(), chunk = (size_t)W.chunkPts;
     const size_t nGroups = (chunk + GBA_TILE - 1) / GBA_TILE;
     const int64_t total = W.nKind[1] + W.nKind[2];
     size_t most = 0;
     for (const int32_t m : W.chunkMoved) most = std::max(most, (size_t)m);
-    StageLayout<16> in, out, scr, li;
+    StageLayout<16> in, out, scr;
     const auto sList = in.add<int32_t>(nV);
     const auto sOff = in.add<int32_t>(W.roundOff.size());
     const auto sKf = in.add<int32_t>(W.roundKf.size());
@@ -253,23 +249,19 @@ int gba_device(drfe_lmap* db, const GbaPlan& W, GbaResult& R, void* stream)
     const auto xItem = scr.add<int32_t>(most);
     const auto xWorld = scr.add<float>(3 * most);
     const auto xPk = scr.add<uint8_t>(most);
-    const auto lItem = li.add<int32_t>(most);
-    const auto lWorld = li.add<float>(3 * most);
-    const auto lKind = li.add<uint8_t>(most);
-    const auto lTot = li.add<int32_t>(1);
-    HIPCHK_TO(db->err, db->io.grow(in.bytes(), out.bytes()));
-    HIPCHK_TO(db->err, db->scratch.grow(scr.bytes()));
-    HIPCHK_TO(db->err, db->hlist.grow(li.bytes()));
-    char* h = db->io.hin;
+    if (const int rc = call.stage(in.bytes(), out.bytes(), scr.bytes())) return rc;
+    const auto [h, d, dO, dS, ho] = call.at;
+    LmapFetch f;
+    const auto lTot = f.add(xCnt.at(dS), 1);
+    const auto lItem = f.add(xItem.at(dS), most);
+    const auto lWorld = f.add(xWorld.at(dS), 3 * most);
+    const auto lKind = f.add(xPk.at(dS), most);
+    if (const int rc = call.room(f)) return rc;
     sList.put(h, W.list.data());
     sOff.put(h, W.roundOff.data());
     sKf.put(h, W.roundKf.data());
     sPar.put(h, W.roundParent.data());
-    const char* d = db->io.din;
-    char* dO = db->io.dout;
-    char* dS = db->scratch;
-    char* hl = db->hlist;
-    HIPCHK_TO(db->err, hipMemcpyAsync(db->io.din, h, in.bytes(), hipMemcpyHostToDevice, st));
+    if (const int rc = call.send()) return rc;
     GbaLaunch L{};
     L.I = db->dView;
     L.G = db->dCorr;
@@ -289,13 +281,8 @@ int gba_device(drfe_lmap* db, const GbaPlan& W, GbaResult& R, void* stream)
     L.pkKind = xPk.at(dS);
     L.outPose = oPose.at(dO);
     L.outBef = oBef.at(dO);
-    db->blk[drfe_lmap::GEO].stale_all();       /* until the last launch has run */
-    db->blk[drfe_lmap::GBA].stale_all();
-    hipError_t e = drfe_launch_gba_keyframes(L, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(db->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return lmap_fail(db, DRFE_ERR_HIP, std::string("lmap gba device call: ") + hipGetErrorString(e));
-    const char* ho = db->io.hout;
+    LmapWrites writes(db->blk[drfe_lmap::GEO], &db->blk[drfe_lmap::GBA]);
+    if (const int rc = call.back(drfe_launch_gba_keyframes(L, call.st))) return rc;
     R.pose.assign(oPose.at(ho), oPose.at(ho) + 16 * nV);
     R.bef.assign(oBef.at(ho), oBef.at(ho) + 16 * nV);
     R.item.resize((size_t)total);
@@ -306,26 +293,17 @@ int gba_device(drfe_lmap* db, const GbaPlan& W, GbaResult& R, void* stream)
         const size_t p1 = std::min(nP, p0 + chunk), cnt = (size_t)W.chunkMoved[k];
         L.p0 = (int32_t)p0;
         L.p1 = (int32_t)p1;
-        e = drfe_launch_gba_points(L, st);
-        if (e != hipSuccess) return lmap_fail(db, DRFE_ERR_HIP, std::string("lmap gba device call: ") + hipGetErrorString(e));
-        const size_t g = (p1 - p0 + GBA_TILE - 1) / GBA_TILE;
-        HIPCHK_TO(db->err, hipMemcpyAsync(lTot.at(hl), xCnt.at(dS) + g, 4, hipMemcpyDeviceToHost, st));
-        if (cnt) {
-            HIPCHK_TO(db->err, hipMemcpyAsync(lItem.at(hl), xItem.at(dS), 4 * cnt, hipMemcpyDeviceToHost, st));
-            HIPCHK_TO(db->err, hipMemcpyAsync(lWorld.at(hl), xWorld.at(dS), 12 * cnt, hipMemcpyDeviceToHost, st));
-            HIPCHK_TO(db->err, hipMemcpyAsync(lKind.at(hl), xPk.at(dS), cnt, hipMemcpyDeviceToHost, st));
-        }
-        HIPCHK_TO(db->err, hipStreamSynchronize(st));
-        if ((size_t)*lTot.at(hl) != cnt) return lmap_fail(db, DRFE_ERR_STATE, "lmap gba device call: the moved points of a chunk are not the host's count");
-        if (cnt) {
-            std::memcpy(&R.item[b], lItem.at(hl), 4 * cnt);
-            std::memcpy(&R.world[3 * b], lWorld.at(hl), 12 * cnt);
-            std::memcpy(&R.kind[b], lKind.at(hl), cnt);
-        }
+        f.set(lTot, xCnt.at(dS) + (p1 - p0 + GBA_TILE - 1) / GBA_TILE, 1);
+        f.set(cnt, lItem, lKind);
+        f.set(3 * cnt, lWorld);
+        if (const int rc = call.fetch(f, drfe_launch_gba_points(L, call.st))) return rc;
+        if ((size_t)*f.at(lTot) != cnt) return lmap_fail(db, DRFE_ERR_STATE, "lmap gba device call: the moved points of a chunk are not the host's count");
+        f.get(lItem, R.item.data() + b);
+        f.get(lWorld, R.world.data() + 3 * b);
+        f.get(lKind, R.kind.data() + b);
         b += cnt;
     }
-    db->blk[drfe_lmap::GEO].assume_current();
-    db->blk[drfe_lmap::GBA].assume_current();
+    writes.done();
     return DRFE_OK;
 }
 
@@ -562,12 +540,6 @@ int drfe_lmap_gba_scratch(drfe_lmap* db, int64_t* out3)
     return DRFE_OK;
 }
 
-int drfe_lmap_gba_stats(drfe_lmap* db, int64_t* stats)
-{
-    if (!db || !stats) return DRFE_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(db->mu);
-    std::memcpy(stats, db->gbaStats, sizeof(db->gbaStats));
-    return DRFE_OK;
-}
+int drfe_lmap_gba_stats(drfe_lmap* db, int64_t* stats) { return lmap_stats(db, &drfe_lmap::gbaStats, stats); }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 /* lmap_internal.h — what lmap.cpp, lmap_conn.cpp, lmap_correct.cpp, lmap_cull.cpp, lmap_gba.cpp and lmap_recent.cpp hand to the store's
- * kernels (DESIGN.md sections 25 to 29 and 31). */
+ * kernels (DESIGN.md sections 25 to 29 and 31).  The host's sequence around these launches is lmap_call.h's. */
 #ifndef DRFE_LMAP_INTERNAL_H
 #define DRFE_LMAP_INTERNAL_H
 

@@ -5,8 +5,7 @@
  * surviving lists and the erased observations, and one commit applies them to the rows and the image - marking for upload what the
  * host entry changed, and nothing of what the device entry already stored in the resident image.  DESIGN.md section 31.  Parity
  * with a build of the reference's LocalMapping.cc is not pinned: it cannot be built here. */
-#include "lmap_store.h"
-#include "stage_layout.h"
+#include "lmap_call.h"
 
 #include <algorithm>
 #include <cstring>
@@ -219,11 +218,8 @@ RecentFit recent_fit(const drfe_lmap* db, int64_t n)
  * entries into the resident image; the commit mirrors them on the host. */
 int recent_device(drfe_lmap* db, const RecentPlan& P, const RecentFit& F, RecentWork& W, void* stream)
 {
-    drfe_ctx* c = db->ctx;
-    HIPCHK_TO(db->err, hipSetDevice(c->device));
-    hipStream_t st = stream ? (hipStream_t)stream : c->stream;
-    const int rc = lmap_upload(db, LMAP_NEED_RECENT, st);
-    if (rc) return rc;
+    LmapCall call{db, "lmap recent cull"};
+    if (const int rc = call.begin(LMAP_NEED_RECENT, stream)) return rc;
     const Image& G = db->img;
     const size_t n = (size_t)P.n, nP = G.mpHandle.size(), nL = G.mlHandle.size(), bound = (size_t)P.bound[n];
     const size_t room = (size_t)std::min<int64_t>((int64_t)n, (std::min<int64_t>(db->scratchBytes, F.whole) - F.fixed) / RECENT_ENTRY_BYTES);
@@ -243,14 +239,10 @@ int recent_device(drfe_lmap* db, const RecentPlan& P, const RecentFit& F, Recent
     const auto xClaimL = scr.add<int32_t>(nL);
     const auto xCnt = scr.add<int32_t>(room);
     const auto xGroup = scr.add<RecentGroup>(groups);
-    HIPCHK_TO(db->err, db->io.grow(in.bytes(), out.bytes()));
-    HIPCHK_TO(db->err, db->scratch.grow(scr.bytes()));
-    char* h = db->io.hin;
+    if (const int rc = call.stage(in.bytes(), out.bytes(), scr.bytes())) return rc;
+    const auto [h, d, dO, dS, r] = call.at;
     sItem.put(h, P.item.data());
     sHandle.put(h, P.handle.data());
-    const char* d = db->io.din;
-    char* dO = db->io.dout;
-    char* dS = db->scratch;
     RecentLaunch L{};
     L.I = db->dView;
     L.A = db->dCull;
@@ -273,30 +265,23 @@ int recent_device(drfe_lmap* db, const RecentPlan& P, const RecentFit& F, Recent
     L.erKf = oErKf.at(dO);
     L.erIdx = oErIdx.at(dO);
     L.head = oHead.at(dO);
-    hipError_t e = hipMemcpyAsync(db->io.din, h, in.bytes(), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && nP + nL) e = hipMemsetAsync(xClaimP.at(dS), 0x7f, xClaimL.off + xClaimL.bytes() - xClaimP.off, st);
-    if (e == hipSuccess) e = hipMemsetAsync(oHead.at(dO), 0, oHead.bytes(), st);
+    if (const int rc = call.send()) return rc;
+    hipError_t e = nP + nL ? hipMemsetAsync(xClaimP.at(dS), 0x7f, xClaimL.off + xClaimL.bytes() - xClaimP.off, call.st) : hipSuccess;
+    if (e == hipSuccess) e = hipMemsetAsync(oHead.at(dO), 0, oHead.bytes(), call.st);
+    LmapWrites writes(db->blk[drfe_lmap::ROWS]);   /* a chunk stores into the resident image */
     for (size_t e0 = 0; e0 < n && e == hipSuccess; e0 += room) {
         L.e0 = (int32_t)e0;
         L.e1 = (int32_t)std::min(n, e0 + room);
-        e = drfe_launch_recent_chunk(L, P.bound[(size_t)L.e1] - P.bound[e0], st);
+        e = drfe_launch_recent_chunk(L, P.bound[(size_t)L.e1] - P.bound[e0], call.st);
     }
-    if (e == hipSuccess) e = hipMemcpyAsync(db->io.hout, dO, out.bytes(), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        /* a chunk may have stored into the resident image: the host's rows go up again */
-        db->blk[drfe_lmap::ROWS].stale_all();
-        return lmap_fail(db, DRFE_ERR_HIP, std::string("lmap recent cull device call: ") + hipGetErrorString(e));
-    }
-    const char* r = db->io.hout;
+    if (const int rc = call.back(e)) return rc;
     const int32_t* head = oHead.at(r);
     const size_t keptP = (size_t)head[RECENT_HEAD_KEPT_P], keptL = (size_t)head[RECENT_HEAD_KEPT_L], culled = (size_t)head[RECENT_HEAD_CULLED],
                  erased = (size_t)head[RECENT_HEAD_ERASED];
     if (head[RECENT_HEAD_KEPT_P] < 0 || head[RECENT_HEAD_KEPT_L] < 0 || head[RECENT_HEAD_CULLED] < 0 || head[RECENT_HEAD_ERASED] < 0 ||
-        keptP > (size_t)P.nPts || keptL > n - (size_t)P.nPts || culled > n || erased > bound) {
-        db->blk[drfe_lmap::ROWS].stale_all();
+        keptP > (size_t)P.nPts || keptL > n - (size_t)P.nPts || culled > n || erased > bound)
         return lmap_fail(db, DRFE_ERR_STATE, "lmap recent cull device call: the device's totals do not fit the call");
-    }
+    writes.done();
     W.onDevice = true;
     W.action.assign(oAction.at(r), oAction.at(r) + n);
     W.kept[0].assign(oKeptP.at(r), oKeptP.at(r) + keptP);
@@ -640,13 +625,7 @@ int drfe_lmap_recent_cull_scratch(drfe_lmap* db, int64_t n_entries, int64_t* out
     return DRFE_OK;
 }
 
-int drfe_lmap_recent_cull_stats(drfe_lmap* db, int64_t* stats)
-{
-    if (!db || !stats) return DRFE_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(db->mu);
-    std::memcpy(stats, db->recStats, sizeof(db->recStats));
-    return DRFE_OK;
-}
+int drfe_lmap_recent_cull_stats(drfe_lmap* db, int64_t* stats) { return lmap_stats(db, &drfe_lmap::recStats, stats); }
 
 int drfe_lmap_recent_upload_bytes(drfe_lmap* db, int64_t* out1)
 {

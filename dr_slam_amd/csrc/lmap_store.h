@@ -4,7 +4,7 @@
  * lmap_conn.cpp (KeyFrame::UpdateConnections, section 26), lmap_correct.cpp (the Sim3 propagation of LoopClosing::CorrectLoop,
  * section 27), lmap_cull.cpp (LocalMapping::KeyFrameCulling with KeyFrame::SetBadFlag, section 28), lmap_gba.cpp (the map update
  * of LoopClosing::RunGlobalBundleAdjustment, section 29) and lmap_recent.cpp (LocalMapping::MapPointCulling and MapLineCulling,
- * section 31). */
+ * section 31).  What the device paths of those six share around their launches is lmap_call.h. */
 #ifndef DRFE_LMAP_STORE_H
 #define DRFE_LMAP_STORE_H
 

@@ -10,7 +10,7 @@ FLAGS := -O1 -g -std=c++17 -ffp-contract=off --offload-arch=gfx950 -Wall -I$(ROO
 
 all: conn_asan
 
-conn_asan: conn_asan.cpp $(SRC)/lmap_store.cpp $(SRC)/lmap.cpp $(SRC)/lmap_conn.cpp $(SRC)/lmap_store.h $(SRC)/resident_block.h $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/conn_core.h $(SRC)/lmap_core.h $(SRC)/lmap_internal.h $(SRC)/lmap_device.h
+conn_asan: conn_asan.cpp $(SRC)/lmap_store.cpp $(SRC)/lmap.cpp $(SRC)/lmap_conn.cpp $(SRC)/lmap_store.h $(SRC)/lmap_call.h $(SRC)/resident_block.h $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/conn_core.h $(SRC)/lmap_core.h $(SRC)/lmap_internal.h $(SRC)/lmap_device.h
 	$(HIPCC) $(FLAGS) -x hip conn_asan.cpp $(SRC)/lmap_store.cpp $(SRC)/lmap.cpp $(SRC)/lmap_conn.cpp $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip -o $@
 
 clean:

@@ -11,7 +11,7 @@ LDFLAGS := -L$(SRC) -ldrfe -Wl,-rpath,'$$ORIGIN/../../dr_slam_amd/csrc' -Wl,-rpa
 
 all: cull_asan
 
-cull_asan: cull_asan.cpp cull_caller.cpp $(SRC)/lmap_store.cpp $(SRC)/lmap.cpp $(SRC)/lmap_conn.cpp $(SRC)/lmap_cull.cpp $(SRC)/lmap_store.h $(SRC)/resident_block.h $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/cull_kernels.hip $(SRC)/cull_core.h $(SRC)/lmap_internal.h $(ROOT)/include/drfe_adaptor.hpp
+cull_asan: cull_asan.cpp cull_caller.cpp $(SRC)/lmap_store.cpp $(SRC)/lmap.cpp $(SRC)/lmap_conn.cpp $(SRC)/lmap_cull.cpp $(SRC)/lmap_store.h $(SRC)/lmap_call.h $(SRC)/resident_block.h $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/cull_kernels.hip $(SRC)/cull_core.h $(SRC)/lmap_internal.h $(ROOT)/include/drfe_adaptor.hpp
 	$(HIPCC) $(FLAGS) -x hip cull_asan.cpp $(SRC)/lmap_store.cpp $(SRC)/lmap.cpp $(SRC)/lmap_conn.cpp $(SRC)/lmap_cull.cpp $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/cull_kernels.hip -o $@ $(LDFLAGS)
 
 clean:

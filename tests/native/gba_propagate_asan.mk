@@ -15,7 +15,7 @@ KERNELS := $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/correct_kernel
 
 all: gba_propagate_asan
 
-gba_propagate_asan: gba_propagate_caller.cpp $(HOST) $(KERNELS) $(SRC)/lmap_store.h $(SRC)/resident_block.h $(SRC)/gba_core.h $(SRC)/lmap_internal.h $(ROOT)/include/drfe_adaptor.hpp
+gba_propagate_asan: gba_propagate_caller.cpp $(HOST) $(KERNELS) $(SRC)/lmap_store.h $(SRC)/lmap_call.h $(SRC)/resident_block.h $(SRC)/gba_core.h $(SRC)/lmap_internal.h $(ROOT)/include/drfe_adaptor.hpp
 	$(HIPCC) $(FLAGS) -x hip gba_propagate_caller.cpp $(HOST) $(KERNELS) -o $@ $(LDFLAGS)
 
 clean:

@@ -12,7 +12,7 @@ LDFLAGS := -L$(SRC) -ldrfe -Wl,-rpath,'$$ORIGIN/../../dr_slam_amd/csrc' -Wl,-rpa
 
 all: loop_correct_asan
 
-loop_correct_asan: loop_correct_caller.cpp $(SRC)/lmap_store.cpp $(SRC)/lmap.cpp $(SRC)/lmap_conn.cpp $(SRC)/lmap_correct.cpp $(SRC)/lmap_store.h $(SRC)/resident_block.h $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/correct_kernels.hip $(SRC)/correct_core.h $(SRC)/lmap_internal.h $(ROOT)/include/drfe_adaptor.hpp
+loop_correct_asan: loop_correct_caller.cpp $(SRC)/lmap_store.cpp $(SRC)/lmap.cpp $(SRC)/lmap_conn.cpp $(SRC)/lmap_correct.cpp $(SRC)/lmap_store.h $(SRC)/lmap_call.h $(SRC)/resident_block.h $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/correct_kernels.hip $(SRC)/correct_core.h $(SRC)/lmap_internal.h $(ROOT)/include/drfe_adaptor.hpp
 	$(HIPCC) $(FLAGS) -x hip loop_correct_caller.cpp $(SRC)/lmap_store.cpp $(SRC)/lmap.cpp $(SRC)/lmap_conn.cpp $(SRC)/lmap_correct.cpp $(SRC)/lmap_kernels.hip $(SRC)/conn_kernels.hip $(SRC)/correct_kernels.hip -o $@ $(LDFLAGS)
 
 clean:

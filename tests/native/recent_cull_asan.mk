@@ -15,7 +15,7 @@ KERNELS := $(SRC)/lmap_kernels.hip $(SRC)/cull_kernels.hip $(SRC)/recent_kernels
 
 all: recent_cull_asan
 
-recent_cull_asan: recent_cull_asan.cpp recent_cull_caller.cpp $(HOST) $(KERNELS) $(SRC)/lmap_store.h $(SRC)/resident_block.h $(SRC)/recent_core.h $(SRC)/lmap_internal.h $(ROOT)/include/drfe_adaptor.hpp
+recent_cull_asan: recent_cull_asan.cpp recent_cull_caller.cpp $(HOST) $(KERNELS) $(SRC)/lmap_store.h $(SRC)/lmap_call.h $(SRC)/resident_block.h $(SRC)/recent_core.h $(SRC)/lmap_internal.h $(ROOT)/include/drfe_adaptor.hpp
 	$(HIPCC) $(FLAGS) -x hip recent_cull_asan.cpp $(HOST) $(KERNELS) -o $@ $(LDFLAGS)
 
 clean:
