@@ -1,5 +1,5 @@
-/* lmap_internal.h — what lmap.cpp, lmap_conn.cpp, lmap_correct.cpp, lmap_cull.cpp, lmap_gba.cpp and lmap_recent.cpp hand to the store's
- * kernels (DESIGN.md sections 25 to 29 and 31).  The host's sequence around these launches is lmap_call.h's. */
+/* lmap_internal.h — what lmap.cpp, lmap_conn.cpp, lmap_correct.cpp, lmap_cull.cpp, lmap_gba.cpp, lmap_recent.cpp and lmap_fuse.cpp hand to the
+ * store's kernels (DESIGN.md sections 25 to 29, 31 and 32).  The host's sequence around these launches is lmap_call.h's. */
 #ifndef DRFE_LMAP_INTERNAL_H
 #define DRFE_LMAP_INTERNAL_H
 
@@ -10,6 +10,7 @@
 #include "cull_core.h"
 #include "gba_core.h"
 #include "recent_core.h"
+#include "fuse_core.h"
 
 /* threads of a workgroup: frame points and key-frame slots go across them in the vote, the entries of a match row in the gather */
 #define LMAP_THREADS 256
@@ -276,6 +277,64 @@ struct RecentLaunch {
 /* the claims, the verdicts, their prefix, the packed outputs with the bad flags, the erasure: in stream order.  eraseBound is the
  * host's bound on the observations the chunk erases. */
 hipError_t drfe_launch_recent_chunk(const RecentLaunch& L, int64_t eraseBound, hipStream_t s);
+
+/* ---- the fuse commit (fuse_kernels.hip) ---- */
+/* candidates of one workgroup of the live pre-pass, a lane each, and the threads of the one workgroup that walks */
+#define FUSE_TILE LMAP_THREADS
+/* entries of the walk's append log: the observations the call added to its items so far, (item * 2 + kind, key-frame slot, index) */
+#define FUSE_LOG_ENTRIES 8192
+/* records the walk holds: (key-frame slot, index, moved) of every former observation of every loser */
+#define FUSE_REC_ENTRIES (1 << 18)
+/* stored key frames the winner's observer bitmap in LDS holds (8 KiB) */
+#define FUSE_MAX_KFS 65536
+/* bytes of scratch per candidate tile: its packed live candidates and their count */
+#define FUSE_TILE_BYTES (4 * FUSE_TILE + 4)
+/* bytes of scratch every call takes besides the per-item words: the log, the records, alignment of the sections */
+#define FUSE_FIXED_BYTES (12 * FUSE_LOG_ENTRIES + 9 * FUSE_REC_ENTRIES + 1024)
+
+struct FuseStep {
+    int32_t kf, kind, form, n;
+    int32_t candOff;               /* its candidates in the flat arrays */
+    int32_t tile0, tile1;          /* its tiles: a step starts a tile of its own */
+    int32_t pad;
+};
+
+/* head words of a call: whether the walk stopped early and where, and its totals */
+enum { FUSE_HEAD_STOPPED = 0, FUSE_HEAD_STEP, FUSE_HEAD_PASS, FUSE_HEAD_CAND, FUSE_HEAD_FUSED, FUSE_HEAD_REPL, FUSE_HEAD_REC,
+       FUSE_HEAD_LOG, FUSE_HEAD_WORDS };
+
+struct FuseLaunch {
+    LmapImage I;                   /* resident; the bad flags and the two kinds of match rows are written */
+    CullImage A;                   /* resident: nObs of the points is written */
+    RecentImage R;                 /* resident: the counters and the lines' nObs are written */
+    int32_t nSteps, nTiles;
+    int32_t logCap, recCap;
+    /* staged */
+    const FuseStep* step;          /* nSteps */
+    const int32_t* tileStep;       /* nTiles: the step of each tile */
+    const int32_t* cand;           /* item slots, -1 = null */
+    const int32_t* best;
+    /* scratch */
+    int32_t* packed;               /* nTiles x FUSE_TILE: the live candidates of each tile, in order */
+    int32_t* tileCnt;              /* nTiles */
+    int32_t* snap;                 /* nP, zero before the launch: the LOOP step (+ 1) whose row named the point at its start */
+    int32_t* clearedAt[2];         /* nP, nL, zero before the launch: 0, or 1 + the log length when a Replace last cleared the item */
+    int32_t* log;                  /* 3 x logCap */
+    int32_t* recKf;                /* recCap */
+    int32_t* recIdx;
+    uint8_t* recMoved;
+    /* out */
+    int32_t* head;                 /* FUSE_HEAD_WORDS */
+    uint8_t* action;               /* per candidate */
+    int32_t* rep;                  /* per candidate: the recorded occupant of a LOOP step (slot), else -1 */
+    int32_t* nFused;               /* per step */
+    int32_t* rKind;                /* per Replace, in execution order */
+    int32_t* rLoser;
+    int32_t* rWinner;
+    int32_t* rOff;                 /* one more: offsets into the records */
+};
+/* the live pre-pass over every tile, then the walk: in stream order */
+hipError_t drfe_launch_fuse(const FuseLaunch& L, hipStream_t s);
 
 /* ---- the map update of LoopClosing::RunGlobalBundleAdjustment (gba_kernels.hip) ---- */
 /* point slots of one workgroup of the point launches, a lane each */

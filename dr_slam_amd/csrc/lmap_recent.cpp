@@ -13,10 +13,8 @@
 
 using namespace lmap_store;
 
-namespace {
-
 /* the attributes by slot, after the image and the culling attributes */
-int build_recent(drfe_lmap* db)
+int lmap_build_recent(drfe_lmap* db)
 {
     const int rc = lmap_build_cull(db);
     if (rc) return rc;
@@ -82,6 +80,8 @@ int build_recent(drfe_lmap* db)
     return DRFE_OK;
 }
 
+namespace {
+
 struct KindView {
     const std::vector<uint8_t>*bad, *has;
     const std::vector<int32_t>*handle, *found, *visible, *nObs, *obsOff, *obs, *obsIdx, *rowOff;
@@ -124,7 +124,7 @@ int recent_plan(drfe_lmap* db, int64_t current, int32_t monocular, const drfe_lm
     for (int k = 0; k < 2; k++)
         if (lists[k]->n > DRFE_LMAP_RECENT_MAX_ENTRIES)
             return lmap_fail(db, DRFE_ERR_INVALID, "lmap_recent_cull: more than DRFE_LMAP_RECENT_MAX_ENTRIES entries in a list");
-    const int rc = build_recent(db);
+    const int rc = lmap_build_recent(db);
     if (rc) return rc;
     const Image& G = db->img;
     P.current = current;

@@ -414,6 +414,7 @@ int drfe_lmap_set_points(drfe_lmap* db, int32_t count, const int32_t* handles, c
         MpRow& P = db->mp[handles[i]];
         P.bad = bad[i] ? 1 : 0;
         P.obs.assign(obs + obs_offsets[i], obs + obs_offsets[i + 1]);
+        db->mpReplaced.erase(handles[i]);
     }
     db->imgDirty = true;
     return DRFE_OK;
@@ -426,7 +427,10 @@ int drfe_lmap_set_lines(drfe_lmap* db, int32_t count, const int32_t* handles, co
     if (count < 0 || (count > 0 && (!handles || !bad))) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_lines: invalid argument");
     for (int i = 0; i < count; i++)
         if (handles[i] < 0) return lmap_fail(db, DRFE_ERR_INVALID, "lmap_set_lines: a negative handle");
-    for (int i = 0; i < count; i++) db->ml[handles[i]] = bad[i] ? 1 : 0;
+    for (int i = 0; i < count; i++) {
+        db->ml[handles[i]] = bad[i] ? 1 : 0;
+        db->mlReplaced.erase(handles[i]);
+    }
     if (count) db->imgDirty = true;
     return DRFE_OK;
 }
@@ -466,12 +470,14 @@ int drfe_lmap_remove(drfe_lmap* db, int kind, int32_t handle)
             db->mpCull.erase(handle);
             db->mpGba.erase(handle);
             db->mpRec.erase(handle);
+            db->mpReplaced.erase(handle);
         }
     } else if (kind == DRFE_LMAP_LINE) {
         gone = db->ml.erase(handle);
         if (gone) {
             db->mlRec.erase(handle);
             db->mlObs.erase(handle);
+            db->mlReplaced.erase(handle);
         }
     } else {
         return lmap_fail(db, DRFE_ERR_INVALID, "lmap_remove: unknown kind");

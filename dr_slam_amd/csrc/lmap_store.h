@@ -3,8 +3,9 @@
  * its lifecycle, setters, image and upload; its entries are in lmap.cpp (Tracking::UpdateLocalMap),
  * lmap_conn.cpp (KeyFrame::UpdateConnections, section 26), lmap_correct.cpp (the Sim3 propagation of LoopClosing::CorrectLoop,
  * section 27), lmap_cull.cpp (LocalMapping::KeyFrameCulling with KeyFrame::SetBadFlag, section 28), lmap_gba.cpp (the map update
- * of LoopClosing::RunGlobalBundleAdjustment, section 29) and lmap_recent.cpp (LocalMapping::MapPointCulling and MapLineCulling,
- * section 31).  What the device paths of those six share around their launches is lmap_call.h. */
+ * of LoopClosing::RunGlobalBundleAdjustment, section 29), lmap_recent.cpp (LocalMapping::MapPointCulling and MapLineCulling,
+ * section 31) and lmap_fuse.cpp (the fuse commit with MapPoint::Replace, section 32).  What the device paths of those seven share
+ * around their launches is lmap_call.h. */
 #ifndef DRFE_LMAP_STORE_H
 #define DRFE_LMAP_STORE_H
 
@@ -174,6 +175,9 @@ struct drfe_lmap {
     bool recDirty = true;              /* that image lacks an edit of the rows, of the culling attributes or of these */
     bool recCheck = false;             /* the line observations changed since the image looked for dangling ones */
     int64_t recStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    /* mpReplaced of the fuse commit, by handle: an item without an entry has none.  Host state only. */
+    std::unordered_map<int32_t, int32_t> mpReplaced, mlReplaced;
+    int64_t fuseStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     /* the host walk's stamps, kept between calls: an item is stamped for the query whose serial it holds */
     std::vector<int32_t> stampP, stampL, inP, inL;
     int32_t serial = 0;
@@ -209,5 +213,7 @@ bool lmap_offsets_ok(const int32_t* off, int n);
 int lmap_build_geo(drfe_lmap* db);
 /* lmap_cull.cpp's, for lmap_recent.cpp: the culling attributes by slot, rebuilt when stale */
 int lmap_build_cull(drfe_lmap* db);
+/* lmap_recent.cpp's, for lmap_fuse.cpp: the recent-list attributes by slot, rebuilt when stale */
+int lmap_build_recent(drfe_lmap* db);
 
 #endif

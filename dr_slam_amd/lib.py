@@ -84,6 +84,8 @@ SYMBOLS = (
     "drfe_lmap_set_recent_attributes", "drfe_lmap_get_recent_attributes", "drfe_lmap_recent_increase", "drfe_lmap_recent_cull_host",
     "drfe_lmap_recent_cull_device", "drfe_lmap_recent_cull_batch", "drfe_lmap_recent_cull_limits", "drfe_lmap_recent_cull_scratch",
     "drfe_lmap_recent_cull_stats", "drfe_lmap_recent_upload_bytes",
+    "drfe_lmap_fuse_host", "drfe_lmap_fuse_device", "drfe_lmap_fuse_batch", "drfe_lmap_fuse_limits", "drfe_lmap_fuse_scratch",
+    "drfe_lmap_fuse_stats", "drfe_lmap_get_replaced", "drfe_lmap_get_match_row", "drfe_lmap_get_observers",
 )
 
 FAST_CELL_DTYPE = np.dtype([(n, "<i4") for n in ("level", "x0", "y0", "ww", "wh", "offX", "offY", "cellIdx", "ncp", "rpl", "nrb",
@@ -410,6 +412,25 @@ class LmapRecentList(C.Structure):
         "action", "n_kept", "kept", "n_culled", "culled", "erased_offsets", "erased_kf", "erased_index")]   # drfe_lmap_recent_list
 
 
+LMAP_FUSE_STATS = ("calls", "candidates", "device_calls", "added", "replaced", "moved", "erased", "handed_back")
+LMAP_FUSE_LIMITS = ("tile", "wavefront", "log_entries", "record_entries", "max_kfs", "tile_bytes", "max_candidates", "device_from")
+FUSE_NEIGHBOURS, FUSE_LOOP, FUSE_MATCHED = range(3)                                   # drfe_lmap_fuse_step.form
+(FUSE_NONE, FUSE_SKIPPED, FUSE_ADDED, FUSE_ROW_ONLY, FUSE_OCCUPANT_BAD, FUSE_CANDIDATE_REPLACED, FUSE_OCCUPANT_REPLACED, FUSE_SELF,
+ FUSE_RECORDED) = range(9)                                                            # drfe_lmap_fuse_step.action
+
+
+class LmapFuseStep(C.Structure):
+    _fields_ = [("keyframe", C.c_int32), ("kind", C.c_int32), ("form", C.c_int32), ("n", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "candidates", "best_idx", "action", "n_fused", "replace")]                   # drfe_lmap_fuse_step
+
+
+class LmapFuseCall(C.Structure):
+    _fields_ = [("n_steps", C.c_int32), ("steps", C.c_void_p), ("replaced_capacity", C.c_int32), ("record_capacity", C.c_int32),
+                ("touched_capacity", C.c_int32)] + [(k, C.c_void_p) for k in (
+        "n_replaced", "replaced_kind", "loser", "winner", "record_offsets", "record_kf", "record_index", "record_moved",
+        "n_touched", "touched_points", "touched_lines")]                             # drfe_lmap_fuse_call
+
+
 class InitProblems(C.Structure):
     _fields_ = [("n", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_void_p) for k in (
         "K", "sigma", "max_iterations", "seed", "key1_offsets", "key2_offsets", "keys1", "keys2",
@@ -729,6 +750,15 @@ def load() -> C.CDLL:
     L.drfe_lmap_recent_cull_scratch.argtypes = [vp, C.c_int64, vp]
     L.drfe_lmap_recent_cull_stats.argtypes = [vp, vp]
     L.drfe_lmap_recent_upload_bytes.argtypes = [vp, vp]
+    L.drfe_lmap_fuse_host.argtypes = [vp, vp]
+    L.drfe_lmap_fuse_device.argtypes = [vp, vp, vp]
+    L.drfe_lmap_fuse_batch.argtypes = [vp, vp, vp]
+    L.drfe_lmap_fuse_limits.argtypes = [vp]
+    L.drfe_lmap_fuse_scratch.argtypes = [vp, C.c_int64, C.c_int64, vp]
+    L.drfe_lmap_fuse_stats.argtypes = [vp, vp]
+    L.drfe_lmap_get_replaced.argtypes = [vp, i32, i32, vp, vp]
+    L.drfe_lmap_get_match_row.argtypes = [vp, i32, i32, i32, vp, vp]
+    L.drfe_lmap_get_observers.argtypes = [vp, i32, i32, i32, vp, vp, vp]
     L.drfe_pnp_stats.argtypes = [vp, vp]
     L.drfe_lines_is_good_batch.argtypes = [vp, vp, vp, vp]
     L.drfe_line3d_chunk_frames.argtypes = [i32]
@@ -2346,6 +2376,102 @@ class LocalMap:
                              erased=[np.stack([a["erased_kf"][o[i]:o[i + 1]], a["erased_index"][o[i]:o[i + 1]]], axis=1)
                                      for i in range(nc)])
         return res
+
+    # ---- the fuse commit on the store ----
+
+    @staticmethod
+    def fuse_limits():
+        out = np.zeros(8, np.int32)
+        rc = load().drfe_lmap_fuse_limits(_p(out))
+        if rc != 0:
+            raise DrfeError(f"drfe_lmap_fuse_limits failed ({rc})")
+        return dict(zip(LMAP_FUSE_LIMITS, (int(v) for v in out)))
+
+    def fuse_stats(self):
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_lmap_fuse_stats(self.h, _p(st)), "drfe_lmap_fuse_stats")
+        return dict(zip(LMAP_FUSE_STATS, (int(v) for v in st)))
+
+    def fuse_scratch(self, n_candidates, n_steps):
+        """bytes of device scratch a fuse call takes at most: (the call, the same, the part every call takes)"""
+        out = np.zeros(3, np.int64)
+        self._chk(self.L.drfe_lmap_fuse_scratch(self.h, int(n_candidates), int(n_steps), _p(out)), "drfe_lmap_fuse_scratch")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def get_replaced(self, kind, handles):
+        hs = np.ascontiguousarray(handles, np.int32)
+        out = np.zeros(max(1, len(hs)), np.int32)
+        self._chk(self.L.drfe_lmap_get_replaced(self.h, int(kind), len(hs), _p(hs), _p(out)), "drfe_lmap_get_replaced")
+        return out[:len(hs)].copy()
+
+    def get_match_row(self, kind, keyframe):
+        n = np.zeros(1, np.int32)
+        rc = self.L.drfe_lmap_get_match_row(self.h, int(kind), int(keyframe), 0, _p(n), None)
+        if rc not in (0, ERR_CAPACITY):
+            self._chk(rc, "drfe_lmap_get_match_row")
+        out = np.zeros(max(1, int(n[0])), np.int32)
+        self._chk(self.L.drfe_lmap_get_match_row(self.h, int(kind), int(keyframe), len(out), _p(n), _p(out)), "drfe_lmap_get_match_row")
+        return out[:int(n[0])].copy()
+
+    def get_observers(self, kind, handle):
+        """(bad, the observing key frames in stored order) of a map point or map line"""
+        n, bad = np.zeros(1, np.int32), np.zeros(1, np.uint8)
+        rc = self.L.drfe_lmap_get_observers(self.h, int(kind), int(handle), 0, _p(bad), _p(n), None)
+        if rc not in (0, ERR_CAPACITY):
+            self._chk(rc, "drfe_lmap_get_observers")
+        out = np.zeros(max(1, int(n[0])), np.int32)
+        self._chk(self.L.drfe_lmap_get_observers(self.h, int(kind), int(handle), len(out), _p(bad), _p(n), _p(out)),
+                  "drfe_lmap_get_observers")
+        return int(bad[0]), out[:int(n[0])].copy()
+
+    def fuse(self, steps, mode="batch", capacity=None):
+        """The fuse commit: steps are dicts with keyframe, kind (LMAP_POINT / LMAP_LINE), form (FUSE_NEIGHBOURS / FUSE_LOOP /
+        FUSE_MATCHED), candidates (handles, -1 = null) and best_idx (not for FUSE_MATCHED).  Returns a dict: steps (per step a dict
+        of action [n], n_fused and replace [n]), replaced (a list of (kind, loser, winner, records [m, 3] of (key frame, index,
+        moved) in stored order)), touched_points, touched_lines.  capacity: (replacements, records, touched per kind); default:
+        the documented bounds for the first and third and records grown until the call fits (a call that does not fit changes
+        nothing)."""
+        n = len(steps)
+        S = (LmapFuseStep * max(1, n))()
+        keep = []
+        live = 0
+        for i, st in enumerate(steps):
+            cand = np.ascontiguousarray(st["candidates"], np.int32)
+            m = len(cand)
+            best = None if st["form"] == FUSE_MATCHED and "best_idx" not in st else np.ascontiguousarray(st["best_idx"], np.int32)
+            a = {"cand": cand, "best": best, "action": np.zeros(max(1, m), np.uint8), "n_fused": np.zeros(1, np.int32),
+                 "replace": np.full(max(1, m), -1, np.int32)}
+            keep.append(a)
+            live += int(np.count_nonzero(cand >= 0))
+            S[i] = LmapFuseStep(int(st["keyframe"]), int(st["kind"]), int(st["form"]), m, _p(cand), None if best is None else _p(best),
+                                _p(a["action"]), _p(a["n_fused"]), _p(a["replace"]))
+        grow = capacity is None
+        cr, crec, ct = (live, 1 << 12, live) if grow else (int(c) for c in capacity)
+        fn = getattr(self.L, f"drfe_lmap_fuse_{mode}")
+        while True:
+            r = {"n_replaced": np.zeros(1, np.int32), "replaced_kind": np.zeros(max(1, cr), np.int32),
+                 "loser": np.zeros(max(1, cr), np.int32), "winner": np.zeros(max(1, cr), np.int32),
+                 "record_offsets": np.zeros(cr + 1, np.int32), "record_kf": np.zeros(max(1, crec), np.int32),
+                 "record_index": np.zeros(max(1, crec), np.int32), "record_moved": np.zeros(max(1, crec), np.uint8),
+                 "n_touched": np.zeros(2, np.int32), "touched_points": np.zeros(max(1, ct), np.int32),
+                 "touched_lines": np.zeros(max(1, ct), np.int32)}
+            call = LmapFuseCall(n, C.cast(S, C.c_void_p), cr, crec, ct, *[_p(r[k]) for k in (
+                "n_replaced", "replaced_kind", "loser", "winner", "record_offsets", "record_kf", "record_index", "record_moved",
+                "n_touched", "touched_points", "touched_lines")])
+            args = (self.h, C.byref(call)) + (() if mode == "host" else (None,))
+            rc = fn(*args)
+            if not (grow and rc == ERR_CAPACITY and crec < (1 << 28) and b"record_capacity" in self.L.drfe_lmap_last_error(self.h)):
+                break
+            crec *= 8
+        self._chk(rc, f"drfe_lmap_fuse_{mode}")
+        nr, o = int(r["n_replaced"][0]), r["record_offsets"]
+        return {"steps": [dict(action=a["action"][:len(a["cand"])].copy(), n_fused=int(a["n_fused"][0]),
+                               replace=a["replace"][:len(a["cand"])].copy()) for a in keep],
+                "replaced": [(int(r["replaced_kind"][i]), int(r["loser"][i]), int(r["winner"][i]),
+                              np.stack([r["record_kf"][o[i]:o[i + 1]], r["record_index"][o[i]:o[i + 1]],
+                                        r["record_moved"][o[i]:o[i + 1]].astype(np.int32)], axis=1)) for i in range(nr)],
+                "touched_points": r["touched_points"][:int(r["n_touched"][0])].copy(),
+                "touched_lines": r["touched_lines"][:int(r["n_touched"][1])].copy()}
 
     # ---- the map update of LoopClosing::RunGlobalBundleAdjustment on the store (DESIGN.md section 29) ----
 

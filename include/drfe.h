@@ -2276,6 +2276,121 @@ int drfe_lmap_recent_cull_stats(drfe_lmap* db, int64_t* stats /* 8 */);
 /* host-to-device bytes of the recent-list block since the store was created (the sixth block, next to drfe_lmap_upload_bytes) */
 int drfe_lmap_recent_upload_bytes(drfe_lmap* db, int64_t* out1);
 
+/* The fuse commit on the same store: the loop that applies a fusion search - ORBmatcher::Fuse (src/ORBmatcher.cc:845-976, and the
+ * Sim3 form :1001-1101 with SearchAndFuse's loop, src/LoopClosing.cc:650-657), LSDmatcher::Fuse (src/LSDmatcher.cpp:897-1012), the
+ * matched-point loop of CorrectLoop (src/LoopClosing.cc:566-581) - with MapPoint::Replace / MapLine::Replace
+ * (src/MapPoint.cc:223-261, src/MapLine.cpp:178-214), AddObservation, KeyFrame::AddMapPoint, ReplaceMapPointMatch and
+ * EraseMapPointMatch.  DESIGN.md section 32.  Parity with a build of the reference's ORBmatcher.cc, LSDmatcher.cpp, MapPoint.cc,
+ * MapLine.cpp and LoopClosing.cc is not pinned.
+ *
+ * A call is an ordered list of steps, run one after another on the evolving store.  A step names a key frame, a kind
+ * (DRFE_LMAP_POINT or DRFE_LMAP_LINE), a form, its candidates as handles in the caller's order (-1 = a null pointer) and best_idx per
+ * candidate: the search's answer with the bestDist <= TH_LOW gate applied, any negative value = none.  It reads and writes the
+ * match rows, the bad flags, the observations with mit->second and nObs (the culling attributes of a point, the recent-list state
+ * of a line), mnFound / mnVisible and the per-item `replaced` field below.
+ *
+ * Per candidate one action byte.  0 comes first in every form: a null candidate, or no answer (in MATCHED only the null candidate).
+ *
+ * NEIGHBOURS, per candidate in order: a candidate that is bad, or - a point only: LSDmatcher::Fuse does not ask - that has the
+ * key frame among its observations at its turn, is skipped (1).  The occupant row[k][best_idx] is read now.  Null:
+ * AddObservation(k, best_idx), then row[k][best_idx] = candidate (2; 3 for a line that already observed the key frame, whose
+ * AddObservation is a no-op).  Bad: nothing, and the candidate still counts (4).  The candidate itself: Replace returns at once (7).  Otherwise, on the
+ * stored counters, occupant.nObs > candidate.nObs ? candidate.Replace(occupant) (5) : occupant.Replace(candidate) (6): on a tie
+ * the occupant loses.  n_fused counts 2, 3, 4, 5, 6 and 7.
+ *
+ * LOOP (points, no null candidate): the skip set is taken once at the start of the step - bad then, or among the non-null entries
+ * of row[k] then (1).  Pass 1 in order: occupant not null and not bad: recorded in replace[i] (8); bad: 4; null:
+ * AddObservation and AddMapPoint (2, or 3 when the key frame already was an observer and only the row entry is written).  n_fused
+ * counts 2, 3, 4 and 8.  Pass 2 in order: replace[i].Replace(candidate[i]), whatever the two are by then - an occupant recorded
+ * twice is replaced twice, the second time with no observations left, and its found and visible counts are added again; the
+ * candidate may have gone bad; replace[i] == candidate[i] returns at once.
+ *
+ * MATCHED (points): candidate i stands for row index i, best_idx is not read, n must be the row's length.  A non-null candidate
+ * with an occupant: occupant.Replace(candidate), without a bad test or a comparison (6; 7 for the candidate itself); without one:
+ * AddMapPoint, then AddObservation (2, or 3).  n_fused counts 2, 3, 6 and 7.
+ *
+ * Replace(loser, winner): the loser goes bad, its observations are taken and cleared, replaced[loser] = winner.  Per former
+ * observation (kf, idx) in stored order: kf not among the winner's observers at that moment - row[kf][idx] = winner and the winner
+ * gains (kf, idx) (a record with moved 1); else row[kf][idx] = null (moved 0); either is stored whatever stands in the entry.
+ * The winner's mnFound / mnVisible grow by the loser's, with wrap-around.  The loser's nObs, counters and reference key frame
+ * stay; a bad winner is not tested.  A gained observation adds 2 to a point's nObs when the stereo flag of (kf, idx) is set, else 1,
+ * and 1 to a line's; it enters the stored list in front of the first stored observer of greater rank, at the end if there is none.
+ * Map::EraseMapPoint, ComputeDistinctiveDescriptors and UpdateNormalAndDepth stay with the caller: `touched` names every winner
+ * and every item that gained an observation, once each, in the order first met. */
+enum { DRFE_LMAP_FUSE_NEIGHBOURS = 0, DRFE_LMAP_FUSE_LOOP = 1, DRFE_LMAP_FUSE_MATCHED = 2 };
+enum { DRFE_LMAP_FUSE_NONE = 0, DRFE_LMAP_FUSE_SKIPPED = 1, DRFE_LMAP_FUSE_ADDED = 2, DRFE_LMAP_FUSE_ROW_ONLY = 3,
+       DRFE_LMAP_FUSE_OCCUPANT_BAD = 4, DRFE_LMAP_FUSE_CANDIDATE_REPLACED = 5, DRFE_LMAP_FUSE_OCCUPANT_REPLACED = 6,
+       DRFE_LMAP_FUSE_SELF = 7, DRFE_LMAP_FUSE_RECORDED = 8 };
+enum { DRFE_LMAP_FUSE_MAX_CANDIDATES = 1 << 22 };   /* of all steps of a call */
+typedef struct drfe_lmap_fuse_step {
+    int32_t keyframe;                 /* handle */
+    int32_t kind;                     /* DRFE_LMAP_POINT or DRFE_LMAP_LINE */
+    int32_t form;                     /* DRFE_LMAP_FUSE_... */
+    int32_t n;                        /* candidates */
+    const int32_t* candidates;        /* n handles, -1 = null */
+    const int32_t* best_idx;          /* n; may be NULL in MATCHED */
+    uint8_t* action;                  /* n */
+    int32_t* n_fused;                 /* 1 */
+    int32_t* replace;                 /* LOOP: n handles, -1 = none; may be NULL in the other forms */
+} drfe_lmap_fuse_step;
+typedef struct drfe_lmap_fuse_call {
+    int32_t n_steps;
+    drfe_lmap_fuse_step* steps;
+    int32_t replaced_capacity;        /* Replace calls that change something: the candidates that are not null and have an answer always suffice */
+    int32_t record_capacity;          /* their (kf, idx) records: replaced_capacity x the stored key frames always suffices */
+    int32_t touched_capacity;         /* per kind: the same count of candidates of that kind always suffices */
+    int32_t* n_replaced;              /* 1 */
+    int32_t* replaced_kind;           /* in execution order */
+    int32_t* loser;                   /* handles */
+    int32_t* winner;
+    int32_t* record_offsets;          /* replaced_capacity + 1, from 0 */
+    int32_t* record_kf;               /* the loser's former observations in stored order: key-frame handle */
+    int32_t* record_index;            /* index into its row */
+    uint8_t* record_moved;            /* 1 = the entry names the winner and the winner gained it, 0 = the entry is null */
+    int32_t* n_touched;               /* 2: points, lines */
+    int32_t* touched_points;          /* handles */
+    int32_t* touched_lines;
+} drfe_lmap_fuse_call;
+/* candidates of all steps from which drfe_lmap_fuse_batch of a store with a context uses the device.  Measured (DESIGN.md
+ * section 32, profiles/fuse_timing.jsonl) the device entry loses to the host entry in every one of twelve shapes (0.08x to 0.70x),
+ * so there is no such number: the constant stands above the longest call and _batch runs on the host; _device is there to be
+ * called. */
+enum { DRFE_LMAP_FUSE_DEVICE_FROM = DRFE_LMAP_FUSE_MAX_CANDIDATES + 1 };
+/* _host always runs on the host, _device always on the device (DRFE_ERR_STATE without a context; DRFE_ERR_CAPACITY when the
+ * configured scratch does not hold the call or the store has more key frames than the walk's observer bitmap), _batch on the
+ * device from DRFE_LMAP_FUSE_DEVICE_FROM candidates when the call fits.  All three return the same bytes and leave the same
+ * store.  Refused, and nothing changes: an unknown key frame or item handle, an unknown kind or form, more than
+ * DRFE_LMAP_FUSE_MAX_CANDIDATES candidates (DRFE_ERR_INVALID); with DRFE_ERR_STATE and the name of the item a line in LOOP or
+ * MATCHED, a null candidate in LOOP, a MATCHED list whose length is not the row's, a best_idx beyond row[k], a point step on a
+ * key frame without culling attributes that fit its row (the stereo flags), a point that can take part - a candidate or an entry
+ * of row[k] that a candidate points at, unless it is bad in a form that never touches a bad item - without culling attributes
+ * that fit its observations or without recent-list counters, a line that can take part without its recent-list state, an
+ * obs_index of either outside its observer's row; DRFE_ERR_CAPACITY when a capacity is too small.  The device entry commits the
+ * match rows, the bad flags, nObs and the counters into the resident blocks itself: after it only the observations with their
+ * offsets and indices travel (drfe_lmap_upload_bytes: no match rows, no graph). */
+int drfe_lmap_fuse_host(drfe_lmap* db, drfe_lmap_fuse_call* call);
+int drfe_lmap_fuse_device(drfe_lmap* db, drfe_lmap_fuse_call* call, void* stream);
+int drfe_lmap_fuse_batch(drfe_lmap* db, drfe_lmap_fuse_call* call, void* stream);
+/* out[0] candidates of one workgroup of the live pre-pass = threads of the walk's workgroup, [1] lanes of a wavefront, [2] entries
+ * of the walk's append log, [3] records the walk holds, [4] key frames its observer bitmap holds, [5] bytes of scratch per
+ * candidate tile, [6] DRFE_LMAP_FUSE_MAX_CANDIDATES, [7] DRFE_LMAP_FUSE_DEVICE_FROM */
+int drfe_lmap_fuse_limits(int32_t* out8);
+/* the scratch a device call of n_candidates in n_steps takes at most (a step starts a tile of its own): out[0] bytes, [1] the same
+ * (the walk is one launch: there is no smaller chunk), [2] the part that does not depend on the call */
+int drfe_lmap_fuse_scratch(drfe_lmap* db, int64_t n_candidates, int64_t n_steps, int64_t* out3);
+/* Counters since the store was created: stats[0] calls, [1] candidates, [2] calls run on the device, [3] observations added to an
+ * empty entry, [4] Replace calls that changed something, [5] records moved, [6] records erased, [7] device calls whose walk handed
+ * the rest of the call back to the host (its append log or its record room was full). */
+int drfe_lmap_fuse_stats(drfe_lmap* db, int64_t* stats /* 8 */);
+/* mpReplaced by handle, -1 until a Replace sets it; drfe_lmap_set_points / set_lines of a handle resets it, drfe_lmap_remove
+ * drops it.  Host state only.  An unknown handle: DRFE_ERR_INVALID. */
+int drfe_lmap_get_replaced(drfe_lmap* db, int kind, int32_t count, const int32_t* handles, int32_t* out);
+/* What the store holds by handle, for a caller that compares it with its objects: the match row of a key frame (kind
+ * DRFE_LMAP_POINT or DRFE_LMAP_LINE; *n its length, DRFE_ERR_CAPACITY when capacity is smaller), and the bad flag and observing
+ * key frames of an item in stored order (a line without recent-list state has none). */
+int drfe_lmap_get_match_row(drfe_lmap* db, int kind, int32_t keyframe, int32_t capacity, int32_t* n, int32_t* out);
+int drfe_lmap_get_observers(drfe_lmap* db, int kind, int32_t handle, int32_t capacity, uint8_t* bad, int32_t* n, int32_t* out);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

@@ -657,8 +657,10 @@ public:
     /* ---- src/ORBmatcher.cc:829-985 - LocalMapping::SearchInNeighbors.  The search of every point on the device; the loop that
      * applies it runs here in the reference's order, re-reading isBad() / IsInKeyFrame() / GetMapPoint() at each step exactly where the
      * reference reads them: an earlier Replace or AddMapPoint of this very loop changes what a later point meets (:845, :957) ---- */
-    template <class KeyFrameT, class MapPointT>
-    int Fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const float th = 3.0)
+    /* tracker: a LocalMapTracker (below) that keeps a store of this map; it is told the gated answers before the loop runs, and
+     * its store commits the same fusion (LocalMapTracker::FuseStore) */
+    template <class KeyFrameT, class MapPointT, class TrackerT = void>
+    int Fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const float th = 3.0, TrackerT* tracker = nullptr)
     {
         MatcherDevice& D = Device();
         const int slot = D.Resident(*pKF);
@@ -675,6 +677,13 @@ public:
         const auto Tcw = pKF->GetPose();
         drfe_detail::check(drfe_fuse_search(D.ctx(), slot, drfe_detail::f32(Tcw), fp.data(), descs.data(), skip.data(), n, th, bestIdx.data(), bestDist.data()), D.ctx(),
                            "drfe_fuse_search");
+        if constexpr (!std::is_void<TrackerT>::value)
+            if (tracker) {
+                std::vector<int32_t> gated(bestIdx);
+                for (int i = 0; i < n; i++)
+                    if (bestDist[(size_t)i] > TH_LOW) gated[(size_t)i] = -1;
+                tracker->FuseStore(pKF, vpMapPoints, gated.data(), DRFE_LMAP_POINT, DRFE_LMAP_FUSE_NEIGHBOURS, nullptr);
+            }
         int nFused = 0;
         for (int i = 0; i < n; i++) {
             MapPointT* pMP = vpMapPoints[(size_t)i];
@@ -1234,8 +1243,8 @@ public:
      * in the reference's order and re-reads isBad() / GetMapLine() at each step: an earlier Replace or AddMapLine of this very loop
      * changes what a later line meets (:907, :995).  A predicted level outside the pyramid (the reference reads mvScaleFactors out of
      * bounds there) fuses nothing. ---- */
-    template <class KeyFrameT, class MapLineT>
-    int Fuse(KeyFrameT* pKF, const std::vector<MapLineT*>& vpMapLines, const float th = 3.0)
+    template <class KeyFrameT, class MapLineT, class TrackerT = void>
+    int Fuse(KeyFrameT* pKF, const std::vector<MapLineT*>& vpMapLines, const float th = 3.0, TrackerT* tracker = nullptr)
     {
         drfe_ctx* c = Context();
         const int n = (int)vpMapLines.size(), nk = (int)pKF->mvKeyLines.size();
@@ -1253,6 +1262,14 @@ public:
         std::vector<int32_t> bestIdx((size_t)n, -1), bestDist((size_t)n, 0);
         drfe_detail::check(drfe_lsd_fuse_search(c, drfe_detail::f32(Tcw), &cam, fl.data(), descs.data(), skip.data(), n, kl.data(), drfe_detail::u8(pKF->mLineDescriptors),
                                                 nk, th, bestIdx.data(), bestDist.data()), c, "drfe_lsd_fuse_search");
+        /* tracker: as in ORBmatcher::Fuse */
+        if constexpr (!std::is_void<TrackerT>::value)
+            if (tracker) {
+                std::vector<int32_t> gated(bestIdx);
+                for (int i = 0; i < n; i++)
+                    if (bestDist[(size_t)i] > TH_LOW) gated[(size_t)i] = -1;
+                tracker->FuseStore(pKF, vpMapLines, gated.data(), DRFE_LMAP_LINE, DRFE_LMAP_FUSE_NEIGHBOURS, nullptr);
+            }
         int nFused = 0;
         for (int i = 0; i < n; i++) {
             MapLineT* pML = vpMapLines[(size_t)i];
@@ -3978,6 +3995,158 @@ public:
     void MapLineCulling(std::list<MapLineT*>& recent, KeyFrameT* pCurrentKF, bool bMonocular)
     {
         RecentCulling(recent, (int64_t)pCurrentKF->mnId, bMonocular, DRFE_LMAP_LINE);
+    }
+    /* The fuse commit on the store: the loop that applies a fusion search, with MapPoint::Replace /
+     * MapLine::Replace and AddObservation.  bestIdx[i] is the search's answer for candidate i with the bestDist <= TH_LOW gate
+     * applied, -1 = none.  Each method runs the store call, then the reference's loop on the caller's objects with the objects'
+     * own Replace / AddObservation / AddMapPoint: the objects stay authoritative, and decide the same.  The store must hold the
+     * current rows of pKF (Sync, SyncCulling), of the candidates, of the entries of pKF's row they are sent to and of those items'
+     * observers (Sync, SyncCulling, SyncRecent).  Further accessors: MapPointT / MapLineT IsInKeyFrame(), Replace(),
+     * AddObservation(); KeyFrameT GetMapPoint(), AddMapPoint(), GetMapLine(), AddMapLine(), GetMapPoints().  Returns nFused. */
+    /* ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:845-976) */
+    int Fuse(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMapPoints, const std::vector<int32_t>& bestIdx)
+    {
+        FuseStore(pKF, vpMapPoints, bestIdx.data(), DRFE_LMAP_POINT, DRFE_LMAP_FUSE_NEIGHBOURS, nullptr);
+        int nFused = 0;
+        for (size_t i = 0; i < vpMapPoints.size(); i++) {
+            MapPointT* pMP = vpMapPoints[i];
+            if (!pMP) continue;
+            if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;
+            if (bestIdx[i] < 0) continue;
+            MapPointT* pMPinKF = pKF->GetMapPoint((size_t)bestIdx[i]);
+            if (pMPinKF) {
+                if (!pMPinKF->isBad()) {
+                    if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
+                    else pMPinKF->Replace(pMP);
+                }
+            } else {
+                pMP->AddObservation(pKF, (size_t)bestIdx[i]);
+                pKF->AddMapPoint(pMP, (size_t)bestIdx[i]);
+            }
+            nFused++;
+        }
+        return nFused;
+    }
+    /* LSDmatcher::Fuse(pKF, vpMapLines, th) (src/LSDmatcher.cpp:897-1012) */
+    int Fuse(KeyFrameT* pKF, const std::vector<MapLineT*>& vpMapLines, const std::vector<int32_t>& bestIdx)
+    {
+        FuseStore(pKF, vpMapLines, bestIdx.data(), DRFE_LMAP_LINE, DRFE_LMAP_FUSE_NEIGHBOURS, nullptr);
+        int nFused = 0;
+        for (size_t i = 0; i < vpMapLines.size(); i++) {
+            MapLineT* pML = vpMapLines[i];
+            if (!pML || pML->isBad()) continue;        /* the reference does not ask IsInKeyFrame of a line (:1043 is commented out) */
+            if (bestIdx[i] < 0) continue;
+            MapLineT* pMLinKF = pKF->GetMapLine((size_t)bestIdx[i]);
+            if (pMLinKF) {
+                if (!pMLinKF->isBad()) {
+                    if (pMLinKF->Observations() > pML->Observations()) pML->Replace(pMLinKF);
+                    else pMLinKF->Replace(pML);
+                }
+            } else {
+                pML->AddObservation(pKF, (size_t)bestIdx[i]);
+                pKF->AddMapLine(pML, (size_t)bestIdx[i]);
+            }
+            nFused++;
+        }
+        return nFused;
+    }
+    /* ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) (src/ORBmatcher.cc:1001-1101) followed by SearchAndFuse's loop
+     * (src/LoopClosing.cc:650-657): vpReplacePoint is filled, then every recorded point is replaced by its candidate */
+    int FuseLoop(KeyFrameT* pKF, const std::vector<MapPointT*>& vpPoints, const std::vector<int32_t>& bestIdx, std::vector<MapPointT*>& vpReplacePoint)
+    {
+        std::vector<int32_t> recorded(vpPoints.size(), -1);
+        FuseStore(pKF, vpPoints, bestIdx.data(), DRFE_LMAP_POINT, DRFE_LMAP_FUSE_LOOP, recorded.data());
+        const std::set<MapPointT*> spAlreadyFound = pKF->GetMapPoints();
+        std::vector<uint8_t> skip(vpPoints.size());
+        for (size_t i = 0; i < vpPoints.size(); i++) skip[i] = vpPoints[i]->isBad() || spAlreadyFound.count(vpPoints[i]);
+        vpReplacePoint.assign(vpPoints.size(), static_cast<MapPointT*>(nullptr));
+        int nFused = 0;
+        for (size_t i = 0; i < vpPoints.size(); i++) {
+            if (skip[i] || bestIdx[i] < 0) continue;
+            MapPointT* pMP = vpPoints[i];
+            MapPointT* pMPinKF = pKF->GetMapPoint((size_t)bestIdx[i]);
+            if (pMPinKF) {
+                if (!pMPinKF->isBad()) vpReplacePoint[i] = pMPinKF;
+            } else {
+                pMP->AddObservation(pKF, (size_t)bestIdx[i]);
+                pKF->AddMapPoint(pMP, (size_t)bestIdx[i]);
+            }
+            nFused++;
+        }
+        for (size_t i = 0; i < vpPoints.size(); i++) {
+            /* the store recorded the same occupants */
+            if ((vpReplacePoint[i] ? (int32_t)vpReplacePoint[i]->mnId : -1) != recorded[i])
+                throw std::runtime_error("LocalMapTracker::FuseLoop: the store and the objects disagree: the store was not in sync");
+            if (vpReplacePoint[i]) vpReplacePoint[i]->Replace(vpPoints[i]);
+        }
+        return nFused;
+    }
+    /* the loop over mvpCurrentMatchedPoints of CorrectLoop (src/LoopClosing.cc:566-581): vpMatched is parallel to pKF's row */
+    int FuseMatched(KeyFrameT* pKF, const std::vector<MapPointT*>& vpMatched)
+    {
+        FuseStore(pKF, vpMatched, nullptr, DRFE_LMAP_POINT, DRFE_LMAP_FUSE_MATCHED, nullptr);
+        int nFused = 0;
+        for (size_t i = 0; i < vpMatched.size(); i++) {
+            if (!vpMatched[i]) continue;
+            MapPointT* pLoopMP = vpMatched[i];
+            MapPointT* pCurMP = pKF->GetMapPoint(i);
+            if (pCurMP) pCurMP->Replace(pLoopMP);
+            else {
+                pKF->AddMapPoint(pLoopMP, i);
+                pLoopMP->AddObservation(pKF, i);
+            }
+            nFused++;
+        }
+        return nFused;
+    }
+    /* The store's half alone, for Planar_SLAM::ORBmatcher::Fuse / LSDmatcher::Fuse, which run the loop on the objects themselves
+     * and inform a tracker they are given: one step on the store, nothing on the objects.  recorded: LOOP's replace[] as
+     * handles, or nullptr. */
+    template <class ItemT>
+    void FuseStore(KeyFrameT* pKF, const std::vector<ItemT*>& items, const int32_t* bestIdx, int kind, int form, int32_t* recorded)
+    {
+        const size_t n = items.size();
+        std::unique_lock<std::mutex> lock(mMutex);
+        std::vector<int32_t> handles(n), rep(n + 1, -1);
+        size_t live = 0;
+        for (size_t i = 0; i < n; i++) {
+            handles[i] = items[i] ? (int32_t)items[i]->mnId : -1;
+            live += items[i] != nullptr;
+        }
+        std::vector<uint8_t> action(n + 1), moved;
+        std::vector<int32_t> rkind(live + 1), loser(live + 1), winner(live + 1), off(live + 2), tp(live + 1), tl(live + 1), rkf, ridx;
+        int32_t nFused = 0, nReplaced = 0, nTouched[2] = {0, 0};
+        /* the records grow until the call fits (a call that does not fit changes nothing) */
+        for (size_t cap = 16 * live + 1024;; cap *= 8) {
+            rkf.resize(cap);
+            ridx.resize(cap);
+            moved.resize(cap);
+            drfe_lmap_fuse_step s = {};
+            s.keyframe = (int32_t)pKF->mnId; s.kind = kind; s.form = form; s.n = (int32_t)n;
+            s.candidates = handles.data(); s.best_idx = bestIdx; s.action = action.data(); s.n_fused = &nFused; s.replace = rep.data();
+            drfe_lmap_fuse_call c = {};
+            c.n_steps = 1; c.steps = &s;
+            c.replaced_capacity = (int32_t)live; c.record_capacity = (int32_t)cap; c.touched_capacity = (int32_t)live;
+            c.n_replaced = &nReplaced; c.replaced_kind = rkind.data(); c.loser = loser.data(); c.winner = winner.data();
+            c.record_offsets = off.data(); c.record_kf = rkf.data(); c.record_index = ridx.data(); c.record_moved = moved.data();
+            c.n_touched = nTouched; c.touched_points = tp.data(); c.touched_lines = tl.data();
+            const int rc = mForce < 0 ? drfe_lmap_fuse_host(mDb, &c) : mForce > 0 ? drfe_lmap_fuse_device(mDb, &c, nullptr)
+                                                                                   : drfe_lmap_fuse_batch(mDb, &c, nullptr);
+            if (rc == DRFE_ERR_CAPACITY && cap < ((size_t)1 << 28) && std::string(drfe_lmap_last_error(mDb)).find("record_capacity") != std::string::npos)
+                continue;
+            Check(rc, "drfe_lmap_fuse");
+            break;
+        }
+        if (recorded) std::copy(rep.begin(), rep.begin() + (ptrdiff_t)n, recorded);
+    }
+    /* mpReplaced of pMP as the store holds it: the handle, or -1 */
+    int32_t Replaced(MapPointT* pMP)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const int32_t handle = (int32_t)pMP->mnId;
+        int32_t out = -1;
+        Check(drfe_lmap_get_replaced(mDb, DRFE_LMAP_POINT, 1, &handle, &out), "drfe_lmap_get_replaced");
+        return out;
     }
     drfe_lmap* db() const { return mDb; }
 
