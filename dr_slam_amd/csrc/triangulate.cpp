@@ -270,4 +270,24 @@ int drfe_debug_triangulate_math(int which, const float* y, const float* x, int n
     return DRFE_OK;
 }
 
+int drfe_debug_triangulate_math_device(drfe_ctx* c, int which, const float* y, const float* x, int n, float* out)
+{
+    if (!c || which < 0 || which > 2 || n < 0 || (n > 0 && (!y || !out || (which != 1 && !x)))) return DRFE_ERR_INVALID;
+    if (n == 0) return DRFE_OK;
+    const size_t bytes = (size_t)n * sizeof(float);
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf<float> dy, dx, dout;
+    HIPCHK(c, dy.alloc((size_t)n));
+    HIPCHK(c, dout.alloc((size_t)n));
+    HIPCHK(c, hipMemcpyAsync(dy, y, bytes, hipMemcpyHostToDevice, c->stream));
+    if (which != 1) {
+        HIPCHK(c, dx.alloc((size_t)n));
+        HIPCHK(c, hipMemcpyAsync(dx, x, bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, drfe_launch_triangulate_math(which, dy, which != 1 ? (const float*)dx : (const float*)dy, n, dout, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return DRFE_OK;
+}
+
 }  // extern "C"

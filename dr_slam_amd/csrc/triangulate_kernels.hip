@@ -40,6 +40,23 @@ __global__ __launch_bounds__(TRI_THREADS) void k_tri_match(const TriLaunch L)
     tri_write(L, i, st, br, X);
 }
 
+/* the test hook behind drfe_debug_triangulate_math_device: drfe_math.h's canonical atan2f / cosf as this file compiles them,
+ * one lane per element, the expressions of the host hook (and of tr_point's stereo parallax for which == 2) */
+__global__ __launch_bounds__(TRI_THREADS) void k_tri_math(int which, const float* __restrict__ y, const float* __restrict__ x, int n,
+                                                          float* __restrict__ out)
+{
+    const int i = blockIdx.x * TRI_THREADS + threadIdx.x;
+    if (i >= n) return;
+    out[i] = which == 0 ? drfe_atan2f(y[i], x[i]) : which == 1 ? drfe_cosf(y[i]) : drfe_cosf(2 * drfe_atan2f(y[i] / 2, x[i]));
+}
+
+hipError_t drfe_launch_triangulate_math(int which, const float* y, const float* x, int n, float* out, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_tri_math, dim3((n + TRI_THREADS - 1) / TRI_THREADS), dim3(TRI_THREADS), 0, s, which, y, x, n, out);
+    return hipGetLastError();
+}
+
 hipError_t drfe_launch_triangulate(const TriLaunch& L, hipStream_t s)
 {
     if (L.n <= 0) return hipSuccess;

@@ -51,7 +51,7 @@ SYMBOLS = (
     "drfe_map_point_upkeep_host", "drfe_map_line_upkeep_host", "drfe_map_point_upkeep_batch", "drfe_map_line_upkeep_batch",
     "drfe_map_upkeep_stats",
     "drfe_triangulate_points_host", "drfe_triangulate_lines_host", "drfe_triangulate_points_batch", "drfe_triangulate_lines_batch",
-    "drfe_triangulate_stats", "drfe_debug_triangulate_math",
+    "drfe_triangulate_stats", "drfe_debug_triangulate_math", "drfe_debug_triangulate_math_device",
     "drfe_sim3_ransac_host", "drfe_sim3_ransac_batch", "drfe_sim3_stats", "drfe_debug_sim3_atan2", "drfe_debug_sim3_rand",
     "drfe_debug_sim3_horn", "drfe_debug_sim3_hand_back",
     "drfe_init_ransac_host", "drfe_init_ransac_batch", "drfe_init_stats",
@@ -635,6 +635,7 @@ def load() -> C.CDLL:
     L.drfe_triangulate_lines_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp]
     L.drfe_triangulate_stats.argtypes = [vp, vp]
     L.drfe_debug_triangulate_math.argtypes = [i32, vp, vp, i32, vp]
+    L.drfe_debug_triangulate_math_device.argtypes = [vp, i32, vp, vp, i32, vp]
     L.drfe_sim3_ransac_host.argtypes = [vp, vp]
     L.drfe_sim3_ransac_batch.argtypes = [vp, vp, vp, vp]
     L.drfe_sim3_stats.argtypes = [vp, vp]
@@ -3769,6 +3770,15 @@ class Context:
         rc, r = _tri_call(self.L.drfe_triangulate_lines_batch, (self.h,), True, scene, monocular)
         self._chk(rc, "drfe_triangulate_lines_batch")
         return r
+
+    def triangulate_math(self, which, y, x=None):
+        """triangulate_math on the device (drfe_debug_triangulate_math_device, a kernel of triangulate_kernels.hip): same bits"""
+        y = np.ascontiguousarray(y, np.float32)
+        x = np.ascontiguousarray(np.zeros_like(y) if x is None else x, np.float32)
+        out = np.zeros_like(y)
+        self._chk(self.L.drfe_debug_triangulate_math_device(self.h, which, _p(y), _p(x), len(y), _p(out)),
+                  "drfe_debug_triangulate_math_device")
+        return out
 
     def triangulate_stats(self):
         """dict(calls, pairs, pairs_skipped, matches, svd, stereo1, stereo2, accepted) since the context was created"""

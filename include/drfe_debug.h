@@ -69,6 +69,9 @@ int drfe_debug_manhattan_math(int which, const double* x, int n, double* out);
 /* Test hook of include/drfe_math.h's canonical libm of triangulation: out[i] = drfe_atan2f(y[i], x[i]) (which 0),
  * drfe_cosf(y[i]) (which 1) or the stereo parallax drfe_cosf(2 * drfe_atan2f(y[i] / 2, x[i])) (which 2).  Host code. */
 int drfe_debug_triangulate_math(int which, const float* y, const float* x, int n, float* out);
+/* The same three expressions on the device, one lane per element, by a kernel of dr_slam_amd/csrc/triangulate_kernels.hip (so
+ * under the flags the triangulation kernel is compiled with): same bits as the host hook. */
+int drfe_debug_triangulate_math_device(drfe_ctx* ctx, int which, const float* y, const float* x, int n, float* out);
 
 /* Test hooks of the Sim3 solver.  _atan2: out[i] = dr_slam_amd/csrc/cr_atan2.h's correctly rounded atan2(y[i], x[i]), y >= 0;
  * ok[i] = 0 where it was not certified.  _rand: the first n values of rand() after srand(seed), from

@@ -13,6 +13,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import map_upkeep_numpy as MU  # noqa: E402
+import map_upkeep_scenarios as MS  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32, f64 = np.float32, np.float64
@@ -29,28 +30,7 @@ def _assert_same(got, want):
         assert got[k].tobytes() == want[k].tobytes(), k
 
 
-def _flip(base, bits):
-    b = np.unpackbits(base.copy())
-    b[list(bits)] ^= 1
-    return np.packbits(b)
-
-
-def _scene(rows, obs_kf=None, kf_bad=None, world=None, centers=None, ref_kf=0, ref_level=0, line=False, bad=0):
-    """one item observed by len(rows) keyframes (keyframe q = observation q unless obs_kf says otherwise)"""
-    n = len(rows)
-    obs_kf = np.arange(n, dtype=np.int32) if obs_kf is None else np.asarray(obs_kf, np.int32)
-    K = max(int(obs_kf.max()) + 1 if n else 1, ref_kf + 1)
-    rng = np.random.default_rng(7)
-    centers = rng.normal(0, 1, (K, 3)).astype(f32) if centers is None else np.asarray(centers, f32)
-    if world is None:
-        world = np.array([[0.5, 1.5, 4.0, 0.7, 1.1, 4.4]], f64) if line else np.array([[0.5, 1.5, 4.0]], f32)
-    return dict(kf_center=centers, kf_bad=np.zeros(len(centers), np.uint8) if kf_bad is None else np.asarray(kf_bad, np.uint8),
-                scale_factors=MU.scale_factors(), bad=np.array([bad], np.uint8), obs_offsets=np.array([0, n], np.int32),
-                obs_kf=obs_kf, obs_desc=np.asarray(rows, np.uint8).reshape(-1, 32), world=world,
-                ref_kf=np.array([ref_kf], np.int32), ref_level=np.array([ref_level], np.int32))
-
-
-BASE = np.random.default_rng(3).integers(0, 256, 32, dtype=np.uint8)
+_flip, _scene, BASE = MS.flip, MS.scene, MS.BASE          # the hand-built items: tests/map_upkeep_scenarios.py
 
 
 @pytest.mark.parametrize("line", [False, True])
@@ -80,7 +60,7 @@ def test_halves_are_independent(what):
 
 def test_median_tie_first_row_wins():
     """a far row first, then three rows 8 apart: medians 40, 8, 8, 8 - the first of the tied rows (1) wins"""
-    rows = [_flip(BASE, range(100, 140)), _flip(BASE, range(0, 4)), _flip(BASE, range(4, 8)), _flip(BASE, range(8, 12))]
+    rows = MS.tie_rows()
     for line in (False, True):
         s = _scene(rows, line=line)
         got = _host(s, line)
@@ -93,14 +73,8 @@ def test_small_and_even_n(N, expect):
     """N = 1 and 2: the median index is 0, so row 0 wins.  N = 3: a far row, then B and B^{30,31}: medians 30, 2, 2, so
     row 1.  N = 4: B, B^{0,1}, B^{0..9}, B^{200..249}: the lower median (index 1) ties rows 0 and 1 at 2, so row 0; the
     upper median would have picked row 1 (8 against 10)."""
-    if N == 1:
-        rows = [BASE]
-    elif N == 2:
-        rows = [_flip(BASE, range(0, 30)), BASE]
-    elif N == 3:
-        rows = [_flip(BASE, range(0, 30)), BASE, _flip(BASE, range(30, 32))]
-    else:
-        rows = [BASE, _flip(BASE, [0, 1]), _flip(BASE, range(0, 10)), _flip(BASE, range(200, 250))]
+    rows, win = MS.small_n_rows(N)
+    assert win == expect
     s = _scene(rows)
     got = _host(s)
     assert got["best_obs"][0] == expect
@@ -111,7 +85,7 @@ def test_bad_keyframes_interleaved():
     """observations of keyframes [bad, good, bad, good, good]: the rows are the three good ones (far, then two 6 apart), the
     first of the two close rows wins and best_obs points into the caller's list (3).  The bad keyframe's row B would have
     won (3 from both close rows) had it counted."""
-    rows = [_flip(BASE, range(50, 90)), _flip(BASE, range(100, 120)), BASE, _flip(BASE, range(0, 3)), _flip(BASE, range(3, 6))]
+    rows = MS.interleaved_rows()
     s = _scene(rows, kf_bad=[1, 0, 1, 0, 0])
     got = _host(s)
     assert got["best_obs"][0] == 3 and got["desc"][0].tobytes() == rows[3].tobytes()
@@ -146,12 +120,36 @@ def test_bad_keyframe_still_counts_in_the_normal():
 @pytest.mark.parametrize("line", [False, True])
 def test_zero_length_viewing_ray(line):
     """a keyframe centre at the point (the line's middle): norm 0, and the normal becomes NaN as in the reference"""
-    centers = np.array([[0.5, 1.5, 4.0], [1.0, 0.0, 0.0]], f32)
-    world = np.array([[0.25, 1.25, 3.5, 0.75, 1.75, 4.5]], f64) if line else np.array([[0.5, 1.5, 4.0]], f32)
-    s = _scene([BASE, BASE], centers=centers, world=world, ref_kf=1, line=line)
+    s = MS.zero_ray_scene(line)
     got = _host(s, line)
     assert np.isnan(got["normal"]).all() and got["status"][0] == 3
     _assert_same(got, MU.upkeep(s, line=line))
+
+
+@pytest.mark.parametrize("line", [False, True])
+def test_every_case_holds_on_the_host(line):
+    """every case of the scenario module, as the device tests run them: host == numpy and the case's own expectation"""
+    for name, s, expect in MS.cases(line):
+        for what in (1, 2, 3):
+            got = _host(s, line, what)
+            _assert_same(got, MU.upkeep(s, what=what, line=line))
+            MS.holds(expect, got, what=what)
+
+
+def test_bucket_items_are_what_they_claim():
+    """the items built for the device's kernels win where their construction says (numpy, up to 65 rows here)"""
+    for nr in MS.BUCKET_ROWS:
+        for name, rows, win in MS.bucket_items(nr):
+            if nr <= 65 and win is not None:
+                assert MU.distinctive(np.array(rows)) == win, (nr, name)
+    s = MS.with_bad_keyframes(70, 4)
+    got = _host(s)
+    assert s["kf_bad"][got["best_obs"][0]] == 0
+    _assert_same(got, MU.upkeep(s))
+    m = MS.merge([s, _scene(MS.tie_rows()), MS.zero_ray_scene(False)])
+    got = _host(m)
+    _assert_same(got, MU.upkeep(m))
+    assert got["best_obs"][1] == 1 and np.isnan(got["normal"][2]).all()
 
 
 def test_line_full_matrix_gives_the_point_answer():

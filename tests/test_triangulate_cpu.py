@@ -16,6 +16,7 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import triangulate_numpy as TN  # noqa: E402
+import triangulate_scenarios as TS  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 f32, F = np.float32, np.float32
@@ -55,55 +56,19 @@ def test_host_equals_numpy_on_random_scenes(line):
         assert "past" in seen
 
 
-# --- hand-built scenes -----------------------------------------------------------------------------------------------------
+# --- hand-built scenes (tests/triangulate_scenarios.py) ------------------------------------------------------------------------
 
-def _pt_scene(kfs, feats1, feats2, matches=((0, 0),), n_levels=8):
-    """two keyframes (records), their keypoint lists (dicts of un, raw, octave, u_right, depth), one pair"""
-    sc, sg = TN.scale_tables(n_levels)
-    f = [dict(un=np.array([k["un"] for k in fs], f32), raw=np.array([k.get("raw", k["un"]) for k in fs], f32),
-              octave=np.array([k.get("octave", 0) for k in fs], np.int32), u_right=np.array([k.get("u_right", -1.0) for k in fs], f32),
-              depth=np.array([k.get("depth", -1.0) for k in fs], f32)) for fs in (feats1, feats2)]
-    s = dict(kf=np.array(kfs), scale_factors=np.tile(sc, (2, 1)), level_sigma2=np.tile(sg, (2, 1)),
-             offsets=np.int32([0, len(feats1), len(feats1) + len(feats2)]), kf1=np.int32([0]), kf2=np.int32([1]),
-             match_offsets=np.int32([0, len(matches)]), matches=np.int32(matches).reshape(-1, 2))
-    for key in f[0]:
-        s[key] = np.concatenate([f[0][key], f[1][key]])
-    return s
+_pt_scene, _proj, _two, _line_scene = TS.pt_scene, TS.proj, TS.two, TS.line_scene
 
 
-def _proj(kf, X):
-    T = kf["Tcw"].reshape(3, 4).astype(np.float64)
-    x = T[:, :3] @ np.asarray(X, np.float64) + T[:, 3]
-    return [kf["fx"] * x[0] / x[2] + kf["cx"], kf["fy"] * x[1] / x[2] + kf["cy"]], x[2]
-
-
-def _two(X=(0.2, 0.1, 2.0), t2=(-0.3, 0.0, 0.0), st1=False, st2=False, R2=None, Ow2=None):
-    """KF1 at the origin, KF2 at pose (R2, t2) (its centre input Ow2 if given: the baseline test reads it), a point X seen by
-    both; the keypoints are its projections"""
-    k1 = TN.keyframe(np.eye(3), np.zeros(3))
-    k2 = TN.keyframe(np.eye(3) if R2 is None else R2, np.array(t2), Ow=Ow2)
-    u1, z1 = _proj(k1, X)
-    u2, z2 = _proj(k2, X)
-    p1 = dict(un=u1, u_right=u1[0] - 40.0 / z1 if st1 else -1.0, depth=z1 if st1 else -1.0)
-    p2 = dict(un=u2, u_right=u2[0] - 40.0 / z2 if st2 else -1.0, depth=z2 if st2 else -1.0)
-    return k1, k2, p1, p2
-
-
-def _bits_search(make, lo, hi, decide):
-    """the least float32 v in [lo, hi] (positive, by bit pattern) with decide(status of make(v)) != decide(at lo); the cases at
-    v - 1 ulp, v, v + 1 ulp are checked host == numpy and returned"""
-    a, b = int(np.float32(lo).view(np.int32)), int(np.float32(hi).view(np.int32))
-    d0 = decide(TN.triangulate(make(F(lo)))["status"][0])
-    assert decide(TN.triangulate(make(F(hi)))["status"][0]) != d0
-    while b - a > 1:
-        m = (a + b) // 2
-        if decide(TN.triangulate(make(np.int32(m).view(np.float32)))["status"][0]) == d0:
-            a = m
-        else:
-            b = m
+def _bits_search(name):
+    """the gate's flip (the least float32 at which the decision differs from the one at the low end, found with numpy alone);
+    the cases at v - 1 ulp, v, v + 1 ulp are checked host == numpy and returned"""
+    make, b, d0 = TS.flip_of(name)
+    decide = TS.GATES[name]()[3]
     out = []
     for bits in (b - 1, b, b + 1):
-        out.append(_check(make(np.int32(bits).view(np.float32))))
+        out.append(_check(make(TS.float_of(bits))))
     assert decide(out[0]["status"][0]) == d0 and decide(out[1]["status"][0]) != d0
     return out
 
@@ -111,69 +76,33 @@ def _bits_search(make, lo, hi, decide):
 @pytest.mark.parametrize("stereo", [False, True])
 def test_reprojection_threshold_steps(stereo):
     """5.991 sigma^2 (mono) / 7.8 sigma^2 (stereo), compared in double: KF1's level sigma^2 one step either side"""
-    k1, k2, p1, p2 = _two(st1=stereo)
-    p1["un"] = [p1["un"][0] + 0.8, p1["un"][1] - 0.5]
-    if stereo:
-        p1["u_right"] += 0.6
-
-    def make(s2):
-        s = _pt_scene([k1, k2], [p1], [p2])
-        s["level_sigma2"] = s["level_sigma2"].copy()
-        s["level_sigma2"][0, 0] = s2
-        return s
-    out = _bits_search(make, 1e-4, 4.0, lambda st: st == TN.P_CODES["reproj1"])
+    out = _bits_search("reproj_stereo" if stereo else "reproj_mono")
     assert out[0]["status"][0] == TN.P_CODES["reproj1"] and out[1]["status"][0] != TN.P_CODES["reproj1"]
 
 
 def test_parallax_09998_steps():
     """cosParallaxRays < 0.9998 (a double) for two monocular keypoints: KF2 moved along x one float step at a time"""
-    X = (0.0, 0.0, 3.0)
-
-    def make(tx):
-        k1, k2, p1, p2 = _two(X=X, t2=(-float(tx), 0.0, 0.0))
-        k2["Ow"] = np.float32([1.0, 0.0, 0.0])        # keep the pair (the baseline test reads Ow)
-        return _pt_scene([k1, k2], [p1], [p2])
-    out = _bits_search(make, 0.01, 0.2, lambda st: st == TN.P_CODES["no_parallax"])
+    out = _bits_search("parallax_09998")
     assert out[0]["branch"][0] == 0 and out[1]["branch"][0] == 1
 
 
 def test_cos_rays_positive_steps():
     """cosParallaxRays > 0: KF2 looks along world x, so KF1's keypoint at cx gives perpendicular rays (cos == 0 exactly)"""
-    R2 = np.array([[0, 0, -1], [0, 1, 0], [1, 0, 0]], np.float64)       # camera z = world x
-    k1, k2, _, _ = _two(R2=R2, t2=(0.0, 0.0, 1.0))
-    p2 = dict(un=[float(k2["cx"]), float(k2["cy"])])
-    res = []
-    for du in (-0.25, 0.0, 0.25):
-        p1 = dict(un=[float(k1["cx"]) + du, 260.0])
-        h = _check(_pt_scene([k1, k2], [p1], [p2]))
-        res.append(h["branch"][0])
+    res = [_check(s)["branch"][0] for s in TS.cos_rays_scenes()]
     assert res[1] == 0                                 # cos == 0: not > 0
     assert sorted({res[0], res[2]}) != [0]             # one side is positive
 
 
 def test_ratio_tests_steps_and_equality():
-    k1, k2, p1, p2 = _two()
-    p1["octave"], p2["octave"] = 1, 0
-
-    def make(sc):
-        s = _pt_scene([k1, k2], [p1], [p2])
-        s["scale_factors"] = s["scale_factors"].copy()
-        s["scale_factors"][0, 1] = sc
-        return s
+    make, k1, k2 = TS.ratio_make()
     h = TN.triangulate(make(F(1.2)))
     assert h["status"][0] == 0
     # ratioDist * ratioFactor < ratioOctave flips as KF1's scale grows; ratioDist > ratioOctave * ratioFactor as it shrinks
-    _bits_search(make, 1.2, 50.0, lambda st: st == TN.P_CODES["scale"])
-    _bits_search(make, 1.2, 0.01, lambda st: st == TN.P_CODES["scale"]) if False else None
-    lo = _bits_search(lambda v: make(F(1.0) / v), F(1.0) / F(1.2), 50.0, lambda st: st == TN.P_CODES["scale"])
+    _bits_search("ratio_above")
+    lo = _bits_search("ratio_below")
     assert lo[1]["status"][0] == TN.P_CODES["scale"]
     # equality of the first test: ratioOctave == ratioDist * ratioFactor exactly is kept (strict <)
-    X = np.float32([0.2, 0.1, 2.0])
-    d1 = TN._dist(X, k1["Ow"])
-    d2 = TN._dist(X, k2["Ow"])
-    rd = F(d2 / d1)
-    prod = F(rd * F(F(1.5) * F(1.2)))
-    eq = make(prod)
+    eq, X = TS.ratio_equality_scene()
     h = TN.triangulate(eq)
     _check(eq)
     if h["x3d"][0].tolist() == X.tolist() or h["status"][0] in (0, TN.P_CODES["scale"]):
@@ -183,129 +112,78 @@ def test_ratio_tests_steps_and_equality():
 def test_equal_stereo_cosines():
     """cosParallaxStereo1 == cosParallaxStereo2 (= cosParallaxRays + 1, rays just past perpendicular): neither stereo
     branch is taken; one depth step nearer, stereo 1 is"""
-    R2 = np.array([[0, 0, -1], [0, 1, 0], [1, 0, 0]], np.float64)
-    k1, k2, _, _ = _two(R2=R2, t2=(0.0, 0.0, 1.0))
-    p2 = dict(un=[float(k2["cx"]) + 0.05, float(k2["cy"])])
-
-    def make(d):
-        p1 = dict(un=[float(k1["cx"]), 260.0], u_right=100.0, depth=d)
-        return _pt_scene([k1, k2], [p1], [p2])
-    out = _bits_search(make, 0.5, 2000.0, lambda st: st == TN.P_CODES["no_parallax"])
+    out = _bits_search("equal_stereo_cosines")
     assert out[1]["status"][0] == TN.P_CODES["no_parallax"] and out[0]["branch"][0] == 2
 
 
 def test_z_zero_w_zero_dist_zero_rank_deficient():
     # z1 == 0: the stereo point lands on KF1's plane (Twc and Tcw are independent inputs); low parallax: stereo 1
-    k1, k2, p1, p2 = _two(X=(0.2, 0.1, 30.0), t2=(-0.01, 0.0, 0.0), st1=True, Ow2=(1.0, 0.0, 0.0))
-    k1["Tcw"] = np.float32([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, -p1["depth"]])
-    h = _check(_pt_scene([k1, k2], [p1], [p2]))
+    h = _check(TS.z_zero_scene())
     assert h["status"][0] == TN.P_CODES["z1"] and h["branch"][0] == 2
     # w == 0: keypoints at the principal point, A's third column zero and its fourth orthogonal to the rest
-    k1 = TN.keyframe(np.eye(3), np.array([0.5, 0.25, 0.0]))
-    k2 = TN.keyframe(np.eye(3), np.array([-0.5, -0.25, 0.0]))
-    k2["Tcw"] = np.float32([1, 0, 0, -0.5, 0, 1, 0, -0.25, 0.1, 0, 1, 0])
-    pc = dict(un=[float(k1["cx"]), float(k1["cy"])])
-    h = _check(_pt_scene([k1, k2], [pc], [pc]))
+    h = _check(TS.w_zero_scene())
     assert h["status"][0] == TN.P_CODES["w_zero"] and h["branch"][0] == 1
     # rank-deficient A with w != 0: KF2's first two rows equal KF1's (rows 2, 3 of A repeat rows 0, 1)
-    k1 = TN.keyframe(np.eye(3), np.array([0.1, 0.0, 0.5]))
-    k2 = TN.keyframe(np.eye(3), np.array([-0.2, 0.0, 0.5]))
-    k2["Tcw"] = np.concatenate([k1["Tcw"][:8], np.float32([0.3, 0, 1, 0.5])])
-    pa = dict(un=[300.0, 200.0])
-    h = _check(_pt_scene([k1, k2], [pa], [pa]))
+    h = _check(TS.rank_deficient_scene())
     assert h["branch"][0] == 1 and h["status"][0] != TN.P_CODES["w_zero"]
     # dist == 0: KF1's centre (GetCameraCenter, an input of its own) on the unprojected point
-    k1, k2, p1, p2 = _two(X=(0.2, 0.1, 30.0), t2=(-0.01, 0.0, 0.0), st1=True, Ow2=(1.0, 0.0, 0.0))
-    s = _pt_scene([k1, k2], [p1], [p2])
-    X = TN._twc(k1["Twc"], [F(F((F(p1["un"][0]) - k1["cx"]) * F(p1["depth"])) * k1["invfx"]),
-                            F(F((F(p1["un"][1]) - k1["cy"]) * F(p1["depth"])) * k1["invfy"]), F(p1["depth"])])
-    s["kf"] = s["kf"].copy()
-    s["kf"][0]["Ow"] = np.float32(X)
-    s["kf"][1]["Ow"] = np.float32([5.0, 0.0, 0.0])
-    h = _check(s)
+    h = _check(TS.dist_zero_scene())
     assert h["status"][0] == TN.P_CODES["dist"] and h["branch"][0] == 2
 
 
 def test_kf2_residual_uses_kf1_mbf():
-    k1, k2, p1, p2 = _two(st2=True)
-    ok = _check(_pt_scene([k1, k2], [p1], [p2]))
+    s_ok, s_off = TS.kf2_residual_scenes()
+    ok = _check(s_ok)
     assert ok["status"][0] == 0
-    k1["mbf"] = F(80.0)                                 # KF2's own mbf stays 40: its residual is now off by 40 / z
-    h = _check(_pt_scene([k1, k2], [p1], [p2]))
+    h = _check(s_off)                                   # KF1's mbf 80, KF2's own stays 40: its residual is now off by 40 / z
     assert h["status"][0] == TN.P_CODES["reproj2"]
 
 
 def test_unproject_reads_the_distorted_keys():
-    k1, k2, p1, p2 = _two(st1=True, X=(0.2, 0.1, 30.0), t2=(-0.01, 0.0, 0.0), Ow2=(1.0, 0.0, 0.0))   # low parallax: stereo 1
-    p1["raw"] = [p1["un"][0] + 0.5, p1["un"][1] - 0.25]
-    h = _check(_pt_scene([k1, k2], [p1], [p2]))
+    k1, p1, s, s2 = TS.distorted_keys_scenes()          # low parallax: stereo 1
+    h = _check(s)
     assert h["branch"][0] == 2
     z = F(p1["depth"])
     want = TN._twc(k1["Twc"], [F(F((F(p1["raw"][0]) - k1["cx"]) * z) * k1["invfx"]), F(F((F(p1["raw"][1]) - k1["cy"]) * z) * k1["invfy"]), z])
     if h["status"][0] == 0:
         assert h["x3d"][0].tolist() == [float(v) for v in want]
-        s2 = _pt_scene([k1, k2], [dict(p1, raw=p1["un"])], [p2])
         assert _check(s2)["x3d"][0].tolist() != h["x3d"][0].tolist()
 
 
-def _line_scene(d1, d2, n1=2, n2=3, idx2=1):
-    """KF1 with n1 key lines, KF2 with n2; one match (0, idx2); depth lines d1 (KF1's, per line), d2 (KF2's)"""
-    from dr_slam_amd import lib  # noqa: F401
-    k1 = TN.keyframe(np.eye(3), np.zeros(3))
-    k2 = TN.keyframe(np.eye(3), np.array([-0.3, 0.0, 0.0]))
-    A, B = np.array([0.1, 0.0, 2.0]), np.array([0.3, 0.2, 2.2])
-    ends, l3 = [], []
-    for kf in (k1, k2):
-        T = kf["Tcw"].reshape(3, 4).astype(np.float64)
-        a, b = T[:, :3] @ A + T[:, 3], T[:, :3] @ B + T[:, 3]
-        ends.append([kf["fx"] * a[0] / a[2] + kf["cx"], kf["fy"] * a[1] / a[2] + kf["cy"], kf["fx"] * b[0] / b[2] + kf["cx"],
-                     kf["fy"] * b[1] / b[2] + kf["cy"]])
-        l3.append(np.concatenate([a, b]))
-    sc, sg = TN.scale_tables()
-    s = dict(kf=np.array([k1, k2]), scale_factors=np.tile(sc, (2, 1)), level_sigma2=np.tile(sg, (2, 1)),
-             offsets=np.int32([0, n1, n1 + n2]), ends=np.array([ends[0]] * n1 + [ends[1]] * n2, f32),
-             octave=np.zeros(n1 + n2, np.int32), depth=np.array(list(d1) + list(d2), f32),
-             lines3d=np.array([l3[0]] * n1 + [l3[1]] * n2, np.float64), kf1=np.int32([0]), kf2=np.int32([1]),
-             match_offsets=np.int32([0, 1]), matches=np.int32([[0, idx2]]))
-    return s
-
-
 def test_line_idx2_quirk():
+    q = TS.line_idx2_scenes()
     # in range: KF1's line idx2 has depth, KF2's has none: bStereo2 is read from KF1, so stereo 2 is taken
-    h = _check(_line_scene([-1.0, 2.0], [2.0, -1.0, -1.0], idx2=1), True)
+    h = _check(q[0], True)
     assert h["branch"][0] == 3 and h["status"][0] == 0
     # KF1's line idx2 without depth, KF2's with: no line
-    h = _check(_line_scene([-1.0, -1.0], [2.0, 2.0, 2.0], idx2=1), True)
+    h = _check(q[1], True)
     assert h["status"][0] == TN.L_CODES["no_stereo"]
     # idx2 past KF1's lines: bStereo2 false, flagged
-    h = _check(_line_scene([-1.0, 2.0], [2.0, 2.0, 2.0], idx2=2), True)
+    h = _check(q[2], True)
     assert h["status"][0] == TN.L_CODES["no_stereo"] | TN.PAST_KF1
-    h = _check(_line_scene([2.0, -1.0], [2.0, 2.0, 2.0], idx2=2), True)
+    h = _check(q[3], True)
     assert h["status"][0] == TN.PAST_KF1 and h["branch"][0] == 2 and h["accepted"][0] == 1
 
 
 def test_line_gates_hand_built():
-    s = _line_scene([2.0, 2.0], [2.0, 2.0, 2.0], idx2=0)
-    s["kf"] = s["kf"].copy()
-    s["kf"][1]["Tcw"] = np.float32([1, 0, 0, 0.3, 0, 1, 0, 0, 0, 0, -1, 2.0])     # KF2 looks back: sp behind it
-    assert _check(s, True)["status"][0] == TN.L_CODES["z_sp2"]
-    s["kf"][1]["Tcw"] = np.float32([1, 0, 0, 0.3, 0, 1, 0, 0, 0, 0, -1, 2.1])     # sp in front of KF2, ep behind it
-    assert _check(s, True)["status"][0] == TN.L_CODES["z_ep2"]
-    s = _line_scene([2.0, 2.0], [2.0, 2.0, 2.0], idx2=0)
-    s["kf"] = s["kf"].copy()
-    s["kf"][0]["Ow"] = np.float32(TN._twc(s["kf"][0]["Twc"], [F(v) for v in s["lines3d"][0, 3:]]))
-    assert _check(s, True)["status"][0] == TN.L_CODES["dist"]
+    g = TS.line_gate_scenes()
+    assert _check(g[0], True)["status"][0] == TN.L_CODES["z_sp2"]         # KF2 looks back: sp behind it
+    assert _check(g[1], True)["status"][0] == TN.L_CODES["z_ep2"]         # sp in front of KF2, ep behind it
+    assert _check(g[2], True)["status"][0] == TN.L_CODES["dist"]
 
 
 def test_baseline_skip_at_equality():
-    k1, k2, p1, p2 = _two()
-    base = TN._dist(k2["Ow"], k1["Ow"])
-    k2["mb"] = base
-    h = _check(_pt_scene([k1, k2], [p1], [p2]))
+    eq, above = TS.baseline_scenes()
+    h = _check(eq)
     assert h["pair_skipped"][0] == 0
-    k2["mb"] = np.nextafter(base, F(1))
-    h = _check(_pt_scene([k1, k2], [p1], [p2]))
+    h = _check(above)
     assert h["pair_skipped"][0] == 1 and h["status"][0] == 1
+
+
+def test_every_case_holds_on_the_host():
+    """every case of the scenario module, as the device tests run them: host == numpy and the case's own expectation"""
+    for name, scene, line, expect in TS.cases():
+        TS.holds(expect, _check(scene, line))
 
 
 def test_bad_arguments_are_rejected():
