@@ -1,5 +1,5 @@
-/* lmap_internal.h — what lmap.cpp, lmap_conn.cpp, lmap_correct.cpp, lmap_cull.cpp, lmap_gba.cpp, lmap_recent.cpp and lmap_fuse.cpp hand to the
- * store's kernels (DESIGN.md sections 25 to 29, 31 and 32).  The host's sequence around these launches is lmap_call.h's. */
+/* lmap_internal.h — what lmap.cpp, lmap_conn.cpp, lmap_correct.cpp, lmap_cull.cpp, lmap_gba.cpp, lmap_recent.cpp, lmap_fuse.cpp and
+ * lmap_insert.cpp hand to the store's kernels (DESIGN.md sections 25 to 29 and 31 to 33).  The host's sequence around these launches is lmap_call.h's. */
 #ifndef DRFE_LMAP_INTERNAL_H
 #define DRFE_LMAP_INTERNAL_H
 
@@ -11,6 +11,7 @@
 #include "gba_core.h"
 #include "recent_core.h"
 #include "fuse_core.h"
+#include "insert_core.h"
 
 /* threads of a workgroup: frame points and key-frame slots go across them in the vote, the entries of a match row in the gather */
 #define LMAP_THREADS 256
@@ -335,6 +336,56 @@ struct FuseLaunch {
 };
 /* the live pre-pass over every tile, then the walk: in stream order */
 hipError_t drfe_launch_fuse(const FuseLaunch& L, hipStream_t s);
+
+/* ---- the item loops of LocalMapping::ProcessNewKeyFrame (insert_kernels.hip) ---- */
+/* row entries of one workgroup of the entry launches, a lane each */
+#define INSERT_TILE LMAP_THREADS
+/* workgroups of the normals launch at most: a lane per ADDED point entry, over a grid */
+#define INSERT_NORMAL_GROUPS 1024
+
+/* totals of a call: ADDED points, RECENT points, ADDED lines, RECENT lines */
+enum { INSERT_HEAD_ADDED_P = 0, INSERT_HEAD_RECENT_P, INSERT_HEAD_ADDED_L, INSERT_HEAD_RECENT_L, INSERT_HEAD_WORDS };
+/* those of one workgroup, then their exclusive prefix over the call's workgroups */
+struct InsertGroup {
+    int32_t v[INSERT_HEAD_WORDS];
+};
+
+/* One call.  Its rows are one flat entry space (insert_core.h): the point rows of the called key frames in call order, then their
+ * line rows.  A chunk is the called key frames [j0, j1): their claim words, their verdicts and the nObs they add; the lists and the
+ * records are packed once, after the last chunk. */
+struct InsertLaunch {
+    LmapImage I;                   /* resident */
+    CullImage A;                   /* resident: nObs of the points is added to */
+    RecentImage R;                 /* resident: nObs of the lines is added to */
+    CorrImage G;                   /* resident; read only with normals */
+    int32_t n;                     /* called key frames */
+    int32_t normals;
+    int32_t words;                 /* of an item's adder bits: (n + 31) / 32 */
+    int32_t j0, j1;
+    /* staged */
+    const int32_t* called;         /* n slots, in call order */
+    const int32_t* segOff;         /* 2n + 1 */
+    const int32_t* byRank;         /* n: the positions of the call in ascending slot */
+    const int32_t* rankOf;         /* n: the inverse */
+    /* scratch */
+    int32_t* claim[2];             /* (j1 - j0) x nP, (j1 - j0) x nL: LMAP_NO_CLAIM bytes before each chunk */
+    uint32_t* adders;              /* nP x words, zero before the first chunk; only with normals */
+    InsertGroup* group;            /* per workgroup of the flat entry space */
+    int32_t* addEntry[2];          /* the ADDED entries of each kind, in walk order */
+    int32_t* recent[2];            /* the RECENT items of each kind as slots, in push order */
+    float* nrm;                    /* per ADDED point entry: 3 */
+    float* maxD;
+    float* minD;
+    uint8_t* status;
+    /* out */
+    int32_t* head;                 /* INSERT_HEAD_WORDS */
+    uint8_t* action;               /* per entry of the flat space */
+};
+/* the claims and the verdicts of the chunk, with the commit of nObs: in stream order after the memset of the claim words.
+ * hostSegOff: segOff on the host, from which the launches size their grids */
+hipError_t drfe_launch_insert_chunk(const InsertLaunch& L, const int32_t* hostSegOff, hipStream_t s);
+/* after the last chunk: the totals, their prefix, the packed lists, the normals of the ADDED point entries */
+hipError_t drfe_launch_insert_finish(const InsertLaunch& L, const int32_t* hostSegOff, hipStream_t s);
 
 /* ---- the map update of LoopClosing::RunGlobalBundleAdjustment (gba_kernels.hip) ---- */
 /* point slots of one workgroup of the point launches, a lane each */

@@ -86,6 +86,8 @@ SYMBOLS = (
     "drfe_lmap_recent_cull_stats", "drfe_lmap_recent_upload_bytes",
     "drfe_lmap_fuse_host", "drfe_lmap_fuse_device", "drfe_lmap_fuse_batch", "drfe_lmap_fuse_limits", "drfe_lmap_fuse_scratch",
     "drfe_lmap_fuse_stats", "drfe_lmap_get_replaced", "drfe_lmap_get_match_row", "drfe_lmap_get_observers",
+    "drfe_lmap_insert_host", "drfe_lmap_insert_device", "drfe_lmap_insert_batch", "drfe_lmap_insert_limits", "drfe_lmap_insert_scratch",
+    "drfe_lmap_insert_stats",
 )
 
 FAST_CELL_DTYPE = np.dtype([(n, "<i4") for n in ("level", "x0", "y0", "ww", "wh", "offX", "offY", "cellIdx", "ncp", "rpl", "nrb",
@@ -431,6 +433,20 @@ class LmapFuseCall(C.Structure):
         "n_touched", "touched_points", "touched_lines")]                             # drfe_lmap_fuse_call
 
 
+LMAP_INSERT_STATS = ("calls", "keyframes", "device_calls", "points_added", "lines_added", "recent_points", "recent_lines", "device_chunks")
+LMAP_INSERT_LIMITS = ("tile", "wavefront", "claim_bytes", "normal_groups", "threads", "max_keyframes", "device_from", "reserved")
+INSERT_NULL, INSERT_BAD, INSERT_RECENT, INSERT_ADDED = range(4)                       # drfe_lmap_insert_call's action bytes
+LMAP_INSERT_CALL_FIELDS = ("point_offsets", "point_action", "line_offsets", "line_action", "n_added", "added_points", "added_point_kf",
+                           "added_point_index", "normal", "max_distance", "min_distance", "status", "added_lines", "added_line_kf",
+                           "added_line_index", "n_recent", "recent_points", "recent_lines")
+
+
+class LmapInsertCall(C.Structure):
+    _fields_ = [("n", C.c_int32), ("pad", C.c_int32), ("handles", C.c_void_p), ("action_capacity", C.c_int32 * 2),
+                ("added_capacity", C.c_int32 * 2), ("recent_capacity", C.c_int32 * 2)] + [
+        (k, C.c_void_p) for k in LMAP_INSERT_CALL_FIELDS]                           # drfe_lmap_insert_call
+
+
 class InitProblems(C.Structure):
     _fields_ = [("n", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_void_p) for k in (
         "K", "sigma", "max_iterations", "seed", "key1_offsets", "key2_offsets", "keys1", "keys2",
@@ -757,6 +773,12 @@ def load() -> C.CDLL:
     L.drfe_lmap_fuse_limits.argtypes = [vp]
     L.drfe_lmap_fuse_scratch.argtypes = [vp, C.c_int64, C.c_int64, vp]
     L.drfe_lmap_fuse_stats.argtypes = [vp, vp]
+    L.drfe_lmap_insert_host.argtypes = [vp, vp]
+    L.drfe_lmap_insert_device.argtypes = [vp, vp, vp]
+    L.drfe_lmap_insert_batch.argtypes = [vp, vp, vp]
+    L.drfe_lmap_insert_limits.argtypes = [vp]
+    L.drfe_lmap_insert_scratch.argtypes = [vp, i32, vp, i32, vp]
+    L.drfe_lmap_insert_stats.argtypes = [vp, vp]
     L.drfe_lmap_get_replaced.argtypes = [vp, i32, i32, vp, vp]
     L.drfe_lmap_get_match_row.argtypes = [vp, i32, i32, i32, vp, vp]
     L.drfe_lmap_get_observers.argtypes = [vp, i32, i32, i32, vp, vp, vp]
@@ -2473,6 +2495,70 @@ class LocalMap:
                                         r["record_moved"][o[i]:o[i + 1]].astype(np.int32)], axis=1)) for i in range(nr)],
                 "touched_points": r["touched_points"][:int(r["n_touched"][0])].copy(),
                 "touched_lines": r["touched_lines"][:int(r["n_touched"][1])].copy()}
+
+    # ---- the item loops of LocalMapping::ProcessNewKeyFrame on the store ----
+
+    @staticmethod
+    def insert_limits():
+        out = np.zeros(8, np.int32)
+        rc = load().drfe_lmap_insert_limits(_p(out))
+        if rc != 0:
+            raise DrfeError(f"drfe_lmap_insert_limits failed ({rc})")
+        return dict(zip(LMAP_INSERT_LIMITS, (int(v) for v in out)))
+
+    def insert_stats(self):
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_lmap_insert_stats(self.h, _p(st)), "drfe_lmap_insert_stats")
+        return dict(zip(LMAP_INSERT_STATS, (int(v) for v in st)))
+
+    def insert_scratch(self, handles, normals=True):
+        """bytes of device scratch an insert call of these key frames takes: (as one chunk, with one key frame a chunk, the part
+        every chunk shares)"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        out = np.zeros(3, np.int64)
+        self._chk(self.L.drfe_lmap_insert_scratch(self.h, len(hs), _p(hs), int(bool(normals)), _p(out)), "drfe_lmap_insert_scratch")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def insert(self, handles, mode="batch", normals=True, capacity=None):
+        """The item loops of ProcessNewKeyFrame for the key frames `handles` in queue order.  Returns a dict: point_action and
+        line_action (per called key frame an array of action bytes, INSERT_NULL / _BAD / _RECENT / _ADDED), added_points [m, 3] and
+        added_lines [m, 3] of (item, key frame, index) in walk order, recent_points and recent_lines (handles in push order) and,
+        with normals, normal [m, 3], max_distance, min_distance and status per added point.  capacity: (action, added, recent)
+        entries per kind; default: grown until the call fits (a call that does not fit changes nothing)."""
+        hs = np.ascontiguousarray(handles, np.int32)
+        n = len(hs)
+        grow = capacity is None
+        ca, cd, cr = (1 << 12, 1 << 12, 1 << 12) if grow else (int(c) for c in capacity)
+        fn = getattr(self.L, f"drfe_lmap_insert_{mode}")
+        while True:
+            r = {"point_offsets": np.zeros(n + 1, np.int32), "point_action": np.zeros(max(1, ca), np.uint8),
+                 "line_offsets": np.zeros(n + 1, np.int32), "line_action": np.zeros(max(1, ca), np.uint8),
+                 "n_added": np.zeros(2, np.int32), "added_points": np.zeros(max(1, cd), np.int32),
+                 "added_point_kf": np.zeros(max(1, cd), np.int32), "added_point_index": np.zeros(max(1, cd), np.int32),
+                 "normal": np.zeros((max(1, cd), 3), np.float32) if normals else None, "max_distance": np.zeros(max(1, cd), np.float32),
+                 "min_distance": np.zeros(max(1, cd), np.float32), "status": np.zeros(max(1, cd), np.uint8),
+                 "added_lines": np.zeros(max(1, cd), np.int32), "added_line_kf": np.zeros(max(1, cd), np.int32),
+                 "added_line_index": np.zeros(max(1, cd), np.int32), "n_recent": np.zeros(2, np.int32),
+                 "recent_points": np.zeros(max(1, cr), np.int32), "recent_lines": np.zeros(max(1, cr), np.int32)}
+            call = LmapInsertCall(n, 0, _p(hs), (C.c_int32 * 2)(ca, ca), (C.c_int32 * 2)(cd, cd), (C.c_int32 * 2)(cr, cr),
+                                  *[None if r[k] is None else _p(r[k]) for k in LMAP_INSERT_CALL_FIELDS])
+            args = (self.h, C.byref(call)) + (() if mode == "host" else (None,))
+            rc = fn(*args)
+            if not (grow and rc == ERR_CAPACITY and ca < (1 << 28) and b"_capacity[" in self.L.drfe_lmap_last_error(self.h)):
+                break
+            ca, cd, cr = ca * 8, cd * 8, cr * 8
+        self._chk(rc, f"drfe_lmap_insert_{mode}")
+        po, lo = r["point_offsets"], r["line_offsets"]
+        ap, al = int(r["n_added"][0]), int(r["n_added"][1])
+        res = {"point_action": [r["point_action"][po[j]:po[j + 1]].copy() for j in range(n)],
+               "line_action": [r["line_action"][lo[j]:lo[j + 1]].copy() for j in range(n)],
+               "added_points": np.stack([r["added_points"][:ap], r["added_point_kf"][:ap], r["added_point_index"][:ap]], axis=1),
+               "added_lines": np.stack([r["added_lines"][:al], r["added_line_kf"][:al], r["added_line_index"][:al]], axis=1),
+               "recent_points": r["recent_points"][:int(r["n_recent"][0])].copy(),
+               "recent_lines": r["recent_lines"][:int(r["n_recent"][1])].copy()}
+        if normals:
+            res.update({k: r[k][:ap].copy() for k in ("normal", "max_distance", "min_distance", "status")})
+        return res
 
     # ---- the map update of LoopClosing::RunGlobalBundleAdjustment on the store (DESIGN.md section 29) ----
 

@@ -2391,6 +2391,106 @@ int drfe_lmap_get_replaced(drfe_lmap* db, int kind, int32_t count, const int32_t
 int drfe_lmap_get_match_row(drfe_lmap* db, int kind, int32_t keyframe, int32_t capacity, int32_t* n, int32_t* out);
 int drfe_lmap_get_observers(drfe_lmap* db, int kind, int32_t handle, int32_t capacity, uint8_t* bad, int32_t* n, int32_t* out);
 
+/* The item loops of LocalMapping::ProcessNewKeyFrame (src/LocalMapping.cc:113-173) on the same store, with MapPoint::AddObservation
+ * and UpdateNormalAndDepth (src/MapPoint.cc:124-138, :370-417) and MapLine::AddObservation (src/MapLine.cpp:91-100).  DESIGN.md
+ * section 33.  Parity with a build of the reference's LocalMapping.cc, MapPoint.cc and MapLine.cpp is not pinned.
+ *
+ * A call names n key frames in queue order (at most DRFE_LMAP_MAX_QUERIES), each once (a handle named twice: DRFE_ERR_INVALID),
+ * already stored with their match rows.  The call is the item loops for key frame 0, then key frame 1, and so on, on the evolving
+ * store.  Per called key frame k its point row is walked in index order i, then its line row; one action byte per entry:
+ *
+ *   0 NULL    a null entry.
+ *   1 BAD     the item is bad.
+ *   2 RECENT  k is among the item's observers at that moment: the handle is appended to recent_points (recent_lines), once per
+ *             row index, as the reference pushes; nothing else changes.
+ *   3 ADDED   the item gains the observation (k, i).  A point's nObs grows by 2 when the stereo flag of (k, i) in the key frame's
+ *             culling attributes is set, else by 1; a line's by 1.  The new observer enters the stored list in front of the first
+ *             stored observer of greater rank, at the end if there is none, one addition after another (the fuse commit's rule).
+ *
+ * So an item that stands twice in one row is ADDED at its first index and RECENT at the second, and an item that already observed
+ * k is RECENT at every occurrence.  The bad flags, the match rows and the poses do not change.
+ *
+ * UpdateNormalAndDepth of an ADDED point runs right after its addition, on the stored position, over the observer list as it stands
+ * then - the stored list plus the additions of this and earlier called key frames, in list order - with the stored camera centres,
+ * the stored reference key frame and ref_level and the stored scales (the geometry of drfe_lmap_set_poses /
+ * _set_point_geometry / _set_scales); float sums in list order.  It is reported per ADDED entry, the way drfe_lmap_correct_out
+ * reports it: a point added by two called key frames is reported twice, the second time over one more observer.  The stored
+ * geometry holds no normal, so nothing of it is written.  With normal == NULL this part is skipped, no geometry is read and the
+ * call is integer-only.  The store holds no line geometry: UpdateAverageDir stays with drfe_map_line_upkeep_*, as do
+ * ComputeDistinctiveDescriptors of both kinds, the plane list, ComputeBoW, Map::AddKeyFrame and UpdateConnections
+ * (drfe_lmap_connect_*); added_* names every ADDED entry in walk order, which is what the upkeep batch needs.
+ *
+ * Several key frames in one call: the reference runs UpdateConnections(k) before the next key frame's additions.  A call of several
+ * key frames followed by one drfe_lmap_connect_* of all of them lets an earlier key frame's vote see a later one's new
+ * observations; a caller who wants the reference's interleaving calls once per key frame.  The result is the same whenever no
+ * item is ADDED by two called key frames. */
+enum { DRFE_LMAP_INSERT_NULL = 0, DRFE_LMAP_INSERT_BAD = 1, DRFE_LMAP_INSERT_RECENT = 2, DRFE_LMAP_INSERT_ADDED = 3 };
+typedef struct drfe_lmap_insert_call {
+    int32_t n;                        /* called key frames */
+    int32_t pad;
+    const int32_t* handles;           /* n, in queue order */
+    int32_t action_capacity[2];       /* entries of point_action, line_action: the total length of the called rows of that kind */
+    int32_t added_capacity[2];        /* ADDED points, lines; the total length of the called rows of that kind always suffices */
+    int32_t recent_capacity[2];       /* RECENT points, lines; the same bound */
+    /* per called key frame: its entries are point_action[point_offsets[j] .. point_offsets[j + 1]), row order */
+    int32_t* point_offsets;           /* n + 1, from 0 */
+    uint8_t* point_action;
+    int32_t* line_offsets;            /* n + 1 */
+    uint8_t* line_action;
+    int32_t* n_added;                 /* 2: points, lines */
+    /* per ADDED point entry, in walk order */
+    int32_t* added_points;            /* handles */
+    int32_t* added_point_kf;          /* the called key frame */
+    int32_t* added_point_index;       /* the row index */
+    float* normal;                    /* 3 each, or NULL: no UpdateNormalAndDepth, the next three are not written */
+    float* max_distance;
+    float* min_distance;
+    uint8_t* status;                  /* DRFE_UPKEEP_NORMAL */
+    /* per ADDED line entry, in walk order */
+    int32_t* added_lines;
+    int32_t* added_line_kf;
+    int32_t* added_line_index;
+    int32_t* n_recent;                /* 2 */
+    int32_t* recent_points;           /* handles in push order */
+    int32_t* recent_lines;
+} drfe_lmap_insert_call;
+/* row entries of both kinds in a call from which drfe_lmap_insert_batch of a store with a context uses the device.  Measured
+ * (profiles/insert_timing.jsonl) the device entry beats the host entry at 64 called key frames on stores
+ * of 100 and 1 000 key frames (0.75x to 0.96x of its time) but loses at 4 000 key frames with nine tenths of the entries added,
+ * and at 1 and 4 called key frames on the smaller stores: there is no call size from which it wins at every store size, so the
+ * constant stands above the longest call and _batch runs on the host; _device is there to be called. */
+enum { DRFE_LMAP_INSERT_DEVICE_FROM = 0x7fffffff };
+/* _host always runs on the host, _device always on the device (DRFE_ERR_STATE without a context; DRFE_ERR_CAPACITY when the
+ * configured scratch does not hold the call with one key frame a chunk), _batch on the device from DRFE_LMAP_INSERT_DEVICE_FROM row
+ * entries when the call fits.  All three return the same bytes and leave the same store.  Refused, and nothing changes: an
+ * unknown or repeated key-frame handle, more than DRFE_LMAP_MAX_QUERIES key frames (DRFE_ERR_INVALID); with DRFE_ERR_STATE and the
+ * name of the item a called key frame with a point entry that is ADDED but without culling attributes that fit its row (the stereo
+ * flags), a point entry that is not bad without culling attributes that fit its observations, a line entry that is not bad
+ * without its recent-list state, and - when normals are asked for and a point is ADDED - missing scales, a missing position of an
+ * ADDED point, a missing pose of one of its observers or of its reference key frame, a reference key frame of -1 or unknown, a
+ * ref_level out of range; DRFE_ERR_CAPACITY when an output array is too small.  The host entry commits into the rows and the
+ * image; the device entry commits nObs into the resident attribute and recent-list blocks itself.  The observation arrays are
+ * spliced on the host in both, so after a device call only the observations with their offsets and indices travel
+ * (drfe_lmap_upload_bytes, drfe_lmap_recent_upload_bytes: no match rows, no graph, no geometry).  Because it commits as it goes,
+ * the device entry settles every refusal before its first launch: at once when every stored key frame and point has culling
+ * attributes that fit, every stored point and line its recent-list state and - with normals - every stored item its geometry,
+ * and when added_capacity and recent_capacity are at least the called rows' lengths; otherwise by running the host's walk first,
+ * so that such a call costs the host's work and the device's. */
+int drfe_lmap_insert_host(drfe_lmap* db, drfe_lmap_insert_call* call);
+int drfe_lmap_insert_device(drfe_lmap* db, drfe_lmap_insert_call* call, void* stream);
+int drfe_lmap_insert_batch(drfe_lmap* db, drfe_lmap_insert_call* call, void* stream);
+/* out[0] row entries of one workgroup of the device's entry launches, [1] lanes of a wavefront, [2] bytes of scratch per stored
+ * point and line and key frame of a chunk (its claim word), [3] the most workgroups of the normals launch, [4] its workgroup size,
+ * [5] DRFE_LMAP_MAX_QUERIES, [6] DRFE_LMAP_INSERT_DEVICE_FROM, [7] 0 */
+int drfe_lmap_insert_limits(int32_t* out8);
+/* the scratch a device call of these handles takes: out[0] bytes with which it runs as one chunk, [1] the least bytes with which
+ * it runs at all (one key frame a chunk), [2] the part every chunk shares (the lists, the records and, with normals, a bit per
+ * stored point and called key frame) */
+int drfe_lmap_insert_scratch(drfe_lmap* db, int32_t n, const int32_t* handles, int32_t normals, int64_t* out3);
+/* Counters since the store was created: stats[0] calls, [1] called key frames, [2] calls run on the device, [3] points added, [4]
+ * lines added, [5] recent pushes of points, [6] of lines, [7] chunks run on the device. */
+int drfe_lmap_insert_stats(drfe_lmap* db, int64_t* stats /* 8 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

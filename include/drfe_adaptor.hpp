@@ -4139,6 +4139,97 @@ public:
         }
         if (recorded) std::copy(rep.begin(), rep.begin() + (ptrdiff_t)n, recorded);
     }
+    /* The item loops of LocalMapping::ProcessNewKeyFrame (src/LocalMapping.cc:124-157) on the store for
+     * mpCurrentKeyFrame = pKF, or for a queue of new key frames in order.  The store must hold the current rows of the key frames
+     * (Sync, SyncCulling), of the items in them (Sync, SyncCulling, SyncRecent) and - with normals - the geometry of those points,
+     * of their observers and reference key frames (SyncGeometry).  The store decides and commits; then the rows are walked as the
+     * reference walks them: an ADDED entry gets the object's own AddObservation(pKF, i), a RECENT one is pushed onto recentPoints /
+     * recentLines.  Returns one record per ADDED point entry in walk order, as MapUpkeep::Points returns them (status
+     * DRFE_UPKEEP_NORMAL with the normal and the two distances of its UpdateNormalAndDepth; best_obs and descriptor unset:
+     * ComputeDistinctiveDescriptors stays with the upkeep batch); `added`, when given, receives the points of those entries.
+     * normals = false skips that part: no geometry is read and every status is 0.  Several key frames in one call: see drfe.h on
+     * UpdateConnections between them.  Further accessors: MapPointT / MapLineT IsInKeyFrame(), AddObservation(). */
+    std::vector<drfe::MapPointUpkeep> ProcessNewKeyFrame(KeyFrameT* pKF, std::list<MapPointT*>& recentPoints, std::list<MapLineT*>& recentLines,
+                                                   bool normals = true, std::vector<MapPointT*>* added = nullptr)
+    {
+        return ProcessNewKeyFrame(std::vector<KeyFrameT*>(1, pKF), recentPoints, recentLines, normals, added);
+    }
+    std::vector<drfe::MapPointUpkeep> ProcessNewKeyFrame(const std::vector<KeyFrameT*>& vpKFs, std::list<MapPointT*>& recentPoints,
+                                                   std::list<MapLineT*>& recentLines, bool normals = true, std::vector<MapPointT*>* added = nullptr)
+    {
+        const size_t n = vpKFs.size();
+        std::unique_lock<std::mutex> lock(mMutex);
+        std::vector<int32_t> handles(n);
+        size_t rows[2] = {0, 0};
+        for (size_t j = 0; j < n; j++) {
+            handles[j] = (int32_t)vpKFs[j]->mnId;
+            rows[0] += vpKFs[j]->GetMapPointMatches().size();
+            rows[1] += vpKFs[j]->GetMapLineMatches().size();
+        }
+        std::vector<int32_t> pOff(n + 1), lOff(n + 1), ap(rows[0] + 1), apKf(rows[0] + 1), apIdx(rows[0] + 1), al(rows[1] + 1), alKf(rows[1] + 1),
+            alIdx(rows[1] + 1), rp(rows[0] + 1), rl(rows[1] + 1);
+        std::vector<uint8_t> pAct(rows[0] + 1), lAct(rows[1] + 1), status(rows[0] + 1);
+        std::vector<float> nrm(3 * (rows[0] + 1)), maxD(rows[0] + 1), minD(rows[0] + 1);
+        int32_t nAdded[2] = {0, 0}, nRecent[2] = {0, 0};
+        drfe_lmap_insert_call c = {};
+        c.n = (int32_t)n; c.handles = handles.data();
+        for (int k = 0; k < 2; k++) c.action_capacity[k] = c.added_capacity[k] = c.recent_capacity[k] = (int32_t)rows[k];
+        c.point_offsets = pOff.data(); c.point_action = pAct.data(); c.line_offsets = lOff.data(); c.line_action = lAct.data();
+        c.n_added = nAdded; c.added_points = ap.data(); c.added_point_kf = apKf.data(); c.added_point_index = apIdx.data();
+        c.normal = normals ? nrm.data() : nullptr; c.max_distance = maxD.data(); c.min_distance = minD.data(); c.status = status.data();
+        c.added_lines = al.data(); c.added_line_kf = alKf.data(); c.added_line_index = alIdx.data();
+        c.n_recent = nRecent; c.recent_points = rp.data(); c.recent_lines = rl.data();
+        Check(mForce < 0 ? drfe_lmap_insert_host(mDb, &c) : mForce > 0 ? drfe_lmap_insert_device(mDb, &c, nullptr) : drfe_lmap_insert_batch(mDb, &c, nullptr),
+              "drfe_lmap_insert");
+        lock.unlock();
+        std::vector<drfe::MapPointUpkeep> records((size_t)nAdded[0]);
+        for (size_t t = 0; t < records.size(); t++) {
+            drfe::MapPointUpkeep& u = records[t];
+            if (!normals) continue;
+            u.status = status[t];
+            for (int k = 0; k < 3; k++) u.normal[k] = nrm[3 * t + (size_t)k];
+            u.max_distance = maxD[t];
+            u.min_distance = minD[t];
+        }
+        if (added) added->clear();
+        /* the reference's loops on the objects, which decide the same */
+        auto disagree = []() { return std::runtime_error("LocalMapTracker::ProcessNewKeyFrame: the store and the objects disagree: the store was not in sync"); };
+        for (size_t j = 0; j < n; j++) {
+            KeyFrameT* pKF = vpKFs[j];
+            const std::vector<MapPointT*> vpMapPointMatches = pKF->GetMapPointMatches();
+            for (size_t i = 0; i < vpMapPointMatches.size(); i++) {
+                MapPointT* pMP = vpMapPointMatches[i];
+                const uint8_t a = pAct[(size_t)pOff[j] + i];
+                const bool live = pMP && !pMP->isBad();
+                if (live != (a == DRFE_LMAP_INSERT_ADDED || a == DRFE_LMAP_INSERT_RECENT)) throw disagree();
+                if (!live) continue;
+                if (!pMP->IsInKeyFrame(pKF)) {
+                    if (a != DRFE_LMAP_INSERT_ADDED) throw disagree();
+                    pMP->AddObservation(pKF, i);
+                    if (added) added->push_back(pMP);
+                } else {
+                    if (a != DRFE_LMAP_INSERT_RECENT) throw disagree();
+                    recentPoints.push_back(pMP);
+                }
+            }
+            const std::vector<MapLineT*> vpMapLineMatches = pKF->GetMapLineMatches();
+            for (size_t i = 0; i < vpMapLineMatches.size(); i++) {
+                MapLineT* pML = vpMapLineMatches[i];
+                const uint8_t a = lAct[(size_t)lOff[j] + i];
+                const bool live = pML && !pML->isBad();
+                if (live != (a == DRFE_LMAP_INSERT_ADDED || a == DRFE_LMAP_INSERT_RECENT)) throw disagree();
+                if (!live) continue;
+                if (!pML->IsInKeyFrame(pKF)) {
+                    if (a != DRFE_LMAP_INSERT_ADDED) throw disagree();
+                    pML->AddObservation(pKF, i);
+                } else {
+                    if (a != DRFE_LMAP_INSERT_RECENT) throw disagree();
+                    recentLines.push_back(pML);
+                }
+            }
+        }
+        return records;
+    }
     /* mpReplaced of pMP as the store holds it: the handle, or -1 */
     int32_t Replaced(MapPointT* pMP)
     {
