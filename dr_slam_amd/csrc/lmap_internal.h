@@ -1,5 +1,5 @@
-/* lmap_internal.h — what lmap.cpp, lmap_conn.cpp, lmap_correct.cpp, lmap_cull.cpp, lmap_gba.cpp, lmap_recent.cpp, lmap_fuse.cpp and
- * lmap_insert.cpp hand to the store's kernels (DESIGN.md sections 25 to 29 and 31 to 33).  The host's sequence around these launches is lmap_call.h's. */
+/* lmap_internal.h — what lmap.cpp, lmap_conn.cpp, lmap_correct.cpp, lmap_cull.cpp, lmap_gba.cpp, lmap_recent.cpp, lmap_fuse.cpp,
+ * lmap_insert.cpp and lmap_create.cpp hand to the store's kernels (DESIGN.md sections 25 to 29 and 31 to 34).  The host's sequence around these launches is lmap_call.h's. */
 #ifndef DRFE_LMAP_INTERNAL_H
 #define DRFE_LMAP_INTERNAL_H
 
@@ -12,6 +12,7 @@
 #include "recent_core.h"
 #include "fuse_core.h"
 #include "insert_core.h"
+#include "create_core.h"
 
 /* threads of a workgroup: frame points and key-frame slots go across them in the vote, the entries of a match row in the gather */
 #define LMAP_THREADS 256
@@ -386,6 +387,49 @@ struct InsertLaunch {
 hipError_t drfe_launch_insert_chunk(const InsertLaunch& L, const int32_t* hostSegOff, hipStream_t s);
 /* after the last chunk: the totals, their prefix, the packed lists, the normals of the ADDED point entries */
 hipError_t drfe_launch_insert_finish(const InsertLaunch& L, const int32_t* hostSegOff, hipStream_t s);
+
+/* ---- map-point and map-line creation (create_kernels.hip) ---- */
+/* creations of one workgroup, a lane each; the entry launches take the same number of observation entries */
+#define CREATE_TILE LMAP_THREADS
+/* bytes of scratch per creation of a chunk (its offset inside its tile) and per tile (the tile's observers, then their prefix) */
+#define CREATE_ITEM_BYTES 4
+/* bytes of scratch per stored row entry of either kind: its claim word */
+#define CREATE_CLAIM_BYTES 4
+
+/* One chunk of a call: the creations [t0, t1) of one kind.  The staged arrays hold the call's creations of that kind from 0, two
+ * entries per creation where an observation is meant.  The resident sections have room behind their elements for everything the
+ * call appends: the host granted it before the upload.  Creation t takes the slot slot0 + t. */
+struct CreateLaunch {
+    LmapImage I;                   /* resident; the bad flags, the observations and the match rows are written */
+    CullImage A;                   /* resident: nObs and obsIdx of the new points are written */
+    RecentImage R;                 /* resident: the counters, and all of a new line, are written */
+    CorrImage G;                   /* resident: the centres and scales are read; with `geo` the new points' geometry is written */
+    int32_t kind;                  /* FUSE_POINT or FUSE_LINE */
+    int32_t geo, normals;
+    int32_t t0, t1;
+    int32_t slot0;                 /* the slot of creation 0 of the call */
+    int32_t obs0;                  /* the kind's observations stored before creation t0's */
+    /* staged */
+    const int32_t* cnt;            /* 1 or 2 */
+    const int32_t* kf;             /* 2 each: slots */
+    const int32_t* idx;            /* 2 each */
+    const int32_t* ref;            /* slot */
+    const int64_t* first;
+    const float* world;            /* 3 each; points */
+    const int32_t* prev;           /* 2 each: the creation that named the same row entry last before this one, or -1 */
+    /* scratch */
+    int32_t* local;                /* t1 - t0: the observers of the creations before it in its tile */
+    int32_t* tile;                 /* per tile of the chunk: its observers, then their exclusive prefix */
+    int32_t* claim;                /* per row entry of the kind; only the words the chunk names are cleared and read */
+    /* out */
+    int32_t* displaced;            /* 2 each: the slot that stood in the row entry, or -1 */
+    float* nrm;                    /* per point creation: 3 */
+    float* maxD;
+    float* minD;
+    uint8_t* status;
+};
+/* the offsets, the claims, the new slots of every section, the row entries: in stream order */
+hipError_t drfe_launch_create_chunk(const CreateLaunch& L, hipStream_t s);
 
 /* ---- the map update of LoopClosing::RunGlobalBundleAdjustment (gba_kernels.hip) ---- */
 /* point slots of one workgroup of the point launches, a lane each */

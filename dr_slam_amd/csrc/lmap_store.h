@@ -4,8 +4,9 @@
  * lmap_conn.cpp (KeyFrame::UpdateConnections, section 26), lmap_correct.cpp (the Sim3 propagation of LoopClosing::CorrectLoop,
  * section 27), lmap_cull.cpp (LocalMapping::KeyFrameCulling with KeyFrame::SetBadFlag, section 28), lmap_gba.cpp (the map update
  * of LoopClosing::RunGlobalBundleAdjustment, section 29), lmap_recent.cpp (LocalMapping::MapPointCulling and MapLineCulling,
- * section 31), lmap_fuse.cpp (the fuse commit with MapPoint::Replace, section 32) and lmap_insert.cpp (the item loops of
- * LocalMapping::ProcessNewKeyFrame, section 33).  What the device paths of those eight share around their launches is lmap_call.h. */
+ * section 31), lmap_fuse.cpp (the fuse commit with MapPoint::Replace, section 32), lmap_insert.cpp (the item loops of
+ * LocalMapping::ProcessNewKeyFrame, section 33) and lmap_create.cpp (map-point and map-line creation, appended in place, section
+ * 34).  What the device paths of the first eight share around their launches is lmap_call.h. */
 #ifndef DRFE_LMAP_STORE_H
 #define DRFE_LMAP_STORE_H
 
@@ -179,6 +180,7 @@ struct drfe_lmap {
     std::unordered_map<int32_t, int32_t> mpReplaced, mlReplaced;
     int64_t fuseStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t insStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};    /* of the item loops of ProcessNewKeyFrame */
+    int64_t createStats[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* of map-point and map-line creation */
     /* the host walk's stamps, kept between calls: an item is stamped for the query whose serial it holds */
     std::vector<int32_t> stampP, stampL, inP, inL;
     int32_t serial = 0;

@@ -13,7 +13,14 @@
  * into staging and hands the caller one copy (dst_offset, src, bytes) per run, from the first section's offset to the next
  * current section's offset or the block end; then the single elements of sections that did not go up anyway, from the host array
  * itself.  It points the device view at `base`, adds the bytes to the caller's counter and returns them.  An empty section takes
- * no room and sends nothing. */
+ * no room and sends nothing.
+ *
+ * A section may be granted a capacity, in elements (grant(), section_of()): room behind its elements, so that an array that is
+ * only appended to keeps its offset and those of the sections behind it.  Such a section takes max(size, capacity) elements of
+ * room, empty or not.  When it has grown since the last send, inside its room, without a mark and without moving, only the new
+ * tail goes up, from the host array itself: the caller appended and changed nothing below.  grant(section, need) leaves a capacity
+ * that holds `need` elements alone and else sets it to twice `need`, which moves the sections behind (they go up once) and
+ * returns true.  A block without a granted section lays out, plans and sends exactly as described above. */
 #ifndef DRFE_RESIDENT_BLOCK_H
 #define DRFE_RESIDENT_BLOCK_H
 
@@ -62,6 +69,31 @@ public:
         elems_.clear();
     }
     void stale_at(int section, size_t index) { elems_.emplace_back(section, index); }
+
+    /* the section bound to this vector, or -1 */
+    int section_of(const void* vec) const
+    {
+        for (size_t i = 0; i < s_.size(); i++)
+            if (s_[i].vec == vec) return (int)i;
+        return -1;
+    }
+    /* room for `need` elements in the section: true when its capacity had to be set anew, to twice `need` */
+    bool grant(int section, size_t need)
+    {
+        Bound& b = s_[(size_t)section];
+        if (need * b.elem <= b.cap) return false;
+        b.cap = 2 * need * b.elem;
+        return true;
+    }
+    /* a device call appended to the section itself, inside its room, what the host array now holds too */
+    void took(int section)
+    {
+        Bound& b = s_[(size_t)section];
+        size_t n;
+        b.span(b.vec, &n);
+        if (!b.marked && b.off == b.heldOff && n * b.elem <= (b.cap > b.heldBytes ? b.cap : b.heldBytes)) b.heldBytes = n * b.elem;
+    }
+    size_t capacity(int section) const { return s_[(size_t)section].cap / s_[(size_t)section].elem; }
     void assume_current()
     {
         for (Bound& b : s_) b.marked = false;
@@ -75,14 +107,16 @@ public:
             size_t n;
             b.span(b.vec, &n);
             b.bytes = n * b.elem;
-            b.off = L.add<char>(b.bytes).off;
+            b.off = L.add<char>(b.bytes > b.cap ? b.bytes : b.cap).off;
         }
         bytes_ = L.bytes();
         if (bytes_ > have) stale_all();
         staged_ = 0;
         for (size_t i = 0; i < s_.size(); i++) {
             Bound& b = s_[i];
-            b.up = b.marked || b.off != b.heldOff || b.bytes != b.heldBytes;
+            /* appended to inside its room: the tail alone */
+            b.tail = !b.marked && b.off == b.heldOff && b.bytes > b.heldBytes && b.bytes <= b.cap;
+            b.up = !b.tail && (b.marked || b.off != b.heldOff || b.bytes != b.heldBytes);
             if (b.up) staged_ += end(i) - b.off;
         }
         return bytes_ > have ? 2 * bytes_ : have;
@@ -117,7 +151,15 @@ public:
             copy(b.off + e.second * b.elem, src + e.second * b.elem, b.elem);
             sent += b.elem;
         }
+        for (const Bound& b : s_) {
+            if (!b.tail) continue;
+            size_t n;
+            const char* src = b.span(b.vec, &n);
+            copy(b.off + b.heldBytes, src + b.heldBytes, b.bytes - b.heldBytes);
+            sent += b.bytes - b.heldBytes;
+        }
         for (Bound& b : s_) {
+            b.tail = false;
             b.heldOff = b.off;
             b.heldBytes = b.bytes;
             b.up = false;
@@ -144,7 +186,8 @@ private:
         void (*point)(void* field, char* p);
         size_t off = 0, bytes = 0;                         /* as planned */
         size_t heldOff = (size_t)-1, heldBytes = 0;        /* what the device copy holds */
-        bool marked = true, up = false;
+        size_t cap = 0;                                    /* granted room in bytes, 0 = none */
+        bool marked = true, up = false, tail = false;
     };
     size_t end(size_t i) const { return i + 1 < s_.size() ? s_[i + 1].off : bytes_; }
 

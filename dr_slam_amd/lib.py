@@ -87,7 +87,8 @@ SYMBOLS = (
     "drfe_lmap_fuse_host", "drfe_lmap_fuse_device", "drfe_lmap_fuse_batch", "drfe_lmap_fuse_limits", "drfe_lmap_fuse_scratch",
     "drfe_lmap_fuse_stats", "drfe_lmap_get_replaced", "drfe_lmap_get_match_row", "drfe_lmap_get_observers",
     "drfe_lmap_insert_host", "drfe_lmap_insert_device", "drfe_lmap_insert_batch", "drfe_lmap_insert_limits", "drfe_lmap_insert_scratch",
-    "drfe_lmap_insert_stats",
+    "drfe_lmap_insert_stats", "drfe_lmap_create_host", "drfe_lmap_create_device", "drfe_lmap_create_batch",
+    "drfe_lmap_create_limits", "drfe_lmap_create_scratch", "drfe_lmap_create_stats",
 )
 
 FAST_CELL_DTYPE = np.dtype([(n, "<i4") for n in ("level", "x0", "y0", "ww", "wh", "offX", "offY", "cellIdx", "ncp", "rpl", "nrb",
@@ -447,6 +448,19 @@ class LmapInsertCall(C.Structure):
         (k, C.c_void_p) for k in LMAP_INSERT_CALL_FIELDS]                           # drfe_lmap_insert_call
 
 
+LMAP_CREATE_STATS = ("calls", "device_calls", "points_created", "lines_created", "displaced", "stale_calls", "relayouts", "device_chunks")
+LMAP_CREATE_LIMITS = ("tile", "wavefront", "claim_bytes", "item_bytes", "threads", "reserved0", "device_from", "reserved1")
+LMAP_CREATE_IN_FIELDS = ("point_handle", "point_n_obs", "point_obs_kf", "point_obs_index", "point_ref_kf", "point_first_kf", "point_world",
+                         "line_handle", "line_n_obs", "line_obs_kf", "line_obs_index", "line_ref_kf", "line_first_kf")
+LMAP_CREATE_OUT_FIELDS = ("point_displaced", "line_displaced", "normal", "max_distance", "min_distance", "status")
+
+
+class LmapCreateCall(C.Structure):
+    _fields_ = [("n_points", C.c_int32), ("n_lines", C.c_int32)] + [(k, C.c_void_p) for k in LMAP_CREATE_IN_FIELDS] + [
+        ("displaced_capacity", C.c_int32 * 2), ("record_capacity", C.c_int32), ("pad", C.c_int32)] + [
+        (k, C.c_void_p) for k in LMAP_CREATE_OUT_FIELDS]                            # drfe_lmap_create_call
+
+
 class InitProblems(C.Structure):
     _fields_ = [("n", C.c_int32), ("pad", C.c_int32)] + [(k, C.c_void_p) for k in (
         "K", "sigma", "max_iterations", "seed", "key1_offsets", "key2_offsets", "keys1", "keys2",
@@ -779,6 +793,12 @@ def load() -> C.CDLL:
     L.drfe_lmap_insert_limits.argtypes = [vp]
     L.drfe_lmap_insert_scratch.argtypes = [vp, i32, vp, i32, vp]
     L.drfe_lmap_insert_stats.argtypes = [vp, vp]
+    L.drfe_lmap_create_host.argtypes = [vp, vp]
+    L.drfe_lmap_create_device.argtypes = [vp, vp, vp]
+    L.drfe_lmap_create_batch.argtypes = [vp, vp, vp]
+    L.drfe_lmap_create_limits.argtypes = [vp]
+    L.drfe_lmap_create_scratch.argtypes = [vp, i32, i32, vp]
+    L.drfe_lmap_create_stats.argtypes = [vp, vp]
     L.drfe_lmap_get_replaced.argtypes = [vp, i32, i32, vp, vp]
     L.drfe_lmap_get_match_row.argtypes = [vp, i32, i32, i32, vp, vp]
     L.drfe_lmap_get_observers.argtypes = [vp, i32, i32, i32, vp, vp, vp]
@@ -2558,6 +2578,66 @@ class LocalMap:
                "recent_lines": r["recent_lines"][:int(r["n_recent"][1])].copy()}
         if normals:
             res.update({k: r[k][:ap].copy() for k in ("normal", "max_distance", "min_distance", "status")})
+        return res
+
+    # ---- map-point and map-line creation on the store, appended in place ----
+
+    @staticmethod
+    def create_limits():
+        out = np.zeros(8, np.int32)
+        rc = load().drfe_lmap_create_limits(_p(out))
+        if rc != 0:
+            raise DrfeError(f"drfe_lmap_create_limits failed ({rc})")
+        return dict(zip(LMAP_CREATE_LIMITS, (int(v) for v in out)))
+
+    def create_scratch(self, n_points, n_lines=0):
+        """bytes of device scratch a create call of that many creations takes: (each kind as one chunk, with one workgroup of
+        creations a chunk, the part every chunk shares)"""
+        out = np.zeros(3, np.int64)
+        self._chk(self.L.drfe_lmap_create_scratch(self.h, int(n_points), int(n_lines), _p(out)), "drfe_lmap_create_scratch")
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def create_stats(self):
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_lmap_create_stats(self.h, _p(st)), "drfe_lmap_create_stats")
+        return dict(zip(LMAP_CREATE_STATS, (int(v) for v in st)))
+
+    def create(self, points=(), lines=(), mode="batch", normals=True, capacity=None):
+        """The tail of CreateNewMapPoints / CreateNewMapLines2 for the creations `points`, then `lines`, in order.  A creation is
+        a dict: handle, obs (1 or 2 (key frame, index) pairs in the caller's order), ref_kf, first_kf and, for a point, world.
+        Returns a dict: point_displaced and line_displaced [n, 2] (the handle that stood in the row entry of each observation, -1
+        for none) and, with normals, normal [n, 3], max_distance, min_distance and status per created point.  capacity:
+        (displaced entries per kind, records); default: what the call needs."""
+        fn = getattr(self.L, f"drfe_lmap_create_{mode}")
+        def pack(items, point):
+            n = len(items)
+            r = {"handle": np.zeros(n, np.int32), "n_obs": np.zeros(n, np.int32), "obs_kf": np.zeros((n, 2), np.int32),
+                 "obs_index": np.zeros((n, 2), np.int32), "ref_kf": np.zeros(n, np.int32), "first_kf": np.zeros(n, np.int64)}
+            if point:
+                r["world"] = np.zeros((n, 3), np.float32)
+            for t, it in enumerate(items):
+                r["handle"][t], r["ref_kf"][t], r["first_kf"][t] = it["handle"], it["ref_kf"], it.get("first_kf", 0)
+                obs = list(it["obs"])
+                r["n_obs"][t] = len(obs)
+                for o, (k, i) in enumerate(obs[:2]):
+                    r["obs_kf"][t, o], r["obs_index"][t, o] = k, i
+                if point:
+                    r["world"][t] = it["world"]
+            return r
+        points, lines = list(points), list(lines)
+        a = {"point_" + k: v for k, v in pack(points, True).items()}
+        a.update({"line_" + k: v for k, v in pack(lines, False).items()})
+        nP, nL = len(points), len(lines)
+        cd, cr = (2 * max(nP, nL), nP) if capacity is None else (int(v) for v in capacity)
+        out = {"point_displaced": np.full((max(1, nP), 2), -1, np.int32), "line_displaced": np.full((max(1, nL), 2), -1, np.int32),
+               "normal": np.zeros((max(1, nP), 3), np.float32) if normals else None, "max_distance": np.zeros(max(1, nP), np.float32),
+               "min_distance": np.zeros(max(1, nP), np.float32), "status": np.zeros(max(1, nP), np.uint8)}
+        call = LmapCreateCall(nP, nL, *[_p(a[k]) for k in LMAP_CREATE_IN_FIELDS], (C.c_int32 * 2)(cd, cd), cr, 0,
+                              *[None if out[k] is None else _p(out[k]) for k in LMAP_CREATE_OUT_FIELDS])
+        self._chk(fn(*((self.h, C.byref(call)) + (() if mode == "host" else (None,)))), f"drfe_lmap_create_{mode}")
+        res = {"point_displaced": out["point_displaced"][:nP].copy(), "line_displaced": out["line_displaced"][:nL].copy()}
+        if normals:
+            res.update({k: out[k][:nP].copy() for k in ("normal", "max_distance", "min_distance", "status")})
         return res
 
     # ---- the map update of LoopClosing::RunGlobalBundleAdjustment on the store (DESIGN.md section 29) ----

@@ -2491,6 +2491,100 @@ int drfe_lmap_insert_scratch(drfe_lmap* db, int32_t n, const int32_t* handles, i
  * lines added, [5] recent pushes of points, [6] of lines, [7] chunks run on the device. */
 int drfe_lmap_insert_stats(drfe_lmap* db, int64_t* stats /* 8 */);
 
+/* ---- map-point and map-line creation on the map store, appended in place ---- */
+/* The tail of LocalMapping::CreateNewMapPoints and CreateNewMapLines2 (reference src/LocalMapping.cc:522-535, :1019-1031), which
+ * also ends StereoInitialization, CreateInitialMapMonocular, CreateInitialMapMonoWithLine and both loops of CreateNewKeyFrame in
+ * Tracking.cc: a new item, AddObservation per observer (src/MapPoint.cc:124-138, src/MapLine.cpp:91-100), AddMapPoint / AddMapLine
+ * into the observers' match rows (src/KeyFrame.cc:287-291, :849-853) and, for a point, UpdateNormalAndDepth
+ * (src/MapPoint.cc:376-417).  DESIGN.md section 34.  Parity with a build of the reference's files is not pinned.
+ *
+ * A call is an ordered list of point creations and one of line creations; the two kinds touch different rows and items, so the
+ * call is the point creations one after another, then the line creations, on the evolving store.  A creation holds a new handle,
+ * 1 or 2 observations (key frame, row index) in the caller's order, the reference key frame, mnFirstKFid and, for a point, its
+ * world position.  The new item is not bad, has found 1, visible 1, first_kf as given, no adjustment state and no mpReplaced; a
+ * point gets the geometry (position, ref_kf, level, corrected_by 0, corrected_ref 0).
+ *
+ * Per observation in order: a key frame that is already among the item's observers is skipped as an observer (two observations on
+ * one key frame keep the first); else it enters the observer list in rank order (the fuse commit's rule) with its index, and nObs
+ * grows by 2 when the stereo flag of (key frame, index) in the key frame's culling attributes is set, else by 1; a line's by 1.
+ * Either way row[key frame][index] = the new handle, whatever stood there: the displaced item keeps its observation and its nObs,
+ * as in the reference, and its handle (or -1) is reported per observation.  When two creations of a call name the same entry the
+ * later one holds it after the call, and its report names the earlier one.
+ *
+ * UpdateNormalAndDepth of a created point runs right after, over its own observers in rank order with the stored camera centres
+ * and scales: level is the octave, in the reference key frame's culling attributes, of the index the point observes it with.
+ * normal, max_distance, min_distance and status are reported per created point, the way drfe_lmap_insert_call reports them; the
+ * stored geometry gets level.  With normal == NULL this part is skipped and level is still stored.  The store holds no line
+ * geometry: UpdateAverageDir and both kinds' ComputeDistinctiveDescriptors stay with drfe_map_*_upkeep_*, Map::AddMapPoint and
+ * the push onto mlpRecentAdded* with the caller.
+ *
+ * In place: when the store's image is current after the entry's own build, and the new handles of a kind are above every stored
+ * handle of that kind and ascending in call order, the new items take the next slots at the end of everything the store keeps by
+ * slot and the rows are written by handle and by slot; no image is rebuilt and no resident block is sent again as a whole.  The
+ * sections of the resident blocks the call appends to are granted room (twice what the call needs when they lack it: a relayout,
+ * which sends that block once and is counted), so that the next device call of any kind uploads the appended tails and the
+ * touched row entries only.  A call whose handles do not qualify commits into the rows by handle, leaves the image stale for the
+ * next call to rebuild, and is counted. */
+typedef struct drfe_lmap_create_call {
+    int32_t n_points, n_lines;
+    /* per point creation */
+    const int32_t* point_handle;
+    const int32_t* point_n_obs;       /* 1 or 2 */
+    const int32_t* point_obs_kf;      /* 2 each; the second is not read when n_obs is 1 */
+    const int32_t* point_obs_index;   /* 2 each */
+    const int32_t* point_ref_kf;      /* one of the observations' key frames */
+    const int64_t* point_first_kf;
+    const float* point_world;         /* 3 each */
+    /* per line creation */
+    const int32_t* line_handle;
+    const int32_t* line_n_obs;
+    const int32_t* line_obs_kf;
+    const int32_t* line_obs_index;
+    const int32_t* line_ref_kf;
+    const int64_t* line_first_kf;
+    /* out */
+    int32_t displaced_capacity[2];    /* entries of point_displaced, line_displaced: 2 per creation */
+    int32_t record_capacity;          /* entries of the four arrays below: 1 per point creation */
+    int32_t pad;
+    int32_t* point_displaced;         /* 2 each: the handle that stood in the row entry or -1; -1 for an observation not given */
+    int32_t* line_displaced;
+    float* normal;                    /* 3 each, or NULL: no UpdateNormalAndDepth, the next three are not written */
+    float* max_distance;
+    float* min_distance;
+    uint8_t* status;                  /* DRFE_UPKEEP_NORMAL */
+} drfe_lmap_create_call;
+/* creations of both kinds in a call from which drfe_lmap_create_batch of a store with a context uses the device.  Measured
+ * (profiles/create_timing.jsonl: a call followed by one update on the device) the device entry loses at one
+ * creation on stores of 100, 1 000 and 4 000 key frames (0.85x to 0.97x of the host entry's speed) and wins at 64 on all three
+ * (1.6x, 1.9x, 2.3x), at 512 (3.8x to 4.3x) and at 4 096 (5.1x to 6.3x): 64 is the smallest measured call size from which it wins
+ * at every store size.  Most of the margin is the host entry's upload of one copy per touched row entry. */
+enum { DRFE_LMAP_CREATE_DEVICE_FROM = 64 };
+/* _host always runs on the host, _device always on the device (DRFE_ERR_STATE without a context; DRFE_ERR_CAPACITY when the
+ * configured scratch does not hold the call with one tile of creations a chunk), _batch on the device from
+ * DRFE_LMAP_CREATE_DEVICE_FROM creations when the call fits.  All three return the same bytes and leave the same store.  Refused,
+ * and nothing changes: DRFE_ERR_INVALID for a handle the store already holds, a handle that stands twice in the call, a negative
+ * handle, an unknown key frame, an index outside the key frame's row, 0 or more than 2 observations, a reference key frame that is
+ * not among the creation's observations; DRFE_ERR_STATE with the item's name for a named key frame of a point without culling
+ * attributes that fit its row and, with normals, missing scales, a missing pose of an observer, an octave outside the scales;
+ * DRFE_ERR_CAPACITY for an output array that is too small.  The host settles every refusal before the first launch.  The device
+ * entry needs handles that qualify for the append (else it runs on the host: there is no slot to write); it writes the new slots
+ * of the rows, attribute, recent-list and (when current) geometry blocks and the row entries in place, so that only the records
+ * come back and the next call of any kind uploads nothing of them (drfe_lmap_upload_bytes); the adjustment block gets its tail
+ * with the next call that needs it. */
+int drfe_lmap_create_host(drfe_lmap* db, drfe_lmap_create_call* call);
+int drfe_lmap_create_device(drfe_lmap* db, drfe_lmap_create_call* call, void* stream);
+int drfe_lmap_create_batch(drfe_lmap* db, drfe_lmap_create_call* call, void* stream);
+/* out[0] creations of one workgroup of the device's launches (a chunk is a whole number of them), [1] lanes of a wavefront, [2]
+ * bytes of scratch per stored row entry (its claim word), [3] bytes of scratch per creation of a chunk, [4] the workgroup size,
+ * [5] 0, [6] DRFE_LMAP_CREATE_DEVICE_FROM, [7] 0 */
+int drfe_lmap_create_limits(int32_t* out8);
+/* the scratch a device call of n_points and n_lines creations takes: out[0] bytes with which each kind runs as one chunk, [1] the
+ * least bytes with which it runs at all (one workgroup of creations a chunk), [2] the part every chunk shares (the claim words) */
+int drfe_lmap_create_scratch(drfe_lmap* db, int32_t n_points, int32_t n_lines, int64_t* out3);
+/* Counters since the store was created: stats[0] calls, [1] calls run on the device, [2] points created, [3] lines created,
+ * [4] row entries displaced, [5] calls that left the image stale, [6] block relayouts, [7] chunks run on the device. */
+int drfe_lmap_create_stats(drfe_lmap* db, int64_t* stats /* 8 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

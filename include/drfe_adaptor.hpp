@@ -4230,6 +4230,41 @@ public:
         }
         return records;
     }
+    /* The tail of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:522-535) on the store for the
+     * already constructed points vpMPs[t] = new MapPoint(x3D, pRefKF, mpMap): point t is observed by kf1[t] at idx1[t] and by
+     * kf2[t] at idx2[t], in that order, as the reference calls AddObservation; pRefKF is the key frame it was constructed with
+     * (mpCurrentKeyFrame; the first key frame in CreateInitialMapMonocular, where it stands second).  world[t] is x3D as 3 floats.
+     * The store must hold the current rows and culling attributes of the named key frames (Sync, SyncCulling) and - with normals
+     * - their poses and the scales (SyncGeometry).  The store creates and commits; then every object gets what the reference
+     * gives it: AddObservation, AddMapPoint on both key frames, and the tracker learns the object (as Sync does).  Returns one
+     * record per point in order, as ProcessNewKeyFrame returns them (status DRFE_UPKEEP_NORMAL with the normal and the two
+     * distances of its UpdateNormalAndDepth: assign them the way the upkeep batch's are assigned; best_obs and descriptor unset:
+     * ComputeDistinctiveDescriptors stays with the upkeep batch).  Map::AddMapPoint and the push onto mlpRecentAddedMapPoints
+     * stay with the caller.  Further accessors: MapPointT mnFirstKFid; KeyFrameT AddMapPoint(MapPointT*, size_t). */
+    std::vector<drfe::MapPointUpkeep> CreateMapPoints(const std::vector<MapPointT*>& vpMPs, const std::vector<KeyFrameT*>& kf1,
+                                                      const std::vector<size_t>& idx1, const std::vector<KeyFrameT*>& kf2,
+                                                      const std::vector<size_t>& idx2, KeyFrameT* pRefKF, const float* world, bool normals = true)
+    {
+        return CreatePoints(vpMPs, kf1, idx1, &kf2, &idx2, pRefKF, world, normals);
+    }
+    /* the single-observer form: CreateNewKeyFrame's two loops and StereoInitialization (src/Tracking.cc:3097-3103, :3145-3150,
+     * :1579-1589), every point observed by pKF alone, at idx[t] */
+    std::vector<drfe::MapPointUpkeep> CreateMapPoints(const std::vector<MapPointT*>& vpMPs, KeyFrameT* pKF, const std::vector<size_t>& idx,
+                                                      const float* world, bool normals = true)
+    {
+        return CreatePoints(vpMPs, std::vector<KeyFrameT*>(vpMPs.size(), pKF), idx, nullptr, nullptr, pKF, world, normals);
+    }
+    /* The tail of LocalMapping::CreateNewMapLines2 (src/LocalMapping.cc:1019-1031) for the already constructed lines: as
+     * CreateMapPoints, with AddMapLine; the store holds no line geometry, so UpdateAverageDir stays with the upkeep batch. */
+    void CreateMapLines(const std::vector<MapLineT*>& vpMLs, const std::vector<KeyFrameT*>& kf1, const std::vector<size_t>& idx1,
+                        const std::vector<KeyFrameT*>& kf2, const std::vector<size_t>& idx2, KeyFrameT* pRefKF)
+    {
+        CreateLines(vpMLs, kf1, idx1, &kf2, &idx2, pRefKF);
+    }
+    void CreateMapLines(const std::vector<MapLineT*>& vpMLs, KeyFrameT* pKF, const std::vector<size_t>& idx)
+    {
+        CreateLines(vpMLs, std::vector<KeyFrameT*>(vpMLs.size(), pKF), idx, nullptr, nullptr, pKF);
+    }
     /* mpReplaced of pMP as the store holds it: the handle, or -1 */
     int32_t Replaced(MapPointT* pMP)
     {
@@ -4245,6 +4280,92 @@ private:
     void Check(int rc, const char* what) const
     {
         if (rc != DRFE_OK) throw std::runtime_error(std::string(what) + ": " + drfe_lmap_last_error(mDb));
+    }
+    /* the arrays of one kind of a drfe_lmap_create_call */
+    struct CreateArrays {
+        std::vector<int32_t> handle, nObs, kf, idx, ref, displaced;
+        std::vector<int64_t> first;
+    };
+    template <class ItemT>
+    static CreateArrays CreateFill(const std::vector<ItemT*>& items, const std::vector<KeyFrameT*>& kf1, const std::vector<size_t>& idx1,
+                                   const std::vector<KeyFrameT*>* kf2, const std::vector<size_t>* idx2, KeyFrameT* pRefKF)
+    {
+        const size_t n = items.size();
+        CreateArrays A;
+        A.handle.resize(n); A.nObs.resize(n); A.kf.assign(2 * n, 0); A.idx.assign(2 * n, 0); A.ref.resize(n); A.first.resize(n);
+        A.displaced.assign(2 * n + 1, -1);
+        for (size_t t = 0; t < n; t++) {
+            A.handle[t] = (int32_t)items[t]->mnId;
+            A.nObs[t] = kf2 ? 2 : 1;
+            A.kf[2 * t] = (int32_t)kf1[t]->mnId; A.idx[2 * t] = (int32_t)idx1[t];
+            if (kf2) { A.kf[2 * t + 1] = (int32_t)(*kf2)[t]->mnId; A.idx[2 * t + 1] = (int32_t)(*idx2)[t]; }
+            A.ref[t] = (int32_t)pRefKF->mnId;
+            A.first[t] = (int64_t)items[t]->mnFirstKFid;
+        }
+        return A;
+    }
+    int CreateCall(drfe_lmap_create_call* c)
+    {
+        return mForce < 0 ? drfe_lmap_create_host(mDb, c) : mForce > 0 ? drfe_lmap_create_device(mDb, c, nullptr) : drfe_lmap_create_batch(mDb, c, nullptr);
+    }
+    std::vector<drfe::MapPointUpkeep> CreatePoints(const std::vector<MapPointT*>& vpMPs, const std::vector<KeyFrameT*>& kf1,
+                                                   const std::vector<size_t>& idx1, const std::vector<KeyFrameT*>* kf2,
+                                                   const std::vector<size_t>* idx2, KeyFrameT* pRefKF, const float* world, bool normals)
+    {
+        const size_t n = vpMPs.size();
+        std::vector<drfe::MapPointUpkeep> records(n);
+        if (!n) return records;
+        CreateArrays A = CreateFill(vpMPs, kf1, idx1, kf2, idx2, pRefKF);
+        std::vector<float> nrm(3 * n), maxD(n), minD(n);
+        std::vector<uint8_t> status(n);
+        drfe_lmap_create_call c = {};
+        c.n_points = (int32_t)n;
+        c.point_handle = A.handle.data(); c.point_n_obs = A.nObs.data(); c.point_obs_kf = A.kf.data(); c.point_obs_index = A.idx.data();
+        c.point_ref_kf = A.ref.data(); c.point_first_kf = A.first.data(); c.point_world = world;
+        c.displaced_capacity[0] = (int32_t)(2 * n); c.record_capacity = (int32_t)n; c.point_displaced = A.displaced.data();
+        c.normal = normals ? nrm.data() : nullptr; c.max_distance = maxD.data(); c.min_distance = minD.data(); c.status = status.data();
+        {
+            std::unique_lock<std::mutex> lock(mMutex);
+            Check(CreateCall(&c), "drfe_lmap_create");
+            for (size_t t = 0; t < n; t++) mMPs[A.handle[t]] = vpMPs[t];
+        }
+        for (size_t t = 0; t < n; t++) {
+            /* the reference's tail on the objects */
+            vpMPs[t]->AddObservation(kf1[t], idx1[t]);
+            if (kf2) vpMPs[t]->AddObservation((*kf2)[t], (*idx2)[t]);
+            kf1[t]->AddMapPoint(vpMPs[t], idx1[t]);
+            if (kf2) (*kf2)[t]->AddMapPoint(vpMPs[t], (*idx2)[t]);
+            if (!normals) continue;
+            drfe::MapPointUpkeep& u = records[t];
+            u.status = status[t];
+            for (int k = 0; k < 3; k++) u.normal[k] = nrm[3 * t + (size_t)k];
+            u.max_distance = maxD[t];
+            u.min_distance = minD[t];
+        }
+        return records;
+    }
+    void CreateLines(const std::vector<MapLineT*>& vpMLs, const std::vector<KeyFrameT*>& kf1, const std::vector<size_t>& idx1,
+                     const std::vector<KeyFrameT*>* kf2, const std::vector<size_t>* idx2, KeyFrameT* pRefKF)
+    {
+        const size_t n = vpMLs.size();
+        if (!n) return;
+        CreateArrays A = CreateFill(vpMLs, kf1, idx1, kf2, idx2, pRefKF);
+        drfe_lmap_create_call c = {};
+        c.n_lines = (int32_t)n;
+        c.line_handle = A.handle.data(); c.line_n_obs = A.nObs.data(); c.line_obs_kf = A.kf.data(); c.line_obs_index = A.idx.data();
+        c.line_ref_kf = A.ref.data(); c.line_first_kf = A.first.data();
+        c.displaced_capacity[1] = (int32_t)(2 * n); c.line_displaced = A.displaced.data();
+        {
+            std::unique_lock<std::mutex> lock(mMutex);
+            Check(CreateCall(&c), "drfe_lmap_create");
+            for (size_t t = 0; t < n; t++) mMLs[A.handle[t]] = vpMLs[t];
+        }
+        for (size_t t = 0; t < n; t++) {
+            vpMLs[t]->AddObservation(kf1[t], idx1[t]);
+            if (kf2) vpMLs[t]->AddObservation((*kf2)[t], (*idx2)[t]);
+            kf1[t]->AddMapLine(vpMLs[t], idx1[t]);
+            if (kf2) (*kf2)[t]->AddMapLine(vpMLs[t], (*idx2)[t]);
+        }
     }
     void Increase(int kind, int32_t handle, int dFound, int dVisible)
     {
