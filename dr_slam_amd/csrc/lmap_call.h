@@ -1,5 +1,5 @@
 /* lmap_call.h — what the device entries of the local-map store share on the host (lmap.cpp, lmap_conn.cpp, lmap_correct.cpp,
- * lmap_cull.cpp, lmap_gba.cpp, lmap_recent.cpp, lmap_fuse.cpp, lmap_insert.cpp; DESIGN.md section 25, "A device call of the store"): the second-stage fetch, the
+ * lmap_cull.cpp, lmap_gba.cpp, lmap_recent.cpp, lmap_fuse.cpp, lmap_insert.cpp, lmap_essential.cpp; DESIGN.md section 25, "A device call of the store"): the second-stage fetch, the
  * mark of a call that writes resident blocks, the sequence around the launches and the body of a _stats getter.  An entry keeps
  * its checks, its layout, its launch record, its chunk rule and what it does with the results.  Host only; LmapFetch and
  * LmapWrites are free of HIP, as ResidentBlock is: the copy is the caller's. */

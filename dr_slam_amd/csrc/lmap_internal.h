@@ -1,5 +1,5 @@
 /* lmap_internal.h — what lmap.cpp, lmap_conn.cpp, lmap_correct.cpp, lmap_cull.cpp, lmap_gba.cpp, lmap_recent.cpp, lmap_fuse.cpp,
- * lmap_insert.cpp and lmap_create.cpp hand to the store's kernels (DESIGN.md sections 25 to 29 and 31 to 34).  The host's sequence around these launches is lmap_call.h's. */
+ * lmap_insert.cpp, lmap_create.cpp and lmap_essential.cpp hand to the store's kernels (DESIGN.md sections 25 to 29 and 31 to 35).  The host's sequence around these launches is lmap_call.h's. */
 #ifndef DRFE_LMAP_INTERNAL_H
 #define DRFE_LMAP_INTERNAL_H
 
@@ -13,6 +13,7 @@
 #include "fuse_core.h"
 #include "insert_core.h"
 #include "create_core.h"
+#include "essential_core.h"
 
 /* threads of a workgroup: frame points and key-frame slots go across them in the vote, the entries of a match row in the gather */
 #define LMAP_THREADS 256
@@ -470,5 +471,98 @@ struct GbaLaunch {
 hipError_t drfe_launch_gba_keyframes(const GbaLaunch& L, hipStream_t s);
 /* the points of the chunk: moved in place, then packed in slot order; groupCnt[workgroups] is their number */
 hipError_t drfe_launch_gba_points(const GbaLaunch& L, hipStream_t s);
+
+/* ---- what surrounds the solver of Optimizer::OptimizeEssentialGraph (essential_kernels.hip) ---- */
+/* point slots of one workgroup of the commit's point launch, a lane each; edges of one workgroup of the write launch */
+#define ESS_TILE LMAP_THREADS
+/* lanes of the wavefront that walks one unit of the edge builder, and the wavefronts of a workgroup */
+#define ESS_WAVE 64
+#define ESS_WAVES (LMAP_THREADS / ESS_WAVE)
+/* bytes of scratch per stored key frame of an edges call (its EssKf, its share of the unit words) and per edge of the host's bound
+ * (descriptor 5 bytes, record 73 bytes, rounded up) */
+#define ESS_VERTEX_BYTES 288
+#define ESS_EDGE_BYTES 88
+/* bytes of scratch per stored key frame of a commit call (its EssMove) and per point slot of a chunk (its record, 41 bytes,
+ * rounded up) */
+#define ESS_KF_BYTES 128
+#define ESS_POINT_BYTES 48
+/* bytes of scratch every call takes besides: alignment of the sections */
+#define ESS_FIXED_BYTES 1024
+
+/* One edges call.  Units 0 .. nLc are the rows of LoopConnections in rank order of their keys, units nLc .. nU the key frames of
+ * the map (the vertices) in rank order; the descriptors of unit u lie from capOff[u], a bound the host has from the row lengths. */
+struct EssEdgesLaunch {
+    LmapImage I;                   /* resident */
+    ConnImage C;                   /* resident */
+    CorrImage G;                   /* resident: the stored poses */
+    EssImage E;                    /* resident: the loop edges */
+    int32_t nV, nLc, nU, nPairs;
+    int32_t cur, loop;             /* slots */
+    int32_t bound;                 /* capOff[nU] */
+    /* staged */
+    const int32_t* kfHandle;       /* nK */
+    const int32_t* vert;           /* nV slots */
+    const int32_t* tab;            /* nK: the key frame's row of the two tables, or -1 */
+    const double* corrected;       /* 8 per row */
+    const double* nonCorrected;
+    const int32_t* lcKey;          /* nLc slots */
+    const int32_t* lcOff;          /* nLc + 1 */
+    const int32_t* lcKf;           /* member slots, ascending within a row */
+    const uint64_t* pairKey;       /* nPairs: every entry as ess_pair, ascending */
+    const int32_t* pairI;          /* its key */
+    const int32_t* pairJ;          /* its member */
+    const int32_t* capOff;         /* nU + 1 */
+    /* scratch */
+    EssKf* kf;                     /* nK, written for the vertices */
+    int32_t* cnt;                  /* nU + 2: edges of each unit, then their exclusive prefix, the total and the emptied prefixes */
+    uint8_t* emptied;              /* nU */
+    int32_t* dTo;                  /* bound: the other end of each descriptor, a slot */
+    uint8_t* dKind;
+    /* out */
+    double* outScw;                /* nV x 8 */
+    int32_t* eFrom;                /* bound, filled to the total: slots */
+    int32_t* eTo;
+    double* eMeas;                 /* 8 each */
+    uint8_t* eKind;
+};
+/* the vertices' Sim3s, the descriptors and counts of every unit, their prefix: in stream order */
+hipError_t drfe_launch_essential_plan(const EssEdgesLaunch& L, hipStream_t s);
+/* a lane per edge of the total, which the host read back after the plan */
+hipError_t drfe_launch_essential_write(const EssEdgesLaunch& L, int32_t total, hipStream_t s);
+
+/* One commit call; a chunk is the point slots [p0, p1). */
+struct EssCommitLaunch {
+    LmapImage I;                   /* resident */
+    CorrImage G;                   /* resident: poses, centres and positions are written in place */
+    int32_t n;                     /* named key frames */
+    int32_t cur;                   /* handle */
+    int32_t p0, p1;
+    int32_t pkCap;                 /* records the packed arrays hold: the host's count of the fullest chunk */
+    /* staged */
+    const int32_t* named;          /* n slots, in the caller's order */
+    const int32_t* posOf;          /* nK: index in the call or -1 */
+    const double* scw;             /* n x 8 */
+    const double* optimised;       /* n x 8 */
+    const int32_t* kfHandle;       /* nK */
+    const int32_t* hSorted;        /* nK: the handles ascending */
+    const int32_t* hSlot;          /* nK: their slots */
+    const int32_t* grpOff;         /* per workgroup of the chunk: the moved points of the chunk before it (the host's count) */
+    /* scratch */
+    EssMove* mv;                   /* nK */
+    int32_t* pkItem;               /* point slot */
+    int32_t* pkRef;                /* nIDr as a handle */
+    float* pkWorld;                /* 3 each */
+    float* pkNormal;               /* 3 each */
+    float* pkMax;
+    float* pkMin;
+    uint8_t* pkStatus;
+    /* out */
+    float* outTiw;                 /* n x 16 */
+    double* outSwc;                /* n x 8 */
+};
+/* a lane per stored key frame: its EssMove, and for a named one the pose and centre in place and its record */
+hipError_t drfe_launch_essential_poses(const EssCommitLaunch& L, hipStream_t s);
+/* the points of the chunk: moved in place, packed in slot order */
+hipError_t drfe_launch_essential_points(const EssCommitLaunch& L, hipStream_t s);
 
 #endif

@@ -1,5 +1,5 @@
 /* lmap_store.cpp — the local-map store behind the C-ABI of include/drfe.h (lmap_store.h): its lifecycle, the setters of its rows,
- * the flat image of them, the bindings of the six resident blocks and the one function that brings them up to date on the device.
+ * the flat image of them, the bindings of the seven resident blocks and the one function that brings them up to date on the device.
  * DESIGN.md section 25, "The resident blocks". */
 #include "lmap_store.h"
 
@@ -168,6 +168,7 @@ int lmap_build_image(drfe_lmap* db)
     db->cullDirty = true;
     db->gbaDirty = true;
     db->recDirty = true;
+    db->essDirty = true;
     for (ResidentBlock& B : db->blk) B.stale_all();
     return DRFE_OK;
 }
@@ -241,6 +242,9 @@ static void bind_blocks(drfe_lmap* db)
     db->secRecObsOff = Rc.bind(Q.mlObsOff, &db->dRec.mlObsOff, &db->hRec.mlObsOff);
     Rc.bind(Q.mlObs, &db->dRec.mlObs, &db->hRec.mlObs);
     Rc.bind(Q.mlObsIdx, &db->dRec.mlObsIdx, &db->hRec.mlObsIdx);
+    ResidentBlock& Lp = db->blk[drfe_lmap::LOOPS];
+    Lp.bind(db->ess.leOff, &db->dEss.leOff, &db->hEss.leOff);
+    Lp.bind(db->ess.le, &db->dEss.le, &db->hEss.le);
 }
 
 void lmap_host_views(drfe_lmap* db)
@@ -257,7 +261,7 @@ void lmap_host_views(drfe_lmap* db)
 int lmap_upload(drfe_lmap* db, unsigned need, hipStream_t st)
 {
     lmap_host_views(db);
-    size_t staged = 0, all = 0, sent[drfe_lmap::BLOCKS] = {0, 0, 0, 0, 0, 0};
+    size_t staged = 0, all = 0, sent[drfe_lmap::BLOCKS] = {0, 0, 0, 0, 0, 0, 0};
     for (int b = 0; b < drfe_lmap::BLOCKS; b++) {
         if (!(need >> b & 1)) continue;
         /* a block that no longer fits is allocated at twice the size */
@@ -461,6 +465,7 @@ int drfe_lmap_remove(drfe_lmap* db, int kind, int32_t handle)
             db->kfPose.erase(handle);
             db->kfCull.erase(handle);
             db->kfGba.erase(handle);
+            db->loopEdges.erase(handle);
             gone = 1;
         }
     } else if (kind == DRFE_LMAP_POINT) {

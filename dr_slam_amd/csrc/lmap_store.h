@@ -1,12 +1,13 @@
 /* lmap_store.h — the local-map store itself: its rows by handle, the flat image of them, the optional geometry, culling attributes
- * and adjustment state by slot, and the six resident blocks that keep them on the device (resident_block.h).  lmap_store.cpp holds
+ * and adjustment state by slot, and the seven resident blocks that keep them on the device (resident_block.h).  lmap_store.cpp holds
  * its lifecycle, setters, image and upload; its entries are in lmap.cpp (Tracking::UpdateLocalMap),
  * lmap_conn.cpp (KeyFrame::UpdateConnections, section 26), lmap_correct.cpp (the Sim3 propagation of LoopClosing::CorrectLoop,
  * section 27), lmap_cull.cpp (LocalMapping::KeyFrameCulling with KeyFrame::SetBadFlag, section 28), lmap_gba.cpp (the map update
  * of LoopClosing::RunGlobalBundleAdjustment, section 29), lmap_recent.cpp (LocalMapping::MapPointCulling and MapLineCulling,
  * section 31), lmap_fuse.cpp (the fuse commit with MapPoint::Replace, section 32), lmap_insert.cpp (the item loops of
  * LocalMapping::ProcessNewKeyFrame, section 33) and lmap_create.cpp (map-point and map-line creation, appended in place, section
- * 34).  What the device paths of the first eight share around their launches is lmap_call.h. */
+ * 34) and lmap_essential.cpp (what surrounds the solver of Optimizer::OptimizeEssentialGraph, section 35).  What the device paths
+ * share around their launches is lmap_call.h. */
 #ifndef DRFE_LMAP_STORE_H
 #define DRFE_LMAP_STORE_H
 
@@ -119,6 +120,13 @@ struct RecentAttr {
     bool complete = false;             /* every stored point and line has them and every index is inside its observer's row */
 };
 
+/* mspLoopEdges by slot, next to the image: the known members of each row in ascending slot, and the
+ * members no stored key frame answers to, which a call looks at when their edge would be added */
+struct EssAttr {
+    std::vector<int32_t> leOff, le;
+    std::vector<std::pair<int32_t, int32_t>> unknown;   /* (key-frame slot, member handle) */
+};
+
 /* the graph with every handle resolved to a slot: what the host walk and the kernels read */
 struct Image {
     std::vector<int32_t> kfHandle, mpHandle, mlHandle;   /* by slot */
@@ -161,7 +169,7 @@ struct drfe_lmap {
     std::unordered_map<int32_t, lmap_store::MpCull> mpCull;
     lmap_store::CullAttr cull;
     bool cullDirty = true;             /* the attribute image lacks an edit of the rows or of the attributes */
-    int64_t sentBytes[6] = {0, 0, 0, 0, 0, 0};   /* host-to-device bytes of the rows, graph, geometry, attribute, adjustment and recent-list blocks */
+    int64_t sentBytes[7] = {0, 0, 0, 0, 0, 0, 0};   /* host-to-device bytes of the rows, graph, geometry, attribute, adjustment, recent-list and loop-edge blocks */
     int64_t cullStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     /* the optional state of the map update after a global bundle adjustment, by handle, and by slot */
     std::unordered_map<int32_t, lmap_store::KfGba> kfGba;
@@ -181,12 +189,17 @@ struct drfe_lmap {
     int64_t fuseStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int64_t insStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};    /* of the item loops of ProcessNewKeyFrame */
     int64_t createStats[8] = {0, 0, 0, 0, 0, 0, 0, 0}; /* of map-point and map-line creation */
+    /* the optional loop edges, by handle, and by slot */
+    std::unordered_map<int32_t, std::vector<int32_t>> loopEdges;
+    lmap_store::EssAttr ess;
+    bool essDirty = true;              /* the loop edges by slot lack an edit of the rows or of the loop edges */
+    int64_t essStats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     /* the host walk's stamps, kept between calls: an item is stamped for the query whose serial it holds */
     std::vector<int32_t> stampP, stampL, inP, inL;
     int32_t serial = 0;
     /* the resident blocks, in upload order, with their device memory; the views of them the kernels take (d...) and the host walks
      * (h...); the sections that edits mark by name (lmap_store.cpp binds them) */
-    enum { ROWS, GRAPH, GEO, ATTR, GBA, RECENT, BLOCKS };
+    enum { ROWS, GRAPH, GEO, ATTR, GBA, RECENT, LOOPS, BLOCKS };
     ResidentBlock blk[BLOCKS];
     DevBuf<char> dev[BLOCKS];
     LmapImage dView = {}, hView = {};
@@ -195,6 +208,7 @@ struct drfe_lmap {
     CullImage dCull = {}, hCull = {};
     GbaImage dGba = {};
     RecentImage dRec = {}, hRec = {};
+    EssImage dEss = {}, hEss = {};
     int secMlBad = 0, secKfMp = 0, secKfMl = 0, secObsOff = 0, secNObs = 0, secObsIdx = 0, secRecCounters = 0, secRecObsOff = 0;
     StagePair io;
     DevBuf<char> scratch;
@@ -209,7 +223,8 @@ int lmap_build_image(drfe_lmap* db);
 void lmap_host_views(drfe_lmap* db);
 /* the blocks of `need` (bit b = block b; a later block implies the rows and the graph) brought up to date in block order: the stale
  * runs staged back to back, one synchronisation.  A call's build_* runs before it. */
-enum { LMAP_NEED_IMAGE = 3, LMAP_NEED_GEO = 3 | 4, LMAP_NEED_ATTR = 3 | 8, LMAP_NEED_GBA = 3 | 4 | 16, LMAP_NEED_RECENT = 3 | 8 | 32 };
+enum { LMAP_NEED_IMAGE = 3, LMAP_NEED_GEO = 3 | 4, LMAP_NEED_ATTR = 3 | 8, LMAP_NEED_GBA = 3 | 4 | 16, LMAP_NEED_RECENT = 3 | 8 | 32,
+       LMAP_NEED_LOOPS = 3 | 4 | 64 };
 int lmap_upload(drfe_lmap* db, unsigned need, hipStream_t st);
 bool lmap_offsets_ok(const int32_t* off, int n);
 /* lmap_correct.cpp's, for lmap_gba.cpp: the geometry by slot, rebuilt when stale */

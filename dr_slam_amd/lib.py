@@ -89,6 +89,10 @@ SYMBOLS = (
     "drfe_lmap_insert_host", "drfe_lmap_insert_device", "drfe_lmap_insert_batch", "drfe_lmap_insert_limits", "drfe_lmap_insert_scratch",
     "drfe_lmap_insert_stats", "drfe_lmap_create_host", "drfe_lmap_create_device", "drfe_lmap_create_batch",
     "drfe_lmap_create_limits", "drfe_lmap_create_scratch", "drfe_lmap_create_stats",
+    "drfe_lmap_set_loop_edges", "drfe_lmap_get_loop_edges", "drfe_lmap_essential_upload_bytes", "drfe_lmap_essential_edges_host",
+    "drfe_lmap_essential_edges_device", "drfe_lmap_essential_edges_batch", "drfe_lmap_essential_commit_host",
+    "drfe_lmap_essential_commit_device", "drfe_lmap_essential_commit_batch", "drfe_lmap_essential_limits",
+    "drfe_lmap_essential_scratch", "drfe_lmap_essential_stats",
 )
 
 FAST_CELL_DTYPE = np.dtype([(n, "<i4") for n in ("level", "x0", "y0", "ww", "wh", "offX", "offY", "cellIdx", "ncp", "rpl", "nrb",
@@ -448,6 +452,29 @@ class LmapInsertCall(C.Structure):
         (k, C.c_void_p) for k in LMAP_INSERT_CALL_FIELDS]                           # drfe_lmap_insert_call
 
 
+LMAP_ESSENTIAL_STATS = ("edges_calls", "commit_calls", "device_calls", "vertices", "edges", "points_moved", "points_identity",
+                        "prefixes_emptied")
+LMAP_ESSENTIAL_LIMITS = ("threads", "wavefront", "edges_device_from", "commit_device_from", "point_bytes", "kf_bytes", "edge_bytes",
+                         "vertex_bytes")
+ESSENTIAL_MIN_FEAT = 100                                                             # DRFE_LMAP_ESSENTIAL_MIN_FEAT
+ESSENTIAL_LOOP_CONNECTION, ESSENTIAL_SPANNING_TREE, ESSENTIAL_LOOP_EDGE, ESSENTIAL_COVISIBILITY = 0, 1, 2, 3   # ..._edges_call.kind
+LMAP_ESSENTIAL_EDGES_IN = ("sim3_handles", "corrected", "non_corrected", "lc_handles", "lc_offsets", "lc_kfs")
+LMAP_ESSENTIAL_EDGES_OUT = ("n_vertices", "vertices", "Scw", "fixed", "n_edges", "from", "to", "measurement", "kind")
+LMAP_ESSENTIAL_COMMIT_OUT = ("Tiw", "Swc", "n_points", "points", "ref", "world", "normal", "max_distance", "min_distance", "status")
+
+
+class LmapEssentialEdgesCall(C.Structure):
+    _fields_ = ([(k, C.c_int32) for k in ("loop_kf", "cur_kf", "n_sim3", "n_lc")] + [(k, C.c_void_p) for k in LMAP_ESSENTIAL_EDGES_IN] +
+                [("vertices_capacity", C.c_int32), ("edges_capacity", C.c_int32)] +
+                [(k, C.c_void_p) for k in LMAP_ESSENTIAL_EDGES_OUT])                 # drfe_lmap_essential_edges_call
+
+
+class LmapEssentialCommitCall(C.Structure):
+    _fields_ = ([("cur_kf", C.c_int32), ("n", C.c_int32)] + [(k, C.c_void_p) for k in ("handles", "Scw", "optimised")] +
+                [("points_capacity", C.c_int32), ("pad", C.c_int32)] +
+                [(k, C.c_void_p) for k in LMAP_ESSENTIAL_COMMIT_OUT])                # drfe_lmap_essential_commit_call
+
+
 LMAP_CREATE_STATS = ("calls", "device_calls", "points_created", "lines_created", "displaced", "stale_calls", "relayouts", "device_chunks")
 LMAP_CREATE_LIMITS = ("tile", "wavefront", "claim_bytes", "item_bytes", "threads", "reserved0", "device_from", "reserved1")
 LMAP_CREATE_IN_FIELDS = ("point_handle", "point_n_obs", "point_obs_kf", "point_obs_index", "point_ref_kf", "point_first_kf", "point_world",
@@ -799,6 +826,18 @@ def load() -> C.CDLL:
     L.drfe_lmap_create_limits.argtypes = [vp]
     L.drfe_lmap_create_scratch.argtypes = [vp, i32, i32, vp]
     L.drfe_lmap_create_stats.argtypes = [vp, vp]
+    L.drfe_lmap_set_loop_edges.argtypes = [vp, i32, vp, vp, vp]
+    L.drfe_lmap_get_loop_edges.argtypes = [vp, i32, vp, i32, vp, vp]
+    L.drfe_lmap_essential_upload_bytes.argtypes = [vp, vp]
+    L.drfe_lmap_essential_edges_host.argtypes = [vp, vp]
+    L.drfe_lmap_essential_edges_device.argtypes = [vp, vp, vp]
+    L.drfe_lmap_essential_edges_batch.argtypes = [vp, vp, vp]
+    L.drfe_lmap_essential_commit_host.argtypes = [vp, vp]
+    L.drfe_lmap_essential_commit_device.argtypes = [vp, vp, vp]
+    L.drfe_lmap_essential_commit_batch.argtypes = [vp, vp, vp]
+    L.drfe_lmap_essential_limits.argtypes = [vp]
+    L.drfe_lmap_essential_scratch.argtypes = [vp, i32, vp]
+    L.drfe_lmap_essential_stats.argtypes = [vp, vp]
     L.drfe_lmap_get_replaced.argtypes = [vp, i32, i32, vp, vp]
     L.drfe_lmap_get_match_row.argtypes = [vp, i32, i32, i32, vp, vp]
     L.drfe_lmap_get_observers.argtypes = [vp, i32, i32, i32, vp, vp, vp]
@@ -2638,6 +2677,109 @@ class LocalMap:
         res = {"point_displaced": out["point_displaced"][:nP].copy(), "line_displaced": out["line_displaced"][:nL].copy()}
         if normals:
             res.update({k: out[k][:nP].copy() for k in ("normal", "max_distance", "min_distance", "status")})
+        return res
+
+    # ---- what surrounds the solver of Optimizer::OptimizeEssentialGraph on the store ----
+
+    @staticmethod
+    def essential_limits():
+        out = np.zeros(8, np.int32)
+        rc = load().drfe_lmap_essential_limits(_p(out))
+        if rc != 0:
+            raise DrfeError(f"drfe_lmap_essential_limits failed ({rc})")
+        return dict(zip(LMAP_ESSENTIAL_LIMITS, (int(v) for v in out)))
+
+    def essential_stats(self):
+        st = np.zeros(8, np.int64)
+        self._chk(self.L.drfe_lmap_essential_stats(self.h, _p(st)), "drfe_lmap_essential_stats")
+        return dict(zip(LMAP_ESSENTIAL_STATS, (int(v) for v in st)))
+
+    def essential_scratch(self, lc_entries=0):
+        """bytes of device scratch on the store as it is: dict of edges (an edges call with that many loop-connection members, as a
+        whole), edges_fixed, commit_whole, commit_least, commit_fixed, and edge_bound (the edges the bound counts)"""
+        out = np.zeros(6, np.int64)
+        self._chk(self.L.drfe_lmap_essential_scratch(self.h, int(lc_entries), _p(out)), "drfe_lmap_essential_scratch")
+        return dict(zip(("edges", "edges_fixed", "commit_whole", "commit_least", "commit_fixed", "edge_bound"), (int(v) for v in out)))
+
+    def essential_upload_bytes(self):
+        """host-to-device bytes of the loop-edge block since the store was made"""
+        out = np.zeros(1, np.int64)
+        self._chk(self.L.drfe_lmap_essential_upload_bytes(self.h, _p(out)), "drfe_lmap_essential_upload_bytes")
+        return int(out[0])
+
+    def set_loop_edges(self, rows):
+        """rows: (handle, [loop-edge handles]) pairs: mspLoopEdges of each key frame; a row replaces the stored one"""
+        rows = [(int(h), [int(e) for e in es]) for h, es in rows]
+        hs = np.array([h for h, _ in rows], np.int32)
+        off = np.zeros(len(rows) + 1, np.int32)
+        off[1:] = np.cumsum([len(es) for _, es in rows])
+        ed = np.array([e for _, es in rows for e in es], np.int32)
+        self._chk(self.L.drfe_lmap_set_loop_edges(self.h, len(hs), _p(hs), _p(off), _p(ed) if len(ed) else None),
+                  "drfe_lmap_set_loop_edges")
+
+    def get_loop_edges(self, handles):
+        """the stored rows, each in ascending rank: a list of int32 arrays"""
+        hs = np.ascontiguousarray(handles, np.int32)
+        off = np.zeros(len(hs) + 1, np.int32)
+        ed = np.zeros(64, np.int32)
+        rc = self.L.drfe_lmap_get_loop_edges(self.h, len(hs), _p(hs), len(ed), _p(off), _p(ed))
+        if rc == ERR_CAPACITY:
+            ed = np.zeros(int(off[len(hs)]), np.int32)
+            rc = self.L.drfe_lmap_get_loop_edges(self.h, len(hs), _p(hs), len(ed), _p(off), _p(ed))
+        self._chk(rc, "drfe_lmap_get_loop_edges")
+        return [ed[off[i]:off[i + 1]].copy() for i in range(len(hs))]
+
+    def essential_edges(self, loop_kf, cur_kf, sim3=(), loop_connections=(), mode="batch", capacity=None):
+        """The vertices and the ordered edge list of OptimizeEssentialGraph (src/Optimizer.cc:2910-3080).  sim3: (handle, corrected,
+        non_corrected) rows, each Sim3 as (qx, qy, qz, qw, tx, ty, tz, s); loop_connections: (key, [members]) rows.  Returns a dict:
+        per vertex in rank order vertices, Scw [v, 8], fixed; per edge in addEdge order from, to, measurement [e, 8], kind.
+        capacity: (vertices, edges), default the bound that always suffices.  The store is not changed."""
+        sim3, lcs = list(sim3), [(int(k), [int(m) for m in ms]) for k, ms in loop_connections]
+        a = {"sim3_handles": np.array([r[0] for r in sim3], np.int32),
+             "corrected": np.array([r[1] for r in sim3], np.float64).reshape(len(sim3), 8),
+             "non_corrected": np.array([r[2] for r in sim3], np.float64).reshape(len(sim3), 8),
+             "lc_handles": np.array([k for k, _ in lcs], np.int32), "lc_offsets": np.zeros(len(lcs) + 1, np.int32),
+             "lc_kfs": np.array([m for _, ms in lcs for m in ms], np.int32)}
+        a["lc_offsets"][1:] = np.cumsum([len(ms) for _, ms in lcs])
+        if capacity is None:
+            capacity = (self.size()[0], self.essential_scratch(len(a["lc_kfs"]))["edge_bound"])
+        cv, ce = (int(v) for v in capacity)
+        v, e = max(1, cv), max(1, ce)
+        r = {"n_vertices": np.zeros(1, np.int32), "vertices": np.zeros(v, np.int32), "Scw": np.zeros((v, 8), np.float64),
+             "fixed": np.zeros(v, np.uint8), "n_edges": np.zeros(1, np.int32), "from": np.zeros(e, np.int32), "to": np.zeros(e, np.int32),
+             "measurement": np.zeros((e, 8), np.float64), "kind": np.zeros(e, np.uint8)}
+        call = LmapEssentialEdgesCall(int(loop_kf), int(cur_kf), len(sim3), len(lcs),
+                                      *[_p(a[k]) if len(a[k]) else None for k in LMAP_ESSENTIAL_EDGES_IN[:3]],
+                                      *[_p(a[k]) for k in LMAP_ESSENTIAL_EDGES_IN[3:]], cv, ce,
+                                      *[_p(r[k]) for k in LMAP_ESSENTIAL_EDGES_OUT])
+        fn = getattr(self.L, f"drfe_lmap_essential_edges_{mode}")
+        self._chk(fn(*((self.h, C.byref(call)) + (() if mode == "host" else (None,)))), f"drfe_lmap_essential_edges_{mode}")
+        nv, ne = int(r["n_vertices"][0]), int(r["n_edges"][0])
+        res = {k: r[k][:nv].copy() for k in ("vertices", "Scw", "fixed")}
+        res.update({k: r[k][:ne].copy() for k in ("from", "to", "measurement", "kind")})
+        return res
+
+    def essential_commit(self, cur_kf, handles, Scw, optimised, mode="batch", capacity=None):
+        """The tail of OptimizeEssentialGraph (src/Optimizer.cc:3088-3131): the vertices `handles` with the Scw the edges call gave
+        and the solver's estimates `optimised` [n, 8].  Returns a dict: per named key frame Tiw [n, 4, 4] and Swc [n, 8]
+        (vCorrectedSwc, for the caller's lines and planes); per moved point in ascending handle points, ref (nIDr), world, normal,
+        max_distance, min_distance, status.  capacity: moved points, default the stored points.  Commits poses and positions."""
+        hs = np.ascontiguousarray(handles, np.int32)
+        n = len(hs)
+        S = np.ascontiguousarray(Scw, np.float64).reshape(n, 8)
+        O = np.ascontiguousarray(optimised, np.float64).reshape(n, 8)
+        cap = self.size()[1] if capacity is None else int(capacity)
+        k, m = max(1, n), max(1, cap)
+        r = {"Tiw": np.zeros((k, 4, 4), np.float32), "Swc": np.zeros((k, 8), np.float64), "n_points": np.zeros(1, np.int32),
+             "points": np.zeros(m, np.int32), "ref": np.zeros(m, np.int32), "world": np.zeros((m, 3), np.float32),
+             "normal": np.zeros((m, 3), np.float32), "max_distance": np.zeros(m, np.float32), "min_distance": np.zeros(m, np.float32),
+             "status": np.zeros(m, np.uint8)}
+        call = LmapEssentialCommitCall(int(cur_kf), n, _p(hs), _p(S), _p(O), cap, 0, *[_p(r[f]) for f in LMAP_ESSENTIAL_COMMIT_OUT])
+        fn = getattr(self.L, f"drfe_lmap_essential_commit_{mode}")
+        self._chk(fn(*((self.h, C.byref(call)) + (() if mode == "host" else (None,)))), f"drfe_lmap_essential_commit_{mode}")
+        nm = int(r["n_points"][0])
+        res = {f: r[f][:n].copy() for f in ("Tiw", "Swc")}
+        res.update({f: r[f][:nm].copy() for f in LMAP_ESSENTIAL_COMMIT_OUT[3:]})
         return res
 
     # ---- the map update of LoopClosing::RunGlobalBundleAdjustment on the store (DESIGN.md section 29) ----

@@ -2585,6 +2585,149 @@ int drfe_lmap_create_scratch(drfe_lmap* db, int32_t n_points, int32_t n_lines, i
  * [4] row entries displaced, [5] calls that left the image stale, [6] block relayouts, [7] chunks run on the device. */
 int drfe_lmap_create_stats(drfe_lmap* db, int64_t* stats /* 8 */);
 
+/* What surrounds the solver of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:2894-3205, called at src/LoopClosing.cc:613)
+ * on the same store: before it the vertices and the ordered edge list with their double Sim3 measurements (:2910-3080), after it
+ * the pose of every key frame and the move of every map point with UpdateNormalAndDepth (:3088-3131).  The solver itself, a sparse
+ * Cholesky with an ordering, stays with the caller, as the adjustment of section 29 does.  DESIGN.md section 35.  Parity with a
+ * build of g2o's sim3.h is not pinned (no Eigen here): g2o::Sim3's product, inverse and map are read as in sections 22 and 27.
+ * The store holds no line or plane geometry: map lines and planes (:3134-3204) are not touched, and the commit returns
+ * vCorrectedSwc per key frame so that the caller moves them.
+ *
+ * mspLoopEdges per key frame, as handles.  The state is optional: a store that is never given it has empty rows and behaves as
+ * before.  Rows are CSR (offsets[0] = 0, count + 1 entries); a row replaces the stored one and the last row of a handle wins; a
+ * negative handle or a member named twice in a row: DRFE_ERR_INVALID, nothing changed.  A row may name key frames that are not
+ * stored (yet); drfe_lmap_remove of a key frame drops its row.  The state lies in a device block of its own: an edit of it sends
+ * no other block again (drfe_lmap_essential_upload_bytes). */
+int drfe_lmap_set_loop_edges(drfe_lmap* db, int32_t count, const int32_t* handles, const int32_t* offsets, const int32_t* edges);
+/* the rows of `count` stored key frames (an unknown handle: DRFE_ERR_INVALID), each in ascending rank, members that are not stored
+ * last in ascending handle; offsets gets count + 1 entries; DRFE_ERR_CAPACITY when capacity holds fewer than offsets[count] */
+int drfe_lmap_get_loop_edges(drfe_lmap* db, int32_t count, const int32_t* handles, int32_t capacity, int32_t* offsets, int32_t* edges);
+/* host-to-device bytes of the loop-edge block since the store was created (the seventh block, next to drfe_lmap_upload_bytes) */
+int drfe_lmap_essential_upload_bytes(drfe_lmap* db, int64_t* out1);
+
+/* const int minFeat = 100 of the reference; not an argument */
+enum { DRFE_LMAP_ESSENTIAL_MIN_FEAT = 100 };
+/* drfe_lmap_essential_edges_call.kind */
+enum { DRFE_LMAP_ESSENTIAL_LOOP_CONNECTION = 0, DRFE_LMAP_ESSENTIAL_SPANNING_TREE = 1, DRFE_LMAP_ESSENTIAL_LOOP_EDGE = 2,
+       DRFE_LMAP_ESSENTIAL_COVISIBILITY = 3 };
+
+/* The edge builder.  Handles are mnId, as everywhere on this store: every `mnId <` of the reference and the (min, max) pair of
+ * sInsertedEdges are on handles.
+ *
+ * Kept from the reference.  The key frames of the map are the stored key frames that are not bad, in rank order; a stored bad key
+ * frame gets no vertex and is walked by none of the loops.  vScw of a vertex is its `corrected` row when the table names it, else
+ * Sim3(Rcw, tcw, 1.0) of the stored pose; `fixed` is set exactly for loop_kf.  Loop-connection edges come first, keys in rank
+ * order and members in rank order: a member j of key i is skipped when (i != cur_kf || j != loop_kf) && GetWeight(i, j) < 100,
+ * GetWeight read from i's stored weights row, 0 when absent; Sji = vScw[j] * vScw[i].inverse(); the pair enters the inserted set
+ * only with its edge; non_corrected is not used.  Then one pass per key frame in rank order, Swi the inverse of its non_corrected
+ * row when the table names it, else of vScw[i], and Sjw of the other end likewise: the parent edge when there is a parent; the
+ * stored loop edges with a smaller handle in rank order; the edges of GetCovisiblesByWeight(100), which is the prefix of the
+ * stored ordered row with weight >= 100, EMPTY when that prefix is the whole row (upper_bound returning end(),
+ * src/KeyFrame.cc:268-270), in stored order, less every entry that is the parent, a child, a loop edge, bad, not of a smaller
+ * handle or in the inserted set.
+ *
+ * Refused, and nothing is counted: DRFE_ERR_INVALID for a handle that stands twice in the table, a key that stands twice in
+ * lc_handles or a member twice in its row; DRFE_ERR_STATE for loop_kf or cur_kf unknown, for a key or member of the loop
+ * connections that is not stored, for a key frame of the map without a pose that the table does not name, and, with a message that
+ * names the edge, for every edge the reference would add to a null vertex: a parent, a loop edge of a smaller handle or a kept
+ * loop-connection member that is bad (a loop edge: or not stored), and a kept member of a bad key; DRFE_ERR_CAPACITY for an output
+ * array that is too small.  A call never changes the store. */
+typedef struct drfe_lmap_essential_edges_call {
+    int32_t loop_kf, cur_kf;
+    /* LoopClosing::KeyFrameAndPose, both tables over the same handles, each once; a handle that is not stored is ignored */
+    int32_t n_sim3;
+    int32_t n_lc;                     /* keys of LoopConnections */
+    const int32_t* sim3_handles;
+    const double* corrected;          /* 8 each, the layout of drfe_lmap_correct_out: qx qy qz qw tx ty tz s */
+    const double* non_corrected;
+    const int32_t* lc_handles;        /* n_lc, any order */
+    const int32_t* lc_offsets;        /* n_lc + 1 */
+    const int32_t* lc_kfs;            /* the members, any order */
+    int32_t vertices_capacity;        /* the number of stored key frames always suffices */
+    int32_t edges_capacity;           /* lc_offsets[n_lc] + the stored key frames + the entries of their loop-edge rows and of
+                                       * their ordered rows always suffices */
+    /* per vertex, in rank order */
+    int32_t* n_vertices;              /* 1 */
+    int32_t* vertices;                /* handles */
+    double* Scw;                      /* 8 each: the estimate the vertex is given */
+    uint8_t* fixed;
+    /* per edge, in the order of the reference's addEdge: the host solver sums in it */
+    int32_t* n_edges;                 /* 1 */
+    int32_t* from;                    /* vertex 0, i */
+    int32_t* to;                      /* vertex 1, j */
+    double* measurement;              /* 8 each: Sji */
+    uint8_t* kind;
+} drfe_lmap_essential_edges_call;
+
+/* The tail.  The call names every stored key frame that is not bad once (one missing, or a named bad one: DRFE_ERR_STATE; an
+ * unknown or repeated handle: DRFE_ERR_INVALID) with the Scw the edges call returned and `optimised`, the estimates after the
+ * solver.
+ *
+ * Kept from the reference.  Per key frame vCorrectedSwc = optimised.inverse() and the pose toCvSE3(r.toRotationMatrix(), t * (1. /
+ * s)), Ow and Twc as SetPose derives them.  Then every stored point in slot order, bad ones skipped: nIDr = corrected_ref when
+ * corrected_by == cur_kf, else the reference key frame's handle; the new position is (float) vCorrectedSwc[nIDr].map(vScw[nIDr].map(
+ * (double) X)); an nIDr that is a stored key frame the call does not name goes through default-constructed Sim3s by the same
+ * arithmetic (which turns -0.0 into 0.0).  Then UpdateNormalAndDepth at the new position over the observations in stored order,
+ * every named observer at its new centre and every other at its stored one, ref_level and the scales as drfe_lmap_correct_* uses
+ * them; a point without observations still moves, with status 0.  The stamps are not changed.
+ *
+ * Refused with DRFE_ERR_STATE and the item's name, and nothing changes: a point that is not bad without geometry, with an unknown
+ * reference key frame, with an nIDr that is not a stored key frame (an out-of-range read in the reference), with ref_level out of
+ * range or no scales, and, when it has observations, an observer or reference key frame the call does not name that has no pose.
+ * DRFE_ERR_CAPACITY when points_capacity is too small.  On success the call commits poses and positions into the rows and, on the
+ * device, into the resident geometry block in place, with no upload of what it wrote. */
+typedef struct drfe_lmap_essential_commit_call {
+    int32_t cur_kf;
+    int32_t n;
+    const int32_t* handles;
+    const double* Scw;                /* n x 8 */
+    const double* optimised;          /* n x 8 */
+    int32_t points_capacity;          /* the number of stored points always suffices */
+    int32_t pad;
+    /* per named key frame, in the caller's order */
+    float* Tiw;                       /* 16 each: what SetPose received */
+    double* Swc;                      /* 8 each: vCorrectedSwc, for the caller's map lines and planes */
+    /* per moved point, in ascending slot (ascending handle) */
+    int32_t* n_points;                /* 1 */
+    int32_t* points;                  /* handles */
+    int32_t* ref;                     /* nIDr */
+    float* world;                     /* 3 each */
+    float* normal;                    /* 3 each */
+    float* max_distance;
+    float* min_distance;
+    uint8_t* status;                  /* DRFE_UPKEEP_NORMAL, or 0 for a point without observations */
+} drfe_lmap_essential_commit_call;
+
+/* stored key frames from which drfe_lmap_essential_edges_batch, and stored points from which drfe_lmap_essential_commit_batch, of
+ * a store with a context use the device: the measured crossovers (profiles/essential_timing.jsonl: the
+ * smallest measured shape from which the device entry wins at every mix, the setters that precede a call included).  INT32_MAX:
+ * the device entry won at no measured shape, _batch stays on the host.
+ * Measured host time over device time: edges 0.35x to 0.52x at 100, 0.66x to 0.82x at 1000, 1.01x to 2.01x at 4000 key frames;
+ * commit 1.72x to 1.93x at 12500, 2.18x to 2.51x at 125000, 2.02x to 2.27x at 500000 points. */
+enum { DRFE_LMAP_ESSENTIAL_EDGES_DEVICE_FROM = 2147483647, DRFE_LMAP_ESSENTIAL_COMMIT_DEVICE_FROM = 12500 };
+/* _host always runs on the host, _device always on the device (DRFE_ERR_STATE without a context; DRFE_ERR_CAPACITY when the call
+ * - an edges call as a whole, a commit call with one point slot a chunk - does not fit the configured scratch), _batch on the
+ * device from the crossover when the call fits.  All three return the same bytes and leave the same store. */
+int drfe_lmap_essential_edges_host(drfe_lmap* db, drfe_lmap_essential_edges_call* call);
+int drfe_lmap_essential_edges_device(drfe_lmap* db, drfe_lmap_essential_edges_call* call, void* stream);
+int drfe_lmap_essential_edges_batch(drfe_lmap* db, drfe_lmap_essential_edges_call* call, void* stream);
+int drfe_lmap_essential_commit_host(drfe_lmap* db, drfe_lmap_essential_commit_call* call);
+int drfe_lmap_essential_commit_device(drfe_lmap* db, drfe_lmap_essential_commit_call* call, void* stream);
+int drfe_lmap_essential_commit_batch(drfe_lmap* db, drfe_lmap_essential_commit_call* call, void* stream);
+/* out[0] threads of a workgroup = point slots of one, [1] lanes of a wavefront = ordered-row entries of one pass, [2]
+ * DRFE_LMAP_ESSENTIAL_EDGES_DEVICE_FROM, [3] DRFE_LMAP_ESSENTIAL_COMMIT_DEVICE_FROM, [4] bytes of scratch per point slot of a
+ * commit chunk, [5] per stored key frame of a commit call, [6] per edge of the bound of an edges call, [7] per stored key frame of
+ * an edges call */
+int drfe_lmap_essential_limits(int32_t* out8);
+/* the scratch the device calls take on the store as it is: out[0] bytes of an edges call with lc_entries loop-connection members
+ * (it runs as a whole), [1] the part of it that does not depend on the edges, [2] bytes with which a commit call runs as one chunk,
+ * [3] the least with which it runs at all (one point slot a chunk), [4] the part every chunk shares, [5] the edges of the bound */
+int drfe_lmap_essential_scratch(drfe_lmap* db, int32_t lc_entries, int64_t* out6);
+/* Counters since the store was created: stats[0] edges calls, [1] commit calls, [2] calls of either run on the device, [3]
+ * vertices, [4] edges, [5] points moved, [6] points moved through a default-constructed entry, [7] covisibility prefixes emptied
+ * by the end() rule. */
+int drfe_lmap_essential_stats(drfe_lmap* db, int64_t* stats /* 8 */);
+
 /* ------------------------------------------------------------------------------------------------ */
 /* measurement                                                                                       */
 /* DRFE_STAGE_FAST = the first FAST launch (k_fast_cells_cols<8>: the cells of at most 8 rows per lane - the four large levels at

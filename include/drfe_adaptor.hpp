@@ -3842,6 +3842,157 @@ public:
         return visited;
     }
 
+    /* What surrounds the solver of Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:2910-3131) on the store (DESIGN.md section
+     * 35).  Further accessor of KeyFrameT: GetLoopEdges().  Sim3T as for CorrectLoop. */
+    /* mspLoopEdges of pKF into the store: call it after AddLoopEdge */
+    void SyncLoopEdges(KeyFrameT* pKF)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const int32_t handle = (int32_t)pKF->mnId;
+        std::vector<int32_t> edges;
+        for (KeyFrameT* l : pKF->GetLoopEdges()) edges.push_back((int32_t)l->mnId);
+        const int32_t off[2] = {0, (int32_t)edges.size()};
+        Check(drfe_lmap_set_loop_edges(mDb, 1, &handle, off, edges.data()), "drfe_lmap_set_loop_edges");
+    }
+    /* the vertices in rank order and the edges in the order of the reference's addEdge: what the caller's solver is given */
+    template <class Sim3T>
+    struct EssentialGraph {
+        struct Vertex { KeyFrameT* pKF; Sim3T Scw; bool fixed; };
+        struct Edge { KeyFrameT* from; KeyFrameT* to; Sim3T Sji; int kind; };
+        std::vector<Vertex> vertices;
+        std::vector<Edge> edges;
+    };
+    /* Lines :2910-3080.  The store must hold the current rows, connections, loop edges and poses of every key frame of the map
+     * (Sync, SyncConnections, SyncLoopEdges, SyncGeometry; they are current after CorrectLoop and UpdateConnections above). */
+    template <class Sim3T>
+    EssentialGraph<Sim3T> EssentialEdges(KeyFrameT* pLoopKF, KeyFrameT* pCurKF, const std::map<KeyFrameT*, Sim3T>& NonCorrectedSim3,
+                                         const std::map<KeyFrameT*, Sim3T>& CorrectedSim3,
+                                         const std::map<KeyFrameT*, std::set<KeyFrameT*>>& LoopConnections)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        auto put = [](const Sim3T& S, double* v) {
+            const auto& q = S.rotation();
+            v[0] = q.x(); v[1] = q.y(); v[2] = q.z(); v[3] = q.w();
+            for (int k = 0; k < 3; k++) v[4 + k] = S.translation()[k];
+            v[7] = S.scale();
+        };
+        auto fill = [](Sim3T& S, const double* v) {
+            auto& r = S.rotation();
+            r.x() = v[0]; r.y() = v[1]; r.z() = v[2]; r.w() = v[3];
+            for (int k = 0; k < 3; k++) S.translation()[k] = v[4 + k];
+            S.scale() = v[7];
+        };
+        std::vector<int32_t> tab, lcH, lcOff(1, 0), lcKf;
+        std::vector<double> co, nc;
+        for (const auto& e : CorrectedSim3) {
+            const auto n = NonCorrectedSim3.find(e.first);
+            tab.push_back((int32_t)e.first->mnId);
+            co.resize(co.size() + 8);
+            nc.resize(nc.size() + 8);
+            put(e.second, &co[co.size() - 8]);
+            put(n == NonCorrectedSim3.end() ? e.second : n->second, &nc[nc.size() - 8]);
+        }
+        for (const auto& e : LoopConnections) {
+            lcH.push_back((int32_t)e.first->mnId);
+            for (KeyFrameT* m : e.second) lcKf.push_back((int32_t)m->mnId);
+            lcOff.push_back((int32_t)lcKf.size());
+        }
+        int64_t need[6] = {0, 0, 0, 0, 0, 0};
+        int32_t size[3] = {0, 0, 0};
+        Check(drfe_lmap_size(mDb, size), "drfe_lmap_size");
+        Check(drfe_lmap_essential_scratch(mDb, (int32_t)lcKf.size(), need), "drfe_lmap_essential_scratch");
+        const size_t capV = (size_t)size[0] + 1, capE = (size_t)need[5] + 1;
+        std::vector<int32_t> vert(capV), from(capE), to(capE);
+        std::vector<double> scw(8 * capV), meas(8 * capE);
+        std::vector<uint8_t> fixed(capV), kind(capE);
+        int32_t nV = 0, nE = 0;
+        drfe_lmap_essential_edges_call c = {};
+        c.loop_kf = (int32_t)pLoopKF->mnId; c.cur_kf = (int32_t)pCurKF->mnId;
+        c.n_sim3 = (int32_t)tab.size(); c.n_lc = (int32_t)lcH.size();
+        c.sim3_handles = tab.data(); c.corrected = co.data(); c.non_corrected = nc.data();
+        c.lc_handles = lcH.data(); c.lc_offsets = lcOff.data(); c.lc_kfs = lcKf.data();
+        c.vertices_capacity = (int32_t)capV; c.edges_capacity = (int32_t)capE;
+        c.n_vertices = &nV; c.vertices = vert.data(); c.Scw = scw.data(); c.fixed = fixed.data();
+        c.n_edges = &nE; c.from = from.data(); c.to = to.data(); c.measurement = meas.data(); c.kind = kind.data();
+        Check(mForce < 0 ? drfe_lmap_essential_edges_host(mDb, &c)
+            : mForce > 0 ? drfe_lmap_essential_edges_device(mDb, &c, nullptr) : drfe_lmap_essential_edges_batch(mDb, &c, nullptr),
+              "drfe_lmap_essential_edges");
+        EssentialGraph<Sim3T> G;
+        G.vertices.resize((size_t)nV);
+        G.edges.resize((size_t)nE);
+        for (int32_t v = 0; v < nV; v++) {
+            G.vertices[(size_t)v].pKF = mKFs.at(vert[(size_t)v]);
+            fill(G.vertices[(size_t)v].Scw, &scw[8 * (size_t)v]);
+            G.vertices[(size_t)v].fixed = fixed[(size_t)v] != 0;
+        }
+        for (int32_t e = 0; e < nE; e++) {
+            G.edges[(size_t)e].from = mKFs.at(from[(size_t)e]);
+            G.edges[(size_t)e].to = mKFs.at(to[(size_t)e]);
+            fill(G.edges[(size_t)e].Sji, &meas[8 * (size_t)e]);
+            G.edges[(size_t)e].kind = kind[(size_t)e];
+        }
+        return G;
+    }
+    /* Lines :3088-3131 for the graph EssentialEdges returned and the solver's estimates, one per vertex in the graph's order.
+     * The store must hold the current geometry of every map point (SyncGeometry).  Writes SetPose into every key frame in the
+     * graph's order, then SetWorldPos and the normal and distances into every moved point in ascending mnId (the reference walks
+     * set<MapPoint*>; no point reads another).  Map lines and planes stay with the caller: the returned vCorrectedSwc, with the
+     * graph's Scw, is what :3134-3204 read. */
+    template <class Sim3T>
+    std::map<KeyFrameT*, Sim3T> EssentialCommit(KeyFrameT* pCurKF, const EssentialGraph<Sim3T>& G, const std::vector<Sim3T>& optimised)
+    {
+        std::unique_lock<std::mutex> lock(mMutex);
+        const size_t n = G.vertices.size();
+        if (optimised.size() != n) throw std::runtime_error("EssentialCommit: one estimate per vertex");
+        std::vector<int32_t> handles(n);
+        std::vector<double> scw(8 * n + 8), opt(8 * n + 8), swc(8 * n + 8);
+        auto put = [](const Sim3T& S, double* v) {
+            const auto& q = S.rotation();
+            v[0] = q.x(); v[1] = q.y(); v[2] = q.z(); v[3] = q.w();
+            for (int k = 0; k < 3; k++) v[4 + k] = S.translation()[k];
+            v[7] = S.scale();
+        };
+        for (size_t v = 0; v < n; v++) {
+            handles[v] = (int32_t)G.vertices[v].pKF->mnId;
+            put(G.vertices[v].Scw, &scw[8 * v]);
+            put(optimised[v], &opt[8 * v]);
+        }
+        int32_t size[3] = {0, 0, 0};
+        Check(drfe_lmap_size(mDb, size), "drfe_lmap_size");
+        const size_t cap = (size_t)size[1] + 1;
+        std::vector<int32_t> points(cap), ref(cap);
+        std::vector<float> Tiw(16 * n + 16), world(3 * cap), normal(3 * cap), maxD(cap), minD(cap);
+        std::vector<uint8_t> status(cap);
+        int32_t nPoints = 0;
+        drfe_lmap_essential_commit_call c = {};
+        c.cur_kf = (int32_t)pCurKF->mnId; c.n = (int32_t)n;
+        c.handles = handles.data(); c.Scw = scw.data(); c.optimised = opt.data();
+        c.points_capacity = (int32_t)cap;
+        c.Tiw = Tiw.data(); c.Swc = swc.data(); c.n_points = &nPoints; c.points = points.data(); c.ref = ref.data();
+        c.world = world.data(); c.normal = normal.data(); c.max_distance = maxD.data(); c.min_distance = minD.data(); c.status = status.data();
+        Check(mForce < 0 ? drfe_lmap_essential_commit_host(mDb, &c)
+            : mForce > 0 ? drfe_lmap_essential_commit_device(mDb, &c, nullptr) : drfe_lmap_essential_commit_batch(mDb, &c, nullptr),
+              "drfe_lmap_essential_commit");
+        using ::drfe::drfe_detail_sim3::mat32;
+        std::map<KeyFrameT*, Sim3T> vCorrectedSwc;
+        for (size_t v = 0; v < n; v++) {
+            KeyFrameT* pKF = G.vertices[v].pKF;
+            Sim3T& S = vCorrectedSwc[pKF];
+            auto& r = S.rotation();
+            const double* w = &swc[8 * v];
+            r.x() = w[0]; r.y() = w[1]; r.z() = w[2]; r.w() = w[3];
+            for (int k = 0; k < 3; k++) S.translation()[k] = w[4 + k];
+            S.scale() = w[7];
+            pKF->SetPose(mat32(4, 4, &Tiw[16 * v]));
+        }
+        for (int32_t t = 0; t < nPoints; t++) {
+            MapPointT* pMP = mMPs.at(points[(size_t)t]);
+            pMP->SetWorldPos(mat32(3, 1, &world[3 * (size_t)t]));
+            if (status[(size_t)t] & DRFE_UPKEEP_NORMAL) pMP->SetNormalAndDepth(&normal[3 * (size_t)t], maxD[(size_t)t], minD[(size_t)t]);
+        }
+        return vCorrectedSwc;
+    }
+
     /* LocalMapping::KeyFrameCulling (src/LocalMapping.cc:1226-1285) with KeyFrame::SetBadFlag on the store.
      * Further accessors of KeyFrameT: the public mThDepth, mvKeysUn (.octave), mvDepth, mvuRight and mbNewPlane, SetBadFlag(), and
      * two getters that the integrator adds because mbNotErase and mbToBeErased are protected:
